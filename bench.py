@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X-native LceBconv2d hot path (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input: the LceBconv2d
 layer of BASELINE.json configs[1] -- 3x3, 256->256 channels, 56x56, SAME padding with
@@ -15,17 +15,23 @@ through.  The batch dimension is sharded: every rank runs its own 256 images, th
 collective; RCCL carries the barrier, the max-over-ranks of the elapsed time and the
 gather of the per-rank times.  `value` is whole-job binary MACs per second.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+A plain run sets up, warms up, times exactly K steps and prints the line; --dump-outputs DIR then also writes what
+the last timed step computed (DIR/output.npy, float32: the whole output when it is at most 32 MB, else the channel
+vectors of a fixed seeded sample of its pixels).  Rank 0 prints ONE JSON line.  Extra objects:
   roofline      dominant kernel: algorithmic bytes per launch / mean launch duration (HIP events on the
-                launch stream around the timed region; one launch per step) vs the 8 TB/s HBM peak;
+                launch stream around the timed region; one launch per step) vs the 8 TB/s HBM peak
+                (a step of two kernels: the whole step; with --full, runs of its GEMM phase alone);
   compute       the same kernel against the other roofline (FP4 MFMA peak, or the measured
                 v_xor+v_bcnt pair ceiling for the xor-popcount engine);
+Only with --full (each has runs of its own, none is part of `value`):
+  layer_latency_ms  the layer's mean step time in K steps of their own, the first measurement after a spin-up;
   extra         the other BASELINE configs: L0 with int8 / bitpacked output, the four QuickNet layer
                 shapes, QuickNet (16 layers), QuickNetLarge (32 layers, config 4's per-GPU shard) and the
                 Bi-RealNet-style int8 stack (12 layers, config 5) as REAL device-resident chains, the
                 streaming ops;
   cpu_baseline  the CPU oracle (a port of the reference's two portable C++ formulations) on the host
-                cores, on a bounded sample of the same workload (rank 0, N == 1 only).
+                cores, on a bounded sample of the same workload (rank 0, N == 1 only);
+  config4_quicknet_large_sharded   N > 1: every rank's shard of a QuickNetLarge batch as one chain.
 """
 from __future__ import annotations
 
@@ -108,20 +114,21 @@ class Rotation:
         self.x = [x] + [x.clone() for _ in range(self.n - 1)]
         self.out = [out] + [torch.empty_like(out) for _ in range(self.n - 1)]
         self.i = 0
+        self.last = 0
         self.total_bytes = per_set * self.n
 
     def run(self, plan):
         k = self.i
         self.i = (k + 1) % self.n
+        self.last = k
         plan.run(self.x[k], self.out[k])
 
     def describe(self):
         return "%d operand sets used round-robin, %.0f MB in total (> the 256 MB Infinity Cache)" % (self.n, self.total_bytes / 1e6)
 
 
-def time_layer(amd, torch, layer, dst, steps, warmup, seed, dev, scale=1.0, zp=0, engine="auto", rotate=False):
-    """Returns (mean seconds per step from stream events, kernel name, plan, x, out) -- with rotate=True a sixth element,
-    the Rotation whose buffer sets the timed launches cycled through.
+def setup_layer(amd, torch, layer, dst, seed, dev, scale=1.0, zp=0, engine="auto"):
+    """(plan, x, out) of one layer after the plan's first, untimed call (it selects the kernel and uploads the weights).
     Synthetic operands from tools/synthetic_layers.py -- the oracle is not involved."""
     w, mul, bias, thr = SL.weights(layer, seed)
     x = torch.from_numpy(SL.activations(layer, seed)).to(dev)
@@ -131,6 +138,13 @@ def time_layer(amd, torch, layer, dst, steps, warmup, seed, dev, scale=1.0, zp=0
     dt = {amd.F32: torch.float32, amd.I8: torch.int8, amd.BITPACKED: torch.int32}[dst]
     out = torch.empty(plan.output_shape, dtype=dt, device=dev)
     plan.run(x, out)
+    return plan, x, out
+
+
+def time_layer(amd, torch, layer, dst, steps, warmup, seed, dev, scale=1.0, zp=0, engine="auto", rotate=False):
+    """Returns (mean seconds per step from stream events, kernel name, plan, x, out) -- with rotate=True a sixth element,
+    the Rotation whose buffer sets the timed launches cycled through."""
+    plan, x, out = setup_layer(amd, torch, layer, dst, seed, dev, scale, zp, engine)
     rot = Rotation(torch, x, out) if rotate else None
     fn = (lambda: rot.run(plan)) if rotate else (lambda: plan.run(x, out))
     spin_up(torch, dev, fn)
@@ -225,6 +239,27 @@ def cpu_baseline(target_seconds=12.0, reps=5):
                       f"(min {min(all_dt):.2f}, max {max(all_dt):.2f}), {best_name}; {lib_note}",
             "repetitions": reps,
             "single_thread_one_image": {k: {"ms": v * 1e3, "bmac_per_s": one.binary_macs / v, "median_of": reps} for k, v in single.items()}}
+
+
+DUMP_WHOLE_BYTES = 32 << 20          # --dump-outputs: a larger output is written as a seeded sample of its pixels
+
+
+def dump_outputs(torch, directory, y, seed=0):
+    """--dump-outputs: DIR/output.npy, float32 -- `y` (N, H, W, C) whole when it fits DUMP_WHOLE_BYTES, else the C-channel
+    vectors of a sample of its pixels, sorted, drawn from a generator seeded with `seed` (the same pixels for the same shape,
+    so that two builds' files compare element for element).  Returns what the file holds."""
+    y = y.float()
+    flat = y.reshape(-1, y.shape[-1])
+    keep = DUMP_WHOLE_BYTES // (flat.shape[1] * 4)
+    if flat.shape[0] <= keep:
+        arr, what = y.cpu().numpy(), "the whole output"
+    else:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.shape[0], keep, replace=False))
+        arr = flat.index_select(0, torch.from_numpy(idx).to(y.device)).cpu().numpy()
+        what = f"{keep} of {flat.shape[0]} pixels (seeded sample), all {flat.shape[1]} channels"
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "output.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    return what
 
 
 def _free_port():
@@ -327,8 +362,14 @@ def main():
     ap.add_argument("--spinup-ms", type=float, default=40.0, help="untimed clock spin-up before the warmup steps")
     ap.add_argument("--one-operand-set", action="store_true",
                     help="time the headline on ONE input / output set (rounds 1-5) instead of a rotation of >= 4 sets")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, in runs of their own: layer_latency_ms, `extra`, "
+                         "`cpu_baseline`, the GEMM phase of a two-kernel step, and with N > 1 the sharded config-4 chain")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/output.npy (float32; a seeded sample "
+                         "of the pixels of an output over 32 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out `extra` and the config-4 chain")
     ap.add_argument("--extra-json", default=os.path.join(ROOT, "gpurun_out", "bench_extra.json"),
                     help="where the full `extra` entries go (the JSON line carries a compact map of them); '' = nowhere")
     ap.add_argument("--launch-selftest", action="store_true", help="CPU-only check of the multi-rank launch path (gloo)")
@@ -382,14 +423,21 @@ def main():
     global_batch = args.global_batch if strong else args.batch * world
     _, my_batch = shard.shard_range(global_batch, world, rank)
     spec = SL.Layer(batch=my_batch, padding=SL.PADDING_SAME, pad_values=1, **L0)
-    # warm up + per-step time from stream events (a step = every kernel of one LceBconv2d call)
-    step_sec, kname, plan, x, out, rot = time_layer(amd, torch, spec, amd.F32, args.steps, args.warmup, 0, dev, rotate=True)
+    plan, x, out = setup_layer(amd, torch, spec, amd.F32, 0, dev)
+    kname = plan.kernel_name()
     # The headline's launches cycle through >= 4 operand sets (3.4 GB) like every `extra` layer's (round-5 review: with ONE set the
     # 25.7 MB input of launch k + 1 is still in the 256 MB Infinity Cache from launch k -- 3 % of the bytes): every launch reads its
     # input from HBM.  `--one-operand-set` restores the round-5 loop; the line says which it was.
-    if args.one_operand_set:
-        rot = None
+    rot = None if args.one_operand_set else Rotation(torch, x, out)
     step = (lambda: plan.run(x, out)) if rot is None else (lambda: rot.run(plan))
+    layer_sec = None
+    if args.full:
+        # `layer_latency_ms`: the first measurement after a spin-up, K steps of its own before the timed region
+        spin_up(torch, dev, step)
+        for _ in range(max(1, args.warmup)):
+            step()
+        torch.cuda.synchronize(dev)
+        layer_sec = _event_time(torch, dev, step, args.steps)
 
     # the contract's timed region: barrier + sync, exactly K steps, sync + barrier, MAX over ranks
     def barrier():
@@ -406,8 +454,12 @@ def main():
     # same box, same binary).  A fixed stretch of the same layer brings every run, short or long, to the state a
     # serving process is in; the timed region below is still exactly W warmup + K timed steps.
     spin_launches = spin_up(torch, dev, step)
+    # (the process's first timing events cost the host tens of us: a pair around the warmup steps keeps that out of the timed region)
+    warm_evs = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    warm_evs[0].record()
     for _ in range(args.warmup):
         step()
+    warm_evs[1].record()
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     barrier()
     t0 = time.perf_counter()
@@ -423,12 +475,15 @@ def main():
     pct = lambda q: per_step_ms[min(len(per_step_ms) - 1, int(q * len(per_step_ms)))]
     elapsed = shard.max_over_ranks(elapsed_local, dist, cdev)
     per_rank = shard.gather_over_ranks(elapsed_local, dist, cdev)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(torch, args.dump_outputs, out if rot is None else rot.out[rot.last])
 
     # BASELINE config 4 at its size when N > 1 (never part of `value`): every rank runs ITS shard of a QuickNetLarge batch --
     # the 32 binary convolutions at batch 256 as one device-resident chain -- in the same barrier-bracketed way; the
     # global batch is 256 x N (2048 on 8 GPUs).  Every rank takes part in the barriers and the gather whatever happens to it.
     config4 = None
-    if dist is not None and not args.no_extra:
+    if dist is not None and args.full and not args.no_extra:
         chain4, local4 = None, float("nan")
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -484,7 +539,6 @@ def main():
                                "float32 output transform, device-resident bitpacked input",
                    "per_gpu_batch": my_batch if strong else args.batch, "global_batch": global_batch,
                    "parallelism": f"batch-shard x{world} (no data-path collective)"},
-        "layer_latency_ms": step_sec * 1e3,
         "clock_spin_up": {"ms": args.spinup_ms, "launches": spin_launches, "note": "untimed, before the W warmup steps"},
         # spread of the K timed steps (the chip's power management moves the clock during a run)
         "ms_per_step_p10_p50_p90": [pct(0.1), pct(0.5), pct(0.9)],
@@ -501,16 +555,21 @@ def main():
         result["multi_gpu_self_check"] = verified
     if config4 is not None:
         result["config4_quicknet_large_sharded"] = config4
+    if layer_sec is not None:
+        result["layer_latency_ms"] = layer_sec * 1e3
+    if dumped is not None:
+        result["outputs_dumped"] = {"file": "output.npy", "holds": dumped}
     if rank == 0:
         # dominant kernel alone (the GEMM of the matrix-core engine, or the single VALU kernel)
-        if mfma and not direct:
+        two_kernels = mfma and not direct and args.full     # (its GEMM phase alone takes runs of its own: --full)
+        if two_kernels:
             plan.set_option("phase", "gemm")
             k_sec = _event_time(torch, dev, lambda: plan.run(x, out), args.steps)
             plan.set_option("phase", "expand")
             e_sec = _event_time(torch, dev, lambda: plan.run(x, out), args.steps)
             plan.set_option("phase", "all")
         else:
-            # one kernel per step: its average duration IS the event time of the timed region / K
+            # one kernel per step: its average duration IS the event time of the timed region / K (else: the whole step)
             k_sec, e_sec = region_event_sec, 0.0
         ach = abytes / k_sec / 1e9
         traffic, traffic_src = None, None
@@ -530,8 +589,9 @@ def main():
                                            "one set; the 25.7 MB input of each launch is served by the Infinity Cache"),
                               "mfma_frac": 2.0 * spec.binary_macs / (MFMA_FP4_PEAK_TFLOPS * 1e12) / k_sec,
                               "kernel_ms": k_sec * 1e3, "expand_fp4_ms": e_sec * 1e3,
-                              "kernel_ms_source": ("phase=gemm re-run, HIP events" if mfma and not direct else
-                                                   "HIP events around the timed region / steps (one launch per step)"),
+                              "kernel_ms_source": ("phase=gemm re-run, HIP events" if two_kernels else
+                                                   "HIP events around the timed region / steps (one launch per step)" if direct else
+                                                   "HIP events around the timed region / steps (both kernels of a step; --full: GEMM alone)"),
                               "note": "HBM is the binding roofline of this layer at spec peaks (0.106 ms vs 0.095 ms of FP4 "
                                       "MFMA); the output stream alone needs 0.137 ms at the 6.0 TB/s this chip writes "
                                       "(tools/probes/store_overlap.hip); see `compute` for the other roofline"}
@@ -546,13 +606,13 @@ def main():
                                  "unit": "binary-MAC/s", "frac": spec.binary_macs / k_sec / VALU_BMAC_PEAK,
                                  "model": "v_xor_b32 + v_bcnt_u32_b32 per 32 bMAC, measured pair ceiling"}
         full_extra = None
-        if not args.no_extra and world == 1 and not one_rank_rccl:
+        if args.full and not args.no_extra and world == 1 and not one_rank_rccl:
             full_extra = extra_measurements(amd, torch, spec, args, dev)
             # The driver keeps the last 8 KB of stdout: the line carries a COMPACT map of every extra measurement (round 4's
             # 13 KB line lost five layers from the driver's record); the full entries (kernel names, operand rotation, chain
             # variants) go to a file beside it.
             result["extra"] = compact_extra(full_extra)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 result["cpu_baseline"] = cpu_baseline()
             except Exception as exc:   # noqa: BLE001  (the oracle library missing on the box: the GPU line still prints)

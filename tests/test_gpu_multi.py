@@ -168,10 +168,11 @@ def test_one_process_drives_one_plan_per_device():
         amd.check(amd.lib().lce_hip_set_device(0))
 
 
-def _bench(*flags, timeout=900, no_extra=True):
+def _bench(*flags, timeout=900, no_extra=True, plain=False):
+    """bench.py's one line; plain=True: without the --no-extra / --no-cpu-baseline opt-outs (which act with --full only)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2",
-                          *(["--no-extra"] if no_extra else []), "--no-cpu-baseline", *flags],
+    opt_outs = [] if plain else [*(["--no-extra"] if no_extra else []), "--no-cpu-baseline"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", *opt_outs, *flags],
                          env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
@@ -194,6 +195,38 @@ def test_bench_global_batch_is_strong_scaling():
     r = _bench("--global-batch", "64")
     assert r["scaling"] == "strong" and r["config"]["global_batch"] == 64 and r["config"]["per_gpu_batch"] == 64
     assert abs(r["value"] - 9 * 256 * 256 * 56 * 56 * 64 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+
+
+def _layer_on_the_oracle(batch):
+    """The float output of bench.py's layer on its own seeded operands (tools/synthetic_layers.py, seed 0), from the CPU oracle."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import oracle_lib as O
+    import synthetic_layers as SL
+    layer = SL.Layer(batch=batch, in_h=56, in_w=56, channels_in=256, filter_h=3, filter_w=3, channels_out=256,
+                     padding=SL.PADDING_SAME, pad_values=1)
+    w, mul, bias, _ = SL.weights(layer, 0)
+    spec = O.ConvSpec(batch=batch, in_h=56, in_w=56, channels_in=256, filter_h=3, filter_w=3, channels_out=256,
+                      padding=O.PADDING_SAME, pad_values=1)
+    return O.bconv2d(spec, O.DST_F32, SL.activations(layer, 0), w, mul, bias, threads=8)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run times exactly --steps steps and measures nothing beyond its headline (no `extra`, `cpu_baseline`: --full
+    has them); --dump-outputs writes the last timed step's float output, whole when it fits 32 MB, else the 32768 pixels a
+    generator seeded with 0 draws (all 256 channels) -- bit for bit the oracle's on the same seeded operands, so two builds'
+    files compare element for element."""
+    r = _bench("--steps", "7", "--warmup", "1", "--dump-outputs", str(tmp_path / "b256"), plain=True)
+    assert r["steps"] == 7 and "extra" not in r and "cpu_baseline" not in r and r["roofline"]["bound"] == "hbm"
+    got = np.load(tmp_path / "b256" / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (32768, 256) and got.nbytes <= 64 << 20
+    idx = np.sort(np.random.default_rng(0).choice(256 * 56 * 56, 32768, replace=False))
+    want = _layer_on_the_oracle(256).reshape(-1, 256)[idx]
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    r = _bench("--global-batch", "8", "--dump-outputs", str(tmp_path / "b8"), plain=True)
+    assert r["steps"] == 5 and r["outputs_dumped"]["holds"] == "the whole output"
+    got = np.load(tmp_path / "b8" / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (8, 56, 56, 256)
+    assert np.array_equal(got.view(np.int32), _layer_on_the_oracle(8).view(np.int32))
 
 
 @pytest.mark.skipif(NGPU < 2, reason="needs at least two GPUs")
@@ -220,7 +253,7 @@ def test_bench_collectives_against_the_real_rccl_with_one_rank():
     env["LCE_BENCH_RCCL_WITH_ONE_RANK"] = "1"
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline"],
+                          "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
@@ -244,7 +277,7 @@ def test_bench_multi_rank_path_with_two_ranks_sharing_one_gpu():
     """The N > 1 code path of bench.py -- self-launch through torch.distributed.run, shard ranges, barriers, max / gather over
     ranks, the config-4 chain every rank runs -- on a box with ONE GPU: --share-gpu puts both ranks on cuda:0 and lets them meet
     over gloo (a test aid, not a measurement; the RCCL variant is the test above)."""
-    r = _bench("--gpus", "2", "--share-gpu", no_extra=False, timeout=900)
+    r = _bench("--gpus", "2", "--share-gpu", "--full", no_extra=False, timeout=900)
     assert r["n_gpus"] == 2 and r["rccl_world_size"] == 2 and len(r["per_rank_ms_per_step"]) == 2
     assert r["collective_backend"].startswith("gloo") and r["config"]["global_batch"] == 512 and r["scaling"] == "weak"
     assert abs(r["value"] - 9 * 256 * 256 * 56 * 56 * 512 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
@@ -263,7 +296,7 @@ def test_eight_gpu_preflight_config4_as_stated_with_two_ranks_on_one_gpu():
     fields -- runs here end to end with two ranks that share GPU 0 over gloo (`--share-gpu`; 1024 images per rank).  What this cannot
     show is the xGMI transport; everything else of `python -m torch.distributed.run ... bench.py --gpus N --global-batch 2048` is the
     code that runs there."""
-    r = _bench("--gpus", "2", "--share-gpu", "--global-batch", "2048", "--steps", "3", no_extra=False, timeout=1200)
+    r = _bench("--gpus", "2", "--share-gpu", "--global-batch", "2048", "--steps", "3", "--full", no_extra=False, timeout=1200)
     assert r["n_gpus"] == 2 and r["rccl_world_size"] == 2 and r["steps"] == 3 and r["scaling"] == "strong"
     assert r["config"]["global_batch"] == 2048 and r["config"]["per_gpu_batch"] == 1024
     assert abs(r["value"] - 9 * 256 * 256 * 56 * 56 * 2048 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The round's rocprofv3 evidence in one GPU call:
 #   bash tools/gpu_profile_round.sh <tag>            (writes gpurun_out/<tag>/...)
-# 1. --kernel-trace --stats over the default bench.py command (the L0 headline + every `extra` line)
+# 1. --kernel-trace --stats over bench.py --full (the L0 headline + every `extra` line)
 # 2. --kernel-trace --stats per single layer named in bench.py's `extra` (one process per layer, so the
 #    per-kernel average IS that layer's launch duration)
 # 3. PMC passes (separate runs, counters only + kernel trace) over the L0 float layer
@@ -24,7 +24,7 @@ PY
 # 1 -------------------------------------------------------------------------------------------------
 if [[ $PARTS == *1* ]]; then
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o t -- \
-    python $R/bench.py --no-cpu-baseline > $OUT/bench/stdout.log 2> $OUT/bench/stderr.log
+    python $R/bench.py --full --no-cpu-baseline > $OUT/bench/stdout.log 2> $OUT/bench/stderr.log
 echo "bench rc=$?"
 tail -1 $OUT/bench/stdout.log > $OUT/bench_under_rocprof.json
 summ $OUT/bench/t_kernel_stats.csv | tee $OUT/bench_kernel_stats.txt

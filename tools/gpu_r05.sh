@@ -157,7 +157,7 @@ evidence)
   done
   fi
   if [[ $PARTS == *4* ]]; then
-  cd $R && timeout 900 python bench.py --extra-json $OUT/bench_extra.json > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
+  cd $R && timeout 900 python bench.py --full --extra-json $OUT/bench_extra.json > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
   timeout 600 python bench.py --spinup-ms 0 --no-extra --no-cpu-baseline > $OUT/bench_no_spinup.json 2> $OUT/bench_no_spinup.err
   timeout 900 python bench.py --measure-traffic --no-extra --no-cpu-baseline > $OUT/bench_measured_traffic.json 2> $OUT/bench_measured_traffic.err
   fi
@@ -173,7 +173,7 @@ stacks)
   for r in 1 2 3; do
     for v in "" 1; do
       if [ -z "$v" ]; then tag=with_wstream; unset LCE_PLAN_NO_WSTREAM; else tag=without_wstream; export LCE_PLAN_NO_WSTREAM=1; fi
-      python bench.py --no-cpu-baseline --extra-json "" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); e=d['extra']; print('$tag', 'L0 %.4f' % d['ms_per_step'], {k: e[k] for k in e if 'layers' in k or k.startswith('quicknet_1') or k.startswith('quicknet_7')})" | tee -a $OUT/stacks.txt
+      python bench.py --full --no-cpu-baseline --extra-json "" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); e=d['extra']; print('$tag', 'L0 %.4f' % d['ms_per_step'], {k: e[k] for k in e if 'layers' in k or k.startswith('quicknet_1') or k.startswith('quicknet_7')})" | tee -a $OUT/stacks.txt
     done
   done
   ;;
@@ -192,7 +192,7 @@ i8floor)
   for r in 1 2 3; do
     for v in "" 1; do
       if [ -z "$v" ]; then tag=floor; unset LCE_PLAN_INT8_EXACT; else tag=exact; export LCE_PLAN_INT8_EXACT=1; fi
-      python bench.py --no-cpu-baseline --extra-json "" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); e=d['extra']; print('$tag', 'L0 %.4f' % d['ms_per_step'], {k: e[k] for k in e if 'layers' in k or k.startswith('quicknet_1') or k.startswith('quicknet_7')})" | tee -a $OUT/stacks.txt
+      python bench.py --full --no-cpu-baseline --extra-json "" 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); e=d['extra']; print('$tag', 'L0 %.4f' % d['ms_per_step'], {k: e[k] for k in e if 'layers' in k or k.startswith('quicknet_1') or k.startswith('quicknet_7')})" | tee -a $OUT/stacks.txt
     done
   done
   ;;

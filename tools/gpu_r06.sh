@@ -3,7 +3,7 @@
 #   new      the round's new parity tests alone, timed
 #   tests    the whole -m gpu suite (what the driver runs at round end), timed
 #   smoke    __graft_entry__.smoke()
-#   bench    bench.py as the driver runs it (--steps 20 --warmup 5) -> gpurun_out/r06/bench_default_run.json (+ bench_extra.json)
+#   bench    bench.py --full --steps 20 --warmup 5 -> $OUT/bench_default_run.json (+ bench_extra.json)
 #   prof     rocprofv3 --kernel-trace --stats over the same command (no extras) -> gpurun_out/r06/prof
 OUT=gpurun_out/r06
 mkdir -p $OUT
@@ -14,7 +14,7 @@ for step in "$@"; do
     new)   ( time timeout 1500 python -m pytest tests/test_gpu_parity_r6.py -x -q --durations=8 ) > $OUT/pytest_new.log 2>&1; echo "rc=$?"; tail -25 $OUT/pytest_new.log ;;
     tests) ( time timeout 2400 python -m pytest tests -m gpu -x -q --durations=12 ) > $OUT/pytest_gpu.log 2>&1; echo "rc=$?"; tail -30 $OUT/pytest_gpu.log ;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "rc=$?"; tail -4 $OUT/smoke.log ;;
-    bench) ( time timeout 1200 python bench.py --steps 20 --warmup 5 --extra-json $OUT/bench_extra.json ) > $OUT/bench_default_run.json 2> $OUT/bench.err; echo "rc=$?"; wc -c $OUT/bench_default_run.json; cat $OUT/bench_default_run.json; tail -5 $OUT/bench.err ;;
+    bench) ( time timeout 1200 python bench.py --full --steps 20 --warmup 5 --extra-json $OUT/bench_extra.json ) > $OUT/bench_default_run.json 2> $OUT/bench.err; echo "rc=$?"; wc -c $OUT/bench_default_run.json; cat $OUT/bench_default_run.json; tail -5 $OUT/bench.err ;;
     bench1) ( time timeout 600 python bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline --one-operand-set ) > $OUT/bench_one_operand_set.json 2>> $OUT/bench.err; cat $OUT/bench_one_operand_set.json ;;
     sweep) ( time timeout 2400 python tools/planner_regret.py --remeasure $OUT/engine_sweep_r06_box${BOX:-1}.jsonl ) > $OUT/planner_regret_box${BOX:-1}.txt 2>&1; echo "rc=$?"; tail -15 $OUT/planner_regret_box${BOX:-1}.txt ;;
     abl)   # single-round float layers: what each part of the weight-stationary kernel costs (ablation builds of tools/build_abl.sh; the

@@ -13,7 +13,7 @@ timeout 1500 python -m pytest tests -m gpu --maxfail=15 -q > $OUT/pytest_gpu.log
 echo "== valu peak"
 timeout 120 ./tools/valu_peak > $OUT/valu_peak.jsonl 2>&1; cat $OUT/valu_peak.jsonl
 echo "== bench"
-timeout 900 python bench.py --steps 50 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -3 $OUT/bench.err
+timeout 900 python bench.py --full --steps 50 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cat $OUT/bench.json; tail -3 $OUT/bench.err
 echo "== sweep"
 timeout 900 python tools/sweep.py > $OUT/sweep.jsonl 2> $OUT/sweep.err; echo "sweep rc=$?"; cat $OUT/sweep.jsonl | head -80; tail -3 $OUT/sweep.err
 echo "== rocprof kernel trace"

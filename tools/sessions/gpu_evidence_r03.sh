@@ -23,7 +23,7 @@ if [ -f $R/build_exp/lib_sph.so ]; then
   done
 fi
 ( echo "== AGPR accumulators (the empty-asm pin forces copies: ignore)"; timeout 200 $R/tools/probes/mfma_gap_a; echo "== VGPR accumulators (-amdgpu-mfma-vgpr-form), as the streaming kernel is built"; timeout 200 $R/tools/probes/mfma_gap_v ) > $OUT/probe_mfma_gap.txt 2>&1
-cd $R && timeout 900 python bench.py > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
+cd $R && timeout 900 python bench.py --full > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
 # the same command without the untimed clock spin-up (README: its share of the headline) and with the traffic measured in the run
 timeout 600 python bench.py --spinup-ms 0 --no-extra --no-cpu-baseline > $OUT/bench_no_spinup.json 2> $OUT/bench_no_spinup.err
 timeout 900 python bench.py --measure-traffic --no-extra --no-cpu-baseline > $OUT/bench_measured_traffic.json 2> $OUT/bench_measured_traffic.err

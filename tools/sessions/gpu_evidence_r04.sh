@@ -45,7 +45,7 @@ for spec in "pmc_l0_f32 3 56 256 f32 256" "pmc_7x512_f32 3 7 512 f32 256" "pmc_7
 done
 fi
 if [[ $PARTS == *4* ]]; then
-cd $R && timeout 900 python bench.py > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
+cd $R && timeout 900 python bench.py --full > $OUT/bench_default_run.json 2> $OUT/bench_default_run.err
 timeout 600 python bench.py --spinup-ms 0 --no-extra --no-cpu-baseline > $OUT/bench_no_spinup.json 2> $OUT/bench_no_spinup.err
 timeout 900 python bench.py --measure-traffic --no-extra --no-cpu-baseline > $OUT/bench_measured_traffic.json 2> $OUT/bench_measured_traffic.err
 fi

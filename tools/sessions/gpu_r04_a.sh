@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 echo "== smoke"; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -3 $OUT/smoke.log
 echo "== pytest -m gpu"; ( time timeout 1500 python -m pytest tests -m gpu --maxfail=20 -q -x ) > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -15 $OUT/pytest_gpu.log
-echo "== bench"; ( time timeout 900 python bench.py --steps 20 --warmup 5 ) > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+echo "== bench"; ( time timeout 900 python bench.py --full --steps 20 --warmup 5 ) > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
 LCE_TAG=$TAG python - <<'PY'
 import json,sys
 try:
