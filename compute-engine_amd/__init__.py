@@ -36,7 +36,7 @@ ABI_SYMBOLS = (
     "lce_hip_host_register", "lce_hip_host_unregister",
     "lce_hip_stream_create", "lce_hip_stream_destroy", "lce_hip_stream_synchronize",
     "lce_hip_graph_begin_capture", "lce_hip_graph_end_capture", "lce_hip_graph_launch", "lce_hip_graph_destroy",
-    "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack",
+    "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -45,6 +45,9 @@ ABI_SYMBOLS = (
     "lce_hip_prepare_bitpacked_output", "lce_hip_prepare_bitpack_filter",
 )
 POST_ADD, POST_SUB, POST_MUL, POST_DIV = 0, 1, 2, 3
+EW_ADD, EW_MUL = 0, 1                                   # lce_hip_ew_op
+EW_SCALAR, EW_PER_CHANNEL, EW_TENSOR = 0, 1, 2          # lce_hip_ew_operand
+EW_MAX_STEPS = 8
 
 
 class LceHipError(RuntimeError):
@@ -61,6 +64,12 @@ class Bconv2dDesc(C.Structure):
         "channels_out", "groups", "stride_height", "stride_width", "dilation_height",
         "dilation_width", "padding", "pad_values", "activation", "dst_type", "semantics")] + [
         ("out_scale", C.c_float), ("out_zero_point", C.c_int32)]
+
+
+class EwStep(C.Structure):
+    """``lce_hip_ew_step``."""
+    _fields_ = [("op", C.c_int32), ("operand", C.c_int32), ("values", C.c_void_p), ("scalar", C.c_float),
+                ("activation", C.c_int32)]
 
 
 _lib = None
@@ -101,6 +110,8 @@ def lib() -> C.CDLL:
                                       C.c_void_p, C.c_void_p]
         l.lce_hip_unpack.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float,
                                      C.c_int32, C.c_void_p, C.c_void_p]
+        l.lce_hip_elementwise.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(EwStep), C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -356,6 +367,105 @@ def unpack(words, channels: int, dtype, scale: float = 1.0, zero_point: int = 0,
         check(lib().lce_hip_unpack(t, C.c_void_p(words.data_ptr()), rows, channels, float(scale),
                                    int(zero_point), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
     return out
+
+
+def _ew_check(x, steps, out, out_bits):
+    """Argument checks of ``elementwise`` on shapes and dtypes only (NumPy or torch): nothing here touches a device."""
+    def dtype_name(a):
+        return str(a.dtype).replace("torch.", "")
+    shape = tuple(x.shape)
+    if dtype_name(x) != "float32" or len(shape) < 1:
+        raise ValueError("elementwise: x must be a float32 tensor with a channel axis, got %s %r" % (x.dtype, shape))
+    channels = shape[-1]
+    if not isinstance(steps, (list, tuple)) or not 1 <= len(steps) <= EW_MAX_STEPS:
+        raise ValueError("elementwise: 1..%d steps, got %r" % (EW_MAX_STEPS, steps))
+    kinds = []
+    for k, step in enumerate(steps):
+        if not isinstance(step, (list, tuple)) or len(step) != 3:
+            raise ValueError("elementwise: step %d must be (op, operand, activation), got %r" % (k, step))
+        op, operand, act = step
+        if op not in (EW_ADD, EW_MUL, "add", "mul"):
+            raise ValueError("elementwise: step %d: unknown op %r" % (k, op))
+        if act not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
+            raise ValueError("elementwise: step %d: unknown activation %r" % (k, act))
+        if operand is None:
+            raise ValueError("elementwise: step %d: no operand" % k)
+        if isinstance(operand, (int, float, np.floating, np.integer)):
+            kinds.append(EW_SCALAR)
+            continue
+        oshape = tuple(operand.shape)
+        if dtype_name(operand) != "float32":
+            raise ValueError("elementwise: step %d: operand must be float32, got %s" % (k, operand.dtype))
+        if oshape == shape:
+            kinds.append(EW_TENSOR)
+        elif oshape == (channels,):
+            kinds.append(EW_PER_CHANNEL)
+        else:
+            raise ValueError("elementwise: step %d: operand shape %r is neither x's %r nor [channels] (%d,)" % (k, oshape, shape, channels))
+    if out is False and out_bits is None:
+        raise ValueError("elementwise: no output requested")
+    if out is not None and out is not False:
+        if tuple(out.shape) != shape or dtype_name(out) != "float32":
+            raise ValueError("elementwise: out must be float32 of shape %r, got %s %r" % (shape, out.dtype, tuple(out.shape)))
+    if out_bits is not None and out_bits is not True:
+        want = shape[:-1] + (bitpacked_size(channels),)
+        if tuple(out_bits.shape) != want or dtype_name(out_bits) != "int32":
+            raise ValueError("elementwise: out_bits must be int32 of shape %r, got %s %r" % (want, out_bits.dtype, tuple(out_bits.shape)))
+    return kinds
+
+
+def elementwise(x, steps, out=None, out_bits=None, stream: int | None = None):
+    """TFLite's float ADD / MUL chain between binary layers and the LceQuantize of its result, in one pass
+    (``lce_hip_elementwise``).  ``x``: float32 [..., C] on the device (or NumPy: copied to cuda:0 and back).  ``steps``: up to 8
+    ``(op, operand, activation)`` -- op ``EW_ADD`` / ``EW_MUL`` (or "add" / "mul"), operand a Python float (scalar), a [C]
+    tensor (per channel) or a tensor of x's shape, activation ``ACT_*``.  ``out``: a float32 tensor to fill (may be ``x`` or a
+    tensor operand), None for a new one, False for none.  ``out_bits``: an int32 [..., ceil(C/32)] tensor to fill, True for a
+    new one, None for none.  Returns ``(out, out_bits)`` with None for an output not asked for."""
+    kinds = _ew_check(x, steps, out, out_bits)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+
+    def on_dev(a):
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
+        if not (t.is_cuda and t.device == dev and t.is_contiguous()):
+            raise ValueError("elementwise: tensors must be contiguous and on x's device %s" % dev)
+        return t
+
+    xd = on_dev(x)
+    operands = [None if k == EW_SCALAR else on_dev(step[1]) for k, step in zip(kinds, steps)]
+    channels = x.shape[-1]
+    rows = xd.numel() // channels if channels else 0
+    out_d = None if out is False else torch.empty_like(xd) if out is None else on_dev(out)
+    bits_d = None
+    if out_bits is True:
+        bits_d = torch.empty(tuple(xd.shape[:-1]) + (bitpacked_size(channels),), dtype=torch.int32, device=dev)
+    elif out_bits is not None:
+        bits_d = on_dev(out_bits)
+    arr = (EwStep * len(steps))()
+    for k, ((op, operand, act), kind, t) in enumerate(zip(steps, kinds, operands)):
+        arr[k].op = {EW_ADD: EW_ADD, EW_MUL: EW_MUL, "add": EW_ADD, "mul": EW_MUL}[op]
+        arr[k].operand = kind
+        arr[k].values = None if t is None else t.data_ptr()
+        arr[k].scalar = float(operand) if kind == EW_SCALAR else 0.0
+        arr[k].activation = int(act)
+    with torch.cuda.device(dev):
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().lce_hip_elementwise(C.c_void_p(xd.data_ptr()), rows, channels, arr, len(steps),
+                                        C.c_void_p(None if out_d is None else out_d.data_ptr()),
+                                        C.c_void_p(None if bits_d is None else bits_d.data_ptr()), C.c_void_p(stream)))
+    if host:
+        ret_out = None if out_d is None else out_d.cpu().numpy()
+        if isinstance(out, np.ndarray) and ret_out is not None:
+            out[...] = ret_out
+            ret_out = out
+        ret_bits = None if bits_d is None else bits_d.cpu().numpy()
+        if isinstance(out_bits, np.ndarray) and ret_bits is not None:
+            out_bits[...] = ret_bits
+            ret_bits = out_bits
+        return ret_out, ret_bits
+    return out_d, bits_d
 
 
 def bmaxpool(x, filter_height, filter_width, stride_height, stride_width, padding, stream: int | None = None, out=None):

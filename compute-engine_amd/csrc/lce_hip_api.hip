@@ -2,6 +2,7 @@
 // There is no CPU fallback in this file: every compute entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include "../../include/lce_hip.h"
 #include "lce_kernels.h"          // the LceQuantize / LceDequantize / LceBMaxPool2d kernels are launched from here
 #include "lce_kernel_types.h"    // the convolution kernels live in their own translation units (lce_tu_*.hip)
+#include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -29,6 +31,7 @@
 #include "lce_tu_wstream_i8.hip"
 #include "lce_tu_wstream_i8_floor.hip"
 #include "lce_tu_wstream_bitpacked.hip"
+#include "lce_tu_eltwise.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -453,6 +456,58 @@ lce_hip_status lce_hip_unpack(lce_hip_dtype out_type, const int32_t* in_dev, siz
     else lce::unpack_rows<uint8_t><<<grid, 256, 0, st>>>((const uint32_t*)in_dev, (uint8_t*)out_dev, total, (uint32_t)cols, wpr, (uint8_t)1, (uint8_t)0);
   }
   LCE_HIP_TRY(hipGetLastError());
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Float ADD / MUL chains (lce_kernels_eltwise.h)
+// ------------------------------------------------------------------------------------
+lce_hip_status lce_hip_elementwise(const float* in_dev, size_t rows, size_t channels, const lce_hip_ew_step* steps,
+                                   int32_t num_steps, float* out_dev, int32_t* out_bits_dev, void* stream) {
+  if (num_steps < 1 || num_steps > lce::kEwMaxSteps)
+    return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: num_steps must be 1..%d, got %d", lce::kEwMaxSteps, (int)num_steps);
+  if (!steps) return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: null steps");
+  if (channels >= (1ull << 31)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: channels must be below 2^31");
+  lce::EwArgs a;
+  memset(&a, 0, sizeof a);
+  bool aligned = ((uintptr_t)in_dev % 16 == 0) && ((uintptr_t)out_dev % 16 == 0) && ((uintptr_t)out_bits_dev % 16 == 0);
+  for (int32_t s = 0; s < num_steps; ++s) {
+    const lce_hip_ew_step& st = steps[s];
+    lce::EwStep& k = a.steps[s];
+    if (st.op != LCE_HIP_EW_ADD && st.op != LCE_HIP_EW_MUL)
+      return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: unknown op %d", (int)s, (int)st.op);
+    if (st.operand != LCE_HIP_EW_SCALAR && st.operand != LCE_HIP_EW_PER_CHANNEL && st.operand != LCE_HIP_EW_TENSOR)
+      return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: unknown operand kind %d", (int)s, (int)st.operand);
+    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
+    switch (st.activation) {
+      case LCE_HIP_ACT_NONE: k.lo = -FLT_MAX; k.hi = FLT_MAX; break;
+      case LCE_HIP_ACT_RELU: k.lo = 0.0f; k.hi = FLT_MAX; break;
+      case LCE_HIP_ACT_RELU_N1_TO_1: k.lo = -1.0f; k.hi = 1.0f; break;
+      case LCE_HIP_ACT_RELU6: k.lo = 0.0f; k.hi = 6.0f; break;
+      default: return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: unknown activation %d", (int)s, (int)st.activation);
+    }
+    k.op = st.op;
+    k.operand = st.operand;
+    k.values = st.operand == LCE_HIP_EW_SCALAR ? nullptr : st.values;
+    k.scalar = st.scalar;
+    if (k.values && (uintptr_t)k.values % 16 != 0) aligned = false;
+  }
+  if (rows == 0 || channels == 0) return LCE_HIP_OK;   // (an empty tensor may come with null pointers)
+  for (int32_t s = 0; s < num_steps; ++s)
+    if (steps[s].operand != LCE_HIP_EW_SCALAR && !steps[s].values)
+      return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: null operand", (int)s);
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: both outputs are null");
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: null input");
+  if (lce_hip_status s = require_device()) return s;
+  a.in = in_dev;
+  a.out = out_dev;
+  a.bits = (uint32_t*)out_bits_dev;
+  a.rows = rows;
+  a.channels = (uint32_t)channels;
+  a.wpr = (uint32_t)((channels + 31) / 32);
+  a.num_steps = num_steps;
+  const int e = lce::launch_eltwise(a, channels % 32 == 0 && aligned, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_elementwise: launch failed: %s", hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
 

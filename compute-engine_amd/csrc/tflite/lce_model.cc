@@ -21,7 +21,10 @@ struct lce_tflite_section {
 };
 struct lce_tflite_model {
   lce_tfl::Model m;
+  uint32_t flags = 0;                         // lce_tflite_model_open_ex
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
+  std::vector<char> absorbed;                 // per operator: a builtin ADD / MUL that runs inside a section
+  std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
   void Partition();
   // ---- state of lce_tflite_model_run_section (one run at a time per model) ----
   std::mutex run_mu;
@@ -29,6 +32,9 @@ struct lce_tflite_model {
   struct DevBuf { void* ptr = nullptr; size_t bytes = 0; };
   std::map<int32_t, DevBuf> scratch;                                    // intermediate tensors of a section, grow-only
   int32_t last_run_fused = 0;                                           // LceQuantize launches the last run folded into a convolution
+  std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
+  struct EwStats { int32_t launches = 0, ops = 0, quantize = 0; };
+  EwStats last_ew;                                                      // lce_hip_elementwise launches of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
   // stream, tensor pointers) and replayed as one launch.  The first call with a key runs eagerly (plans are made, weights
   // uploaded, intermediate buffers sized), the second records, later ones replay.  Recorded launches hold the model's
@@ -41,7 +47,7 @@ struct lce_tflite_model {
       return std::tie(section, batch, semantics, stream, ptrs) < std::tie(o.section, o.batch, o.semantics, o.stream, o.ptrs);
     }
   };
-  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; int32_t fused = 0; };
+  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; int32_t fused = 0; EwStats ew; };
   std::map<GraphKey, GraphEntry> graphs;
   bool use_graphs = false;
   int32_t graph_captures = 0, graph_replays = 0;
@@ -53,6 +59,7 @@ struct lce_tflite_model {
     DropGraphs();
     for (auto& kv : plans) lce_hip_bconv2d_plan_destroy(kv.second);
     for (auto& kv : scratch) if (kv.second.ptr) lce_hip_free(kv.second.ptr);
+    for (auto& kv : consts) if (kv.second.ptr) lce_hip_free(kv.second.ptr);
   }
 };
 
@@ -60,6 +67,42 @@ namespace {
 bool IsLceOp(const lce_tfl::Operator& o) {
   return o.builtin_code == 32 && (o.custom_code == "LceBconv2d" || o.custom_code == "LceQuantize" ||
                                   o.custom_code == "LceDequantize" || o.custom_code == "LceBMaxPool2d");
+}
+
+// Element count of a constant ADD / MUL operand that broadcasts over the last axis: [C] / [1,1,1,C] -> C, [1] / [] -> 1;
+// -1 for any other shape.
+int64_t BroadcastCount(const lce_tfl::Tensor& t) {
+  const std::vector<int32_t>& s = t.shape;
+  if (s.empty()) return 1;
+  if (s.size() == 1) return s[0];
+  if (s.size() == 4 && s[0] == 1 && s[1] == 1 && s[2] == 1) return s[3];
+  return -1;
+}
+
+// The static half of "a builtin ADD / MUL that a section may run" (LCE_TFLITE_SECTIONS_ELEMENTWISE): float32 in and out, a
+// 4-D output, each input either a non-constant tensor of the output's shape (batch ignored) or a constant of shape [C],
+// [1,1,1,C], [1] or [], and an activation lce_hip_elementwise knows.  The other half -- one of its non-constant inputs is
+// produced in the same epoch -- is decided by Partition().
+bool ElementwiseCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinAdd && o.builtin_code != lce_tfl::kBuiltinMul) return false;
+  if (o.inputs.size() != 2 || o.outputs.size() != 1) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (out.type != lce_tfl::kTensorFloat32 || out.shape.size() != 4 || out.shape[3] <= 0) return false;
+  int variable = 0;
+  for (int32_t t : o.inputs) {
+    if (t < 0) return false;
+    const lce_tfl::Tensor& in = M.tensors[t];
+    if (in.type != lce_tfl::kTensorFloat32) return false;
+    if (in.data) {
+      const int64_t n = BroadcastCount(in);
+      if ((n != 1 && n != out.shape[3]) || in.bytes != (size_t)n * 4) return false;
+    } else {
+      if (in.shape.size() != 4 || in.shape[1] != out.shape[1] || in.shape[2] != out.shape[2] || in.shape[3] != out.shape[3]) return false;
+      ++variable;
+    }
+  }
+  return variable > 0;
 }
 }  // namespace
 
@@ -73,11 +116,16 @@ bool IsLceOp(const lce_tfl::Operator& o) {
 void lce_tflite_model::Partition() {
   const int n_ops = (int)m.operators.size(), n_t = (int)m.tensors.size();
   auto valid = [&](int32_t t) { return t >= 0 && t < n_t; };
-  std::vector<char> produced(n_t, 0), is_output(n_t, 0), is_lce(n_ops, 0);
-  std::vector<std::vector<int32_t>> readers(n_t);
+  std::vector<char> produced(n_t, 0), is_output(n_t, 0), is_lce(n_ops, 0), candidate(n_ops, 0);
+  readers.assign(n_t, {});
+  absorbed.assign(n_ops, 0);
   std::vector<int32_t> unready(n_ops, 0);
   for (int i = 0; i < n_ops; ++i) {
     is_lce[i] = IsLceOp(m.operators[i]) ? 1 : 0;
+    // LCE_TFLITE_SECTIONS_ELEMENTWISE: a float ADD / MUL joins the epoch in which it becomes ready, so it lands in a section
+    // exactly when the last of its inputs was produced by an LCE epoch (one that is ready from the start -- a stem op -- is
+    // a builtin one)
+    if (flags & LCE_TFLITE_SECTIONS_ELEMENTWISE) candidate[i] = ElementwiseCandidate(m, m.operators[i]) ? 1 : 0;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -92,7 +140,7 @@ void lce_tflite_model::Partition() {
   // ready operators of either kind, waiting for their epoch
   std::vector<int32_t> queue[2];
   for (int i = 0; i < n_ops; ++i)
-    if (unready[i] == 0) queue[(int)is_lce[i]].push_back(i);
+    if (unready[i] == 0) queue[(int)is_lce[i]].push_back(i);   // (a candidate ready from the start is a builtin op)
   std::vector<int32_t> section_of(n_ops, -1);
   std::vector<char> made(n_t, 0), listed(n_t, 0);
   int remaining = n_ops;
@@ -111,11 +159,12 @@ void lce_tflite_model::Partition() {
       any = true;
       --remaining;
       if (kind) sec.ops.push_back(i);
+      if (kind && candidate[i]) absorbed[i] = 1;
       for (int32_t t : m.operators[i].outputs) {
         if (!valid(t) || made[t]) continue;
         made[t] = 1;
         for (int32_t r : readers[t])
-          if (--unready[r] == 0) queue[(int)is_lce[r]].push_back(r);
+          if (--unready[r] == 0) queue[candidate[r] ? kind : (int)is_lce[r]].push_back(r);
       }
     }
     q.clear();
@@ -161,9 +210,16 @@ lce_hip_status Fail(lce_hip_status code, const std::string& msg) {
 extern "C" {
 
 lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err, size_t err_len) {
+  return lce_tflite_model_open_ex(data, size, 0u, err, err_len);
+}
+
+lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len) {
   auto* model = new (std::nothrow) lce_tflite_model{};
   std::string e = "out of memory";
-  if (model && data && model->m.Parse(data, size, &e)) {
+  if (flags & ~(uint32_t)LCE_TFLITE_SECTIONS_ELEMENTWISE) {
+    e = "unknown flags";
+  } else if (model && data && model->m.Parse(data, size, &e)) {
+    model->flags = flags;
     model->Partition();
     return model;
   }
@@ -219,6 +275,13 @@ lce_hip_status lce_tflite_model_operator(const lce_tflite_model* model, int32_t 
   info->num_outputs = (int32_t)o.outputs.size();
   info->custom_options = o.custom_options;
   info->custom_options_size = o.custom_options_size;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_tflite_model_operator_activation(const lce_tflite_model* model, int32_t index, int32_t* activation) {
+  if (!model || !activation || index < 0 || index >= (int32_t)model->m.operators.size())
+    return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_activation: bad argument");
+  *activation = model->m.operators[index].activation;
   return LCE_HIP_OK;
 }
 
@@ -394,6 +457,137 @@ std::vector<int32_t> QuantizeConsumers(const lce_tflite_model* model, const lce_
   return js;
 }
 
+// Device copy of a constant ADD / MUL operand, uploaded on `stream` by the first run that needs it (never while a graph is
+// being recorded: the eager run before a recording has made every one).
+lce_hip_status ConstOnDevice(lce_tflite_model* model, int32_t t, void* stream, bool capturing, const float** out) {
+  lce_tflite_model::DevBuf& b = model->consts[t];
+  if (!b.ptr) {
+    if (capturing) return Fail(LCE_HIP_ERR_INVALID, "run_section: a constant would have to be uploaded during graph capture");
+    const lce_tfl::Tensor& T = model->m.tensors[t];
+    if (lce_hip_status s = lce_hip_malloc(&b.ptr, T.bytes)) return s;
+    b.bytes = T.bytes;
+    if (lce_hip_status s = lce_hip_memcpy_h2d(b.ptr, T.data, T.bytes, stream)) return s;
+  }
+  *out = (const float*)b.ptr;
+  return LCE_HIP_OK;
+}
+
+// A maximal chain of absorbed ADD / MUL operators that starts at operator `first`, as ONE lce_hip_elementwise launch.  The
+// chain streams a float tensor x (an input of `first`: an LceBconv2d output or a section input) and extends through an
+// operator whose input tensor has exactly one reader and is not a section output (up to 8 steps); the other input of each
+// operator is the step's operand (a constant: scalar or per channel; otherwise a tensor of x's shape).  The chain's last
+// tensor is written in float when anything but a folded LceQuantize reads it or the section delivers it; the first
+// LceQuantize of the section that reads it becomes the launch's bit output and its own launch disappears.
+template <typename BufferFor>
+lce_hip_status WalkElementwiseChain(lce_tflite_model* model, const lce_tflite_section& sec, int32_t first, int32_t batch,
+                                    std::map<int32_t, Shape>* shapes, std::map<int32_t, void*>* ptr, bool run, void* stream,
+                                    bool capturing, BufferFor& buffer_for, std::vector<char>* done) {
+  const lce_tfl::Model& M = model->m;
+  auto is_section_output = [&](int32_t t) { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); };
+  const lce_tfl::Operator& op0 = M.operators[first];
+  const int32_t x_t = M.tensors[op0.inputs[0]].data ? op0.inputs[1] : op0.inputs[0];
+  auto x_it = shapes->find(x_t);
+  if (x_it == shapes->end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
+  const Shape xs = x_it->second;
+  const std::vector<int32_t>& fs = M.tensors[op0.outputs[0]].shape;
+  // the file's shapes were checked by the partition; the walk's inferred shape must agree with them (untrusted input)
+  if (xs.type != lce_tfl::kTensorFloat32 || xs.dims[0] != batch || xs.dims[1] != fs[1] || xs.dims[2] != fs[2] || xs.dims[3] != fs[3])
+    return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL input's shape does not match the one its producer infers");
+  const size_t rows = (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2], channels = (size_t)xs.dims[3];
+
+  std::vector<lce_hip_ew_step> steps;
+  std::vector<int32_t> chain;
+  int32_t cur = first, v_t = x_t;
+  // the operand of operator `o` whose streamed input is `v`; false when it is not available yet (produced further down)
+  auto operand_of = [&](const lce_tfl::Operator& o, int32_t v, lce_hip_ew_step* st) -> lce_hip_status {
+    const int32_t other = (o.inputs[0] == v) ? o.inputs[1] : o.inputs[0];
+    const lce_tfl::Tensor& T = M.tensors[other];
+    memset(st, 0, sizeof *st);
+    st->op = o.builtin_code == lce_tfl::kBuiltinMul ? LCE_HIP_EW_MUL : LCE_HIP_EW_ADD;
+    st->activation = o.activation;
+    if (T.data) {
+      if (T.bytes == 4) {
+        st->operand = LCE_HIP_EW_SCALAR;
+        memcpy(&st->scalar, T.data, 4);
+      } else {
+        st->operand = LCE_HIP_EW_PER_CHANNEL;
+        if (T.bytes != channels * 4) return Fail(LCE_HIP_ERR_INVALID, "run_section: a per-channel constant does not match the channels");
+        if (run) {
+          const float* d = nullptr;
+          if (lce_hip_status s = ConstOnDevice(model, other, stream, capturing, &d)) return s;
+          st->values = d;
+        }
+      }
+      return LCE_HIP_OK;
+    }
+    auto it = shapes->find(other);
+    if (it == shapes->end()) return LCE_HIP_ERR_UNSUPPORTED;        // (not an error: the chain stops before `o`)
+    const Shape& os = it->second;
+    if (os.type != lce_tfl::kTensorFloat32 || memcmp(os.dims, xs.dims, sizeof xs.dims) != 0)
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: the two tensors of an ADD / MUL differ in shape");
+    st->operand = LCE_HIP_EW_TENSOR;
+    if (run) {
+      auto p = ptr->find(other);
+      if (p == ptr->end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of an ADD / MUL input");
+      st->values = (const float*)p->second;
+    }
+    return LCE_HIP_OK;
+  };
+  for (;;) {
+    const lce_tfl::Operator& o = M.operators[cur];
+    lce_hip_ew_step st;
+    const lce_hip_status s = operand_of(o, v_t, &st);
+    if (s == LCE_HIP_ERR_UNSUPPORTED && chain.empty())
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
+    if (s == LCE_HIP_ERR_UNSUPPORTED) break;
+    if (s != LCE_HIP_OK) return s;
+    steps.push_back(st);
+    chain.push_back(cur);
+    (*done)[cur] = 1;
+    v_t = o.outputs[0];
+    Shape vs = xs;
+    (*shapes)[v_t] = vs;
+    const std::vector<int32_t>& rd = model->readers[v_t];
+    if (steps.size() == 8 || rd.size() != 1 || is_section_output(v_t)) break;
+    const int32_t next = rd[0];
+    if (!model->absorbed[next] || (*done)[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
+    cur = next;
+  }
+  // the LceQuantize that becomes the launch's bit output
+  int32_t quant = -1;
+  for (int32_t j : sec.ops) {
+    const lce_tfl::Operator& q = M.operators[j];
+    if (j > chain.back() && !(*done)[j] && q.builtin_code == lce_tfl::kBuiltinCustom && q.custom_code == "LceQuantize" &&
+        q.inputs.size() == 1 && q.inputs[0] == v_t && q.outputs.size() == 1) { quant = j; break; }
+  }
+  bool need_float = quant < 0 || is_section_output(v_t);
+  for (int32_t r : model->readers[v_t]) need_float = need_float || r != quant;
+  int32_t bits_t = -1;
+  if (quant >= 0) {
+    (*done)[quant] = 1;
+    bits_t = M.operators[quant].outputs[0];
+    Shape q = xs;
+    q.dims[3] = (xs.dims[3] + 31) / 32;
+    q.type = lce_tfl::kTensorInt32;
+    (*shapes)[bits_t] = q;
+  }
+  if (!run) return LCE_HIP_OK;
+  auto in = ptr->find(x_t);
+  if (in == ptr->end() || !in->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of an ADD / MUL input");
+  void* out = nullptr;
+  void* bits = nullptr;
+  if (need_float)
+    if (lce_hip_status s = buffer_for(v_t, (*shapes)[v_t].bytes(), &out)) return s;
+  if (quant >= 0)
+    if (lce_hip_status s = buffer_for(bits_t, (*shapes)[bits_t].bytes(), &bits)) return s;
+  if (lce_hip_status s = lce_hip_elementwise((const float*)in->second, rows, channels, steps.data(), (int32_t)steps.size(),
+                                             (float*)out, (int32_t*)bits, stream)) return s;
+  ++model->last_ew.launches;
+  model->last_ew.ops += (int32_t)chain.size();
+  if (quant >= 0) ++model->last_ew.quantize;
+  return LCE_HIP_OK;
+}
+
 // Walks section `sec` at `batch` images: shapes of every tensor it touches (shape inference exactly as the ops' Prepare
 // does it) and, with `run`, the launches.  `ptr` maps tensor -> device pointer (section inputs and outputs on entry;
 // intermediates are added from the model's scratch buffers).
@@ -433,6 +627,10 @@ lce_hip_status WalkSection(lce_tflite_model* model, const lce_tflite_section& se
   std::vector<char> done(M.operators.size(), 0);
   for (int32_t i : sec.ops) {
     if (done[i]) continue;
+    if (model->absorbed[i]) {
+      if (lce_hip_status s = WalkElementwiseChain(model, sec, i, batch, shapes, ptr, run, stream, capturing, buffer_for, &done)) return s;
+      continue;
+    }
     const lce_tfl::Operator& op = M.operators[i];
     if (op.inputs.empty() || op.outputs.size() != 1 || op.inputs[0] < 0)
       return Fail(LCE_HIP_ERR_INVALID, "run_section: malformed LCE operator");
@@ -569,6 +767,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
     ptr[sec.outputs[k]] = outputs_dev[k];
   }
   model->last_run_fused = 0;
+  model->last_ew = lce_tflite_model::EwStats();
   if (!model->use_graphs || !stream) return WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
 
   lce_tflite_model::GraphKey key{section, batch, semantics, stream, {}};
@@ -578,6 +777,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
     lce_tflite_model::GraphEntry& e = model->graphs[key];
     if (e.graph) {
       model->last_run_fused = e.fused;
+      model->last_ew = e.ew;
       ++model->graph_replays;
       return lce_hip_graph_launch(e.graph, stream);
     }
@@ -586,6 +786,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       bool recorded = false;
       void* g = nullptr;
       int32_t fused = 0;
+      lce_tflite_model::EwStats ew;
       if (lce_hip_graph_begin_capture(stream) == LCE_HIP_OK) {
         std::map<int32_t, Shape> shapes_c;
         std::map<int32_t, void*> ptr_c = ptr;
@@ -593,6 +794,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
         const lce_hip_status ended = lce_hip_graph_end_capture(stream, &g);
         recorded = walked == LCE_HIP_OK && ended == LCE_HIP_OK && g != nullptr;
         fused = model->last_run_fused;
+        ew = model->last_ew;
         if (!recorded && g) { lce_hip_graph_destroy(g); g = nullptr; }
       }
       g_model_error.clear();
@@ -600,6 +802,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       if (recorded) {
         e2.graph = g;
         e2.fused = fused;
+        e2.ew = ew;
         e2.eager_runs = 1;
         ++model->graph_captures;
         ++model->graph_replays;
@@ -607,6 +810,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       }
       e2.unrecordable = true;
       model->last_run_fused = 0;
+      model->last_ew = lce_tflite_model::EwStats();
     }
   }
   const lce_hip_status s = WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
@@ -626,6 +830,14 @@ void lce_tflite_model_graph_stats(lce_tflite_model* model, int32_t* recorded, in
   std::lock_guard<std::mutex> lock(model->run_mu);
   if (recorded) *recorded = model->graph_captures;
   if (replays) *replays = model->graph_replays;
+}
+
+void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (launches) *launches = model->last_ew.launches;
+  if (ops_folded) *ops_folded = model->last_ew.ops;
+  if (quantize_folded) *quantize_folded = model->last_ew.quantize;
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

@@ -16,6 +16,9 @@
 //   Operator         0 opcode_index  1 inputs  2 outputs  3/4 builtin_options (union)
 //                    5 custom_options[ubyte]  6 custom_options_format
 //   Buffer           0 data[ubyte]
+//   BuiltinOptions union types: 11 AddOptions, 21 MulOptions; both tables: 0 fused_activation_function(int8,
+//   ActivationFunctionType: 0 NONE, 1 RELU, 2 RELU_N1_TO_1, 3 RELU6, 4 TANH, 5 SIGN_BIT); BuiltinOperator 0 ADD, 18 MUL.
+//   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
 // which custom_options carry unchanged.  Everything else is tested against a writer that
@@ -31,6 +34,8 @@
 namespace lce_tfl {
 
 constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
+constexpr int32_t kBuiltinAdd = 0, kBuiltinMul = 18;
+constexpr int kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 // TensorType values used by LCE graphs
 constexpr int kTensorFloat32 = 0, kTensorInt32 = 2, kTensorBool = 6, kTensorInt8 = 9;
 
@@ -52,6 +57,7 @@ struct Operator {
   std::vector<int32_t> inputs, outputs;   // tensor indices, -1 = optional input not present
   const uint8_t* custom_options = nullptr;
   size_t custom_options_size = 0;
+  int32_t activation = 0;          // fused_activation_function of AddOptions / MulOptions; 0 (NONE) when absent
 };
 
 class Model {
@@ -220,6 +226,14 @@ class Model {
       O.custom_code = codes[idx].custom;
       O.custom_options = c ? b_ + f : nullptr;
       O.custom_options_size = c;
+      uint8_t opt_type;
+      size_t opt_pos, opt;
+      if (!Scalar<uint8_t>(t, 3, 0, &opt_type) || !Field(t, 4, &opt_pos)) return Fail("bad Operator.builtin_options");
+      if ((opt_type == kOptionsAdd || opt_type == kOptionsMul) && opt_pos != 0) {
+        int8_t act;
+        if (!Indirect(opt_pos, &opt) || !Scalar<int8_t>(opt, 0, 0, &act)) return Fail("bad AddOptions / MulOptions");
+        O.activation = act;
+      }
       for (int32_t x : O.inputs) if (x < -1 || x >= (int32_t)nt) return Fail("Operator input index out of range");
       for (int32_t x : O.outputs) if (x < 0 || x >= (int32_t)nt) return Fail("Operator output index out of range");
     }

@@ -14,6 +14,9 @@ convolutions, float head -- is cut into its binary SECTIONS (``Interpreter.secti
 with no builtin operator between them, include/lce_tflite_model.h); ``run_section(k, inputs)`` runs one of them on
 its boundary tensors, the float operators stay with TensorFlow Lite (``predict`` on such a graph raises
 ``NotImplementedError`` naming the first builtin operator).
+With ``elementwise_sections=True`` (``lce_tflite_model_open_ex`` with LCE_TFLITE_SECTIONS_ELEMENTWISE) the float ADD / MUL
+between binary layers -- batch norm constants, residual shortcuts -- join the sections and run on the GPU as one fused pass
+per chain (``lce_hip_elementwise``); a graph whose every operator then lies in a section runs through ``predict``.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -30,6 +33,7 @@ _TFL_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "tfl
 _tfl = None
 
 FLOAT32, INT32, BOOL, INT8 = 0, 2, 6, 9
+SECTIONS_ELEMENTWISE = 1          # LCE_TFLITE_SECTIONS_ELEMENTWISE
 _NP = {FLOAT32: np.float32, INT32: np.int32, BOOL: np.bool_, INT8: np.int8}
 LCE_OPS = ("LceQuantize", "LceDequantize", "LceBconv2d", "LceBMaxPool2d")
 
@@ -74,6 +78,11 @@ def tflite_lib() -> C.CDLL:
         l = C.CDLL(path)
         l.lce_tflite_model_open.restype = C.c_void_p
         l.lce_tflite_model_open.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        l.lce_tflite_model_open_ex.restype = C.c_void_p
+        l.lce_tflite_model_open_ex.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_char_p, C.c_size_t]
+        l.lce_tflite_model_operator_activation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        l.lce_tflite_model_elementwise_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
+        l.lce_tflite_model_elementwise_stats.restype = None
         l.lce_tflite_model_close.argtypes = [C.c_void_p]
         for f in ("lce_tflite_model_num_tensors", "lce_tflite_model_num_operators"):
             getattr(l, f).argtypes = [C.c_void_p]
@@ -111,8 +120,9 @@ class Tensor:
 
 
 class Operator:
-    def __init__(self, info: _OperatorInfo):
+    def __init__(self, info: _OperatorInfo, activation: int = 0):
         self.builtin_code = info.builtin_code
+        self.activation = activation          # fused_activation_function of a builtin ADD / MUL (0: NONE)
         self.custom_code = (info.custom_code or b"").decode()
         self.inputs = [info.inputs[i] for i in range(info.num_inputs)]
         self.outputs = [info.outputs[i] for i in range(info.num_outputs)]
@@ -127,13 +137,17 @@ class Operator:
 class LceModel:
     """A parsed .tflite flatbuffer (first subgraph)."""
 
-    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike]):
+    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False):
+        """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
+        include/lce_tflite_model.h); the host then runs only what lies outside them."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
         self._data = bytes(flatbuffer)            # must outlive the handle (zero-copy reader)
+        self.elementwise_sections = bool(elementwise_sections)
         err = C.create_string_buffer(256)
-        self._h = tflite_lib().lce_tflite_model_open(self._data, len(self._data), err, 256)
+        flags = SECTIONS_ELEMENTWISE if elementwise_sections else 0
+        self._h = tflite_lib().lce_tflite_model_open_ex(self._data, len(self._data), flags, err, 256)
         if not self._h:
             raise ValueError("not a readable TFLite model: " + err.value.decode(errors="replace"))
         l = tflite_lib()
@@ -146,7 +160,9 @@ class LceModel:
         for i in range(l.lce_tflite_model_num_operators(self._h)):
             info = _OperatorInfo()
             _amd.check(l.lce_tflite_model_operator(self._h, i, C.byref(info)))
-            self.operators.append(Operator(info))
+            act = C.c_int32()
+            _amd.check(l.lce_tflite_model_operator_activation(self._h, i, C.byref(act)))
+            self.operators.append(Operator(info, act.value))
         buf = (C.c_int32 * 64)()
         self.inputs = [buf[i] for i in range(l.lce_tflite_model_inputs(self._h, buf, 64))]
         self.outputs = [buf[i] for i in range(l.lce_tflite_model_outputs(self._h, buf, 64))]
@@ -187,6 +203,12 @@ class LceModel:
         tflite_lib().lce_tflite_model_run_stats(self._h, C.byref(a), C.byref(b), C.byref(c))
         return int(a.value), int(b.value), int(c.value)
 
+    def elementwise_stats(self):
+        """(lce_hip_elementwise launches, ADD / MUL operators they ran, LceQuantize launches they absorbed) of the last run."""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        tflite_lib().lce_tflite_model_elementwise_stats(self._h, C.byref(a), C.byref(b), C.byref(c))
+        return int(a.value), int(b.value), int(c.value)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -215,13 +237,21 @@ class Interpreter:
     """``Interpreter(flatbuffer_model, batch_size=...)`` -- see the module docstring."""
 
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
-                 use_reference_bconv: bool = False):
-        self.model = flatbuffer_model if isinstance(flatbuffer_model, LceModel) else LceModel(flatbuffer_model)
+                 use_reference_bconv: bool = False, elementwise_sections: bool = False):
+        """``elementwise_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its own setting holds)."""
+        self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
+                      else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        self._foreign = [(i, op) for i, op in enumerate(self.model.operators)
-                         if op.builtin_code != 32 or op.custom_code not in LCE_OPS]
+        if self.model.elementwise_sections:
+            # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
+            # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
+            covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()
+            self._foreign = [(i, op) for i, op in enumerate(self.model.operators) if i not in covered]
+        else:
+            self._foreign = [(i, op) for i, op in enumerate(self.model.operators)
+                             if op.builtin_code != 32 or op.custom_code not in LCE_OPS]
 
     @property
     def sections(self) -> List[Section]:

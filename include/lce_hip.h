@@ -126,6 +126,37 @@ lce_hip_status lce_hip_unpack(lce_hip_dtype out_type, const int32_t* in_dev, siz
                               void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Float ADD / MUL between binary layers (TFLite builtins) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* A converted residual binary network runs, between two LceBconv2d, the builtin float ADD / MUL of its batch norm
+ * and its residual shortcut, then the next layer's LceQuantize.  lce_hip_elementwise runs such a chain in ONE pass
+ * over an NHWC float32 tensor `in_dev` ([rows, channels], rows = N*H*W): per element
+ *     v = in;  for each step: v = fl(v op operand) (one rounding, never an fma); v = min(max(v, lo), hi)
+ * where [lo, hi] is CalculateActivationRange of the step's activation (NONE = [-FLT_MAX, FLT_MAX]: an infinity
+ * becomes +-FLT_MAX; RELU = [0, FLT_MAX]; RELU_N1_TO_1 = [-1, 1]; RELU6 = [0, 6]) and std::max(a, b) = a < b ? b : a
+ * (RELU(-0.0) = -0.0); subnormals are kept.  `out_dev` (nullable) gets v; `out_bits_dev` (nullable) gets the
+ * LceQuantize of v as lce_hip_bitpack(F32, ...) writes it: bit = v < 0, ceil(channels/32) words per row.  out_dev
+ * may be in_dev or a TENSOR operand (in place).  Steps (1..8) are read at the call; their device arrays at run time.
+ * Zero rows or channels is a no-op (checked before the pointers: an empty tensor may have none).  Asynchronous on
+ * `stream`. */
+typedef enum lce_hip_ew_op { LCE_HIP_EW_ADD = 0, LCE_HIP_EW_MUL = 1 } lce_hip_ew_op;
+typedef enum lce_hip_ew_operand {
+  LCE_HIP_EW_SCALAR = 0,        /* `scalar` */
+  LCE_HIP_EW_PER_CHANNEL = 1,   /* values[channels] (a batch norm's constants) */
+  LCE_HIP_EW_TENSOR = 2         /* values[rows * channels] (the residual) */
+} lce_hip_ew_operand;
+typedef struct lce_hip_ew_step {
+  int32_t op, operand;      /* lce_hip_ew_op, lce_hip_ew_operand */
+  const float* values;      /* device: [channels] or [rows * channels]; NULL for SCALAR */
+  float scalar;
+  int32_t activation;       /* an lce_hip_activation: NONE, RELU, RELU_N1_TO_1 or RELU6 */
+} lce_hip_ew_step;
+lce_hip_status lce_hip_elementwise(const float* in_dev, size_t rows, size_t channels,
+                                   const lce_hip_ew_step* steps, int32_t num_steps,
+                                   float* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

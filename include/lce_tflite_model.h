@@ -28,6 +28,19 @@ enum { LCE_TFLITE_FLOAT32 = 0, LCE_TFLITE_INT32 = 2, LCE_TFLITE_BOOL = 6, LCE_TF
 /* Parses `data` (kept by reference: it must outlive the model).  Returns NULL and writes a
  * message into err (if given) when the buffer is not a well-formed TFL3 flatbuffer. */
 lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err, size_t err_len);
+
+/* lce_tflite_model_open with flags (0: exactly lce_tflite_model_open).
+ *   LCE_TFLITE_SECTIONS_ELEMENTWISE: the host hands the float ADD / MUL BETWEEN binary layers (batch norm constants,
+ *   residual shortcuts) to this library, so they join the binary sections.  A builtin operator joins an LCE epoch of the
+ *   partition below when it is ADD (0) or MUL (18) on float32 tensors with a 4-D output, each input either a tensor of
+ *   the output's shape (batch ignored) or a constant of shape [C], [1,1,1,C], [1] or [], its fused activation is NONE /
+ *   RELU / RELU_N1_TO_1 / RELU6, and one of its non-constant inputs is produced by an operator of the same epoch (so stem
+ *   and head ops, and ops on unrelated branches, stay with the host).  lce_tflite_model_run_section then runs each chain
+ *   of such operators as one lce_hip_elementwise launch, with the LceQuantize that reads its result as the launch's bit
+ *   output.  Every other builtin operator still cuts a section.  The flag changes the partition -- the host's contract --
+ *   and is therefore opt-in. */
+enum { LCE_TFLITE_SECTIONS_ELEMENTWISE = 1u };
+lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
 int32_t lce_tflite_model_num_tensors(const lce_tflite_model* model);
@@ -60,6 +73,9 @@ typedef struct lce_tflite_operator_info {
   size_t custom_options_size;
 } lce_tflite_operator_info;
 lce_hip_status lce_tflite_model_operator(const lce_tflite_model* model, int32_t index, lce_tflite_operator_info* info);
+/* fused_activation_function of a builtin ADD / MUL (AddOptions / MulOptions: lce_hip_activation values, and 4 TANH /
+ * 5 SIGN_BIT as the file says); 0 (NONE) when the options table is absent and for every other operator. */
+lce_hip_status lce_tflite_model_operator_activation(const lce_tflite_model* model, int32_t index, int32_t* activation);
 
 /* Binary SECTIONS of a mixed graph.  A converted model interleaves builtin float operators (the stem, batch norms, adds,
  * the head) with LCE custom ops; what this library runs are the maximal groups of LCE ops that can execute without a
@@ -109,6 +125,9 @@ lce_hip_status lce_tflite_model_section_tensor_shape(lce_tflite_model* model, in
  * LceQuantize launches the LAST run folded into a convolution's epilogue, bytes of intermediate buffers.  Any pointer may
  * be NULL. */
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes);
+/* The LAST run's lce_hip_elementwise launches (LCE_TFLITE_SECTIONS_ELEMENTWISE): launches, ADD / MUL operators they ran,
+ * LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
+void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
