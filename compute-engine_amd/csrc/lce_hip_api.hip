@@ -116,7 +116,6 @@ struct lce_hip_bconv2d_plan {
   DevBuf<uint8_t> d_wq;
   DevBuf<float> d_thrq;
   DevBuf<uint32_t> d_sched;        // streaming kernel: its production schedule
-  bool cus_forced = false;         // num_cus was set through the "compute_units" option
   int device = -1;                 // the HIP device the plan's buffers live on (bound at the first upload)
   void* workspace = nullptr;       // FP4 expanded activations (matrix-core engine, workspace variant)
   void* lds_opt_in = nullptr;      // kernel already granted > 64 KiB of dynamic LDS
@@ -200,7 +199,7 @@ lce_hip_status ensure_selected(lce_hip_bconv2d_plan* plan, int batch_chunk) {
       (!h.use_tiled || !h.packed.empty() || !h.have_weights) &&
       (!h.use_mfma || !h.wq.empty() || !h.have_weights))
     return LCE_HIP_OK;
-  if (!plan->cus_forced) {
+  if (!h.cus_forced) {
     // the streaming kernel sizes its grid by the compute units of the device the plan runs on: the one it is bound to, or
     // the current one before its first run (asked once per device and process)
     int dev = plan->device;
@@ -576,150 +575,13 @@ lce_hip_status lce_hip_bconv2d_plan_folded(const lce_hip_bconv2d_plan* plan, flo
 
 lce_hip_status lce_hip_bconv2d_plan_set_option(lce_hip_bconv2d_plan* plan, const char* key, const char* value) {
   if (!plan || !key || !value) return fail(LCE_HIP_ERR_INVALID, "plan_set_option: null argument");
-  lce::HostPlan& h = plan->host;
-  if (!strcmp(key, "tile2d")) {   // tuning aid for the direct variant: auto | on | off
-    if (!strcmp(value, "auto")) h.tile2d_pref = 0;
-    else if (!strcmp(value, "on")) h.tile2d_pref = 1;
-    else if (!strcmp(value, "off")) h.tile2d_pref = 2;
-    else return fail(LCE_HIP_ERR_INVALID, "plan_set_option: tile2d must be auto|on|off");
-    plan->selected_for_pixels = -1;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "pointwise_tiles")) {   // tuning aid for the 1x1 streaming kernel: tiles per wave
-    const int v = atoi(value);
-    if (v < 0 || v > 8 || (v == 0 && strcmp(value, "0")))
-      return fail(LCE_HIP_ERR_INVALID, "plan_set_option: pointwise_tiles must be 0 (auto) .. 8");
-    h.pw_tiles_pref = v;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "pointwise_channels")) {   // tuning aid for the 1x1 streaming kernel: output channels per block
-    const int v = atoi(value);
-    if (!(v == 32 || v == 64 || v == 128 || (v == 0 && !strcmp(value, "0"))))
-      return fail(LCE_HIP_ERR_INVALID, "plan_set_option: pointwise_channels must be 0 (auto), 32, 64 or 128");
-    h.pw_nj_pref = v / 32;
-    plan->selected_for_pixels = -1;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "stream_rows")) {       // tuning aid for the streaming kernel: output rows per segment (0 = auto)
-    const int v = atoi(value);
-    if (v < 0 || (v == 0 && strcmp(value, "0")))
-      return fail(LCE_HIP_ERR_INVALID, "plan_set_option: stream_rows must be 0 (auto) or a positive row count");
-    h.stream_rows_pref = v;
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "stream_strip")) {      // testing aid for the streaming kernel: -1 auto, 0 never, else the column strip's width
-    const int v = atoi(value);
-    if (v < -1 || (v == 0 && strcmp(value, "0"))) return fail(LCE_HIP_ERR_INVALID, "plan_set_option: stream_strip must be -1 (auto), 0 (whole rows) or a strip width");
-    h.stream_strip_pref = v;
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "stream_interleave")) {   // the streaming kernel's segment -> block map: 1 = block b owns segments b, b + grid, ... (a compact write window), 0 = consecutive ones
-    if (strcmp(value, "0") && strcmp(value, "1") && strcmp(value, "auto")) return fail(LCE_HIP_ERR_INVALID, "plan_set_option: stream_interleave must be auto, 0 or 1");
-    h.stream_interleave_pref = value[0] == 'a' ? -1 : value[0] == '1';
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "stream_blocks_per_cu")) {   // the streaming kernel's launch: blocks per CU (2: only where the instance is compiled for it and both blocks' LDS fit)
-    if (strcmp(value, "1") && strcmp(value, "2") && strcmp(value, "auto")) return fail(LCE_HIP_ERR_INVALID, "plan_set_option: stream_blocks_per_cu must be auto, 1 or 2");
-    h.stream_occ_pref = value[0] == 'a' ? 0 : value[0] - '0';
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "wstream_blocks") || !strcmp(key, "wstream_images")) {   // tuning aids for the weight-streaming kernel: pixel blocks per block (1..4), images per group; 0 = auto
-    const int v = atoi(value);
-    const bool blocks = key[8] == 'b';
-    if (v < 0 || (v == 0 && strcmp(value, "0")) || (blocks && v > 4))
-      return fail(LCE_HIP_ERR_INVALID, "plan_set_option: wstream_blocks must be 0 (auto) .. 4, wstream_images 0 (auto) or a positive count");
-    (blocks ? h.ws_blocks_pref : h.ws_images_pref) = v;
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "int8_rounding")) {      // testing aid: "exact" keeps the round-half-away instances even where floor(x + 0.5) is proven equal
-    if (strcmp(value, "auto") && strcmp(value, "exact")) return fail(LCE_HIP_ERR_INVALID, "plan_set_option: int8_rounding must be auto or exact");
-    h.int8_exact_pref = value[0] == 'e';
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    h.wq.clear();
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "stream_flat")) {       // testing aid for the streaming kernel: 0 = never cut pixel blocks across a block's images
-    if (strcmp(value, "0") && strcmp(value, "1")) return fail(LCE_HIP_ERR_INVALID, "plan_set_option: stream_flat must be 0 or 1");
-    h.stream_noflat = value[0] == '0';
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "stream_pixel_phases")) {   // tuning aid for the streaming kernel: pixel phases per block (the other waves take channel slices)
-    const int v = atoi(value);
-    if (!(v == 1 || v == 2 || v == 4 || (v == 0 && !strcmp(value, "0"))))
-      return fail(LCE_HIP_ERR_INVALID, "plan_set_option: stream_pixel_phases must be 0 (auto), 1, 2 or 4");
-    h.stream_phases_pref = v;
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "compute_units")) {     // testing aid: the device's CU count as the streaming kernel's planner sees it
-    const int v = atoi(value);
-    if (v < 1) return fail(LCE_HIP_ERR_INVALID, "plan_set_option: compute_units must be positive");
-    h.num_cus = v;
-    plan->cus_forced = true;
-    plan->selected_for_pixels = -1;
-    plan->device_current = false;
-    return LCE_HIP_OK;
-  }
-  if (!strcmp(key, "engine")) {
-    if (!strcmp(value, "auto")) h.engine_pref = 0;
-    else if (!strcmp(value, "valu")) h.engine_pref = 1;
-    else if (!strcmp(value, "mfma")) h.engine_pref = 2;
-    else if (!strcmp(value, "direct")) h.engine_pref = 3;
-    else if (!strcmp(value, "pointwise")) h.engine_pref = 4;
-    else if (!strcmp(value, "stream")) h.engine_pref = 5;
-    else if (!strcmp(value, "wstream")) h.engine_pref = 6;
-    else return fail(LCE_HIP_ERR_INVALID, "plan_set_option: engine must be auto|valu|mfma|direct|pointwise|stream|wstream");
-  } else if (!strcmp(key, "phase")) {
-    // profiling aid for the matrix-core engine: time its two kernels separately
-    if (!strcmp(value, "all")) h.phase = 0;
-    else if (!strcmp(value, "expand")) h.phase = 1;
-    else if (!strcmp(value, "gemm")) h.phase = 2;
-    else return fail(LCE_HIP_ERR_INVALID, "plan_set_option: phase must be all|expand|gemm");
-    return LCE_HIP_OK;
-  } else if (!strcmp(key, "epilogue")) {
-    // tuning aid for the matrix-core engine's float / int8 epilogues
-    if (!strcmp(value, "auto")) h.epilogue_pref = 0;
-    else if (!strcmp(value, "tile")) h.epilogue_pref = 1;
-    else if (!strcmp(value, "wide")) h.epilogue_pref = 2;
-    else return fail(LCE_HIP_ERR_INVALID, "plan_set_option: epilogue must be auto|tile|wide");
-    return LCE_HIP_OK;
-  } else if (!strcmp(key, "kernel")) {
-    if (!strcmp(value, "auto")) h.kernel_pref = 0;
-    else if (!strcmp(value, "tiled")) h.kernel_pref = 1;
-    else if (!strcmp(value, "general")) h.kernel_pref = 2;
-    else return fail(LCE_HIP_ERR_INVALID, "plan_set_option: kernel must be auto|tiled|general");
-  } else if (!strcmp(key, "tile")) {
-    int tm = 0, tn = 0;
-    if (!strcmp(value, "auto")) { h.tile_pref = lce::TileShape{0, 0}; }
-    else if (sscanf(value, "%dx%d", &tm, &tn) == 2 &&
-             ((tn <= 32 && lce::lookup_tiled(LCE_HIP_F32, tm, tn, 1)) || lce::mfma_cfg_by_tile(tm, tn))) {
-      h.tile_pref = lce::TileShape{tm, tn};
-    } else {
-      return fail(LCE_HIP_ERR_INVALID, "plan_set_option: tile must be auto, a xor-popcount tile "
-                  "(4x16|2x32|2x16|1x32|1x16) or, with engine=mfma, a block tile "
-                  "(256x256|256x128|512x64|128x256|128x128|256x64|128x64)");
-    }
-  } else {
-    return fail(LCE_HIP_ERR_INVALID, "plan_set_option: unknown key '%s'", key);
-  }
-  plan->selected_for_pixels = -1;
-  plan->device_current = false;
-  h.packed.clear();
-  h.wq.clear();
+  unsigned stale = 0;
+  const std::string err = lce::set_plan_option(plan->host, key, value, &stale);
+  if (!err.empty()) return fail(LCE_HIP_ERR_INVALID, "%s", err.c_str());
+  if (stale & lce::kStaleSelection) plan->selected_for_pixels = -1;
+  if (stale & lce::kStaleUpload) plan->device_current = false;
+  if (stale & lce::kStalePacked) plan->host.packed.clear();
+  if (stale & lce::kStaleWeightImage) plan->host.wq.clear();
   return LCE_HIP_OK;
 }
 
@@ -741,9 +603,7 @@ lce_hip_status lce_hip_bconv2d_plan_int8_epilogue(lce_hip_bconv2d_plan* plan, in
   const lce::HostPlan& h = plan->host;
   if (h.d.dst_type != LCE_HIP_I8 || !h.have_weights) return LCE_HIP_OK;
   if (lce_hip_status s = ensure_selected(plan, lce::max_batch_per_launch(h))) return s;
-  // (only the streaming / weight-streaming / pointwise kernels have the proven forms; the block GEMM and the xor-popcount engine run
-  //  the reference's sequence whatever the proof said)
-  const bool forms = h.use_mfma && (h.use_stream || h.use_wstream || h.use_pointwise) && h.int8_floor_ok;
+  const bool forms = lce::int8_one_instruction_forms(h);
   if (one_instruction_forms) *one_instruction_forms = forms ? 1 : 0;
   if (adjusted_channels) *adjusted_channels = forms ? h.int8_bias_adjusted : 0;
   return LCE_HIP_OK;
@@ -757,7 +617,7 @@ static lce_hip_status run_images(lce_hip_bconv2d_plan* plan, const int32_t* inpu
   lce::HostPlan& h = plan->host;
   const int chunk = lce::max_batch_per_launch(h);
   if (lce_hip_status s = check_device(plan)) return s;          // binds the plan to the current device on its first run ...
-  if (!plan->cus_forced && plan->host.num_cus != device_compute_units(plan->device) && device_compute_units(plan->device) > 0)
+  if (!h.cus_forced && plan->host.num_cus != device_compute_units(plan->device) && device_compute_units(plan->device) > 0)
     plan->selected_for_pixels = -1;                              // ... whose size the streaming kernel's grid follows
   if (lce_hip_status s = ensure_selected(plan, chunk)) return s;
   if (lce_hip_status s = ensure_uploaded(plan)) return s;

@@ -4,6 +4,7 @@
 // Citations are relative to /root/reference/larq_compute_engine/.
 #include "lce_plan.h"
 #include "lce_plan_internal.h"
+#include "lce_kernel_types.h"   // lookup_tiled: which xor-popcount tiles the option "tile" accepts
 #include <cstdio>
 #include <cstdlib>
 
@@ -12,6 +13,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <initializer_list>
 #include <limits>
 #include <cstdio>
 
@@ -103,6 +105,114 @@ std::string validate_and_infer(HostPlan& p) {
   const int64_t per_image_bytes = (int64_t)d.in_height * d.in_width * p.cw * 4;
   if (per_image_bytes >= (1ll << 31)) return "bconv2d: one input image must be smaller than 2 GiB";
   if ((int64_t)p.out_h * p.out_w >= (1ll << 31)) return "bconv2d: output plane too large";
+  return "";
+}
+
+// The position of `s` among `words`, or -1
+static int word_index(const char* s, std::initializer_list<const char*> words) {
+  int i = 0;
+  for (const char* w : words) {
+    if (!strcmp(s, w)) return i;
+    ++i;
+  }
+  return -1;
+}
+
+// An integer option is read with atoi ("3abc" is 3); a 0 counts only when it is written "0" (atoi's answer to a word is 0 too)
+static bool int_value(const char* s, int* v) {
+  *v = atoi(s);
+  return *v != 0 || !strcmp(s, "0");
+}
+
+static bool in_set(int v, std::initializer_list<int> set) { return std::find(set.begin(), set.end(), v) != set.end(); }
+
+std::string set_plan_option(HostPlan& p, const char* key, const char* value, unsigned* invalidates) {
+  PlanOptions& o = p;
+  const unsigned plan_and_upload = kStaleSelection | kStaleUpload;
+  const unsigned all = plan_and_upload | kStalePacked | kStaleWeightImage;
+  unsigned stale = 0;
+  int v = 0;
+  *invalidates = 0;
+  if (!strcmp(key, "tile2d")) {
+    if ((v = word_index(value, {"auto", "on", "off"})) < 0) return "plan_set_option: tile2d must be auto|on|off";
+    o.tile2d_pref = v;
+    stale = kStaleSelection;
+  } else if (!strcmp(key, "pointwise_tiles")) {        // read at launch: nothing to redo
+    if (!int_value(value, &v) || v < 0 || v > 8) return "plan_set_option: pointwise_tiles must be 0 (auto) .. 8";
+    o.pw_tiles_pref = v;
+  } else if (!strcmp(key, "pointwise_channels")) {
+    if (!int_value(value, &v) || !in_set(v, {0, 32, 64, 128}))
+      return "plan_set_option: pointwise_channels must be 0 (auto), 32, 64 or 128";
+    o.pw_nj_pref = v / 32;
+    stale = kStaleSelection;
+  } else if (!strcmp(key, "stream_rows")) {
+    if (!int_value(value, &v) || v < 0) return "plan_set_option: stream_rows must be 0 (auto) or a positive row count";
+    o.stream_rows_pref = v;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "stream_strip")) {
+    if (!int_value(value, &v) || v < -1)
+      return "plan_set_option: stream_strip must be -1 (auto), 0 (whole rows) or a strip width";
+    o.stream_strip_pref = v;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "stream_interleave")) {
+    if ((v = word_index(value, {"0", "1", "auto"})) < 0) return "plan_set_option: stream_interleave must be auto, 0 or 1";
+    o.stream_interleave_pref = v == 2 ? -1 : v;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "stream_blocks_per_cu")) {
+    if ((v = word_index(value, {"auto", "1", "2"})) < 0) return "plan_set_option: stream_blocks_per_cu must be auto, 1 or 2";
+    o.stream_occ_pref = v;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "stream_flat")) {
+    if ((v = word_index(value, {"0", "1"})) < 0) return "plan_set_option: stream_flat must be 0 or 1";
+    o.stream_noflat = v == 0;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "stream_pixel_phases")) {
+    if (!int_value(value, &v) || !in_set(v, {0, 1, 2, 4}))
+      return "plan_set_option: stream_pixel_phases must be 0 (auto), 1, 2 or 4";
+    o.stream_phases_pref = v;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "wstream_blocks") || !strcmp(key, "wstream_images")) {
+    const bool blocks = key[8] == 'b';
+    if (!int_value(value, &v) || v < 0 || (blocks && v > 4))
+      return "plan_set_option: wstream_blocks must be 0 (auto) .. 4, wstream_images 0 (auto) or a positive count";
+    (blocks ? o.ws_blocks_pref : o.ws_images_pref) = v;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "compute_units")) {
+    if ((v = atoi(value)) < 1) return "plan_set_option: compute_units must be positive";
+    p.num_cus = v;
+    o.cus_forced = true;
+    stale = plan_and_upload;
+  } else if (!strcmp(key, "int8_rounding")) {
+    if ((v = word_index(value, {"auto", "exact"})) < 0) return "plan_set_option: int8_rounding must be auto or exact";
+    o.int8_exact_pref = v == 1;
+    stale = plan_and_upload | kStaleWeightImage;
+  } else if (!strcmp(key, "phase")) {                  // read at launch
+    if ((v = word_index(value, {"all", "expand", "gemm"})) < 0) return "plan_set_option: phase must be all|expand|gemm";
+    o.phase = v;
+  } else if (!strcmp(key, "epilogue")) {               // read at launch (make_mfma_args)
+    if ((v = word_index(value, {"auto", "tile", "wide"})) < 0) return "plan_set_option: epilogue must be auto|tile|wide";
+    o.epilogue_pref = v;
+  } else if (!strcmp(key, "engine")) {
+    if ((v = word_index(value, {"auto", "valu", "mfma", "direct", "pointwise", "stream", "wstream"})) < 0)
+      return "plan_set_option: engine must be auto|valu|mfma|direct|pointwise|stream|wstream";
+    o.engine_pref = v;
+    stale = all;
+  } else if (!strcmp(key, "kernel")) {
+    if ((v = word_index(value, {"auto", "tiled", "general"})) < 0) return "plan_set_option: kernel must be auto|tiled|general";
+    o.kernel_pref = v;
+    stale = all;
+  } else if (!strcmp(key, "tile")) {
+    int tm = 0, tn = 0;
+    if (strcmp(value, "auto") && !(sscanf(value, "%dx%d", &tm, &tn) == 2 &&
+                                   ((tn <= 32 && lookup_tiled(LCE_HIP_F32, tm, tn, 1)) || mfma_cfg_by_tile(tm, tn))))
+      return "plan_set_option: tile must be auto, a xor-popcount tile (4x16|2x32|2x16|1x32|1x16) or, with engine=mfma, a block tile "
+             "(256x256|256x128|512x64|128x256|128x128|256x64|128x64)";
+    o.tile_pref = TileShape{tm, tn};
+    stale = all;
+  } else {
+    return std::string("plan_set_option: unknown key '") + key + "'";
+  }
+  *invalidates = stale;
   return "";
 }
 
@@ -781,15 +891,15 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
   p.use_mfma = false;
   p.use_direct = false;
   p.use_pointwise = false;
-  if (p.engine_pref == 4 && !pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj))
+  if (p.engine_pref == kEnginePointwise && !pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj))
     return "bconv2d: the pointwise kernel runs 1x1 ungrouped convolutions with 64, 128, 256 or 512 input channels (after padding to 64) "
            "and a multiple of 32 output channels (pointwise_channels must divide them)";
-  if (p.engine_pref >= 2 && !mfma_supported(p))
+  if (p.engine_pref >= kEngineMfma && !mfma_supported(p))
     return "bconv2d: the matrix-core engine cannot run this convolution (channels per group not a multiple of 64, or too deep)";
   p.use_stream = false;
   p.use_wstream = false;
   p.est_us = -1.0;
-  if (p.engine_pref == 6) {
+  if (p.engine_pref == kEngineWstream) {
     // weight-streaming kernel (activations stationary in LDS): the planner's FP4 weight image with 64-channel granularity
     const int batch_chunk = (int)std::max<int64_t>(1, pixels / std::max<int64_t>(1, (int64_t)p.out_h * p.out_w));
     const std::string err = plan_wstream(p, batch_chunk);
@@ -798,9 +908,9 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
     use_wstream_plan(p);
     return "";
   }
-  const bool auto_rule = p.engine_pref == 0 && p.kernel_pref == 0 && p.tile_pref.tm == 0;
+  const bool auto_rule = p.engine_pref == kEngineAuto && p.kernel_pref == kKernelAuto && p.tile_pref.tm == 0;
   bool gemm_by_estimate = false;      // the block GEMM was priced cheapest among the matrix-core kernels: not the xor-popcount engine then
-  if ((p.engine_pref == 5 || auto_rule) && stream_supported(p)) {
+  if ((p.engine_pref == kEngineStream || auto_rule) && stream_supported(p)) {
     // The streaming family: every candidate is planned and priced (estimate_*_us above); the cheapest runs.  engine=stream
     // restricts the choice to the weight-stationary kernel's own variants; stream_rows / stream_interleave pin theirs.
     const int batch_chunk = (int)std::max<int64_t>(1, pixels / std::max<int64_t>(1, (int64_t)p.out_h * p.out_w));
@@ -908,25 +1018,25 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
       p.kernel_name = nm;
       return "";
     }
-    if (p.engine_pref == 5) return first_err.empty() ? std::string("bconv2d: the streaming kernel cannot run this launch") : first_err;
-  } else if (p.engine_pref == 5) {
+    if (p.engine_pref == kEngineStream) return first_err.empty() ? std::string("bconv2d: the streaming kernel cannot run this launch") : first_err;
+  } else if (p.engine_pref == kEngineStream) {
     return plan_stream(p, 1);      // (the message that says why)
   }
-  if (p.engine_pref >= 2 || (p.engine_pref == 0 && p.kernel_pref == 0 && p.tile_pref.tm == 0 &&
+  if (p.engine_pref >= kEngineMfma || (p.engine_pref == kEngineAuto && p.kernel_pref == kKernelAuto && p.tile_pref.tm == 0 &&
                              mfma_supported(p) && (gemm_by_estimate || pixels * d.channels_out >= (1 << 16)))) {
     p.use_mfma = true;
     p.use_tiled = false;
     p.est_us = estimate_block_gemm_us(p, pixels);
     MfmaCfg want = choose_mfma_cfg(p, pixels);
     bool direct = false;
-    if (p.engine_pref >= 2 && p.tile_pref.tm != 0) {
+    if (p.engine_pref >= kEngineMfma && p.tile_pref.tm != 0) {
       const MfmaCfg* forced = mfma_cfg_by_tile(p.tile_pref.tm, p.tile_pref.tn);
       if (!forced) return "bconv2d: no matrix-core kernel instance for the requested block tile";
       if (d.groups > 1 && p.npg % forced->bn())
         return "bconv2d: the requested block tile would straddle channel groups";
       want = *forced;
-      direct = p.engine_pref == 3;
-    } else if (p.engine_pref != 2) {
+      direct = p.engine_pref == kEngineDirect;
+    } else if (p.engine_pref != kEngineMfma) {
       // auto / engine=direct without a tile: the direct variant when a good tile exists
       MfmaCfg dc;
       // (auto: a launch of at most half a round of blocks with a deep K loop -- >= 27 K-steps: 3x3 over 192+ channels -- runs at the
@@ -935,12 +1045,12 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
       //  every such row, 0.99 at worst; with more blocks the direct variant wins by 10 ... 50 %.)
       const int ks_deep = d.filter_height * d.filter_width * ceil_div(d.channels_in / std::max(1, d.groups), 64);
       auto tiny_deep = [&](const MfmaCfg& c) {
-        return p.engine_pref == 0 && ks_deep >= 27 && ((pixels + c.bm() - 1) / c.bm()) * ceil_div(d.channels_out, c.bn()) <= 128;
+        return p.engine_pref == kEngineAuto && ks_deep >= 27 && ((pixels + c.bm() - 1) / c.bm()) * ceil_div(d.channels_out, c.bn()) <= 128;
       };
       if (choose_direct_cfg(p, &dc) && !tiny_deep(dc)) {
         want = dc;
         direct = true;
-      } else if (p.engine_pref == 3) {
+      } else if (p.engine_pref == kEngineDirect) {
         // forced: take any tile whose halo fits, whatever the padding waste
         for (int bm : {128, 256}) {
           const MfmaCfg* c = mfma_cfg_by_tile(bm, d.channels_out > 64 && (d.groups == 1 || p.npg % 128 == 0) ? 128 : 64);
@@ -963,7 +1073,7 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
     if (repack && p.have_weights) pack_for_mfma(p);
     if (direct) {
       if (!direct_geometry(p, want, &p.tpi, &p.halo_rows, &p.ps, &p.halo_bytes, &p.ipt,
-                           p.engine_pref == 3 ? kDirectLdsMax : kDirectLdsAuto, &p.tile_tx, &p.halo_w))
+                           p.engine_pref == kEngineDirect ? kDirectLdsMax : kDirectLdsAuto, &p.tile_tx, &p.halo_w))
         return "bconv2d: the direct matrix-core variant cannot hold this tile's input halo in LDS";
       p.use_direct = true;
     }
@@ -975,8 +1085,8 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
     p.kernel_name = nm;
     // 1x1 stride-1 layers: the streaming kernel on top of the same weight image (the block GEMM stays the
     // fallback for output pointers that are not 16-byte aligned)
-    if ((p.engine_pref == 4 || (p.engine_pref == 0 && p.tile_pref.tm == 0)) && pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj) &&
-        (p.engine_pref == 4 || pointwise_preferred(p, pixels))) {
+    if ((p.engine_pref == kEnginePointwise || (p.engine_pref == kEngineAuto && p.tile_pref.tm == 0)) && pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj) &&
+        (p.engine_pref == kEnginePointwise || pointwise_preferred(p, pixels))) {
       p.use_pointwise = true;
       snprintf(nm, sizeof nm, "bconv2d_pointwise<%s,K%dx64,N%dx32%s>",
                d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked", p.pw_nc, p.pw_nj,
@@ -987,10 +1097,10 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
   }
 
   TileShape chosen{0, 0};
-  if (p.kernel_pref != 2) {
+  if (p.kernel_pref != kKernelGeneral) {
     if (p.tile_pref.tm != 0) {
       if (tiled_supports(p, p.tile_pref.tn)) chosen = p.tile_pref;
-      else if (p.kernel_pref == 1) return "bconv2d: the requested tile cannot run this convolution";
+      else if (p.kernel_pref == kKernelTiled) return "bconv2d: the requested tile cannot run this convolution";
     } else {
       // One wave task = 64*TM pixels x TN channels.  Measured on MI355X
       // (profiles/r01/tile_sweep_v8.jsonl): one pixel per lane wins on every BASELINE layer --
@@ -1014,7 +1124,7 @@ static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
       }
     }
   }
-  if (chosen.tm == 0 && p.kernel_pref == 1)
+  if (chosen.tm == 0 && p.kernel_pref == kKernelTiled)
     return "bconv2d: the tiled kernel cannot run this convolution (grouped, channels per group "
            "not a multiple of the tile)";
 
@@ -1045,7 +1155,7 @@ int max_batch_per_launch(const HostPlan& p) {
   int64_t by_bytes = ((1ll << 31) - 1) / per_image_bytes;
   int64_t by_pixels = ((1ll << 31) - 64 * 4 - 1) / per_image_pixels;
   int64_t b = std::min(by_bytes, by_pixels);
-  if (p.engine_pref != 1 && mfma_supported(p)) {
+  if (p.engine_pref != kEngineValu && mfma_supported(p)) {
     // the FP4 workspace is 4x the bitpacked input (plus the halo) and is indexed in
     // 16-byte chunks by a 32-bit counter
     const int cpad = ceil_div(p.d.channels_in, 64) * 64;

@@ -39,7 +39,55 @@ struct MfmaCfg {
 // The instantiated shapes, by block tile (pixels x channels).
 const MfmaCfg* mfma_cfg_by_tile(int bm, int bn);
 
-struct HostPlan {
+// The option "engine" (include/lce_hip.h); the order is the order of its words
+enum EnginePref {
+  kEngineAuto = 0,
+  kEngineValu,        // xor-popcount
+  kEngineMfma,        // FP4 workspace GEMM; this and every engine below runs on the matrix cores
+  kEngineDirect,      // LDS halo
+  kEnginePointwise,   // 1x1 streaming kernel (lce_kernels_pointwise.h)
+  kEngineStream,      // weight-stationary persistent kernel (lce_kernels_stream.h)
+  kEngineWstream,     // weight-streaming kernel for short launches (lce_kernels_wstream.h)
+};
+// The option "kernel": the xor-popcount engine's kernels
+enum KernelPref { kKernelAuto = 0, kKernelTiled, kKernelGeneral };
+
+// What a caller asks of the planner: the tuning and testing options of lce_hip_bconv2d_plan_set_option, parsed by set_plan_option.
+// HostPlan derives from it, so the planner reads them as plain fields of the plan (p.engine_pref).
+struct PlanOptions {
+  int engine_pref = kEngineAuto;
+  int kernel_pref = kKernelAuto;
+  TileShape tile_pref{0, 0};               // {0,0} = auto
+  int tile2d_pref = 0;                     // tuning aid: 0 auto, 1 always when it fits, 2 never
+  int phase = 0;                           // profiling aid: 0 all, 1 expand_fp4 only, 2 GEMM only
+  int epilogue_pref = 0;                   // float/int8 epilogue: 0 auto, 1 per-tile transpose, 2 joint transpose
+  int pw_tiles_pref = 0;                   // tuning aid: 32-pixel tiles per wave (0 = auto)
+  int pw_nj_pref = 0;                      // tuning aid: 32-channel tiles per block (0 = auto, 1, 2, 4)
+  bool int8_exact_pref = false;            // testing aid (int8_rounding=exact): never take the floor instances
+  int stream_rows_pref = 0;                // tuning aid: output rows per segment (0 = auto)
+  int stream_noflat = 0;                   // testing aid: never cut pixel blocks across a block's segments
+  int stream_phases_pref = 0;              // tuning aid: pixel phases per block (0 = auto, else 1, 2 or 4: 4 / phases channel slices)
+  // testing aid: -1 auto, 0 never, else the strip width (a multiple of 32 that divides the output width)
+  int stream_strip_pref = -1;
+  // 1: a block's segments are gx apart (interleaved runs: a compact, moving write window), 0: consecutive, -1: the cost estimate decides
+  int stream_interleave_pref = -1;
+  // blocks per CU the launch is planned for: 0 = the cost estimate decides (1, or 2 where the instance is compiled for two and both
+  // blocks' LDS fit), 1 / 2 = tuning aid (stream_blocks_per_cu)
+  int stream_occ_pref = 0;
+  // tuning aids of the weight-streaming kernel: most pixel blocks per block (0 = 4), images per group (0 = the cost model's choice)
+  int ws_blocks_pref = 0, ws_images_pref = 0;
+  bool cus_forced = false;                 // HostPlan::num_cus was set through "compute_units" (the C ABI leaves it alone then)
+};
+
+// What an option change makes stale (set_plan_option's *invalidates)
+enum : unsigned {
+  kStaleSelection = 1,                     // the kernel choice
+  kStaleUpload = 2,                        // the plan's device buffers
+  kStalePacked = 4,                        // the xor-popcount kernels' packed operands (HostPlan::packed)
+  kStaleWeightImage = 8,                   // the FP4 weight image (HostPlan::wq)
+};
+
+struct HostPlan : PlanOptions {
   lce_hip_bconv2d_desc d{};
   // inferred by Prepare (tflite/kernels/bconv2d.cc:203-210)
   int out_h = 0, out_w = 0, pad_h = 0, pad_w = 0;
@@ -59,8 +107,6 @@ struct HostPlan {
   std::vector<float> zero_pad_cache;       // zero_padding_correction.h:39-176
 
   // kernel selection
-  int kernel_pref = 0;                     // 0 auto, 1 tiled, 2 general
-  TileShape tile_pref{0, 0};               // {0,0} = auto
   bool use_tiled = false;
   TileShape tile{0, 0};
   int ch = 1;                              // activation words per vector load
@@ -68,21 +114,12 @@ struct HostPlan {
   std::string kernel_name;
 
   // matrix-core engine (lce_kernels_mfma.h)
-  int engine_pref = 0;                     // 0 auto, 1 valu (xor-popcount), 2 mfma (FP4 workspace GEMM), 3 direct (LDS halo),
-                                           // 4 pointwise (1x1 streaming kernel, lce_kernels_pointwise.h),
-                                           // 5 stream (weight-stationary persistent kernel, lce_kernels_stream.h),
-                                           // 6 wstream (weight-streaming kernel for short launches, lce_kernels_wstream.h)
   bool use_direct = false;                 // with use_mfma: the LDS-halo variant, no workspace
   int tpi = 0, halo_rows = 0, ps = 0, halo_bytes = 0, ipt = 1;  // direct-variant geometry
   int tile_tx = 0, halo_w = 0;             // ... 2-D tiles: tiles across the image (0 = strip tiles), halo width in pixels
-  int tile2d_pref = 0;                     // tuning aid: 0 auto, 1 always when it fits, 2 never
-  int phase = 0;                           // profiling aid: 0 all, 1 expand_fp4 only, 2 GEMM only
-  int epilogue_pref = 0;                   // float/int8 epilogue: 0 auto, 1 per-tile transpose, 2 joint transpose
   bool use_mfma = false;
   bool use_pointwise = false;              // with use_mfma: the 1x1 streaming kernel runs instead of the block GEMM
   int pw_nc = 0, pw_nj = 0;                // its K-steps and 32-channel tiles per block
-  int pw_tiles_pref = 0;                   // tuning aid: 32-pixel tiles per wave (0 = auto)
-  int pw_nj_pref = 0;                      // tuning aid: 32-channel tiles per block (0 = auto, 1, 2, 4)
   MfmaCfg mfma{0, 0, 0, 0};                // chosen block shape
   int cpad = 0, hp = 0, wp = 0, npad = 0;  // workspace geometry / padded channel count
   int kch = 0;                             // K-steps (64-channel chunks) per filter tap that a block runs: cpad/64,
@@ -92,8 +129,7 @@ struct HostPlan {
   bool int8_floor_ok = false;
   // channels that the proof of the one-instruction forms gave neighbouring parameters (lce_plan.cpp, prepare_int8_epilogue)
   int int8_bias_adjusted = 0;
-  bool int8_exact_pref = false;            // testing aid (int8_rounding=exact): never take the floor instances
-  std::vector<uint8_t> wq;                 // FP4 weights [KS][Npad][32 bytes]
+  std::vector<uint8_t> wq;                // FP4 weights [KS][Npad][32 bytes]
   // 0: K-major [K-step][K-half][Npad][16 B]; 1: tile-major [Npad/32][K-step][K-half][32][16 B] (wstream)
   int wq_layout = 0;
   std::vector<float> mul_q, bias_q, thr_q; // Npad entries
@@ -101,22 +137,12 @@ struct HostPlan {
   // weight-stationary streaming kernel (lce_kernels_stream.h); with use_mfma
   bool use_stream = false;
   int num_cus = 256;                       // compute units of the device (the C ABI fills it in; the stream kernel's grid)
-  int stream_rows_pref = 0;                // tuning aid: output rows per segment (0 = auto)
-  int stream_noflat = 0;                   // testing aid: never cut pixel blocks across a block's segments
-  int stream_phases_pref = 0;              // tuning aid: pixel phases per block (0 = auto, else 1, 2 or 4: 4 / phases channel slices)
   int st_rs = 0, st_spi = 0, st_srs = 0, st_pbs = 0, st_pph_log = 0, st_ny = 1, st_qg = 0, st_ipr = 0;
   int st_pitch = 0;                          // bytes per ring row slot
   // column strips of wide images: strips per image, row segments per image, output columns per strip
   int st_nstrip = 1, st_rseg = 0, st_wso = 0;
-  // testing aid: -1 auto, 0 never, else the strip width (a multiple of 32 that divides the output width)
-  int stream_strip_pref = -1;
-  // 1: a block's segments are gx apart (interleaved runs: a compact, moving write window), 0: consecutive, -1: the cost estimate decides
-  int stream_interleave_pref = -1;
   int st_gstr = 1;                           // the planned segment stride of a block's run (1: consecutive segments)
-  // blocks per CU the launch is planned for: 0 = the cost estimate decides (1, or 2 where the instance is compiled for two and both
-  // blocks' LDS fit), 1 / 2 = tuning aid (stream_blocks_per_cu)
-  int stream_occ_pref = 0;
-  int st_occ = 1;                            // ... as planned
+  int st_occ = 1;                            // blocks per CU the launch is planned for
   // 1: 32-pixel blocks are cut from the concatenated pixels of a block's segments (whole small images)
   int st_flat = 0;
   int st_nq = 0;                             // pixel blocks of a full block's stream (rows of the context table)
@@ -129,8 +155,6 @@ struct HostPlan {
   // images per group, blocks per group, pixel blocks / pixels per group, most pixel blocks per block, grid.y
   int ws_ipb = 0, ws_parts = 0, ws_nq = 0, ws_npxg = 0, ws_nb = 0, ws_ny = 1;
   int ws_hp = 0, ws_wp = 0, ws_pitch = 0, ws_img_pitch = 0, ws_qg = 0, ws_lds_images = 0;   // LDS image geometry
-  // tuning aids: most pixel blocks per block (0 = 4), images per group (0 = the cost model's choice)
-  int ws_blocks_pref = 0, ws_images_pref = 0;
   int ws_occupancy = 1;                      // blocks that fit a CU's LDS side by side (the kernel is built for two)
   uint32_t ws_tab_part = 0, ws_tab_ctx = 0;  // byte offsets inside st_tabs
   int64_t ws_cost = 0;                       // the planner's cycle estimate of a launch (plan_wstream)
@@ -155,6 +179,16 @@ struct HostPlan {
 
 // Returns "" when the descriptor is acceptable, otherwise the message Prepare would log.
 std::string validate_and_infer(HostPlan& p);
+
+// One option of lce_hip_bconv2d_plan_set_option (include/lce_hip.h) into p's PlanOptions (compute_units: also p.num_cus).  Returns "" or the
+// refusal, which leaves the plan as it was; *invalidates = the kStale* bits of what the change makes stale.
+std::string set_plan_option(HostPlan& p, const char* key, const char* value, unsigned* invalidates);
+
+// The selected kernel has int8 instances with the one-instruction forms: the streaming, weight-streaming and pointwise kernels (the
+// block GEMM and the xor-popcount engine run the reference's sequence whatever the proof said) ...
+inline bool int8_forms_kernel(const HostPlan& p) { return p.use_mfma && (p.use_stream || p.use_wstream || p.use_pointwise); }
+// ... and this plan runs them: the proof held and int8_rounding is not "exact" (prepare_int8_epilogue)
+inline bool int8_one_instruction_forms(const HostPlan& p) { return int8_forms_kernel(p) && p.int8_floor_ok; }
 
 // OneTimeSetup: fold multiplier/bias/clamps (double arithmetic, float storage), keep
 // thresholds, compute the zero-padding correction cache.

@@ -130,16 +130,24 @@ class GuardedBytes {
 };
 
 std::string g_err;
-void* g_sign_out = nullptr;   // second output of the next hostsim_bconv2d call (float output, matrix-core engine)
-int g_num_cus = 256;          // what the streaming kernel's planner takes for the device's CU count
-int g_stream_rows = 0;        // its segment size (0 = auto)
-int g_stream_phases = 0;      // its pixel phases per block (0 = auto)
-int g_stream_strip = -1;      // its column strips (-1 auto, 0 never, else the width)
-int g_stream_interleave = 0;  // its segment -> block map (1: interleaved runs)
-int g_stream_occ = 0;         // its blocks per CU (0 = the estimate decides, 1, 2)
-int g_pw_nj = 0;              // the pointwise kernel's 32-channel tiles per block (0 = auto)
+int g_last_int8_floor = -1;   // the last convolution's plan: 1 = its int8 rounding ran as floor(x + 0.5), 0 = round-half-away, -1 = not an int8 plan of the kernels that have that form
 int g_last_int8_adjusted = 0;   // ... and the number of channels whose bias its floor-rounding proof adjusted
-int g_last_int8_floor = -1;   // the last convolution's plan: 1 = its int8 rounding ran as floor(x + 0.5), 0 = round-half-away, -1 = not an int8 matrix-core plan
+
+// "key=value;key=value;...": each pair through the C ABI's parser (set_plan_option, include/lce_hip.h).  "" or the first refusal.
+std::string apply_options(HostPlan& h, const char* options) {
+  const std::string s = options ? options : "";
+  for (size_t pos = 0; pos < s.size();) {
+    const size_t end = std::min(s.find(';', pos), s.size());
+    const std::string item = s.substr(pos, end - pos);
+    pos = end + 1;
+    const size_t eq = item.find('=');
+    if (eq == std::string::npos) return "hostsim: option '" + item + "' is not key=value";
+    unsigned stale = 0;   // (a fresh plan: nothing is stale)
+    const std::string err = set_plan_option(h, item.substr(0, eq).c_str(), item.c_str() + eq + 1, &stale);
+    if (!err.empty()) return err;
+  }
+  return "";
+}
 
 }  // namespace
 
@@ -147,37 +155,21 @@ extern "C" {
 
 const char* hostsim_last_error() { return g_err.c_str(); }
 float hostsim_int8_below_threshold(int32_t zero_point) { return int8_below_threshold(zero_point); }
-void hostsim_set_sign_output(void* words) { g_sign_out = words; }
-void hostsim_set_stream(int num_cus, int rows) { g_num_cus = num_cus; g_stream_rows = rows; }
-void hostsim_set_stream_phases(int phases) { g_stream_phases = phases; }
-void hostsim_set_stream_strip(int width) { g_stream_strip = width; }
-void hostsim_set_stream_interleave(int on) { g_stream_interleave = on; }
-void hostsim_set_stream_blocks_per_cu(int n) { g_stream_occ = n; }
-void hostsim_set_pointwise(int channel_tiles) { g_pw_nj = channel_tiles; }
 int hostsim_last_int8_floor() { return g_last_int8_floor; }
 int hostsim_last_int8_adjusted() { return g_last_int8_adjusted; }
 
-// kernel_pref: 0 auto, 1 tiled, 2 general; tm/tn 0 = auto; max_batch 0 = planner's choice
-// engine_pref: 0 auto, 1 valu, 2 mfma
-int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const int32_t* filter, const float* post_mul,
-                    const float* post_bias, const int32_t* thresholds, const int32_t* input,
-                    void* output, int kernel_pref, int tm, int tn, int max_batch, char* name_out,
-                    int name_len, int engine_pref) {
+// options: the plan's options as "key=value;..." (lce_hip_bconv2d_plan_set_option's keys and values); sign_out: the float / int8
+// output's sign words (the second output of run_dual), may be null; max_batch 0 = the planner's launch size
+int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const char* options, const int32_t* filter, const float* post_mul,
+                    const float* post_bias, const int32_t* thresholds, const int32_t* input, void* output, void* sign_out,
+                    int max_batch, char* name_out, int name_len) {
   HostPlan h;
   h.d = *desc;
   std::string err = validate_and_infer(h);
   if (!err.empty()) { g_err = err; return 1; }
   fold_parameters(h, filter, post_mul, post_bias, thresholds);
-  h.engine_pref = engine_pref;
-  h.num_cus = g_num_cus;
-  h.stream_rows_pref = g_stream_rows;
-  h.stream_phases_pref = g_stream_phases;
-  h.stream_strip_pref = g_stream_strip;
-  h.stream_interleave_pref = g_stream_interleave;
-  h.stream_occ_pref = g_stream_occ;
-  h.pw_nj_pref = g_pw_nj;
-  h.kernel_pref = kernel_pref;
-  h.tile_pref = TileShape{tm, tn};
+  err = apply_options(h, options);
+  if (!err.empty()) { g_err = err; return 1; }
   int chunk = max_batch_per_launch(h);
   if (max_batch > 0) chunk = std::min(chunk, max_batch);
   err = select_kernel(h, (int64_t)chunk * h.out_h * h.out_w);
@@ -187,7 +179,7 @@ int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const int32_t* filter, con
     name_out[name_len - 1] = 0;
   }
   g_last_int8_adjusted = h.int8_bias_adjusted;
-  g_last_int8_floor = h.d.dst_type == LCE_HIP_I8 && h.use_mfma && (h.use_stream || h.use_wstream || h.use_pointwise) ? (h.int8_floor_ok ? 1 : 0) : -1;
+  g_last_int8_floor = h.d.dst_type == LCE_HIP_I8 && int8_forms_kernel(h) ? int8_one_instruction_forms(h) : -1;
   // the padded tables get the same slack as the device uploads
   auto slack_u = [](std::vector<uint32_t> v) { v.resize(v.size() + 16, 0u); return v; };
   const std::vector<uint32_t> packed = slack_u(h.packed), filt = slack_u(h.filter);
@@ -203,7 +195,7 @@ int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const int32_t* filter, con
     void* out = (char*)output + (size_t)b0 * out_img_bytes;
     if (h.use_mfma && h.use_wstream) {
       const WsArgs G = make_ws_args(h, nb);
-      uint32_t* sgn = g_sign_out && h.d.dst_type != LCE_HIP_BITPACKED ? (uint32_t*)g_sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr;
+      uint32_t* sgn = sign_out && h.d.dst_type != LCE_HIP_BITPACKED ? (uint32_t*)sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr;
       wstream_fn fn = lookup_wstream(h.d.dst_type, stream_chunks(h.d), h.ws_nb, sgn != nullptr, h.int8_floor_ok);
       if (!fn) { g_err = "no kernel instance for " + h.kernel_name; return 3; }
       std::vector<uint8_t> wq = h.wq;
@@ -215,7 +207,7 @@ int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const int32_t* filter, con
       });
     } else if (h.use_mfma && h.use_stream) {
       const StreamArgs G = make_stream_args(h, nb);
-      uint32_t* sgn = g_sign_out && h.d.dst_type != LCE_HIP_BITPACKED ? (uint32_t*)g_sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr;
+      uint32_t* sgn = sign_out && h.d.dst_type != LCE_HIP_BITPACKED ? (uint32_t*)sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr;
       stream_fn fn = lookup_stream(h.d.dst_type, stream_chunks(h.d), stream_fast(G), stream_clamps(G), sgn != nullptr, G.NSTRIP > 1, h.int8_floor_ok);
       if (!fn) { g_err = "no kernel instance for " + h.kernel_name; return 3; }
       std::vector<uint8_t> wq = h.wq;
@@ -234,7 +226,7 @@ int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const int32_t* filter, con
       // a small grid: waves loop over several tiles
       launch_block_lockstep(std::min((P.tiles + 3) / 4, 2), h.d.channels_out / (32 * h.pw_nj), 256, (size_t)(4 * h.pw_nj * 4096), [&] {
         fn(P, in, wq.data(), h.mul_q.data(), h.bias_q.data(), h.thr_q.data(), out,
-           g_sign_out ? (uint32_t*)g_sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr);
+           sign_out ? (uint32_t*)sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr);
       });
     } else if (h.use_mfma) {
       mfma_fn fn = lookup_mfma(h.d.dst_type, h.mfma.bm(), h.mfma.bn(), h.zero_pad_mode == lce::kZeroPadCorrection,
@@ -246,7 +238,7 @@ int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const int32_t* filter, con
       const int bm = h.mfma.bm(), bn = h.mfma.bn();
       if (h.use_direct) {
         launch_block_lockstep(h.ipt > 1 ? (nb + h.ipt - 1) / h.ipt : nb * h.tpi, h.npad / bn, h.mfma.threads(), (size_t)h.mfma.direct_lds_bytes(h.halo_bytes), [&] {
-          fn(A, G, (const uint8_t*)in, wq.data(), h.mul_q.data(), h.bias_q.data(), h.thr_q.data(), zpc, out, g_sign_out ? (uint32_t*)g_sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr);
+          fn(A, G, (const uint8_t*)in, wq.data(), h.mul_q.data(), h.bias_q.data(), h.thr_q.data(), zpc, out, sign_out ? (uint32_t*)sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr);
         });
         continue;
       }
@@ -254,7 +246,7 @@ int hostsim_bconv2d(const lce_hip_bconv2d_desc* desc, const int32_t* filter, con
       std::vector<lce_dev::u32x4> work(ws / 16 + 16);
       launch_sequential(3, 1, 256, [&] { expand_fp4<>(in, work.data(), G, (uint64_t)G.NPIX * (uint64_t)((G.CPW + 3) / 4)); });
       launch_block_lockstep((A.M + bm - 1) / bm, h.npad / bn, h.mfma.threads(), (size_t)h.mfma.lds_bytes(), [&] {
-        fn(A, G, (const uint8_t*)work.data(), wq.data(), h.mul_q.data(), h.bias_q.data(), h.thr_q.data(), zpc, out, g_sign_out ? (uint32_t*)g_sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr);
+        fn(A, G, (const uint8_t*)work.data(), wq.data(), h.mul_q.data(), h.bias_q.data(), h.thr_q.data(), zpc, out, sign_out ? (uint32_t*)sign_out + (size_t)b0 * h.out_h * h.out_w * h.wout : nullptr);
       });
     } else if (h.use_tiled) {
       tiled_fn fn = lookup_tiled(h.d.dst_type, h.tile.tm, h.tile.tn, h.ch);
@@ -377,17 +369,12 @@ int hostsim_cost_count() { return cost_constant_count(); }
 const char* hostsim_cost_name(int i) { return cost_constant_name(i); }
 double hostsim_cost_get(int i) { return get_cost_constant(i); }
 int hostsim_cost_set(int i, double v) { return set_cost_constant(i, v) ? 0 : 1; }
-// The estimate (us) and kernel name of the plan that select_kernel makes of `desc` under the given preferences (engine_pref as
-// hostsim_bconv2d; stream_rows / interleave: the streaming kernel's segment options); < 0: the configuration cannot be planned.
-double hostsim_plan_estimate(const lce_hip_bconv2d_desc* desc, int engine_pref, int stream_rows, int interleave, int num_cus,
-                             char* name_out, int name_len) {
+// The estimate (us) and kernel name of the plan that select_kernel makes of `desc` under the given options (as hostsim_bconv2d's);
+// < 0: the configuration cannot be planned.
+double hostsim_plan_estimate(const lce_hip_bconv2d_desc* desc, const char* options, char* name_out, int name_len) {
   HostPlan h;
   h.d = *desc;
-  if (!validate_and_infer(h).empty()) return -2.0;
-  h.engine_pref = engine_pref;
-  h.num_cus = num_cus;
-  h.stream_rows_pref = stream_rows;
-  h.stream_interleave_pref = interleave;
+  if (!validate_and_infer(h).empty() || !apply_options(h, options).empty()) return -2.0;
   const int chunk = max_batch_per_launch(h);
   if (!select_kernel(h, (int64_t)chunk * h.out_h * h.out_w).empty()) return -3.0;
   if (name_out && name_len > 0) {

@@ -58,10 +58,23 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def option_string(options: dict) -> bytes:
+    """{"engine": "stream", "compute_units": 4} -> b"engine=stream;compute_units=4": plan options as hostsim_bconv2d and
+    hostsim_plan_estimate take them (the keys and values of lce_hip_bconv2d_plan_set_option, include/lce_hip.h)."""
+    return ";".join("%s=%s" % kv for kv in options.items()).encode()
+
+
+# Where a plan made here differs from a C-ABI plan by default: consecutive segments on the streaming kernel unless a test asks for
+# interleaved runs (a C-ABI plan's stream_interleave is "auto": the cost estimate decides).
+DEFAULT_OPTIONS = {"stream_interleave": 0}
+
+
 def bconv2d(spec: O.ConvSpec, dst_type: int, inp, filt, post_mul=None, post_bias=None,
             thresholds=None, out_scale=1.0, out_zero_point=0, kernel="auto", tile=(0, 0),
-            max_batch=0, engine="valu", sign_words=None):
-    """sign_words: an int32 array [B,OH,OW,ceil(Cout/32)] that receives the float output's sign bits (the
+            max_batch=0, engine="valu", sign_words=None, options=None):
+    """options: plan options by key, e.g. {"compute_units": 4, "stream_rows": 2}, on top of DEFAULT_OPTIONS and of engine / kernel /
+    tile (shorthands for three of them; tile (0, 0) = auto).
+    sign_words: an int32 array [B,OH,OW,ceil(Cout/32)] that receives the float output's sign bits (the
     matrix-core kernels' second output; stays untouched when the chosen kernel variant cannot write it)."""
     inp = np.ascontiguousarray(inp, np.int32)
     filt = np.ascontiguousarray(filt, np.int32)
@@ -73,39 +86,12 @@ def bconv2d(spec: O.ConvSpec, dst_type: int, inp, filt, post_mul=None, post_bias
         else np.full(spec.output_shape(dst_type), -7, dtype=dt)
     name = C.create_string_buffer(128)
     d = make_desc(spec, dst_type, out_scale, out_zero_point)
-    lib().hostsim_set_sign_output(_p(sign_words))
-    rc = lib().hostsim_bconv2d(C.byref(d), _p(filt), _p(mul), _p(bias), _p(thr), _p(inp), _p(out),
-                               {"auto": 0, "tiled": 1, "general": 2}[kernel], tile[0], tile[1],
-                               max_batch, name, 128, {"auto": 0, "valu": 1, "mfma": 2, "direct": 3, "pointwise": 4, "stream": 5, "wstream": 6}[engine])
-    lib().hostsim_set_sign_output(None)
+    opts = {**DEFAULT_OPTIONS, "engine": engine, "kernel": kernel, "tile": "%dx%d" % tuple(tile) if tile[0] else "auto", **(options or {})}
+    rc = lib().hostsim_bconv2d(C.byref(d), option_string(opts), _p(filt), _p(mul), _p(bias), _p(thr), _p(inp), _p(out),
+                               _p(sign_words), max_batch, name, 128)
     if rc != 0:
         raise RuntimeError(lib().hostsim_last_error().decode())
     return out, name.value.decode()
-
-
-def set_stream(num_cus: int = 256, rows: int = 0):
-    """What the streaming kernel's planner takes for the device's CU count, and its segment size (0 = auto)."""
-    lib().hostsim_set_stream(int(num_cus), int(rows))
-
-
-def set_stream_phases(phases: int = 0):
-    """The streaming kernel's pixel phases per block (0 = auto; 2 / 4: fewer channel slices per block, more blocks in y)."""
-    lib().hostsim_set_stream_phases(int(phases))
-
-
-def set_stream_strip(width: int = -1):
-    """The streaming kernel's column strips for wide images: -1 auto, 0 never, else the strip's width in output columns."""
-    lib().hostsim_set_stream_strip(int(width))
-
-
-def set_stream_interleave(on: int = 0):
-    """1: a block of the streaming kernel owns segments b, b + grid, ... (interleaved runs); 0: consecutive ones."""
-    lib().hostsim_set_stream_interleave(int(on))
-
-
-def set_stream_blocks_per_cu(n: int = 0):
-    """The streaming kernel's resident blocks per CU: 0 = the cost estimate decides, 1, 2 (2: the bitpacked 64-input-channel instance)."""
-    lib().hostsim_set_stream_blocks_per_cu(int(n))
 
 
 def last_int8_floor() -> int:
@@ -117,11 +103,6 @@ def last_int8_floor() -> int:
 def last_int8_adjusted() -> int:
     """Channels of the last int8 plan that the planner's proof of the one-instruction forms gave neighbouring parameters (lce_plan.cpp, prepare_int8_epilogue)."""
     return int(lib().hostsim_last_int8_adjusted())
-
-
-def set_pointwise(channel_tiles: int = 0):
-    """The pointwise kernel's 32-channel tiles per block (0 = auto: 1 for the small launches of these tests)."""
-    lib().hostsim_set_pointwise(int(channel_tiles))
 
 
 def bitpack(x: np.ndarray, zero_point: int = 0, force_rows: bool = False) -> np.ndarray:

@@ -214,6 +214,44 @@ def test_forced_strips_on_another_bank_say_so():
     assert "256-channel filter bank only" in amd.lib().lce_hip_last_error().decode()
 
 
+OPTION_PINS = [
+    # key, an accepted value, a refused value, the refusal (after "plan_set_option: ")
+    ("engine", "wstream", "gpu", "engine must be auto|valu|mfma|direct|pointwise|stream|wstream"),
+    ("kernel", "general", "tile", "kernel must be auto|tiled|general"),
+    ("tile", "128x64", "3x7", "tile must be auto, a xor-popcount tile (4x16|2x32|2x16|1x32|1x16) or, with engine=mfma, a block tile "
+                             "(256x256|256x128|512x64|128x256|128x128|256x64|128x64)"),
+    ("tile2d", "off", "", "tile2d must be auto|on|off"),
+    ("phase", "expand", "auto", "phase must be all|expand|gemm"),
+    ("epilogue", "wide", "all", "epilogue must be auto|tile|wide"),
+    ("pointwise_tiles", "8", "9", "pointwise_tiles must be 0 (auto) .. 8"),
+    ("pointwise_channels", "128", "48", "pointwise_channels must be 0 (auto), 32, 64 or 128"),
+    ("int8_rounding", "exact", "floor", "int8_rounding must be auto or exact"),
+    ("stream_rows", "3abc", "-1", "stream_rows must be 0 (auto) or a positive row count"),    # (atoi: "3abc" is 3)
+    ("stream_strip", "-1", "-2", "stream_strip must be -1 (auto), 0 (whole rows) or a strip width"),
+    ("stream_interleave", "auto", "2", "stream_interleave must be auto, 0 or 1"),
+    ("stream_blocks_per_cu", "2", "0", "stream_blocks_per_cu must be auto, 1 or 2"),
+    ("stream_flat", "0", "auto", "stream_flat must be 0 or 1"),
+    ("stream_pixel_phases", "4", "3", "stream_pixel_phases must be 0 (auto), 1, 2 or 4"),
+    ("wstream_blocks", "0", "5", "wstream_blocks must be 0 (auto) .. 4, wstream_images 0 (auto) or a positive count"),
+    ("wstream_images", "9", "auto", "wstream_blocks must be 0 (auto) .. 4, wstream_images 0 (auto) or a positive count"),
+    ("compute_units", "1", "0", "compute_units must be positive"),
+]
+
+
+@pytest.mark.parametrize("key,good,bad,why", OPTION_PINS, ids=[p[0] for p in OPTION_PINS])
+def test_every_plan_option_takes_its_values_and_refuses_others_by_name(key, good, bad, why):
+    plan = amd.Bconv2dPlan(amd.ConvParams(2, 14, 14, 256, 3, 3, 256, padding=amd.PADDING_SAME, pad_values=1, dst_type=amd.I8,
+                                          out_scale=0.5))
+    plan.set_option(key, good)
+    with pytest.raises(amd.LceHipError) as e:
+        plan.set_option(key, bad)
+    assert e.value.code == amd.ERR_INVALID and e.value.message == "plan_set_option: " + why
+    with pytest.raises(amd.LceHipError) as e:
+        plan.set_option(key + "s", good)
+    assert e.value.message == "plan_set_option: unknown key '%ss'" % key
+    plan.close()
+
+
 def test_planner_choice_for_run_dual():
     """lce_hip_bconv2d_plan_kernel_name_dual names the kernel run_dual launches: since round 5 the same kernel as run's (the cost
     estimate does not depend on the kind of call; round 4's twin plan is gone)."""

@@ -190,13 +190,13 @@ def test_round_sat_i8_every_float():
 MFMA_TILES = [(256, 256), (256, 128), (512, 64), (128, 256), (128, 128), (256, 64), (128, 64)]
 
 
-def _run_all_dst_mfma(spec, seed, tile=(0, 0), max_batch=0, engine="mfma"):
+def _run_all_dst_mfma(spec, seed, tile=(0, 0), max_batch=0, engine="mfma", options=None):
     x, w, mul, bias = synth.conv_inputs(spec, seed, negative_mul_fraction=0.2)
     zero_pad = spec.padding == O.PADDING_SAME and spec.pad_values == 0
     names = []
     if not (zero_pad and spec.semantics == O.SEM_OPTIMIZED and spec.activation != O.ACT_NONE):
         want = O.bconv2d(spec, O.DST_F32, x, w, mul, bias)
-        got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, tile=tile, max_batch=max_batch, engine=engine)
+        got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, tile=tile, max_batch=max_batch, engine=engine, options=options)
         assert np.array_equal(got.view(np.int32), want.view(np.int32)), name
         names.append(name)
     if zero_pad and spec.semantics == O.SEM_OPTIMIZED:
@@ -204,7 +204,7 @@ def _run_all_dst_mfma(spec, seed, tile=(0, 0), max_batch=0, engine="mfma"):
     scale, zp = synth.int8_quant_params(seed)
     want = O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=float(scale), out_zero_point=zp)
     got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=float(scale), out_zero_point=zp,
-                          tile=tile, max_batch=max_batch, engine=engine)
+                          tile=tile, max_batch=max_batch, engine=engine, options=options)
     assert np.array_equal(got, want), name
     names.append(name)
     thr = O.thresholds_converter(spec, mul, bias)
@@ -212,7 +212,8 @@ def _run_all_dst_mfma(spec, seed, tile=(0, 0), max_batch=0, engine="mfma"):
     thr[1::7] = np.iinfo(np.int32).min
     thr[2::11] = -1
     want = O.bconv2d(spec, O.DST_BITPACKED, x, w, thresholds=thr)
-    got, name = H.bconv2d(spec, O.DST_BITPACKED, x, w, thresholds=thr, tile=tile, max_batch=max_batch, engine=engine)
+    got, name = H.bconv2d(spec, O.DST_BITPACKED, x, w, thresholds=thr, tile=tile, max_batch=max_batch, engine=engine,
+                          options=options)
     assert np.array_equal(got, want), name
     names.append(name)
     return names
@@ -267,19 +268,17 @@ def test_pointwise_streaming_kernel(cin, cout, act):
     widest = 4 if t % 4 == 0 else 2 if t % 2 == 0 else 1
     if cin > 256:
         widest = min(widest, 2)
-    try:
-        for k, (b, h, w_, mb) in enumerate(((3, 5, 7, 0), (2, 9, 11, 0), (5, 4, 4, 2))):
-            for padding in (O.PADDING_VALID, O.PADDING_SAME):
-                # the launch-size rule gives these small launches at most 64 channels per block: ask for the widest and for 32 too
-                H.set_pointwise(widest if (k + padding) % 2 == 0 else 1 if k == 1 else 0)
-                spec = O.ConvSpec(b, h, w_, cin, 1, 1, cout, padding=padding, pad_values=1, activation=act)
-                names = _run_all_dst_mfma(spec, seed=cin + 3 * cout + b, max_batch=mb, engine="pointwise")
-                assert all(n.startswith("bconv2d_pointwise<") for n in names), names
-                want = widest if (k + padding) % 2 == 0 else 1 if k == 1 else min(widest, 2)
-                for n in names:      # (float output: at most 64 channels per block)
-                    assert "N%dx32" % (min(want, 2) if "<f32" in n else want) in n, (names, want)
-    finally:
-        H.set_pointwise(0)
+    for k, (b, h, w_, mb) in enumerate(((3, 5, 7, 0), (2, 9, 11, 0), (5, 4, 4, 2))):
+        for padding in (O.PADDING_VALID, O.PADDING_SAME):
+            # the launch-size rule gives these small launches at most 64 channels per block: ask for the widest and for 32 too
+            nj = widest if (k + padding) % 2 == 0 else 1 if k == 1 else 0
+            spec = O.ConvSpec(b, h, w_, cin, 1, 1, cout, padding=padding, pad_values=1, activation=act)
+            names = _run_all_dst_mfma(spec, seed=cin + 3 * cout + b, max_batch=mb, engine="pointwise",
+                                      options={"pointwise_channels": 32 * nj})
+            assert all(n.startswith("bconv2d_pointwise<") for n in names), names
+            want = widest if (k + padding) % 2 == 0 else 1 if k == 1 else min(widest, 2)
+            for n in names:      # (float output: at most 64 channels per block)
+                assert "N%dx32" % (min(want, 2) if "<f32" in n else want) in n, (names, want)
 
 
 @pytest.mark.parametrize("cin,cout", [(64, 64), (128, 256), (200, 96), (512, 128), (192, 128)])
@@ -287,16 +286,14 @@ def test_pointwise_streaming_kernel(cin, cout, act):
 def test_pointwise_kernel_strided(cin, cout, stride):
     """Strided 1x1 layers (the shortcut convolutions of ResNet-style binary nets): output pixel (b, oy, ox) reads input
     pixel (b, oy * sh, ox * sw); odd and even extents, VALID and SAME (neither pads a 1x1 filter), batch chunking."""
-    try:
-        for k, (b, h, w_, mb) in enumerate(((3, 5, 7, 0), (2, 10, 12, 0), (4, 9, 4, 1))):
-            for padding in (O.PADDING_VALID, O.PADDING_SAME):
-                H.set_pointwise(0 if k else (2 if (cout // 32) % 2 == 0 else 1))
-                spec = O.ConvSpec(b, h, w_, cin, 1, 1, cout, 1, stride[0], stride[1], padding=padding, pad_values=1,
-                                  activation=O.ACT_RELU if k == 1 else O.ACT_NONE)
-                names = _run_all_dst_mfma(spec, seed=cin + cout + b + stride[0], max_batch=mb, engine="pointwise")
-                assert all(n.startswith("bconv2d_pointwise<") for n in names), names
-    finally:
-        H.set_pointwise(0)
+    for k, (b, h, w_, mb) in enumerate(((3, 5, 7, 0), (2, 10, 12, 0), (4, 9, 4, 1))):
+        for padding in (O.PADDING_VALID, O.PADDING_SAME):
+            nj = 0 if k else (2 if (cout // 32) % 2 == 0 else 1)
+            spec = O.ConvSpec(b, h, w_, cin, 1, 1, cout, 1, stride[0], stride[1], padding=padding, pad_values=1,
+                              activation=O.ACT_RELU if k == 1 else O.ACT_NONE)
+            names = _run_all_dst_mfma(spec, seed=cin + cout + b + stride[0], max_batch=mb, engine="pointwise",
+                                      options={"pointwise_channels": 32 * nj})
+            assert all(n.startswith("bconv2d_pointwise<") for n in names), names
 
 
 def test_pointwise_kernel_refuses_what_it_cannot_run():
@@ -424,13 +421,9 @@ def test_planners_own_choice_on_random_layers(seed):
     batch = int(g.integers(4, 20)) if big else int(g.integers(1, 7))
     spec = O.ConvSpec(batch, h, w_, cin, k, k, cout, 1, sh, sw, 1, 1, padding, pv, act, O.SEM_REFERENCE)
     cus = int(g.choice([4, 8, 16])) if big else int(g.choice([1, 2, 3, 4, 8, 256]))
-    H.set_stream(cus, 0)
-    try:
-        names = _run_all_dst_mfma(spec, 9200 + seed, engine="auto")
-        names += _run_all_dst_mfma(spec, 9300 + seed, max_batch=int(g.integers(1, batch + 1)), engine="auto")
-        assert names
-    finally:
-        H.set_stream(256, 0)
+    names = _run_all_dst_mfma(spec, 9200 + seed, engine="auto", options={"compute_units": cus})
+    names += _run_all_dst_mfma(spec, 9300 + seed, max_batch=int(g.integers(1, batch + 1)), engine="auto", options={"compute_units": cus})
+    assert names
 
 
 @pytest.mark.parametrize("engine", ["mfma", "direct"])
@@ -603,15 +596,12 @@ def test_stream_kernel(shape):
     b, h, w_, cin, cout, st, pad, act, cus, rows = shape
     padding, pad_values = PADS[pad]
     spec = O.ConvSpec(b, h, w_, cin, 3, 3, cout, 1, st[0], st[1], 1, 1, padding, pad_values, act, O.SEM_REFERENCE)
-    H.set_stream(cus, rows)
-    try:
-        for mb in (0, 2):
-            names = _run_all_dst_mfma(spec, seed=cin + 7 * cout + b, max_batch=mb, engine="stream")
-            assert all(n.startswith("bconv2d_stream<") for n in names), names
-            if rows:
-                assert all(",rows%d>" % rows in n for n in names), names
-    finally:
-        H.set_stream(256, 0)
+    for mb in (0, 2):
+        names = _run_all_dst_mfma(spec, seed=cin + 7 * cout + b, max_batch=mb, engine="stream",
+                                  options={"compute_units": cus, "stream_rows": rows})
+        assert all(n.startswith("bconv2d_stream<") for n in names), names
+        if rows:
+            assert all(",rows%d>" % rows in n for n in names), names
 
 
 INTERLEAVED_SHAPES = [
@@ -633,19 +623,12 @@ def test_stream_kernel_interleaved_runs(shape):
     b, h, w_, cin, cout, st, pad, act, cus, rows, wso, chunks = shape
     padding, pad_values = PADS[pad]
     spec = O.ConvSpec(b, h, w_, cin, 3, 3, cout, 1, st[0], st[1], 1, 1, padding, pad_values, act, O.SEM_REFERENCE)
-    H.set_stream(cus, rows)
-    H.set_stream_strip(wso)
-    H.set_stream_interleave(1)
-    try:
-        for mb in chunks:
-            names = _run_all_dst_mfma(spec, seed=cin + 5 * cout + b, max_batch=mb, engine="stream")
-            assert all(n.startswith("bconv2d_stream<") for n in names), names
-            if mb == 0:     # (a chunk so small that every block owns ONE segment has nothing to interleave)
-                assert all(",il>" in n or ",il," in n for n in names), names      # (",il,x2>": two blocks per CU, bitpacked 64-channel bank)
-    finally:
-        H.set_stream(256, 0)
-        H.set_stream_strip(-1)
-        H.set_stream_interleave(0)
+    for mb in chunks:
+        names = _run_all_dst_mfma(spec, seed=cin + 5 * cout + b, max_batch=mb, engine="stream",
+                                  options={"compute_units": cus, "stream_rows": rows, "stream_strip": wso, "stream_interleave": 1})
+        assert all(n.startswith("bconv2d_stream<") for n in names), names
+        if mb == 0:     # (a chunk so small that every block owns ONE segment has nothing to interleave)
+            assert all(",il>" in n or ",il," in n for n in names), names      # (",il,x2>": two blocks per CU, bitpacked 64-channel bank)
 
 
 @pytest.mark.parametrize("shape", [
@@ -667,21 +650,15 @@ def test_stream_kernel_two_blocks_per_cu(shape):
     thr[::5] = np.iinfo(np.int32).max
     thr[1::7] = np.iinfo(np.int32).min
     want = O.bconv2d(spec, O.DST_BITPACKED, x, w, thresholds=thr)
-    H.set_stream(cus, 0)
-    try:
-        for occ, mb in ((2, 0), (2, 2), (1, 0), (0, 0), (0, 3)):      # (mb: launches of at most mb images -- a smaller last chunk)
-            H.set_stream_blocks_per_cu(occ)
-            got, name = H.bconv2d(spec, O.DST_BITPACKED, x, w, thresholds=thr, engine="stream", max_batch=mb)
-            assert np.array_equal(got, want), (name, mb)
-            assert name.startswith("bconv2d_stream<bitpacked,3x3x64,") and (",x2>" in name) == (occ == 2 or (occ == 0 and ",x2>" in name)), name
-            if occ == 1:
-                assert ",x2" not in name, name
-        H.set_stream_blocks_per_cu(2)
-        with pytest.raises(RuntimeError, match="stream_blocks_per_cu=2"):
-            H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream")
-    finally:
-        H.set_stream(256, 0)
-        H.set_stream_blocks_per_cu(0)
+    for occ, mb in ((2, 0), (2, 2), (1, 0), (0, 0), (0, 3)):      # (mb: launches of at most mb images -- a smaller last chunk)
+        got, name = H.bconv2d(spec, O.DST_BITPACKED, x, w, thresholds=thr, engine="stream", max_batch=mb,
+                              options={"compute_units": cus, "stream_blocks_per_cu": occ or "auto"})
+        assert np.array_equal(got, want), (name, mb)
+        assert name.startswith("bconv2d_stream<bitpacked,3x3x64,") and (",x2>" in name) == (occ == 2 or (occ == 0 and ",x2>" in name)), name
+        if occ == 1:
+            assert ",x2" not in name, name
+    with pytest.raises(RuntimeError, match="stream_blocks_per_cu=2"):
+        H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream", options={"compute_units": cus, "stream_blocks_per_cu": 2})
 
 
 @pytest.mark.parametrize("phases,cout,cus", [(2, 256, 2), (4, 256, 4)])
@@ -690,14 +667,9 @@ def test_stream_kernel_with_forced_pixel_phases(phases, cout, cus):
     slices -- half (a quarter) of the filter bank per block, grid.y picks the slices.  Same results, all output types;
     the first block step takes its weights as they arrive (round 4), whatever the mapping."""
     spec = O.ConvSpec(3, 6, 8, 256, 3, 3, cout, padding=O.PADDING_SAME, pad_values=1)
-    H.set_stream(cus, 0)
-    H.set_stream_phases(phases)
-    try:
-        names = _run_all_dst_mfma(spec, seed=11 + phases + cout, max_batch=0, engine="stream")
-        assert all(n.startswith("bconv2d_stream<") and ",phases%d>" % phases in n for n in names), names
-    finally:
-        H.set_stream(256, 0)
-        H.set_stream_phases(0)
+    names = _run_all_dst_mfma(spec, seed=11 + phases + cout, max_batch=0, engine="stream",
+                              options={"compute_units": cus, "stream_pixel_phases": phases})
+    assert all(n.startswith("bconv2d_stream<") and ",phases%d>" % phases in n for n in names), names
 
 
 KSPLIT_SHAPES = [
@@ -717,13 +689,9 @@ def test_stream_kernel_k_split_over_wave_pairs(shape):
     b, h, w_, cin, cout, st, pad, act, cus, chunks = shape
     padding, pad_values = PADS[pad]
     spec = O.ConvSpec(b, h, w_, cin, 3, 3, cout, 1, st[0], st[1], 1, 1, padding, pad_values, act, O.SEM_REFERENCE)
-    H.set_stream(cus, 0)
-    try:
-        for mb in chunks:
-            names = _run_all_dst_mfma(spec, seed=cin + 3 * cout + b, max_batch=mb, engine="stream")
-            assert all(n.startswith("bconv2d_stream<") and "3x3x512" in n for n in names), names
-    finally:
-        H.set_stream(256, 0)
+    for mb in chunks:
+        names = _run_all_dst_mfma(spec, seed=cin + 3 * cout + b, max_batch=mb, engine="stream", options={"compute_units": cus})
+        assert all(n.startswith("bconv2d_stream<") and "3x3x512" in n for n in names), names
 
 
 @pytest.mark.parametrize("cin,cout", [(512, 128)])
@@ -733,20 +701,18 @@ def test_stream_flat_pixel_blocks_second_output(cin, cout):
     x, w, mul, bias = synth.conv_inputs(spec, 5 + cin, negative_mul_fraction=0.3)
     bias = (bias - np.median(O.bconv2d(spec, O.DST_F32, x, w, mul, bias), axis=(0, 1, 2))).astype(np.float32)
     words = np.full(spec.output_shape(O.DST_BITPACKED), 0x5A5A5A5A, np.int32)
-    H.set_stream(1, 0)
-    try:
-        got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream", sign_words=words)
-        want = O.bconv2d(spec, O.DST_F32, x, w, mul, bias)
-        assert name.startswith("bconv2d_stream<f32"), name
-        assert np.array_equal(got.view(np.int32), want.view(np.int32)), name
-        assert np.array_equal(words, O.bitpack(want)), name
-        words[:] = 0x5A5A5A5A
-        got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=2, engine="stream", sign_words=words)
-        want = O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=2)
-        assert np.array_equal(got, want), name
-        assert np.array_equal(words, O.bitpack(want, 2)), name
-    finally:
-        H.set_stream(256, 0)
+    one_cu = {"compute_units": 1}
+    got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream", sign_words=words, options=one_cu)
+    want = O.bconv2d(spec, O.DST_F32, x, w, mul, bias)
+    assert name.startswith("bconv2d_stream<f32"), name
+    assert np.array_equal(got.view(np.int32), want.view(np.int32)), name
+    assert np.array_equal(words, O.bitpack(want)), name
+    words[:] = 0x5A5A5A5A
+    got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=2, engine="stream", sign_words=words,
+                          options=one_cu)
+    want = O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=2)
+    assert np.array_equal(got, want), name
+    assert np.array_equal(words, O.bitpack(want, 2)), name
 
 
 STRIP_SHAPES = [
@@ -768,20 +734,15 @@ def test_stream_kernel_column_strips(shape):
     b, h, w_, cin, cout, st, pad, act, cus, wso, chunks = shape
     padding, pad_values = PADS[pad]
     spec = O.ConvSpec(b, h, w_, cin, 3, 3, cout, 1, st[0], st[1], 1, 1, padding, pad_values, act, O.SEM_REFERENCE)
-    H.set_stream(cus, 0)
-    H.set_stream_strip(wso)
-    try:
-        if spec.out_w % wso:
-            x, w, mul, bias = synth.conv_inputs(spec, 1)
-            with pytest.raises(RuntimeError, match="stream_strip"):
-                H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream")
-            return
-        for mb in chunks:
-            names = _run_all_dst_mfma(spec, seed=cin + cout + w_, max_batch=mb, engine="stream")
-            assert all(n.startswith("bconv2d_stream<") and ",strips%d>" % wso in n for n in names), names
-    finally:
-        H.set_stream(256, 0)
-        H.set_stream_strip(-1)
+    options = {"compute_units": cus, "stream_strip": wso}
+    if spec.out_w % wso:
+        x, w, mul, bias = synth.conv_inputs(spec, 1)
+        with pytest.raises(RuntimeError, match="stream_strip"):
+            H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream", options=options)
+        return
+    for mb in chunks:
+        names = _run_all_dst_mfma(spec, seed=cin + cout + w_, max_batch=mb, engine="stream", options=options)
+        assert all(n.startswith("bconv2d_stream<") and ",strips%d>" % wso in n for n in names), names
 
 
 WSTREAM_SHAPES = [
@@ -806,13 +767,9 @@ def test_wstream_kernel(shape):
     b, h, w_, cin, cout, st, pad, act, cus, chunks = shape
     padding, pad_values = PADS[pad]
     spec = O.ConvSpec(b, h, w_, cin, 3, 3, cout, 1, st[0], st[1], 1, 1, padding, pad_values, act, O.SEM_REFERENCE)
-    H.set_stream(cus, 0)
-    try:
-        for mb in chunks:
-            names = _run_all_dst_mfma(spec, seed=cin + 3 * cout + b, max_batch=mb, engine="wstream")
-            assert all(n.startswith("bconv2d_wstream<") for n in names), names
-    finally:
-        H.set_stream(256, 0)
+    for mb in chunks:
+        names = _run_all_dst_mfma(spec, seed=cin + 3 * cout + b, max_batch=mb, engine="wstream", options={"compute_units": cus})
+        assert all(n.startswith("bconv2d_wstream<") for n in names), names
 
 
 @pytest.mark.parametrize("cin,cout,hw,zp", [(256, 256, 14, 3), (512, 320, 7, -5)])
@@ -822,20 +779,18 @@ def test_wstream_second_output_is_the_lcequantize_of_the_output(cin, cout, hw, z
     x, w, mul, bias = synth.conv_inputs(spec, 9 + cin, negative_mul_fraction=0.3)
     bias = (bias - np.median(O.bconv2d(spec, O.DST_F32, x, w, mul, bias), axis=(0, 1, 2))).astype(np.float32)
     words = np.full(spec.output_shape(O.DST_BITPACKED), 0x5A5A5A5A, np.int32)
-    H.set_stream(4, 0)
-    try:
-        got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="wstream", sign_words=words)
-        want = O.bconv2d(spec, O.DST_F32, x, w, mul, bias)
-        assert name.startswith("bconv2d_wstream<f32"), name
-        assert np.array_equal(got.view(np.int32), want.view(np.int32)), name
-        assert np.array_equal(words, O.bitpack(want)), name
-        words[:] = 0x5A5A5A5A
-        got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=zp, engine="wstream", sign_words=words)
-        want = O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=zp)
-        assert np.array_equal(got, want), name
-        assert np.array_equal(words, O.bitpack(want, zp)), name
-    finally:
-        H.set_stream(256, 0)
+    four_cus = {"compute_units": 4}
+    got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="wstream", sign_words=words, options=four_cus)
+    want = O.bconv2d(spec, O.DST_F32, x, w, mul, bias)
+    assert name.startswith("bconv2d_wstream<f32"), name
+    assert np.array_equal(got.view(np.int32), want.view(np.int32)), name
+    assert np.array_equal(words, O.bitpack(want)), name
+    words[:] = 0x5A5A5A5A
+    got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=zp, engine="wstream", sign_words=words,
+                          options=four_cus)
+    want = O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=8.0, out_zero_point=zp)
+    assert np.array_equal(got, want), name
+    assert np.array_equal(words, O.bitpack(want, zp)), name
 
 
 @pytest.mark.parametrize("engine,shape", [("stream", (2, 8, 8, 64, 64, 3)), ("stream", (2, 6, 6, 256, 64, 3)), ("wstream", (2, 7, 7, 256, 64, 3)),
@@ -849,20 +804,17 @@ def test_int8_floor_rounding_is_taken_only_where_it_is_exact(engine, shape):
     b, h, w_, cin, cout, k = shape
     spec = O.ConvSpec(b, h, w_, cin, k, k, cout, padding=O.PADDING_SAME if k == 3 else O.PADDING_VALID, pad_values=1 if k == 3 else 0)
     x, w, mul, bias = synth.conv_inputs(spec, 17 + cin)
-    H.set_stream(2, 0)
-    try:
-        got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.5, out_zero_point=-7, engine=engine)
-        assert H.last_int8_floor() == 1, name
-        assert np.array_equal(got, O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.5, out_zero_point=-7)), name
-        mul_t = np.full(cout, -0.25, np.float32)
-        mul_t[::3] = 0.25
-        bias_t = np.zeros(cout, np.float32)
-        got, name = H.bconv2d(spec, O.DST_I8, x, w, mul_t, bias_t, out_scale=1.0, out_zero_point=0, engine=engine)
-        want = O.bconv2d(spec, O.DST_I8, x, w, mul_t, bias_t, out_scale=1.0, out_zero_point=0)
-        assert H.last_int8_floor() == 0, name
-        assert np.array_equal(got, want), name
-    finally:
-        H.set_stream(256, 0)
+    two_cus = {"compute_units": 2}
+    got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.5, out_zero_point=-7, engine=engine, options=two_cus)
+    assert H.last_int8_floor() == 1, name
+    assert np.array_equal(got, O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.5, out_zero_point=-7)), name
+    mul_t = np.full(cout, -0.25, np.float32)
+    mul_t[::3] = 0.25
+    bias_t = np.zeros(cout, np.float32)
+    got, name = H.bconv2d(spec, O.DST_I8, x, w, mul_t, bias_t, out_scale=1.0, out_zero_point=0, engine=engine, options=two_cus)
+    want = O.bconv2d(spec, O.DST_I8, x, w, mul_t, bias_t, out_scale=1.0, out_zero_point=0)
+    assert H.last_int8_floor() == 0, name
+    assert np.array_equal(got, want), name
 
 
 def test_int8_floor_rounding_with_an_adjusted_bias_equals_the_oracle():
@@ -871,22 +823,19 @@ def test_int8_floor_rounding_with_an_adjusted_bias_equals_the_oracle():
     adjusted channel shows up (about every second draw of this shape); every plan's bytes equal the oracle's."""
     spec = O.ConvSpec(1, 5, 5, 256, 3, 3, 96, padding=O.PADDING_SAME, pad_values=1)
     adjusted = 0
-    H.set_stream(2, 0)
-    try:
-        for seed in range(12):
-            rng = np.random.default_rng(900 + seed)
-            x, w, _, _ = synth.conv_inputs(spec, seed)
-            mul = rng.uniform(0.02, 0.09, 96).astype(np.float32) * rng.choice([-1.0, 1.0], 96).astype(np.float32)
-            bias = rng.uniform(-20.0, 20.0, 96).astype(np.float32)
-            got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.73, out_zero_point=3, engine="stream")
-            assert np.array_equal(got, O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.73, out_zero_point=3)), (seed, name)
-            if H.last_int8_floor() == 1:
-                adjusted += H.last_int8_adjusted()
-            if adjusted:
-                break
-        assert adjusted > 0
-    finally:
-        H.set_stream(256, 0)
+    for seed in range(12):
+        rng = np.random.default_rng(900 + seed)
+        x, w, _, _ = synth.conv_inputs(spec, seed)
+        mul = rng.uniform(0.02, 0.09, 96).astype(np.float32) * rng.choice([-1.0, 1.0], 96).astype(np.float32)
+        bias = rng.uniform(-20.0, 20.0, 96).astype(np.float32)
+        got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.73, out_zero_point=3, engine="stream",
+                              options={"compute_units": 2})
+        assert np.array_equal(got, O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.73, out_zero_point=3)), (seed, name)
+        if H.last_int8_floor() == 1:
+            adjusted += H.last_int8_adjusted()
+        if adjusted:
+            break
+    assert adjusted > 0
 
 
 def test_int8_floor_proof_leaves_non_finite_parameters_to_the_exact_instances():
@@ -895,19 +844,16 @@ def test_int8_floor_proof_leaves_non_finite_parameters_to_the_exact_instances():
     spec = O.ConvSpec(1, 5, 5, 64, 3, 3, 32, padding=O.PADDING_SAME, pad_values=1)
     x, w, mul, bias = synth.conv_inputs(spec, 5)
     want = O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=0.37, out_zero_point=2)
-    H.set_stream(2, 0)
-    try:
-        for bad in (np.inf, -np.inf, np.nan):
-            for which in ("mul", "bias"):
-                m2, b2 = mul.copy(), bias.copy()
-                (m2 if which == "mul" else b2)[3] = bad
-                got, name = H.bconv2d(spec, O.DST_I8, x, w, m2, b2, out_scale=0.37, out_zero_point=2, engine="stream")
-                if which == "mul" or bad != bad:          # (an infinite bias saturates every value: that IS provable)
-                    assert H.last_int8_floor() == 0, (bad, which, name)
-                keep = np.arange(32) != 3
-                assert np.array_equal(got[..., keep], want[..., keep]), (bad, which, name)
-    finally:
-        H.set_stream(256, 0)
+    for bad in (np.inf, -np.inf, np.nan):
+        for which in ("mul", "bias"):
+            m2, b2 = mul.copy(), bias.copy()
+            (m2 if which == "mul" else b2)[3] = bad
+            got, name = H.bconv2d(spec, O.DST_I8, x, w, m2, b2, out_scale=0.37, out_zero_point=2, engine="stream",
+                                  options={"compute_units": 2})
+            if which == "mul" or bad != bad:          # (an infinite bias saturates every value: that IS provable)
+                assert H.last_int8_floor() == 0, (bad, which, name)
+            keep = np.arange(32) != 3
+            assert np.array_equal(got[..., keep], want[..., keep]), (bad, which, name)
 
 
 def test_int8_floor_proof_by_bisection_equals_the_full_enumeration(monkeypatch):
@@ -969,23 +915,16 @@ def test_stream_kernel_refuses_what_it_cannot_run():
     # stream_rows must divide the output height
     spec = O.ConvSpec(2, 9, 9, 64, 3, 3, 64, padding=O.PADDING_SAME, pad_values=1)
     x, w, mul, bias = synth.conv_inputs(spec, 3)
-    H.set_stream(2, 4)
-    try:
-        with pytest.raises(RuntimeError, match="divide the output height"):
-            H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream")
-    finally:
-        H.set_stream(256, 0)
+    with pytest.raises(RuntimeError, match="divide the output height"):
+        H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream", options={"compute_units": 2, "stream_rows": 4})
 
 
 def test_stream_kernel_is_the_auto_choice_for_a_256_channel_3x3_layer_that_fills_the_chip():
     spec = O.ConvSpec(6, 12, 16, 256, 3, 3, 256, padding=O.PADDING_SAME, pad_values=1)
     x, w, mul, bias = synth.conv_inputs(spec, 5)
     want = O.bconv2d(spec, O.DST_F32, x, w, mul, bias)
-    H.set_stream(4, 0)          # a 4-CU "device": 6 images fill it, 12 block steps per block
-    try:
-        got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="auto")
-    finally:
-        H.set_stream(256, 0)
+    # a 4-CU "device": 6 images fill it, 12 block steps per block
+    got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="auto", options={"compute_units": 4})
     assert name.startswith("bconv2d_stream<") and np.array_equal(got.view(np.int32), want.view(np.int32)), name
     # 256 CUs: round 4's rule sent a launch that fills 6 of them to the block GEMM; the cost estimate (round 5) cuts the six images
     # into 2-row segments over 36 blocks of the streaming kernel (profiles/r05/engine_sweep_box*.jsonl: the faster choice at small batch)
@@ -1002,11 +941,7 @@ def test_stream_second_output_is_the_lcequantize_of_the_float_output(cin, cout, 
     x, w, mul, bias = synth.conv_inputs(spec, 77 + cout, negative_mul_fraction=0.3)
     bias = (bias - np.median(O.bconv2d(spec, O.DST_F32, x, w, mul, bias), axis=(0, 1, 2))).astype(np.float32)   # both signs occur
     words = np.full(spec.output_shape(O.DST_BITPACKED), 0x5A5A5A5A, np.int32)
-    H.set_stream(cus, 0)
-    try:
-        got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream", sign_words=words)
-    finally:
-        H.set_stream(256, 0)
+    got, name = H.bconv2d(spec, O.DST_F32, x, w, mul, bias, engine="stream", sign_words=words, options={"compute_units": cus})
     want = O.bconv2d(spec, O.DST_F32, x, w, mul, bias)
     assert name.startswith("bconv2d_stream<f32"), name
     assert np.array_equal(got.view(np.int32), want.view(np.int32)), name
@@ -1023,11 +958,8 @@ def test_stream_second_output_of_an_int8_layer_is_its_lcequantize(zp):
     bias = np.zeros_like(bias)
     scale = float(3 * 3 * 4)                        # |y| up to ~ K/scale = 8 around zp; halves occur -> exact ties
     words = np.full(spec.output_shape(O.DST_BITPACKED), 0x5A5A5A5A, np.int32)
-    H.set_stream(2, 0)
-    try:
-        got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=scale, out_zero_point=zp, engine="stream", sign_words=words)
-    finally:
-        H.set_stream(256, 0)
+    got, name = H.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=scale, out_zero_point=zp, engine="stream", sign_words=words,
+                          options={"compute_units": 2})
     want = O.bconv2d(spec, O.DST_I8, x, w, mul, bias, out_scale=scale, out_zero_point=zp)
     assert name.startswith("bconv2d_stream<i8"), name
     assert np.array_equal(got, want), name

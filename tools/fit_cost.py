@@ -28,9 +28,9 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import hostsim_lib as H  # noqa: E402  (ctypes front end of the host simulation: test tooling, not the oracle)
 import oracle_lib as O  # noqa: E402  (only its ConvSpec, to fill the C descriptor)
 
-ENGINE = {"direct": (3, 0, -1), "mfma": (2, 0, -1), "stream": (5, 0, -1), "wstream": (6, 0, -1)}
+ENGINE = {e: {"engine": e} for e in ("direct", "mfma", "stream", "wstream")}
 for r in (2, 4, 7, 8, 14):
-    ENGINE["stream_il%d" % r] = (5, r, 1)
+    ENGINE["stream_il%d" % r] = {"engine": "stream", "stream_rows": r, "stream_interleave": 1}
 DST = {"f32": O.DST_F32, "i8": O.DST_I8, "bp": O.DST_BITPACKED}
 
 
@@ -66,11 +66,10 @@ class Planner:
 
     def estimate(self, key, cand):
         hw, cin, cout, stride, batch, dst = key
-        eng, rows, il = ENGINE[cand]
         spec = O.ConvSpec(batch, hw, hw, cin, 3, 3, cout, 1, stride, stride, 1, 1, O.PADDING_SAME, 1, O.ACT_NONE, O.SEM_OPTIMIZED)
         desc = H.make_desc(spec, DST[dst], 0.125, 3)
         name = C.create_string_buffer(128)
-        us = self.lib.hostsim_plan_estimate(C.byref(desc), eng, rows, il, 256, name, 128)
+        us = self.lib.hostsim_plan_estimate(C.byref(desc), H.option_string(ENGINE[cand]), name, 128)
         return us, name.value.decode()
 
 
