@@ -37,6 +37,7 @@ ABI_SYMBOLS = (
     "lce_hip_stream_create", "lce_hip_stream_destroy", "lce_hip_stream_synchronize",
     "lce_hip_graph_begin_capture", "lce_hip_graph_end_capture", "lce_hip_graph_launch", "lce_hip_graph_destroy",
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
+    "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -48,6 +49,7 @@ POST_ADD, POST_SUB, POST_MUL, POST_DIV = 0, 1, 2, 3
 EW_ADD, EW_MUL = 0, 1                                   # lce_hip_ew_op
 EW_SCALAR, EW_PER_CHANNEL, EW_TENSOR = 0, 1, 2          # lce_hip_ew_operand
 EW_MAX_STEPS = 8
+ADD_INT8_LITERAL, ADD_INT8_SPLIT, ADD_INT8_SHIFT = 0, 1, 2   # lce_hip_add_int8_variant_id
 
 
 class LceHipError(RuntimeError):
@@ -70,6 +72,18 @@ class EwStep(C.Structure):
     """``lce_hip_ew_step``."""
     _fields_ = [("op", C.c_int32), ("operand", C.c_int32), ("values", C.c_void_p), ("scalar", C.c_float),
                 ("activation", C.c_int32)]
+
+
+class AddInt8Desc(C.Structure):
+    """``lce_hip_add_int8_desc``."""
+    _fields_ = [("in1_scale", C.c_float), ("in1_zero_point", C.c_int32), ("in2_scale", C.c_float), ("in2_zero_point", C.c_int32),
+                ("out_scale", C.c_float), ("out_zero_point", C.c_int32), ("activation", C.c_int32)]
+
+
+class AddInt8Params(C.Structure):
+    """``lce_hip_add_int8_params``."""
+    _fields_ = [(n, C.c_int32) for n in ("left_shift", "in1_multiplier", "in1_shift", "in2_multiplier", "in2_shift",
+                                         "out_multiplier", "out_shift", "act_min", "act_max")]
 
 
 _lib = None
@@ -112,6 +126,12 @@ def lib() -> C.CDLL:
                                      C.c_int32, C.c_void_p, C.c_void_p]
         l.lce_hip_elementwise.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(EwStep), C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_add_int8_prepare.argtypes = [C.POINTER(AddInt8Desc), C.POINTER(AddInt8Params)]
+        l.lce_hip_add_int8_variant.argtypes = [C.POINTER(AddInt8Desc), C.POINTER(C.c_int32)]
+        l.lce_hip_add_int8.argtypes = [C.POINTER(AddInt8Desc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_add_int8_forced.argtypes = [C.POINTER(AddInt8Desc), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -455,6 +475,110 @@ def elementwise(x, steps, out=None, out_bits=None, stream: int | None = None):
         check(lib().lce_hip_elementwise(C.c_void_p(xd.data_ptr()), rows, channels, arr, len(steps),
                                         C.c_void_p(None if out_d is None else out_d.data_ptr()),
                                         C.c_void_p(None if bits_d is None else bits_d.data_ptr()), C.c_void_p(stream)))
+    if host:
+        ret_out = None if out_d is None else out_d.cpu().numpy()
+        if isinstance(out, np.ndarray) and ret_out is not None:
+            out[...] = ret_out
+            ret_out = out
+        ret_bits = None if bits_d is None else bits_d.cpu().numpy()
+        if isinstance(out_bits, np.ndarray) and ret_bits is not None:
+            out_bits[...] = ret_bits
+            ret_bits = out_bits
+        return ret_out, ret_bits
+    return out_d, bits_d
+
+
+def _add_int8_desc(q1, q2, q_out, activation) -> AddInt8Desc:
+    """Checks of the quantization arguments that need no library: each q is (scale, zero_point)."""
+    vals = []
+    for name, q in (("q1", q1), ("q2", q2), ("q_out", q_out)):
+        if not isinstance(q, (list, tuple)) or len(q) != 2:
+            raise ValueError("add_int8: %s must be (scale, zero_point), got %r" % (name, q))
+        scale, zp = float(q[0]), q[1]
+        if not (np.isfinite(scale) and scale > 0):
+            raise ValueError("add_int8: %s scale must be finite and positive, got %r" % (name, q[0]))
+        if int(zp) != zp or not -128 <= int(zp) <= 127:
+            raise ValueError("add_int8: %s zero point must be an integer in [-128, 127], got %r" % (name, zp))
+        vals += [scale, int(zp)]
+    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
+        raise ValueError("add_int8: unknown activation %r" % (activation,))
+    return AddInt8Desc(*vals, int(activation))
+
+
+def add_int8_params(q1, q2, q_out, activation=ACT_NONE) -> dict:
+    """TFLite's Prepare of the builtin int8 ADD (``lce_hip_add_int8_prepare``, host only): the nine numbers of
+    ``lce_hip_add_int8_params`` as a dict, plus ``variant`` -- the kernel variant ``add_int8`` uses for these parameters
+    (``ADD_INT8_*``).  Raises ``LceHipError`` for parameters TFLite's Prepare refuses (a real multiplier outside (0, 1))."""
+    d = _add_int8_desc(q1, q2, q_out, activation)
+    p, v = AddInt8Params(), C.c_int32()
+    check(lib().lce_hip_add_int8_prepare(C.byref(d), C.byref(p)))
+    check(lib().lce_hip_add_int8_variant(C.byref(d), C.byref(v)))
+    out = {n: int(getattr(p, n)) for n, _ in AddInt8Params._fields_}
+    out["variant"] = int(v.value)
+    return out
+
+
+def _add_int8_check(x1, x2, out, out_bits):
+    """Argument checks of ``add_int8`` on shapes and dtypes only (NumPy or torch): nothing here touches a device."""
+    def dtype_name(a):
+        return str(a.dtype).replace("torch.", "")
+    shape = tuple(x1.shape)
+    if dtype_name(x1) != "int8" or len(shape) < 1:
+        raise ValueError("add_int8: x1 must be an int8 tensor with a channel axis, got %s %r" % (x1.dtype, shape))
+    if dtype_name(x2) != "int8" or tuple(x2.shape) != shape:
+        raise ValueError("add_int8: x2 must be int8 of x1's shape %r, got %s %r" % (shape, x2.dtype, tuple(x2.shape)))
+    if out is False and out_bits is None:
+        raise ValueError("add_int8: no output requested")
+    if out is not None and out is not False:
+        if tuple(out.shape) != shape or dtype_name(out) != "int8":
+            raise ValueError("add_int8: out must be int8 of shape %r, got %s %r" % (shape, out.dtype, tuple(out.shape)))
+    if out_bits is not None and out_bits is not True:
+        want = shape[:-1] + (bitpacked_size(shape[-1]),)
+        if tuple(out_bits.shape) != want or dtype_name(out_bits) != "int32":
+            raise ValueError("add_int8: out_bits must be int32 of shape %r, got %s %r" % (want, out_bits.dtype, tuple(out_bits.shape)))
+
+
+def add_int8(x1, x2, q1, q2, q_out, activation=ACT_NONE, out=None, out_bits=None, stream: int | None = None,
+             variant: int | None = None):
+    """TFLite's builtin int8 ADD of two tensors -- the residual shortcut of an int8-converted network -- byte for byte, and
+    the LceQuantize of the sum at the sum's zero point, in one pass (``lce_hip_add_int8``).  ``x1``, ``x2``: int8 [..., C] of
+    one shape on the device (or NumPy: copied to cuda:0 and back).  ``q1``, ``q2``, ``q_out``: (scale, zero_point) of the two
+    inputs and the sum.  ``out``: an int8 tensor to fill (may be ``x1`` or ``x2``), None for a new one, False for none.
+    ``out_bits``: an int32 [..., ceil(C/32)] tensor to fill, True for a new one, None for none.  ``variant``: run this kernel
+    variant (``ADD_INT8_*``; refused when it is not proven for the parameters) instead of the chosen one -- for tests and
+    measurements.  Returns ``(out, out_bits)`` with None for an output not asked for."""
+    desc = _add_int8_desc(q1, q2, q_out, activation)
+    _add_int8_check(x1, x2, out, out_bits)
+    if variant is not None and variant not in (ADD_INT8_LITERAL, ADD_INT8_SPLIT, ADD_INT8_SHIFT):
+        raise ValueError("add_int8: unknown variant %r" % (variant,))
+    import torch
+    host = isinstance(x1, np.ndarray)
+    dev = torch.device("cuda:0") if host else x1.device
+
+    def on_dev(a):
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
+        if not (t.is_cuda and t.device == dev and t.is_contiguous()):
+            raise ValueError("add_int8: tensors must be contiguous and on x1's device %s" % dev)
+        return t
+
+    a, b = on_dev(x1), on_dev(x2)
+    channels = x1.shape[-1]
+    rows = a.numel() // channels if channels else 0
+    out_d = None if out is False else torch.empty_like(a) if out is None else on_dev(out)
+    bits_d = None
+    if out_bits is True:
+        bits_d = torch.empty(tuple(a.shape[:-1]) + (bitpacked_size(channels),), dtype=torch.int32, device=dev)
+    elif out_bits is not None:
+        bits_d = on_dev(out_bits)
+    ptrs = (C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), rows, channels,
+            C.c_void_p(None if out_d is None else out_d.data_ptr()), C.c_void_p(None if bits_d is None else bits_d.data_ptr()))
+    with torch.cuda.device(dev):
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        if variant is None:
+            check(lib().lce_hip_add_int8(C.byref(desc), *ptrs, C.c_void_p(stream)))
+        else:
+            check(lib().lce_hip_add_int8_forced(C.byref(desc), int(variant), *ptrs, C.c_void_p(stream)))
     if host:
         ret_out = None if out_d is None else out_d.cpu().numpy()
         if isinstance(out, np.ndarray) and ret_out is not None:

@@ -2,11 +2,14 @@
 // There is no CPU fallback in this file: every compute entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -15,6 +18,7 @@
 #include "lce_kernels.h"          // the LceQuantize / LceDequantize / LceBMaxPool2d kernels are launched from here
 #include "lce_kernel_types.h"    // the convolution kernels live in their own translation units (lce_tu_*.hip)
 #include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip)
+#include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -32,6 +36,7 @@
 #include "lce_tu_wstream_i8_floor.hip"
 #include "lce_tu_wstream_bitpacked.hip"
 #include "lce_tu_eltwise.hip"
+#include "lce_tu_eltwise_i8.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -508,6 +513,230 @@ lce_hip_status lce_hip_elementwise(const float* in_dev, size_t rows, size_t chan
   const int e = lce::launch_eltwise(a, channels % 32 == 0 && aligned, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_elementwise: launch failed: %s", hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// int8 residual ADD (lce_kernels_eltwise_i8.h)
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// QuantizeMultiplier (tensorflow/lite/kernels/internal/quantization_util.cc)
+void quantize_multiplier(double d, int32_t* m, int32_t* e) {
+  *m = 0;
+  *e = 0;
+  if (d == 0.0) return;
+  int exp = 0;
+  const double q = std::frexp(d, &exp);
+  int64_t q_fixed = (int64_t)std::round(q * (double)(1ll << 31));
+  if (q_fixed == (1ll << 31)) {
+    q_fixed /= 2;
+    ++exp;
+  }
+  if (exp < -31) {
+    exp = 0;
+    q_fixed = 0;
+  }
+  *m = (int32_t)q_fixed;
+  *e = exp;
+}
+
+// What the host derives from one lce_hip_add_int8_desc: TFLite's nine parameters, the kernel arguments in canonical input
+// order (pointers and sizes unset), and which variants are PROVEN for it.
+struct PreparedAddI8 {
+  lce_hip_add_int8_params params;
+  lce::AddI8Args args;
+  bool swapped = false;                         // the kernel's input 1 is the caller's input 2
+  int32_t c_for[lce::kAddI8Variants] = {0, 0, 0};
+  bool proven[lce::kAddI8Variants] = {true, false, false};
+  int variant = lce::kAddI8Literal;             // the chooser's pick
+};
+
+lce_hip_status add_int8_params(const lce_hip_add_int8_desc* d, lce_hip_add_int8_params* p, const char* who) {
+  if (!d || !p) return fail(LCE_HIP_ERR_INVALID, "%s: null argument", who);
+  const float scales[3] = {d->in1_scale, d->in2_scale, d->out_scale};
+  const int32_t zps[3] = {d->in1_zero_point, d->in2_zero_point, d->out_zero_point};
+  static const char* const names[3] = {"in1", "in2", "out"};
+  for (int i = 0; i < 3; ++i) {
+    if (!std::isfinite(scales[i]) || !(scales[i] > 0.0f))
+      return fail(LCE_HIP_ERR_INVALID, "%s: %s_scale must be finite and positive, got %g", who, names[i], (double)scales[i]);
+    if (zps[i] < -128 || zps[i] > 127)
+      return fail(LCE_HIP_ERR_INVALID, "%s: %s_zero_point must be in [-128, 127], got %d", who, names[i], (int)zps[i]);
+  }
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  // Prepare of the builtin ADD (tensorflow/lite/kernels/add.cc), int8 branch
+  const double s1 = (double)d->in1_scale, s2 = (double)d->in2_scale, so = (double)d->out_scale;
+  const double twice_max = 2.0 * std::max(s1, s2);
+  const double real[3] = {s1 / twice_max, s2 / twice_max, twice_max / ((double)(1 << 20) * so)};
+  for (int i = 0; i < 3; ++i)
+    if (!(real[i] > 0.0 && real[i] < 1.0))
+      return fail(LCE_HIP_ERR_INVALID, "%s: the real multiplier of %s is %g, not in (0, 1)", who, names[i], real[i]);
+  p->left_shift = 20;
+  quantize_multiplier(real[0], &p->in1_multiplier, &p->in1_shift);
+  quantize_multiplier(real[1], &p->in2_multiplier, &p->in2_shift);
+  quantize_multiplier(real[2], &p->out_multiplier, &p->out_shift);
+  // CalculateActivationRangeQuantized (kernel_util.cc) for int8: Q(f) = zo + (int32)round(f / so), the division in float
+  auto Q = [&](float f) -> int64_t {
+    double r = (double)std::round(f / d->out_scale);
+    r = std::min(std::max(r, -2147483000.0), 2147483000.0);        // (the cast of a larger value is undefined)
+    return (int64_t)d->out_zero_point + (int64_t)r;
+  };
+  int64_t lo = -128, hi = 127;
+  if (d->activation == LCE_HIP_ACT_RELU) {
+    lo = std::max<int64_t>(lo, Q(0.0f));
+  } else if (d->activation == LCE_HIP_ACT_RELU6) {
+    lo = std::max<int64_t>(lo, Q(0.0f));
+    hi = std::min<int64_t>(hi, Q(6.0f));
+  } else if (d->activation == LCE_HIP_ACT_RELU_N1_TO_1) {
+    lo = std::max<int64_t>(lo, Q(-1.0f));
+    hi = std::min<int64_t>(hi, Q(1.0f));
+  }
+  p->act_min = (int32_t)lo;
+  p->act_max = (int32_t)hi;
+  return LCE_HIP_OK;
+}
+
+template <int V>
+bool add_i8_variant_is_exact(const lce::AddI8Args& a, const std::vector<int8_t>& literal) {
+  for (int x1 = -128; x1 < 128; ++x1)
+    for (int x2 = -128; x2 < 128; ++x2)
+      if ((int8_t)lce::add_i8_value<V>(a, x1, x2) != literal[(size_t)(x1 + 128) * 256 + (size_t)(x2 + 128)]) return false;
+  return true;
+}
+
+// The kernel arguments of every variant whose preconditions hold, and the proof: the variant's own arithmetic over all
+// 65 536 input pairs against the literal formula (the precedent: int8_one_instruction_forms, lce_plan.cpp).
+void prove_add_int8(PreparedAddI8* P, const lce_hip_add_int8_desc& d) {
+  const lce_hip_add_int8_params& p = P->params;
+  struct In { int32_t z, m, n; } in[2] = {{d.in1_zero_point, p.in1_multiplier, -p.in1_shift},
+                                          {d.in2_zero_point, p.in2_multiplier, -p.in2_shift}};
+  auto is_shift = [](const In& i) { return i.m == (1 << 30) && i.n >= 0 && i.n <= 19; };   // sa = (x - z) << (19 - n), exact
+  // canonical order: a shift-form input first; of two, the one with the smaller shift (so the split form applies to the other)
+  P->swapped = is_shift(in[1]) && (!is_shift(in[0]) || in[0].n > in[1].n);
+  if (P->swapped) std::swap(in[0], in[1]);
+  lce::AddI8Args& a = P->args;
+  memset(&a, 0, sizeof a);
+  a.z1 = in[0].z; a.m1 = in[0].m; a.n1 = in[0].n;
+  a.z2 = in[1].z; a.m2 = in[1].m; a.n2 = in[1].n;
+  a.zo = d.out_zero_point; a.mo = p.out_multiplier; a.no = -p.out_shift;
+  a.lo = p.act_min; a.hi = p.act_max;
+  a.lo_rel = a.lo - a.zo; a.hi_rel = a.hi - a.zo;
+  bool candidate[lce::kAddI8Variants] = {true, false, false};
+  if (is_shift(in[0]) && a.no >= 1 && a.no <= 30 && a.mo > 0) {
+    a.half_o = 1 << (a.no - 1);
+    a.ka = 1 << (19 - in[0].n);
+    P->c_for[lce::kAddI8Split] = -(in[0].z * a.ka);
+    if (in[1].m > 0 && in[1].n >= 1 && in[1].n <= 30) {
+      a.mh = in[1].m >> 11;
+      a.ml = in[1].m & 2047;
+      a.nb = in[1].n;
+      a.half_b = 1 << (a.nb - 1);
+      candidate[lce::kAddI8Split] = true;
+    }
+    if (is_shift(in[1])) {
+      a.kb = 1 << (19 - in[1].n);
+      P->c_for[lce::kAddI8Shift] = -(in[0].z * a.ka) - in[1].z * a.kb;
+      candidate[lce::kAddI8Shift] = true;
+    }
+  }
+  if (candidate[lce::kAddI8Split] || candidate[lce::kAddI8Shift]) {
+    std::vector<int8_t> literal(65536);
+    for (int x1 = -128; x1 < 128; ++x1)
+      for (int x2 = -128; x2 < 128; ++x2)
+        literal[(size_t)(x1 + 128) * 256 + (size_t)(x2 + 128)] = (int8_t)lce::add_i8_value<lce::kAddI8Literal>(a, x1, x2);
+    if (candidate[lce::kAddI8Split]) {
+      a.c = P->c_for[lce::kAddI8Split];
+      P->proven[lce::kAddI8Split] = add_i8_variant_is_exact<lce::kAddI8Split>(a, literal);
+    }
+    if (candidate[lce::kAddI8Shift]) {
+      a.c = P->c_for[lce::kAddI8Shift];
+      P->proven[lce::kAddI8Shift] = add_i8_variant_is_exact<lce::kAddI8Shift>(a, literal);
+    }
+  }
+  P->variant = P->proven[lce::kAddI8Shift] ? lce::kAddI8Shift : P->proven[lce::kAddI8Split] ? lce::kAddI8Split : lce::kAddI8Literal;
+}
+
+// One PreparedAddI8 per parameter set, kept by the host: a network has a handful, and the proof takes about a millisecond.
+lce_hip_status prepared_add_int8(const lce_hip_add_int8_desc* d, PreparedAddI8* out, const char* who) {
+  typedef std::array<int32_t, 7> Key;
+  static std::mutex mu;
+  static std::map<Key, PreparedAddI8> cache;
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  Key key;
+  memcpy(&key[0], &d->in1_scale, 4);
+  memcpy(&key[2], &d->in2_scale, 4);
+  memcpy(&key[4], &d->out_scale, 4);
+  key[1] = d->in1_zero_point; key[3] = d->in2_zero_point; key[5] = d->out_zero_point; key[6] = d->activation;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) { *out = it->second; return LCE_HIP_OK; }
+  }
+  PreparedAddI8 P;
+  if (lce_hip_status s = add_int8_params(d, &P.params, who)) return s;
+  prove_add_int8(&P, *d);
+  std::lock_guard<std::mutex> lock(mu);
+  if (cache.size() >= 1024) cache.clear();
+  cache[key] = P;
+  *out = P;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status add_int8_run(const lce_hip_add_int8_desc* desc, int32_t forced, const int8_t* in1_dev, const int8_t* in2_dev,
+                            size_t rows, size_t channels, int8_t* out_dev, int32_t* out_bits_dev, void* stream, const char* who) {
+  PreparedAddI8 P;
+  if (lce_hip_status s = prepared_add_int8(desc, &P, who)) return s;
+  int variant = P.variant;
+  if (forced >= 0) {
+    if (forced >= lce::kAddI8Variants) return fail(LCE_HIP_ERR_INVALID, "%s: unknown variant %d", who, (int)forced);
+    if (!P.proven[forced]) return fail(LCE_HIP_ERR_INVALID, "%s: variant %d is not proven for these parameters", who, (int)forced);
+    variant = forced;
+  }
+  if (channels >= (1ull << 31)) return fail(LCE_HIP_ERR_INVALID, "%s: channels must be below 2^31", who);
+  if (rows == 0 || channels == 0) return LCE_HIP_OK;   // (an empty tensor may come with null pointers)
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  if (!in1_dev || !in2_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::AddI8Args a = P.args;
+  a.c = P.c_for[variant];
+  a.in1 = P.swapped ? in2_dev : in1_dev;
+  a.in2 = P.swapped ? in1_dev : in2_dev;
+  a.out = out_dev;
+  a.bits = (uint32_t*)out_bits_dev;
+  a.rows = rows;
+  a.channels = (uint32_t)channels;
+  a.wpr = (uint32_t)((channels + 31) / 32);
+  const bool aligned = ((uintptr_t)in1_dev % 16 == 0) && ((uintptr_t)in2_dev % 16 == 0) && ((uintptr_t)out_dev % 16 == 0) &&
+                       ((uintptr_t)out_bits_dev % 4 == 0);
+  const int e = lce::launch_add_i8(a, variant, channels % 32 == 0 && aligned, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+}  // namespace
+extern "C" {
+
+lce_hip_status lce_hip_add_int8_prepare(const lce_hip_add_int8_desc* desc, lce_hip_add_int8_params* params) {
+  return add_int8_params(desc, params, "lce_hip_add_int8_prepare");
+}
+
+lce_hip_status lce_hip_add_int8_variant(const lce_hip_add_int8_desc* desc, int32_t* variant) {
+  if (!variant) return fail(LCE_HIP_ERR_INVALID, "lce_hip_add_int8_variant: null argument");
+  PreparedAddI8 P;
+  if (lce_hip_status s = prepared_add_int8(desc, &P, "lce_hip_add_int8_variant")) return s;
+  *variant = P.variant;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_add_int8(const lce_hip_add_int8_desc* desc, const int8_t* in1_dev, const int8_t* in2_dev, size_t rows,
+                                size_t channels, int8_t* out_dev, int32_t* out_bits_dev, void* stream) {
+  return add_int8_run(desc, -1, in1_dev, in2_dev, rows, channels, out_dev, out_bits_dev, stream, "lce_hip_add_int8");
+}
+
+lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_t variant, const int8_t* in1_dev,
+                                       const int8_t* in2_dev, size_t rows, size_t channels, int8_t* out_dev,
+                                       int32_t* out_bits_dev, void* stream) {
+  if (variant < 0) return fail(LCE_HIP_ERR_INVALID, "lce_hip_add_int8_forced: unknown variant %d", (int)variant);
+  return add_int8_run(desc, variant, in1_dev, in2_dev, rows, channels, out_dev, out_bits_dev, stream, "lce_hip_add_int8_forced");
 }
 
 // ------------------------------------------------------------------------------------

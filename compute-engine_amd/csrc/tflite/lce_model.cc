@@ -23,7 +23,7 @@ struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
-  std::vector<char> absorbed;                 // per operator: a builtin ADD / MUL that runs inside a section
+  std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
   void Partition();
   // ---- state of lce_tflite_model_run_section (one run at a time per model) ----
@@ -35,6 +35,8 @@ struct lce_tflite_model {
   std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
   struct EwStats { int32_t launches = 0, ops = 0, quantize = 0; };
   EwStats last_ew;                                                      // lce_hip_elementwise launches of the last run
+  struct AddI8Stats { int32_t launches = 0, quantize = 0; };
+  AddI8Stats last_add_i8;                                               // lce_hip_add_int8 launches of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
   // stream, tensor pointers) and replayed as one launch.  The first call with a key runs eagerly (plans are made, weights
   // uploaded, intermediate buffers sized), the second records, later ones replay.  Recorded launches hold the model's
@@ -47,7 +49,7 @@ struct lce_tflite_model {
       return std::tie(section, batch, semantics, stream, ptrs) < std::tie(o.section, o.batch, o.semantics, o.stream, o.ptrs);
     }
   };
-  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; int32_t fused = 0; EwStats ew; };
+  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; int32_t fused = 0; EwStats ew; AddI8Stats add_i8; };
   std::map<GraphKey, GraphEntry> graphs;
   bool use_graphs = false;
   int32_t graph_captures = 0, graph_replays = 0;
@@ -104,6 +106,39 @@ bool ElementwiseCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   }
   return variable > 0;
 }
+
+// lce_hip_add_int8_desc of a builtin int8 ADD from its three tensors; false when a tensor has no quantization parameters or a
+// zero point that is no int8.
+bool Int8AddDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, lce_hip_add_int8_desc* d) {
+  const lce_tfl::Tensor* t[3] = {&M.tensors[o.inputs[0]], &M.tensors[o.inputs[1]], &M.tensors[o.outputs[0]]};
+  for (const lce_tfl::Tensor* x : t)
+    if (x->type != lce_tfl::kTensorInt8 || !x->quantized || x->zero_point < -128 || x->zero_point > 127) return false;
+  d->in1_scale = t[0]->scale; d->in1_zero_point = (int32_t)t[0]->zero_point;
+  d->in2_scale = t[1]->scale; d->in2_zero_point = (int32_t)t[1]->zero_point;
+  d->out_scale = t[2]->scale; d->out_zero_point = (int32_t)t[2]->zero_point;
+  d->activation = o.activation;
+  return true;
+}
+
+// The static half of "a builtin int8 ADD that a section may run" (LCE_TFLITE_SECTIONS_INT8_ADD): the residual shortcut of an
+// int8-converted network.  Two inputs and one output, all int8 with quantization parameters, a 4-D output, both inputs
+// non-constant tensors of the output's shape (batch ignored), an activation lce_hip_add_int8 knows, and parameters TFLite's
+// Prepare accepts.  The other half -- one input is produced in the same epoch -- is decided by Partition().
+bool Int8AddCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinAdd || o.inputs.size() != 2 || o.outputs.size() != 1) return false;
+  if (o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (out.shape.size() != 4 || out.shape[3] <= 0) return false;
+  for (int32_t t : o.inputs) {
+    const lce_tfl::Tensor& in = M.tensors[t];
+    if (in.data || in.shape.size() != 4 || in.shape[1] != out.shape[1] || in.shape[2] != out.shape[2] || in.shape[3] != out.shape[3])
+      return false;
+  }
+  lce_hip_add_int8_desc d;
+  lce_hip_add_int8_params p;
+  return Int8AddDesc(M, o, &d) && lce_hip_add_int8_prepare(&d, &p) == LCE_HIP_OK;
+}
+enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2 };
 }  // namespace
 
 // The partition a delegate would get (tensorflow/lite/graph_info.cc, PartitionGraphIntoIndependentNodeSubsets, restated from
@@ -125,7 +160,9 @@ void lce_tflite_model::Partition() {
     // LCE_TFLITE_SECTIONS_ELEMENTWISE: a float ADD / MUL joins the epoch in which it becomes ready, so it lands in a section
     // exactly when the last of its inputs was produced by an LCE epoch (one that is ready from the start -- a stem op -- is
     // a builtin one)
-    if (flags & LCE_TFLITE_SECTIONS_ELEMENTWISE) candidate[i] = ElementwiseCandidate(m, m.operators[i]) ? 1 : 0;
+    if (flags & LCE_TFLITE_SECTIONS_ELEMENTWISE) candidate[i] = ElementwiseCandidate(m, m.operators[i]) ? kAbsorbedElementwise : 0;
+    // LCE_TFLITE_SECTIONS_INT8_ADD: the same rule for the int8 ADD of a shortcut
+    if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_INT8_ADD)) candidate[i] = Int8AddCandidate(m, m.operators[i]) ? kAbsorbedInt8Add : 0;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -159,7 +196,7 @@ void lce_tflite_model::Partition() {
       any = true;
       --remaining;
       if (kind) sec.ops.push_back(i);
-      if (kind && candidate[i]) absorbed[i] = 1;
+      if (kind && candidate[i]) absorbed[i] = candidate[i];
       for (int32_t t : m.operators[i].outputs) {
         if (!valid(t) || made[t]) continue;
         made[t] = 1;
@@ -216,7 +253,7 @@ lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err
 lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len) {
   auto* model = new (std::nothrow) lce_tflite_model{};
   std::string e = "out of memory";
-  if (flags & ~(uint32_t)LCE_TFLITE_SECTIONS_ELEMENTWISE) {
+  if (flags & ~(uint32_t)(LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD)) {
     e = "unknown flags";
   } else if (model && data && model->m.Parse(data, size, &e)) {
     model->flags = flags;
@@ -550,7 +587,7 @@ lce_hip_status WalkElementwiseChain(lce_tflite_model* model, const lce_tflite_se
     const std::vector<int32_t>& rd = model->readers[v_t];
     if (steps.size() == 8 || rd.size() != 1 || is_section_output(v_t)) break;
     const int32_t next = rd[0];
-    if (!model->absorbed[next] || (*done)[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
+    if (model->absorbed[next] != kAbsorbedElementwise || (*done)[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
     cur = next;
   }
   // the LceQuantize that becomes the launch's bit output
@@ -585,6 +622,69 @@ lce_hip_status WalkElementwiseChain(lce_tflite_model* model, const lce_tflite_se
   ++model->last_ew.launches;
   model->last_ew.ops += (int32_t)chain.size();
   if (quant >= 0) ++model->last_ew.quantize;
+  return LCE_HIP_OK;
+}
+
+// An absorbed int8 ADD (LCE_TFLITE_SECTIONS_INT8_ADD) as ONE lce_hip_add_int8 launch.  The first LceQuantize of the section
+// that reads the sum becomes the launch's bit output and its own launch disappears; the int8 sum is written when anything
+// else reads it (in a residual chain the next ADD does) or the section delivers it.
+template <typename BufferFor>
+lce_hip_status WalkInt8Add(lce_tflite_model* model, const lce_tflite_section& sec, int32_t i, int32_t batch,
+                           std::map<int32_t, Shape>* shapes, std::map<int32_t, void*>* ptr, bool run, void* stream,
+                           BufferFor& buffer_for, std::vector<char>* done) {
+  const lce_tfl::Model& M = model->m;
+  const lce_tfl::Operator& op = M.operators[i];
+  const int32_t out_t = op.outputs[0];
+  const std::vector<int32_t>& fs = M.tensors[out_t].shape;
+  // the file's shapes were checked by the partition; the walk's inferred shape and type of BOTH inputs must agree with them
+  // (untrusted input: a convolution whose output is smaller than the file declares must not be read past its buffer)
+  Shape xs;
+  for (int k = 0; k < 2; ++k) {
+    auto it = shapes->find(op.inputs[k]);
+    if (it == shapes->end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD reads a tensor nothing produced");
+    xs = it->second;
+    if (xs.type != lce_tfl::kTensorInt8 || xs.dims[0] != batch || xs.dims[1] != fs[1] || xs.dims[2] != fs[2] || xs.dims[3] != fs[3])
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD input's shape or type does not match the one its producer infers");
+  }
+  (*shapes)[out_t] = xs;
+  (*done)[i] = 1;
+  auto is_section_output = [&](int32_t t) { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); };
+  int32_t quant = -1;
+  for (int32_t j : sec.ops) {
+    const lce_tfl::Operator& q = M.operators[j];
+    if (j > i && !(*done)[j] && q.builtin_code == lce_tfl::kBuiltinCustom && q.custom_code == "LceQuantize" &&
+        q.inputs.size() == 1 && q.inputs[0] == out_t && q.outputs.size() == 1) { quant = j; break; }
+  }
+  bool need_int8 = quant < 0 || is_section_output(out_t);
+  for (int32_t r : model->readers[out_t]) need_int8 = need_int8 || r != quant;
+  int32_t bits_t = -1;
+  if (quant >= 0) {
+    (*done)[quant] = 1;
+    bits_t = M.operators[quant].outputs[0];
+    Shape q = xs;
+    q.dims[3] = (xs.dims[3] + 31) / 32;
+    q.type = lce_tfl::kTensorInt32;
+    (*shapes)[bits_t] = q;
+  }
+  if (!run) return LCE_HIP_OK;
+  lce_hip_add_int8_desc d;
+  if (!Int8AddDesc(M, op, &d)) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD without quantization parameters");
+  const void* in[2];
+  for (int k = 0; k < 2; ++k) {
+    auto p = ptr->find(op.inputs[k]);
+    if (p == ptr->end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of an int8 ADD input");
+    in[k] = p->second;
+  }
+  void* out = nullptr;
+  void* bits = nullptr;
+  if (need_int8)
+    if (lce_hip_status s = buffer_for(out_t, xs.bytes(), &out)) return s;
+  if (quant >= 0)
+    if (lce_hip_status s = buffer_for(bits_t, (*shapes)[bits_t].bytes(), &bits)) return s;
+  if (lce_hip_status s = lce_hip_add_int8(&d, (const int8_t*)in[0], (const int8_t*)in[1], (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2],
+                                          (size_t)xs.dims[3], (int8_t*)out, (int32_t*)bits, stream)) return s;
+  ++model->last_add_i8.launches;
+  if (quant >= 0) ++model->last_add_i8.quantize;
   return LCE_HIP_OK;
 }
 
@@ -627,6 +727,10 @@ lce_hip_status WalkSection(lce_tflite_model* model, const lce_tflite_section& se
   std::vector<char> done(M.operators.size(), 0);
   for (int32_t i : sec.ops) {
     if (done[i]) continue;
+    if (model->absorbed[i] == kAbsorbedInt8Add) {
+      if (lce_hip_status s = WalkInt8Add(model, sec, i, batch, shapes, ptr, run, stream, buffer_for, &done)) return s;
+      continue;
+    }
     if (model->absorbed[i]) {
       if (lce_hip_status s = WalkElementwiseChain(model, sec, i, batch, shapes, ptr, run, stream, capturing, buffer_for, &done)) return s;
       continue;
@@ -768,6 +872,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
   }
   model->last_run_fused = 0;
   model->last_ew = lce_tflite_model::EwStats();
+  model->last_add_i8 = lce_tflite_model::AddI8Stats();
   if (!model->use_graphs || !stream) return WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
 
   lce_tflite_model::GraphKey key{section, batch, semantics, stream, {}};
@@ -778,6 +883,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
     if (e.graph) {
       model->last_run_fused = e.fused;
       model->last_ew = e.ew;
+      model->last_add_i8 = e.add_i8;
       ++model->graph_replays;
       return lce_hip_graph_launch(e.graph, stream);
     }
@@ -787,6 +893,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       void* g = nullptr;
       int32_t fused = 0;
       lce_tflite_model::EwStats ew;
+      lce_tflite_model::AddI8Stats add_i8;
       if (lce_hip_graph_begin_capture(stream) == LCE_HIP_OK) {
         std::map<int32_t, Shape> shapes_c;
         std::map<int32_t, void*> ptr_c = ptr;
@@ -795,6 +902,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
         recorded = walked == LCE_HIP_OK && ended == LCE_HIP_OK && g != nullptr;
         fused = model->last_run_fused;
         ew = model->last_ew;
+        add_i8 = model->last_add_i8;
         if (!recorded && g) { lce_hip_graph_destroy(g); g = nullptr; }
       }
       g_model_error.clear();
@@ -803,6 +911,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
         e2.graph = g;
         e2.fused = fused;
         e2.ew = ew;
+        e2.add_i8 = add_i8;
         e2.eager_runs = 1;
         ++model->graph_captures;
         ++model->graph_replays;
@@ -811,6 +920,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       e2.unrecordable = true;
       model->last_run_fused = 0;
       model->last_ew = lce_tflite_model::EwStats();
+      model->last_add_i8 = lce_tflite_model::AddI8Stats();
     }
   }
   const lce_hip_status s = WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
@@ -838,6 +948,13 @@ void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launch
   if (launches) *launches = model->last_ew.launches;
   if (ops_folded) *ops_folded = model->last_ew.ops;
   if (quantize_folded) *quantize_folded = model->last_ew.quantize;
+}
+
+void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (launches) *launches = model->last_add_i8.launches;
+  if (quantize_folded) *quantize_folded = model->last_add_i8.quantize;
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

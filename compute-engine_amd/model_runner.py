@@ -17,6 +17,8 @@ its boundary tensors, the float operators stay with TensorFlow Lite (``predict``
 With ``elementwise_sections=True`` (``lce_tflite_model_open_ex`` with LCE_TFLITE_SECTIONS_ELEMENTWISE) the float ADD / MUL
 between binary layers -- batch norm constants, residual shortcuts -- join the sections and run on the GPU as one fused pass
 per chain (``lce_hip_elementwise``); a graph whose every operator then lies in a section runs through ``predict``.
+With ``int8_add_sections=True`` (LCE_TFLITE_SECTIONS_INT8_ADD) the int8 residual ADD of an int8-converted network joins the
+sections in the same way (``lce_hip_add_int8``: TFLite's integer arithmetic byte for byte); the two flags combine.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -34,6 +36,7 @@ _tfl = None
 
 FLOAT32, INT32, BOOL, INT8 = 0, 2, 6, 9
 SECTIONS_ELEMENTWISE = 1          # LCE_TFLITE_SECTIONS_ELEMENTWISE
+SECTIONS_INT8_ADD = 2             # LCE_TFLITE_SECTIONS_INT8_ADD
 _NP = {FLOAT32: np.float32, INT32: np.int32, BOOL: np.bool_, INT8: np.int8}
 LCE_OPS = ("LceQuantize", "LceDequantize", "LceBconv2d", "LceBMaxPool2d")
 
@@ -83,6 +86,8 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_operator_activation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_elementwise_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
         l.lce_tflite_model_elementwise_stats.restype = None
+        l.lce_tflite_model_int8_add_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
+        l.lce_tflite_model_int8_add_stats.restype = None
         l.lce_tflite_model_close.argtypes = [C.c_void_p]
         for f in ("lce_tflite_model_num_tensors", "lce_tflite_model_num_operators"):
             getattr(l, f).argtypes = [C.c_void_p]
@@ -137,16 +142,19 @@ class Operator:
 class LceModel:
     """A parsed .tflite flatbuffer (first subgraph)."""
 
-    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False):
+    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
+                 int8_add_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
-        include/lce_tflite_model.h); the host then runs only what lies outside them."""
+        include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
+        residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD)."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
         self._data = bytes(flatbuffer)            # must outlive the handle (zero-copy reader)
         self.elementwise_sections = bool(elementwise_sections)
+        self.int8_add_sections = bool(int8_add_sections)
         err = C.create_string_buffer(256)
-        flags = SECTIONS_ELEMENTWISE if elementwise_sections else 0
+        flags = (SECTIONS_ELEMENTWISE if elementwise_sections else 0) | (SECTIONS_INT8_ADD if int8_add_sections else 0)
         self._h = tflite_lib().lce_tflite_model_open_ex(self._data, len(self._data), flags, err, 256)
         if not self._h:
             raise ValueError("not a readable TFLite model: " + err.value.decode(errors="replace"))
@@ -209,6 +217,12 @@ class LceModel:
         tflite_lib().lce_tflite_model_elementwise_stats(self._h, C.byref(a), C.byref(b), C.byref(c))
         return int(a.value), int(b.value), int(c.value)
 
+    def int8_add_stats(self):
+        """(lce_hip_add_int8 launches, LceQuantize launches they absorbed) of the last run."""
+        a, b = C.c_int32(), C.c_int32()
+        tflite_lib().lce_tflite_model_int8_add_stats(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -237,14 +251,16 @@ class Interpreter:
     """``Interpreter(flatbuffer_model, batch_size=...)`` -- see the module docstring."""
 
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
-                 use_reference_bconv: bool = False, elementwise_sections: bool = False):
-        """``elementwise_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its own setting holds)."""
+                 use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False):
+        """``elementwise_sections``, ``int8_add_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+        own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
-                      else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections))
+                      else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
+                                    int8_add_sections=int8_add_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.elementwise_sections:
+        if self.model.elementwise_sections or self.model.int8_add_sections:
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

@@ -157,6 +157,55 @@ lce_hip_status lce_hip_elementwise(const float* in_dev, size_t rows, size_t chan
                                    float* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * int8 residual ADD between binary layers (TFLite builtin) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* In an int8-converted residual network the batch norm is folded into LceBconv2d and the one operator left between two
+ * binary layers is TFLite's builtin int8 ADD of the shortcut.  lce_hip_add_int8 computes it byte for byte as TFLite's
+ * default (double-rounding) build does -- which is NOT the correctly rounded (s1 (x1 - z1) + s2 (x2 - z2)) / so:
+ *   prepare, once per operator, in double:
+ *     left_shift = 20; twice_max = 2 max(s1, s2); (m1, e1) = QuantizeMultiplier(s1 / twice_max); (m2, e2) likewise;
+ *     (mo, eo) = QuantizeMultiplier(twice_max / (2^20 so)); [act_min, act_max] = CalculateActivationRangeQuantized
+ *   per element, in int32 / int64:
+ *     sa = RDivPOT(SRDHM((x1 - z1) << 20, m1), -e1);  sb likewise;  out = clamp(RDivPOT(SRDHM(sa + sb, mo), -eo) + zo)
+ * over two NHWC int8 tensors ([rows, channels], rows = N*H*W) in ONE pass.  `out_dev` (nullable) gets the int8 sum and may
+ * be in1_dev or in2_dev (in place); `out_bits_dev` (nullable) gets the LceQuantize of the sum at ITS zero point, as
+ * lce_hip_bitpack(I8, ..., out_zero_point, ...) writes it: bit = out < zo, ceil(channels/32) words per row.
+ * Refused (LCE_HIP_ERR_INVALID, before any pointer is touched): a scale that is not finite and positive, a zero point
+ * outside [-128, 127], an activation other than NONE / RELU / RELU_N1_TO_1 / RELU6, a real multiplier outside (0, 1),
+ * both outputs NULL.  Zero rows or channels is a no-op.  Asynchronous on `stream`, capturable in a HIP graph, allocates
+ * nothing on the device (the parameters travel as kernel arguments; the host keeps what it derived per parameter set). */
+typedef struct lce_hip_add_int8_desc {
+  float in1_scale; int32_t in1_zero_point;
+  float in2_scale; int32_t in2_zero_point;
+  float out_scale; int32_t out_zero_point;
+  int32_t activation;       /* an lce_hip_activation */
+} lce_hip_add_int8_desc;
+typedef struct lce_hip_add_int8_params {
+  int32_t left_shift, in1_multiplier, in1_shift, in2_multiplier, in2_shift, out_multiplier, out_shift, act_min, act_max;
+} lce_hip_add_int8_params;
+/* TFLite's Prepare for this operator.  Host only: needs no device. */
+lce_hip_status lce_hip_add_int8_prepare(const lce_hip_add_int8_desc* desc, lce_hip_add_int8_params* params);
+lce_hip_status lce_hip_add_int8(const lce_hip_add_int8_desc* desc, const int8_t* in1_dev, const int8_t* in2_dev,
+                                size_t rows, size_t channels, int8_t* out_dev /* nullable */,
+                                int32_t* out_bits_dev /* nullable */, void* stream);
+/* The kernel has three variants of the per-element arithmetic that give the same bytes.  For each parameter set the host
+ * runs a cheap variant over all 65 536 input pairs against the literal formula and uses it only if every byte agrees:
+ *   LITERAL: the formula as written above (three 64-bit products); right for every parameter set.
+ *   SPLIT  : one input is a shift ((x - z) << k: its multiplier is 2^30), the other in 24-bit multiply-adds; one 64-bit
+ *            multiply-add in the output stage.
+ *   SHIFT  : both inputs are shifts (equal scales, power-of-two ratios).
+ * lce_hip_add_int8_variant reports the variant lce_hip_add_int8 uses for `desc` (host only).  lce_hip_add_int8_forced runs
+ * a given variant -- for tests and measurements -- and refuses one that is not proven for `desc`. */
+typedef enum lce_hip_add_int8_variant_id {
+  LCE_HIP_ADD_INT8_LITERAL = 0, LCE_HIP_ADD_INT8_SPLIT = 1, LCE_HIP_ADD_INT8_SHIFT = 2
+} lce_hip_add_int8_variant_id;
+lce_hip_status lce_hip_add_int8_variant(const lce_hip_add_int8_desc* desc, int32_t* variant);
+lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_t variant, const int8_t* in1_dev,
+                                       const int8_t* in2_dev, size_t rows, size_t channels, int8_t* out_dev,
+                                       int32_t* out_bits_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

@@ -38,8 +38,17 @@ lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err
  *   and head ops, and ops on unrelated branches, stay with the host).  lce_tflite_model_run_section then runs each chain
  *   of such operators as one lce_hip_elementwise launch, with the LceQuantize that reads its result as the launch's bit
  *   output.  Every other builtin operator still cuts a section.  The flag changes the partition -- the host's contract --
- *   and is therefore opt-in. */
-enum { LCE_TFLITE_SECTIONS_ELEMENTWISE = 1u };
+ *   and is therefore opt-in.
+ *   LCE_TFLITE_SECTIONS_INT8_ADD: the same for the int8 residual ADD of an int8-converted network (batch norm folded into
+ *   LceBconv2d, the shortcut added by the builtin int8 ADD).  A builtin ADD (0) joins the LCE epoch in which it becomes ready
+ *   when it has two inputs and one output, all three int8 WITH quantization parameters, the output is 4-D, both inputs are
+ *   non-constant tensors of the output's shape (batch ignored), its fused activation is NONE / RELU / RELU_N1_TO_1 / RELU6,
+ *   lce_hip_add_int8_prepare accepts its parameters, and one input is produced by an operator of the same epoch.  A constant
+ *   or broadcast int8 operand, int8 MUL or SUB, and uint8 / int16 tensors do not join.  lce_tflite_model_run_section runs
+ *   such an ADD as one lce_hip_add_int8 launch (TFLite's arithmetic byte for byte), with the first LceQuantize of the section
+ *   that reads the sum as the launch's bit output; the int8 sum is written only when something else reads it.
+ *   The flags combine; every other bit is refused. */
+enum { LCE_TFLITE_SECTIONS_ELEMENTWISE = 1u, LCE_TFLITE_SECTIONS_INT8_ADD = 2u };
 lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -128,6 +137,9 @@ void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, 
 /* The LAST run's lce_hip_elementwise launches (LCE_TFLITE_SECTIONS_ELEMENTWISE): launches, ADD / MUL operators they ran,
  * LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
 void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
+/* The LAST run's lce_hip_add_int8 launches (LCE_TFLITE_SECTIONS_INT8_ADD): launches (one per absorbed ADD) and LceQuantize
+ * operators whose launch they absorbed.  Any pointer may be NULL. */
+void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
