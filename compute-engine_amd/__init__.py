@@ -38,6 +38,7 @@ ABI_SYMBOLS = (
     "lce_hip_graph_begin_capture", "lce_hip_graph_end_capture", "lce_hip_graph_launch", "lce_hip_graph_destroy",
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
+    "lce_hip_concat",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -49,6 +50,7 @@ POST_ADD, POST_SUB, POST_MUL, POST_DIV = 0, 1, 2, 3
 EW_ADD, EW_MUL = 0, 1                                   # lce_hip_ew_op
 EW_SCALAR, EW_PER_CHANNEL, EW_TENSOR = 0, 1, 2          # lce_hip_ew_operand
 EW_MAX_STEPS = 8
+CONCAT_MAX_INPUTS = 8                                   # LCE_HIP_CONCAT_MAX_INPUTS
 ADD_INT8_LITERAL, ADD_INT8_SPLIT, ADD_INT8_SHIFT = 0, 1, 2   # lce_hip_add_int8_variant_id
 
 
@@ -132,6 +134,8 @@ def lib() -> C.CDLL:
                                        C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_add_int8_forced.argtypes = [C.POINTER(AddInt8Desc), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_concat.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_size_t, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -589,6 +593,79 @@ def add_int8(x1, x2, q1, q2, q_out, activation=ACT_NONE, out=None, out_bits=None
             out_bits[...] = ret_bits
             ret_bits = out_bits
         return ret_out, ret_bits
+    return out_d, bits_d
+
+
+def _concat_check(tensors, out, out_bits, zero_point):
+    """Argument checks of ``concat`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (lce_hip_dtype, leading shape, channels per input)."""
+    def dtype_name(a):
+        return str(a.dtype).replace("torch.", "")
+    tensors = list(tensors)
+    if not 2 <= len(tensors) <= CONCAT_MAX_INPUTS:
+        raise ValueError("concat: 2..%d tensors, got %d" % (CONCAT_MAX_INPUTS, len(tensors)))
+    name = dtype_name(tensors[0])
+    kinds = {"float32": F32, "int8": I8, "int32": BITPACKED}
+    if name not in kinds:
+        raise ValueError("concat: tensors must be float32, int8 or int32 (bitpacked), got %s" % name)
+    lead = tuple(tensors[0].shape[:-1])
+    for k, t in enumerate(tensors):
+        if dtype_name(t) != name or len(t.shape) < 1 or tuple(t.shape[:-1]) != lead or t.shape[-1] < 1:
+            raise ValueError("concat: tensor %d must be %s of shape %r + (C,), got %s %r" % (k, name, lead, dtype_name(t), tuple(t.shape)))
+    channels = [int(t.shape[-1]) for t in tensors]
+    kind = kinds[name]
+    if out_bits and kind == BITPACKED:
+        raise ValueError("concat: a bitpacked join has no bit output")
+    zp = int(zero_point)
+    if (kind == I8 and not -128 <= zp <= 127) or (kind != I8 and zp != 0):
+        raise ValueError("concat: zero point %r (int8: -128..127; otherwise 0)" % (zero_point,))
+    if out is False and not out_bits:
+        raise ValueError("concat: no output requested")
+    if out is not None and out is not False:
+        want = lead + (sum(channels),)
+        if dtype_name(out) != name or tuple(out.shape) != want:
+            raise ValueError("concat: out must be %s of shape %r, got %s %r" % (name, want, dtype_name(out), tuple(out.shape)))
+    return kind, lead, channels
+
+
+def concat(tensors, out=None, out_bits=False, zero_point: int = 0, stream: int | None = None):
+    """The channel join of a dense block -- TFLite's builtin CONCATENATION on the last axis -- and the LceQuantize of the
+    joined tensor, in one pass (``lce_hip_concat``).  ``tensors``: 2..8 tensors [..., C_k] of one dtype (float32, int8, or
+    int32 holding bitpacked words) and one leading shape, contiguous on one device (or NumPy: copied to cuda:0 and back);
+    one may appear twice.  ``out``: a tensor [..., sum C_k] to fill (it must not overlap an input), None for a new one, False
+    for none.  ``out_bits``: True for the int32 [..., ceil(sum C_k / 32)] bits of the joined tensor (float32: value < 0; int8:
+    value < ``zero_point``).  Returns ``(joined or None, bits or None)``."""
+    tensors = list(tensors)
+    kind, lead, channels = _concat_check(tensors, out, out_bits, zero_point)
+    import torch
+    host = isinstance(tensors[0], np.ndarray)
+    dev = torch.device("cuda:0") if host else tensors[0].device
+
+    def on_dev(a):
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
+        if not (t.is_cuda and t.device == dev and t.is_contiguous()):
+            raise ValueError("concat: tensors must be contiguous and on the first tensor's device %s" % dev)
+        return t
+
+    ins = [on_dev(t) for t in tensors]
+    total = sum(channels)
+    rows = ins[0].numel() // channels[0]
+    out_d = None if out is False else torch.empty(lead + (total,), dtype=ins[0].dtype, device=dev) if out is None else on_dev(out)
+    bits_d = torch.empty(lead + (bitpacked_size(total),), dtype=torch.int32, device=dev) if out_bits else None
+    ptrs = (C.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
+    ch = (C.c_int32 * len(ins))(*channels)
+    with torch.cuda.device(dev):
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().lce_hip_concat(kind, ptrs, ch, len(ins), rows, int(zero_point),
+                                   C.c_void_p(None if out_d is None else out_d.data_ptr()),
+                                   C.c_void_p(None if bits_d is None else bits_d.data_ptr()), C.c_void_p(stream)))
+    if host:
+        ret_out = None if out_d is None else out_d.cpu().numpy()
+        if isinstance(out, np.ndarray) and ret_out is not None:
+            out[...] = ret_out
+            ret_out = out
+        return ret_out, None if bits_d is None else bits_d.cpu().numpy()
     return out_d, bits_d
 
 

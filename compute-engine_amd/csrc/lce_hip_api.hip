@@ -19,6 +19,7 @@
 #include "lce_kernel_types.h"    // the convolution kernels live in their own translation units (lce_tu_*.hip)
 #include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip)
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
+#include "lce_kernels_concat.h"      // (lce_tu_concat.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -37,6 +38,7 @@
 #include "lce_tu_wstream_bitpacked.hip"
 #include "lce_tu_eltwise.hip"
 #include "lce_tu_eltwise_i8.hip"
+#include "lce_tu_concat.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -737,6 +739,75 @@ lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_
                                        int32_t* out_bits_dev, void* stream) {
   if (variant < 0) return fail(LCE_HIP_ERR_INVALID, "lce_hip_add_int8_forced: unknown variant %d", (int)variant);
   return add_int8_run(desc, variant, in1_dev, in2_dev, rows, channels, out_dev, out_bits_dev, stream, "lce_hip_add_int8_forced");
+}
+
+// ------------------------------------------------------------------------------------
+// Channel join (lce_kernels_concat.h)
+// ------------------------------------------------------------------------------------
+lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev, const int32_t* channels, int32_t num_inputs,
+                              size_t rows, int32_t zero_point, void* out_dev, int32_t* out_bits_dev, void* stream) {
+  if (type != LCE_HIP_F32 && type != LCE_HIP_I8 && type != LCE_HIP_BITPACKED)
+    return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: type must be float32, int8 or bitpacked int32, got %d", (int)type);
+  if (num_inputs < 2 || num_inputs > LCE_HIP_CONCAT_MAX_INPUTS)
+    return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: num_inputs must be 2..%d, got %d", LCE_HIP_CONCAT_MAX_INPUTS, (int)num_inputs);
+  if (!inputs_dev || !channels) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: null argument");
+  uint64_t sum = 0;
+  for (int32_t k = 0; k < num_inputs; ++k) {
+    if (channels[k] <= 0) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: input %d: channels must be positive, got %d", (int)k, (int)channels[k]);
+    sum += (uint64_t)channels[k];
+  }
+  if (sum >= (1ull << 31)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: the joined channel count must be below 2^31");
+  if (type == LCE_HIP_BITPACKED && out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: a bitpacked join has no bit output");
+  if (type == LCE_HIP_I8 ? (zero_point < -128 || zero_point > 127) : zero_point != 0)
+    return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: zero point %d (int8: -128..127; otherwise 0)", (int)zero_point);
+  if (rows == 0) return LCE_HIP_OK;   // (an empty tensor may come with null pointers)
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: both outputs are null");
+  if (rows >= (1ull << 32)) return fail(LCE_HIP_ERR_UNSUPPORTED, "lce_hip_concat: rows must be below 2^32");
+  const uint64_t esz = type == LCE_HIP_I8 ? 1 : 4;
+  const uint64_t wpr = (sum + 31) / 32;
+  // the output ranges must not meet an input range: the row pitches differ, so there is no in-place join
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? rows * sum * esz : 0);
+  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? rows * wpr * 4 : 0);
+  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t c0, uintptr_t c1) { return a0 < c1 && c0 < a1; };
+  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: the two outputs overlap");
+  bool vec = (o0 % 16 == 0) && (b0 % 4 == 0);
+  for (int32_t k = 0; k < num_inputs; ++k) {
+    if (!inputs_dev[k]) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: input %d is null", (int)k);
+    const uintptr_t i0 = (uintptr_t)inputs_dev[k], i1 = i0 + rows * (uint64_t)channels[k] * esz;
+    if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1))
+      return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: an output overlaps input %d", (int)k);
+    vec = vec && i0 % 16 == 0 && ((uint64_t)channels[k] * esz) % 16 == 0;
+  }
+  if (out_bits_dev && sum % 32 != 0) vec = false;   // (a word of bits then straddles rows of chunks)
+  if (lce_hip_status s = require_device()) return s;
+  lce::ConcatArgs a;
+  memset(&a, 0, sizeof a);
+  const uint64_t unit = vec ? 16 / esz : 1;          // elements per width unit
+  uint32_t at = 0;
+  for (int32_t k = 0; k < lce::kConcatMaxInputs; ++k) {
+    if (k >= num_inputs) { a.start[k] = 0xffffffffu; continue; }
+    a.in[k] = inputs_dev[k];
+    a.width[k] = (uint32_t)((uint64_t)channels[k] / unit);
+    a.start[k] = at;
+    at += a.width[k];
+  }
+  a.out = out_dev;
+  a.bits = (uint32_t*)out_bits_dev;
+  a.rows = rows;
+  a.total = at;
+  a.wpr = (uint32_t)wpr;
+  a.zero_point = zero_point;
+  if (vec) {
+    a.total_chunks = (uint64_t)rows * at;
+    const uint64_t stride = (uint64_t)lce::concat_vec_grid(a.total_chunks) * 4ull * 256ull;   // chunks per grid step
+    a.step_rows = stride / at;
+    a.step_cols = (uint32_t)(stride % at);
+    a.div_total = lce::make_fastdiv(at);
+  }
+  const int kind = type == LCE_HIP_F32 ? lce::kConcatF32 : type == LCE_HIP_I8 ? lce::kConcatI8 : lce::kConcatWords;
+  const int e = lce::launch_concat(a, kind, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_concat: launch failed: %s", hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
 }
 
 // ------------------------------------------------------------------------------------

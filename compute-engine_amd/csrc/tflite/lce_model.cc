@@ -37,6 +37,8 @@ struct lce_tflite_model {
   EwStats last_ew;                                                      // lce_hip_elementwise launches of the last run
   struct AddI8Stats { int32_t launches = 0, quantize = 0; };
   AddI8Stats last_add_i8;                                               // lce_hip_add_int8 launches of the last run
+  struct ConcatStats { int32_t launches = 0, quantize = 0; };
+  ConcatStats last_concat;                                              // lce_hip_concat launches of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
   // stream, tensor pointers) and replayed as one launch.  The first call with a key runs eagerly (plans are made, weights
   // uploaded, intermediate buffers sized), the second records, later ones replay.  Recorded launches hold the model's
@@ -49,7 +51,7 @@ struct lce_tflite_model {
       return std::tie(section, batch, semantics, stream, ptrs) < std::tie(o.section, o.batch, o.semantics, o.stream, o.ptrs);
     }
   };
-  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; int32_t fused = 0; EwStats ew; AddI8Stats add_i8; };
+  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; int32_t fused = 0; EwStats ew; AddI8Stats add_i8; ConcatStats concat; };
   std::map<GraphKey, GraphEntry> graphs;
   bool use_graphs = false;
   int32_t graph_captures = 0, graph_replays = 0;
@@ -138,7 +140,35 @@ bool Int8AddCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   lce_hip_add_int8_params p;
   return Int8AddDesc(M, o, &d) && lce_hip_add_int8_prepare(&d, &p) == LCE_HIP_OK;
 }
-enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2 };
+
+// The static half of "a builtin CONCATENATION that a section may run" (LCE_TFLITE_SECTIONS_CONCAT): the channel join of a dense
+// block.  2..8 inputs and one output, all of ONE type among float32, int8 and int32 (bitpacked), a 4-D output joined along its
+// last axis (3 or -1) with no fused activation, every input a non-constant 4-D tensor of the output's height and width, the
+// inputs' channels summing to the output's; for int8 every tensor carries quantization parameters with the SAME scale and
+// zero point (a requantizing join is the host's).  The other half -- it becomes ready in an LCE epoch -- is decided by
+// Partition().
+bool ConcatCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinConcatenation || o.outputs.size() != 1) return false;
+  if (o.inputs.size() < 2 || o.inputs.size() > (size_t)LCE_HIP_CONCAT_MAX_INPUTS) return false;
+  if ((o.axis != 3 && o.axis != -1) || o.activation != LCE_HIP_ACT_NONE) return false;
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (out.type != lce_tfl::kTensorFloat32 && out.type != lce_tfl::kTensorInt8 && out.type != lce_tfl::kTensorInt32) return false;
+  if (out.shape.size() != 4 || out.shape[3] <= 0) return false;
+  const bool i8 = out.type == lce_tfl::kTensorInt8;
+  if (i8 && (!out.quantized || out.zero_point < -128 || out.zero_point > 127)) return false;
+  int64_t sum = 0;
+  for (int32_t t : o.inputs) {
+    if (t < 0) return false;
+    const lce_tfl::Tensor& in = M.tensors[t];
+    if (in.type != out.type || in.data || in.shape.size() != 4 || in.shape[1] != out.shape[1] || in.shape[2] != out.shape[2] ||
+        in.shape[3] <= 0)
+      return false;
+    if (i8 && (!in.quantized || in.scale != out.scale || in.zero_point != out.zero_point)) return false;
+    sum += in.shape[3];
+  }
+  return sum == out.shape[3];
+}
+enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3 };
 }  // namespace
 
 // The partition a delegate would get (tensorflow/lite/graph_info.cc, PartitionGraphIntoIndependentNodeSubsets, restated from
@@ -163,6 +193,8 @@ void lce_tflite_model::Partition() {
     if (flags & LCE_TFLITE_SECTIONS_ELEMENTWISE) candidate[i] = ElementwiseCandidate(m, m.operators[i]) ? kAbsorbedElementwise : 0;
     // LCE_TFLITE_SECTIONS_INT8_ADD: the same rule for the int8 ADD of a shortcut
     if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_INT8_ADD)) candidate[i] = Int8AddCandidate(m, m.operators[i]) ? kAbsorbedInt8Add : 0;
+    // LCE_TFLITE_SECTIONS_CONCAT: the same rule for the channel join of a dense block
+    if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_CONCAT)) candidate[i] = ConcatCandidate(m, m.operators[i]) ? kAbsorbedConcat : 0;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -250,20 +282,36 @@ lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err
   return lce_tflite_model_open_ex(data, size, 0u, err, err_len);
 }
 
-lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len) {
+// Both entries funnel into ONE flags word; `allowed` is the entry's own mask.
+static lce_tflite_model* OpenWithFlags(const void* data, size_t size, uint32_t flags, uint32_t allowed, const char* refusal,
+                                       char* err, size_t err_len) {
   auto* model = new (std::nothrow) lce_tflite_model{};
   std::string e = "out of memory";
-  if (flags & ~(uint32_t)(LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD)) {
+  if (refusal) {
+    e = refusal;
+  } else if (flags & ~allowed) {
     e = "unknown flags";
   } else if (model && data && model->m.Parse(data, size, &e)) {
     model->flags = flags;
     model->Partition();
     return model;
   }
-  if (!data) e = "null buffer";
+  if (!data && !refusal) e = "null buffer";
   if (err && err_len) snprintf(err, err_len, "%s", e.c_str());
   delete model;
   return nullptr;
+}
+
+lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len) {
+  return OpenWithFlags(data, size, flags, LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD, nullptr, err, err_len);
+}
+
+lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
+                                             size_t err_len) {
+  const char* refusal = !options ? "null options"
+                        : options->struct_size != (uint32_t)sizeof(lce_tflite_open_options) ? "options: unknown struct_size" : nullptr;
+  return OpenWithFlags(data, size, refusal ? 0u : options->sections,
+                       LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD | LCE_TFLITE_SECTIONS_CONCAT, refusal, err, err_len);
 }
 
 void lce_tflite_model_close(lce_tflite_model* model) { delete model; }
@@ -319,6 +367,13 @@ lce_hip_status lce_tflite_model_operator_activation(const lce_tflite_model* mode
   if (!model || !activation || index < 0 || index >= (int32_t)model->m.operators.size())
     return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_activation: bad argument");
   *activation = model->m.operators[index].activation;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_tflite_model_operator_axis(const lce_tflite_model* model, int32_t index, int32_t* axis) {
+  if (!model || !axis || index < 0 || index >= (int32_t)model->m.operators.size())
+    return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_axis: bad argument");
+  *axis = model->m.operators[index].axis;
   return LCE_HIP_OK;
 }
 
@@ -688,6 +743,79 @@ lce_hip_status WalkInt8Add(lce_tflite_model* model, const lce_tflite_section& se
   return LCE_HIP_OK;
 }
 
+// An absorbed CONCATENATION (LCE_TFLITE_SECTIONS_CONCAT) as ONE lce_hip_concat launch.  The first LceQuantize of the section
+// that reads the joined tensor becomes the launch's bit output and its own launch disappears; the joined tensor itself is
+// written when anything else reads it (in a dense block the next join does) or the section delivers it.
+template <typename BufferFor>
+lce_hip_status WalkConcat(lce_tflite_model* model, const lce_tflite_section& sec, int32_t i, int32_t batch,
+                          std::map<int32_t, Shape>* shapes, std::map<int32_t, void*>* ptr, bool run, void* stream,
+                          BufferFor& buffer_for, std::vector<char>* done) {
+  const lce_tfl::Model& M = model->m;
+  const lce_tfl::Operator& op = M.operators[i];
+  const int32_t out_t = op.outputs[0];
+  const lce_tfl::Tensor& OT = M.tensors[out_t];
+  const std::vector<int32_t>& fs = OT.shape;
+  // the file's shapes were checked by the partition; the walk's inferred shape and type of EVERY input must agree with them
+  // (untrusted input: a producer whose output is smaller than the file declares must not be read past its buffer)
+  int32_t channels[LCE_HIP_CONCAT_MAX_INPUTS];
+  int64_t sum = 0;
+  const size_t n = op.inputs.size();
+  for (size_t k = 0; k < n; ++k) {
+    auto it = shapes->find(op.inputs[k]);
+    if (it == shapes->end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION reads a tensor nothing produced");
+    const Shape& xs = it->second;
+    const std::vector<int32_t>& is = M.tensors[op.inputs[k]].shape;
+    if (xs.type != OT.type || xs.dims[0] != batch || xs.dims[1] != fs[1] || xs.dims[2] != fs[2] || xs.dims[3] != is[3])
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION input's shape or type does not match the one its producer infers");
+    channels[k] = xs.dims[3];
+    sum += xs.dims[3];
+  }
+  if (sum != fs[3]) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION's inputs do not add up to its output");
+  Shape os;
+  os.dims[0] = batch; os.dims[1] = fs[1]; os.dims[2] = fs[2]; os.dims[3] = fs[3];
+  os.type = OT.type;
+  (*shapes)[out_t] = os;
+  (*done)[i] = 1;
+  auto is_section_output = [&](int32_t t) { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); };
+  int32_t quant = -1;
+  if (OT.type != lce_tfl::kTensorInt32)
+    for (int32_t j : sec.ops) {
+      const lce_tfl::Operator& q = M.operators[j];
+      if (j > i && !(*done)[j] && q.builtin_code == lce_tfl::kBuiltinCustom && q.custom_code == "LceQuantize" &&
+          q.inputs.size() == 1 && q.inputs[0] == out_t && q.outputs.size() == 1) { quant = j; break; }
+    }
+  bool need_out = quant < 0 || is_section_output(out_t);
+  for (int32_t r : model->readers[out_t]) need_out = need_out || r != quant;
+  int32_t bits_t = -1;
+  if (quant >= 0) {
+    (*done)[quant] = 1;
+    bits_t = M.operators[quant].outputs[0];
+    Shape q = os;
+    q.dims[3] = (os.dims[3] + 31) / 32;
+    q.type = lce_tfl::kTensorInt32;
+    (*shapes)[bits_t] = q;
+  }
+  if (!run) return LCE_HIP_OK;
+  const void* in[LCE_HIP_CONCAT_MAX_INPUTS];
+  for (size_t k = 0; k < n; ++k) {
+    auto p = ptr->find(op.inputs[k]);
+    if (p == ptr->end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of a CONCATENATION input");
+    in[k] = p->second;
+  }
+  void* out = nullptr;
+  void* bits = nullptr;
+  if (need_out)
+    if (lce_hip_status s = buffer_for(out_t, os.bytes(), &out)) return s;
+  if (quant >= 0)
+    if (lce_hip_status s = buffer_for(bits_t, (*shapes)[bits_t].bytes(), &bits)) return s;
+  const lce_hip_dtype type = OT.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : OT.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BITPACKED;
+  if (lce_hip_status s = lce_hip_concat(type, in, channels, (int32_t)n, (size_t)batch * fs[1] * fs[2],
+                                        type == LCE_HIP_I8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
+  ++model->last_concat.launches;
+  if (quant >= 0) ++model->last_concat.quantize;
+  return LCE_HIP_OK;
+}
+
 // Walks section `sec` at `batch` images: shapes of every tensor it touches (shape inference exactly as the ops' Prepare
 // does it) and, with `run`, the launches.  `ptr` maps tensor -> device pointer (section inputs and outputs on entry;
 // intermediates are added from the model's scratch buffers).
@@ -729,6 +857,10 @@ lce_hip_status WalkSection(lce_tflite_model* model, const lce_tflite_section& se
     if (done[i]) continue;
     if (model->absorbed[i] == kAbsorbedInt8Add) {
       if (lce_hip_status s = WalkInt8Add(model, sec, i, batch, shapes, ptr, run, stream, buffer_for, &done)) return s;
+      continue;
+    }
+    if (model->absorbed[i] == kAbsorbedConcat) {
+      if (lce_hip_status s = WalkConcat(model, sec, i, batch, shapes, ptr, run, stream, buffer_for, &done)) return s;
       continue;
     }
     if (model->absorbed[i]) {
@@ -873,6 +1005,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
   model->last_run_fused = 0;
   model->last_ew = lce_tflite_model::EwStats();
   model->last_add_i8 = lce_tflite_model::AddI8Stats();
+  model->last_concat = lce_tflite_model::ConcatStats();
   if (!model->use_graphs || !stream) return WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
 
   lce_tflite_model::GraphKey key{section, batch, semantics, stream, {}};
@@ -884,6 +1017,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       model->last_run_fused = e.fused;
       model->last_ew = e.ew;
       model->last_add_i8 = e.add_i8;
+      model->last_concat = e.concat;
       ++model->graph_replays;
       return lce_hip_graph_launch(e.graph, stream);
     }
@@ -894,6 +1028,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       int32_t fused = 0;
       lce_tflite_model::EwStats ew;
       lce_tflite_model::AddI8Stats add_i8;
+      lce_tflite_model::ConcatStats concat;
       if (lce_hip_graph_begin_capture(stream) == LCE_HIP_OK) {
         std::map<int32_t, Shape> shapes_c;
         std::map<int32_t, void*> ptr_c = ptr;
@@ -903,6 +1038,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
         fused = model->last_run_fused;
         ew = model->last_ew;
         add_i8 = model->last_add_i8;
+        concat = model->last_concat;
         if (!recorded && g) { lce_hip_graph_destroy(g); g = nullptr; }
       }
       g_model_error.clear();
@@ -912,6 +1048,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
         e2.fused = fused;
         e2.ew = ew;
         e2.add_i8 = add_i8;
+        e2.concat = concat;
         e2.eager_runs = 1;
         ++model->graph_captures;
         ++model->graph_replays;
@@ -921,6 +1058,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       model->last_run_fused = 0;
       model->last_ew = lce_tflite_model::EwStats();
       model->last_add_i8 = lce_tflite_model::AddI8Stats();
+  model->last_concat = lce_tflite_model::ConcatStats();
     }
   }
   const lce_hip_status s = WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
@@ -955,6 +1093,13 @@ void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches,
   std::lock_guard<std::mutex> lock(model->run_mu);
   if (launches) *launches = model->last_add_i8.launches;
   if (quantize_folded) *quantize_folded = model->last_add_i8.quantize;
+}
+
+void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (launches) *launches = model->last_concat.launches;
+  if (quantize_folded) *quantize_folded = model->last_concat.quantize;
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

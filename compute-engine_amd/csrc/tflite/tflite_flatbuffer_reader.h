@@ -18,6 +18,8 @@
 //   Buffer           0 data[ubyte]
 //   BuiltinOptions union types: 11 AddOptions, 21 MulOptions; both tables: 0 fused_activation_function(int8,
 //   ActivationFunctionType: 0 NONE, 1 RELU, 2 RELU_N1_TO_1, 3 RELU6, 4 TANH, 5 SIGN_BIT); BuiltinOperator 0 ADD, 18 MUL.
+//   BuiltinOptions union type 10 ConcatenationOptions: 0 axis(int32, default 0), 1 fused_activation_function(int8);
+//   BuiltinOperator 2 CONCATENATION.
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -34,8 +36,8 @@
 namespace lce_tfl {
 
 constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
-constexpr int32_t kBuiltinAdd = 0, kBuiltinMul = 18;
-constexpr int kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
+constexpr int32_t kBuiltinAdd = 0, kBuiltinConcatenation = 2, kBuiltinMul = 18;
+constexpr int kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 // TensorType values used by LCE graphs
 constexpr int kTensorFloat32 = 0, kTensorInt32 = 2, kTensorBool = 6, kTensorInt8 = 9;
 
@@ -57,7 +59,8 @@ struct Operator {
   std::vector<int32_t> inputs, outputs;   // tensor indices, -1 = optional input not present
   const uint8_t* custom_options = nullptr;
   size_t custom_options_size = 0;
-  int32_t activation = 0;          // fused_activation_function of AddOptions / MulOptions; 0 (NONE) when absent
+  int32_t activation = 0;          // fused_activation_function of AddOptions / MulOptions / ConcatenationOptions; 0 (NONE) when absent
+  int32_t axis = 0;                // ConcatenationOptions.axis; 0 when absent
 };
 
 class Model {
@@ -232,6 +235,14 @@ class Model {
       if ((opt_type == kOptionsAdd || opt_type == kOptionsMul) && opt_pos != 0) {
         int8_t act;
         if (!Indirect(opt_pos, &opt) || !Scalar<int8_t>(opt, 0, 0, &act)) return Fail("bad AddOptions / MulOptions");
+        O.activation = act;
+      }
+      if (opt_type == kOptionsConcatenation && opt_pos != 0) {
+        int32_t axis;
+        int8_t act;
+        if (!Indirect(opt_pos, &opt) || !Scalar<int32_t>(opt, 0, 0, &axis) || !Scalar<int8_t>(opt, 1, 0, &act))
+          return Fail("bad ConcatenationOptions");
+        O.axis = axis;
         O.activation = act;
       }
       for (int32_t x : O.inputs) if (x < -1 || x >= (int32_t)nt) return Fail("Operator input index out of range");

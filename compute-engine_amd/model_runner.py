@@ -19,6 +19,9 @@ between binary layers -- batch norm constants, residual shortcuts -- join the se
 per chain (``lce_hip_elementwise``); a graph whose every operator then lies in a section runs through ``predict``.
 With ``int8_add_sections=True`` (LCE_TFLITE_SECTIONS_INT8_ADD) the int8 residual ADD of an int8-converted network joins the
 sections in the same way (``lce_hip_add_int8``: TFLite's integer arithmetic byte for byte); the two flags combine.
+With ``concat_sections=True`` (LCE_TFLITE_SECTIONS_CONCAT, ``lce_tflite_model_open_opts``) the channel CONCATENATION of a
+dense network (BinaryDenseNet, MeliusNet) joins them too (``lce_hip_concat``); with ``elementwise_sections`` a float dense
+block is one section.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -37,6 +40,7 @@ _tfl = None
 FLOAT32, INT32, BOOL, INT8 = 0, 2, 6, 9
 SECTIONS_ELEMENTWISE = 1          # LCE_TFLITE_SECTIONS_ELEMENTWISE
 SECTIONS_INT8_ADD = 2             # LCE_TFLITE_SECTIONS_INT8_ADD
+SECTIONS_CONCAT = 4               # LCE_TFLITE_SECTIONS_CONCAT (lce_tflite_model_open_opts only)
 _NP = {FLOAT32: np.float32, INT32: np.int32, BOOL: np.bool_, INT8: np.int8}
 LCE_OPS = ("LceQuantize", "LceDequantize", "LceBconv2d", "LceBMaxPool2d")
 
@@ -56,6 +60,11 @@ class _OperatorInfo(C.Structure):
 class _SectionInfo(C.Structure):
     _fields_ = [("ops", C.POINTER(C.c_int32)), ("num_ops", C.c_int32), ("inputs", C.POINTER(C.c_int32)), ("num_inputs", C.c_int32),
                 ("outputs", C.POINTER(C.c_int32)), ("num_outputs", C.c_int32)]
+
+
+class _OpenOptions(C.Structure):
+    """``lce_tflite_open_options``."""
+    _fields_ = [("struct_size", C.c_uint32), ("sections", C.c_uint32)]
 
 
 class Section:
@@ -83,6 +92,11 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_open.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
         l.lce_tflite_model_open_ex.restype = C.c_void_p
         l.lce_tflite_model_open_ex.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_char_p, C.c_size_t]
+        l.lce_tflite_model_open_opts.restype = C.c_void_p
+        l.lce_tflite_model_open_opts.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_OpenOptions), C.c_char_p, C.c_size_t]
+        l.lce_tflite_model_operator_axis.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        l.lce_tflite_model_concat_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
+        l.lce_tflite_model_concat_stats.restype = None
         l.lce_tflite_model_operator_activation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_elementwise_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
         l.lce_tflite_model_elementwise_stats.restype = None
@@ -125,9 +139,10 @@ class Tensor:
 
 
 class Operator:
-    def __init__(self, info: _OperatorInfo, activation: int = 0):
+    def __init__(self, info: _OperatorInfo, activation: int = 0, axis: int = 0):
         self.builtin_code = info.builtin_code
-        self.activation = activation          # fused_activation_function of a builtin ADD / MUL (0: NONE)
+        self.activation = activation          # fused_activation_function of a builtin ADD / MUL / CONCATENATION (0: NONE)
+        self.axis = axis                      # axis of a builtin CONCATENATION as the file says (0 when absent)
         self.custom_code = (info.custom_code or b"").decode()
         self.inputs = [info.inputs[i] for i in range(info.num_inputs)]
         self.outputs = [info.outputs[i] for i in range(info.num_outputs)]
@@ -143,19 +158,25 @@ class LceModel:
     """A parsed .tflite flatbuffer (first subgraph)."""
 
     def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
-                 int8_add_sections: bool = False):
+                 int8_add_sections: bool = False, concat_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
-        residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD)."""
+        residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
+        CONCATENATION of a dense block joins them (LCE_TFLITE_SECTIONS_CONCAT, through ``lce_tflite_model_open_opts``)."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
         self._data = bytes(flatbuffer)            # must outlive the handle (zero-copy reader)
         self.elementwise_sections = bool(elementwise_sections)
         self.int8_add_sections = bool(int8_add_sections)
+        self.concat_sections = bool(concat_sections)
         err = C.create_string_buffer(256)
         flags = (SECTIONS_ELEMENTWISE if elementwise_sections else 0) | (SECTIONS_INT8_ADD if int8_add_sections else 0)
-        self._h = tflite_lib().lce_tflite_model_open_ex(self._data, len(self._data), flags, err, 256)
+        if concat_sections:
+            opts = _OpenOptions(C.sizeof(_OpenOptions), flags | SECTIONS_CONCAT)
+            self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
+        else:
+            self._h = tflite_lib().lce_tflite_model_open_ex(self._data, len(self._data), flags, err, 256)
         if not self._h:
             raise ValueError("not a readable TFLite model: " + err.value.decode(errors="replace"))
         l = tflite_lib()
@@ -170,7 +191,9 @@ class LceModel:
             _amd.check(l.lce_tflite_model_operator(self._h, i, C.byref(info)))
             act = C.c_int32()
             _amd.check(l.lce_tflite_model_operator_activation(self._h, i, C.byref(act)))
-            self.operators.append(Operator(info, act.value))
+            axis = C.c_int32()
+            _amd.check(l.lce_tflite_model_operator_axis(self._h, i, C.byref(axis)))
+            self.operators.append(Operator(info, act.value, axis.value))
         buf = (C.c_int32 * 64)()
         self.inputs = [buf[i] for i in range(l.lce_tflite_model_inputs(self._h, buf, 64))]
         self.outputs = [buf[i] for i in range(l.lce_tflite_model_outputs(self._h, buf, 64))]
@@ -223,6 +246,12 @@ class LceModel:
         tflite_lib().lce_tflite_model_int8_add_stats(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    def concat_stats(self):
+        """(lce_hip_concat launches, LceQuantize launches they absorbed) of the last run."""
+        a, b = C.c_int32(), C.c_int32()
+        tflite_lib().lce_tflite_model_concat_stats(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -251,16 +280,17 @@ class Interpreter:
     """``Interpreter(flatbuffer_model, batch_size=...)`` -- see the module docstring."""
 
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
-                 use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False):
-        """``elementwise_sections``, ``int8_add_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+                 use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
+                 concat_sections: bool = False):
+        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
-                                    int8_add_sections=int8_add_sections))
+                                    int8_add_sections=int8_add_sections, concat_sections=concat_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.elementwise_sections or self.model.int8_add_sections:
+        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections:
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

@@ -206,6 +206,30 @@ lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_
                                        int32_t* out_bits_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Channel join between binary layers (TFLite builtin CONCATENATION) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* A converted dense binary network (BinaryDenseNet, MeliusNet) joins every binary layer's output to its input with the
+ * builtin CONCATENATION on the channel axis.  lce_hip_concat joins `num_inputs` (2..8) NHWC tensors [rows, channels[k]]
+ * (rows = N*H*W) of ONE element type -- F32, I8 or BITPACKED (int32 words, channels[k] counted in words) -- along the last
+ * axis into [rows, sum channels[k]] in ONE pass.  `out_dev` (nullable) gets exactly the bytes of the inputs side by side:
+ * a copy, so float NaN payloads, -0.0 and subnormals come through untouched.  `out_bits_dev` (nullable; F32 and I8 only)
+ * gets the LceQuantize of the joined tensor as lce_hip_bitpack(type, out, rows, sum, zero_point, ...) writes it: bit =
+ * out < 0 (F32) or out < zero_point (I8), ceil(sum/32) words per row, padding bits 0 -- from the values the copy holds,
+ * the inputs are read once.  The same input may appear twice.  `inputs_dev` and `channels` are host arrays read at the call.
+ * Refused (LCE_HIP_ERR_INVALID, before any device pointer is dereferenced or a device touched): num_inputs outside 2..8,
+ * a channels[k] <= 0 (or a sum of 2^31 or more), a type other than the three, bits for BITPACKED, a zero point outside
+ * [-128, 127] for I8 or non-zero otherwise, both outputs NULL, a NULL input, an output range that overlaps an input range or
+ * the other output (the row pitches differ: there is no in-place join).  Zero rows is a no-op (checked before the
+ * pointers).  rows must be below 2^32; the byte counts are unbounded (64-bit offsets throughout).  Asynchronous on
+ * `stream`, capturable in a HIP graph, allocates nothing and copies nothing between host and device (offsets and counts
+ * travel as kernel arguments). */
+#define LCE_HIP_CONCAT_MAX_INPUTS 8
+lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev, const int32_t* channels,
+                              int32_t num_inputs, size_t rows, int32_t zero_point, void* out_dev /* nullable */,
+                              int32_t* out_bits_dev /* nullable */, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

@@ -50,6 +50,29 @@ lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err
  *   The flags combine; every other bit is refused. */
 enum { LCE_TFLITE_SECTIONS_ELEMENTWISE = 1u, LCE_TFLITE_SECTIONS_INT8_ADD = 2u };
 lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len);
+
+/* lce_tflite_model_open with an options struct: the entry that new opt-ins extend (lce_tflite_model_open_ex keeps its two
+ * flags and refuses every other bit).  `struct_size` must be sizeof(lce_tflite_open_options); `sections` takes the two
+ * flags above with the meaning given there, and
+ *   LCE_TFLITE_SECTIONS_CONCAT: the same for the channel join of a DENSE network (BinaryDenseNet, MeliusNet: each binary
+ *   layer's output is joined to its input by the builtin CONCATENATION).  A CONCATENATION (2) joins the LCE epoch in which
+ *   it becomes ready when it has 2..8 inputs and one output, all tensors of one type among float32, int8 and int32, the
+ *   output is 4-D and the axis is 3 or -1, its fused activation is NONE, every input is a non-constant 4-D tensor of the
+ *   output's height and width, the inputs' channels add up to the output's, and -- for int8 -- all inputs and the output
+ *   carry quantization parameters with the SAME scale and zero point (a requantizing join stays with the host).  A join
+ *   that is ready from the start is the host's.  lce_tflite_model_run_section runs such a join as one lce_hip_concat
+ *   launch, with the first LceQuantize of the section that reads the joined tensor as the launch's bit output; the joined
+ *   tensor itself is written only when something else reads it or the section delivers it.  Together with
+ *   LCE_TFLITE_SECTIONS_ELEMENTWISE a float dense block is one section; the float MAX_POOL_2D / CONV_2D of a transition
+ *   block still cut.
+ * sections == 0..3 gives exactly lce_tflite_model_open_ex with that value; every other bit is refused. */
+enum { LCE_TFLITE_SECTIONS_CONCAT = 4u };
+typedef struct lce_tflite_open_options {
+  uint32_t struct_size;    /* sizeof(lce_tflite_open_options) */
+  uint32_t sections;       /* LCE_TFLITE_SECTIONS_* */
+} lce_tflite_open_options;
+lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
+                                             size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
 int32_t lce_tflite_model_num_tensors(const lce_tflite_model* model);
@@ -85,6 +108,9 @@ lce_hip_status lce_tflite_model_operator(const lce_tflite_model* model, int32_t 
 /* fused_activation_function of a builtin ADD / MUL (AddOptions / MulOptions: lce_hip_activation values, and 4 TANH /
  * 5 SIGN_BIT as the file says); 0 (NONE) when the options table is absent and for every other operator. */
 lce_hip_status lce_tflite_model_operator_activation(const lce_tflite_model* model, int32_t index, int32_t* activation);
+/* axis of a builtin CONCATENATION (ConcatenationOptions, as the file says: may be negative); 0 when the options table is
+ * absent and for every other operator.  Its fused activation is reported by the call above. */
+lce_hip_status lce_tflite_model_operator_axis(const lce_tflite_model* model, int32_t index, int32_t* axis);
 
 /* Binary SECTIONS of a mixed graph.  A converted model interleaves builtin float operators (the stem, batch norms, adds,
  * the head) with LCE custom ops; what this library runs are the maximal groups of LCE ops that can execute without a
@@ -140,6 +166,9 @@ void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launch
 /* The LAST run's lce_hip_add_int8 launches (LCE_TFLITE_SECTIONS_INT8_ADD): launches (one per absorbed ADD) and LceQuantize
  * operators whose launch they absorbed.  Any pointer may be NULL. */
 void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's lce_hip_concat launches (LCE_TFLITE_SECTIONS_CONCAT): launches (one per absorbed CONCATENATION) and
+ * LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
+void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
