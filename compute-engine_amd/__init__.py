@@ -393,12 +393,63 @@ def unpack(words, channels: int, dtype, scale: float = 1.0, zero_point: int = 0,
     return out
 
 
+# ---- what the fused passes between binary layers share (elementwise, add_int8, concat) ----
+def _dtype_name(a):
+    return str(a.dtype).replace("torch.", "")
+
+
+def _check_outputs(who, out, out_bits, dtype, shape):
+    """The ``out`` (a tensor to fill, None, or False) and ``out_bits`` (a tensor to fill, True, or None) of a pass that produces
+    a ``dtype`` tensor of ``shape``, on shapes and dtypes only (NumPy or torch): nothing here touches a device."""
+    if out is False and out_bits is None:
+        raise ValueError("%s: no output requested" % who)
+    want_bits = shape[:-1] + (bitpacked_size(shape[-1]),)
+    for name, a, dt, want in (("out", out, dtype, shape), ("out_bits", out_bits, "int32", want_bits)):
+        if a is not None and a is not False and a is not True and (tuple(a.shape) != want or _dtype_name(a) != dt):
+            raise ValueError("%s: %s must be %s of shape %r, got %s %r" % (who, name, dt, want, a.dtype, tuple(a.shape)))
+
+
+def _on_dev(a, dev, who, whose):
+    """``a`` as a contiguous tensor on ``dev`` (a NumPy array is copied there); ``whose`` device that is, for the message."""
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
+    if not (t.is_cuda and t.device == dev and t.is_contiguous()):
+        raise ValueError("%s: tensors must be contiguous and on %s device %s" % (who, whose, dev))
+    return t
+
+
+def _new_bits(lead, channels, dev):
+    import torch
+    return torch.empty(tuple(lead) + (bitpacked_size(channels),), dtype=torch.int32, device=dev)
+
+
+def _stream_or_current(stream, dev):
+    import torch
+    return torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+
+
+def _dev_ptr(t):
+    return C.c_void_p(None if t is None else t.data_ptr())
+
+
+def _results(host, out_d, bits_d, out=None, out_bits=None):
+    """What a pass returns: the device tensors, or for NumPy input NumPy arrays (the caller's own where they passed some)."""
+    if not host:
+        return out_d, bits_d
+    ret = []
+    for t, mine in ((out_d, out), (bits_d, out_bits)):
+        a = None if t is None else t.cpu().numpy()
+        if isinstance(mine, np.ndarray) and a is not None:
+            mine[...] = a
+            a = mine
+        ret.append(a)
+    return tuple(ret)
+
+
 def _ew_check(x, steps, out, out_bits):
     """Argument checks of ``elementwise`` on shapes and dtypes only (NumPy or torch): nothing here touches a device."""
-    def dtype_name(a):
-        return str(a.dtype).replace("torch.", "")
     shape = tuple(x.shape)
-    if dtype_name(x) != "float32" or len(shape) < 1:
+    if _dtype_name(x) != "float32" or len(shape) < 1:
         raise ValueError("elementwise: x must be a float32 tensor with a channel axis, got %s %r" % (x.dtype, shape))
     channels = shape[-1]
     if not isinstance(steps, (list, tuple)) or not 1 <= len(steps) <= EW_MAX_STEPS:
@@ -418,7 +469,7 @@ def _ew_check(x, steps, out, out_bits):
             kinds.append(EW_SCALAR)
             continue
         oshape = tuple(operand.shape)
-        if dtype_name(operand) != "float32":
+        if _dtype_name(operand) != "float32":
             raise ValueError("elementwise: step %d: operand must be float32, got %s" % (k, operand.dtype))
         if oshape == shape:
             kinds.append(EW_TENSOR)
@@ -426,15 +477,7 @@ def _ew_check(x, steps, out, out_bits):
             kinds.append(EW_PER_CHANNEL)
         else:
             raise ValueError("elementwise: step %d: operand shape %r is neither x's %r nor [channels] (%d,)" % (k, oshape, shape, channels))
-    if out is False and out_bits is None:
-        raise ValueError("elementwise: no output requested")
-    if out is not None and out is not False:
-        if tuple(out.shape) != shape or dtype_name(out) != "float32":
-            raise ValueError("elementwise: out must be float32 of shape %r, got %s %r" % (shape, out.dtype, tuple(out.shape)))
-    if out_bits is not None and out_bits is not True:
-        want = shape[:-1] + (bitpacked_size(channels),)
-        if tuple(out_bits.shape) != want or dtype_name(out_bits) != "int32":
-            raise ValueError("elementwise: out_bits must be int32 of shape %r, got %s %r" % (want, out_bits.dtype, tuple(out_bits.shape)))
+    _check_outputs("elementwise", out, out_bits, "float32", shape)
     return kinds
 
 
@@ -449,23 +492,13 @@ def elementwise(x, steps, out=None, out_bits=None, stream: int | None = None):
     import torch
     host = isinstance(x, np.ndarray)
     dev = torch.device("cuda:0") if host else x.device
-
-    def on_dev(a):
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
-        if not (t.is_cuda and t.device == dev and t.is_contiguous()):
-            raise ValueError("elementwise: tensors must be contiguous and on x's device %s" % dev)
-        return t
-
+    on_dev = lambda a: _on_dev(a, dev, "elementwise", "x's")
     xd = on_dev(x)
     operands = [None if k == EW_SCALAR else on_dev(step[1]) for k, step in zip(kinds, steps)]
     channels = x.shape[-1]
     rows = xd.numel() // channels if channels else 0
     out_d = None if out is False else torch.empty_like(xd) if out is None else on_dev(out)
-    bits_d = None
-    if out_bits is True:
-        bits_d = torch.empty(tuple(xd.shape[:-1]) + (bitpacked_size(channels),), dtype=torch.int32, device=dev)
-    elif out_bits is not None:
-        bits_d = on_dev(out_bits)
+    bits_d = None if out_bits is None else _new_bits(xd.shape[:-1], channels, dev) if out_bits is True else on_dev(out_bits)
     arr = (EwStep * len(steps))()
     for k, ((op, operand, act), kind, t) in enumerate(zip(steps, kinds, operands)):
         arr[k].op = {EW_ADD: EW_ADD, EW_MUL: EW_MUL, "add": EW_ADD, "mul": EW_MUL}[op]
@@ -474,22 +507,9 @@ def elementwise(x, steps, out=None, out_bits=None, stream: int | None = None):
         arr[k].scalar = float(operand) if kind == EW_SCALAR else 0.0
         arr[k].activation = int(act)
     with torch.cuda.device(dev):
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().lce_hip_elementwise(C.c_void_p(xd.data_ptr()), rows, channels, arr, len(steps),
-                                        C.c_void_p(None if out_d is None else out_d.data_ptr()),
-                                        C.c_void_p(None if bits_d is None else bits_d.data_ptr()), C.c_void_p(stream)))
-    if host:
-        ret_out = None if out_d is None else out_d.cpu().numpy()
-        if isinstance(out, np.ndarray) and ret_out is not None:
-            out[...] = ret_out
-            ret_out = out
-        ret_bits = None if bits_d is None else bits_d.cpu().numpy()
-        if isinstance(out_bits, np.ndarray) and ret_bits is not None:
-            out_bits[...] = ret_bits
-            ret_bits = out_bits
-        return ret_out, ret_bits
-    return out_d, bits_d
+        check(lib().lce_hip_elementwise(_dev_ptr(xd), rows, channels, arr, len(steps), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                        C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, out, out_bits)
 
 
 def _add_int8_desc(q1, q2, q_out, activation) -> AddInt8Desc:
@@ -524,22 +544,12 @@ def add_int8_params(q1, q2, q_out, activation=ACT_NONE) -> dict:
 
 def _add_int8_check(x1, x2, out, out_bits):
     """Argument checks of ``add_int8`` on shapes and dtypes only (NumPy or torch): nothing here touches a device."""
-    def dtype_name(a):
-        return str(a.dtype).replace("torch.", "")
     shape = tuple(x1.shape)
-    if dtype_name(x1) != "int8" or len(shape) < 1:
+    if _dtype_name(x1) != "int8" or len(shape) < 1:
         raise ValueError("add_int8: x1 must be an int8 tensor with a channel axis, got %s %r" % (x1.dtype, shape))
-    if dtype_name(x2) != "int8" or tuple(x2.shape) != shape:
+    if _dtype_name(x2) != "int8" or tuple(x2.shape) != shape:
         raise ValueError("add_int8: x2 must be int8 of x1's shape %r, got %s %r" % (shape, x2.dtype, tuple(x2.shape)))
-    if out is False and out_bits is None:
-        raise ValueError("add_int8: no output requested")
-    if out is not None and out is not False:
-        if tuple(out.shape) != shape or dtype_name(out) != "int8":
-            raise ValueError("add_int8: out must be int8 of shape %r, got %s %r" % (shape, out.dtype, tuple(out.shape)))
-    if out_bits is not None and out_bits is not True:
-        want = shape[:-1] + (bitpacked_size(shape[-1]),)
-        if tuple(out_bits.shape) != want or dtype_name(out_bits) != "int32":
-            raise ValueError("add_int8: out_bits must be int32 of shape %r, got %s %r" % (want, out_bits.dtype, tuple(out_bits.shape)))
+    _check_outputs("add_int8", out, out_bits, "int8", shape)
 
 
 def add_int8(x1, x2, q1, q2, q_out, activation=ACT_NONE, out=None, out_bits=None, stream: int | None = None,
@@ -558,60 +568,35 @@ def add_int8(x1, x2, q1, q2, q_out, activation=ACT_NONE, out=None, out_bits=None
     import torch
     host = isinstance(x1, np.ndarray)
     dev = torch.device("cuda:0") if host else x1.device
-
-    def on_dev(a):
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
-        if not (t.is_cuda and t.device == dev and t.is_contiguous()):
-            raise ValueError("add_int8: tensors must be contiguous and on x1's device %s" % dev)
-        return t
-
+    on_dev = lambda a: _on_dev(a, dev, "add_int8", "x1's")
     a, b = on_dev(x1), on_dev(x2)
     channels = x1.shape[-1]
     rows = a.numel() // channels if channels else 0
     out_d = None if out is False else torch.empty_like(a) if out is None else on_dev(out)
-    bits_d = None
-    if out_bits is True:
-        bits_d = torch.empty(tuple(a.shape[:-1]) + (bitpacked_size(channels),), dtype=torch.int32, device=dev)
-    elif out_bits is not None:
-        bits_d = on_dev(out_bits)
-    ptrs = (C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), rows, channels,
-            C.c_void_p(None if out_d is None else out_d.data_ptr()), C.c_void_p(None if bits_d is None else bits_d.data_ptr()))
+    bits_d = None if out_bits is None else _new_bits(a.shape[:-1], channels, dev) if out_bits is True else on_dev(out_bits)
+    args = (_dev_ptr(a), _dev_ptr(b), rows, channels, _dev_ptr(out_d), _dev_ptr(bits_d), C.c_void_p(_stream_or_current(stream, dev)))
     with torch.cuda.device(dev):
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
         if variant is None:
-            check(lib().lce_hip_add_int8(C.byref(desc), *ptrs, C.c_void_p(stream)))
+            check(lib().lce_hip_add_int8(C.byref(desc), *args))
         else:
-            check(lib().lce_hip_add_int8_forced(C.byref(desc), int(variant), *ptrs, C.c_void_p(stream)))
-    if host:
-        ret_out = None if out_d is None else out_d.cpu().numpy()
-        if isinstance(out, np.ndarray) and ret_out is not None:
-            out[...] = ret_out
-            ret_out = out
-        ret_bits = None if bits_d is None else bits_d.cpu().numpy()
-        if isinstance(out_bits, np.ndarray) and ret_bits is not None:
-            out_bits[...] = ret_bits
-            ret_bits = out_bits
-        return ret_out, ret_bits
-    return out_d, bits_d
+            check(lib().lce_hip_add_int8_forced(C.byref(desc), int(variant), *args))
+    return _results(host, out_d, bits_d, out, out_bits)
 
 
 def _concat_check(tensors, out, out_bits, zero_point):
     """Argument checks of ``concat`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
     (lce_hip_dtype, leading shape, channels per input)."""
-    def dtype_name(a):
-        return str(a.dtype).replace("torch.", "")
     tensors = list(tensors)
     if not 2 <= len(tensors) <= CONCAT_MAX_INPUTS:
         raise ValueError("concat: 2..%d tensors, got %d" % (CONCAT_MAX_INPUTS, len(tensors)))
-    name = dtype_name(tensors[0])
+    name = _dtype_name(tensors[0])
     kinds = {"float32": F32, "int8": I8, "int32": BITPACKED}
     if name not in kinds:
         raise ValueError("concat: tensors must be float32, int8 or int32 (bitpacked), got %s" % name)
     lead = tuple(tensors[0].shape[:-1])
     for k, t in enumerate(tensors):
-        if dtype_name(t) != name or len(t.shape) < 1 or tuple(t.shape[:-1]) != lead or t.shape[-1] < 1:
-            raise ValueError("concat: tensor %d must be %s of shape %r + (C,), got %s %r" % (k, name, lead, dtype_name(t), tuple(t.shape)))
+        if _dtype_name(t) != name or len(t.shape) < 1 or tuple(t.shape[:-1]) != lead or t.shape[-1] < 1:
+            raise ValueError("concat: tensor %d must be %s of shape %r + (C,), got %s %r" % (k, name, lead, _dtype_name(t), tuple(t.shape)))
     channels = [int(t.shape[-1]) for t in tensors]
     kind = kinds[name]
     if out_bits and kind == BITPACKED:
@@ -619,12 +604,7 @@ def _concat_check(tensors, out, out_bits, zero_point):
     zp = int(zero_point)
     if (kind == I8 and not -128 <= zp <= 127) or (kind != I8 and zp != 0):
         raise ValueError("concat: zero point %r (int8: -128..127; otherwise 0)" % (zero_point,))
-    if out is False and not out_bits:
-        raise ValueError("concat: no output requested")
-    if out is not None and out is not False:
-        want = lead + (sum(channels),)
-        if dtype_name(out) != name or tuple(out.shape) != want:
-            raise ValueError("concat: out must be %s of shape %r, got %s %r" % (name, want, dtype_name(out), tuple(out.shape)))
+    _check_outputs("concat", out, True if out_bits else None, name, lead + (sum(channels),))
     return kind, lead, channels
 
 
@@ -640,33 +620,18 @@ def concat(tensors, out=None, out_bits=False, zero_point: int = 0, stream: int |
     import torch
     host = isinstance(tensors[0], np.ndarray)
     dev = torch.device("cuda:0") if host else tensors[0].device
-
-    def on_dev(a):
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a
-        if not (t.is_cuda and t.device == dev and t.is_contiguous()):
-            raise ValueError("concat: tensors must be contiguous and on the first tensor's device %s" % dev)
-        return t
-
+    on_dev = lambda a: _on_dev(a, dev, "concat", "the first tensor's")
     ins = [on_dev(t) for t in tensors]
     total = sum(channels)
     rows = ins[0].numel() // channels[0]
     out_d = None if out is False else torch.empty(lead + (total,), dtype=ins[0].dtype, device=dev) if out is None else on_dev(out)
-    bits_d = torch.empty(lead + (bitpacked_size(total),), dtype=torch.int32, device=dev) if out_bits else None
+    bits_d = _new_bits(lead, total, dev) if out_bits else None
     ptrs = (C.c_void_p * len(ins))(*[t.data_ptr() for t in ins])
     ch = (C.c_int32 * len(ins))(*channels)
     with torch.cuda.device(dev):
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().lce_hip_concat(kind, ptrs, ch, len(ins), rows, int(zero_point),
-                                   C.c_void_p(None if out_d is None else out_d.data_ptr()),
-                                   C.c_void_p(None if bits_d is None else bits_d.data_ptr()), C.c_void_p(stream)))
-    if host:
-        ret_out = None if out_d is None else out_d.cpu().numpy()
-        if isinstance(out, np.ndarray) and ret_out is not None:
-            out[...] = ret_out
-            ret_out = out
-        return ret_out, None if bits_d is None else bits_d.cpu().numpy()
-    return out_d, bits_d
+        check(lib().lce_hip_concat(kind, ptrs, ch, len(ins), rows, int(zero_point), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                   C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, out)
 
 
 def bmaxpool(x, filter_height, filter_width, stride_height, stride_width, padding, stream: int | None = None, out=None):

@@ -31,14 +31,15 @@ struct lce_tflite_model {
   std::map<std::pair<int32_t, int64_t>, lce_hip_bconv2d_plan*> plans;   // (operator, batch * 2 + semantics) -> ready plan
   struct DevBuf { void* ptr = nullptr; size_t bytes = 0; };
   std::map<int32_t, DevBuf> scratch;                                    // intermediate tensors of a section, grow-only
-  int32_t last_run_fused = 0;                                           // LceQuantize launches the last run folded into a convolution
   std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
-  struct EwStats { int32_t launches = 0, ops = 0, quantize = 0; };
-  EwStats last_ew;                                                      // lce_hip_elementwise launches of the last run
-  struct AddI8Stats { int32_t launches = 0, quantize = 0; };
-  AddI8Stats last_add_i8;                                               // lce_hip_add_int8 launches of the last run
-  struct ConcatStats { int32_t launches = 0, quantize = 0; };
-  ConcatStats last_concat;                                              // lce_hip_concat launches of the last run
+  // What one run launched.  A recorded graph keeps the record of its recording, so a replay reports the same numbers.
+  struct RunStats {
+    int32_t conv_quantize = 0;                                          // LceQuantize launches folded into a convolution (run_dual)
+    int32_t ew_ops = 0;                                                 // ADD / MUL operators inside the lce_hip_elementwise launches
+    struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
+    Pass ew, add_i8, concat;                                            // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat
+  };
+  RunStats last;                                                        // of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
   // stream, tensor pointers) and replayed as one launch.  The first call with a key runs eagerly (plans are made, weights
   // uploaded, intermediate buffers sized), the second records, later ones replay.  Recorded launches hold the model's
@@ -51,7 +52,7 @@ struct lce_tflite_model {
       return std::tie(section, batch, semantics, stream, ptrs) < std::tie(o.section, o.batch, o.semantics, o.stream, o.ptrs);
     }
   };
-  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; int32_t fused = 0; EwStats ew; AddI8Stats add_i8; ConcatStats concat; };
+  struct GraphEntry { int32_t eager_runs = 0; void* graph = nullptr; bool unrecordable = false; RunStats stats; };
   std::map<GraphKey, GraphEntry> graphs;
   bool use_graphs = false;
   int32_t graph_captures = 0, graph_replays = 0;
@@ -83,6 +84,12 @@ int64_t BroadcastCount(const lce_tfl::Tensor& t) {
   return -1;
 }
 
+// A non-constant 4-D tensor of `out`'s height and width: what a fused pass streams next to its output (batch ignored, the
+// channels are the caller's to check).
+bool SameImage(const lce_tfl::Tensor& in, const lce_tfl::Tensor& out) {
+  return !in.data && in.shape.size() == 4 && in.shape[1] == out.shape[1] && in.shape[2] == out.shape[2];
+}
+
 // The static half of "a builtin ADD / MUL that a section may run" (LCE_TFLITE_SECTIONS_ELEMENTWISE): float32 in and out, a
 // 4-D output, each input either a non-constant tensor of the output's shape (batch ignored) or a constant of shape [C],
 // [1,1,1,C], [1] or [], and an activation lce_hip_elementwise knows.  The other half -- one of its non-constant inputs is
@@ -102,7 +109,7 @@ bool ElementwiseCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
       const int64_t n = BroadcastCount(in);
       if ((n != 1 && n != out.shape[3]) || in.bytes != (size_t)n * 4) return false;
     } else {
-      if (in.shape.size() != 4 || in.shape[1] != out.shape[1] || in.shape[2] != out.shape[2] || in.shape[3] != out.shape[3]) return false;
+      if (!SameImage(in, out) || in.shape[3] != out.shape[3]) return false;
       ++variable;
     }
   }
@@ -133,8 +140,7 @@ bool Int8AddCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   if (out.shape.size() != 4 || out.shape[3] <= 0) return false;
   for (int32_t t : o.inputs) {
     const lce_tfl::Tensor& in = M.tensors[t];
-    if (in.data || in.shape.size() != 4 || in.shape[1] != out.shape[1] || in.shape[2] != out.shape[2] || in.shape[3] != out.shape[3])
-      return false;
+    if (!SameImage(in, out) || in.shape[3] != out.shape[3]) return false;
   }
   lce_hip_add_int8_desc d;
   lce_hip_add_int8_params p;
@@ -160,9 +166,7 @@ bool ConcatCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   for (int32_t t : o.inputs) {
     if (t < 0) return false;
     const lce_tfl::Tensor& in = M.tensors[t];
-    if (in.type != out.type || in.data || in.shape.size() != 4 || in.shape[1] != out.shape[1] || in.shape[2] != out.shape[2] ||
-        in.shape[3] <= 0)
-      return false;
+    if (in.type != out.type || !SameImage(in, out) || in.shape[3] <= 0) return false;
     if (i8 && (!in.quantized || in.scale != out.scale || in.zero_point != out.zero_point)) return false;
     sum += in.shape[3];
   }
@@ -564,277 +568,41 @@ lce_hip_status ConstOnDevice(lce_tflite_model* model, int32_t t, void* stream, b
   return LCE_HIP_OK;
 }
 
-// A maximal chain of absorbed ADD / MUL operators that starts at operator `first`, as ONE lce_hip_elementwise launch.  The
-// chain streams a float tensor x (an input of `first`: an LceBconv2d output or a section input) and extends through an
-// operator whose input tensor has exactly one reader and is not a section output (up to 8 steps); the other input of each
-// operator is the step's operand (a constant: scalar or per channel; otherwise a tensor of x's shape).  The chain's last
-// tensor is written in float when anything but a folded LceQuantize reads it or the section delivers it; the first
-// LceQuantize of the section that reads it becomes the launch's bit output and its own launch disappears.
-template <typename BufferFor>
-lce_hip_status WalkElementwiseChain(lce_tflite_model* model, const lce_tflite_section& sec, int32_t first, int32_t batch,
-                                    std::map<int32_t, Shape>* shapes, std::map<int32_t, void*>* ptr, bool run, void* stream,
-                                    bool capturing, BufferFor& buffer_for, std::vector<char>* done) {
-  const lce_tfl::Model& M = model->m;
-  auto is_section_output = [&](int32_t t) { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); };
-  const lce_tfl::Operator& op0 = M.operators[first];
-  const int32_t x_t = M.tensors[op0.inputs[0]].data ? op0.inputs[1] : op0.inputs[0];
-  auto x_it = shapes->find(x_t);
-  if (x_it == shapes->end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
-  const Shape xs = x_it->second;
-  const std::vector<int32_t>& fs = M.tensors[op0.outputs[0]].shape;
-  // the file's shapes were checked by the partition; the walk's inferred shape must agree with them (untrusted input)
-  if (xs.type != lce_tfl::kTensorFloat32 || xs.dims[0] != batch || xs.dims[1] != fs[1] || xs.dims[2] != fs[2] || xs.dims[3] != fs[3])
-    return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL input's shape does not match the one its producer infers");
-  const size_t rows = (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2], channels = (size_t)xs.dims[3];
-
-  std::vector<lce_hip_ew_step> steps;
-  std::vector<int32_t> chain;
-  int32_t cur = first, v_t = x_t;
-  // the operand of operator `o` whose streamed input is `v`; false when it is not available yet (produced further down)
-  auto operand_of = [&](const lce_tfl::Operator& o, int32_t v, lce_hip_ew_step* st) -> lce_hip_status {
-    const int32_t other = (o.inputs[0] == v) ? o.inputs[1] : o.inputs[0];
-    const lce_tfl::Tensor& T = M.tensors[other];
-    memset(st, 0, sizeof *st);
-    st->op = o.builtin_code == lce_tfl::kBuiltinMul ? LCE_HIP_EW_MUL : LCE_HIP_EW_ADD;
-    st->activation = o.activation;
-    if (T.data) {
-      if (T.bytes == 4) {
-        st->operand = LCE_HIP_EW_SCALAR;
-        memcpy(&st->scalar, T.data, 4);
-      } else {
-        st->operand = LCE_HIP_EW_PER_CHANNEL;
-        if (T.bytes != channels * 4) return Fail(LCE_HIP_ERR_INVALID, "run_section: a per-channel constant does not match the channels");
-        if (run) {
-          const float* d = nullptr;
-          if (lce_hip_status s = ConstOnDevice(model, other, stream, capturing, &d)) return s;
-          st->values = d;
-        }
-      }
-      return LCE_HIP_OK;
-    }
-    auto it = shapes->find(other);
-    if (it == shapes->end()) return LCE_HIP_ERR_UNSUPPORTED;        // (not an error: the chain stops before `o`)
-    const Shape& os = it->second;
-    if (os.type != lce_tfl::kTensorFloat32 || memcmp(os.dims, xs.dims, sizeof xs.dims) != 0)
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: the two tensors of an ADD / MUL differ in shape");
-    st->operand = LCE_HIP_EW_TENSOR;
-    if (run) {
-      auto p = ptr->find(other);
-      if (p == ptr->end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of an ADD / MUL input");
-      st->values = (const float*)p->second;
-    }
-    return LCE_HIP_OK;
-  };
-  for (;;) {
-    const lce_tfl::Operator& o = M.operators[cur];
-    lce_hip_ew_step st;
-    const lce_hip_status s = operand_of(o, v_t, &st);
-    if (s == LCE_HIP_ERR_UNSUPPORTED && chain.empty())
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
-    if (s == LCE_HIP_ERR_UNSUPPORTED) break;
-    if (s != LCE_HIP_OK) return s;
-    steps.push_back(st);
-    chain.push_back(cur);
-    (*done)[cur] = 1;
-    v_t = o.outputs[0];
-    Shape vs = xs;
-    (*shapes)[v_t] = vs;
-    const std::vector<int32_t>& rd = model->readers[v_t];
-    if (steps.size() == 8 || rd.size() != 1 || is_section_output(v_t)) break;
-    const int32_t next = rd[0];
-    if (model->absorbed[next] != kAbsorbedElementwise || (*done)[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
-    cur = next;
-  }
-  // the LceQuantize that becomes the launch's bit output
-  int32_t quant = -1;
-  for (int32_t j : sec.ops) {
-    const lce_tfl::Operator& q = M.operators[j];
-    if (j > chain.back() && !(*done)[j] && q.builtin_code == lce_tfl::kBuiltinCustom && q.custom_code == "LceQuantize" &&
-        q.inputs.size() == 1 && q.inputs[0] == v_t && q.outputs.size() == 1) { quant = j; break; }
-  }
-  bool need_float = quant < 0 || is_section_output(v_t);
-  for (int32_t r : model->readers[v_t]) need_float = need_float || r != quant;
-  int32_t bits_t = -1;
-  if (quant >= 0) {
-    (*done)[quant] = 1;
-    bits_t = M.operators[quant].outputs[0];
-    Shape q = xs;
-    q.dims[3] = (xs.dims[3] + 31) / 32;
-    q.type = lce_tfl::kTensorInt32;
-    (*shapes)[bits_t] = q;
-  }
-  if (!run) return LCE_HIP_OK;
-  auto in = ptr->find(x_t);
-  if (in == ptr->end() || !in->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of an ADD / MUL input");
-  void* out = nullptr;
-  void* bits = nullptr;
-  if (need_float)
-    if (lce_hip_status s = buffer_for(v_t, (*shapes)[v_t].bytes(), &out)) return s;
-  if (quant >= 0)
-    if (lce_hip_status s = buffer_for(bits_t, (*shapes)[bits_t].bytes(), &bits)) return s;
-  if (lce_hip_status s = lce_hip_elementwise((const float*)in->second, rows, channels, steps.data(), (int32_t)steps.size(),
-                                             (float*)out, (int32_t*)bits, stream)) return s;
-  ++model->last_ew.launches;
-  model->last_ew.ops += (int32_t)chain.size();
-  if (quant >= 0) ++model->last_ew.quantize;
-  return LCE_HIP_OK;
-}
-
-// An absorbed int8 ADD (LCE_TFLITE_SECTIONS_INT8_ADD) as ONE lce_hip_add_int8 launch.  The first LceQuantize of the section
-// that reads the sum becomes the launch's bit output and its own launch disappears; the int8 sum is written when anything
-// else reads it (in a residual chain the next ADD does) or the section delivers it.
-template <typename BufferFor>
-lce_hip_status WalkInt8Add(lce_tflite_model* model, const lce_tflite_section& sec, int32_t i, int32_t batch,
-                           std::map<int32_t, Shape>* shapes, std::map<int32_t, void*>* ptr, bool run, void* stream,
-                           BufferFor& buffer_for, std::vector<char>* done) {
-  const lce_tfl::Model& M = model->m;
-  const lce_tfl::Operator& op = M.operators[i];
-  const int32_t out_t = op.outputs[0];
-  const std::vector<int32_t>& fs = M.tensors[out_t].shape;
-  // the file's shapes were checked by the partition; the walk's inferred shape and type of BOTH inputs must agree with them
-  // (untrusted input: a convolution whose output is smaller than the file declares must not be read past its buffer)
-  Shape xs;
-  for (int k = 0; k < 2; ++k) {
-    auto it = shapes->find(op.inputs[k]);
-    if (it == shapes->end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD reads a tensor nothing produced");
-    xs = it->second;
-    if (xs.type != lce_tfl::kTensorInt8 || xs.dims[0] != batch || xs.dims[1] != fs[1] || xs.dims[2] != fs[2] || xs.dims[3] != fs[3])
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD input's shape or type does not match the one its producer infers");
-  }
-  (*shapes)[out_t] = xs;
-  (*done)[i] = 1;
-  auto is_section_output = [&](int32_t t) { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); };
-  int32_t quant = -1;
-  for (int32_t j : sec.ops) {
-    const lce_tfl::Operator& q = M.operators[j];
-    if (j > i && !(*done)[j] && q.builtin_code == lce_tfl::kBuiltinCustom && q.custom_code == "LceQuantize" &&
-        q.inputs.size() == 1 && q.inputs[0] == out_t && q.outputs.size() == 1) { quant = j; break; }
-  }
-  bool need_int8 = quant < 0 || is_section_output(out_t);
-  for (int32_t r : model->readers[out_t]) need_int8 = need_int8 || r != quant;
-  int32_t bits_t = -1;
-  if (quant >= 0) {
-    (*done)[quant] = 1;
-    bits_t = M.operators[quant].outputs[0];
-    Shape q = xs;
-    q.dims[3] = (xs.dims[3] + 31) / 32;
-    q.type = lce_tfl::kTensorInt32;
-    (*shapes)[bits_t] = q;
-  }
-  if (!run) return LCE_HIP_OK;
-  lce_hip_add_int8_desc d;
-  if (!Int8AddDesc(M, op, &d)) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD without quantization parameters");
-  const void* in[2];
-  for (int k = 0; k < 2; ++k) {
-    auto p = ptr->find(op.inputs[k]);
-    if (p == ptr->end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of an int8 ADD input");
-    in[k] = p->second;
-  }
-  void* out = nullptr;
-  void* bits = nullptr;
-  if (need_int8)
-    if (lce_hip_status s = buffer_for(out_t, xs.bytes(), &out)) return s;
-  if (quant >= 0)
-    if (lce_hip_status s = buffer_for(bits_t, (*shapes)[bits_t].bytes(), &bits)) return s;
-  if (lce_hip_status s = lce_hip_add_int8(&d, (const int8_t*)in[0], (const int8_t*)in[1], (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2],
-                                          (size_t)xs.dims[3], (int8_t*)out, (int32_t*)bits, stream)) return s;
-  ++model->last_add_i8.launches;
-  if (quant >= 0) ++model->last_add_i8.quantize;
-  return LCE_HIP_OK;
-}
-
-// An absorbed CONCATENATION (LCE_TFLITE_SECTIONS_CONCAT) as ONE lce_hip_concat launch.  The first LceQuantize of the section
-// that reads the joined tensor becomes the launch's bit output and its own launch disappears; the joined tensor itself is
-// written when anything else reads it (in a dense block the next join does) or the section delivers it.
-template <typename BufferFor>
-lce_hip_status WalkConcat(lce_tflite_model* model, const lce_tflite_section& sec, int32_t i, int32_t batch,
-                          std::map<int32_t, Shape>* shapes, std::map<int32_t, void*>* ptr, bool run, void* stream,
-                          BufferFor& buffer_for, std::vector<char>* done) {
-  const lce_tfl::Model& M = model->m;
-  const lce_tfl::Operator& op = M.operators[i];
-  const int32_t out_t = op.outputs[0];
-  const lce_tfl::Tensor& OT = M.tensors[out_t];
-  const std::vector<int32_t>& fs = OT.shape;
-  // the file's shapes were checked by the partition; the walk's inferred shape and type of EVERY input must agree with them
-  // (untrusted input: a producer whose output is smaller than the file declares must not be read past its buffer)
-  int32_t channels[LCE_HIP_CONCAT_MAX_INPUTS];
-  int64_t sum = 0;
-  const size_t n = op.inputs.size();
-  for (size_t k = 0; k < n; ++k) {
-    auto it = shapes->find(op.inputs[k]);
-    if (it == shapes->end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION reads a tensor nothing produced");
-    const Shape& xs = it->second;
-    const std::vector<int32_t>& is = M.tensors[op.inputs[k]].shape;
-    if (xs.type != OT.type || xs.dims[0] != batch || xs.dims[1] != fs[1] || xs.dims[2] != fs[2] || xs.dims[3] != is[3])
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION input's shape or type does not match the one its producer infers");
-    channels[k] = xs.dims[3];
-    sum += xs.dims[3];
-  }
-  if (sum != fs[3]) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION's inputs do not add up to its output");
-  Shape os;
-  os.dims[0] = batch; os.dims[1] = fs[1]; os.dims[2] = fs[2]; os.dims[3] = fs[3];
-  os.type = OT.type;
-  (*shapes)[out_t] = os;
-  (*done)[i] = 1;
-  auto is_section_output = [&](int32_t t) { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); };
-  int32_t quant = -1;
-  if (OT.type != lce_tfl::kTensorInt32)
-    for (int32_t j : sec.ops) {
-      const lce_tfl::Operator& q = M.operators[j];
-      if (j > i && !(*done)[j] && q.builtin_code == lce_tfl::kBuiltinCustom && q.custom_code == "LceQuantize" &&
-          q.inputs.size() == 1 && q.inputs[0] == out_t && q.outputs.size() == 1) { quant = j; break; }
-    }
-  bool need_out = quant < 0 || is_section_output(out_t);
-  for (int32_t r : model->readers[out_t]) need_out = need_out || r != quant;
-  int32_t bits_t = -1;
-  if (quant >= 0) {
-    (*done)[quant] = 1;
-    bits_t = M.operators[quant].outputs[0];
-    Shape q = os;
-    q.dims[3] = (os.dims[3] + 31) / 32;
-    q.type = lce_tfl::kTensorInt32;
-    (*shapes)[bits_t] = q;
-  }
-  if (!run) return LCE_HIP_OK;
-  const void* in[LCE_HIP_CONCAT_MAX_INPUTS];
-  for (size_t k = 0; k < n; ++k) {
-    auto p = ptr->find(op.inputs[k]);
-    if (p == ptr->end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of a CONCATENATION input");
-    in[k] = p->second;
-  }
-  void* out = nullptr;
-  void* bits = nullptr;
-  if (need_out)
-    if (lce_hip_status s = buffer_for(out_t, os.bytes(), &out)) return s;
-  if (quant >= 0)
-    if (lce_hip_status s = buffer_for(bits_t, (*shapes)[bits_t].bytes(), &bits)) return s;
-  const lce_hip_dtype type = OT.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : OT.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BITPACKED;
-  if (lce_hip_status s = lce_hip_concat(type, in, channels, (int32_t)n, (size_t)batch * fs[1] * fs[2],
-                                        type == LCE_HIP_I8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
-  ++model->last_concat.launches;
-  if (quant >= 0) ++model->last_concat.quantize;
-  return LCE_HIP_OK;
-}
-
-// Walks section `sec` at `batch` images: shapes of every tensor it touches (shape inference exactly as the ops' Prepare
+// One walk of a section at `batch` images: shapes of every tensor it touches (shape inference exactly as the ops' Prepare
 // does it) and, with `run`, the launches.  `ptr` maps tensor -> device pointer (section inputs and outputs on entry;
-// intermediates are added from the model's scratch buffers).
-lce_hip_status WalkSection(lce_tflite_model* model, const lce_tflite_section& sec, int32_t batch, int32_t semantics,
-                           std::map<int32_t, Shape>* shapes, std::map<int32_t, void*>* ptr, bool run, void* stream,
-                           bool capturing = false) {
-  const lce_tfl::Model& M = model->m;
-  for (int32_t t : sec.inputs) {
-    const lce_tfl::Tensor& T = M.tensors[t];
-    if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
-    Shape sh;
-    for (int k = 0; k < 4; ++k) sh.dims[k] = T.shape[k];
-    sh.dims[0] = batch;
-    sh.type = T.type;
-    (*shapes)[t] = sh;
+// intermediates are added from the model's scratch buffers).  A fused pass between binary layers plugs in as a candidate
+// predicate (above), a walker here that ends in FoldQuantize / FoldBuffers, and its counters in RunStats.
+struct Walk {
+  lce_tflite_model* model;
+  const lce_tflite_section& sec;
+  int32_t batch, semantics;
+  bool run;
+  void* stream;
+  bool capturing;                        // `stream` records a HIP graph: nothing may be allocated, freed or uploaded
+  std::map<int32_t, void*> ptr;
+  std::map<int32_t, Shape> shapes;
+  std::vector<char> done;                // per operator: a launch further up has already produced its output
+
+  bool IsSectionOutput(int32_t t) const { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); }
+
+  // The walk's inferred shape `s` is a `type` tensor of `batch` x h x w x c.  The file's shapes were checked by the partition;
+  // what the walk infers must agree with them (untrusted input).
+  bool Agrees(const Shape& s, int type, int32_t h, int32_t w, int32_t c) const {
+    return s.type == type && s.dims[0] == batch && s.dims[1] == h && s.dims[2] == w && s.dims[3] == c;
   }
-  auto buffer_for = [&](int32_t t, size_t bytes, void** out) -> lce_hip_status {
-    auto it = ptr->find(t);
-    if (it != ptr->end()) { *out = it->second; return LCE_HIP_OK; }
+
+  // Device pointer of tensor `t`, which `what` reads ("an input tensor", "a CONCATENATION input", ...).
+  lce_hip_status DevicePtr(int32_t t, const char* what, const void** out) const {
+    auto p = ptr.find(t);
+    if (p == ptr.end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of " + std::string(what));
+    *out = p->second;
+    return LCE_HIP_OK;
+  }
+
+  // Device buffer of tensor `t`: the caller's for a section input or output, otherwise the model's grow-only scratch buffer.
+  lce_hip_status BufferFor(int32_t t, size_t bytes, void** out) {
+    auto it = ptr.find(t);
+    if (it != ptr.end()) { *out = it->second; return LCE_HIP_OK; }
     lce_tflite_model::DevBuf& b = model->scratch[t];
     if (b.bytes < bytes) {
       // while `stream` records a graph nothing may be freed or allocated (a hipFree / hipMalloc inside a capture invalidates it and
@@ -848,123 +616,357 @@ lce_hip_status WalkSection(lce_tflite_model* model, const lce_tflite_section& se
       if (lce_hip_status s = lce_hip_malloc(&b.ptr, bytes ? bytes : 1)) return s;
       b.bytes = bytes;
     }
-    (*ptr)[t] = b.ptr;
+    ptr[t] = b.ptr;
     *out = b.ptr;
     return LCE_HIP_OK;
+  }
+
+  // Where the result of a fused pass (an ADD / MUL chain, an int8 ADD, a CONCATENATION) goes.
+  struct Fold {
+    int32_t value_t;                     // the tensor the pass produces
+    int32_t bits_t = -1;                 // the output of the folded LceQuantize; -1: none
+    bool need_value = true;              // false: only the folded LceQuantize reads value_t, so it is not written
   };
-  std::vector<char> done(M.operators.size(), 0);
-  for (int32_t i : sec.ops) {
-    if (done[i]) continue;
-    if (model->absorbed[i] == kAbsorbedInt8Add) {
-      if (lce_hip_status s = WalkInt8Add(model, sec, i, batch, shapes, ptr, run, stream, buffer_for, &done)) return s;
-      continue;
+  // THE fold rule.  Tensor `t` of shape `s` is produced by a pass whose last operator is `last`.  The first LceQuantize of the
+  // section after `last` that reads `t` and has not run becomes the pass's bit output (`allowed`: a bitpacked join has none):
+  // it is marked done -- its own launch disappears -- and its output's shape registered.  `t` itself is still written when
+  // nothing folds, when the section delivers it, or when anything but the folded LceQuantize reads it.
+  Fold FoldQuantize(int32_t last, int32_t t, const Shape& s, bool allowed = true) {
+    const lce_tfl::Model& M = model->m;
+    Fold f{t};
+    int32_t quant = -1;
+    if (allowed)
+      for (int32_t j : sec.ops) {
+        const lce_tfl::Operator& q = M.operators[j];
+        if (j > last && !done[j] && q.builtin_code == lce_tfl::kBuiltinCustom && q.custom_code == "LceQuantize" &&
+            q.inputs.size() == 1 && q.inputs[0] == t && q.outputs.size() == 1) { quant = j; break; }
+      }
+    f.need_value = quant < 0 || IsSectionOutput(t);
+    for (int32_t r : model->readers[t]) f.need_value = f.need_value || r != quant;
+    if (quant >= 0) {
+      done[quant] = 1;
+      f.bits_t = M.operators[quant].outputs[0];
+      Shape q = s;
+      q.dims[3] = (s.dims[3] + 31) / 32;
+      q.type = lce_tfl::kTensorInt32;
+      shapes[f.bits_t] = q;
     }
-    if (model->absorbed[i] == kAbsorbedConcat) {
-      if (lce_hip_status s = WalkConcat(model, sec, i, batch, shapes, ptr, run, stream, buffer_for, &done)) return s;
-      continue;
+    return f;
+  }
+  // The (value, bits) buffers of a fused pass; null for an output that is not written.
+  lce_hip_status FoldBuffers(const Fold& f, void** value, void** bits) {
+    *value = *bits = nullptr;
+    if (f.need_value)
+      if (lce_hip_status s = BufferFor(f.value_t, shapes[f.value_t].bytes(), value)) return s;
+    if (f.bits_t >= 0)
+      if (lce_hip_status s = BufferFor(f.bits_t, shapes[f.bits_t].bytes(), bits)) return s;
+    return LCE_HIP_OK;
+  }
+
+  // A maximal chain of absorbed ADD / MUL operators that starts at operator `first`, as ONE lce_hip_elementwise launch.  The
+  // chain streams a float tensor x (an input of `first`: an LceBconv2d output or a section input) and extends through an
+  // operator whose input tensor has exactly one reader and is not a section output (up to 8 steps); the other input of each
+  // operator is the step's operand (a constant: scalar or per channel; otherwise a tensor of x's shape).  The chain's last
+  // tensor is written in float when anything but a folded LceQuantize reads it or the section delivers it; the first
+  // LceQuantize of the section that reads it becomes the launch's bit output and its own launch disappears.
+  lce_hip_status ElementwiseChain(int32_t first) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op0 = M.operators[first];
+    const int32_t x_t = M.tensors[op0.inputs[0]].data ? op0.inputs[1] : op0.inputs[0];
+    auto x_it = shapes.find(x_t);
+    if (x_it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
+    const Shape xs = x_it->second;
+    const std::vector<int32_t>& fs = M.tensors[op0.outputs[0]].shape;
+    if (!Agrees(xs, lce_tfl::kTensorFloat32, fs[1], fs[2], fs[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL input's shape does not match the one its producer infers");
+    const size_t rows = (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2], channels = (size_t)xs.dims[3];
+
+    std::vector<lce_hip_ew_step> steps;
+    std::vector<int32_t> chain;
+    int32_t cur = first, v_t = x_t;
+    // the operand of operator `o` whose streamed input is `v`; false when it is not available yet (produced further down)
+    auto operand_of = [&](const lce_tfl::Operator& o, int32_t v, lce_hip_ew_step* st) -> lce_hip_status {
+      const int32_t other = (o.inputs[0] == v) ? o.inputs[1] : o.inputs[0];
+      const lce_tfl::Tensor& T = M.tensors[other];
+      memset(st, 0, sizeof *st);
+      st->op = o.builtin_code == lce_tfl::kBuiltinMul ? LCE_HIP_EW_MUL : LCE_HIP_EW_ADD;
+      st->activation = o.activation;
+      if (T.data) {
+        if (T.bytes == 4) {
+          st->operand = LCE_HIP_EW_SCALAR;
+          memcpy(&st->scalar, T.data, 4);
+        } else {
+          st->operand = LCE_HIP_EW_PER_CHANNEL;
+          if (T.bytes != channels * 4) return Fail(LCE_HIP_ERR_INVALID, "run_section: a per-channel constant does not match the channels");
+          if (run) {
+            const float* d = nullptr;
+            if (lce_hip_status s = ConstOnDevice(model, other, stream, capturing, &d)) return s;
+            st->values = d;
+          }
+        }
+        return LCE_HIP_OK;
+      }
+      auto it = shapes.find(other);
+      if (it == shapes.end()) return LCE_HIP_ERR_UNSUPPORTED;        // (not an error: the chain stops before `o`)
+      const Shape& os = it->second;
+      if (os.type != lce_tfl::kTensorFloat32 || memcmp(os.dims, xs.dims, sizeof xs.dims) != 0)
+        return Fail(LCE_HIP_ERR_INVALID, "run_section: the two tensors of an ADD / MUL differ in shape");
+      st->operand = LCE_HIP_EW_TENSOR;
+      if (run) {
+        const void* p = nullptr;
+        if (lce_hip_status s = DevicePtr(other, "an ADD / MUL input", &p)) return s;
+        st->values = (const float*)p;
+      }
+      return LCE_HIP_OK;
+    };
+    for (;;) {
+      const lce_tfl::Operator& o = M.operators[cur];
+      lce_hip_ew_step st;
+      const lce_hip_status s = operand_of(o, v_t, &st);
+      if (s == LCE_HIP_ERR_UNSUPPORTED && chain.empty())
+        return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
+      if (s == LCE_HIP_ERR_UNSUPPORTED) break;
+      if (s != LCE_HIP_OK) return s;
+      steps.push_back(st);
+      chain.push_back(cur);
+      done[cur] = 1;
+      v_t = o.outputs[0];
+      shapes[v_t] = xs;
+      const std::vector<int32_t>& rd = model->readers[v_t];
+      if (steps.size() == 8 || rd.size() != 1 || IsSectionOutput(v_t)) break;
+      const int32_t next = rd[0];
+      if (model->absorbed[next] != kAbsorbedElementwise || done[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
+      cur = next;
     }
-    if (model->absorbed[i]) {
-      if (lce_hip_status s = WalkElementwiseChain(model, sec, i, batch, shapes, ptr, run, stream, capturing, buffer_for, &done)) return s;
-      continue;
-    }
+    const Fold fold = FoldQuantize(chain.back(), v_t, xs);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(x_t, "an ADD / MUL input", &in)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = lce_hip_elementwise((const float*)in, rows, channels, steps.data(), (int32_t)steps.size(), (float*)out,
+                                               (int32_t*)bits, stream)) return s;
+    ++model->last.ew.launches;
+    model->last.ew_ops += (int32_t)chain.size();
+    if (fold.bits_t >= 0) ++model->last.ew.quantize;
+    return LCE_HIP_OK;
+  }
+
+  // An absorbed int8 ADD (LCE_TFLITE_SECTIONS_INT8_ADD) as ONE lce_hip_add_int8 launch.  The first LceQuantize of the section
+  // that reads the sum becomes the launch's bit output and its own launch disappears; the int8 sum is written when anything
+  // else reads it (in a residual chain the next ADD does) or the section delivers it.
+  lce_hip_status Int8Add(int32_t i) {
+    const lce_tfl::Model& M = model->m;
     const lce_tfl::Operator& op = M.operators[i];
-    if (op.inputs.empty() || op.outputs.size() != 1 || op.inputs[0] < 0)
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: malformed LCE operator");
-    auto in_it = shapes->find(op.inputs[0]);
-    if (in_it == shapes->end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an operator reads a tensor nothing produced");
-    const Shape in = in_it->second;
+    const int32_t out_t = op.outputs[0];
+    const std::vector<int32_t>& fs = M.tensors[out_t].shape;
+    // the inferred shape and type of BOTH inputs must agree with the file's (a convolution whose output is smaller than the
+    // file declares must not be read past its buffer)
+    Shape xs;
+    for (int k = 0; k < 2; ++k) {
+      auto it = shapes.find(op.inputs[k]);
+      if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD reads a tensor nothing produced");
+      xs = it->second;
+      if (!Agrees(xs, lce_tfl::kTensorInt8, fs[1], fs[2], fs[3]))
+        return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD input's shape or type does not match the one its producer infers");
+    }
+    shapes[out_t] = xs;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, xs);
+    if (!run) return LCE_HIP_OK;
+    lce_hip_add_int8_desc d;
+    if (!Int8AddDesc(M, op, &d)) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD without quantization parameters");
+    const void* in[2];
+    for (int k = 0; k < 2; ++k)
+      if (lce_hip_status s = DevicePtr(op.inputs[k], "an int8 ADD input", &in[k])) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = lce_hip_add_int8(&d, (const int8_t*)in[0], (const int8_t*)in[1], (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2],
+                                            (size_t)xs.dims[3], (int8_t*)out, (int32_t*)bits, stream)) return s;
+    ++model->last.add_i8.launches;
+    if (fold.bits_t >= 0) ++model->last.add_i8.quantize;
+    return LCE_HIP_OK;
+  }
+
+  // An absorbed CONCATENATION (LCE_TFLITE_SECTIONS_CONCAT) as ONE lce_hip_concat launch.  The first LceQuantize of the section
+  // that reads the joined tensor becomes the launch's bit output and its own launch disappears; the joined tensor itself is
+  // written when anything else reads it (in a dense block the next join does) or the section delivers it.
+  lce_hip_status Concat(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
     const int32_t out_t = op.outputs[0];
     const lce_tfl::Tensor& OT = M.tensors[out_t];
+    const std::vector<int32_t>& fs = OT.shape;
+    // the inferred shape and type of EVERY input must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    int32_t channels[LCE_HIP_CONCAT_MAX_INPUTS];
+    int64_t sum = 0;
+    const size_t n = op.inputs.size();
+    for (size_t k = 0; k < n; ++k) {
+      auto it = shapes.find(op.inputs[k]);
+      if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION reads a tensor nothing produced");
+      const Shape& xs = it->second;
+      if (!Agrees(xs, OT.type, fs[1], fs[2], M.tensors[op.inputs[k]].shape[3]))
+        return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION input's shape or type does not match the one its producer infers");
+      channels[k] = xs.dims[3];
+      sum += xs.dims[3];
+    }
+    if (sum != fs[3]) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION's inputs do not add up to its output");
+    Shape os;
+    os.dims[0] = batch; os.dims[1] = fs[1]; os.dims[2] = fs[2]; os.dims[3] = fs[3];
+    os.type = OT.type;
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os, /*allowed=*/OT.type != lce_tfl::kTensorInt32);
+    if (!run) return LCE_HIP_OK;
+    const void* in[LCE_HIP_CONCAT_MAX_INPUTS];
+    for (size_t k = 0; k < n; ++k)
+      if (lce_hip_status s = DevicePtr(op.inputs[k], "a CONCATENATION input", &in[k])) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    const lce_hip_dtype type = OT.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : OT.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BITPACKED;
+    if (lce_hip_status s = lce_hip_concat(type, in, channels, (int32_t)n, (size_t)batch * fs[1] * fs[2],
+                                          type == LCE_HIP_I8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
+    ++model->last.concat.launches;
+    if (fold.bits_t >= 0) ++model->last.concat.quantize;
+    return LCE_HIP_OK;
+  }
+
+  // The four LCE operators.  `in` is the inferred shape of operator `i`'s first input, `in_dev` its device pointer (with `run`).
+  lce_hip_status Quantize(int32_t i, const Shape& in, const void* in_dev) {                      // quantization.cc:19-41,76-114
+    const lce_tfl::Operator& op = model->m.operators[i];
+    if (in.type != lce_tfl::kTensorFloat32 && in.type != lce_tfl::kTensorInt8 && in.type != lce_tfl::kTensorBool)
+      return Fail(LCE_HIP_ERR_INVALID, "LceQuantize: input must be float32, int8 or bool");
+    Shape out = in;
+    out.dims[3] = (in.dims[3] + 31) / 32;
+    out.type = lce_tfl::kTensorInt32;
+    shapes[op.outputs[0]] = out;
+    if (!run) return LCE_HIP_OK;
+    void* o = nullptr;
+    if (lce_hip_status s = BufferFor(op.outputs[0], out.bytes(), &o)) return s;
+    const lce_hip_dtype t = in.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : in.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BOOL;
+    const int32_t zp = in.type == lce_tfl::kTensorInt8 ? (int32_t)model->m.tensors[op.inputs[0]].zero_point : in.type == lce_tfl::kTensorBool ? 1 : 0;
+    return lce_hip_bitpack(t, in_dev, (size_t)in.dims[0] * in.dims[1] * in.dims[2], (size_t)in.dims[3], zp, (int32_t*)o, stream);
+  }
+
+  lce_hip_status Dequantize(int32_t i, const Shape& in, const void* in_dev) {                    // quantization.cc:43-74,116-147
+    const lce_tfl::Operator& op = model->m.operators[i];
+    const lce_tfl::Tensor& OT = model->m.tensors[op.outputs[0]];
+    if (OT.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "LceDequantize: the output's channel count comes from the file (4-D)");
     Shape out = in;
     out.type = OT.type;
-    const void* in_dev = nullptr;
-    if (run) {
-      auto p = ptr->find(op.inputs[0]);
-      if (p == ptr->end() || !p->second) return Fail(LCE_HIP_ERR_INVALID, "run_section: missing device pointer of an input tensor");
-      in_dev = p->second;
-    }
-    if (op.custom_code == "LceQuantize") {                      // quantization.cc:19-41,76-114
-      if (in.type != lce_tfl::kTensorFloat32 && in.type != lce_tfl::kTensorInt8 && in.type != lce_tfl::kTensorBool)
-        return Fail(LCE_HIP_ERR_INVALID, "LceQuantize: input must be float32, int8 or bool");
-      out.dims[3] = (in.dims[3] + 31) / 32;
-      out.type = lce_tfl::kTensorInt32;
-      (*shapes)[out_t] = out;
-      if (run) {
-        void* o = nullptr;
-        if (lce_hip_status s = buffer_for(out_t, out.bytes(), &o)) return s;
-        const lce_tfl::Tensor& IT = M.tensors[op.inputs[0]];
-        const lce_hip_dtype t = in.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : in.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BOOL;
-        const int32_t zp = in.type == lce_tfl::kTensorInt8 ? (int32_t)IT.zero_point : in.type == lce_tfl::kTensorBool ? 1 : 0;
-        if (lce_hip_status s = lce_hip_bitpack(t, in_dev, (size_t)in.dims[0] * in.dims[1] * in.dims[2], (size_t)in.dims[3], zp, (int32_t*)o, stream)) return s;
-      }
-    } else if (op.custom_code == "LceDequantize") {             // quantization.cc:43-74,116-147
-      if (OT.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "LceDequantize: the output's channel count comes from the file (4-D)");
-      out.dims[3] = OT.shape[3];
-      if ((out.dims[3] + 31) / 32 != in.dims[3]) return Fail(LCE_HIP_ERR_INVALID, "LceDequantize: output channels do not match the packed input");
-      (*shapes)[out_t] = out;
-      if (run) {
-        void* o = nullptr;
-        if (lce_hip_status s = buffer_for(out_t, out.bytes(), &o)) return s;
-        const lce_hip_dtype t = out.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : out.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BOOL;
-        if (lce_hip_status s = lce_hip_unpack(t, (const int32_t*)in_dev, (size_t)out.dims[0] * out.dims[1] * out.dims[2], (size_t)out.dims[3],
-                                              OT.quantized ? OT.scale : 1.0f, OT.quantized ? (int32_t)OT.zero_point : 0, o, stream)) return s;
-      }
-    } else if (op.custom_code == "LceBMaxPool2d") {             // bmaxpool.cc:20-91
-      if (in.type != lce_tfl::kTensorInt32) return Fail(LCE_HIP_ERR_INVALID, "LceBMaxPool2d: input must be bitpacked int32");
-      const lce_flex::Map fm(op.custom_options, op.custom_options_size);
-      if (!fm.valid()) return Fail(LCE_HIP_ERR_INVALID, "LceBMaxPool2d: unreadable options");
-      const int32_t fh = fm.AsInt32("filter_height"), fw = fm.AsInt32("filter_width"), sh = fm.AsInt32("stride_height"),
-                    sw = fm.AsInt32("stride_width"), pad = fm.AsInt32("padding");
-      if (lce_hip_status s = lce_hip_bmaxpool_output_shape(in.dims[1], in.dims[2], fh, fw, sh, sw, pad, &out.dims[1], &out.dims[2])) return s;
-      (*shapes)[out_t] = out;
-      if (run) {
-        void* o = nullptr;
-        if (lce_hip_status s = buffer_for(out_t, out.bytes(), &o)) return s;
-        if (lce_hip_status s = lce_hip_bmaxpool((const int32_t*)in_dev, in.dims[0], in.dims[1], in.dims[2], in.dims[3], fh, fw, sh, sw, pad, (int32_t*)o, stream)) return s;
-      }
-    } else if (op.custom_code == "LceBconv2d") {                // bconv2d.cc:137-300,550-564
-      // The plan is built from the FILE's static shape of the input tensor (lce_tflite_model_bconv2d_plan); the buffer it will
-      // read was sized from THIS walk's shape inference.  A model whose declared shapes disagree with what its operators
-      // produce (dynamic / -1 dimensions, a hand-edited file, an int8 tensor wired into a convolution) must fail here, not read
-      // past a scratch buffer on the device: the file is untrusted input.
-      {
-        const lce_tfl::Tensor& IT = M.tensors[op.inputs[0]];
-        if (in.type != lce_tfl::kTensorInt32)
-          return Fail(LCE_HIP_ERR_INVALID, "LceBconv2d: the tensor feeding the convolution is not bitpacked int32");
-        if (IT.shape.size() != 4 || IT.shape[1] != in.dims[1] || IT.shape[2] != in.dims[2] || IT.shape[3] != in.dims[3])
-          return Fail(LCE_HIP_ERR_INVALID, "LceBconv2d: the input tensor's declared shape does not match the shape its producer infers");
-      }
-      lce_hip_bconv2d_plan* plan = nullptr;
-      if (lce_hip_status s = PlanFor(model, i, batch, semantics, &plan)) return s;
-      if (lce_hip_status s = lce_hip_bconv2d_plan_output_shape(plan, out.dims)) return s;
-      (*shapes)[out_t] = out;
-      const std::vector<int32_t> fused = QuantizeConsumers(model, sec, i);
-      for (int32_t j : fused) {                                 // their shapes; the first one's launch disappears
-        Shape q = out;
-        q.dims[3] = (out.dims[3] + 31) / 32;
-        q.type = lce_tfl::kTensorInt32;
-        (*shapes)[M.operators[j].outputs[0]] = q;
-      }
-      if (!fused.empty()) done[fused[0]] = 1;
-      if (run) {
-        void* o = nullptr;
-        if (lce_hip_status s = buffer_for(out_t, out.bytes(), &o)) return s;
-        if (fused.empty()) {
-          if (lce_hip_status s = lce_hip_bconv2d_run(plan, (const int32_t*)in_dev, o, stream)) return s;
-        } else {
-          void* bits = nullptr;
-          const int32_t bits_t = M.operators[fused[0]].outputs[0];
-          if (lce_hip_status s = buffer_for(bits_t, (*shapes)[bits_t].bytes(), &bits)) return s;
-          if (lce_hip_status s = lce_hip_bconv2d_run_dual(plan, (const int32_t*)in_dev, o, (int32_t*)bits, stream)) return s;
-          ++model->last_run_fused;
-        }
-      }
-    } else {
-      return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: operator " + op.custom_code + " is not an LCE op");
-    }
+    out.dims[3] = OT.shape[3];
+    if ((out.dims[3] + 31) / 32 != in.dims[3]) return Fail(LCE_HIP_ERR_INVALID, "LceDequantize: output channels do not match the packed input");
+    shapes[op.outputs[0]] = out;
+    if (!run) return LCE_HIP_OK;
+    void* o = nullptr;
+    if (lce_hip_status s = BufferFor(op.outputs[0], out.bytes(), &o)) return s;
+    const lce_hip_dtype t = out.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : out.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BOOL;
+    return lce_hip_unpack(t, (const int32_t*)in_dev, (size_t)out.dims[0] * out.dims[1] * out.dims[2], (size_t)out.dims[3],
+                          OT.quantized ? OT.scale : 1.0f, OT.quantized ? (int32_t)OT.zero_point : 0, o, stream);
   }
-  return LCE_HIP_OK;
-}
+
+  lce_hip_status BMaxPool2d(int32_t i, const Shape& in, const void* in_dev) {                    // bmaxpool.cc:20-91
+    const lce_tfl::Operator& op = model->m.operators[i];
+    if (in.type != lce_tfl::kTensorInt32) return Fail(LCE_HIP_ERR_INVALID, "LceBMaxPool2d: input must be bitpacked int32");
+    const lce_flex::Map fm(op.custom_options, op.custom_options_size);
+    if (!fm.valid()) return Fail(LCE_HIP_ERR_INVALID, "LceBMaxPool2d: unreadable options");
+    const int32_t fh = fm.AsInt32("filter_height"), fw = fm.AsInt32("filter_width"), sh = fm.AsInt32("stride_height"),
+                  sw = fm.AsInt32("stride_width"), pad = fm.AsInt32("padding");
+    Shape out = in;
+    out.type = model->m.tensors[op.outputs[0]].type;
+    if (lce_hip_status s = lce_hip_bmaxpool_output_shape(in.dims[1], in.dims[2], fh, fw, sh, sw, pad, &out.dims[1], &out.dims[2])) return s;
+    shapes[op.outputs[0]] = out;
+    if (!run) return LCE_HIP_OK;
+    void* o = nullptr;
+    if (lce_hip_status s = BufferFor(op.outputs[0], out.bytes(), &o)) return s;
+    return lce_hip_bmaxpool((const int32_t*)in_dev, in.dims[0], in.dims[1], in.dims[2], in.dims[3], fh, fw, sh, sw, pad, (int32_t*)o, stream);
+  }
+
+  lce_hip_status Bconv2d(int32_t i, const Shape& in, const void* in_dev) {                       // bconv2d.cc:137-300,550-564
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    // The plan is built from the FILE's static shape of the input tensor (lce_tflite_model_bconv2d_plan); the buffer it will
+    // read was sized from THIS walk's shape inference.  A model whose declared shapes disagree with what its operators
+    // produce (dynamic / -1 dimensions, a hand-edited file, an int8 tensor wired into a convolution) must fail here, not read
+    // past a scratch buffer on the device: the file is untrusted input.
+    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
+    if (in.type != lce_tfl::kTensorInt32)
+      return Fail(LCE_HIP_ERR_INVALID, "LceBconv2d: the tensor feeding the convolution is not bitpacked int32");
+    if (is.size() != 4 || !Agrees(in, lce_tfl::kTensorInt32, is[1], is[2], is[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "LceBconv2d: the input tensor's declared shape does not match the shape its producer infers");
+    lce_hip_bconv2d_plan* plan = nullptr;
+    if (lce_hip_status s = PlanFor(model, i, batch, semantics, &plan)) return s;
+    Shape out = in;
+    out.type = M.tensors[out_t].type;
+    if (lce_hip_status s = lce_hip_bconv2d_plan_output_shape(plan, out.dims)) return s;
+    shapes[out_t] = out;
+    // (not the fold rule of the passes above: EVERY LceQuantize reading the output gets its shape here, the first one's launch
+    // disappears, and the convolution's own output is always written)
+    const std::vector<int32_t> fused = QuantizeConsumers(model, sec, i);
+    for (int32_t j : fused) {
+      Shape q = out;
+      q.dims[3] = (out.dims[3] + 31) / 32;
+      q.type = lce_tfl::kTensorInt32;
+      shapes[M.operators[j].outputs[0]] = q;
+    }
+    if (!fused.empty()) done[fused[0]] = 1;
+    if (!run) return LCE_HIP_OK;
+    void* o = nullptr;
+    if (lce_hip_status s = BufferFor(out_t, out.bytes(), &o)) return s;
+    if (fused.empty()) return lce_hip_bconv2d_run(plan, (const int32_t*)in_dev, o, stream);
+    void* bits = nullptr;
+    const int32_t bits_t = M.operators[fused[0]].outputs[0];
+    if (lce_hip_status s = BufferFor(bits_t, shapes[bits_t].bytes(), &bits)) return s;
+    if (lce_hip_status s = lce_hip_bconv2d_run_dual(plan, (const int32_t*)in_dev, o, (int32_t*)bits, stream)) return s;
+    ++model->last.conv_quantize;
+    return LCE_HIP_OK;
+  }
+
+  lce_hip_status LceOp(int32_t i) {
+    const lce_tfl::Operator& op = model->m.operators[i];
+    if (op.inputs.empty() || op.outputs.size() != 1 || op.inputs[0] < 0)
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: malformed LCE operator");
+    auto in_it = shapes.find(op.inputs[0]);
+    if (in_it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an operator reads a tensor nothing produced");
+    const Shape in = in_it->second;
+    const void* in_dev = nullptr;
+    if (run)
+      if (lce_hip_status s = DevicePtr(op.inputs[0], "an input tensor", &in_dev)) return s;
+    if (op.custom_code == "LceQuantize") return Quantize(i, in, in_dev);
+    if (op.custom_code == "LceDequantize") return Dequantize(i, in, in_dev);
+    if (op.custom_code == "LceBMaxPool2d") return BMaxPool2d(i, in, in_dev);
+    if (op.custom_code == "LceBconv2d") return Bconv2d(i, in, in_dev);
+    return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: operator " + op.custom_code + " is not an LCE op");
+  }
+
+  lce_hip_status Section() {
+    const lce_tfl::Model& M = model->m;
+    for (int32_t t : sec.inputs) {
+      const lce_tfl::Tensor& T = M.tensors[t];
+      if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
+      Shape sh;
+      for (int k = 0; k < 4; ++k) sh.dims[k] = T.shape[k];
+      sh.dims[0] = batch;
+      sh.type = T.type;
+      shapes[t] = sh;
+    }
+    done = std::vector<char>(M.operators.size(), 0);
+    for (int32_t i : sec.ops) {
+      if (done[i]) continue;
+      lce_hip_status s;
+      switch (model->absorbed[i]) {
+        case kAbsorbedElementwise: s = ElementwiseChain(i); break;
+        case kAbsorbedInt8Add: s = Int8Add(i); break;
+        case kAbsorbedConcat: s = Concat(i); break;
+        default: s = LceOp(i);
+      }
+      if (s) return s;
+    }
+    return LCE_HIP_OK;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -975,11 +977,10 @@ lce_hip_status lce_tflite_model_section_tensor_shape(lce_tflite_model* model, in
   if (!model || section < 0 || section >= (int32_t)model->sections.size() || batch <= 0)
     return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_section_tensor_shape: bad argument");
   std::lock_guard<std::mutex> lock(model->run_mu);
-  std::map<int32_t, Shape> shapes;
-  std::map<int32_t, void*> ptr;
-  if (lce_hip_status s = WalkSection(model, model->sections[section], batch, semantics, &shapes, &ptr, false, nullptr)) return s;
-  auto it = shapes.find(tensor);
-  if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_section_tensor_shape: the section does not touch this tensor");
+  Walk w{model, model->sections[section], batch, semantics, /*run=*/false, /*stream=*/nullptr, /*capturing=*/false, {}, {}, {}};
+  if (lce_hip_status s = w.Section()) return s;
+  auto it = w.shapes.find(tensor);
+  if (it == w.shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_section_tensor_shape: the section does not touch this tensor");
   for (int k = 0; dims && k < 4; ++k) dims[k] = it->second.dims[k];
   if (bytes) *bytes = it->second.bytes();
   return LCE_HIP_OK;
@@ -992,7 +993,6 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
     return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_run_section: bad argument");
   const lce_tflite_section& sec = model->sections[section];
   std::lock_guard<std::mutex> lock(model->run_mu);
-  std::map<int32_t, Shape> shapes;
   std::map<int32_t, void*> ptr;
   for (size_t k = 0; k < sec.inputs.size(); ++k) {
     if (!inputs_dev[k]) return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_run_section: null input pointer");
@@ -1002,11 +1002,10 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
     if (!outputs_dev[k]) return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_run_section: null output pointer");
     ptr[sec.outputs[k]] = outputs_dev[k];
   }
-  model->last_run_fused = 0;
-  model->last_ew = lce_tflite_model::EwStats();
-  model->last_add_i8 = lce_tflite_model::AddI8Stats();
-  model->last_concat = lce_tflite_model::ConcatStats();
-  if (!model->use_graphs || !stream) return WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
+  // every walk starts from the caller's pointers alone (a walk adds the scratch buffers it uses to its own copy)
+  auto walk = [&](bool capturing) { return Walk{model, sec, batch, semantics, /*run=*/true, stream, capturing, ptr, {}, {}}.Section(); };
+  model->last = lce_tflite_model::RunStats();
+  if (!model->use_graphs || !stream) return walk(false);
 
   lce_tflite_model::GraphKey key{section, batch, semantics, stream, {}};
   for (size_t k = 0; k < sec.inputs.size(); ++k) key.ptrs.push_back(inputs_dev[k]);
@@ -1014,10 +1013,7 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
   {
     lce_tflite_model::GraphEntry& e = model->graphs[key];
     if (e.graph) {
-      model->last_run_fused = e.fused;
-      model->last_ew = e.ew;
-      model->last_add_i8 = e.add_i8;
-      model->last_concat = e.concat;
+      model->last = e.stats;
       ++model->graph_replays;
       return lce_hip_graph_launch(e.graph, stream);
     }
@@ -1025,43 +1021,27 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
       // record: the same walk, on a capturing stream (nothing executes); whatever goes wrong, the section then runs eagerly
       bool recorded = false;
       void* g = nullptr;
-      int32_t fused = 0;
-      lce_tflite_model::EwStats ew;
-      lce_tflite_model::AddI8Stats add_i8;
-      lce_tflite_model::ConcatStats concat;
       if (lce_hip_graph_begin_capture(stream) == LCE_HIP_OK) {
-        std::map<int32_t, Shape> shapes_c;
-        std::map<int32_t, void*> ptr_c = ptr;
-        const lce_hip_status walked = WalkSection(model, sec, batch, semantics, &shapes_c, &ptr_c, true, stream, /*capturing=*/true);
+        const lce_hip_status walked = walk(true);
         const lce_hip_status ended = lce_hip_graph_end_capture(stream, &g);
         recorded = walked == LCE_HIP_OK && ended == LCE_HIP_OK && g != nullptr;
-        fused = model->last_run_fused;
-        ew = model->last_ew;
-        add_i8 = model->last_add_i8;
-        concat = model->last_concat;
         if (!recorded && g) { lce_hip_graph_destroy(g); g = nullptr; }
       }
       g_model_error.clear();
       lce_tflite_model::GraphEntry& e2 = model->graphs[key];     // (the walk may have dropped the table)
       if (recorded) {
         e2.graph = g;
-        e2.fused = fused;
-        e2.ew = ew;
-        e2.add_i8 = add_i8;
-        e2.concat = concat;
+        e2.stats = model->last;
         e2.eager_runs = 1;
         ++model->graph_captures;
         ++model->graph_replays;
         return lce_hip_graph_launch(g, stream);
       }
       e2.unrecordable = true;
-      model->last_run_fused = 0;
-      model->last_ew = lce_tflite_model::EwStats();
-      model->last_add_i8 = lce_tflite_model::AddI8Stats();
-  model->last_concat = lce_tflite_model::ConcatStats();
+      model->last = lce_tflite_model::RunStats();
     }
   }
-  const lce_hip_status s = WalkSection(model, sec, batch, semantics, &shapes, &ptr, true, stream);
+  const lce_hip_status s = walk(false);
   if (s == LCE_HIP_OK) ++model->graphs[key].eager_runs;
   return s;
 }
@@ -1083,30 +1063,30 @@ void lce_tflite_model_graph_stats(lce_tflite_model* model, int32_t* recorded, in
 void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
   if (!model) return;
   std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last_ew.launches;
-  if (ops_folded) *ops_folded = model->last_ew.ops;
-  if (quantize_folded) *quantize_folded = model->last_ew.quantize;
+  if (launches) *launches = model->last.ew.launches;
+  if (ops_folded) *ops_folded = model->last.ew_ops;
+  if (quantize_folded) *quantize_folded = model->last.ew.quantize;
 }
 
 void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
   if (!model) return;
   std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last_add_i8.launches;
-  if (quantize_folded) *quantize_folded = model->last_add_i8.quantize;
+  if (launches) *launches = model->last.add_i8.launches;
+  if (quantize_folded) *quantize_folded = model->last.add_i8.quantize;
 }
 
 void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
   if (!model) return;
   std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last_concat.launches;
-  if (quantize_folded) *quantize_folded = model->last_concat.quantize;
+  if (launches) *launches = model->last.concat.launches;
+  if (quantize_folded) *quantize_folded = model->last.concat.quantize;
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {
   if (!model) return;
   std::lock_guard<std::mutex> lock(model->run_mu);
   if (cached_plans) *cached_plans = (int32_t)model->plans.size();
-  if (fused_quantize_ops) *fused_quantize_ops = model->last_run_fused;
+  if (fused_quantize_ops) *fused_quantize_ops = model->last.conv_quantize;
   size_t b = 0;
   for (auto& kv : model->scratch) b += kv.second.bytes;
   if (scratch_bytes) *scratch_bytes = b;

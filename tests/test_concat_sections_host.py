@@ -5,26 +5,21 @@ of lce_hip_concat / amd.concat, which all fail before any device is touched.  Al
 (tests/test_gpu_concat.py) and of tools/concat_sections.py."""
 import ctypes as C
 import importlib
-import os
 import re
-import shutil
 import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import hipcc_lib as H
 import oracle_lib as O
 import synth
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, _scalar_memory_write, ew_op
+from test_elementwise_sections_host import ADD, MUL, NONE, RELU, ew_op
 from test_model_reader_host import bconv_options, mixed_model
 from tflite_writer import ModelBuilder, _Scalar, _Table, _Vector
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "compute-engine_amd", "csrc")
 
 CONCATENATION = 2                      # schema.fbs BuiltinOperator
 CONCATENATION_OPTIONS = 10             # schema.fbs BuiltinOptions
@@ -605,29 +600,15 @@ NEW_SOURCES = ("lce_kernels_concat.h", "lce_tu_concat.hip")
 
 
 def test_the_new_sources_hold_no_scalar_memory_write():
-    for f in NEW_SOURCES:
-        words = re.findall(r"\b[sS]_[A-Za-z0-9_]+", open(os.path.join(CSRC, f)).read())
-        assert not [w for w in words if _scalar_memory_write(w)], f
+    assert not H.sources_with_scalar_memory_writes(NEW_SOURCES)
 
 
 def test_the_concat_kernels_use_no_scratch_and_no_lds():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc is not here")
-    with tempfile.TemporaryDirectory() as d:
-        asm = os.path.join(d, "concat.s")
-        r = subprocess.run([hipcc, "-DLCE_PRODUCT_BUILD", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950",
-                            "-I", CSRC, "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", "-o", asm,
-                            os.path.join(CSRC, "lce_tu_concat.hip")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        kernels = re.findall(r"Function Name: (\S+)", r.stderr)
-        assert sorted(k for k in kernels if "concat" in k) == sorted(k for k in kernels), kernels
-        assert len(kernels) == 8, kernels                        # vector: F32 / I8 with and without bits, words; rows: three
-        for key in ("ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "VGPRs Spill", "SGPRs Spill"):
-            vals = re.findall(re.escape(key) + r": (\d+)", r.stderr)
-            assert vals == ["0"] * len(kernels), (key, vals)
-        text = open(asm).read()
-        mnemonics = set(re.findall(r"^\s+([a-z]+_[a-z0-9_]+)", text, re.M))
-        assert not [m for m in mnemonics if _scalar_memory_write(m)]
-        # the vector path moves 16 bytes per lane and instruction
-        assert "global_load_dwordx4" in mnemonics and "global_store_dwordx4" in mnemonics
+    kernels, resources, _, mnemonics = H.compile_unit("lce_tu_concat.hip")
+    assert sorted(k for k in kernels if "concat" in k) == sorted(k for k in kernels), kernels
+    assert len(kernels) == 8, kernels                        # vector: F32 / I8 with and without bits, words; rows: three
+    for key in H.RESOURCE_KEYS:
+        assert resources[key] == ["0"] * len(kernels), (key, resources[key])
+    assert not [m for m in mnemonics if H.scalar_memory_write(m)]
+    # the vector path moves 16 bytes per lane and instruction
+    assert "global_load_dwordx4" in mnemonics and "global_store_dwordx4" in mnemonics

@@ -4,15 +4,12 @@ through the reader, shape inference over the absorbed tensors, and the argument 
 amd.elementwise, which all fail before any device is touched.  The GPU side is tests/test_gpu_elementwise.py."""
 import ctypes as C
 import importlib
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import hipcc_lib as H
 import oracle_lib as O
 import synth
 from test_model_reader_host import bconv_options, mixed_model
@@ -20,8 +17,6 @@ from tflite_writer import ModelBuilder, _Scalar, _Table, _Vector
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "compute-engine_amd", "csrc")
 
 ADD, MUL, SUB, CONV_2D = 0, 18, 41, 3           # schema.fbs BuiltinOperator
 ADD_OPTIONS, MUL_OPTIONS = 11, 21               # schema.fbs BuiltinOptions
@@ -271,35 +266,16 @@ def test_python_checks_fail_before_any_device_call(monkeypatch, steps, kw, msg):
 NEW_SOURCES = ("lce_kernels_eltwise.h", "lce_tu_eltwise.hip")
 
 
-def _scalar_memory_write(word: str) -> bool:
-    """An SMEM mnemonic that writes or invalidates memory (the store / atomic forms and the data-cache write-back / discard)."""
-    w = word.lower()
-    return w.startswith("s_") and ("store" in w or "atomic" in w or w.startswith("s_dcache"))
-
-
 def test_the_new_sources_hold_no_scalar_memory_write():
-    for f in NEW_SOURCES:
-        words = re.findall(r"\b[sS]_[A-Za-z0-9_]+", open(os.path.join(CSRC, f)).read())
-        assert not [w for w in words if _scalar_memory_write(w)], f
+    assert not H.sources_with_scalar_memory_writes(NEW_SOURCES)
 
 
 def test_the_elementwise_kernels_use_no_scratch_and_no_lds():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc is not here")
-    with tempfile.TemporaryDirectory() as d:
-        asm = os.path.join(d, "ew.s")
-        r = subprocess.run([hipcc, "-DLCE_PRODUCT_BUILD", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950",
-                            "-I", CSRC, "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", "-o", asm,
-                            os.path.join(CSRC, "lce_tu_eltwise.hip")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        kernels = re.findall(r"Function Name: (\S+)", r.stderr)
-        assert sorted(k for k in kernels if "eltwise" in k) == sorted(k for k in kernels), kernels
-        assert len(kernels) == 2, kernels
-        for key in ("ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "VGPRs Spill", "SGPRs Spill"):
-            vals = re.findall(re.escape(key) + r": (\d+)", r.stderr)
-            assert vals == ["0", "0"], (key, vals)
-        mnemonics = set(re.findall(r"^\s+([sv]_[a-z0-9_]+)", open(asm).read(), re.M))
-        assert not [m for m in mnemonics if _scalar_memory_write(m)]
-        # one rounding per op: the float adds and multiplies are not contracted (the only fma forms are the 64-bit division's)
-        assert "v_add_f32_e32" in mnemonics and "v_mul_f32_e32" in mnemonics
+    kernels, resources, _, mnemonics = H.compile_unit("lce_tu_eltwise.hip")
+    assert sorted(k for k in kernels if "eltwise" in k) == sorted(k for k in kernels), kernels
+    assert len(kernels) == 2, kernels
+    for key in H.RESOURCE_KEYS:
+        assert resources[key] == ["0", "0"], (key, resources[key])
+    assert not [m for m in mnemonics if H.scalar_memory_write(m)]
+    # one rounding per op: the float adds and multiplies are not contracted (the only fma forms are the 64-bit division's)
+    assert "v_add_f32_e32" in mnemonics and "v_mul_f32_e32" in mnemonics

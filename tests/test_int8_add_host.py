@@ -4,26 +4,21 @@ with and without the flag, which int8 operators stay with the host, shape infere
 checks that come before any device call, and the build of the new sources.  The GPU side is tests/test_gpu_int8_add.py."""
 import ctypes as C
 import importlib
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import hipcc_lib as H
 import int8_add_ref as R
 import oracle_lib as O
 import synth
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, _scalar_memory_write, ew_op
+from test_elementwise_sections_host import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, ew_op
 from test_model_reader_host import bconv_options, mixed_model
 from tflite_writer import ModelBuilder
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "compute-engine_amd", "csrc")
 
 EQUAL_SCALES = (0.5, 1, 0.5, 2, 0.7, 3)
 RATIO_2_12 = (1.0, 4, 2.0 ** -12, -9, 1.0, 0)
@@ -351,36 +346,22 @@ NEW_SOURCES = ("lce_kernels_eltwise_i8.h", "lce_tu_eltwise_i8.hip")
 
 
 def test_the_new_sources_hold_no_scalar_memory_write():
-    for f in NEW_SOURCES:
-        words = re.findall(r"\b[sS]_[A-Za-z0-9_]+", open(os.path.join(CSRC, f)).read())
-        assert not [w for w in words if _scalar_memory_write(w)], f
+    assert not H.sources_with_scalar_memory_writes(NEW_SOURCES)
 
 
 def test_the_int8_add_kernels_use_no_scratch_and_no_lds():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc is not here")
-    with tempfile.TemporaryDirectory() as d:
-        asm = os.path.join(d, "add_i8.s")
-        r = subprocess.run([hipcc, "-DLCE_PRODUCT_BUILD", "-O3", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950",
-                            "-I", CSRC, "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", "-o", asm,
-                            os.path.join(CSRC, "lce_tu_eltwise_i8.hip")], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        kernels = re.findall(r"Function Name: (\S+)", r.stderr)
-        # the unit emits only its own kernels: a flat and a row kernel per variant
-        assert sorted(k for k in kernels if "add_i8_flat" in k or "add_i8_rows" in k) == sorted(kernels), kernels
-        assert len(kernels) == 6 and len(set(kernels)) == 6, kernels
-        for key in ("ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "VGPRs Spill", "SGPRs Spill"):
-            vals = re.findall(re.escape(key) + r": (\d+)", r.stderr)
-            assert vals == ["0"] * 6, (key, vals)
-        text = open(asm).read()
-        mnemonics = set(re.findall(r"^\s+([a-z]+_[a-z0-9_]+)", text, re.M))
-        assert not [m for m in mnemonics if _scalar_memory_write(m)]
-        assert not [m for m in mnemonics if m.startswith("ds_") or m.startswith("scratch_")], mnemonics
-        # the cheap variants hold ONE 64-bit multiply-add per element and no slow 32-bit multiply; the literal one holds six
-        body = lambda v: text.split("_ZN3lce11add_i8_flatILi%dEEEvNS_9AddI8ArgsEm:" % v)[1].split(".Lfunc_end")[0]
-        count = lambda v, m: len(re.findall(r"^\s+" + m + r"\b", body(v), re.M))
-        for v in (amd.ADD_INT8_SPLIT, amd.ADD_INT8_SHIFT):
-            assert 64 <= count(v, "v_mad_i64_i32") <= 66, (v, count(v, "v_mad_i64_i32"))       # 64 elements per lane and iteration
-            assert count(v, "v_mul_lo_u32") == 0 and count(v, "v_mul_hi_i32") == 0 and count(v, "v_mul_hi_u32") == 0
-        assert count(amd.ADD_INT8_LITERAL, "v_mad_i64_i32") >= 6 * 64
+    kernels, resources, text, mnemonics = H.compile_unit("lce_tu_eltwise_i8.hip")
+    # the unit emits only its own kernels: a flat and a row kernel per variant
+    assert sorted(k for k in kernels if "add_i8_flat" in k or "add_i8_rows" in k) == sorted(kernels), kernels
+    assert len(kernels) == 6 and len(set(kernels)) == 6, kernels
+    for key in H.RESOURCE_KEYS:
+        assert resources[key] == ["0"] * 6, (key, resources[key])
+    assert not [m for m in mnemonics if H.scalar_memory_write(m)]
+    assert not [m for m in mnemonics if m.startswith("ds_") or m.startswith("scratch_")], mnemonics
+    # the cheap variants hold ONE 64-bit multiply-add per element and no slow 32-bit multiply; the literal one holds six
+    body = lambda v: text.split("_ZN3lce11add_i8_flatILi%dEEEvNS_9AddI8ArgsEm:" % v)[1].split(".Lfunc_end")[0]
+    count = lambda v, m: len(re.findall(r"^\s+" + m + r"\b", body(v), re.M))
+    for v in (amd.ADD_INT8_SPLIT, amd.ADD_INT8_SHIFT):
+        assert 64 <= count(v, "v_mad_i64_i32") <= 66, (v, count(v, "v_mad_i64_i32"))       # 64 elements per lane and iteration
+        assert count(v, "v_mul_lo_u32") == 0 and count(v, "v_mul_hi_i32") == 0 and count(v, "v_mul_hi_u32") == 0
+    assert count(amd.ADD_INT8_LITERAL, "v_mad_i64_i32") >= 6 * 64
