@@ -371,10 +371,7 @@ bool mfma_supported(const HostPlan& p) {
   if (d.groups != 1 && (d.channels_out / d.groups) % 64 != 0) return false;
   if (p.backtransform_add >= (1 << 23)) return false;    // fp32 accumulation must stay exact
   const int cpad = ceil_div(d.channels_in, 64) * 64;
-  const int64_t hp = std::max<int64_t>(p.pad_h + d.in_height,
-                                       (int64_t)(p.out_h - 1) * d.stride_height + (d.filter_height - 1) * d.dilation_height + 1);
-  const int64_t wp = std::max<int64_t>(p.pad_w + d.in_width,
-                                       (int64_t)(p.out_w - 1) * d.stride_width + (d.filter_width - 1) * d.dilation_width + 1);
+  const int64_t hp = padded_height(p), wp = padded_width(p);
   if (hp * wp * (cpad / 2) >= (1ll << 31)) return false; // one padded image must fit a buffer resource
   if (hp * wp * (cpad / 32) >= (1ll << 31)) return false;
   return true;
@@ -438,9 +435,8 @@ PwArgs make_pw_args(const HostPlan& p, int batch_chunk) {
   P.tiles = (int32_t)((m + 31) / 32);
   P.noclamp = (p.clamp_min <= 0 && (int64_t)p.clamp_max >= 2 * (int64_t)p.backtransform_add) ? 1 : 0;
   P.in_bytes = (uint32_t)((int64_t)batch_chunk * d.in_height * d.in_width * p.cw * 4);
-  const int64_t row = d.dst_type == LCE_HIP_BITPACKED ? (int64_t)p.wout * 4 : (int64_t)d.channels_out * (d.dst_type == LCE_HIP_I8 ? 1 : 4);
   // (max_batch_per_launch keeps a launch's output below 2 GiB: the kernel's offsets are 32-bit)
-  P.out_bytes = (uint32_t)std::min<int64_t>(m * row, (1ll << 31) - 1);
+  P.out_bytes = (uint32_t)std::min<int64_t>(out_bytes_of(p, batch_chunk), (1ll << 31) - 1);
   P.a_bt = (float)p.backtransform_add;
   P.cmin = (float)p.clamp_min;
   P.cmax = (float)p.clamp_max;
@@ -704,8 +700,7 @@ bool direct_geometry(const HostPlan& p, const MfmaCfg& c, int* tpi, int* halo_ro
   const lce_hip_bconv2d_desc& d = p.d;
   if (!mfma_supported(p)) return false;
   const int cpad = ceil_div(d.channels_in, 64) * 64;
-  const int64_t wp = std::max<int64_t>(p.pad_w + d.in_width,
-                                       (int64_t)(p.out_w - 1) * d.stride_width + (d.filter_width - 1) * d.dilation_width + 1);
+  const int64_t wp = padded_width(p);
   const int bm = c.bm(), ohow = p.out_h * p.out_w;
   const int64_t ring = (int64_t)MfmaCfg::kDirectStages * c.bn() * 32;
   const int64_t stride = (cpad / 32) * 16 + 16;
@@ -846,307 +841,317 @@ MfmaArgs make_mfma_args(const HostPlan& p, int batch_chunk) {
 }
 
 // ------------------------------------------------------------------------------------
-// Which kernel runs a layer: a cost estimate per candidate (lce_plan_cost.cpp), not a list of shapes (round 5)
+// Which kernel runs a layer: a cost estimate per candidate (lce_plan_cost.cpp), not a list of shapes (round 5).  select_kernel, at the
+// end, is the dispatcher; the steps it names come first.  They read the caller's options through a const PlanOptions& -- trying a
+// candidate never writes one (a candidate is a StreamPick, handed to plan_stream).
 // ------------------------------------------------------------------------------------
-// the streaming kernel's candidates: the planner's own segments, then interleaved runs of r-row segments
-struct StreamCandidate { int rows, interleave; double us; int occ = 1; };
+// What pricing the streaming family settled
+enum class Family { kNone, kStream, kWstream, kBlockGemm };
+struct FamilyChoice {
+  Family take = Family::kNone;
+  StreamPick pick;          // kStream: the candidate to run
+  double us = -1.0;         // kStream / kWstream: its estimate
+  std::string refusal;      // kNone: why a forced engine=stream / engine=wstream cannot run
+};
 
-// plan_wstream succeeded: the plan runs the weight-streaming kernel
-static void use_wstream_plan(HostPlan& p) {
+// The streaming kernel's candidates: the planner's own segments, then interleaved runs of r-row segments.  stream_rows /
+// stream_interleave pin theirs.
+static std::vector<StreamPick> stream_candidates(const HostPlan& p, const PlanOptions& o) {
+  const int rows_pref = o.stream_rows_pref, il_pref = o.stream_interleave_pref, occ_pref = o.stream_occ_pref;
+  std::vector<StreamPick> cands;
+  if (il_pref <= 0) cands.push_back(StreamPick{rows_pref, 0});
+  if (il_pref != 0)
+    for (int r = p.out_h - 1; r >= 2; --r) {
+      if (p.out_h % r != 0 || (rows_pref != 0 && rows_pref != r)) continue;
+      // (segments that would leave more than 15 % of their last pixel block empty are not worth pricing: every block of
+      //  such a run pays the padded matrix work and the out-of-line stores)
+      const int px = r * p.out_w;
+      if (rows_pref == 0 && ceil_div(px, 32) * 32 * 100 > px * 115) continue;
+      cands.push_back(StreamPick{r, 1});
+    }
+  // (nothing to interleave: one segment per image)
+  if (il_pref == 1 && cands.empty()) cands.push_back(StreamPick{rows_pref, 1});
+  // every candidate again with two blocks per CU where the instance is compiled for that (a candidate whose two blocks' LDS do not
+  // fit a CU is refused by plan_stream and drops out); stream_blocks_per_cu pins the choice
+  if (occ_pref == 2 || (occ_pref == 0 && stream_blocks_per_cu_max(p) >= 2)) {
+    const size_t n1 = cands.size();
+    for (size_t i = 0; i < n1; ++i) { cands.push_back(cands[i]); cands.back().occ = 2; }
+    if (occ_pref == 2) cands.erase(cands.begin(), cands.begin() + (long)n1);
+  }
+  return cands;
+}
+
+// Plans and prices one candidate (c.us; -1 and false: it cannot run, or it is the same launch as without interleaving)
+static bool price_stream_pick(HostPlan& p, int batch_chunk, StreamPick& c, std::string* first_err) {
+  c.us = -1.0;
+  const std::string err = plan_stream(p, batch_chunk, c);
+  if (!err.empty()) { if (first_err->empty()) *first_err = err; return false; }
+  if (c.interleave && p.st_gstr <= 1) return false;      // (one segment per block: the same plan as without)
+  c.us = estimate_stream_us(p, batch_chunk);
+  return true;
+}
+
+// The streaming family: every candidate is planned and priced (estimate_*_us); the cheapest runs.  engine=stream restricts the choice
+// to the weight-stationary kernel's own variants; under the auto rule the weight-streaming kernel and the block GEMM are priced too.
+static FamilyChoice price_stream_family(HostPlan& p, const PlanOptions& o, int64_t pixels, int batch_chunk) {
+  FamilyChoice r;
+  if (!stream_supported(p)) { r.refusal = plan_stream(p, 1, StreamPick{}); return r; }      // (the message that says why)
+  std::vector<StreamPick> cands = stream_candidates(p, o);
+  int best = -1;
+  auto price_from = [&](size_t first) {
+    for (size_t i = first; i < cands.size(); ++i)
+      if (price_stream_pick(p, batch_chunk, cands[i], &r.refusal) && (best < 0 || cands[i].us < cands[best].us)) best = (int)i;
+  };
+  price_from(0);
+  if (best < 0 && o.stream_interleave_pref == 1) {
+    // stream_interleave=1 and nothing to interleave (every interleaved candidate came out as one segment per block, or could not be
+    // planned): the consecutive-segment plan is the same launch -- take it instead of refusing engine=stream / dropping the family
+    cands.push_back(StreamPick{o.stream_rows_pref, 0, o.stream_occ_pref == 2 ? 2 : 1});
+    price_from(cands.size() - 1);
+  }
+  if (best >= 0) { r.take = Family::kStream; r.pick = cands[best]; r.us = cands[best].us; }
+  else if (r.refusal.empty()) r.refusal = "bconv2d: the streaming kernel cannot run this launch";
+  double best_us = best >= 0 ? r.us : 1e30;
+  // (LCE_PLAN_DEBUG, read at plan creation: the estimates of every candidate, on stderr: tools/planner_regret.py)
+  const bool debug = p.dbg_level >= 1;
+  if (debug)
+    for (const StreamPick& c : cands)
+      fprintf(stderr, "[lce plan] stream rows=%d il=%d blocks/CU=%d: %.2f us\n", c.rows, c.interleave, c.occ, c.us);
+  if (!auto_rule(o)) return r;
+  // (LCE_PLAN_NO_WSTREAM, read at plan creation: an A/B aid)
+  if (wstream_supported(p) && !p.dbg_no_wstream && plan_wstream(p, batch_chunk).empty()) {
+    const double us = estimate_wstream_us(p, batch_chunk);
+    if (debug) fprintf(stderr, "[lce plan] wstream images=%d blocks=%d: %.2f us\n", p.ws_ipb, p.ws_nb, us);
+    if (us < best_us) { best_us = r.us = us; r.take = Family::kWstream; }
+  }
+  const double gemm_us = estimate_block_gemm_us(p, pixels);
+  if (debug) fprintf(stderr, "[lce plan] block GEMM: %.2f us\n", gemm_us);
+  if (gemm_us < best_us) r.take = Family::kBlockGemm;      // priced cheapest among the matrix-core kernels: not the xor-popcount engine then
+  return r;
+}
+
+// engine=wstream: the weight-streaming kernel (activations stationary in LDS), or why it cannot run
+static FamilyChoice plan_forced_wstream(HostPlan& p, int batch_chunk) {
+  FamilyChoice r;
+  r.refusal = plan_wstream(p, batch_chunk);
+  if (r.refusal.empty()) { r.take = Family::kWstream; r.us = estimate_wstream_us(p, batch_chunk); }
+  return r;
+}
+
+// The plan runs the kernel of the streaming family that `c` names: the weight-stationary kernel on the K-major FP4 weight image, or the
+// weight-streaming kernel on the tile-major one ([32-channel tile][K-step][K-half][32 x 16 B], pack_for_mfma); 64-channel granularity.
+static std::string commit_stream_family(HostPlan& p, const FamilyChoice& c, int batch_chunk) {
   const lce_hip_bconv2d_desc& d = p.d;
+  const bool wstream = c.take == Family::kWstream;
+  p.est_us = c.us;
+  if (!wstream) {
+    // plan_stream and plan_wstream both write st_tabs, and the candidates were planned one over the other: the chosen one is planned
+    // again, last
+    const std::string err = plan_stream(p, batch_chunk, c.pick);
+    if (!err.empty()) return err;     // (cannot happen: the same plan succeeded a moment ago)
+  }
   const MfmaCfg want = *mfma_cfg_by_tile(128, 64);
-  const bool repack = p.wq.empty() || p.mfma.bn() != want.bn() || p.wq_layout != 1 || p.kch != stream_chunks(d);
-  p.wq_layout = 1;                       // tile-major: [32-channel tile][K-step][K-half][32 x 16 B] (pack_for_mfma)
+  const int layout = wstream ? 1 : 0;
+  const bool repack = p.wq.empty() || p.mfma.bn() != want.bn() || p.wq_layout != layout || p.kch != stream_chunks(d);
+  p.wq_layout = layout;
   p.mfma = want;
   p.use_mfma = true;
-  p.use_wstream = true;
-  p.use_stream = false;
+  p.use_wstream = wstream;
+  p.use_stream = !wstream;
   p.use_tiled = false;
   p.cpad = stream_chunks(d) * 64;
   p.npad = ceil_div(d.channels_out, 64) * 64;
-  p.hp = (int)std::max<int64_t>(p.pad_h + d.in_height, (int64_t)(p.out_h - 1) * d.stride_height + d.filter_height);
+  p.hp = (int)padded_height(p);
   if (repack && p.have_weights) pack_for_mfma(p);
   char nm[96];
-  snprintf(nm, sizeof nm, "bconv2d_wstream<%s,3x3x%d,images%d,blocks%d>",
-           d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked", 64 * stream_chunks(d), p.ws_ipb, p.ws_nb);
+  if (wstream) {
+    snprintf(nm, sizeof nm, "bconv2d_wstream<%s,3x3x%d,images%d,blocks%d>", dst_name(d), 64 * stream_chunks(d), p.ws_ipb, p.ws_nb);
+  } else {
+    char ph[40] = "";
+    if ((4 >> p.st_pph_log) < std::min(4, ceil_div(d.channels_out, 64))) snprintf(ph, sizeof ph, ",phases%d", 1 << p.st_pph_log);
+    if (p.st_nstrip > 1) snprintf(ph + strlen(ph), sizeof ph - strlen(ph), ",strips%d", p.st_wso);
+    if (p.st_gstr > 1) snprintf(ph + strlen(ph), sizeof ph - strlen(ph), ",il");
+    if (p.st_occ > 1) snprintf(ph + strlen(ph), sizeof ph - strlen(ph), ",x%d", p.st_occ);
+    snprintf(nm, sizeof nm, "bconv2d_stream<%s,3x3x%d,rows%d%s>", dst_name(d), 64 * stream_chunks(d), p.st_rs, ph);
+  }
   p.kernel_name = nm;
+  return "";
 }
 
-static std::string select_kernel_impl(HostPlan& p, int64_t pixels);
-
-std::string select_kernel(HostPlan& p, int64_t pixels) {
-  const std::string err = select_kernel_impl(p, pixels);
-  // int8 plans of the matrix-core kernels: the epilogue's constants follow the kernel that was selected (its arithmetic decides what
-  // can be proven); cheap (a bisection per channel), so simply redone at every selection
-  if (err.empty() && p.d.dst_type == LCE_HIP_I8 && p.use_mfma && p.have_weights && !p.wq.empty()) prepare_int8_epilogue(p);
-  return err;
-}
-
-static std::string select_kernel_impl(HostPlan& p, int64_t pixels) {
+// The block GEMM's tile and whether its direct variant (LDS halo, no workspace) runs: the forced tile, or the rules' choice
+static std::string choose_gemm_tile(const HostPlan& p, const PlanOptions& o, int64_t pixels, MfmaCfg* want, bool* direct) {
   const lce_hip_bconv2d_desc& d = p.d;
-  const bool bp = d.dst_type == LCE_HIP_BITPACKED;
-  p.ch = (p.cwg % 4 == 0) ? 4 : (p.cwg % 2 == 0) ? 2 : 1;
+  *want = choose_mfma_cfg(p, pixels);
+  *direct = false;
+  if (o.engine_pref >= kEngineMfma && o.tile_pref.tm != 0) {
+    const MfmaCfg* forced = mfma_cfg_by_tile(o.tile_pref.tm, o.tile_pref.tn);
+    if (!forced) return "bconv2d: no matrix-core kernel instance for the requested block tile";
+    if (d.groups > 1 && p.npg % forced->bn())
+      return "bconv2d: the requested block tile would straddle channel groups";
+    *want = *forced;
+    *direct = o.engine_pref == kEngineDirect;
+  } else if (o.engine_pref != kEngineMfma) {
+    // auto / engine=direct without a tile: the direct variant when a good tile exists
+    MfmaCfg dc;
+    // (auto: a launch of at most half a round of blocks with a deep K loop -- >= 27 K-steps: 3x3 over 192+ channels -- runs at the
+    //  latency of one block's K loop, and the workspace GEMM's is shorter: its A fragments come from the expanded workspace, no halo
+    //  expansion in front of the first MFMA.  profiles/r05/engine_sweep_*.jsonl, batch 1 / 16: direct / workspace = 1.03 ... 1.26 on
+    //  every such row, 0.99 at worst; with more blocks the direct variant wins by 10 ... 50 %.)
+    const int ks_deep = d.filter_height * d.filter_width * ceil_div(d.channels_in / std::max(1, d.groups), 64);
+    auto tiny_deep = [&](const MfmaCfg& c) {
+      return o.engine_pref == kEngineAuto && ks_deep >= 27 && ((pixels + c.bm() - 1) / c.bm()) * ceil_div(d.channels_out, c.bn()) <= 128;
+    };
+    if (choose_direct_cfg(p, &dc) && !tiny_deep(dc)) {
+      *want = dc;
+      *direct = true;
+    } else if (o.engine_pref == kEngineDirect) {
+      // forced: take any tile whose halo fits, whatever the padding waste
+      for (int bm : {128, 256}) {
+        const MfmaCfg* c = mfma_cfg_by_tile(bm, d.channels_out > 64 && (d.groups == 1 || p.npg % 128 == 0) ? 128 : 64);
+        int a, b, c2, e, f, ttx, hw;   // (with the 2-D tile outputs: a wide image's strip may not fit where its 2-D tile does)
+        if (c && direct_geometry(p, *c, &a, &b, &c2, &e, &f, kDirectLdsMax, &ttx, &hw)) { *want = *c; break; }
+      }
+      *direct = true;  // (no tile fits: reported by the caller's direct_geometry)
+    }
+  }
+  return "";
+}
 
-  // ---- engine: matrix cores vs xor-popcount VALU ----
-  p.use_mfma = false;
-  p.use_direct = false;
-  p.use_pointwise = false;
-  if (p.engine_pref == kEnginePointwise && !pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj))
-    return "bconv2d: the pointwise kernel runs 1x1 ungrouped convolutions with 64, 128, 256 or 512 input channels (after padding to 64) "
-           "and a multiple of 32 output channels (pointwise_channels must divide them)";
-  if (p.engine_pref >= kEngineMfma && !mfma_supported(p))
-    return "bconv2d: the matrix-core engine cannot run this convolution (channels per group not a multiple of 64, or too deep)";
-  p.use_stream = false;
-  p.use_wstream = false;
-  p.est_us = -1.0;
-  if (p.engine_pref == kEngineWstream) {
-    // weight-streaming kernel (activations stationary in LDS): the planner's FP4 weight image with 64-channel granularity
-    const int batch_chunk = (int)std::max<int64_t>(1, pixels / std::max<int64_t>(1, (int64_t)p.out_h * p.out_w));
-    const std::string err = plan_wstream(p, batch_chunk);
-    if (!err.empty()) return err;
-    p.est_us = estimate_wstream_us(p, batch_chunk);
-    use_wstream_plan(p);
-    return "";
+// The block GEMM (workspace or direct variant) and, on top of the same weight image, the pointwise kernel
+static std::string select_block_gemm(HostPlan& p, const PlanOptions& o, int64_t pixels) {
+  const lce_hip_bconv2d_desc& d = p.d;
+  p.use_mfma = true;
+  p.use_tiled = false;
+  p.est_us = estimate_block_gemm_us(p, pixels);
+  MfmaCfg want;
+  bool direct;
+  const std::string err = choose_gemm_tile(p, o, pixels, &want, &direct);
+  if (!err.empty()) return err;
+  const bool repack = p.wq.empty() || p.mfma.bn() != want.bn() || p.wq_layout != 0 ||
+                      p.kch != (d.groups > 1 ? group_chunks(d) : ceil_div(d.channels_in, 64));
+  p.wq_layout = 0;
+  p.mfma = want;
+  p.cpad = ceil_div(d.channels_in, 64) * 64;
+  p.npad = ceil_div(d.channels_out, want.bn()) * want.bn();
+  p.hp = (int)padded_height(p);
+  p.wp = (int)padded_width(p);
+  if (repack && p.have_weights) pack_for_mfma(p);
+  if (direct) {
+    if (!direct_geometry(p, want, &p.tpi, &p.halo_rows, &p.ps, &p.halo_bytes, &p.ipt,
+                         o.engine_pref == kEngineDirect ? kDirectLdsMax : kDirectLdsAuto, &p.tile_tx, &p.halo_w))
+      return "bconv2d: the direct matrix-core variant cannot hold this tile's input halo in LDS";
+    p.use_direct = true;
   }
-  const bool auto_rule = p.engine_pref == kEngineAuto && p.kernel_pref == kKernelAuto && p.tile_pref.tm == 0;
-  bool gemm_by_estimate = false;      // the block GEMM was priced cheapest among the matrix-core kernels: not the xor-popcount engine then
-  if ((p.engine_pref == kEngineStream || auto_rule) && stream_supported(p)) {
-    // The streaming family: every candidate is planned and priced (estimate_*_us above); the cheapest runs.  engine=stream
-    // restricts the choice to the weight-stationary kernel's own variants; stream_rows / stream_interleave pin theirs.
-    const int batch_chunk = (int)std::max<int64_t>(1, pixels / std::max<int64_t>(1, (int64_t)p.out_h * p.out_w));
-    const int rows_pref = p.stream_rows_pref, il_pref = p.stream_interleave_pref;
-    std::vector<StreamCandidate> cands;
-    if (il_pref <= 0) cands.push_back(StreamCandidate{rows_pref, 0, 0.0});
-    if (il_pref != 0)
-      for (int r = p.out_h - 1; r >= 2; --r) {
-        if (p.out_h % r != 0 || (rows_pref != 0 && rows_pref != r)) continue;
-        // (segments that would leave more than 15 % of their last pixel block empty are not worth pricing: every block of
-        //  such a run pays the padded matrix work and the out-of-line stores)
-        const int px = r * p.out_w;
-        if (rows_pref == 0 && ceil_div(px, 32) * 32 * 100 > px * 115) continue;
-        cands.push_back(StreamCandidate{r, 1, 0.0});
-      }
-    // (nothing to interleave: one segment per image)
-    if (il_pref == 1 && cands.empty()) cands.push_back(StreamCandidate{rows_pref, 1, 0.0});
-    // every candidate again with two blocks per CU where the instance is compiled for that (a candidate whose two blocks' LDS do not
-    // fit a CU is refused by plan_stream and drops out); stream_blocks_per_cu pins the choice
-    const int occ_pref = p.stream_occ_pref;
-    if (occ_pref == 2 || (occ_pref == 0 && stream_blocks_per_cu_max(p) >= 2)) {
-      const size_t n1 = cands.size();
-      for (size_t i = 0; i < n1; ++i) { cands.push_back(cands[i]); cands.back().occ = 2; }
-      if (occ_pref == 2) cands.erase(cands.begin(), cands.begin() + (long)n1);
-    }
-    int best = -1;
-    std::string first_err;
-    for (size_t i = 0; i < cands.size(); ++i) {
-      p.stream_rows_pref = cands[i].rows;
-      p.stream_interleave_pref = cands[i].interleave;
-      p.stream_occ_pref = cands[i].occ;
-      const std::string err = plan_stream(p, batch_chunk);
-      if (!err.empty()) { if (first_err.empty()) first_err = err; cands[i].us = -1.0; continue; }
-      if (cands[i].interleave && p.st_gstr <= 1) { cands[i].us = -1.0; continue; }      // (one segment per block: the same plan as without)
-      cands[i].us = estimate_stream_us(p, batch_chunk);
-      if (best < 0 || cands[i].us < cands[best].us) best = (int)i;
-    }
-    if (best < 0 && il_pref == 1) {
-      // stream_interleave=1 and nothing to interleave (every interleaved candidate came out as one segment per block, or could not be
-      // planned): the consecutive-segment plan is the same launch -- take it instead of refusing engine=stream / dropping the family
-      cands.push_back(StreamCandidate{rows_pref, 0, 0.0});
-      cands.back().occ = occ_pref == 2 ? 2 : 1;
-      p.stream_rows_pref = rows_pref;
-      p.stream_interleave_pref = 0;
-      p.stream_occ_pref = cands.back().occ;
-      const std::string err = plan_stream(p, batch_chunk);
-      if (err.empty()) { cands.back().us = estimate_stream_us(p, batch_chunk); best = (int)cands.size() - 1; }
-      else { cands.back().us = -1.0; if (first_err.empty()) first_err = err; }
-    }
-    p.stream_rows_pref = rows_pref;
-    p.stream_interleave_pref = il_pref;
-    p.stream_occ_pref = occ_pref;
-    double best_us = best >= 0 ? cands[best].us : 1e30;
-    bool take_wstream = false;
-    // (LCE_PLAN_DEBUG, read at plan creation: the estimates of every candidate, on stderr: tools/planner_regret.py)
-    const bool debug = p.dbg_level >= 1;
-    if (debug)
-      for (const StreamCandidate& c : cands)
-        fprintf(stderr, "[lce plan] stream rows=%d il=%d blocks/CU=%d: %.2f us\n", c.rows, c.interleave, c.occ, c.us);
-    if (auto_rule) {
-      // (LCE_PLAN_NO_WSTREAM, read at plan creation: an A/B aid)
-      if (wstream_supported(p) && !p.dbg_no_wstream && plan_wstream(p, batch_chunk).empty()) {
-        const double us = estimate_wstream_us(p, batch_chunk);
-        if (debug) fprintf(stderr, "[lce plan] wstream images=%d blocks=%d: %.2f us\n", p.ws_ipb, p.ws_nb, us);
-        if (us < best_us) { best_us = us; take_wstream = true; }
-      }
-      const double gemm_us = estimate_block_gemm_us(p, pixels);
-      if (debug) fprintf(stderr, "[lce plan] block GEMM: %.2f us\n", gemm_us);
-      if (gemm_us < best_us) { best = -1; take_wstream = false; best_us = -1.0; gemm_by_estimate = true; }   // the block GEMM, below
-    }
-    if (take_wstream) {
-      p.est_us = best_us;
-      use_wstream_plan(p);
-      return "";
-    }
-    if (best >= 0 && best_us >= 0.0) {
-      p.est_us = best_us;
-      p.stream_rows_pref = cands[best].rows;
-      p.stream_interleave_pref = cands[best].interleave;
-      p.stream_occ_pref = cands[best].occ;
-      const std::string err = plan_stream(p, batch_chunk);
-      p.stream_rows_pref = rows_pref;
-      p.stream_interleave_pref = il_pref;
-      p.stream_occ_pref = occ_pref;
-      if (!err.empty()) return err;     // (cannot happen: the same plan succeeded a moment ago)
-      const MfmaCfg want = *mfma_cfg_by_tile(128, 64);
-      const bool repack = p.wq.empty() || p.mfma.bn() != want.bn() || p.wq_layout != 0 || p.kch != stream_chunks(d);
-      p.wq_layout = 0;
-      p.mfma = want;
-      p.use_mfma = true;
-      p.use_stream = true;
-      p.use_tiled = false;
-      p.cpad = stream_chunks(d) * 64;
-      p.npad = ceil_div(d.channels_out, 64) * 64;
-      p.hp = (int)std::max<int64_t>(p.pad_h + d.in_height, (int64_t)(p.out_h - 1) * d.stride_height + d.filter_height);
-      if (repack && p.have_weights) pack_for_mfma(p);
-      char nm[96];
-      char ph[40] = "";
-      if ((4 >> p.st_pph_log) < std::min(4, ceil_div(d.channels_out, 64))) snprintf(ph, sizeof ph, ",phases%d", 1 << p.st_pph_log);
-      if (p.st_nstrip > 1) snprintf(ph + strlen(ph), sizeof ph - strlen(ph), ",strips%d", p.st_wso);
-      if (p.st_gstr > 1) snprintf(ph + strlen(ph), sizeof ph - strlen(ph), ",il");
-      if (p.st_occ > 1) snprintf(ph + strlen(ph), sizeof ph - strlen(ph), ",x%d", p.st_occ);
-      snprintf(nm, sizeof nm, "bconv2d_stream<%s,3x3x%d,rows%d%s>",
-               d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked", 64 * stream_chunks(d), p.st_rs, ph);
-      p.kernel_name = nm;
-      return "";
-    }
-    if (p.engine_pref == kEngineStream) return first_err.empty() ? std::string("bconv2d: the streaming kernel cannot run this launch") : first_err;
-  } else if (p.engine_pref == kEngineStream) {
-    return plan_stream(p, 1);      // (the message that says why)
-  }
-  if (p.engine_pref >= kEngineMfma || (p.engine_pref == kEngineAuto && p.kernel_pref == kKernelAuto && p.tile_pref.tm == 0 &&
-                             mfma_supported(p) && (gemm_by_estimate || pixels * d.channels_out >= (1 << 16)))) {
-    p.use_mfma = true;
-    p.use_tiled = false;
-    p.est_us = estimate_block_gemm_us(p, pixels);
-    MfmaCfg want = choose_mfma_cfg(p, pixels);
-    bool direct = false;
-    if (p.engine_pref >= kEngineMfma && p.tile_pref.tm != 0) {
-      const MfmaCfg* forced = mfma_cfg_by_tile(p.tile_pref.tm, p.tile_pref.tn);
-      if (!forced) return "bconv2d: no matrix-core kernel instance for the requested block tile";
-      if (d.groups > 1 && p.npg % forced->bn())
-        return "bconv2d: the requested block tile would straddle channel groups";
-      want = *forced;
-      direct = p.engine_pref == kEngineDirect;
-    } else if (p.engine_pref != kEngineMfma) {
-      // auto / engine=direct without a tile: the direct variant when a good tile exists
-      MfmaCfg dc;
-      // (auto: a launch of at most half a round of blocks with a deep K loop -- >= 27 K-steps: 3x3 over 192+ channels -- runs at the
-      //  latency of one block's K loop, and the workspace GEMM's is shorter: its A fragments come from the expanded workspace, no halo
-      //  expansion in front of the first MFMA.  profiles/r05/engine_sweep_*.jsonl, batch 1 / 16: direct / workspace = 1.03 ... 1.26 on
-      //  every such row, 0.99 at worst; with more blocks the direct variant wins by 10 ... 50 %.)
-      const int ks_deep = d.filter_height * d.filter_width * ceil_div(d.channels_in / std::max(1, d.groups), 64);
-      auto tiny_deep = [&](const MfmaCfg& c) {
-        return p.engine_pref == kEngineAuto && ks_deep >= 27 && ((pixels + c.bm() - 1) / c.bm()) * ceil_div(d.channels_out, c.bn()) <= 128;
-      };
-      if (choose_direct_cfg(p, &dc) && !tiny_deep(dc)) {
-        want = dc;
-        direct = true;
-      } else if (p.engine_pref == kEngineDirect) {
-        // forced: take any tile whose halo fits, whatever the padding waste
-        for (int bm : {128, 256}) {
-          const MfmaCfg* c = mfma_cfg_by_tile(bm, d.channels_out > 64 && (d.groups == 1 || p.npg % 128 == 0) ? 128 : 64);
-          int a, b, c2, e, f, ttx, hw;   // (with the 2-D tile outputs: a wide image's strip may not fit where its 2-D tile does)
-          if (c && direct_geometry(p, *c, &a, &b, &c2, &e, &f, kDirectLdsMax, &ttx, &hw)) { want = *c; direct = true; break; }
-        }
-        if (!direct) direct = true;  // reported below by direct_geometry
-      }
-    }
-    const bool repack = p.wq.empty() || p.mfma.bn() != want.bn() || p.wq_layout != 0 ||
-                        p.kch != (d.groups > 1 ? group_chunks(d) : ceil_div(d.channels_in, 64));
-    p.wq_layout = 0;
-    p.mfma = want;
-    p.cpad = ceil_div(d.channels_in, 64) * 64;
-    p.npad = ceil_div(d.channels_out, want.bn()) * want.bn();
-    p.hp = (int)std::max<int64_t>(p.pad_h + d.in_height,
-                                  (int64_t)(p.out_h - 1) * d.stride_height + (d.filter_height - 1) * d.dilation_height + 1);
-    p.wp = (int)std::max<int64_t>(p.pad_w + d.in_width,
-                                  (int64_t)(p.out_w - 1) * d.stride_width + (d.filter_width - 1) * d.dilation_width + 1);
-    if (repack && p.have_weights) pack_for_mfma(p);
-    if (direct) {
-      if (!direct_geometry(p, want, &p.tpi, &p.halo_rows, &p.ps, &p.halo_bytes, &p.ipt,
-                           p.engine_pref == kEngineDirect ? kDirectLdsMax : kDirectLdsAuto, &p.tile_tx, &p.halo_w))
-        return "bconv2d: the direct matrix-core variant cannot hold this tile's input halo in LDS";
-      p.use_direct = true;
-    }
-    char nm[96];
-    if (!direct) { p.tile_tx = 0; p.halo_w = p.wp; }
-    snprintf(nm, sizeof nm, "bconv2d_mfma%s<%s,%dx%d>%s", p.use_direct ? "_direct" : "",
-             d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked", want.bm(), want.bn(),
-             p.use_direct && p.tile_tx > 0 ? "/2d" : "");
+  char nm[96];
+  if (!direct) { p.tile_tx = 0; p.halo_w = p.wp; }
+  snprintf(nm, sizeof nm, "bconv2d_mfma%s<%s,%dx%d>%s", p.use_direct ? "_direct" : "", dst_name(d), want.bm(), want.bn(),
+           p.use_direct && p.tile_tx > 0 ? "/2d" : "");
+  p.kernel_name = nm;
+  // 1x1 stride-1 layers: the streaming kernel on top of the same weight image (the block GEMM stays the
+  // fallback for output pointers that are not 16-byte aligned)
+  if ((o.engine_pref == kEnginePointwise || auto_rule(o)) && pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj) &&
+      (o.engine_pref == kEnginePointwise || pointwise_preferred(p, pixels))) {
+    p.use_pointwise = true;
+    snprintf(nm, sizeof nm, "bconv2d_pointwise<%s,K%dx64,N%dx32%s>", dst_name(d), p.pw_nc, p.pw_nj,
+             d.stride_height != 1 || d.stride_width != 1 ? ",strided" : "");
     p.kernel_name = nm;
-    // 1x1 stride-1 layers: the streaming kernel on top of the same weight image (the block GEMM stays the
-    // fallback for output pointers that are not 16-byte aligned)
-    if ((p.engine_pref == kEnginePointwise || (p.engine_pref == kEngineAuto && p.tile_pref.tm == 0)) && pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj) &&
-        (p.engine_pref == kEnginePointwise || pointwise_preferred(p, pixels))) {
-      p.use_pointwise = true;
-      snprintf(nm, sizeof nm, "bconv2d_pointwise<%s,K%dx64,N%dx32%s>",
-               d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked", p.pw_nc, p.pw_nj,
-               d.stride_height != 1 || d.stride_width != 1 ? ",strided" : "");
-      p.kernel_name = nm;
-    }
-    return "";
   }
+  return "";
+}
 
-  TileShape chosen{0, 0};
-  if (p.kernel_pref != kKernelGeneral) {
-    if (p.tile_pref.tm != 0) {
-      if (tiled_supports(p, p.tile_pref.tn)) chosen = p.tile_pref;
-      else if (p.kernel_pref == kKernelTiled) return "bconv2d: the requested tile cannot run this convolution";
-    } else {
-      // One wave task = 64*TM pixels x TN channels.  Measured on MI355X
-      // (profiles/r01/tile_sweep_v8.jsonl): one pixel per lane wins on every BASELINE layer --
-      // the bigger accumulator tiles (4x16, 2x32) run out of scalar registers for the weight
-      // words and spill -- with 32 channels per task on long launches (L0: 1x32 0.80 ms vs 4x16
-      // 0.90) and 16 on short ones (14x14x256: 1x16 0.060 vs 1x32 0.071; 7x7x512: 0.064 vs 0.085).
-      const TileShape order_f[] = {{1, 32}, {1, 16}, {2, 16}, {2, 32}, {4, 16}};
-      const TileShape order_b[] = {{1, 32}, {2, 32}};
-      const TileShape* order = bp ? order_b : order_f;
-      const int count = bp ? 2 : 5;
-      for (int k = 0; k < count && chosen.tm == 0; ++k) {
-        const TileShape t = order[k];
-        if (!tiled_supports(p, t.tn)) continue;
-        const int64_t tasks = ((pixels + 64 * t.tm - 1) / (64 * t.tm)) * ceil_div(d.channels_out, t.tn);
-        if (!bp && k == 0 && tasks < 32768 && tiled_supports(p, 16)) continue;   // short launch: 1x16
-        chosen = t;
-      }
-      if (chosen.tm == 0) {  // nothing large enough: take the smallest supported tile
-        for (int k = count - 1; k >= 0 && chosen.tm == 0; --k)
-          if (tiled_supports(p, order[k].tn)) chosen = order[k];
-      }
+// The xor-popcount engine's tile: the forced one, or by the rule; {0, 0}: the general kernel
+static std::string choose_valu_tile(const HostPlan& p, const PlanOptions& o, int64_t pixels, TileShape* chosen) {
+  const bool bp = p.d.dst_type == LCE_HIP_BITPACKED;
+  *chosen = TileShape{0, 0};
+  if (o.kernel_pref == kKernelGeneral) return "";
+  if (o.tile_pref.tm != 0) {
+    if (tiled_supports(p, o.tile_pref.tn)) *chosen = o.tile_pref;
+    else if (o.kernel_pref == kKernelTiled) return "bconv2d: the requested tile cannot run this convolution";
+  } else {
+    // One wave task = 64*TM pixels x TN channels.  Measured on MI355X
+    // (profiles/r01/tile_sweep_v8.jsonl): one pixel per lane wins on every BASELINE layer --
+    // the bigger accumulator tiles (4x16, 2x32) run out of scalar registers for the weight
+    // words and spill -- with 32 channels per task on long launches (L0: 1x32 0.80 ms vs 4x16
+    // 0.90) and 16 on short ones (14x14x256: 1x16 0.060 vs 1x32 0.071; 7x7x512: 0.064 vs 0.085).
+    const TileShape order_f[] = {{1, 32}, {1, 16}, {2, 16}, {2, 32}, {4, 16}};
+    const TileShape order_b[] = {{1, 32}, {2, 32}};
+    const TileShape* order = bp ? order_b : order_f;
+    const int count = bp ? 2 : 5;
+    for (int k = 0; k < count && chosen->tm == 0; ++k) {
+      const TileShape t = order[k];
+      if (!tiled_supports(p, t.tn)) continue;
+      const int64_t tasks = ((pixels + 64 * t.tm - 1) / (64 * t.tm)) * ceil_div(p.d.channels_out, t.tn);
+      if (!bp && k == 0 && tasks < 32768 && tiled_supports(p, 16)) continue;   // short launch: 1x16
+      *chosen = t;
     }
+    // nothing large enough: take the smallest supported tile
+    for (int k = count - 1; k >= 0 && chosen->tm == 0; --k)
+      if (tiled_supports(p, order[k].tn)) *chosen = order[k];
   }
-  if (chosen.tm == 0 && p.kernel_pref == kKernelTiled)
+  if (chosen->tm == 0 && o.kernel_pref == kKernelTiled)
     return "bconv2d: the tiled kernel cannot run this convolution (grouped, channels per group "
            "not a multiple of the tile)";
+  return "";
+}
 
-  const bool tiled = chosen.tm != 0;
+// The xor-popcount engine: the tiled kernel on its packed operands, or the general kernel
+static std::string select_valu(HostPlan& p, const PlanOptions& o, int64_t pixels) {
+  const lce_hip_bconv2d_desc& d = p.d;
+  TileShape chosen;
+  const std::string err = choose_valu_tile(p, o, pixels, &chosen);
+  if (!err.empty()) return err;
   char name[96];
-  if (tiled) {
+  if (chosen.tm != 0) {
     const bool repack = !p.use_tiled || p.tile.tn != chosen.tn || p.packed.empty();
     p.use_tiled = true;
     p.tile = chosen;
     if (repack && p.have_weights) pack_for_tile(p);
     p.nt = ceil_div(d.channels_out, chosen.tn);
-    snprintf(name, sizeof name, "bconv2d_tiled<%s,TM=%d,TN=%d,CH=%d>",
-             d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked",
-             chosen.tm, chosen.tn, p.ch);
+    snprintf(name, sizeof name, "bconv2d_tiled<%s,TM=%d,TN=%d,CH=%d>", dst_name(d), chosen.tm, chosen.tn, p.ch);
   } else {
     p.use_tiled = false;
     p.tile = TileShape{0, 0};
-    snprintf(name, sizeof name, "bconv2d_general<%s>",
-             d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked");
+    snprintf(name, sizeof name, "bconv2d_general<%s>", dst_name(d));
   }
   p.kernel_name = name;
   return "";
+}
+
+std::string select_kernel(HostPlan& p, int64_t pixels) {
+  const PlanOptions& o = p;
+  const lce_hip_bconv2d_desc& d = p.d;
+  p.ch = (p.cwg % 4 == 0) ? 4 : (p.cwg % 2 == 0) ? 2 : 1;
+  p.use_mfma = false;
+  p.use_direct = false;
+  p.use_pointwise = false;
+  if (o.engine_pref == kEnginePointwise && !pointwise_supported(p, pixels, &p.pw_nc, &p.pw_nj))
+    return "bconv2d: the pointwise kernel runs 1x1 ungrouped convolutions with 64, 128, 256 or 512 input channels (after padding to 64) "
+           "and a multiple of 32 output channels (pointwise_channels must divide them)";
+  if (o.engine_pref >= kEngineMfma && !mfma_supported(p))
+    return "bconv2d: the matrix-core engine cannot run this convolution (channels per group not a multiple of 64, or too deep)";
+  p.use_stream = false;
+  p.use_wstream = false;
+  p.est_us = -1.0;
+  // 1. the streaming family: forced (engine=wstream / engine=stream), or priced against the block GEMM under the auto rule
+  const int batch_chunk = images_per_launch(p, pixels);
+  FamilyChoice family;
+  if (o.engine_pref == kEngineWstream) family = plan_forced_wstream(p, batch_chunk);
+  else if (o.engine_pref == kEngineStream || auto_rule(o)) family = price_stream_family(p, o, pixels, batch_chunk);
+  std::string err;
+  if (family.take == Family::kStream || family.take == Family::kWstream) {
+    err = commit_stream_family(p, family, batch_chunk);
+  } else if (o.engine_pref == kEngineStream || o.engine_pref == kEngineWstream) {
+    err = family.refusal;
+  } else if (o.engine_pref >= kEngineMfma ||
+             (auto_rule(o) && mfma_supported(p) && (family.take == Family::kBlockGemm || pixels * d.channels_out >= (1 << 16)))) {
+    err = select_block_gemm(p, o, pixels);      // 2. the matrix cores' block GEMM, its direct variant, the pointwise kernel
+  } else {
+    err = select_valu(p, o, pixels);            // 3. the xor-popcount engine
+  }
+  // int8 plans of the matrix-core kernels: the epilogue's constants follow the kernel that was selected (its arithmetic decides what
+  // can be proven); cheap (a bisection per channel), so simply redone at every selection
+  if (err.empty() && d.dst_type == LCE_HIP_I8 && p.use_mfma && p.have_weights && !p.wq.empty()) prepare_int8_epilogue(p);
+  return err;
 }
 
 int max_batch_per_launch(const HostPlan& p) {
@@ -1159,16 +1164,10 @@ int max_batch_per_launch(const HostPlan& p) {
     // the FP4 workspace is 4x the bitpacked input (plus the halo) and is indexed in
     // 16-byte chunks by a 32-bit counter
     const int cpad = ceil_div(p.d.channels_in, 64) * 64;
-    const int64_t hp = std::max<int64_t>(p.pad_h + p.d.in_height,
-                                         (int64_t)(p.out_h - 1) * p.d.stride_height + (p.d.filter_height - 1) * p.d.dilation_height + 1);
-    const int64_t wp = std::max<int64_t>(p.pad_w + p.d.in_width,
-                                         (int64_t)(p.out_w - 1) * p.d.stride_width + (p.d.filter_width - 1) * p.d.dilation_width + 1);
-    b = std::min<int64_t>(b, (int64_t)(((1ll << 31) - 1) / (hp * wp * (cpad / 2))));
+    b = std::min<int64_t>(b, (int64_t)(((1ll << 31) - 1) / (padded_height(p) * padded_width(p) * (cpad / 2))));
     // the pointwise and the streaming kernel address a whole launch's output through ONE buffer resource with 32-bit
     // byte offsets (an out-of-range marker is offset 2^31): a launch's output stays below 2 GiB
-    const int64_t out_row = p.d.dst_type == LCE_HIP_BITPACKED ? (int64_t)p.wout * 4
-                                                               : (int64_t)p.d.channels_out * (p.d.dst_type == LCE_HIP_I8 ? 1 : 4);
-    b = std::min<int64_t>(b, ((1ll << 31) - 1) / std::max<int64_t>(1, per_image_pixels * out_row));
+    b = std::min<int64_t>(b, ((1ll << 31) - 1) / std::max<int64_t>(1, out_bytes_of(p, 1)));
   }
   b = std::max<int64_t>(1, std::min<int64_t>(b, p.d.batch));
   return (int)b;

@@ -230,9 +230,17 @@ size_t mfma_workspace_bytes(const HostPlan& p, int batch_chunk);
 ConvArgs make_conv_args(const HostPlan& p, int batch_chunk);
 
 // Streaming kernel: can it run this convolution at all; segment size, grid, ring and production schedule for
-// launches of `batch_chunk` images (fills the st_* fields; "" or why not); its launch constants.
+// launches of `batch_chunk` images run as `pick` says (fills the st_* fields; "" or why not); its launch constants.
 bool stream_supported(const HostPlan& p);
-std::string plan_stream(HostPlan& p, int batch_chunk);
+// One way to run the streaming kernel on a launch: what plan_stream plans, and what the selection prices and compares.  A value of its
+// own -- the options stream_rows / stream_interleave / stream_blocks_per_cu say which picks the selection may try, they are not the pick.
+struct StreamPick {
+  int rows = 0;          // output rows per segment (0: the planner's own segments)
+  int interleave = 0;    // 1: a block's segments are gx apart (interleaved runs), 0: consecutive
+  int occ = 1;           // blocks per CU the launch is planned for
+  double us = 0.0;       // the estimate of a launch, once priced (-1: cannot run, or the same launch as another pick)
+};
+std::string plan_stream(HostPlan& p, int batch_chunk, const StreamPick& pick);
 StreamArgs make_stream_args(const HostPlan& p, int batch_chunk);
 // Weight-streaming kernel: can it run this convolution; groups / parts / LDS images for launches of `batch_chunk` images (fills
 // the ws_* fields and st_tabs; "" or why not); its launch constants.

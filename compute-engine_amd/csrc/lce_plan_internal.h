@@ -22,6 +22,31 @@ inline int64_t out_bytes_of(const HostPlan& p, int batch_chunk) {
   return (int64_t)batch_chunk * p.out_h * p.out_w * stream_row_bytes(p);
 }
 
+// "f32" / "i8" / "bitpacked": the output type as the kernel names spell it
+inline const char* dst_name(const lce_hip_bconv2d_desc& d) {
+  return d.dst_type == LCE_HIP_F32 ? "f32" : d.dst_type == LCE_HIP_I8 ? "i8" : "bitpacked";
+}
+
+// Rows / columns of the padded image the matrix-core kernels read: the padding in front plus the input, or as far as the last output's
+// taps reach (the streaming kernels run dilation 1 only -- stream_supported -- where the reach is (out - 1) * stride + filter)
+inline int64_t padded_extent(int pad, int in, int out, int stride, int filter, int dilation) {
+  return std::max<int64_t>(pad + in, (int64_t)(out - 1) * stride + (filter - 1) * dilation + 1);
+}
+inline int64_t padded_height(const HostPlan& p) {
+  return padded_extent(p.pad_h, p.d.in_height, p.out_h, p.d.stride_height, p.d.filter_height, p.d.dilation_height);
+}
+inline int64_t padded_width(const HostPlan& p) {
+  return padded_extent(p.pad_w, p.d.in_width, p.out_w, p.d.stride_width, p.d.filter_width, p.d.dilation_width);
+}
+
+// images of a launch of `pixels` output pixels
+inline int images_per_launch(const HostPlan& p, int64_t pixels) {
+  return (int)std::max<int64_t>(1, pixels / std::max<int64_t>(1, (int64_t)p.out_h * p.out_w));
+}
+
+// nothing is forced: the planner's own rule picks engine, kernel and tile
+inline bool auto_rule(const PlanOptions& o) { return o.engine_pref == kEngineAuto && o.kernel_pref == kKernelAuto && o.tile_pref.tm == 0; }
+
 // lce_plan.cpp
 int group_chunks(const lce_hip_bconv2d_desc& d);
 MfmaCfg choose_mfma_cfg(const HostPlan& p, int64_t pixels);

@@ -94,15 +94,15 @@ static bool simulate_stream(const HostPlan& p, int rs, int spb, int pph_log, boo
   return true;
 }
 
-static bool plan_stream_geometry(HostPlan& p, int batch_chunk, int wso, std::string* why);
+static bool plan_stream_geometry(HostPlan& p, int batch_chunk, const StreamPick& pick, int wso, std::string* why);
 
-std::string plan_stream(HostPlan& p, int batch_chunk) {
+std::string plan_stream(HostPlan& p, int batch_chunk, const StreamPick& pick) {
   const lce_hip_bconv2d_desc& d = p.d;
   if (!stream_supported(p))
     return "bconv2d: the streaming kernel runs ungrouped 3x3 convolutions without dilation, with at most 512 input "
            "channels (on its 64-, 128-, 256- or 512-channel instance) and whole 16-byte groups of output channels (float: a multiple of 4, "
            "int8: of 16), and not the SAME-zero correction semantics";
-  if (p.stream_occ_pref == 2 && stream_blocks_per_cu_max(p) < 2)
+  if (pick.occ == 2 && stream_blocks_per_cu_max(p) < 2)
     return "bconv2d: stream_blocks_per_cu=2: only the bitpacked-output instance of the 64-input-channel bank is compiled for two blocks per CU";
   const uint32_t row_bytes = stream_row_bytes(p);
   if ((int64_t)batch_chunk * p.out_h * p.out_w * row_bytes >= (1ll << 31))
@@ -124,15 +124,15 @@ std::string plan_stream(HostPlan& p, int batch_chunk) {
       widths.push_back(32);
     }
   }
-  std::string why = p.stream_occ_pref == 2 ? "bconv2d: stream_blocks_per_cu=2: two blocks' row rings do not fit a CU's LDS for this layer"
+  std::string why = pick.occ == 2 ? "bconv2d: stream_blocks_per_cu=2: two blocks' row rings do not fit a CU's LDS for this layer"
                                            : "bconv2d: the streaming kernel's row ring does not fit LDS for this layer";
   for (int wso : widths)
-    if (plan_stream_geometry(p, batch_chunk, wso, &why)) return "";
+    if (plan_stream_geometry(p, batch_chunk, pick, wso, &why)) return "";
   return why;
 }
 
 // One attempt: segments of whole rows (wso == 0) or of column strips `wso` output columns wide.
-static bool plan_stream_geometry(HostPlan& p, int batch_chunk, int wso, std::string* why) {
+static bool plan_stream_geometry(HostPlan& p, int batch_chunk, const StreamPick& pick, int wso, std::string* why) {
   const lce_hip_bconv2d_desc& d = p.d;
   const uint32_t row_bytes = stream_row_bytes(p);
   const bool strips = wso > 0;
@@ -148,8 +148,7 @@ static bool plan_stream_geometry(HostPlan& p, int batch_chunk, int wso, std::str
   const bool ksplit = stream_ksplit(p);     // 512 input channels: waves = 2 slices x 2 K-halves, one pixel block per step
   if (ksplit) pph_log = 0;
   const int nslb = ksplit ? 2 : 4 >> pph_log, ny = ceil_div(nsl, nslb), pph = 1 << pph_log;
-  const int wp = strips ? in_w_seg
-                        : (int)std::max<int64_t>(p.pad_w + d.in_width, (int64_t)(p.out_w - 1) * d.stride_width + d.filter_width);
+  const int wp = strips ? in_w_seg : (int)padded_width(p);
   const int kch = stream_chunks(d), ps = kch * 32 + 16;
   // Ring row pitch.  An A-fragment read is one 16-byte piece per lane, lane = pixel; the LDS serves 16 lanes per pass without
   // conflicts when their 16-byte units differ mod 16.  Along a row consecutive pixels are ps / 16 (odd) units apart: fine.
@@ -168,7 +167,7 @@ static bool plan_stream_geometry(HostPlan& p, int batch_chunk, int wso, std::str
 #endif
   const int pitch = wp * ps + skew16 * 16;
   // blocks per CU: two where the instance is compiled for it, the plan asks for it and (below) both blocks' LDS fit
-  const int occ = !strips && p.stream_occ_pref == 2 && stream_blocks_per_cu_max(p) >= 2 ? 2 : 1;
+  const int occ = !strips && pick.occ == 2 && stream_blocks_per_cu_max(p) >= 2 ? 2 : 1;
   const int cus = std::max(1, p.num_cus * occ / ny);
   // segment size (a divisor of the output height: every segment is whole): the fewest block steps on the busiest
   // block (ties: the longer segment, whose halo is re-expanded less)
@@ -183,7 +182,7 @@ static bool plan_stream_geometry(HostPlan& p, int batch_chunk, int wso, std::str
   std::vector<Cand> cands;
   for (int rs = p.out_h; rs >= 1; --rs) {
     if (p.out_h % rs) continue;
-    if (p.stream_rows_pref > 0 && rs != p.stream_rows_pref) continue;
+    if (pick.rows > 0 && rs != pick.rows) continue;
     const int64_t spb = run_length(p.out_h / rs), s = (int64_t)batch_chunk * nstrip * (p.out_h / rs);
     // (the K-split instances are the ones built for it)
     const bool flat_c = !strips && rs == p.out_h && spb > 1 && (rs * p.out_w) % 32 != 0 && !p.stream_noflat && ksplit;
@@ -221,7 +220,7 @@ static bool plan_stream_geometry(HostPlan& p, int batch_chunk, int wso, std::str
     // of gx streams a whole run apart.  Same segments, same ring schedule, same tables but for the output offsets.  (Flat runs
     // cut pixel blocks across consecutive images: they stay consecutive.)
     const int64_t gx_plan = ceil_div((int)s, (int)spb);
-    const int64_t gstr = (p.stream_interleave_pref > 0 && !flat && spb > 1) ? gx_plan : 1;
+    const int64_t gstr = (pick.interleave > 0 && !flat && spb > 1) ? gx_plan : 1;
     p.st_gstr = (int)gstr;
     if (nq * 1024 > (64ll << 20)) continue;               // the context table: 1 KiB per pixel block
     p.st_rs = rs; p.st_spi = spi; p.st_srs = (rs - 1) * d.stride_height + d.filter_height;

@@ -149,6 +149,20 @@ std::string apply_options(HostPlan& h, const char* options) {
   return "";
 }
 
+// hashes of tools/plan_dump.py's lines (hostsim_plan_step)
+uint64_t fnv1a(const void* data, size_t bytes, uint64_t h = 0xcbf29ce484222325ull) {
+  for (size_t i = 0; i < bytes; ++i) h = (h ^ ((const uint8_t*)data)[i]) * 0x100000001b3ull;
+  return h;
+}
+// the launch constants as the kernel receives them; copied into zeroed storage so that padding bytes cannot vary
+template <typename T>
+uint64_t args_hash(const T& args, uint64_t h) {
+  alignas(T) unsigned char raw[sizeof(T)];
+  memset(raw, 0, sizeof raw);
+  *reinterpret_cast<T*>(raw) = args;
+  return fnv1a(raw, sizeof raw, h);
+}
+
 }  // namespace
 
 extern "C" {
@@ -382,6 +396,88 @@ double hostsim_plan_estimate(const lce_hip_bconv2d_desc* desc, const char* optio
     name_out[name_len - 1] = 0;
   }
   return h.est_us;
+}
+
+// ---- the planner's whole answer as text, for tools/plan_dump.py: one plan, re-selected step by step, every field on one line ----
+// filter == null: a plan without weights (as Bconv2dPlan(...).kernel_name() before set_weights)
+void* hostsim_plan_new(const lce_hip_bconv2d_desc* desc, const int32_t* filter, const float* post_mul, const float* post_bias,
+                       const int32_t* thresholds) {
+  HostPlan* h = new HostPlan;
+  h->d = *desc;
+  const std::string err = validate_and_infer(*h);
+  if (!err.empty()) { g_err = err; delete h; return nullptr; }
+  if (filter) fold_parameters(*h, filter, post_mul, post_bias, thresholds);
+  return h;
+}
+void hostsim_plan_free(void* plan) { delete (HostPlan*)plan; }
+
+// Applies `options` ("key=value;...") as lce_hip_bconv2d_plan_set_option does -- what an option makes stale is dropped from the plan --,
+// selects the kernel for launches of min(max_batch, the planner's launch size) images (max_batch 0: the planner's) and returns the plan as
+// one line of text: error, kernel name, estimate, every scalar field, length and hash of every table, hash of the selected engine's
+// launch constants.  The pointer is valid until the next call.
+const char* hostsim_plan_step(void* plan, const char* options, int max_batch) {
+  static std::string line;
+  HostPlan& h = *(HostPlan*)plan;
+  std::string err;
+  const std::string s = options ? options : "";
+  for (size_t pos = 0; pos < s.size() && err.empty();) {
+    const size_t end = std::min(s.find(';', pos), s.size());
+    const std::string item = s.substr(pos, end - pos);
+    pos = end + 1;
+    const size_t eq = item.find('=');
+    if (eq == std::string::npos) { err = "hostsim: option '" + item + "' is not key=value"; break; }
+    unsigned stale = 0;
+    err = set_plan_option(h, item.substr(0, eq).c_str(), item.c_str() + eq + 1, &stale);
+    if (stale & kStalePacked) h.packed.clear();
+    if (stale & kStaleWeightImage) h.wq.clear();
+  }
+  int chunk = max_batch_per_launch(h);
+  if (max_batch > 0) chunk = std::min(chunk, max_batch);
+  if (err.empty()) err = select_kernel(h, (int64_t)chunk * h.out_h * h.out_w);
+  char buf[128];
+  line = "err=\"" + err + "\" kernel=\"" + h.kernel_name + "\"";
+  snprintf(buf, sizeof buf, " est_us=%a chunk=%d", h.est_us, chunk);
+  line += buf;
+  auto put = [&](const char* name, long long v) { snprintf(buf, sizeof buf, " %s=%lld", name, v); line += buf; };
+#define F(field) put(#field, (long long)h.field)
+  F(engine_pref); F(kernel_pref); F(tile_pref.tm); F(tile_pref.tn); F(tile2d_pref); F(phase); F(epilogue_pref); F(pw_tiles_pref);
+  F(pw_nj_pref); F(int8_exact_pref); F(stream_rows_pref); F(stream_noflat); F(stream_phases_pref); F(stream_strip_pref);
+  F(stream_interleave_pref); F(stream_occ_pref); F(ws_blocks_pref); F(ws_images_pref); F(cus_forced);
+  F(out_h); F(out_w); F(pad_h); F(pad_w); F(cw); F(cwg); F(npg); F(wout); F(backtransform_add); F(zero_pad_mode);
+  F(have_weights); F(want_sign); F(clamp_min); F(clamp_max);
+  F(use_tiled); F(tile.tm); F(tile.tn); F(ch); F(nt);
+  F(use_direct); F(tpi); F(halo_rows); F(ps); F(halo_bytes); F(ipt); F(tile_tx); F(halo_w); F(use_mfma); F(use_pointwise);
+  F(pw_nc); F(pw_nj); F(mfma.wgm); F(mfma.wgn); F(mfma.wm); F(mfma.wn); F(cpad); F(hp); F(wp); F(npad); F(kch);
+  F(int8_floor_ok); F(int8_bias_adjusted); F(wq_layout);
+  F(use_stream); F(num_cus); F(st_rs); F(st_spi); F(st_srs); F(st_pbs); F(st_pph_log); F(st_ny); F(st_qg); F(st_ipr); F(st_pitch);
+  F(st_nstrip); F(st_rseg); F(st_wso); F(st_gstr); F(st_occ); F(st_flat); F(st_nq); F(st_spb); F(st_gx); F(st_rows);
+  F(st_ring_bytes); F(st_batch); F(st_tab_lim); F(st_tab_ctx); F(st_tab_sgn); F(st_tab_seg);
+  F(use_wstream); F(ws_ipb); F(ws_parts); F(ws_nq); F(ws_npxg); F(ws_nb); F(ws_ny); F(ws_hp); F(ws_wp); F(ws_pitch);
+  F(ws_img_pitch); F(ws_qg); F(ws_lds_images); F(ws_occupancy); F(ws_tab_part); F(ws_tab_ctx); F(ws_cost);
+#undef F
+  uint32_t bits;
+  memcpy(&bits, &h.bit_thr, 4);
+  put("bit_thr_bits", bits);
+  auto table = [&](const char* name, const void* data, size_t count, size_t elem) {
+    snprintf(buf, sizeof buf, " %s=%zu:%016llx", name, count, (unsigned long long)fnv1a(data, count * elem));
+    line += buf;
+  };
+#define V(field) table(#field, h.field.data(), h.field.size(), sizeof(h.field[0]))
+  V(wq); V(st_tabs); V(mul_q); V(bias_q); V(thr_q); V(packed); V(mul_p); V(bias_p); V(thr_p); V(oob_corr); V(zero_pad_cache);
+#undef V
+  if (err.empty()) {
+    // the selected engine's launch constants, as hostsim_bconv2d / the C ABI build them for a launch of `chunk` images
+    uint64_t a = args_hash(make_conv_args(h, chunk), 0xcbf29ce484222325ull);
+    if (h.use_mfma && h.use_wstream) a = args_hash(make_ws_args(h, chunk), a);
+    else if (h.use_mfma && h.use_stream) a = args_hash(make_stream_args(h, chunk), a);
+    else if (h.use_mfma) {
+      if (h.use_pointwise) a = args_hash(make_pw_args(h, chunk), a);
+      a = args_hash(make_mfma_args(h, chunk), a);       // (the pointwise kernel's fallback for unaligned outputs is the block GEMM)
+    }
+    snprintf(buf, sizeof buf, " args=%016llx", (unsigned long long)a);
+    line += buf;
+  }
+  return line.c_str();
 }
 
 }  // extern "C"
