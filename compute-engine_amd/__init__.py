@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "lce_hip_graph_begin_capture", "lce_hip_graph_end_capture", "lce_hip_graph_launch", "lce_hip_graph_destroy",
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
-    "lce_hip_concat",
+    "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -51,6 +51,8 @@ EW_ADD, EW_MUL = 0, 1                                   # lce_hip_ew_op
 EW_SCALAR, EW_PER_CHANNEL, EW_TENSOR = 0, 1, 2          # lce_hip_ew_operand
 EW_MAX_STEPS = 8
 CONCAT_MAX_INPUTS = 8                                   # LCE_HIP_CONCAT_MAX_INPUTS
+POOL_MAX, POOL_AVERAGE = 0, 1                           # lce_hip_pool_op
+POOL_MAX_TAPS = 65536                                   # LCE_HIP_POOL_MAX_TAPS
 ADD_INT8_LITERAL, ADD_INT8_SPLIT, ADD_INT8_SHIFT = 0, 1, 2   # lce_hip_add_int8_variant_id
 
 
@@ -86,6 +88,13 @@ class AddInt8Params(C.Structure):
     """``lce_hip_add_int8_params``."""
     _fields_ = [(n, C.c_int32) for n in ("left_shift", "in1_multiplier", "in1_shift", "in2_multiplier", "in2_shift",
                                          "out_multiplier", "out_shift", "act_min", "act_max")]
+
+
+class Pool2dDesc(C.Structure):
+    """``lce_hip_pool2d_desc``."""
+    _fields_ = [(n, C.c_int32) for n in ("op", "type", "batch", "in_height", "in_width", "channels", "filter_height",
+                                         "filter_width", "stride_height", "stride_width", "padding", "activation")] + [
+        ("scale", C.c_float), ("zero_point", C.c_int32)]
 
 
 _lib = None
@@ -136,6 +145,8 @@ def lib() -> C.CDLL:
                                               C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_concat.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_size_t, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_pool2d.argtypes = [C.POINTER(Pool2dDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_pool2d_check.argtypes = [C.POINTER(Pool2dDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -393,7 +404,7 @@ def unpack(words, channels: int, dtype, scale: float = 1.0, zero_point: int = 0,
     return out
 
 
-# ---- what the fused passes between binary layers share (elementwise, add_int8, concat) ----
+# ---- what the fused passes between binary layers share (elementwise, add_int8, concat, pool2d) ----
 def _dtype_name(a):
     return str(a.dtype).replace("torch.", "")
 
@@ -632,6 +643,77 @@ def concat(tensors, out=None, out_bits=False, zero_point: int = 0, stream: int |
         check(lib().lce_hip_concat(kind, ptrs, ch, len(ins), rows, int(zero_point), _dev_ptr(out_d), _dev_ptr(bits_d),
                                    C.c_void_p(_stream_or_current(stream, dev))))
     return _results(host, out_d, bits_d, out)
+
+
+def _pair(who, name, v):
+    """An (height, width) argument: one int for both, or two."""
+    hw = (v, v) if isinstance(v, (int, np.integer)) else tuple(v) if isinstance(v, (list, tuple)) else None
+    if hw is None or len(hw) != 2 or any(not isinstance(a, (int, np.integer)) or a <= 0 for a in hw):
+        raise ValueError("%s: %s must be a positive int or a pair of them, got %r" % (who, name, v))
+    return int(hw[0]), int(hw[1])
+
+
+def pool2d_output_hw(in_hw, filter, stride, padding):
+    """Output (height, width) of a pool: SAME ceil(in / stride), VALID ceil((in - filter + 1) / stride) (host only)."""
+    return tuple((i + s - 1) // s if padding == PADDING_SAME else (i + s - f) // s for i, f, s in zip(in_hw, filter, stride))
+
+
+def _pool2d_check(x, op, filter, stride, padding, activation, out, out_bits, scale, zero_point):
+    """Argument checks of ``pool2d`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (Pool2dDesc, output shape)."""
+    ops = {POOL_MAX: POOL_MAX, POOL_AVERAGE: POOL_AVERAGE, "max": POOL_MAX, "average": POOL_AVERAGE}
+    if op not in ops:
+        raise ValueError("pool2d: unknown op %r" % (op,))
+    name = _dtype_name(x)
+    if name not in ("float32", "int8") or len(x.shape) != 4 or min(x.shape) < 1:
+        raise ValueError("pool2d: x must be a non-empty float32 or int8 NHWC tensor, got %s %r" % (x.dtype, tuple(x.shape)))
+    fh, fw = _pair("pool2d", "filter", filter)
+    sh, sw = _pair("pool2d", "stride", stride)
+    if fh * fw > POOL_MAX_TAPS:
+        raise ValueError("pool2d: a filter of %d x %d has more than %d taps" % (fh, fw, POOL_MAX_TAPS))
+    if padding not in (PADDING_SAME, PADDING_VALID):
+        raise ValueError("pool2d: padding must be PADDING_SAME or PADDING_VALID, got %r" % (padding,))
+    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
+        raise ValueError("pool2d: unknown activation %r" % (activation,))
+    if name == "int8":
+        if scale is None or not (np.isfinite(float(scale)) and float(scale) > 0):
+            raise ValueError("pool2d: an int8 tensor needs a finite positive scale, got %r" % (scale,))
+        if int(zero_point) != zero_point or not -128 <= int(zero_point) <= 127:
+            raise ValueError("pool2d: zero point must be an integer in [-128, 127], got %r" % (zero_point,))
+    elif zero_point != 0:
+        raise ValueError("pool2d: a float32 tensor has no zero point, got %r" % (zero_point,))
+    b, h, w, c = (int(v) for v in x.shape)
+    oh, ow = pool2d_output_hw((h, w), (fh, fw), (sh, sw), padding)
+    if oh < 1 or ow < 1:
+        raise ValueError("pool2d: empty output (a VALID filter of %d x %d on an image of %d x %d)" % (fh, fw, h, w))
+    shape = (b, oh, ow, c)
+    _check_outputs("pool2d", None if out is True else out, None if out_bits is False else out_bits, name, shape)
+    desc = Pool2dDesc(ops[op], F32 if name == "float32" else I8, b, h, w, c, fh, fw, sh, sw, int(padding), int(activation),
+                      float(scale) if name == "int8" else 1.0, int(zero_point))
+    return desc, shape
+
+
+def pool2d(x, op, filter, stride, padding, activation=ACT_NONE, out=True, out_bits=False, scale=None, zero_point: int = 0,
+           stream: int | None = None):
+    """TFLite's builtin MAX_POOL_2D / AVERAGE_POOL_2D between binary layers and the LceQuantize of the pooled tensor, in one
+    pass (``lce_hip_pool2d``).  ``x``: float32 or int8 NHWC on the device (or NumPy: copied to cuda:0 and back).  ``op``:
+    ``POOL_MAX`` / ``POOL_AVERAGE`` (or "max" / "average").  ``filter``, ``stride``: an int or (height, width).  ``padding``:
+    ``PADDING_SAME`` / ``PADDING_VALID`` (taps in the padding are excluded).  ``activation``: ``ACT_*``.  int8: ``scale`` and
+    ``zero_point`` of the tensor (the output keeps them).  ``out``: True for a new pooled tensor, a tensor to fill (it must not
+    overlap ``x``), False for none.  ``out_bits``: True for new int32 [B, OH, OW, ceil(C/32)] bits (float32: value < 0; int8:
+    value < ``zero_point``), a tensor to fill, False for none.  Returns ``(pooled or None, bits or None)``."""
+    desc, shape = _pool2d_check(x, op, filter, stride, padding, activation, out, out_bits, scale, zero_point)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "pool2d", "x's")
+    xd = on_dev(x)
+    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if (out is True or out is None) else on_dev(out)
+    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_pool2d(C.byref(desc), _dev_ptr(xd), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                   C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
 
 
 def bmaxpool(x, filter_height, filter_width, stride_height, stride_width, padding, stream: int | None = None, out=None):

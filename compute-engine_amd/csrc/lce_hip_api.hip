@@ -20,6 +20,7 @@
 #include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip)
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
 #include "lce_kernels_concat.h"      // (lce_tu_concat.hip)
+#include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -39,6 +40,7 @@
 #include "lce_tu_eltwise.hip"
 #include "lce_tu_eltwise_i8.hip"
 #include "lce_tu_concat.hip"
+#include "lce_tu_pool.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -553,6 +555,28 @@ struct PreparedAddI8 {
   int variant = lce::kAddI8Literal;             // the chooser's pick
 };
 
+// CalculateActivationRangeQuantized (kernel_util.cc) for an int8 tensor of (scale, zero_point):
+// Q(f) = zero_point + (int32)round(f / scale), the division in float.  Shared by the int8 ADD and the int8 pools.
+void quantized_activation_range(int32_t activation, float scale, int32_t zero_point, int32_t* act_min, int32_t* act_max) {
+  auto Q = [&](float f) -> int64_t {
+    double r = (double)std::round(f / scale);
+    r = std::min(std::max(r, -2147483000.0), 2147483000.0);        // (the cast of a larger value is undefined)
+    return (int64_t)zero_point + (int64_t)r;
+  };
+  int64_t lo = -128, hi = 127;
+  if (activation == LCE_HIP_ACT_RELU) {
+    lo = std::max<int64_t>(lo, Q(0.0f));
+  } else if (activation == LCE_HIP_ACT_RELU6) {
+    lo = std::max<int64_t>(lo, Q(0.0f));
+    hi = std::min<int64_t>(hi, Q(6.0f));
+  } else if (activation == LCE_HIP_ACT_RELU_N1_TO_1) {
+    lo = std::max<int64_t>(lo, Q(-1.0f));
+    hi = std::min<int64_t>(hi, Q(1.0f));
+  }
+  *act_min = (int32_t)lo;
+  *act_max = (int32_t)hi;
+}
+
 lce_hip_status add_int8_params(const lce_hip_add_int8_desc* d, lce_hip_add_int8_params* p, const char* who) {
   if (!d || !p) return fail(LCE_HIP_ERR_INVALID, "%s: null argument", who);
   const float scales[3] = {d->in1_scale, d->in2_scale, d->out_scale};
@@ -577,24 +601,7 @@ lce_hip_status add_int8_params(const lce_hip_add_int8_desc* d, lce_hip_add_int8_
   quantize_multiplier(real[0], &p->in1_multiplier, &p->in1_shift);
   quantize_multiplier(real[1], &p->in2_multiplier, &p->in2_shift);
   quantize_multiplier(real[2], &p->out_multiplier, &p->out_shift);
-  // CalculateActivationRangeQuantized (kernel_util.cc) for int8: Q(f) = zo + (int32)round(f / so), the division in float
-  auto Q = [&](float f) -> int64_t {
-    double r = (double)std::round(f / d->out_scale);
-    r = std::min(std::max(r, -2147483000.0), 2147483000.0);        // (the cast of a larger value is undefined)
-    return (int64_t)d->out_zero_point + (int64_t)r;
-  };
-  int64_t lo = -128, hi = 127;
-  if (d->activation == LCE_HIP_ACT_RELU) {
-    lo = std::max<int64_t>(lo, Q(0.0f));
-  } else if (d->activation == LCE_HIP_ACT_RELU6) {
-    lo = std::max<int64_t>(lo, Q(0.0f));
-    hi = std::min<int64_t>(hi, Q(6.0f));
-  } else if (d->activation == LCE_HIP_ACT_RELU_N1_TO_1) {
-    lo = std::max<int64_t>(lo, Q(-1.0f));
-    hi = std::min<int64_t>(hi, Q(1.0f));
-  }
-  p->act_min = (int32_t)lo;
-  p->act_max = (int32_t)hi;
+  quantized_activation_range(d->activation, d->out_scale, d->out_zero_point, &p->act_min, &p->act_max);
   return LCE_HIP_OK;
 }
 
@@ -807,6 +814,110 @@ lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev,
   const int kind = type == LCE_HIP_F32 ? lce::kConcatF32 : type == LCE_HIP_I8 ? lce::kConcatI8 : lce::kConcatWords;
   const int e = lce::launch_concat(a, kind, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_concat: launch failed: %s", hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// 2-D pooling (lce_kernels_pool.h)
+// ------------------------------------------------------------------------------------
+static_assert(LCE_HIP_POOL_MAX_TAPS == lce::kPoolMaxTaps, "the header's bound is the kernels'");
+lce_hip_status lce_hip_pool2d_check(const lce_hip_pool2d_desc* d, int32_t* out_height, int32_t* out_width) {
+  const char* who = "lce_hip_pool2d";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->op != LCE_HIP_POOL_MAX && d->op != LCE_HIP_POOL_AVERAGE) return fail(LCE_HIP_ERR_INVALID, "%s: unknown op %d", who, (int)d->op);
+  if (d->type != LCE_HIP_F32 && d->type != LCE_HIP_I8) return fail(LCE_HIP_ERR_INVALID, "%s: type must be float32 or int8, got %d", who, (int)d->type);
+  if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d]", who, (int)d->batch, (int)d->in_height,
+                (int)d->in_width, (int)d->channels);
+  if (d->filter_height <= 0 || d->filter_width <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the filter must be positive, got %d x %d", who, (int)d->filter_height, (int)d->filter_width);
+  if (d->stride_height <= 0 || d->stride_width <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)d->stride_height, (int)d->stride_width);
+  if (d->padding != LCE_HIP_PADDING_SAME && d->padding != LCE_HIP_PADDING_VALID)
+    return fail(LCE_HIP_ERR_INVALID, "%s: padding must be SAME or VALID, got %d", who, (int)d->padding);
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  if (d->type == LCE_HIP_I8) {
+    if (d->zero_point < -128 || d->zero_point > 127)
+      return fail(LCE_HIP_ERR_INVALID, "%s: zero_point must be in [-128, 127], got %d", who, (int)d->zero_point);
+    if (!std::isfinite(d->scale) || !(d->scale > 0.0f))
+      return fail(LCE_HIP_ERR_INVALID, "%s: scale must be finite and positive, got %g", who, (double)d->scale);
+  }
+  // (the kernels' window arithmetic, oy * stride - pad + filter, is 32-bit: with these bounds it stays below 2^31)
+  if (std::max(d->in_height, d->in_width) > (1 << 30) || std::max(d->stride_height, d->stride_width) > (1 << 30))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  // (the int8 AVERAGE divides in float: exact while 128.5 taps < 2^24, lce_kernels_pool.h)
+  if ((int64_t)d->filter_height * d->filter_width > (int64_t)lce::kPoolMaxTaps)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: a filter of %d x %d has more than %d taps", who, (int)d->filter_height, (int)d->filter_width,
+                lce::kPoolMaxTaps);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = lce_hip_bmaxpool_output_shape(d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height,
+                                                      d->stride_width, d->padding, &oh, &ow)) return s;
+  if (oh <= 0 || ow <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: empty output (a VALID filter of %d x %d on an image of %d x %d)", who, (int)d->filter_height,
+                (int)d->filter_width, (int)d->in_height, (int)d->in_width);
+  if ((uint64_t)d->batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_pool2d(const lce_hip_pool2d_desc* d, const void* in_dev, void* out_dev, int32_t* out_bits_dev, void* stream) {
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: null desc");
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: null input");
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: both outputs are null");
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = lce_hip_pool2d_check(d, &oh, &ow)) return s;
+  const uint64_t esz = d->type == LCE_HIP_I8 ? 1 : 4;
+  const uint64_t C = (uint64_t)d->channels, pixels = (uint64_t)d->batch * oh * ow, wpr = (C + 31) / 32;
+  // the outputs must not meet the input (another lane still reads what one lane would overwrite) or each other
+  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uint64_t)d->batch * d->in_height * d->in_width * C * esz;
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? pixels * C * esz : 0);
+  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? pixels * wpr * 4 : 0);
+  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t c0, uintptr_t c1) { return a0 < c1 && c0 < a1; };
+  if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: an output overlaps the input");
+  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: the two outputs overlap");
+  if (b0 % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: out_bits_dev must be 4-byte aligned");
+  if (lce_hip_status s = require_device()) return s;
+  bool vec = (C * esz) % 16 == 0 && i0 % 16 == 0 && o0 % 16 == 0;
+  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
+  lce::PoolArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev;
+  a.out = out_dev;
+  a.bits = (uint32_t*)out_bits_dev;
+  a.H = d->in_height; a.W = d->in_width; a.OH = oh; a.OW = ow;
+  a.fh = d->filter_height; a.fw = d->filter_width; a.sh = d->stride_height; a.sw = d->stride_width;
+  // ComputePaddingHeightWidth: total / 2 in front
+  a.ph = (int32_t)(std::max<int64_t>(0, (int64_t)(oh - 1) * d->stride_height + d->filter_height - d->in_height) / 2);
+  a.pw = (int32_t)(std::max<int64_t>(0, (int64_t)(ow - 1) * d->stride_width + d->filter_width - d->in_width) / 2);
+  a.channels = (uint32_t)C;
+  a.wpr = (uint32_t)wpr;
+  a.per_pixel = (uint32_t)(vec ? C * esz / 16 : (C + 63) / 64);
+  a.stream_loads = d->stride_height >= d->filter_height && d->stride_width >= d->filter_width ? 1u : 0u;
+  a.total = pixels * a.per_pixel;
+  switch (d->activation) {    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
+    case LCE_HIP_ACT_RELU: a.lo = 0.0f; a.hi = FLT_MAX; break;
+    case LCE_HIP_ACT_RELU_N1_TO_1: a.lo = -1.0f; a.hi = 1.0f; break;
+    case LCE_HIP_ACT_RELU6: a.lo = 0.0f; a.hi = 6.0f; break;
+    default: a.lo = -FLT_MAX; a.hi = FLT_MAX;
+  }
+  if (d->type == LCE_HIP_I8) {
+    quantized_activation_range(d->activation, d->scale, d->zero_point, &a.qlo, &a.qhi);
+    a.zero_point = d->zero_point;
+  }
+  a.div_ow = lce::make_fastdiv((uint32_t)ow);
+  a.div_oh = lce::make_fastdiv((uint32_t)oh);
+  if (vec) {
+    const uint64_t stride = (uint64_t)lce::pool_vec_grid(a.total) * 4ull * 64ull;   // chunks per grid step
+    a.step_pixels = (uint32_t)(stride / a.per_pixel);
+    a.step_chunks = (uint32_t)(stride % a.per_pixel);
+    a.div_per_pixel = lce::make_fastdiv(a.per_pixel);
+  }
+  const int e = lce::launch_pool(a, d->type == LCE_HIP_I8 ? lce::kPoolI8 : lce::kPoolF32,
+                                 d->op == LCE_HIP_POOL_AVERAGE ? lce::kPoolAverage : lce::kPoolMax, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_pool2d: launch failed: %s", hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
 
@@ -1187,7 +1298,9 @@ lce_hip_status lce_hip_bconv2d_run_host(lce_hip_bconv2d_plan* plan, const int32_
 // ------------------------------------------------------------------------------------
 static int pool_out(int padding, int in, int filter, int stride) {
   if (stride == 0) return 0;
-  return padding == LCE_HIP_PADDING_SAME ? (in + stride - 1) / stride : (in + stride - filter) / stride;
+  // (in 64 bits: the operands may come straight from an untrusted file, and in + stride may pass 2^31)
+  const int64_t n = padding == LCE_HIP_PADDING_SAME ? ((int64_t)in + stride - 1) / stride : ((int64_t)in + stride - filter) / stride;
+  return (int)std::min<int64_t>(std::max<int64_t>(n, INT32_MIN), INT32_MAX);
 }
 
 lce_hip_status lce_hip_bmaxpool_output_shape(int32_t in_h, int32_t in_w, int32_t fh, int32_t fw, int32_t sh,

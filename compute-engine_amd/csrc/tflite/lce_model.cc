@@ -22,6 +22,7 @@ struct lce_tflite_section {
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
+  uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
@@ -37,7 +38,7 @@ struct lce_tflite_model {
     int32_t conv_quantize = 0;                                          // LceQuantize launches folded into a convolution (run_dual)
     int32_t ew_ops = 0;                                                 // ADD / MUL operators inside the lce_hip_elementwise launches
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
-    Pass ew, add_i8, concat;                                            // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat
+    Pass ew, add_i8, concat, pool;                                      // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat, lce_hip_pool2d
   };
   RunStats last;                                                        // of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
@@ -172,7 +173,55 @@ bool ConcatCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   }
   return sum == out.shape[3];
 }
-enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3 };
+
+// lce_hip_pool2d_desc of a builtin pool at `batch` images, from its options and the FILE's input tensor.
+lce_hip_pool2d_desc PoolDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  lce_hip_pool2d_desc d;
+  memset(&d, 0, sizeof d);
+  d.op = o.builtin_code == lce_tfl::kBuiltinMaxPool2d ? LCE_HIP_POOL_MAX : LCE_HIP_POOL_AVERAGE;
+  d.type = in.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_F32;
+  d.batch = batch; d.in_height = in.shape[1]; d.in_width = in.shape[2]; d.channels = in.shape[3];
+  d.filter_height = o.pool_filter_h; d.filter_width = o.pool_filter_w;
+  d.stride_height = o.pool_stride_h; d.stride_width = o.pool_stride_w;
+  d.padding = o.pool_padding;
+  d.activation = o.activation;
+  d.scale = d.type == LCE_HIP_I8 ? in.scale : 1.0f;
+  d.zero_point = d.type == LCE_HIP_I8 ? (int32_t)in.zero_point : 0;
+  return d;
+}
+
+// The static half of "a builtin 2-D pool that a section may run" (LCE_TFLITE_SECTIONS_EXT_POOL): AVERAGE_POOL_2D or
+// MAX_POOL_2D with one input and one output; a 4-D output with positive extents; a non-constant 4-D input of the output's
+// type and channel count; float32, or int8 with both tensors quantized, zero points that are int8 and the SAME scale and
+// zero point (a requantizing pool is the host's); filter and stride positive, padding SAME or VALID, an activation
+// lce_hip_pool2d knows; the declared output height and width equal to what the padding rule gives for the declared input;
+// and a descriptor lce_hip_pool2d's own check accepts.  The other half -- it becomes ready in an LCE epoch -- is decided by
+// Partition().
+bool PoolCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinAveragePool2d && o.builtin_code != lce_tfl::kBuiltinMaxPool2d) return false;
+  if (o.inputs.size() != 1 || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
+  for (int k = 0; k < 4; ++k)
+    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
+  if (in.type != out.type || in.shape[3] != out.shape[3]) return false;
+  if (out.type == lce_tfl::kTensorInt8) {
+    for (const lce_tfl::Tensor* t : {&in, &out})
+      if (!t->quantized || t->zero_point < -128 || t->zero_point > 127) return false;
+    if (in.scale != out.scale || in.zero_point != out.zero_point) return false;
+  } else if (out.type != lce_tfl::kTensorFloat32) {
+    return false;
+  }
+  if (o.pool_filter_h <= 0 || o.pool_filter_w <= 0 || o.pool_stride_h <= 0 || o.pool_stride_w <= 0) return false;
+  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  const lce_hip_pool2d_desc d = PoolDesc(M, o, in.shape[0]);
+  int32_t oh = 0, ow = 0;
+  return lce_hip_pool2d_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
+}
+enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3, kAbsorbedPool = 4 };
 }  // namespace
 
 // The partition a delegate would get (tensorflow/lite/graph_info.cc, PartitionGraphIntoIndependentNodeSubsets, restated from
@@ -199,6 +248,8 @@ void lce_tflite_model::Partition() {
     if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_INT8_ADD)) candidate[i] = Int8AddCandidate(m, m.operators[i]) ? kAbsorbedInt8Add : 0;
     // LCE_TFLITE_SECTIONS_CONCAT: the same rule for the channel join of a dense block
     if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_CONCAT)) candidate[i] = ConcatCandidate(m, m.operators[i]) ? kAbsorbedConcat : 0;
+    // LCE_TFLITE_SECTIONS_EXT_POOL: the same rule for a 2-D pool
+    if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_POOL)) candidate[i] = PoolCandidate(m, m.operators[i]) ? kAbsorbedPool : 0;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -286,17 +337,18 @@ lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err
   return lce_tflite_model_open_ex(data, size, 0u, err, err_len);
 }
 
-// Both entries funnel into ONE flags word; `allowed` is the entry's own mask.
-static lce_tflite_model* OpenWithFlags(const void* data, size_t size, uint32_t flags, uint32_t allowed, const char* refusal,
-                                       char* err, size_t err_len) {
+// Both entries funnel into ONE pair of flag words; `allowed` is the entry's own mask of the first.
+static lce_tflite_model* OpenWithFlags(const void* data, size_t size, uint32_t flags, uint32_t allowed, uint32_t flags_ext,
+                                       const char* refusal, char* err, size_t err_len) {
   auto* model = new (std::nothrow) lce_tflite_model{};
   std::string e = "out of memory";
   if (refusal) {
     e = refusal;
-  } else if (flags & ~allowed) {
+  } else if ((flags & ~allowed) || (flags_ext & ~(uint32_t)LCE_TFLITE_SECTIONS_EXT_POOL)) {
     e = "unknown flags";
   } else if (model && data && model->m.Parse(data, size, &e)) {
     model->flags = flags;
+    model->flags_ext = flags_ext;
     model->Partition();
     return model;
   }
@@ -307,15 +359,31 @@ static lce_tflite_model* OpenWithFlags(const void* data, size_t size, uint32_t f
 }
 
 lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32_t flags, char* err, size_t err_len) {
-  return OpenWithFlags(data, size, flags, LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD, nullptr, err, err_len);
+  return OpenWithFlags(data, size, flags, LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD, 0u, nullptr, err, err_len);
 }
 
 lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
                                              size_t err_len) {
-  const char* refusal = !options ? "null options"
-                        : options->struct_size != (uint32_t)sizeof(lce_tflite_open_options) ? "options: unknown struct_size" : nullptr;
-  return OpenWithFlags(data, size, refusal ? 0u : options->sections,
-                       LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD | LCE_TFLITE_SECTIONS_CONCAT, refusal, err, err_len);
+  // versioned by size: the first form is 8 bytes (struct_size, sections) and nothing behind them is read
+  constexpr uint32_t kFirstForm = 8;
+  static_assert(sizeof(lce_tflite_open_options) == 24, "the second form of the options struct");
+  const char* refusal = nullptr;
+  uint32_t sections = 0, ext = 0;
+  uint32_t first[2] = {0, 0};                      // (copied: the caller's object may be only 8 bytes long)
+  if (options) memcpy(first, options, sizeof first);
+  if (!options) {
+    refusal = "null options";
+  } else if (first[0] != kFirstForm && first[0] != (uint32_t)sizeof(lce_tflite_open_options)) {
+    refusal = "options: unknown struct_size";
+  } else {
+    sections = first[1];
+    if (first[0] != kFirstForm) {
+      ext = options->sections_ext;
+      if (options->reserved[0] | options->reserved[1] | options->reserved[2]) refusal = "options: reserved fields must be zero";
+    }
+  }
+  return OpenWithFlags(data, size, sections, LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD | LCE_TFLITE_SECTIONS_CONCAT,
+                       ext, refusal, err, err_len);
 }
 
 void lce_tflite_model_close(lce_tflite_model* model) { delete model; }
@@ -378,6 +446,15 @@ lce_hip_status lce_tflite_model_operator_axis(const lce_tflite_model* model, int
   if (!model || !axis || index < 0 || index >= (int32_t)model->m.operators.size())
     return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_axis: bad argument");
   *axis = model->m.operators[index].axis;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_tflite_model_operator_pool2d(const lce_tflite_model* model, int32_t index, int32_t options[5]) {
+  if (!model || !options || index < 0 || index >= (int32_t)model->m.operators.size())
+    return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_pool2d: bad argument");
+  const lce_tfl::Operator& o = model->m.operators[index];
+  options[0] = o.pool_padding; options[1] = o.pool_stride_w; options[2] = o.pool_stride_h;
+  options[3] = o.pool_filter_w; options[4] = o.pool_filter_h;
   return LCE_HIP_OK;
 }
 
@@ -621,7 +698,7 @@ struct Walk {
     return LCE_HIP_OK;
   }
 
-  // Where the result of a fused pass (an ADD / MUL chain, an int8 ADD, a CONCATENATION) goes.
+  // Where the result of a fused pass (an ADD / MUL chain, an int8 ADD, a CONCATENATION, a pool) goes.
   struct Fold {
     int32_t value_t;                     // the tensor the pass produces
     int32_t bits_t = -1;                 // the output of the folded LceQuantize; -1: none
@@ -832,6 +909,40 @@ struct Walk {
     return LCE_HIP_OK;
   }
 
+  // An absorbed AVERAGE_POOL_2D / MAX_POOL_2D (LCE_TFLITE_SECTIONS_EXT_POOL) as ONE lce_hip_pool2d launch.  The first
+  // LceQuantize of the section that reads the pooled tensor becomes the launch's bit output and its own launch disappears; the
+  // pooled tensor itself is written when anything else reads it or the section delivers it.
+  lce_hip_status Pool2d(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    const lce_tfl::Tensor& OT = M.tensors[out_t];
+    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
+    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    auto it = shapes.find(op.inputs[0]);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a pool reads a tensor nothing produced");
+    if (!Agrees(it->second, OT.type, is[1], is[2], is[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a pool input's shape or type does not match the one its producer infers");
+    const lce_hip_pool2d_desc d = PoolDesc(M, op, batch);
+    Shape os;
+    os.dims[0] = batch; os.dims[3] = is[3];
+    os.type = OT.type;
+    if (lce_hip_status s = lce_hip_pool2d_check(&d, &os.dims[1], &os.dims[2])) return s;
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(op.inputs[0], "a pool input", &in)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = lce_hip_pool2d(&d, in, out, (int32_t*)bits, stream)) return s;
+    ++model->last.pool.launches;
+    if (fold.bits_t >= 0) ++model->last.pool.quantize;
+    return LCE_HIP_OK;
+  }
+
   // The four LCE operators.  `in` is the inferred shape of operator `i`'s first input, `in_dev` its device pointer (with `run`).
   lce_hip_status Quantize(int32_t i, const Shape& in, const void* in_dev) {                      // quantization.cc:19-41,76-114
     const lce_tfl::Operator& op = model->m.operators[i];
@@ -960,6 +1071,7 @@ struct Walk {
         case kAbsorbedElementwise: s = ElementwiseChain(i); break;
         case kAbsorbedInt8Add: s = Int8Add(i); break;
         case kAbsorbedConcat: s = Concat(i); break;
+        case kAbsorbedPool: s = Pool2d(i); break;
         default: s = LceOp(i);
       }
       if (s) return s;
@@ -1080,6 +1192,13 @@ void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, i
   std::lock_guard<std::mutex> lock(model->run_mu);
   if (launches) *launches = model->last.concat.launches;
   if (quantize_folded) *quantize_folded = model->last.concat.quantize;
+}
+
+void lce_tflite_model_pool_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (launches) *launches = model->last.pool.launches;
+  if (quantize_folded) *quantize_folded = model->last.pool.quantize;
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

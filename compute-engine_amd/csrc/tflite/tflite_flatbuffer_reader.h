@@ -20,6 +20,9 @@
 //   ActivationFunctionType: 0 NONE, 1 RELU, 2 RELU_N1_TO_1, 3 RELU6, 4 TANH, 5 SIGN_BIT); BuiltinOperator 0 ADD, 18 MUL.
 //   BuiltinOptions union type 10 ConcatenationOptions: 0 axis(int32, default 0), 1 fused_activation_function(int8);
 //   BuiltinOperator 2 CONCATENATION.
+//   BuiltinOptions union type 5 Pool2DOptions: 0 padding(int8, Padding: 0 SAME, 1 VALID)  1 stride_w(int32)  2 stride_h(int32)
+//   3 filter_width(int32)  4 filter_height(int32)  5 fused_activation_function(int8); BuiltinOperator 1 AVERAGE_POOL_2D,
+//   17 MAX_POOL_2D.
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -36,8 +39,8 @@
 namespace lce_tfl {
 
 constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
-constexpr int32_t kBuiltinAdd = 0, kBuiltinConcatenation = 2, kBuiltinMul = 18;
-constexpr int kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
+constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
+constexpr int kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 // TensorType values used by LCE graphs
 constexpr int kTensorFloat32 = 0, kTensorInt32 = 2, kTensorBool = 6, kTensorInt8 = 9;
 
@@ -59,8 +62,10 @@ struct Operator {
   std::vector<int32_t> inputs, outputs;   // tensor indices, -1 = optional input not present
   const uint8_t* custom_options = nullptr;
   size_t custom_options_size = 0;
-  int32_t activation = 0;          // fused_activation_function of AddOptions / MulOptions / ConcatenationOptions; 0 (NONE) when absent
+  int32_t activation = 0;          // fused_activation_function of AddOptions / MulOptions / ConcatenationOptions / Pool2DOptions; 0 (NONE) when absent
   int32_t axis = 0;                // ConcatenationOptions.axis; 0 when absent
+  // Pool2DOptions; all 0 when absent (schema defaults: padding SAME, the strides and the filter 0)
+  int32_t pool_padding = 0, pool_stride_w = 0, pool_stride_h = 0, pool_filter_w = 0, pool_filter_h = 0;
 };
 
 class Model {
@@ -243,6 +248,15 @@ class Model {
         if (!Indirect(opt_pos, &opt) || !Scalar<int32_t>(opt, 0, 0, &axis) || !Scalar<int8_t>(opt, 1, 0, &act))
           return Fail("bad ConcatenationOptions");
         O.axis = axis;
+        O.activation = act;
+      }
+      if (opt_type == kOptionsPool2d && opt_pos != 0) {
+        int8_t pad, act;
+        if (!Indirect(opt_pos, &opt) || !Scalar<int8_t>(opt, 0, 0, &pad) || !Scalar<int32_t>(opt, 1, 0, &O.pool_stride_w) ||
+            !Scalar<int32_t>(opt, 2, 0, &O.pool_stride_h) || !Scalar<int32_t>(opt, 3, 0, &O.pool_filter_w) ||
+            !Scalar<int32_t>(opt, 4, 0, &O.pool_filter_h) || !Scalar<int8_t>(opt, 5, 0, &act))
+          return Fail("bad Pool2DOptions");
+        O.pool_padding = pad;
         O.activation = act;
       }
       for (int32_t x : O.inputs) if (x < -1 || x >= (int32_t)nt) return Fail("Operator input index out of range");

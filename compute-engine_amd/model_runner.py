@@ -22,6 +22,9 @@ sections in the same way (``lce_hip_add_int8``: TFLite's integer arithmetic byte
 With ``concat_sections=True`` (LCE_TFLITE_SECTIONS_CONCAT, ``lce_tflite_model_open_opts``) the channel CONCATENATION of a
 dense network (BinaryDenseNet, MeliusNet) joins them too (``lce_hip_concat``); with ``elementwise_sections`` a float dense
 block is one section.
+With ``pool_sections=True`` (LCE_TFLITE_SECTIONS_EXT_POOL, the 24-byte options of ``lce_tflite_model_open_opts``) the builtin
+MAX_POOL_2D / AVERAGE_POOL_2D between binary layers join them (``lce_hip_pool2d``); with ``elementwise_sections`` the body of a
+BinaryAlexNet is one section.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -41,6 +44,7 @@ FLOAT32, INT32, BOOL, INT8 = 0, 2, 6, 9
 SECTIONS_ELEMENTWISE = 1          # LCE_TFLITE_SECTIONS_ELEMENTWISE
 SECTIONS_INT8_ADD = 2             # LCE_TFLITE_SECTIONS_INT8_ADD
 SECTIONS_CONCAT = 4               # LCE_TFLITE_SECTIONS_CONCAT (lce_tflite_model_open_opts only)
+SECTIONS_EXT_POOL = 1             # LCE_TFLITE_SECTIONS_EXT_POOL (sections_ext of the 24-byte options)
 _NP = {FLOAT32: np.float32, INT32: np.int32, BOOL: np.bool_, INT8: np.int8}
 LCE_OPS = ("LceQuantize", "LceDequantize", "LceBconv2d", "LceBMaxPool2d")
 
@@ -65,6 +69,11 @@ class _SectionInfo(C.Structure):
 class _OpenOptions(C.Structure):
     """``lce_tflite_open_options``."""
     _fields_ = [("struct_size", C.c_uint32), ("sections", C.c_uint32)]
+
+
+class _OpenOptionsExt(C.Structure):
+    """``lce_tflite_open_options``, the 24-byte form (``_OpenOptions`` is the first, 8-byte form)."""
+    _fields_ = [("struct_size", C.c_uint32), ("sections", C.c_uint32), ("sections_ext", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class Section:
@@ -93,7 +102,10 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_open_ex.restype = C.c_void_p
         l.lce_tflite_model_open_ex.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_char_p, C.c_size_t]
         l.lce_tflite_model_open_opts.restype = C.c_void_p
-        l.lce_tflite_model_open_opts.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(_OpenOptions), C.c_char_p, C.c_size_t]
+        l.lce_tflite_model_open_opts.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t]   # either form of the options
+        l.lce_tflite_model_operator_pool2d.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        l.lce_tflite_model_pool_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
+        l.lce_tflite_model_pool_stats.restype = None
         l.lce_tflite_model_operator_axis.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_concat_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
         l.lce_tflite_model_concat_stats.restype = None
@@ -139,10 +151,12 @@ class Tensor:
 
 
 class Operator:
-    def __init__(self, info: _OperatorInfo, activation: int = 0, axis: int = 0):
+    def __init__(self, info: _OperatorInfo, activation: int = 0, axis: int = 0, pool=(0, 0, 0, 0, 0)):
         self.builtin_code = info.builtin_code
-        self.activation = activation          # fused_activation_function of a builtin ADD / MUL / CONCATENATION (0: NONE)
+        self.activation = activation          # fused_activation_function of a builtin ADD / MUL / CONCATENATION / pool (0: NONE)
         self.axis = axis                      # axis of a builtin CONCATENATION as the file says (0 when absent)
+        # Pool2DOptions of a builtin AVERAGE_POOL_2D / MAX_POOL_2D as the file says (all 0 when absent)
+        self.padding, self.stride_w, self.stride_h, self.filter_width, self.filter_height = (int(v) for v in pool)
         self.custom_code = (info.custom_code or b"").decode()
         self.inputs = [info.inputs[i] for i in range(info.num_inputs)]
         self.outputs = [info.outputs[i] for i in range(info.num_outputs)]
@@ -158,11 +172,13 @@ class LceModel:
     """A parsed .tflite flatbuffer (first subgraph)."""
 
     def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
-                 int8_add_sections: bool = False, concat_sections: bool = False):
+                 int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
-        CONCATENATION of a dense block joins them (LCE_TFLITE_SECTIONS_CONCAT, through ``lce_tflite_model_open_opts``)."""
+        CONCATENATION of a dense block joins them (LCE_TFLITE_SECTIONS_CONCAT, through ``lce_tflite_model_open_opts``).  ``pool_sections``: the
+        builtin MAX_POOL_2D / AVERAGE_POOL_2D between binary layers join them (LCE_TFLITE_SECTIONS_EXT_POOL, through the
+        24-byte options of ``lce_tflite_model_open_opts``)."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -170,9 +186,13 @@ class LceModel:
         self.elementwise_sections = bool(elementwise_sections)
         self.int8_add_sections = bool(int8_add_sections)
         self.concat_sections = bool(concat_sections)
+        self.pool_sections = bool(pool_sections)
         err = C.create_string_buffer(256)
         flags = (SECTIONS_ELEMENTWISE if elementwise_sections else 0) | (SECTIONS_INT8_ADD if int8_add_sections else 0)
-        if concat_sections:
+        if pool_sections:
+            opts = _OpenOptionsExt(C.sizeof(_OpenOptionsExt), flags | (SECTIONS_CONCAT if concat_sections else 0), SECTIONS_EXT_POOL)
+            self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
+        elif concat_sections:
             opts = _OpenOptions(C.sizeof(_OpenOptions), flags | SECTIONS_CONCAT)
             self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
         else:
@@ -193,7 +213,9 @@ class LceModel:
             _amd.check(l.lce_tflite_model_operator_activation(self._h, i, C.byref(act)))
             axis = C.c_int32()
             _amd.check(l.lce_tflite_model_operator_axis(self._h, i, C.byref(axis)))
-            self.operators.append(Operator(info, act.value, axis.value))
+            pool = (C.c_int32 * 5)()
+            _amd.check(l.lce_tflite_model_operator_pool2d(self._h, i, pool))
+            self.operators.append(Operator(info, act.value, axis.value, tuple(pool)))
         buf = (C.c_int32 * 64)()
         self.inputs = [buf[i] for i in range(l.lce_tflite_model_inputs(self._h, buf, 64))]
         self.outputs = [buf[i] for i in range(l.lce_tflite_model_outputs(self._h, buf, 64))]
@@ -252,6 +274,12 @@ class LceModel:
         tflite_lib().lce_tflite_model_concat_stats(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    def pool_stats(self):
+        """(lce_hip_pool2d launches, LceQuantize launches they absorbed) of the last run."""
+        a, b = C.c_int32(), C.c_int32()
+        tflite_lib().lce_tflite_model_pool_stats(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -281,16 +309,17 @@ class Interpreter:
 
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
                  use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
-                 concat_sections: bool = False):
-        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+                 concat_sections: bool = False, pool_sections: bool = False):
+        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
-                                    int8_add_sections=int8_add_sections, concat_sections=concat_sections))
+                                    int8_add_sections=int8_add_sections, concat_sections=concat_sections,
+                                    pool_sections=pool_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections:
+        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections or self.model.pool_sections:
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

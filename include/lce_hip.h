@@ -230,6 +230,54 @@ lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev,
                               int32_t* out_bits_dev /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * 2-D pooling between binary layers (TFLite builtin MAX_POOL_2D / AVERAGE_POOL_2D) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* BinaryAlexNet, XNOR-Net and DoReFa-Net pool (3x3, stride 2) behind a float LceBconv2d; a dense network's transition block
+ * and the downsampling shortcuts of Bi-RealNet / BinaryResNetE pool 2x2, stride 2.  lce_hip_pool2d is TFLite's builtin
+ * MAX_POOL_2D / AVERAGE_POOL_2D (tensorflow/lite/kernels/pooling.cc: reference_ops::MaxPool / AveragePool for float32,
+ * reference_integer_ops::MaxPool / AveragePool for int8) over an NHWC tensor [batch, in_height, in_width, channels] in ONE
+ * pass.  The output is [batch, out_height, out_width, channels] with the extents of lce_hip_bmaxpool_output_shape and
+ * TFLite's padding (ComputePaddingHeightWidth: total = max(0, (out - 1) stride + filter - in), total / 2 of it in front).
+ * Taps that fall into the padding are EXCLUDED, not read as zero.  Per output element, over its in-bounds taps in raster
+ * order (filter row, then filter column):
+ *   float MAX    : m = -FLT_MAX; m = (m < x) ? x : m.  A NaN never replaces m; a window of only NaN / -inf gives -FLT_MAX;
+ *                  which of +0.0 / -0.0 a window of both gives is unspecified.
+ *   float AVERAGE: t = 0.0f; t += x, one float32 rounding per add, never reassociated; then t / (float)count, the IEEE
+ *                  (correctly rounded) division by the number of in-bounds taps.  Subnormals are not flushed.
+ *   int8 MAX     : the maximum.
+ *   int8 AVERAGE : a = the int32 sum, n = the number of in-bounds taps; q = a > 0 ? (a + n / 2) / n : (a - n / 2) / n with
+ *                  C's truncating division.
+ *   then v = min(max(v, act_min), act_max): CalculateActivationRange of `activation` for float (NONE: [-FLT_MAX, FLT_MAX],
+ *   so an infinity becomes +-FLT_MAX; a NaN passes), CalculateActivationRangeQuantized at (scale, zero_point) for int8 --
+ *   the computation lce_hip_add_int8_prepare reports as act_min / act_max.  int8 input and output share ONE scale and zero
+ *   point (TFLite's Prepare requires it of both pools).
+ * `out_dev` (nullable) gets the pooled tensor; `out_bits_dev` (nullable) gets its LceQuantize as lce_hip_bitpack(type, out,
+ * batch * out_height * out_width, channels, zero_point, ...) writes it: bit = v < 0 (F32) or v < zero_point (I8), LSB first,
+ * ceil(channels/32) words per pixel, padding bits 0 -- from the values the pass holds, the pooled tensor is not read again.
+ * Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc or input, both outputs NULL, an extent, filter or
+ * stride <= 0, an unknown op, type, padding or activation, for I8 a zero point outside [-128, 127] or a scale that is not
+ * finite and positive, an empty output (VALID with a filter larger than the image), an output that overlaps the input or the
+ * other output; LCE_HIP_ERR_UNSUPPORTED: filter_height x filter_width above LCE_HIP_POOL_MAX_TAPS (the bound under which
+ * the int8 AVERAGE's division, done in float, is proven exact: |a| + n / 2 <= 128.5 n < 2^24), 2^31 or more output pixels,
+ * an image extent or a stride above 2^30 (the window arithmetic is 32-bit).
+ * The byte counts are unbounded (64-bit offsets throughout).  Asynchronous on `stream`, capturable in a HIP graph, allocates
+ * nothing and copies nothing between host and device.  Bitpacked pooling is lce_hip_bmaxpool. */
+#define LCE_HIP_POOL_MAX_TAPS 65536
+typedef enum lce_hip_pool_op { LCE_HIP_POOL_MAX = 0, LCE_HIP_POOL_AVERAGE = 1 } lce_hip_pool_op;
+typedef struct lce_hip_pool2d_desc {
+  int32_t op, type;                 /* lce_hip_pool_op; LCE_HIP_F32 | LCE_HIP_I8 */
+  int32_t batch, in_height, in_width, channels;
+  int32_t filter_height, filter_width, stride_height, stride_width;
+  int32_t padding, activation;      /* lce_hip_padding; NONE | RELU | RELU_N1_TO_1 | RELU6 */
+  float scale; int32_t zero_point;  /* int8: shared by input and output */
+} lce_hip_pool2d_desc;
+lce_hip_status lce_hip_pool2d(const lce_hip_pool2d_desc* desc, const void* in_dev, void* out_dev /* nullable */,
+                              int32_t* out_bits_dev /* nullable */, void* stream);
+/* The descriptor checks of lce_hip_pool2d alone, and the output extents (nullable).  Host only: needs no device. */
+lce_hip_status lce_hip_pool2d_check(const lce_hip_pool2d_desc* desc, int32_t* out_height, int32_t* out_width);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

@@ -64,12 +64,35 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   launch, with the first LceQuantize of the section that reads the joined tensor as the launch's bit output; the joined
  *   tensor itself is written only when something else reads it or the section delivers it.  Together with
  *   LCE_TFLITE_SECTIONS_ELEMENTWISE a float dense block is one section; the float MAX_POOL_2D / CONV_2D of a transition
- *   block still cut.
- * sections == 0..3 gives exactly lce_tflite_model_open_ex with that value; every other bit is refused. */
+ *   block still cut (the pool joins with LCE_TFLITE_SECTIONS_EXT_POOL, below).
+ * sections == 0..3 gives exactly lce_tflite_model_open_ex with that value; every other bit is refused.
+ *
+ * The struct is versioned by its size.  struct_size == 8 is the first form (struct_size and sections alone): it behaves
+ * exactly as it always did and nothing beyond its 8 bytes is read.  struct_size == sizeof(lce_tflite_open_options) == 24
+ * also reads `sections_ext`, the opt-ins that do not fit the refusals the first form promises (a host may rely on
+ * sections == 8 being refused), and `reserved`, which must be zero.  Every other size is refused.
+ *   LCE_TFLITE_SECTIONS_EXT_POOL: the same for the builtin 2-D pooling between binary layers (BinaryAlexNet, XNOR-Net and
+ *   DoReFa-Net pool 3x3 / 2 behind a float LceBconv2d; a dense network's transition block and the downsampling shortcuts
+ *   of Bi-RealNet / BinaryResNetE pool 2x2 / 2).  An AVERAGE_POOL_2D (1) or MAX_POOL_2D (17) joins the LCE epoch in which it
+ *   becomes ready when it has one input and one output, the output is 4-D with positive extents, the input is a
+ *   non-constant 4-D tensor of the output's type and channel count, the type is float32 -- or int8 with both tensors
+ *   carrying quantization parameters, zero points in [-128, 127] and the SAME scale and zero point (a requantizing pool
+ *   stays with the host) --, filter and stride are positive, the padding is SAME or VALID, the fused activation is NONE /
+ *   RELU / RELU_N1_TO_1 / RELU6, the file's declared output height and width are what the padding rule gives for the
+ *   declared input, and lce_hip_pool2d_check accepts the descriptor.  A pool that is ready from the start (a stem pool)
+ *   is the host's.  lce_tflite_model_run_section runs such a pool as one lce_hip_pool2d launch, with the first LceQuantize
+ *   of the section that reads the pooled tensor as the launch's bit output; the pooled tensor itself is written only when
+ *   something else reads it or the section delivers it.  Together with LCE_TFLITE_SECTIONS_ELEMENTWISE the body of a
+ *   BinaryAlexNet is one section.  L2 pooling, a CONV_2D and bitpacked pooling (LceBMaxPool2d, an LCE operator already)
+ *   are not concerned.
+ * The flags of both words combine. */
 enum { LCE_TFLITE_SECTIONS_CONCAT = 4u };
+enum { LCE_TFLITE_SECTIONS_EXT_POOL = 1u };
 typedef struct lce_tflite_open_options {
-  uint32_t struct_size;    /* sizeof(lce_tflite_open_options) */
-  uint32_t sections;       /* LCE_TFLITE_SECTIONS_* */
+  uint32_t struct_size;    /* 8 (the first two fields only) or sizeof(lce_tflite_open_options) == 24 */
+  uint32_t sections;       /* LCE_TFLITE_SECTIONS_*: 0..7, every other bit refused */
+  uint32_t sections_ext;   /* LCE_TFLITE_SECTIONS_EXT_*; every other bit refused */
+  uint32_t reserved[3];    /* must be zero */
 } lce_tflite_open_options;
 lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
                                              size_t err_len);
@@ -112,6 +135,11 @@ lce_hip_status lce_tflite_model_operator_activation(const lce_tflite_model* mode
  * absent and for every other operator.  Its fused activation is reported by the call above. */
 lce_hip_status lce_tflite_model_operator_axis(const lce_tflite_model* model, int32_t index, int32_t* axis);
 
+/* Pool2DOptions of a builtin AVERAGE_POOL_2D / MAX_POOL_2D, as the file says: options[0..4] = padding (0 SAME, 1 VALID),
+ * stride_w, stride_h, filter_width, filter_height; all 0 when the options table is absent and for every other operator.
+ * Its fused activation is reported by lce_tflite_model_operator_activation. */
+lce_hip_status lce_tflite_model_operator_pool2d(const lce_tflite_model* model, int32_t index, int32_t options[5]);
+
 /* Binary SECTIONS of a mixed graph.  A converted model interleaves builtin float operators (the stem, batch norms, adds,
  * the head) with LCE custom ops; what this library runs are the maximal groups of LCE ops that can execute without a
  * builtin operator in between -- the partition a TFLite delegate would be handed (TensorFlow Lite's
@@ -148,7 +176,7 @@ lce_hip_status lce_tflite_model_section(const lce_tflite_model* model, int32_t i
  * LceQuantize of the same section writes both tensors from one epilogue (lce_hip_bconv2d_run_dual), the quantize launch
  * disappears.  Asynchronous on `stream` (a hipStream_t, or NULL); calls on one model are serialised by a mutex and must
  * use one stream at a time.  `semantics`: lce_hip_semantics (which registration's SAME-zero behaviour).  Shape inference
- * is the ops' own Prepare (quantization.cc:19-41, bmaxpool.cc:41-77, bconv2d.cc:137-300). */
+ * is the ops' own Prepare (quantization.cc:19-41, bmaxpool.cc:41-77, bconv2d.cc:137-300; an absorbed pool: the padding rule). */
 lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t section, int32_t batch, int32_t semantics,
                                             const void* const* inputs_dev, void* const* outputs_dev, void* stream);
 /* Shape ([N,H,W,C], C in words for bitpacked tensors) and size in bytes of a tensor section `section` reads or produces,
@@ -169,6 +197,9 @@ void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches,
 /* The LAST run's lce_hip_concat launches (LCE_TFLITE_SECTIONS_CONCAT): launches (one per absorbed CONCATENATION) and
  * LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
 void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's lce_hip_pool2d launches (LCE_TFLITE_SECTIONS_EXT_POOL): launches (one per absorbed pool) and LceQuantize
+ * operators whose launch they absorbed.  Any pointer may be NULL. */
+void lce_tflite_model_pool_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
