@@ -38,7 +38,7 @@ ABI_SYMBOLS = (
     "lce_hip_graph_begin_capture", "lce_hip_graph_end_capture", "lce_hip_graph_launch", "lce_hip_graph_destroy",
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
-    "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check",
+    "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -97,6 +97,12 @@ class Pool2dDesc(C.Structure):
         ("scale", C.c_float), ("zero_point", C.c_int32)]
 
 
+class Conv1x1Desc(C.Structure):
+    """``lce_hip_conv1x1_desc``."""
+    _fields_ = [(n, C.c_int32) for n in ("batch", "in_height", "in_width", "channels_in", "channels_out", "stride_height",
+                                         "stride_width", "activation")]
+
+
 _lib = None
 
 
@@ -147,6 +153,8 @@ def lib() -> C.CDLL:
                                      C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_pool2d.argtypes = [C.POINTER(Pool2dDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_pool2d_check.argtypes = [C.POINTER(Pool2dDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_conv1x1_f32.argtypes = [C.POINTER(Conv1x1Desc)] + [C.c_void_p] * 6
+        l.lce_hip_conv1x1_f32_check.argtypes = [C.POINTER(Conv1x1Desc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -404,7 +412,7 @@ def unpack(words, channels: int, dtype, scale: float = 1.0, zero_point: int = 0,
     return out
 
 
-# ---- what the fused passes between binary layers share (elementwise, add_int8, concat, pool2d) ----
+# ---- what the fused passes between binary layers share (elementwise, add_int8, concat, pool2d, conv1x1) ----
 def _dtype_name(a):
     return str(a.dtype).replace("torch.", "")
 
@@ -714,6 +722,50 @@ def pool2d(x, op, filter, stride, padding, activation=ACT_NONE, out=True, out_bi
         check(lib().lce_hip_pool2d(C.byref(desc), _dev_ptr(xd), _dev_ptr(out_d), _dev_ptr(bits_d),
                                    C.c_void_p(_stream_or_current(stream, dev))))
     return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+
+
+def _conv1x1_check(x, w, bias, stride, activation, out, out_bits):
+    """Argument checks of ``conv1x1`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (Conv1x1Desc, output shape)."""
+    if _dtype_name(x) != "float32" or len(x.shape) != 4 or min(x.shape) < 1:
+        raise ValueError("conv1x1: x must be a non-empty float32 NHWC tensor, got %s %r" % (x.dtype, tuple(x.shape)))
+    b, h, wd, cin = (int(v) for v in x.shape)
+    ws = tuple(int(v) for v in w.shape)
+    if _dtype_name(w) != "float32" or len(ws) not in (2, 4) or ws not in ((ws[0], cin), (ws[0], 1, 1, cin)) or ws[0] < 1:
+        raise ValueError("conv1x1: w must be float32 [Cout, %d] or [Cout, 1, 1, %d], got %s %r" % (cin, cin, w.dtype, ws))
+    cout = ws[0]
+    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (cout,)):
+        raise ValueError("conv1x1: bias must be float32 [%d], got %s %r" % (cout, bias.dtype, tuple(bias.shape)))
+    sh, sw = _pair("conv1x1", "stride", stride)
+    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
+        raise ValueError("conv1x1: unknown activation %r" % (activation,))
+    shape = (b, (h + sh - 1) // sh, (wd + sw - 1) // sw, cout)
+    _check_outputs("conv1x1", out, None if out_bits is False else out_bits, "float32", shape)
+    return Conv1x1Desc(b, h, wd, cin, cout, sh, sw, int(activation)), shape
+
+
+def conv1x1(x, w, bias=None, stride=1, activation=ACT_NONE, out=None, out_bits=False, stream: int | None = None):
+    """TFLite's builtin float CONV_2D with a 1x1 filter between binary layers (the convolution of a transition block or a
+    downsampling shortcut) and the LceQuantize of its result, in one pass (``lce_hip_conv1x1_f32``).  ``x``: float32 NHWC on
+    the device (or NumPy: copied to cuda:0 and back).  ``w``: float32 [Cout, Cin] or [Cout, 1, 1, Cin].  ``bias``: float32
+    [Cout] or None.  ``stride``: an int or (height, width); the output extent is ceil(in / stride).  ``activation``: ``ACT_*``.
+    Per output element t = fmaf(x[c], w[o][c], t) over c in order from +0.0, then + bias, then the clamp: exact bytes
+    (include/lce_hip.h).  ``out``: None for a new tensor, a tensor to fill (it must not overlap an operand), False for none.
+    ``out_bits``: True for new int32 [B, OH, OW, ceil(Cout/32)] bits (value < 0), a tensor to fill, False for none.  Returns
+    ``(out or None, bits or None)``."""
+    desc, shape = _conv1x1_check(x, w, bias, stride, activation, out, out_bits)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "conv1x1", "x's")
+    xd, wd = on_dev(x), on_dev(w)
+    bd = None if bias is None else on_dev(bias)
+    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if out is None else on_dev(out)
+    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_conv1x1_f32(C.byref(desc), _dev_ptr(xd), _dev_ptr(wd), _dev_ptr(bd), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                        C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, out, None if out_bits is True else out_bits)
 
 
 def bmaxpool(x, filter_height, filter_width, stride_height, stride_width, padding, stream: int | None = None, out=None):

@@ -21,6 +21,7 @@
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
 #include "lce_kernels_concat.h"      // (lce_tu_concat.hip)
 #include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
+#include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -41,6 +42,7 @@
 #include "lce_tu_eltwise_i8.hip"
 #include "lce_tu_concat.hip"
 #include "lce_tu_pool.hip"
+#include "lce_tu_conv1x1.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -918,6 +920,80 @@ lce_hip_status lce_hip_pool2d(const lce_hip_pool2d_desc* d, const void* in_dev, 
   const int e = lce::launch_pool(a, d->type == LCE_HIP_I8 ? lce::kPoolI8 : lce::kPoolF32,
                                  d->op == LCE_HIP_POOL_AVERAGE ? lce::kPoolAverage : lce::kPoolMax, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_pool2d: launch failed: %s", hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// float 1x1 CONV_2D (lce_kernels_conv1x1.h)
+// ------------------------------------------------------------------------------------
+lce_hip_status lce_hip_conv1x1_f32_check(const lce_hip_conv1x1_desc* d, int32_t* out_height, int32_t* out_width) {
+  const char* who = "lce_hip_conv1x1_f32";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels_in <= 0 || d->channels_out <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d] -> %d channels", who, (int)d->batch,
+                (int)d->in_height, (int)d->in_width, (int)d->channels_in, (int)d->channels_out);
+  if (d->stride_height <= 0 || d->stride_width <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)d->stride_height, (int)d->stride_width);
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  // (the kernel's pixel arithmetic, oy * stride, is 64-bit from 32-bit factors: with these bounds nothing wraps)
+  if (std::max(d->in_height, d->in_width) > (1 << 30) || std::max(d->stride_height, d->stride_width) > (1 << 30))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  // (one grid row per 128 output channels)
+  if ((int64_t)d->channels_out > 65535ll * lce::kConv1x1BN)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: more than %lld output channels are not supported", who, 65535ll * lce::kConv1x1BN);
+  // a 1x1 filter has no padding taps: SAME and VALID both give ceil(in / stride)
+  const int32_t oh = (int32_t)(((int64_t)d->in_height + d->stride_height - 1) / d->stride_height);
+  const int32_t ow = (int32_t)(((int64_t)d->in_width + d->stride_width - 1) / d->stride_width);
+  if ((uint64_t)d->batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_conv1x1_f32(const lce_hip_conv1x1_desc* d, const float* in_dev, const float* filter_dev, const float* bias_dev,
+                                   float* out_dev, int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_conv1x1_f32";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!filter_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = lce_hip_conv1x1_f32_check(d, &oh, &ow)) return s;
+  const uint64_t K = (uint64_t)d->channels_in, N = (uint64_t)d->channels_out, pixels = (uint64_t)d->batch * oh * ow, wpr = (N + 31) / 32;
+  // the outputs must not meet anything the launch reads (another wave still reads what one would overwrite) or each other
+  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uint64_t)d->batch * d->in_height * d->in_width * K * 4;
+  const uintptr_t f0 = (uintptr_t)filter_dev, f1 = f0 + N * K * 4;
+  const uintptr_t c0 = (uintptr_t)bias_dev, c1 = c0 + (bias_dev ? N * 4 : 0);
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? pixels * N * 4 : 0);
+  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? pixels * wpr * 4 : 0);
+  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t e0, uintptr_t e1) { return a0 < e1 && e0 < a1; };
+  if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the input", who);
+  if (meet(o0, o1, f0, f1) || meet(b0, b1, f0, f1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the filter", who);
+  if (meet(o0, o1, c0, c1) || meet(b0, b1, c0, c1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the bias", who);
+  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "%s: the two outputs overlap", who);
+  if ((i0 | f0 | c0 | o0 | b0) % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::Conv1x1Args a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.filter = filter_dev; a.bias = bias_dev; a.out = out_dev; a.bits = (uint32_t*)out_bits_dev;
+  a.M = (uint32_t)pixels; a.Cin = (uint32_t)K; a.Cout = (uint32_t)N; a.wpr = (uint32_t)wpr;
+  a.mtiles = (uint32_t)((pixels + lce::kConv1x1BM - 1) / lce::kConv1x1BM);
+  a.OW = (uint32_t)ow; a.OHW = (uint32_t)oh * (uint32_t)ow;          // (both < 2^31: pixels is)
+  a.IW = (uint32_t)d->in_width;
+  a.IHW = (uint64_t)d->in_height * (uint64_t)d->in_width;
+  a.sh = (uint32_t)d->stride_height; a.sw = (uint32_t)d->stride_width;
+  a.strided = d->stride_height != 1 || d->stride_width != 1 ? 1u : 0u;
+  switch (d->activation) {    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
+    case LCE_HIP_ACT_RELU: a.lo = 0.0f; a.hi = FLT_MAX; break;
+    case LCE_HIP_ACT_RELU_N1_TO_1: a.lo = -1.0f; a.hi = 1.0f; break;
+    case LCE_HIP_ACT_RELU6: a.lo = 0.0f; a.hi = 6.0f; break;
+    default: a.lo = -FLT_MAX; a.hi = FLT_MAX;
+  }
+  const bool vec = K % 4 == 0 && i0 % 16 == 0 && f0 % 16 == 0;
+  const int e = lce::launch_conv1x1(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
 

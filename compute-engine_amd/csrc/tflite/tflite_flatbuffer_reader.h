@@ -23,6 +23,9 @@
 //   BuiltinOptions union type 5 Pool2DOptions: 0 padding(int8, Padding: 0 SAME, 1 VALID)  1 stride_w(int32)  2 stride_h(int32)
 //   3 filter_width(int32)  4 filter_height(int32)  5 fused_activation_function(int8); BuiltinOperator 1 AVERAGE_POOL_2D,
 //   17 MAX_POOL_2D.
+//   BuiltinOptions union type 1 Conv2DOptions: 0 padding(int8)  1 stride_w(int32)  2 stride_h(int32)
+//   3 fused_activation_function(int8)  4 dilation_w_factor(int32, default 1)  5 dilation_h_factor(int32, default 1);
+//   BuiltinOperator 3 CONV_2D.
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -39,8 +42,8 @@
 namespace lce_tfl {
 
 constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
-constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
-constexpr int kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
+constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinConv2d = 3, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
+constexpr int kOptionsConv2d = 1, kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 // TensorType values used by LCE graphs
 constexpr int kTensorFloat32 = 0, kTensorInt32 = 2, kTensorBool = 6, kTensorInt8 = 9;
 
@@ -66,6 +69,9 @@ struct Operator {
   int32_t axis = 0;                // ConcatenationOptions.axis; 0 when absent
   // Pool2DOptions; all 0 when absent (schema defaults: padding SAME, the strides and the filter 0)
   int32_t pool_padding = 0, pool_stride_w = 0, pool_stride_h = 0, pool_filter_w = 0, pool_filter_h = 0;
+  // Conv2DOptions: padding and strides in the pool fields above (filter 0); the dilations (schema default 1; 1 when absent)
+  int32_t dilation_w = 1, dilation_h = 1;
+  bool has_conv_options = false;   // a Conv2DOptions table is present
 };
 
 class Model {
@@ -258,6 +264,16 @@ class Model {
           return Fail("bad Pool2DOptions");
         O.pool_padding = pad;
         O.activation = act;
+      }
+      if (opt_type == kOptionsConv2d && opt_pos != 0) {
+        int8_t pad, act;
+        if (!Indirect(opt_pos, &opt) || !Scalar<int8_t>(opt, 0, 0, &pad) || !Scalar<int32_t>(opt, 1, 0, &O.pool_stride_w) ||
+            !Scalar<int32_t>(opt, 2, 0, &O.pool_stride_h) || !Scalar<int8_t>(opt, 3, 0, &act) ||
+            !Scalar<int32_t>(opt, 4, 1, &O.dilation_w) || !Scalar<int32_t>(opt, 5, 1, &O.dilation_h))
+          return Fail("bad Conv2DOptions");
+        O.pool_padding = pad;
+        O.activation = act;
+        O.has_conv_options = true;
       }
       for (int32_t x : O.inputs) if (x < -1 || x >= (int32_t)nt) return Fail("Operator input index out of range");
       for (int32_t x : O.outputs) if (x < 0 || x >= (int32_t)nt) return Fail("Operator output index out of range");

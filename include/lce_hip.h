@@ -278,6 +278,43 @@ lce_hip_status lce_hip_pool2d(const lce_hip_pool2d_desc* desc, const void* in_de
 lce_hip_status lce_hip_pool2d_check(const lce_hip_pool2d_desc* desc, int32_t* out_height, int32_t* out_width);
 
 /* ------------------------------------------------------------------------------------
+ * The float 1x1 CONV_2D between binary layers (TFLite builtin CONV_2D) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* The downsampling shortcuts of Bi-RealNet / BinaryResNetE and the transition blocks of BinaryDenseNet / MeliusNet run a float
+ * 1x1 convolution behind their 2x2 pool.  lce_hip_conv1x1_f32 is that convolution over an NHWC float32 tensor [batch,
+ * in_height, in_width, channels_in] with the filter in the file's own layout [channels_out][channels_in] ([Cout, 1, 1, Cin])
+ * and an optional bias [channels_out], in ONE pass.  The output is [batch, out_height, out_width, channels_out] with
+ * out = (in + stride - 1) / stride: a 1x1 filter has no padding taps, so SAME and VALID agree, and a stride only selects the
+ * input pixel (b, oy * stride_height, ox * stride_width).
+ * Float CONV_2D has no single "TFLite bytes" (reference_ops::Conv's `total += in * w` is a multiply and an add on baseline
+ * x86-64 and an FMA on AArch64; XNNPACK and Eigen block and reorder), so the library states its own: reference_ops::Conv
+ * (float) as a CONTRACTING build computes it.  Per output element, over input channels c = 0 .. channels_in - 1 in order:
+ *   t = +0.0f;  t = fmaf(x[c], w[o][c], t)     one rounding per step, never reassociated, never split over K
+ *   t = t + bias[o]                            one float32 add; skipped when bias_dev is NULL
+ *   v = min(max(t, act_min), act_max)          the clamp of lce_hip_pool2d (NONE: [-FLT_MAX, FLT_MAX]; a NaN passes)
+ * Subnormals are not flushed, going in or coming out; NaN and infinity flow through the chain.  The kernel runs the chain on
+ * the f32-input matrix instruction, whose result is such a chain bit for bit.
+ * `out_dev` (nullable) gets the result; `out_bits_dev` (nullable) gets its LceQuantize as lce_hip_bitpack(F32, out, ...)
+ * writes it: bit = v < 0, LSB first, ceil(channels_out/32) words per pixel, padding bits 0 -- from the values the pass holds.
+ * Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc, input or filter, both outputs NULL, an extent, channel
+ * count or stride <= 0, an unknown activation, an output that overlaps the input, the filter, the bias or the other output, a
+ * pointer that is not 4-byte aligned; LCE_HIP_ERR_UNSUPPORTED: 2^31 or more output pixels, an image extent or a stride above
+ * 2^30, more than 65535 x 128 output channels.
+ * Pointers need 4-byte alignment only (16-byte aligned input and filter with channels_in % 4 == 0 take a faster load path);
+ * the byte counts are unbounded (64-bit offsets throughout).  Asynchronous on `stream`, capturable in a HIP graph, allocates
+ * nothing and copies nothing between host and device. */
+typedef struct lce_hip_conv1x1_desc {
+  int32_t batch, in_height, in_width, channels_in, channels_out;
+  int32_t stride_height, stride_width, activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+} lce_hip_conv1x1_desc;
+lce_hip_status lce_hip_conv1x1_f32(const lce_hip_conv1x1_desc* desc, const float* in_dev, const float* filter_dev /* [Cout][Cin] */,
+                                   const float* bias_dev /* nullable */, float* out_dev /* nullable */,
+                                   int32_t* out_bits_dev /* nullable */, void* stream);
+/* The descriptor checks of lce_hip_conv1x1_f32 alone, and the output extents (nullable).  Host only: needs no device. */
+lce_hip_status lce_hip_conv1x1_f32_check(const lce_hip_conv1x1_desc* desc, int32_t* out_height, int32_t* out_width);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

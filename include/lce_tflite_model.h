@@ -84,15 +84,34 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   of the section that reads the pooled tensor as the launch's bit output; the pooled tensor itself is written only when
  *   something else reads it or the section delivers it.  Together with LCE_TFLITE_SECTIONS_ELEMENTWISE the body of a
  *   BinaryAlexNet is one section.  L2 pooling, a CONV_2D and bitpacked pooling (LceBMaxPool2d, an LCE operator already)
- *   are not concerned.
+ *   are not concerned (the float 1x1 CONV_2D joins with LCE_TFLITE_SECTIONS_EXT_CONV1X1, below).
+ *
+ * struct_size == 40 is the third form: four more words after `reserved`, which must be zero too, and one more bit in
+ * `sections_ext` (the 24-byte form promises that sections_ext == 2 is refused, and still refuses it; nothing past its 24 bytes
+ * is read).
+ *   LCE_TFLITE_SECTIONS_EXT_CONV1X1: the same for the float 1x1 CONV_2D behind the pool of a downsampling shortcut (Bi-RealNet,
+ *   BinaryResNetE) or of a transition block (BinaryDenseNet, MeliusNet).  A CONV_2D (3) joins the LCE epoch in which it
+ *   becomes ready when it has 2 or 3 inputs (a third input of -1: no bias) and one output; input, filter and output are
+ *   float32, and the bias when present; the output is 4-D with positive extents; the data input is a non-constant 4-D tensor;
+ *   the filter is a constant [Cout, 1, 1, Cin] with data in the file and Cin the input's channels; the bias is absent or a
+ *   constant [Cout]; Cout is the output's channels; the Conv2DOptions table is present, the strides are positive, the
+ *   dilations 1, the padding SAME or VALID, the fused activation NONE / RELU / RELU_N1_TO_1 / RELU6; the declared output
+ *   height and width are ceil(in / stride); and lce_hip_conv1x1_f32_check accepts the descriptor.  A convolution that is
+ *   ready from the start (a stem) is the host's, and so is everything else: a 3x3 filter, int8 or hybrid weights, a
+ *   non-constant filter, DEPTHWISE_CONV_2D, TANH / SIGN_BIT, a missing options table.  lce_tflite_model_run_section runs such
+ *   a convolution as one lce_hip_conv1x1_f32 launch (its arithmetic: include/lce_hip.h), with the first LceQuantize of the
+ *   section that reads the result as the launch's bit output; the float tensor itself is written only when something else
+ *   reads it or the section delivers it; filter and bias are uploaded once per model.  Together with the element-wise and
+ *   pool flags the body of a Bi-RealNet-style or dense network is one section.
  * The flags of both words combine. */
 enum { LCE_TFLITE_SECTIONS_CONCAT = 4u };
-enum { LCE_TFLITE_SECTIONS_EXT_POOL = 1u };
+enum { LCE_TFLITE_SECTIONS_EXT_POOL = 1u, LCE_TFLITE_SECTIONS_EXT_CONV1X1 = 2u /* the 40-byte form only */ };
 typedef struct lce_tflite_open_options {
-  uint32_t struct_size;    /* 8 (the first two fields only) or sizeof(lce_tflite_open_options) == 24 */
+  uint32_t struct_size;    /* 8 (the first two fields only), 24 (up to `reserved`) or sizeof(lce_tflite_open_options) == 40 */
   uint32_t sections;       /* LCE_TFLITE_SECTIONS_*: 0..7, every other bit refused */
   uint32_t sections_ext;   /* LCE_TFLITE_SECTIONS_EXT_*; every other bit refused */
   uint32_t reserved[3];    /* must be zero */
+  uint32_t reserved2[4];   /* the 40-byte form: must be zero */
 } lce_tflite_open_options;
 lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
                                              size_t err_len);
@@ -140,6 +159,11 @@ lce_hip_status lce_tflite_model_operator_axis(const lce_tflite_model* model, int
  * Its fused activation is reported by lce_tflite_model_operator_activation. */
 lce_hip_status lce_tflite_model_operator_pool2d(const lce_tflite_model* model, int32_t index, int32_t options[5]);
 
+/* Conv2DOptions of a builtin CONV_2D, as the file says: options[0..4] = padding (0 SAME, 1 VALID), stride_w, stride_h,
+ * dilation_w_factor, dilation_h_factor (schema default 1).  {0, 0, 0, 1, 1} when the options table is absent and for every
+ * other operator.  Its fused activation is reported by lce_tflite_model_operator_activation. */
+lce_hip_status lce_tflite_model_operator_conv2d(const lce_tflite_model* model, int32_t index, int32_t options[5]);
+
 /* Binary SECTIONS of a mixed graph.  A converted model interleaves builtin float operators (the stem, batch norms, adds,
  * the head) with LCE custom ops; what this library runs are the maximal groups of LCE ops that can execute without a
  * builtin operator in between -- the partition a TFLite delegate would be handed (TensorFlow Lite's
@@ -176,7 +200,7 @@ lce_hip_status lce_tflite_model_section(const lce_tflite_model* model, int32_t i
  * LceQuantize of the same section writes both tensors from one epilogue (lce_hip_bconv2d_run_dual), the quantize launch
  * disappears.  Asynchronous on `stream` (a hipStream_t, or NULL); calls on one model are serialised by a mutex and must
  * use one stream at a time.  `semantics`: lce_hip_semantics (which registration's SAME-zero behaviour).  Shape inference
- * is the ops' own Prepare (quantization.cc:19-41, bmaxpool.cc:41-77, bconv2d.cc:137-300; an absorbed pool: the padding rule). */
+ * is the ops' own Prepare (quantization.cc:19-41, bmaxpool.cc:41-77, bconv2d.cc:137-300; an absorbed pool: the padding rule; an absorbed CONV_2D: ceil(in / stride)). */
 lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t section, int32_t batch, int32_t semantics,
                                             const void* const* inputs_dev, void* const* outputs_dev, void* stream);
 /* Shape ([N,H,W,C], C in words for bitpacked tensors) and size in bytes of a tensor section `section` reads or produces,
@@ -200,6 +224,9 @@ void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, i
 /* The LAST run's lce_hip_pool2d launches (LCE_TFLITE_SECTIONS_EXT_POOL): launches (one per absorbed pool) and LceQuantize
  * operators whose launch they absorbed.  Any pointer may be NULL. */
 void lce_tflite_model_pool_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's lce_hip_conv1x1_f32 launches (LCE_TFLITE_SECTIONS_EXT_CONV1X1): launches (one per absorbed CONV_2D) and
+ * LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
+void lce_tflite_model_conv1x1_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
