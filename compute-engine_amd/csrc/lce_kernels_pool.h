@@ -89,10 +89,12 @@ LCE_DEVICE void pool_store_through(u32x4* p, u32x4 v) {
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
 }
 
-// The window of one output pixel, clipped to the image: rows [y0, y1), columns [x0, x1) of image b.
+// The window of one output pixel, clipped to the image: rows [y0, y1), columns [x0, x1) of image b.  (ys, xs): its
+// unclipped first row and column (what a filter tap's index counts from: lce_kernels_depthwise.h).
 struct PoolWindow {
   uint32_t b;
   int32_t y0, y1, x0, x1;
+  int32_t ys, xs;
 };
 LCE_DEVICE PoolWindow pool_window(const PoolArgs& A, uint32_t pixel, bool ok) {
   const uint32_t row = pool_div(pixel, A.div_ow);                  // b * OH + oy
@@ -105,6 +107,8 @@ LCE_DEVICE PoolWindow pool_window(const PoolArgs& A, uint32_t pixel, bool ok) {
   w.y1 = ys + A.fh > A.H ? A.H : ys + A.fh;
   w.x0 = xs < 0 ? 0 : xs;
   w.x1 = xs + A.fw > A.W ? A.W : xs + A.fw;
+  w.ys = ys;
+  w.xs = xs;
   if (!ok) w.y1 = w.y0;                                            // (a lane past the end walks nothing)
   return w;
 }

@@ -38,7 +38,7 @@ struct lce_tflite_model {
     int32_t conv_quantize = 0;                                          // LceQuantize launches folded into a convolution (run_dual)
     int32_t ew_ops = 0;                                                 // ADD / MUL operators inside the lce_hip_elementwise launches
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
-    Pass ew, add_i8, concat, pool, conv1x1;                             // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat, lce_hip_pool2d, lce_hip_conv1x1_f32
+    Pass ew, add_i8, concat, pool, conv1x1, depthwise;                  // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat, lce_hip_pool2d, lce_hip_conv1x1_f32, lce_hip_depthwise_conv2d_f32
   };
   RunStats last;                                                        // of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
@@ -268,7 +268,59 @@ bool Conv1x1Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   int32_t oh = 0, ow = 0;
   return lce_hip_conv1x1_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
 }
-enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3, kAbsorbedPool = 4, kAbsorbedConv1x1 = 5 };
+
+// lce_hip_depthwise_desc of a builtin DEPTHWISE_CONV_2D at `batch` images, from its options and the FILE's input and filter tensors.
+lce_hip_depthwise_desc DepthwiseDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  lce_hip_depthwise_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = batch; d.in_height = in.shape[1]; d.in_width = in.shape[2]; d.channels_in = in.shape[3];
+  d.depth_multiplier = o.depth_multiplier;
+  d.filter_height = flt.shape[1]; d.filter_width = flt.shape[2];
+  d.stride_height = o.pool_stride_h; d.stride_width = o.pool_stride_w;
+  d.padding = o.pool_padding;
+  d.activation = o.activation;
+  return d;
+}
+
+// The static half of "a builtin DEPTHWISE_CONV_2D that a section may run" (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE): the float blur of
+// QuickNet's transition.  2 or 3 inputs (a third input of -1: no bias) and one output; input, filter and output float32, the
+// bias float32 when present; a 4-D output with positive extents; a non-constant 4-D data input; the filter a constant
+// [1, fh, fw, Cout] with data in the file; the bias absent or a constant [Cout]; the options table present; a depth multiplier
+// >= 1 with Cout == Cin x multiplier == the output's channels; strides positive, dilations 1, padding SAME or VALID, an
+// activation lce_hip_depthwise_conv2d_f32 knows; the declared output height and width what the padding rule gives; and a
+// descriptor the entry's own check accepts.  The other half -- it becomes ready in an LCE epoch -- is decided by Partition().
+bool DepthwiseCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinDepthwiseConv2d) return false;
+  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 || flt.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32) return false;
+  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
+  for (int k = 0; k < 4; ++k)
+    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
+  if (!flt.data || flt.shape.size() != 4 || flt.shape[0] != 1 || flt.shape[1] <= 0 || flt.shape[2] <= 0 || flt.shape[3] <= 0) return false;
+  const int64_t cout = flt.shape[3];
+  // (fh x fw < 2^62 and cout < 2^31: compared by division, the product of the three is never formed)
+  const uint64_t taps = (uint64_t)flt.shape[1] * (uint64_t)flt.shape[2];
+  if ((uint64_t)flt.bytes % 4u != 0 || (uint64_t)flt.bytes / 4u % taps != 0 || (uint64_t)flt.bytes / 4u / taps != (uint64_t)cout) return false;
+  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
+    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
+    if (bias.type != lce_tfl::kTensorFloat32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != cout ||
+        (uint64_t)bias.bytes != (uint64_t)cout * 4u) return false;
+  }
+  if (!o.has_depthwise_options) return false;
+  if (o.depth_multiplier < 1 || (int64_t)in.shape[3] * o.depth_multiplier != cout || out.shape[3] != cout) return false;
+  if (o.pool_stride_h <= 0 || o.pool_stride_w <= 0 || o.dilation_h != 1 || o.dilation_w != 1) return false;
+  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  const lce_hip_depthwise_desc d = DepthwiseDesc(M, o, in.shape[0]);
+  int32_t oh = 0, ow = 0;
+  return lce_hip_depthwise_conv2d_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
+}
+enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3, kAbsorbedPool = 4, kAbsorbedConv1x1 = 5, kAbsorbedDepthwise = 6 };
 }  // namespace
 
 // The partition a delegate would get (tensorflow/lite/graph_info.cc, PartitionGraphIntoIndependentNodeSubsets, restated from
@@ -299,6 +351,8 @@ void lce_tflite_model::Partition() {
     if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_POOL)) candidate[i] = PoolCandidate(m, m.operators[i]) ? kAbsorbedPool : 0;
     // LCE_TFLITE_SECTIONS_EXT_CONV1X1: the same rule for the float 1x1 CONV_2D of a transition block or a shortcut
     if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_CONV1X1)) candidate[i] = Conv1x1Candidate(m, m.operators[i]) ? kAbsorbedConv1x1 : 0;
+    // LCE_TFLITE_SECTIONS_EXT_DEPTHWISE: the same rule for the float DEPTHWISE_CONV_2D of QuickNet's transition
+    if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_DEPTHWISE)) candidate[i] = DepthwiseCandidate(m, m.operators[i]) ? kAbsorbedDepthwise : 0;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -414,16 +468,17 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
 lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
                                              size_t err_len) {
   // versioned by size: the first form is 8 bytes (struct_size, sections), the second 24 (+ sections_ext, reserved[3]), the
-  // third 40 (+ reserved2[4]); nothing behind the size the caller states is read
-  constexpr uint32_t kFirstForm = 8, kSecondForm = 24;
-  static_assert(sizeof(lce_tflite_open_options) == 40, "the third form of the options struct");
+  // third 40 (+ reserved2[4]), the fourth 56 (+ reserved3[4]); nothing behind the size the caller states is read
+  constexpr uint32_t kFirstForm = 8, kSecondForm = 24, kThirdForm = 40;
+  static_assert(sizeof(lce_tflite_open_options) == 56, "the fourth form of the options struct");
   const char* refusal = nullptr;
   uint32_t sections = 0, ext = 0, allowed_ext = 0;
-  uint32_t words[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // (copied: the caller's object may be only 8 or 24 bytes long)
+  uint32_t words[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // (copied: the caller's object may be only 8, 24 or 40 bytes long)
   if (options) memcpy(words, options, kFirstForm);
   if (!options) {
     refusal = "null options";
-  } else if (words[0] != kFirstForm && words[0] != kSecondForm && words[0] != (uint32_t)sizeof(lce_tflite_open_options)) {
+  } else if (words[0] != kFirstForm && words[0] != kSecondForm && words[0] != kThirdForm &&
+             words[0] != (uint32_t)sizeof(lce_tflite_open_options)) {
     refusal = "options: unknown struct_size";
   } else {
     memcpy(words, options, words[0]);
@@ -432,6 +487,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
       ext = words[2];
       allowed_ext = LCE_TFLITE_SECTIONS_EXT_POOL;
       if (words[0] != kSecondForm) allowed_ext |= LCE_TFLITE_SECTIONS_EXT_CONV1X1;
+      if (words[0] != kSecondForm && words[0] != kThirdForm) allowed_ext |= LCE_TFLITE_SECTIONS_EXT_DEPTHWISE;
       uint32_t rest = 0;
       for (uint32_t k = 3; k < words[0] / 4; ++k) rest |= words[k];
       if (rest) refusal = "options: reserved fields must be zero";
@@ -520,6 +576,17 @@ lce_hip_status lce_tflite_model_operator_conv2d(const lce_tflite_model* model, i
   const bool conv = o.has_conv_options;
   options[0] = conv ? o.pool_padding : 0; options[1] = conv ? o.pool_stride_w : 0; options[2] = conv ? o.pool_stride_h : 0;
   options[3] = o.dilation_w; options[4] = o.dilation_h;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_tflite_model_operator_depthwise(const lce_tflite_model* model, int32_t index, int32_t options[6]) {
+  if (!model || !options || index < 0 || index >= (int32_t)model->m.operators.size())
+    return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_depthwise: bad argument");
+  const lce_tfl::Operator& o = model->m.operators[index];
+  const bool dw = o.has_depthwise_options;
+  options[0] = dw ? o.pool_padding : 0; options[1] = dw ? o.pool_stride_w : 0; options[2] = dw ? o.pool_stride_h : 0;
+  options[3] = dw ? o.depth_multiplier : 0;
+  options[4] = dw ? o.dilation_w : 1; options[5] = dw ? o.dilation_h : 1;
   return LCE_HIP_OK;
 }
 
@@ -763,7 +830,7 @@ struct Walk {
     return LCE_HIP_OK;
   }
 
-  // Where the result of a fused pass (an ADD / MUL chain, an int8 ADD, a CONCATENATION, a pool, a 1x1 convolution) goes.
+  // Where the result of a fused pass (an ADD / MUL chain, an int8 ADD, a CONCATENATION, a pool, a 1x1 or depthwise convolution) goes.
   struct Fold {
     int32_t value_t;                     // the tensor the pass produces
     int32_t bits_t = -1;                 // the output of the folded LceQuantize; -1: none
@@ -1045,6 +1112,42 @@ struct Walk {
     return LCE_HIP_OK;
   }
 
+  // An absorbed float DEPTHWISE_CONV_2D (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE) as ONE lce_hip_depthwise_conv2d_f32 launch, folded and
+  // fed as Conv1x1 above.
+  lce_hip_status Depthwise(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
+    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    auto it = shapes.find(op.inputs[0]);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a DEPTHWISE_CONV_2D reads a tensor nothing produced");
+    if (!Agrees(it->second, lce_tfl::kTensorFloat32, is[1], is[2], is[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a DEPTHWISE_CONV_2D input's shape or type does not match the one its producer infers");
+    const lce_hip_depthwise_desc d = DepthwiseDesc(M, op, batch);
+    Shape os;
+    os.dims[0] = batch; os.dims[3] = M.tensors[op.inputs[1]].shape[3];
+    os.type = lce_tfl::kTensorFloat32;
+    if (lce_hip_status s = lce_hip_depthwise_conv2d_f32_check(&d, &os.dims[1], &os.dims[2])) return s;
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(op.inputs[0], "a DEPTHWISE_CONV_2D input", &in)) return s;
+    const float *filter = nullptr, *bias = nullptr;
+    if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &filter)) return s;
+    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = lce_hip_depthwise_conv2d_f32(&d, (const float*)in, filter, bias, (float*)out, (int32_t*)bits, stream)) return s;
+    ++model->last.depthwise.launches;
+    if (fold.bits_t >= 0) ++model->last.depthwise.quantize;
+    return LCE_HIP_OK;
+  }
+
   // The four LCE operators.  `in` is the inferred shape of operator `i`'s first input, `in_dev` its device pointer (with `run`).
   lce_hip_status Quantize(int32_t i, const Shape& in, const void* in_dev) {                      // quantization.cc:19-41,76-114
     const lce_tfl::Operator& op = model->m.operators[i];
@@ -1175,6 +1278,7 @@ struct Walk {
         case kAbsorbedConcat: s = Concat(i); break;
         case kAbsorbedPool: s = Pool2d(i); break;
         case kAbsorbedConv1x1: s = Conv1x1(i); break;
+        case kAbsorbedDepthwise: s = Depthwise(i); break;
         default: s = LceOp(i);
       }
       if (s) return s;
@@ -1309,6 +1413,13 @@ void lce_tflite_model_conv1x1_stats(lce_tflite_model* model, int32_t* launches, 
   std::lock_guard<std::mutex> lock(model->run_mu);
   if (launches) *launches = model->last.conv1x1.launches;
   if (quantize_folded) *quantize_folded = model->last.conv1x1.quantize;
+}
+
+void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (launches) *launches = model->last.depthwise.launches;
+  if (quantize_folded) *quantize_folded = model->last.depthwise.quantize;
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

@@ -26,6 +26,9 @@
 //   BuiltinOptions union type 1 Conv2DOptions: 0 padding(int8)  1 stride_w(int32)  2 stride_h(int32)
 //   3 fused_activation_function(int8)  4 dilation_w_factor(int32, default 1)  5 dilation_h_factor(int32, default 1);
 //   BuiltinOperator 3 CONV_2D.
+//   BuiltinOptions union type 2 DepthwiseConv2DOptions: 0 padding(int8)  1 stride_w(int32)  2 stride_h(int32)
+//   3 depth_multiplier(int32)  4 fused_activation_function(int8)  5 dilation_w_factor(int32, default 1)
+//   6 dilation_h_factor(int32, default 1); BuiltinOperator 4 DEPTHWISE_CONV_2D.
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -42,8 +45,8 @@
 namespace lce_tfl {
 
 constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
-constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinConv2d = 3, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
-constexpr int kOptionsConv2d = 1, kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
+constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinConv2d = 3, kBuiltinDepthwiseConv2d = 4, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
+constexpr int kOptionsConv2d = 1, kOptionsDepthwiseConv2d = 2, kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 // TensorType values used by LCE graphs
 constexpr int kTensorFloat32 = 0, kTensorInt32 = 2, kTensorBool = 6, kTensorInt8 = 9;
 
@@ -72,6 +75,9 @@ struct Operator {
   // Conv2DOptions: padding and strides in the pool fields above (filter 0); the dilations (schema default 1; 1 when absent)
   int32_t dilation_w = 1, dilation_h = 1;
   bool has_conv_options = false;   // a Conv2DOptions table is present
+  // DepthwiseConv2DOptions: padding, strides and dilations in the fields above; the multiplier (0 when absent)
+  int32_t depth_multiplier = 0;
+  bool has_depthwise_options = false;   // a DepthwiseConv2DOptions table is present
 };
 
 class Model {
@@ -274,6 +280,17 @@ class Model {
         O.pool_padding = pad;
         O.activation = act;
         O.has_conv_options = true;
+      }
+      if (opt_type == kOptionsDepthwiseConv2d && opt_pos != 0) {
+        int8_t pad, act;
+        if (!Indirect(opt_pos, &opt) || !Scalar<int8_t>(opt, 0, 0, &pad) || !Scalar<int32_t>(opt, 1, 0, &O.pool_stride_w) ||
+            !Scalar<int32_t>(opt, 2, 0, &O.pool_stride_h) || !Scalar<int32_t>(opt, 3, 0, &O.depth_multiplier) ||
+            !Scalar<int8_t>(opt, 4, 0, &act) || !Scalar<int32_t>(opt, 5, 1, &O.dilation_w) ||
+            !Scalar<int32_t>(opt, 6, 1, &O.dilation_h))
+          return Fail("bad DepthwiseConv2DOptions");
+        O.pool_padding = pad;
+        O.activation = act;
+        O.has_depthwise_options = true;
       }
       for (int32_t x : O.inputs) if (x < -1 || x >= (int32_t)nt) return Fail("Operator input index out of range");
       for (int32_t x : O.outputs) if (x < 0 || x >= (int32_t)nt) return Fail("Operator output index out of range");

@@ -28,6 +28,9 @@ BinaryAlexNet is one section.
 With ``conv1x1_sections=True`` (LCE_TFLITE_SECTIONS_EXT_CONV1X1, the 40-byte options) the float 1x1 CONV_2D of a transition block
 or a downsampling shortcut joins them (``lce_hip_conv1x1_f32``); with ``elementwise_sections`` and ``pool_sections`` the body of
 a Bi-RealNet-style or dense network is one section.
+With ``depthwise_sections=True`` (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, the 56-byte options) the float DEPTHWISE_CONV_2D of
+QuickNet's transition block (its 3x3 / 2 blur) joins them (``lce_hip_depthwise_conv2d_f32``); with the element-wise, pool and 1x1
+flags a QuickNet body is one section.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -49,6 +52,7 @@ SECTIONS_INT8_ADD = 2             # LCE_TFLITE_SECTIONS_INT8_ADD
 SECTIONS_CONCAT = 4               # LCE_TFLITE_SECTIONS_CONCAT (lce_tflite_model_open_opts only)
 SECTIONS_EXT_POOL = 1             # LCE_TFLITE_SECTIONS_EXT_POOL (sections_ext of the 24-byte options)
 SECTIONS_EXT_CONV1X1 = 2          # LCE_TFLITE_SECTIONS_EXT_CONV1X1 (sections_ext of the 40-byte options)
+SECTIONS_EXT_DEPTHWISE = 4        # LCE_TFLITE_SECTIONS_EXT_DEPTHWISE (sections_ext of the 56-byte options)
 _NP = {FLOAT32: np.float32, INT32: np.int32, BOOL: np.bool_, INT8: np.int8}
 LCE_OPS = ("LceQuantize", "LceDequantize", "LceBconv2d", "LceBMaxPool2d")
 
@@ -86,6 +90,12 @@ class _OpenOptions40(C.Structure):
                 ("reserved2", C.c_uint32 * 4)]
 
 
+class _OpenOptions56(C.Structure):
+    """``lce_tflite_open_options``, the 56-byte form."""
+    _fields_ = [("struct_size", C.c_uint32), ("sections", C.c_uint32), ("sections_ext", C.c_uint32), ("reserved", C.c_uint32 * 3),
+                ("reserved2", C.c_uint32 * 4), ("reserved3", C.c_uint32 * 4)]
+
+
 class Section:
     """A maximal group of LCE ops with no builtin operator between them: operator indices in execution order, the
     non-constant tensors it reads from outside, the tensors it must deliver (read outside it, or graph outputs)."""
@@ -119,6 +129,9 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_operator_conv2d.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_conv1x1_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
         l.lce_tflite_model_conv1x1_stats.restype = None
+        l.lce_tflite_model_operator_depthwise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        l.lce_tflite_model_depthwise_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
+        l.lce_tflite_model_depthwise_stats.restype = None
         l.lce_tflite_model_operator_axis.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_concat_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
         l.lce_tflite_model_concat_stats.restype = None
@@ -164,14 +177,17 @@ class Tensor:
 
 
 class Operator:
-    def __init__(self, info: _OperatorInfo, activation: int = 0, axis: int = 0, pool=(0, 0, 0, 0, 0), dilation=(1, 1)):
+    def __init__(self, info: _OperatorInfo, activation: int = 0, axis: int = 0, pool=(0, 0, 0, 0, 0), dilation=(1, 1),
+                 depth_multiplier: int = 0):
         self.builtin_code = info.builtin_code
         self.activation = activation          # fused_activation_function of a builtin ADD / MUL / CONCATENATION / pool (0: NONE)
         self.axis = axis                      # axis of a builtin CONCATENATION as the file says (0 when absent)
         # Pool2DOptions of a builtin AVERAGE_POOL_2D / MAX_POOL_2D as the file says (all 0 when absent)
         # (a builtin CONV_2D fills padding and strides from its Conv2DOptions; its filter fields stay 0)
         self.padding, self.stride_w, self.stride_h, self.filter_width, self.filter_height = (int(v) for v in pool)
+        # (a builtin DEPTHWISE_CONV_2D fills padding, strides and dilations from its DepthwiseConv2DOptions in the same way)
         self.dilation_w, self.dilation_h = (int(v) for v in dilation)   # Conv2DOptions dilation factors (1 when absent)
+        self.depth_multiplier = int(depth_multiplier)   # DepthwiseConv2DOptions.depth_multiplier (0 when absent)
         self.custom_code = (info.custom_code or b"").decode()
         self.inputs = [info.inputs[i] for i in range(info.num_inputs)]
         self.outputs = [info.outputs[i] for i in range(info.num_outputs)]
@@ -188,14 +204,16 @@ class LceModel:
 
     def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
                  int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
-                 conv1x1_sections: bool = False):
+                 conv1x1_sections: bool = False, depthwise_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
         CONCATENATION of a dense block joins them (LCE_TFLITE_SECTIONS_CONCAT, through ``lce_tflite_model_open_opts``).  ``pool_sections``: the
         builtin MAX_POOL_2D / AVERAGE_POOL_2D between binary layers join them (LCE_TFLITE_SECTIONS_EXT_POOL, through the
         24-byte options of ``lce_tflite_model_open_opts``).  ``conv1x1_sections``: the float 1x1 CONV_2D of a transition block or a
-        downsampling shortcut joins them (LCE_TFLITE_SECTIONS_EXT_CONV1X1, through the 40-byte options)."""
+        downsampling shortcut joins them (LCE_TFLITE_SECTIONS_EXT_CONV1X1, through the 40-byte options).  ``depthwise_sections``: the
+        float DEPTHWISE_CONV_2D of QuickNet's transition block joins them (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, through the 56-byte
+        options, which no other combination of flags uses)."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -205,9 +223,15 @@ class LceModel:
         self.concat_sections = bool(concat_sections)
         self.pool_sections = bool(pool_sections)
         self.conv1x1_sections = bool(conv1x1_sections)
+        self.depthwise_sections = bool(depthwise_sections)
         err = C.create_string_buffer(256)
         flags = (SECTIONS_ELEMENTWISE if elementwise_sections else 0) | (SECTIONS_INT8_ADD if int8_add_sections else 0)
-        if conv1x1_sections:
+        if depthwise_sections:
+            opts = _OpenOptions56(C.sizeof(_OpenOptions56), flags | (SECTIONS_CONCAT if concat_sections else 0),
+                                  SECTIONS_EXT_DEPTHWISE | (SECTIONS_EXT_CONV1X1 if conv1x1_sections else 0) |
+                                  (SECTIONS_EXT_POOL if pool_sections else 0))
+            self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
+        elif conv1x1_sections:
             opts = _OpenOptions40(C.sizeof(_OpenOptions40), flags | (SECTIONS_CONCAT if concat_sections else 0),
                                   SECTIONS_EXT_CONV1X1 | (SECTIONS_EXT_POOL if pool_sections else 0))
             self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
@@ -239,7 +263,11 @@ class LceModel:
             _amd.check(l.lce_tflite_model_operator_pool2d(self._h, i, pool))
             conv = (C.c_int32 * 5)()
             _amd.check(l.lce_tflite_model_operator_conv2d(self._h, i, conv))
-            self.operators.append(Operator(info, act.value, axis.value, tuple(pool), tuple(conv)[3:]))
+            dw = (C.c_int32 * 6)()
+            _amd.check(l.lce_tflite_model_operator_depthwise(self._h, i, dw))
+            if dw[3]:        # a DepthwiseConv2DOptions table: padding, strides and dilations are its own
+                pool, conv = (dw[0], dw[1], dw[2], 0, 0), (0, 0, 0, dw[4], dw[5])
+            self.operators.append(Operator(info, act.value, axis.value, tuple(pool), tuple(conv)[3:], dw[3]))
         buf = (C.c_int32 * 64)()
         self.inputs = [buf[i] for i in range(l.lce_tflite_model_inputs(self._h, buf, 64))]
         self.outputs = [buf[i] for i in range(l.lce_tflite_model_outputs(self._h, buf, 64))]
@@ -310,6 +338,12 @@ class LceModel:
         tflite_lib().lce_tflite_model_conv1x1_stats(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    def depthwise_stats(self):
+        """(lce_hip_depthwise_conv2d_f32 launches, LceQuantize launches they absorbed) of the last run."""
+        a, b = C.c_int32(), C.c_int32()
+        tflite_lib().lce_tflite_model_depthwise_stats(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -339,17 +373,19 @@ class Interpreter:
 
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
                  use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
-                 concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False):
-        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+                 concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
+                 depthwise_sections: bool = False):
+        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
                                     int8_add_sections=int8_add_sections, concat_sections=concat_sections,
-                                    pool_sections=pool_sections, conv1x1_sections=conv1x1_sections))
+                                    pool_sections=pool_sections, conv1x1_sections=conv1x1_sections,
+                                    depthwise_sections=depthwise_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections or self.model.pool_sections or self.model.conv1x1_sections:
+        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections or self.model.pool_sections or self.model.conv1x1_sections or self.model.depthwise_sections:
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

@@ -315,6 +315,44 @@ lce_hip_status lce_hip_conv1x1_f32(const lce_hip_conv1x1_desc* desc, const float
 lce_hip_status lce_hip_conv1x1_f32_check(const lce_hip_conv1x1_desc* desc, int32_t* out_height, int32_t* out_width);
 
 /* ------------------------------------------------------------------------------------
+ * The float DEPTHWISE_CONV_2D between binary layers (TFLite builtin DEPTHWISE_CONV_2D) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* QuickNet's transition block blurs its pooled map with a fixed 3x3 / 2 depthwise filter ([1 2 1] x [1 2 1] / 16) in front of
+ * its 1x1 convolution.  lce_hip_depthwise_conv2d_f32 is TFLite's float reference_ops::DepthwiseConv over an NHWC float32
+ * tensor [batch, in_height, in_width, channels_in] with the filter in the file's own layout [1, filter_height, filter_width,
+ * Cout], Cout = channels_in x depth_multiplier, and an optional bias [Cout], in ONE pass.  Output channel o reads input
+ * channel o / depth_multiplier.  The output is [batch, out_height, out_width, Cout]; its extents and the padding are exactly
+ * lce_hip_pool2d's (lce_hip_bmaxpool_output_shape; pad_before = total / 2).  The dilation is 1.
+ * As for lce_hip_conv1x1_f32 the library states its own bytes: the reference as a CONTRACTING build computes it.  Per output
+ * element, over its in-bounds taps in raster order (filter row, then filter column) -- taps in the padding are SKIPPED, not
+ * read as zero, and the filter tap index is the unclipped one:
+ *   t = +0.0f;  t = fmaf(x[y][x][o / m], w[fy][fx][o], t)   one rounding per tap, never reassociated
+ *   t = t + bias[o]                                         one float32 add; skipped when bias_dev is NULL
+ *   v = min(max(t, act_min), act_max)                       the clamp of lce_hip_pool2d (NONE: [-FLT_MAX, FLT_MAX]; a NaN passes)
+ * Subnormals are not flushed, going in or coming out; NaN and infinity flow through the chain.
+ * `out_dev` (nullable) gets the result; `out_bits_dev` (nullable) gets its LceQuantize as lce_hip_bitpack(F32, out, ...)
+ * writes it: bit = v < 0, LSB first, ceil(Cout/32) words per pixel, padding bits 0 -- from the values the pass holds.
+ * Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc, input or filter, both outputs NULL, an extent, channel
+ * count, multiplier, filter or stride <= 0, an unknown padding or activation, an empty output, an output that overlaps the
+ * input, the filter, the bias or the other output, a pointer that is not 4-byte aligned; LCE_HIP_ERR_UNSUPPORTED: 2^31 or more
+ * output pixels, an image extent or a stride above 2^30, filter_height x filter_width x Cout >= 2^31.
+ * Pointers need 4-byte alignment only (depth_multiplier 1 with channels % 4 == 0 and 16-byte aligned input, filter, bias and
+ * output takes a 16-byte path; with bits it also needs channels % 32 == 0); the byte counts are unbounded (64-bit offsets).
+ * Asynchronous on `stream`, capturable in a HIP graph, allocates nothing and copies nothing between host and device. */
+typedef struct lce_hip_depthwise_desc {
+  int32_t batch, in_height, in_width, channels_in, depth_multiplier;
+  int32_t filter_height, filter_width, stride_height, stride_width;
+  int32_t padding;      /* lce_hip_padding: SAME or VALID */
+  int32_t activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+} lce_hip_depthwise_desc;
+lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* desc, const float* in_dev,
+                                            const float* filter_dev /* [1][fh][fw][Cout] */, const float* bias_dev /* nullable */,
+                                            float* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+/* The descriptor checks of lce_hip_depthwise_conv2d_f32 alone, and the output extents (nullable).  Host only: needs no device. */
+lce_hip_status lce_hip_depthwise_conv2d_f32_check(const lce_hip_depthwise_desc* desc, int32_t* out_height, int32_t* out_width);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

@@ -103,15 +103,41 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   section that reads the result as the launch's bit output; the float tensor itself is written only when something else
  *   reads it or the section delivers it; filter and bias are uploaded once per model.  Together with the element-wise and
  *   pool flags the body of a Bi-RealNet-style or dense network is one section.
+ *
+ * struct_size == 56 is the fourth form: four more words after `reserved2`, which must be zero too, and one more bit in
+ * `sections_ext` (the 40-byte form promises that sections_ext & 4 is refused, and still refuses it; nothing past its 40 bytes
+ * is read).  This form ends the growth of the struct: bits of `sections_ext` that this version does not know are refused, but
+ * they are NOT promised to stay refused -- a later version may assign them at this size.  Only bit 31 is reserved forever.
+ *   LCE_TFLITE_SECTIONS_EXT_DEPTHWISE: the same for the float DEPTHWISE_CONV_2D of QuickNet's transition block (ReLU ->
+ *   MAX_POOL_2D -> the fixed 3x3 / 2 blur -> CONV_2D 1x1).  A DEPTHWISE_CONV_2D (4) joins the LCE epoch in which it becomes
+ *   ready when it has 2 or 3 inputs (a third input of -1: no bias) and one output; input, filter and output are float32, and
+ *   the bias when present; the output is 4-D with positive extents; the data input is a non-constant 4-D tensor; the filter
+ *   is a constant [1, fh, fw, Cout] with data in the file; the bias is absent or a constant [Cout]; the
+ *   DepthwiseConv2DOptions table is present; depth_multiplier >= 1 and Cout == Cin x depth_multiplier == the output's
+ *   channels; the strides are positive, the dilations 1, the padding SAME or VALID, the fused activation NONE / RELU /
+ *   RELU_N1_TO_1 / RELU6; the declared output height and width are what the padding rule gives; and
+ *   lce_hip_depthwise_conv2d_f32_check accepts the descriptor.  A depthwise convolution that is ready from the start
+ *   (QuickNet's stem) is the host's, and so is everything else: int8 or hybrid weights, a non-constant filter, a dilation,
+ *   TANH / SIGN_BIT, a missing options table.  lce_tflite_model_run_section runs such a convolution as one
+ *   lce_hip_depthwise_conv2d_f32 launch (its arithmetic: include/lce_hip.h), with the first LceQuantize of the section that
+ *   reads the result as the launch's bit output; the float tensor itself is written only when something else reads it or the
+ *   section delivers it; filter and bias are uploaded once per model.  Together with the element-wise, pool and 1x1 flags a
+ *   QuickNet body is one section.
  * The flags of both words combine. */
 enum { LCE_TFLITE_SECTIONS_CONCAT = 4u };
-enum { LCE_TFLITE_SECTIONS_EXT_POOL = 1u, LCE_TFLITE_SECTIONS_EXT_CONV1X1 = 2u /* the 40-byte form only */ };
+enum {
+  LCE_TFLITE_SECTIONS_EXT_POOL = 1u,
+  LCE_TFLITE_SECTIONS_EXT_CONV1X1 = 2u,  /* the 40- and 56-byte forms only */
+  LCE_TFLITE_SECTIONS_EXT_DEPTHWISE = 4u /* the 56-byte form only */
+};
 typedef struct lce_tflite_open_options {
-  uint32_t struct_size;    /* 8 (the first two fields only), 24 (up to `reserved`) or sizeof(lce_tflite_open_options) == 40 */
+  uint32_t struct_size;    /* 8 (the first two fields only), 24 (up to `reserved`), 40 (up to `reserved2`) or
+                              sizeof(lce_tflite_open_options) == 56 */
   uint32_t sections;       /* LCE_TFLITE_SECTIONS_*: 0..7, every other bit refused */
-  uint32_t sections_ext;   /* LCE_TFLITE_SECTIONS_EXT_*; every other bit refused */
+  uint32_t sections_ext;   /* LCE_TFLITE_SECTIONS_EXT_*; every other bit refused (at 56 bytes: refused by THIS version, see above) */
   uint32_t reserved[3];    /* must be zero */
   uint32_t reserved2[4];   /* the 40-byte form: must be zero */
+  uint32_t reserved3[4];   /* the 56-byte form: must be zero */
 } lce_tflite_open_options;
 lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
                                              size_t err_len);
@@ -164,6 +190,11 @@ lce_hip_status lce_tflite_model_operator_pool2d(const lce_tflite_model* model, i
  * other operator.  Its fused activation is reported by lce_tflite_model_operator_activation. */
 lce_hip_status lce_tflite_model_operator_conv2d(const lce_tflite_model* model, int32_t index, int32_t options[5]);
 
+/* DepthwiseConv2DOptions of a builtin DEPTHWISE_CONV_2D, as the file says: options[0..5] = padding (0 SAME, 1 VALID), stride_w,
+ * stride_h, depth_multiplier, dilation_w_factor, dilation_h_factor (schema default 1).  {0, 0, 0, 0, 1, 1} when the options
+ * table is absent and for every other operator.  Its fused activation is reported by lce_tflite_model_operator_activation. */
+lce_hip_status lce_tflite_model_operator_depthwise(const lce_tflite_model* model, int32_t index, int32_t options[6]);
+
 /* Binary SECTIONS of a mixed graph.  A converted model interleaves builtin float operators (the stem, batch norms, adds,
  * the head) with LCE custom ops; what this library runs are the maximal groups of LCE ops that can execute without a
  * builtin operator in between -- the partition a TFLite delegate would be handed (TensorFlow Lite's
@@ -200,7 +231,7 @@ lce_hip_status lce_tflite_model_section(const lce_tflite_model* model, int32_t i
  * LceQuantize of the same section writes both tensors from one epilogue (lce_hip_bconv2d_run_dual), the quantize launch
  * disappears.  Asynchronous on `stream` (a hipStream_t, or NULL); calls on one model are serialised by a mutex and must
  * use one stream at a time.  `semantics`: lce_hip_semantics (which registration's SAME-zero behaviour).  Shape inference
- * is the ops' own Prepare (quantization.cc:19-41, bmaxpool.cc:41-77, bconv2d.cc:137-300; an absorbed pool: the padding rule; an absorbed CONV_2D: ceil(in / stride)). */
+ * is the ops' own Prepare (quantization.cc:19-41, bmaxpool.cc:41-77, bconv2d.cc:137-300; an absorbed pool: the padding rule; an absorbed CONV_2D: ceil(in / stride); an absorbed DEPTHWISE_CONV_2D: the padding rule). */
 lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t section, int32_t batch, int32_t semantics,
                                             const void* const* inputs_dev, void* const* outputs_dev, void* stream);
 /* Shape ([N,H,W,C], C in words for bitpacked tensors) and size in bytes of a tensor section `section` reads or produces,
@@ -227,6 +258,9 @@ void lce_tflite_model_pool_stats(lce_tflite_model* model, int32_t* launches, int
 /* The LAST run's lce_hip_conv1x1_f32 launches (LCE_TFLITE_SECTIONS_EXT_CONV1X1): launches (one per absorbed CONV_2D) and
  * LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
 void lce_tflite_model_conv1x1_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's lce_hip_depthwise_conv2d_f32 launches (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE): launches (one per absorbed
+ * DEPTHWISE_CONV_2D) and LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
+void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
