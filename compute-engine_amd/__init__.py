@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
     "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
-    "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check",
+    "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -110,6 +110,12 @@ class DepthwiseDesc(C.Structure):
                                          "filter_width", "stride_height", "stride_width", "padding", "activation")]
 
 
+class Conv2dDesc(C.Structure):
+    """``lce_hip_conv2d_desc``."""
+    _fields_ = [(n, C.c_int32) for n in ("batch", "in_height", "in_width", "channels_in", "channels_out", "filter_height",
+                                         "filter_width", "stride_height", "stride_width", "padding", "activation")]
+
+
 _lib = None
 
 
@@ -164,6 +170,8 @@ def lib() -> C.CDLL:
         l.lce_hip_conv1x1_f32_check.argtypes = [C.POINTER(Conv1x1Desc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_depthwise_conv2d_f32.argtypes = [C.POINTER(DepthwiseDesc)] + [C.c_void_p] * 6
         l.lce_hip_depthwise_conv2d_f32_check.argtypes = [C.POINTER(DepthwiseDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_conv2d_f32.argtypes = [C.POINTER(Conv2dDesc)] + [C.c_void_p] * 6
+        l.lce_hip_conv2d_f32_check.argtypes = [C.POINTER(Conv2dDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -831,6 +839,58 @@ def depthwise_conv2d(x, filter, bias=None, stride=1, padding=PADDING_SAME, depth
     with torch.cuda.device(dev):
         check(lib().lce_hip_depthwise_conv2d_f32(C.byref(desc), _dev_ptr(xd), _dev_ptr(fd), _dev_ptr(bd), _dev_ptr(out_d),
                                                  _dev_ptr(bits_d), C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+
+
+def _conv2d_check(x, w, bias, stride, padding, activation, out, out_bits):
+    """Argument checks of ``conv2d`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (Conv2dDesc, output shape)."""
+    who = "conv2d"
+    if _dtype_name(x) != "float32" or len(x.shape) != 4 or min(x.shape) < 1:
+        raise ValueError("%s: x must be a non-empty float32 NHWC tensor, got %s %r" % (who, x.dtype, tuple(x.shape)))
+    b, h, wd, cin = (int(v) for v in x.shape)
+    ws = tuple(int(v) for v in w.shape)
+    if _dtype_name(w) != "float32" or len(ws) != 4 or ws[3] != cin or min(ws) < 1:
+        raise ValueError("%s: w must be float32 [Cout, fh, fw, %d], got %s %r" % (who, cin, w.dtype, ws))
+    cout, fh, fw = ws[0], ws[1], ws[2]
+    if fh * fw * cin >= 1 << 31:
+        raise ValueError("%s: a filter of 2^31 or more elements per output channel is not supported, got %r" % (who, ws))
+    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (cout,)):
+        raise ValueError("%s: bias must be float32 [%d], got %s %r" % (who, cout, bias.dtype, tuple(bias.shape)))
+    sh, sw = _pair(who, "stride", stride)
+    if padding not in (PADDING_SAME, PADDING_VALID):
+        raise ValueError("%s: padding must be PADDING_SAME or PADDING_VALID, got %r" % (who, padding))
+    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
+        raise ValueError("%s: unknown activation %r" % (who, activation))
+    oh, ow = pool2d_output_hw((h, wd), (fh, fw), (sh, sw), padding)
+    if oh < 1 or ow < 1:
+        raise ValueError("%s: empty output (a VALID filter of %d x %d on an image of %d x %d)" % (who, fh, fw, h, wd))
+    shape = (b, oh, ow, cout)
+    _check_outputs(who, None if out is True else out, None if out_bits is False else out_bits, "float32", shape)
+    return Conv2dDesc(b, h, wd, cin, cout, fh, fw, sh, sw, int(padding), int(activation)), shape
+
+
+def conv2d(x, w, bias=None, stride=1, padding=PADDING_SAME, activation=ACT_NONE, out=True, out_bits=False, stream: int | None = None):
+    """TFLite's builtin float CONV_2D with a filter of any extent (a network's stem, or a float KxK convolution between binary
+    layers) and the LceQuantize of its result, in one call (``lce_hip_conv2d_f32``).  ``x``: float32 NHWC on the device (or
+    NumPy: copied to cuda:0 and back).  ``w``: float32 [Cout, fh, fw, Cin].  ``bias``: float32 [Cout] or None.  ``stride``: an
+    int or (height, width).  ``padding``: ``PADDING_SAME`` / ``PADDING_VALID`` with the pools' rule (taps in the padding are
+    skipped).  ``activation``: ``ACT_*``.  Per output element t = fmaf(x, w, t) over its in-bounds taps in raster order and the
+    channels of a tap in order, from +0.0, then + bias, then the clamp: exact bytes (include/lce_hip.h).  ``out``: True for a
+    new tensor, a tensor to fill (it must not overlap an operand), False for none.  ``out_bits``: True for new int32
+    [B, OH, OW, ceil(Cout/32)] bits (value < 0), a tensor to fill, False for none.  Returns ``(out or None, bits or None)``."""
+    desc, shape = _conv2d_check(x, w, bias, stride, padding, activation, out, out_bits)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "conv2d", "x's")
+    xd, wd = on_dev(x), on_dev(w)
+    bd = None if bias is None else on_dev(bias)
+    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if (out is True or out is None) else on_dev(out)
+    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_conv2d_f32(C.byref(desc), _dev_ptr(xd), _dev_ptr(wd), _dev_ptr(bd), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                       C.c_void_p(_stream_or_current(stream, dev))))
     return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
 
 

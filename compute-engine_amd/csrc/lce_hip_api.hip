@@ -23,6 +23,7 @@
 #include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
 #include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
 #include "lce_kernels_depthwise.h"   // (lce_tu_depthwise.hip)
+#include "lce_kernels_conv2d.h"      // (lce_tu_conv2d.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -45,6 +46,7 @@
 #include "lce_tu_pool.hip"
 #include "lce_tu_conv1x1.hip"
 #include "lce_tu_depthwise.hip"
+#include "lce_tu_conv2d.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -1099,6 +1101,90 @@ lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* d, con
     p.div_per_pixel = lce::make_fastdiv(p.per_pixel);
   }
   const int e = lce::launch_depthwise(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// float CONV_2D of any filter extent (lce_kernels_conv2d.h)
+// ------------------------------------------------------------------------------------
+lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* d, int32_t* out_height, int32_t* out_width) {
+  const char* who = "lce_hip_conv2d_f32";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels_in <= 0 || d->channels_out <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d] -> %d channels", who, (int)d->batch,
+                (int)d->in_height, (int)d->in_width, (int)d->channels_in, (int)d->channels_out);
+  if (d->filter_height <= 0 || d->filter_width <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the filter must be positive, got %d x %d", who, (int)d->filter_height, (int)d->filter_width);
+  if (d->stride_height <= 0 || d->stride_width <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)d->stride_height, (int)d->stride_width);
+  if (d->padding != LCE_HIP_PADDING_SAME && d->padding != LCE_HIP_PADDING_VALID)
+    return fail(LCE_HIP_ERR_INVALID, "%s: padding must be SAME or VALID, got %d", who, (int)d->padding);
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  // (the kernels' window arithmetic, oy * stride - pad + filter, is 32-bit: with these bounds it stays below 2^31)
+  if (std::max(d->in_height, d->in_width) > (1 << 30) || std::max(d->stride_height, d->stride_width) > (1 << 30))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  // (K = fh x fw x Cin -- and with it each filter extent -- stays below 2^31; compared by division, so that the product of
+  // three 31-bit factors is never formed)
+  const uint64_t taps = (uint64_t)d->filter_height * (uint64_t)d->filter_width;
+  if ((uint64_t)d->channels_in > ((1ull << 31) - 1) / taps)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: a filter of 2^31 or more elements per output channel (%d x %d x %d) is not supported", who,
+                (int)d->filter_height, (int)d->filter_width, (int)d->channels_in);
+  // (one grid row per 128 output channels)
+  if ((int64_t)d->channels_out > 65535ll * lce::kConv2dBN)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: more than %lld output channels are not supported", who, 65535ll * lce::kConv2dBN);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = lce_hip_bmaxpool_output_shape(d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height,
+                                                      d->stride_width, d->padding, &oh, &ow)) return s;
+  if (oh <= 0 || ow <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: empty output (a VALID filter of %d x %d on an image of %d x %d)", who, (int)d->filter_height,
+                (int)d->filter_width, (int)d->in_height, (int)d->in_width);
+  if ((uint64_t)d->batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* d, const float* in_dev, const float* filter_dev, const float* bias_dev,
+                                  float* out_dev, int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_conv2d_f32";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!filter_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = lce_hip_conv2d_f32_check(d, &oh, &ow)) return s;
+  const uint64_t Cin = (uint64_t)d->channels_in, N = (uint64_t)d->channels_out;
+  const uint64_t K = (uint64_t)d->filter_height * d->filter_width * Cin;             // < 2^31
+  const uint64_t pixels = (uint64_t)d->batch * oh * ow, wpr = (N + 31) / 32;
+  // the outputs must not meet anything the launches read (another wave still reads what one would overwrite) or each other
+  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uint64_t)d->batch * d->in_height * d->in_width * Cin * 4;
+  const uintptr_t f0 = (uintptr_t)filter_dev, f1 = f0 + N * K * 4;
+  const uintptr_t c0 = (uintptr_t)bias_dev, c1 = c0 + (bias_dev ? N * 4 : 0);
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? pixels * N * 4 : 0);
+  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? pixels * wpr * 4 : 0);
+  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t e0, uintptr_t e1) { return a0 < e1 && e0 < a1; };
+  if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the input", who);
+  if (meet(o0, o1, f0, f1) || meet(b0, b1, f0, f1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the filter", who);
+  if (meet(o0, o1, c0, c1) || meet(b0, b1, c0, c1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the bias", who);
+  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "%s: the two outputs overlap", who);
+  if ((i0 | f0 | c0 | o0 | b0) % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::Conv2dArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.filter = filter_dev; a.bias = bias_dev; a.out = out_dev; a.bits = (uint32_t*)out_bits_dev;
+  lce::conv2d_geometry(a, d->batch, d->in_height, d->in_width, d->channels_in, d->channels_out, d->filter_height, d->filter_width,
+                       d->stride_height, d->stride_width, oh, ow);
+  switch (d->activation) {    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
+    case LCE_HIP_ACT_RELU: a.lo = 0.0f; a.hi = FLT_MAX; break;
+    case LCE_HIP_ACT_RELU_N1_TO_1: a.lo = -1.0f; a.hi = 1.0f; break;
+    case LCE_HIP_ACT_RELU6: a.lo = 0.0f; a.hi = 6.0f; break;
+    default: a.lo = -FLT_MAX; a.hi = FLT_MAX;
+  }
+  const bool vec = Cin % 4 == 0 && i0 % 16 == 0 && f0 % 16 == 0;
+  const int e = lce::launch_conv2d(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }

@@ -38,7 +38,7 @@ struct lce_tflite_model {
     int32_t conv_quantize = 0;                                          // LceQuantize launches folded into a convolution (run_dual)
     int32_t ew_ops = 0;                                                 // ADD / MUL operators inside the lce_hip_elementwise launches
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
-    Pass ew, add_i8, concat, pool, conv1x1, depthwise;                  // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat, lce_hip_pool2d, lce_hip_conv1x1_f32, lce_hip_depthwise_conv2d_f32
+    Pass ew, add_i8, concat, pool, conv1x1, depthwise, conv2d;          // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat, lce_hip_pool2d, lce_hip_conv1x1_f32, lce_hip_depthwise_conv2d_f32, lce_hip_conv2d_f32
   };
   RunStats last;                                                        // of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
@@ -320,7 +320,60 @@ bool DepthwiseCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   int32_t oh = 0, ow = 0;
   return lce_hip_depthwise_conv2d_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
 }
-enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3, kAbsorbedPool = 4, kAbsorbedConv1x1 = 5, kAbsorbedDepthwise = 6 };
+
+// lce_hip_conv2d_desc of a builtin CONV_2D at `batch` images, from its options and the FILE's input and filter tensors.
+lce_hip_conv2d_desc Conv2dDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  lce_hip_conv2d_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = batch; d.in_height = in.shape[1]; d.in_width = in.shape[2]; d.channels_in = in.shape[3];
+  d.channels_out = flt.shape[0];
+  d.filter_height = flt.shape[1]; d.filter_width = flt.shape[2];
+  d.stride_height = o.pool_stride_h; d.stride_width = o.pool_stride_w;
+  d.padding = o.pool_padding;
+  d.activation = o.activation;
+  return d;
+}
+
+// The static half of "a builtin CONV_2D that a section may run" (LCE_TFLITE_SECTIONS_EXT_CONV2D): the float convolution of a
+// network's stem, or one of any filter extent between binary layers.  The conditions of Conv1x1Candidate, except that the
+// filter is a constant [Cout, fh, fw, Cin] with fh, fw >= 1 (a grouped filter, shape[3] != Cin, is the host's) whose byte count
+// matches (compared by division: the product of the four extents is never formed); the declared output height and width are
+// what the padding rule gives; and lce_hip_conv2d_f32's own check accepts the descriptor.  The other half -- when it becomes
+// ready -- is decided by Partition().
+bool Conv2dCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinConv2d) return false;
+  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 || flt.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32) return false;
+  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
+  for (int k = 0; k < 4; ++k)
+    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
+  if (!flt.data || flt.shape.size() != 4 || flt.shape[0] <= 0 || flt.shape[1] <= 0 || flt.shape[2] <= 0 || flt.shape[3] != in.shape[3]) return false;
+  const int64_t cout = flt.shape[0];
+  // (fh x fw < 2^62, cout and cin < 2^31: compared by division, the product of the four is never formed)
+  const uint64_t taps = (uint64_t)flt.shape[1] * (uint64_t)flt.shape[2], cin = (uint64_t)flt.shape[3];
+  const uint64_t elems = (uint64_t)flt.bytes / 4u;
+  if ((uint64_t)flt.bytes % 4u != 0 || elems % taps != 0 || elems / taps % cin != 0 || elems / taps / cin != (uint64_t)cout) return false;
+  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
+    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
+    if (bias.type != lce_tfl::kTensorFloat32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != cout ||
+        (uint64_t)bias.bytes != (uint64_t)cout * 4u) return false;
+  }
+  if (out.shape[3] != cout) return false;
+  if (!o.has_conv_options) return false;
+  if (o.pool_stride_h <= 0 || o.pool_stride_w <= 0 || o.dilation_h != 1 || o.dilation_w != 1) return false;
+  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  const lce_hip_conv2d_desc d = Conv2dDesc(M, o, in.shape[0]);
+  int32_t oh = 0, ow = 0;
+  return lce_hip_conv2d_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
+}
+enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3, kAbsorbedPool = 4, kAbsorbedConv1x1 = 5, kAbsorbedDepthwise = 6,
+       kAbsorbedConv2d = 7 };
 }  // namespace
 
 // The partition a delegate would get (tensorflow/lite/graph_info.cc, PartitionGraphIntoIndependentNodeSubsets, restated from
@@ -341,7 +394,7 @@ void lce_tflite_model::Partition() {
     is_lce[i] = IsLceOp(m.operators[i]) ? 1 : 0;
     // LCE_TFLITE_SECTIONS_ELEMENTWISE: a float ADD / MUL joins the epoch in which it becomes ready, so it lands in a section
     // exactly when the last of its inputs was produced by an LCE epoch (one that is ready from the start -- a stem op -- is
-    // a builtin one)
+    // a builtin one without LCE_TFLITE_SECTIONS_EXT_STEM, below)
     if (flags & LCE_TFLITE_SECTIONS_ELEMENTWISE) candidate[i] = ElementwiseCandidate(m, m.operators[i]) ? kAbsorbedElementwise : 0;
     // LCE_TFLITE_SECTIONS_INT8_ADD: the same rule for the int8 ADD of a shortcut
     if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_INT8_ADD)) candidate[i] = Int8AddCandidate(m, m.operators[i]) ? kAbsorbedInt8Add : 0;
@@ -353,6 +406,9 @@ void lce_tflite_model::Partition() {
     if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_CONV1X1)) candidate[i] = Conv1x1Candidate(m, m.operators[i]) ? kAbsorbedConv1x1 : 0;
     // LCE_TFLITE_SECTIONS_EXT_DEPTHWISE: the same rule for the float DEPTHWISE_CONV_2D of QuickNet's transition
     if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_DEPTHWISE)) candidate[i] = DepthwiseCandidate(m, m.operators[i]) ? kAbsorbedDepthwise : 0;
+    // LCE_TFLITE_SECTIONS_EXT_CONV2D: the same rule for a float CONV_2D of any filter extent (Conv1x1Candidate was tried first: with
+    // both bits a 1x1 filter runs as before)
+    if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_CONV2D)) candidate[i] = Conv2dCandidate(m, m.operators[i]) ? kAbsorbedConv2d : 0;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -366,8 +422,11 @@ void lce_tflite_model::Partition() {
     if (valid(t)) is_output[t] = 1;
   // ready operators of either kind, waiting for their epoch
   std::vector<int32_t> queue[2];
+  // (a candidate ready from the start is a builtin op -- the stem is the host's -- unless LCE_TFLITE_SECTIONS_EXT_STEM queues it
+  // with the LCE operators: a stem of candidates then joins the first LCE epoch, and a section need not hold an LCE operator)
+  const bool stem = (flags_ext & LCE_TFLITE_SECTIONS_EXT_STEM) != 0;
   for (int i = 0; i < n_ops; ++i)
-    if (unready[i] == 0) queue[(int)is_lce[i]].push_back(i);   // (a candidate ready from the start is a builtin op)
+    if (unready[i] == 0) queue[is_lce[i] || (stem && candidate[i]) ? 1 : 0].push_back(i);
   std::vector<int32_t> section_of(n_ops, -1);
   std::vector<char> made(n_t, 0), listed(n_t, 0);
   int remaining = n_ops;
@@ -487,7 +546,9 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
       ext = words[2];
       allowed_ext = LCE_TFLITE_SECTIONS_EXT_POOL;
       if (words[0] != kSecondForm) allowed_ext |= LCE_TFLITE_SECTIONS_EXT_CONV1X1;
-      if (words[0] != kSecondForm && words[0] != kThirdForm) allowed_ext |= LCE_TFLITE_SECTIONS_EXT_DEPTHWISE;
+      // (the fourth form also carries the bits assigned after it: none of them widens the struct)
+      if (words[0] != kSecondForm && words[0] != kThirdForm)
+        allowed_ext |= LCE_TFLITE_SECTIONS_EXT_DEPTHWISE | LCE_TFLITE_SECTIONS_EXT_CONV2D | LCE_TFLITE_SECTIONS_EXT_STEM;
       uint32_t rest = 0;
       for (uint32_t k = 3; k < words[0] / 4; ++k) rest |= words[k];
       if (rest) refusal = "options: reserved fields must be zero";
@@ -830,7 +891,7 @@ struct Walk {
     return LCE_HIP_OK;
   }
 
-  // Where the result of a fused pass (an ADD / MUL chain, an int8 ADD, a CONCATENATION, a pool, a 1x1 or depthwise convolution) goes.
+  // Where the result of a fused pass (an ADD / MUL chain, an int8 ADD, a CONCATENATION, a pool, a 1x1, depthwise or KxK convolution) goes.
   struct Fold {
     int32_t value_t;                     // the tensor the pass produces
     int32_t bits_t = -1;                 // the output of the folded LceQuantize; -1: none
@@ -1148,6 +1209,42 @@ struct Walk {
     return LCE_HIP_OK;
   }
 
+  // An absorbed float CONV_2D of any filter extent (LCE_TFLITE_SECTIONS_EXT_CONV2D) as ONE lce_hip_conv2d_f32 call, checked, folded
+  // and fed as Conv1x1 above.
+  lce_hip_status Conv2d(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
+    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    auto it = shapes.find(op.inputs[0]);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONV_2D reads a tensor nothing produced");
+    if (!Agrees(it->second, lce_tfl::kTensorFloat32, is[1], is[2], is[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONV_2D input's shape or type does not match the one its producer infers");
+    const lce_hip_conv2d_desc d = Conv2dDesc(M, op, batch);
+    Shape os;
+    os.dims[0] = batch; os.dims[3] = d.channels_out;
+    os.type = lce_tfl::kTensorFloat32;
+    if (lce_hip_status s = lce_hip_conv2d_f32_check(&d, &os.dims[1], &os.dims[2])) return s;
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(op.inputs[0], "a CONV_2D input", &in)) return s;
+    const float *filter = nullptr, *bias = nullptr;
+    if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &filter)) return s;
+    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = lce_hip_conv2d_f32(&d, (const float*)in, filter, bias, (float*)out, (int32_t*)bits, stream)) return s;
+    ++model->last.conv2d.launches;
+    if (fold.bits_t >= 0) ++model->last.conv2d.quantize;
+    return LCE_HIP_OK;
+  }
+
   // The four LCE operators.  `in` is the inferred shape of operator `i`'s first input, `in_dev` its device pointer (with `run`).
   lce_hip_status Quantize(int32_t i, const Shape& in, const void* in_dev) {                      // quantization.cc:19-41,76-114
     const lce_tfl::Operator& op = model->m.operators[i];
@@ -1279,6 +1376,7 @@ struct Walk {
         case kAbsorbedPool: s = Pool2d(i); break;
         case kAbsorbedConv1x1: s = Conv1x1(i); break;
         case kAbsorbedDepthwise: s = Depthwise(i); break;
+        case kAbsorbedConv2d: s = Conv2d(i); break;
         default: s = LceOp(i);
       }
       if (s) return s;
@@ -1420,6 +1518,13 @@ void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches
   std::lock_guard<std::mutex> lock(model->run_mu);
   if (launches) *launches = model->last.depthwise.launches;
   if (quantize_folded) *quantize_folded = model->last.depthwise.quantize;
+}
+
+void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (launches) *launches = model->last.conv2d.launches;
+  if (quantize_folded) *quantize_folded = model->last.conv2d.quantize;
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

@@ -31,6 +31,10 @@ a Bi-RealNet-style or dense network is one section.
 With ``depthwise_sections=True`` (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, the 56-byte options) the float DEPTHWISE_CONV_2D of
 QuickNet's transition block (its 3x3 / 2 blur) joins them (``lce_hip_depthwise_conv2d_f32``); with the element-wise, pool and 1x1
 flags a QuickNet body is one section.
+With ``conv2d_sections=True`` (LCE_TFLITE_SECTIONS_EXT_CONV2D, the 56-byte options) a float CONV_2D of any filter extent joins
+them (``lce_hip_conv2d_f32``), and with ``stem_sections=True`` (LCE_TFLITE_SECTIONS_EXT_STEM) an operator that qualifies under an
+enabled flag and is ready from the start joins the first section instead of staying with the host: with every flag the stem and
+the body of a converted network are ONE section fed by the image, which ``predict`` runs; only the head stays with the host.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -53,6 +57,8 @@ SECTIONS_CONCAT = 4               # LCE_TFLITE_SECTIONS_CONCAT (lce_tflite_model
 SECTIONS_EXT_POOL = 1             # LCE_TFLITE_SECTIONS_EXT_POOL (sections_ext of the 24-byte options)
 SECTIONS_EXT_CONV1X1 = 2          # LCE_TFLITE_SECTIONS_EXT_CONV1X1 (sections_ext of the 40-byte options)
 SECTIONS_EXT_DEPTHWISE = 4        # LCE_TFLITE_SECTIONS_EXT_DEPTHWISE (sections_ext of the 56-byte options)
+SECTIONS_EXT_CONV2D = 8           # LCE_TFLITE_SECTIONS_EXT_CONV2D (sections_ext of the 56-byte options)
+SECTIONS_EXT_STEM = 16            # LCE_TFLITE_SECTIONS_EXT_STEM (sections_ext of the 56-byte options)
 _NP = {FLOAT32: np.float32, INT32: np.int32, BOOL: np.bool_, INT8: np.int8}
 LCE_OPS = ("LceQuantize", "LceDequantize", "LceBconv2d", "LceBMaxPool2d")
 
@@ -132,6 +138,8 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_operator_depthwise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_depthwise_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
         l.lce_tflite_model_depthwise_stats.restype = None
+        l.lce_tflite_model_conv2d_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
+        l.lce_tflite_model_conv2d_stats.restype = None
         l.lce_tflite_model_operator_axis.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_concat_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
         l.lce_tflite_model_concat_stats.restype = None
@@ -204,7 +212,8 @@ class LceModel:
 
     def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
                  int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
-                 conv1x1_sections: bool = False, depthwise_sections: bool = False):
+                 conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
+                 stem_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -213,7 +222,10 @@ class LceModel:
         24-byte options of ``lce_tflite_model_open_opts``).  ``conv1x1_sections``: the float 1x1 CONV_2D of a transition block or a
         downsampling shortcut joins them (LCE_TFLITE_SECTIONS_EXT_CONV1X1, through the 40-byte options).  ``depthwise_sections``: the
         float DEPTHWISE_CONV_2D of QuickNet's transition block joins them (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, through the 56-byte
-        options, which no other combination of flags uses)."""
+        options).  ``conv2d_sections``: a float CONV_2D of any filter extent -- a network's stem -- joins them
+        (LCE_TFLITE_SECTIONS_EXT_CONV2D).  ``stem_sections``: an operator that qualifies under an enabled flag and is ready from
+        the start joins the first section instead of staying with the host (LCE_TFLITE_SECTIONS_EXT_STEM).  Both are bits of the
+        56-byte options, which no combination of the other flags without ``depthwise_sections`` uses."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -224,11 +236,14 @@ class LceModel:
         self.pool_sections = bool(pool_sections)
         self.conv1x1_sections = bool(conv1x1_sections)
         self.depthwise_sections = bool(depthwise_sections)
+        self.conv2d_sections = bool(conv2d_sections)
+        self.stem_sections = bool(stem_sections)
         err = C.create_string_buffer(256)
         flags = (SECTIONS_ELEMENTWISE if elementwise_sections else 0) | (SECTIONS_INT8_ADD if int8_add_sections else 0)
-        if depthwise_sections:
+        if depthwise_sections or conv2d_sections or stem_sections:
             opts = _OpenOptions56(C.sizeof(_OpenOptions56), flags | (SECTIONS_CONCAT if concat_sections else 0),
-                                  SECTIONS_EXT_DEPTHWISE | (SECTIONS_EXT_CONV1X1 if conv1x1_sections else 0) |
+                                  (SECTIONS_EXT_DEPTHWISE if depthwise_sections else 0) | (SECTIONS_EXT_CONV2D if conv2d_sections else 0) |
+                                  (SECTIONS_EXT_STEM if stem_sections else 0) | (SECTIONS_EXT_CONV1X1 if conv1x1_sections else 0) |
                                   (SECTIONS_EXT_POOL if pool_sections else 0))
             self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
         elif conv1x1_sections:
@@ -344,6 +359,12 @@ class LceModel:
         tflite_lib().lce_tflite_model_depthwise_stats(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
+    def conv2d_stats(self):
+        """(lce_hip_conv2d_f32 calls, LceQuantize launches they absorbed) of the last run."""
+        a, b = C.c_int32(), C.c_int32()
+        tflite_lib().lce_tflite_model_conv2d_stats(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -374,18 +395,20 @@ class Interpreter:
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
                  use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
                  concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
-                 depthwise_sections: bool = False):
-        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+                 depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False):
+        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
+        ``conv2d_sections``, ``stem_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
                                     int8_add_sections=int8_add_sections, concat_sections=concat_sections,
                                     pool_sections=pool_sections, conv1x1_sections=conv1x1_sections,
-                                    depthwise_sections=depthwise_sections))
+                                    depthwise_sections=depthwise_sections, conv2d_sections=conv2d_sections,
+                                    stem_sections=stem_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections or self.model.pool_sections or self.model.conv1x1_sections or self.model.depthwise_sections:
+        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections or self.model.pool_sections or self.model.conv1x1_sections or self.model.depthwise_sections or self.model.conv2d_sections or self.model.stem_sections:
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

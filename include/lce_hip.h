@@ -353,6 +353,48 @@ lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* desc, 
 lce_hip_status lce_hip_depthwise_conv2d_f32_check(const lce_hip_depthwise_desc* desc, int32_t* out_height, int32_t* out_width);
 
 /* ------------------------------------------------------------------------------------
+ * The float CONV_2D of any filter extent (TFLite builtin CONV_2D: a network's stem) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* Every converted network opens with a float convolution: QuickNet 3x3 / 2, Bi-RealNet / BinaryResNetE / BinaryDenseNet
+ * 7x7 / 2, BinaryAlexNet 11x11 / 4.  lce_hip_conv2d_f32 is TFLite's float reference_ops::Conv over an NHWC float32 tensor
+ * [batch, in_height, in_width, channels_in] with the filter in the file's own layout [channels_out][filter_height]
+ * [filter_width][channels_in] and an optional bias [channels_out], in ONE call.  groups is 1 and the dilation is 1.  The
+ * output is [batch, out_height, out_width, channels_out]; its extents and the padding are exactly lce_hip_pool2d's and
+ * lce_hip_depthwise_conv2d_f32's (lce_hip_bmaxpool_output_shape; pad_before = total / 2).
+ * As for lce_hip_conv1x1_f32 the library states its own bytes: the reference as a CONTRACTING build computes it.  Per output
+ * element, over its in-bounds taps in raster order (filter row, then filter column) and within a tap over
+ * c = 0 .. channels_in - 1 in order -- taps in the padding are SKIPPED, not read as zero, and the filter index is the
+ * unclipped one:
+ *   t = +0.0f;  t = fmaf(x[iy][ix][c], w[o][fy][fx][c], t)   one rounding per step, never reassociated, never split over K
+ *   t = t + bias[o]                                          one float32 add; skipped when bias_dev is NULL
+ *   v = min(max(t, act_min), act_max)                        the clamp of lce_hip_pool2d (NONE: [-FLT_MAX, FLT_MAX]; a NaN passes)
+ * Subnormals are not flushed, going in or coming out; NaN and infinity flow through the chain.  For a 1x1 filter the bytes are
+ * those of lce_hip_conv1x1_f32.  Output pixels whose window lies inside the image run the chain on the f32-input matrix
+ * instruction, whose result is such a chain bit for bit; pixels with a clipped window run it as fmaf, tap by tap.
+ * `out_dev` (nullable) gets the result; `out_bits_dev` (nullable) gets its LceQuantize as lce_hip_bitpack(F32, out, ...)
+ * writes it: bit = v < 0, LSB first, ceil(channels_out/32) words per pixel, padding bits 0 -- from the values the pass holds.
+ * Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc, input or filter, both outputs NULL, an extent, channel
+ * count, filter or stride <= 0, an unknown padding or activation, an empty output, an output that overlaps the input, the
+ * filter, the bias or the other output, a pointer that is not 4-byte aligned; LCE_HIP_ERR_UNSUPPORTED: 2^31 or more output
+ * pixels, an image extent or a stride above 2^30, filter_height x filter_width x channels_in >= 2^31, more than 65535 x 128
+ * output channels.
+ * Pointers need 4-byte alignment only (16-byte aligned input and filter with channels_in % 4 == 0 take a faster load path);
+ * the byte counts are unbounded (64-bit offsets throughout).  Asynchronous on `stream` (up to two launches), capturable in a
+ * HIP graph, allocates nothing and copies nothing between host and device. */
+typedef struct lce_hip_conv2d_desc {
+  int32_t batch, in_height, in_width, channels_in, channels_out;
+  int32_t filter_height, filter_width, stride_height, stride_width;
+  int32_t padding;      /* lce_hip_padding: SAME or VALID */
+  int32_t activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+} lce_hip_conv2d_desc;
+lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* desc, const float* in_dev, const float* filter_dev /* [Cout][fh][fw][Cin] */,
+                                  const float* bias_dev /* nullable */, float* out_dev /* nullable */,
+                                  int32_t* out_bits_dev /* nullable */, void* stream);
+/* The descriptor checks of lce_hip_conv2d_f32 alone, and the output extents (nullable).  Host only: needs no device. */
+lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* desc, int32_t* out_height, int32_t* out_width);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

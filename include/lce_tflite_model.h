@@ -60,7 +60,7 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   output is 4-D and the axis is 3 or -1, its fused activation is NONE, every input is a non-constant 4-D tensor of the
  *   output's height and width, the inputs' channels add up to the output's, and -- for int8 -- all inputs and the output
  *   carry quantization parameters with the SAME scale and zero point (a requantizing join stays with the host).  A join
- *   that is ready from the start is the host's.  lce_tflite_model_run_section runs such a join as one lce_hip_concat
+ *   that is ready from the start is the host's (without LCE_TFLITE_SECTIONS_EXT_STEM).  lce_tflite_model_run_section runs such a join as one lce_hip_concat
  *   launch, with the first LceQuantize of the section that reads the joined tensor as the launch's bit output; the joined
  *   tensor itself is written only when something else reads it or the section delivers it.  Together with
  *   LCE_TFLITE_SECTIONS_ELEMENTWISE a float dense block is one section; the float MAX_POOL_2D / CONV_2D of a transition
@@ -80,7 +80,7 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   stays with the host) --, filter and stride are positive, the padding is SAME or VALID, the fused activation is NONE /
  *   RELU / RELU_N1_TO_1 / RELU6, the file's declared output height and width are what the padding rule gives for the
  *   declared input, and lce_hip_pool2d_check accepts the descriptor.  A pool that is ready from the start (a stem pool)
- *   is the host's.  lce_tflite_model_run_section runs such a pool as one lce_hip_pool2d launch, with the first LceQuantize
+ *   is the host's without LCE_TFLITE_SECTIONS_EXT_STEM.  lce_tflite_model_run_section runs such a pool as one lce_hip_pool2d launch, with the first LceQuantize
  *   of the section that reads the pooled tensor as the launch's bit output; the pooled tensor itself is written only when
  *   something else reads it or the section delivers it.  Together with LCE_TFLITE_SECTIONS_ELEMENTWISE the body of a
  *   BinaryAlexNet is one section.  L2 pooling, a CONV_2D and bitpacked pooling (LceBMaxPool2d, an LCE operator already)
@@ -97,7 +97,8 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   constant [Cout]; Cout is the output's channels; the Conv2DOptions table is present, the strides are positive, the
  *   dilations 1, the padding SAME or VALID, the fused activation NONE / RELU / RELU_N1_TO_1 / RELU6; the declared output
  *   height and width are ceil(in / stride); and lce_hip_conv1x1_f32_check accepts the descriptor.  A convolution that is
- *   ready from the start (a stem) is the host's, and so is everything else: a 3x3 filter, int8 or hybrid weights, a
+ *   ready from the start (a stem) is the host's without LCE_TFLITE_SECTIONS_EXT_STEM, and so is everything else: a 3x3 filter (it
+ *   joins with LCE_TFLITE_SECTIONS_EXT_CONV2D), int8 or hybrid weights, a
  *   non-constant filter, DEPTHWISE_CONV_2D, TANH / SIGN_BIT, a missing options table.  lce_tflite_model_run_section runs such
  *   a convolution as one lce_hip_conv1x1_f32 launch (its arithmetic: include/lce_hip.h), with the first LceQuantize of the
  *   section that reads the result as the launch's bit output; the float tensor itself is written only when something else
@@ -117,18 +118,36 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   channels; the strides are positive, the dilations 1, the padding SAME or VALID, the fused activation NONE / RELU /
  *   RELU_N1_TO_1 / RELU6; the declared output height and width are what the padding rule gives; and
  *   lce_hip_depthwise_conv2d_f32_check accepts the descriptor.  A depthwise convolution that is ready from the start
- *   (QuickNet's stem) is the host's, and so is everything else: int8 or hybrid weights, a non-constant filter, a dilation,
+ *   (QuickNet's stem) is the host's without LCE_TFLITE_SECTIONS_EXT_STEM, and so is everything else: int8 or hybrid weights, a non-constant filter, a dilation,
  *   TANH / SIGN_BIT, a missing options table.  lce_tflite_model_run_section runs such a convolution as one
  *   lce_hip_depthwise_conv2d_f32 launch (its arithmetic: include/lce_hip.h), with the first LceQuantize of the section that
  *   reads the result as the launch's bit output; the float tensor itself is written only when something else reads it or the
  *   section delivers it; filter and bias are uploaded once per model.  Together with the element-wise, pool and 1x1 flags a
  *   QuickNet body is one section.
+ * Two bits assigned later at the 56-byte size (the 24- and 40-byte forms refuse them):
+ *   LCE_TFLITE_SECTIONS_EXT_CONV2D: the same for a float CONV_2D of ANY filter extent -- the first operator of every converted
+ *   network (QuickNet 3x3 / 2, Bi-RealNet / BinaryResNetE / BinaryDenseNet 7x7 / 2, BinaryAlexNet 11x11 / 4).  A CONV_2D (3)
+ *   joins the LCE epoch in which it becomes ready under the conditions of LCE_TFLITE_SECTIONS_EXT_CONV1X1, except that the
+ *   filter is a constant [Cout, fh, fw, Cin] with fh, fw >= 1 whose byte count matches, the declared output height and width
+ *   are what the padding rule gives, and lce_hip_conv2d_f32_check accepts the descriptor.  A grouped filter (shape[3] != Cin),
+ *   int8 or hybrid weights, a non-constant filter or bias, a dilation, TANH / SIGN_BIT and a missing options table stay with
+ *   the host.  LCE_TFLITE_SECTIONS_EXT_CONV1X1 is tried first: with both bits a 1x1 filter runs exactly as before, with this
+ *   bit alone it runs on lce_hip_conv2d_f32 (the same bytes).  lce_tflite_model_run_section runs such a convolution as one
+ *   lce_hip_conv2d_f32 call, folded and fed as the 1x1 convolution is.
+ *   LCE_TFLITE_SECTIONS_EXT_STEM: an operator that qualifies under any ENABLED opt-in and whose inputs are all ready at the
+ *   start (model inputs and constants) is queued with the LCE operators instead of the builtin ones.  Nothing else in the
+ *   partition changes.  A stem of such operators therefore joins the first LCE epoch: stem and body are one section whose
+ *   input is the model's input tensor, and a section need not contain an LCE operator.  A stem operator that does not qualify
+ *   (QUANTIZE, PAD, a uint8 input) still opens a builtin epoch, and what it feeds joins later by the rules above.  After both
+ *   bits only the classifier head (MEAN, FULLY_CONNECTED, SOFTMAX) of a converted network is the host's.
  * The flags of both words combine. */
 enum { LCE_TFLITE_SECTIONS_CONCAT = 4u };
 enum {
   LCE_TFLITE_SECTIONS_EXT_POOL = 1u,
   LCE_TFLITE_SECTIONS_EXT_CONV1X1 = 2u,  /* the 40- and 56-byte forms only */
-  LCE_TFLITE_SECTIONS_EXT_DEPTHWISE = 4u /* the 56-byte form only */
+  LCE_TFLITE_SECTIONS_EXT_DEPTHWISE = 4u, /* the 56-byte form only */
+  LCE_TFLITE_SECTIONS_EXT_CONV2D = 8u,    /* the 56-byte form only */
+  LCE_TFLITE_SECTIONS_EXT_STEM = 16u      /* the 56-byte form only */
 };
 typedef struct lce_tflite_open_options {
   uint32_t struct_size;    /* 8 (the first two fields only), 24 (up to `reserved`), 40 (up to `reserved2`) or
@@ -261,6 +280,9 @@ void lce_tflite_model_conv1x1_stats(lce_tflite_model* model, int32_t* launches, 
 /* The LAST run's lce_hip_depthwise_conv2d_f32 launches (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE): launches (one per absorbed
  * DEPTHWISE_CONV_2D) and LceQuantize operators whose launch they absorbed.  Any pointer may be NULL. */
 void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's lce_hip_conv2d_f32 calls (LCE_TFLITE_SECTIONS_EXT_CONV2D): launches (one per absorbed CONV_2D) and the
+ * LceQuantize launches folded into them.  Nullable outputs. */
+void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
