@@ -683,23 +683,77 @@ def pool2d_output_hw(in_hw, filter, stride, padding):
     return tuple((i + s - 1) // s if padding == PADDING_SAME else (i + s - f) // s for i, f, s in zip(in_hw, filter, stride))
 
 
+def _nhwc_check(who, x, dtypes):
+    """``x`` is a non-empty NHWC tensor of one of ``dtypes``: its dtype's name and its four extents."""
+    name = _dtype_name(x)
+    if name not in dtypes or len(x.shape) != 4 or min(x.shape) < 1:
+        raise ValueError("%s: x must be a non-empty %s NHWC tensor, got %s %r" % (who, " or ".join(dtypes), x.dtype, tuple(x.shape)))
+    return (name,) + tuple(int(v) for v in x.shape)
+
+
+def _padding_activation_check(who, padding, activation):
+    """``padding`` (None: the pass has none) and ``activation`` are known values."""
+    if padding is not None and padding not in (PADDING_SAME, PADDING_VALID):
+        raise ValueError("%s: padding must be PADDING_SAME or PADDING_VALID, got %r" % (who, padding))
+    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
+        raise ValueError("%s: unknown activation %r" % (who, activation))
+
+
+def _window_output_hw(who, in_hw, filter, stride, padding):
+    """``pool2d_output_hw``, which must not be empty."""
+    oh, ow = pool2d_output_hw(in_hw, filter, stride, padding)
+    if oh < 1 or ow < 1:
+        raise ValueError("%s: empty output (a VALID filter of %d x %d on an image of %d x %d)" % ((who,) + tuple(filter) + tuple(in_hw)))
+    return oh, ow
+
+
+def _float_conv_check(who, x, filter_of, bias, stride, padding, activation, out, out_bits):
+    """The argument checks the float convolutions share, in their order: ``x`` float32 NHWC and non-empty; the pass's own
+    ``filter_of(cin)``, which checks the filter and returns (Cout, fh, fw); ``bias`` float32 [Cout] or None; ``stride``;
+    ``padding`` (None: a 1x1 filter has none, the extent is ceil(in / stride)) and ``activation``; an output that is not empty;
+    ``out`` and ``out_bits``.  Returns (b, h, w, cin, cout, fh, fw, sh, sw) and the output shape."""
+    _, b, h, w, cin = _nhwc_check(who, x, ("float32",))
+    cout, fh, fw = filter_of(cin)
+    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (cout,)):
+        raise ValueError("%s: bias must be float32 [%d], got %s %r" % (who, cout, bias.dtype, tuple(bias.shape)))
+    sh, sw = _pair(who, "stride", stride)
+    _padding_activation_check(who, padding, activation)
+    oh, ow = _window_output_hw(who, (h, w), (fh, fw), (sh, sw), PADDING_SAME if padding is None else padding)
+    shape = (b, oh, ow, cout)
+    _check_outputs(who, None if out is True else out, None if out_bits is False else out_bits, "float32", shape)
+    return (b, h, w, cin, cout, fh, fw, sh, sw), shape
+
+
+def _run_windowed(who, entry, desc, shape, x, constants, out, out_bits, stream, fresh=(True, None)):
+    """The run the windowed passes share: ``x`` and the ``constants`` behind it (filter and bias; None for an absent one) on
+    x's device (NumPy: cuda:0); ``out`` -- one of ``fresh`` for a new tensor of ``shape``, False for none, else the caller's --
+    and ``out_bits`` -- True for new bits, False or None for none, else the caller's; the library's ``entry`` on ``stream``."""
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x's")
+    xd = on_dev(x)
+    operands = [None if c is None else on_dev(c) for c in constants]
+    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if any(out is f for f in fresh) else on_dev(out)
+    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
+    with torch.cuda.device(dev):
+        check(getattr(lib(), entry)(C.byref(desc), _dev_ptr(xd), *[_dev_ptr(t) for t in operands], _dev_ptr(out_d), _dev_ptr(bits_d),
+                                    C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+
+
 def _pool2d_check(x, op, filter, stride, padding, activation, out, out_bits, scale, zero_point):
     """Argument checks of ``pool2d`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
     (Pool2dDesc, output shape)."""
     ops = {POOL_MAX: POOL_MAX, POOL_AVERAGE: POOL_AVERAGE, "max": POOL_MAX, "average": POOL_AVERAGE}
     if op not in ops:
         raise ValueError("pool2d: unknown op %r" % (op,))
-    name = _dtype_name(x)
-    if name not in ("float32", "int8") or len(x.shape) != 4 or min(x.shape) < 1:
-        raise ValueError("pool2d: x must be a non-empty float32 or int8 NHWC tensor, got %s %r" % (x.dtype, tuple(x.shape)))
+    name, b, h, w, c = _nhwc_check("pool2d", x, ("float32", "int8"))
     fh, fw = _pair("pool2d", "filter", filter)
     sh, sw = _pair("pool2d", "stride", stride)
     if fh * fw > POOL_MAX_TAPS:
         raise ValueError("pool2d: a filter of %d x %d has more than %d taps" % (fh, fw, POOL_MAX_TAPS))
-    if padding not in (PADDING_SAME, PADDING_VALID):
-        raise ValueError("pool2d: padding must be PADDING_SAME or PADDING_VALID, got %r" % (padding,))
-    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
-        raise ValueError("pool2d: unknown activation %r" % (activation,))
+    _padding_activation_check("pool2d", padding, activation)
     if name == "int8":
         if scale is None or not (np.isfinite(float(scale)) and float(scale) > 0):
             raise ValueError("pool2d: an int8 tensor needs a finite positive scale, got %r" % (scale,))
@@ -707,10 +761,7 @@ def _pool2d_check(x, op, filter, stride, padding, activation, out, out_bits, sca
             raise ValueError("pool2d: zero point must be an integer in [-128, 127], got %r" % (zero_point,))
     elif zero_point != 0:
         raise ValueError("pool2d: a float32 tensor has no zero point, got %r" % (zero_point,))
-    b, h, w, c = (int(v) for v in x.shape)
-    oh, ow = pool2d_output_hw((h, w), (fh, fw), (sh, sw), padding)
-    if oh < 1 or ow < 1:
-        raise ValueError("pool2d: empty output (a VALID filter of %d x %d on an image of %d x %d)" % (fh, fw, h, w))
+    oh, ow = _window_output_hw("pool2d", (h, w), (fh, fw), (sh, sw), padding)
     shape = (b, oh, ow, c)
     _check_outputs("pool2d", None if out is True else out, None if out_bits is False else out_bits, name, shape)
     desc = Pool2dDesc(ops[op], F32 if name == "float32" else I8, b, h, w, c, fh, fw, sh, sw, int(padding), int(activation),
@@ -728,36 +779,18 @@ def pool2d(x, op, filter, stride, padding, activation=ACT_NONE, out=True, out_bi
     overlap ``x``), False for none.  ``out_bits``: True for new int32 [B, OH, OW, ceil(C/32)] bits (float32: value < 0; int8:
     value < ``zero_point``), a tensor to fill, False for none.  Returns ``(pooled or None, bits or None)``."""
     desc, shape = _pool2d_check(x, op, filter, stride, padding, activation, out, out_bits, scale, zero_point)
-    import torch
-    host = isinstance(x, np.ndarray)
-    dev = torch.device("cuda:0") if host else x.device
-    on_dev = lambda a: _on_dev(a, dev, "pool2d", "x's")
-    xd = on_dev(x)
-    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if (out is True or out is None) else on_dev(out)
-    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
-    with torch.cuda.device(dev):
-        check(lib().lce_hip_pool2d(C.byref(desc), _dev_ptr(xd), _dev_ptr(out_d), _dev_ptr(bits_d),
-                                   C.c_void_p(_stream_or_current(stream, dev))))
-    return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+    return _run_windowed("pool2d", "lce_hip_pool2d", desc, shape, x, (), out, out_bits, stream)
 
 
 def _conv1x1_check(x, w, bias, stride, activation, out, out_bits):
     """Argument checks of ``conv1x1`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
     (Conv1x1Desc, output shape)."""
-    if _dtype_name(x) != "float32" or len(x.shape) != 4 or min(x.shape) < 1:
-        raise ValueError("conv1x1: x must be a non-empty float32 NHWC tensor, got %s %r" % (x.dtype, tuple(x.shape)))
-    b, h, wd, cin = (int(v) for v in x.shape)
-    ws = tuple(int(v) for v in w.shape)
-    if _dtype_name(w) != "float32" or len(ws) not in (2, 4) or ws not in ((ws[0], cin), (ws[0], 1, 1, cin)) or ws[0] < 1:
-        raise ValueError("conv1x1: w must be float32 [Cout, %d] or [Cout, 1, 1, %d], got %s %r" % (cin, cin, w.dtype, ws))
-    cout = ws[0]
-    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (cout,)):
-        raise ValueError("conv1x1: bias must be float32 [%d], got %s %r" % (cout, bias.dtype, tuple(bias.shape)))
-    sh, sw = _pair("conv1x1", "stride", stride)
-    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
-        raise ValueError("conv1x1: unknown activation %r" % (activation,))
-    shape = (b, (h + sh - 1) // sh, (wd + sw - 1) // sw, cout)
-    _check_outputs("conv1x1", out, None if out_bits is False else out_bits, "float32", shape)
+    def filter_of(cin):
+        ws = tuple(int(v) for v in w.shape)
+        if _dtype_name(w) != "float32" or len(ws) not in (2, 4) or ws not in ((ws[0], cin), (ws[0], 1, 1, cin)) or ws[0] < 1:
+            raise ValueError("conv1x1: w must be float32 [Cout, %d] or [Cout, 1, 1, %d], got %s %r" % (cin, cin, w.dtype, ws))
+        return ws[0], 1, 1
+    (b, h, wd, cin, cout, _, _, sh, sw), shape = _float_conv_check("conv1x1", x, filter_of, bias, stride, None, activation, out, out_bits)
     return Conv1x1Desc(b, h, wd, cin, cout, sh, sw, int(activation)), shape
 
 
@@ -771,48 +804,24 @@ def conv1x1(x, w, bias=None, stride=1, activation=ACT_NONE, out=None, out_bits=F
     ``out_bits``: True for new int32 [B, OH, OW, ceil(Cout/32)] bits (value < 0), a tensor to fill, False for none.  Returns
     ``(out or None, bits or None)``."""
     desc, shape = _conv1x1_check(x, w, bias, stride, activation, out, out_bits)
-    import torch
-    host = isinstance(x, np.ndarray)
-    dev = torch.device("cuda:0") if host else x.device
-    on_dev = lambda a: _on_dev(a, dev, "conv1x1", "x's")
-    xd, wd = on_dev(x), on_dev(w)
-    bd = None if bias is None else on_dev(bias)
-    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if out is None else on_dev(out)
-    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
-    with torch.cuda.device(dev):
-        check(lib().lce_hip_conv1x1_f32(C.byref(desc), _dev_ptr(xd), _dev_ptr(wd), _dev_ptr(bd), _dev_ptr(out_d), _dev_ptr(bits_d),
-                                        C.c_void_p(_stream_or_current(stream, dev))))
-    return _results(host, out_d, bits_d, out, None if out_bits is True else out_bits)
+    return _run_windowed("conv1x1", "lce_hip_conv1x1_f32", desc, shape, x, (w, bias), out, out_bits, stream, fresh=(None,))
 
 
 def _depthwise_check(x, filter, bias, stride, padding, depth_multiplier, activation, out, out_bits):
     """Argument checks of ``depthwise_conv2d`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.
     Returns (DepthwiseDesc, output shape)."""
     who = "depthwise_conv2d"
-    if _dtype_name(x) != "float32" or len(x.shape) != 4 or min(x.shape) < 1:
-        raise ValueError("%s: x must be a non-empty float32 NHWC tensor, got %s %r" % (who, x.dtype, tuple(x.shape)))
-    b, h, w, cin = (int(v) for v in x.shape)
-    if not isinstance(depth_multiplier, (int, np.integer)) or depth_multiplier < 1:
-        raise ValueError("%s: depth_multiplier must be a positive int, got %r" % (who, depth_multiplier))
-    cout = cin * int(depth_multiplier)
-    fs = tuple(int(v) for v in filter.shape)
-    if _dtype_name(filter) != "float32" or len(fs) not in (3, 4) or fs[-1] != cout or min(fs) < 1 or (len(fs) == 4 and fs[0] != 1):
-        raise ValueError("%s: filter must be float32 [1, fh, fw, %d] or [fh, fw, %d], got %s %r" % (who, cout, cout, filter.dtype, fs))
-    fh, fw = fs[-3], fs[-2]
-    if fh * fw * cout >= 1 << 31:
-        raise ValueError("%s: a filter of 2^31 or more elements is not supported, got %r" % (who, fs))
-    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (cout,)):
-        raise ValueError("%s: bias must be float32 [%d], got %s %r" % (who, cout, bias.dtype, tuple(bias.shape)))
-    sh, sw = _pair(who, "stride", stride)
-    if padding not in (PADDING_SAME, PADDING_VALID):
-        raise ValueError("%s: padding must be PADDING_SAME or PADDING_VALID, got %r" % (who, padding))
-    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
-        raise ValueError("%s: unknown activation %r" % (who, activation))
-    oh, ow = pool2d_output_hw((h, w), (fh, fw), (sh, sw), padding)
-    if oh < 1 or ow < 1:
-        raise ValueError("%s: empty output (a VALID filter of %d x %d on an image of %d x %d)" % (who, fh, fw, h, w))
-    shape = (b, oh, ow, cout)
-    _check_outputs(who, None if out is True else out, None if out_bits is False else out_bits, "float32", shape)
+    def filter_of(cin):
+        if not isinstance(depth_multiplier, (int, np.integer)) or depth_multiplier < 1:
+            raise ValueError("%s: depth_multiplier must be a positive int, got %r" % (who, depth_multiplier))
+        cout = cin * int(depth_multiplier)
+        fs = tuple(int(v) for v in filter.shape)
+        if _dtype_name(filter) != "float32" or len(fs) not in (3, 4) or fs[-1] != cout or min(fs) < 1 or (len(fs) == 4 and fs[0] != 1):
+            raise ValueError("%s: filter must be float32 [1, fh, fw, %d] or [fh, fw, %d], got %s %r" % (who, cout, cout, filter.dtype, fs))
+        if fs[-3] * fs[-2] * cout >= 1 << 31:
+            raise ValueError("%s: a filter of 2^31 or more elements is not supported, got %r" % (who, fs))
+        return cout, fs[-3], fs[-2]
+    (b, h, w, cin, _, fh, fw, sh, sw), shape = _float_conv_check(who, x, filter_of, bias, stride, padding, activation, out, out_bits)
     return DepthwiseDesc(b, h, w, cin, int(depth_multiplier), fh, fw, sh, sw, int(padding), int(activation)), shape
 
 
@@ -828,45 +837,21 @@ def depthwise_conv2d(x, filter, bias=None, stride=1, padding=PADDING_SAME, depth
     overlap an operand), False for none.  ``out_bits``: True for new int32 [B, OH, OW, ceil(Cout/32)] bits (value < 0), a
     tensor to fill, False for none.  Returns ``(out or None, bits or None)``."""
     desc, shape = _depthwise_check(x, filter, bias, stride, padding, depth_multiplier, activation, out, out_bits)
-    import torch
-    host = isinstance(x, np.ndarray)
-    dev = torch.device("cuda:0") if host else x.device
-    on_dev = lambda a: _on_dev(a, dev, "depthwise_conv2d", "x's")
-    xd, fd = on_dev(x), on_dev(filter)
-    bd = None if bias is None else on_dev(bias)
-    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if (out is True or out is None) else on_dev(out)
-    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
-    with torch.cuda.device(dev):
-        check(lib().lce_hip_depthwise_conv2d_f32(C.byref(desc), _dev_ptr(xd), _dev_ptr(fd), _dev_ptr(bd), _dev_ptr(out_d),
-                                                 _dev_ptr(bits_d), C.c_void_p(_stream_or_current(stream, dev))))
-    return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+    return _run_windowed("depthwise_conv2d", "lce_hip_depthwise_conv2d_f32", desc, shape, x, (filter, bias), out, out_bits, stream)
 
 
 def _conv2d_check(x, w, bias, stride, padding, activation, out, out_bits):
     """Argument checks of ``conv2d`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
     (Conv2dDesc, output shape)."""
     who = "conv2d"
-    if _dtype_name(x) != "float32" or len(x.shape) != 4 or min(x.shape) < 1:
-        raise ValueError("%s: x must be a non-empty float32 NHWC tensor, got %s %r" % (who, x.dtype, tuple(x.shape)))
-    b, h, wd, cin = (int(v) for v in x.shape)
-    ws = tuple(int(v) for v in w.shape)
-    if _dtype_name(w) != "float32" or len(ws) != 4 or ws[3] != cin or min(ws) < 1:
-        raise ValueError("%s: w must be float32 [Cout, fh, fw, %d], got %s %r" % (who, cin, w.dtype, ws))
-    cout, fh, fw = ws[0], ws[1], ws[2]
-    if fh * fw * cin >= 1 << 31:
-        raise ValueError("%s: a filter of 2^31 or more elements per output channel is not supported, got %r" % (who, ws))
-    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (cout,)):
-        raise ValueError("%s: bias must be float32 [%d], got %s %r" % (who, cout, bias.dtype, tuple(bias.shape)))
-    sh, sw = _pair(who, "stride", stride)
-    if padding not in (PADDING_SAME, PADDING_VALID):
-        raise ValueError("%s: padding must be PADDING_SAME or PADDING_VALID, got %r" % (who, padding))
-    if activation not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
-        raise ValueError("%s: unknown activation %r" % (who, activation))
-    oh, ow = pool2d_output_hw((h, wd), (fh, fw), (sh, sw), padding)
-    if oh < 1 or ow < 1:
-        raise ValueError("%s: empty output (a VALID filter of %d x %d on an image of %d x %d)" % (who, fh, fw, h, wd))
-    shape = (b, oh, ow, cout)
-    _check_outputs(who, None if out is True else out, None if out_bits is False else out_bits, "float32", shape)
+    def filter_of(cin):
+        ws = tuple(int(v) for v in w.shape)
+        if _dtype_name(w) != "float32" or len(ws) != 4 or ws[3] != cin or min(ws) < 1:
+            raise ValueError("%s: w must be float32 [Cout, fh, fw, %d], got %s %r" % (who, cin, w.dtype, ws))
+        if ws[1] * ws[2] * cin >= 1 << 31:
+            raise ValueError("%s: a filter of 2^31 or more elements per output channel is not supported, got %r" % (who, ws))
+        return ws[0], ws[1], ws[2]
+    (b, h, wd, cin, cout, fh, fw, sh, sw), shape = _float_conv_check(who, x, filter_of, bias, stride, padding, activation, out, out_bits)
     return Conv2dDesc(b, h, wd, cin, cout, fh, fw, sh, sw, int(padding), int(activation)), shape
 
 
@@ -880,18 +865,7 @@ def conv2d(x, w, bias=None, stride=1, padding=PADDING_SAME, activation=ACT_NONE,
     new tensor, a tensor to fill (it must not overlap an operand), False for none.  ``out_bits``: True for new int32
     [B, OH, OW, ceil(Cout/32)] bits (value < 0), a tensor to fill, False for none.  Returns ``(out or None, bits or None)``."""
     desc, shape = _conv2d_check(x, w, bias, stride, padding, activation, out, out_bits)
-    import torch
-    host = isinstance(x, np.ndarray)
-    dev = torch.device("cuda:0") if host else x.device
-    on_dev = lambda a: _on_dev(a, dev, "conv2d", "x's")
-    xd, wd = on_dev(x), on_dev(w)
-    bd = None if bias is None else on_dev(bias)
-    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if (out is True or out is None) else on_dev(out)
-    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
-    with torch.cuda.device(dev):
-        check(lib().lce_hip_conv2d_f32(C.byref(desc), _dev_ptr(xd), _dev_ptr(wd), _dev_ptr(bd), _dev_ptr(out_d), _dev_ptr(bits_d),
-                                       C.c_void_p(_stream_or_current(stream, dev))))
-    return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+    return _run_windowed("conv2d", "lce_hip_conv2d_f32", desc, shape, x, (w, bias), out, out_bits, stream)
 
 
 def bmaxpool(x, filter_height, filter_width, stride_height, stride_width, padding, stream: int | None = None, out=None):

@@ -119,6 +119,110 @@ struct DevBuf {
   }
 };
 
+// CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float.  False, and the range of NONE, for an activation
+// that is none of the four.
+bool float_activation_range(int32_t activation, float* lo, float* hi) {
+  *lo = -FLT_MAX;
+  *hi = FLT_MAX;
+  switch (activation) {
+    case LCE_HIP_ACT_NONE: return true;
+    case LCE_HIP_ACT_RELU: *lo = 0.0f; return true;
+    case LCE_HIP_ACT_RELU_N1_TO_1: *lo = -1.0f; *hi = 1.0f; return true;
+    case LCE_HIP_ACT_RELU6: *lo = 0.0f; *hi = 6.0f; return true;
+    default: return false;
+  }
+}
+
+// ---- The host checks that the windowed passes (pool, float 1x1 / depthwise / KxK convolution) share.  `who` is the entry's
+// name: every message is the entry's own. ----
+// The window of a pass as its descriptor states it; the 1x1 convolution, which has neither field, is a 1 x 1 VALID window.
+struct Window {
+  int32_t batch, in_h, in_w, fh, fw, sh, sw, padding, activation;
+};
+
+// Filter and stride positive, padding SAME or VALID, an activation float_activation_range knows: in this order.
+lce_hip_status check_window_options(const char* who, const Window& w) {
+  if (w.fh <= 0 || w.fw <= 0) return fail(LCE_HIP_ERR_INVALID, "%s: the filter must be positive, got %d x %d", who, (int)w.fh, (int)w.fw);
+  if (w.sh <= 0 || w.sw <= 0) return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)w.sh, (int)w.sw);
+  if (w.padding != LCE_HIP_PADDING_SAME && w.padding != LCE_HIP_PADDING_VALID)
+    return fail(LCE_HIP_ERR_INVALID, "%s: padding must be SAME or VALID, got %d", who, (int)w.padding);
+  if (w.activation < LCE_HIP_ACT_NONE || w.activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)w.activation);
+  return LCE_HIP_OK;
+}
+
+// (the kernels' window arithmetic, oy * stride - pad + filter, is 32-bit -- the 1x1 kernel's oy * stride 64-bit from 32-bit
+// factors: with these bounds nothing wraps)
+lce_hip_status check_extent_limit(const char* who, const Window& w) {
+  if (std::max(w.in_h, w.in_w) > (1 << 30) || std::max(w.sh, w.sw) > (1 << 30))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  return LCE_HIP_OK;
+}
+
+// The end of every *_check: an output of oh x ow per image must have fewer than 2^31 pixels; then it is reported.
+lce_hip_status report_output(const char* who, const Window& w, int32_t oh, int32_t ow, int32_t* out_height, int32_t* out_width) {
+  if ((uint64_t)w.batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+
+// The output extent the padding rule gives (lce_hip_bmaxpool_output_shape), which must not be empty; then report_output.
+lce_hip_status window_output(const char* who, const Window& w, int32_t* out_height, int32_t* out_width) {
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = lce_hip_bmaxpool_output_shape(w.in_h, w.in_w, w.fh, w.fw, w.sh, w.sw, w.padding, &oh, &ow)) return s;
+  if (oh <= 0 || ow <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: empty output (a VALID filter of %d x %d on an image of %d x %d)", who, (int)w.fh, (int)w.fw,
+                (int)w.in_h, (int)w.in_w);
+  return report_output(who, w, oh, ow, out_height, out_width);
+}
+
+// ComputePaddingHeightWidth: of the SAME padding along one axis, total / 2 goes in front.
+int32_t same_pad_before(int32_t out, int32_t stride, int32_t filter, int32_t in) {
+  return (int32_t)(std::max<int64_t>(0, (int64_t)(out - 1) * stride + filter - in) / 2);
+}
+
+// The byte range of an operand; empty for a null pointer.
+struct Span {
+  uintptr_t lo, hi;
+  Span(const void* p, uint64_t bytes) : lo((uintptr_t)p), hi((uintptr_t)p + (p ? bytes : 0)) {}
+};
+bool meet(uintptr_t a0, uintptr_t a1, uintptr_t c0, uintptr_t c1) { return a0 < c1 && c0 < a1; }
+
+// The pointer checks of a run entry, in its order: descriptor, input, filter (`has_filter`), at least one output.
+lce_hip_status check_pointers(const char* who, const void* desc, const void* in, bool has_filter, const void* filter, const void* out,
+                              const void* bits) {
+  if (!desc) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!in) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (has_filter && !filter) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
+  if (!out && !bits) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  return LCE_HIP_OK;
+}
+
+// The outputs must not meet anything the launch reads (another lane still reads what one would overwrite) or each other, and
+// the pointers must be aligned: with `float_operands` every one to 4 bytes, otherwise (the pool, whose tensors may be int8)
+// `bits` alone.  An operand the pass does not have is an empty Span.
+lce_hip_status check_operand_ranges(const char* who, Span in, Span filter, Span bias, Span out, Span bits, bool float_operands) {
+  auto reads = [&](Span r) { return meet(out.lo, out.hi, r.lo, r.hi) || meet(bits.lo, bits.hi, r.lo, r.hi); };
+  if (reads(in)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the input", who);
+  if (reads(filter)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the filter", who);
+  if (reads(bias)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the bias", who);
+  if (meet(out.lo, out.hi, bits.lo, bits.hi)) return fail(LCE_HIP_ERR_INVALID, "%s: the two outputs overlap", who);
+  if (!float_operands && bits.lo % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: out_bits_dev must be 4-byte aligned", who);
+  if (float_operands && (in.lo | filter.lo | bias.lo | out.lo | bits.lo) % 4 != 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  return LCE_HIP_OK;
+}
+
+// The grid stepping of the 16-byte-chunk kernels of pool and depthwise: what one grid step advances, in pixels and chunks.
+void pool_vec_steps(lce::PoolArgs& p) {
+  const uint64_t stride = (uint64_t)lce::pool_vec_grid(p.total) * 4ull * 64ull;   // chunks per grid step
+  p.step_pixels = (uint32_t)(stride / p.per_pixel);
+  p.step_chunks = (uint32_t)(stride % p.per_pixel);
+  p.div_per_pixel = lce::make_fastdiv(p.per_pixel);
+}
+
 }  // namespace
 
 struct lce_hip_bconv2d_plan {
@@ -492,14 +596,8 @@ lce_hip_status lce_hip_elementwise(const float* in_dev, size_t rows, size_t chan
       return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: unknown op %d", (int)s, (int)st.op);
     if (st.operand != LCE_HIP_EW_SCALAR && st.operand != LCE_HIP_EW_PER_CHANNEL && st.operand != LCE_HIP_EW_TENSOR)
       return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: unknown operand kind %d", (int)s, (int)st.operand);
-    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
-    switch (st.activation) {
-      case LCE_HIP_ACT_NONE: k.lo = -FLT_MAX; k.hi = FLT_MAX; break;
-      case LCE_HIP_ACT_RELU: k.lo = 0.0f; k.hi = FLT_MAX; break;
-      case LCE_HIP_ACT_RELU_N1_TO_1: k.lo = -1.0f; k.hi = 1.0f; break;
-      case LCE_HIP_ACT_RELU6: k.lo = 0.0f; k.hi = 6.0f; break;
-      default: return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: unknown activation %d", (int)s, (int)st.activation);
-    }
+    if (!float_activation_range(st.activation, &k.lo, &k.hi))
+      return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise: step %d: unknown activation %d", (int)s, (int)st.activation);
     k.op = st.op;
     k.operand = st.operand;
     k.values = st.operand == LCE_HIP_EW_SCALAR ? nullptr : st.values;
@@ -781,7 +879,6 @@ lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev,
   // the output ranges must not meet an input range: the row pitches differ, so there is no in-place join
   const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? rows * sum * esz : 0);
   const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? rows * wpr * 4 : 0);
-  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t c0, uintptr_t c1) { return a0 < c1 && c0 < a1; };
   if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: the two outputs overlap");
   bool vec = (o0 % 16 == 0) && (b0 % 4 == 0);
   for (int32_t k = 0; k < num_inputs; ++k) {
@@ -835,58 +932,35 @@ lce_hip_status lce_hip_pool2d_check(const lce_hip_pool2d_desc* d, int32_t* out_h
   if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels <= 0)
     return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d]", who, (int)d->batch, (int)d->in_height,
                 (int)d->in_width, (int)d->channels);
-  if (d->filter_height <= 0 || d->filter_width <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the filter must be positive, got %d x %d", who, (int)d->filter_height, (int)d->filter_width);
-  if (d->stride_height <= 0 || d->stride_width <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)d->stride_height, (int)d->stride_width);
-  if (d->padding != LCE_HIP_PADDING_SAME && d->padding != LCE_HIP_PADDING_VALID)
-    return fail(LCE_HIP_ERR_INVALID, "%s: padding must be SAME or VALID, got %d", who, (int)d->padding);
-  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
-    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  const Window w{d->batch, d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height, d->stride_width, d->padding,
+                 d->activation};
+  if (lce_hip_status s = check_window_options(who, w)) return s;
   if (d->type == LCE_HIP_I8) {
     if (d->zero_point < -128 || d->zero_point > 127)
       return fail(LCE_HIP_ERR_INVALID, "%s: zero_point must be in [-128, 127], got %d", who, (int)d->zero_point);
     if (!std::isfinite(d->scale) || !(d->scale > 0.0f))
       return fail(LCE_HIP_ERR_INVALID, "%s: scale must be finite and positive, got %g", who, (double)d->scale);
   }
-  // (the kernels' window arithmetic, oy * stride - pad + filter, is 32-bit: with these bounds it stays below 2^31)
-  if (std::max(d->in_height, d->in_width) > (1 << 30) || std::max(d->stride_height, d->stride_width) > (1 << 30))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  if (lce_hip_status s = check_extent_limit(who, w)) return s;
   // (the int8 AVERAGE divides in float: exact while 128.5 taps < 2^24, lce_kernels_pool.h)
   if ((int64_t)d->filter_height * d->filter_width > (int64_t)lce::kPoolMaxTaps)
     return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: a filter of %d x %d has more than %d taps", who, (int)d->filter_height, (int)d->filter_width,
                 lce::kPoolMaxTaps);
-  int32_t oh = 0, ow = 0;
-  if (lce_hip_status s = lce_hip_bmaxpool_output_shape(d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height,
-                                                      d->stride_width, d->padding, &oh, &ow)) return s;
-  if (oh <= 0 || ow <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: empty output (a VALID filter of %d x %d on an image of %d x %d)", who, (int)d->filter_height,
-                (int)d->filter_width, (int)d->in_height, (int)d->in_width);
-  if ((uint64_t)d->batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
-  if (out_height) *out_height = oh;
-  if (out_width) *out_width = ow;
-  return LCE_HIP_OK;
+  return window_output(who, w, out_height, out_width);
 }
 
 lce_hip_status lce_hip_pool2d(const lce_hip_pool2d_desc* d, const void* in_dev, void* out_dev, int32_t* out_bits_dev, void* stream) {
-  if (!d) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: null desc");
-  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: null input");
-  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: both outputs are null");
+  const char* who = "lce_hip_pool2d";
+  if (lce_hip_status s = check_pointers(who, d, in_dev, /*has_filter=*/false, nullptr, out_dev, out_bits_dev)) return s;
   int32_t oh = 0, ow = 0;
   if (lce_hip_status s = lce_hip_pool2d_check(d, &oh, &ow)) return s;
   const uint64_t esz = d->type == LCE_HIP_I8 ? 1 : 4;
   const uint64_t C = (uint64_t)d->channels, pixels = (uint64_t)d->batch * oh * ow, wpr = (C + 31) / 32;
-  // the outputs must not meet the input (another lane still reads what one lane would overwrite) or each other
-  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uint64_t)d->batch * d->in_height * d->in_width * C * esz;
-  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? pixels * C * esz : 0);
-  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? pixels * wpr * 4 : 0);
-  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t c0, uintptr_t c1) { return a0 < c1 && c0 < a1; };
-  if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: an output overlaps the input");
-  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: the two outputs overlap");
-  if (b0 % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "lce_hip_pool2d: out_bits_dev must be 4-byte aligned");
+  const Span in(in_dev, (uint64_t)d->batch * d->in_height * d->in_width * C * esz), none(nullptr, 0);
+  const Span out(out_dev, pixels * C * esz), bits(out_bits_dev, pixels * wpr * 4);
+  if (lce_hip_status s = check_operand_ranges(who, in, none, none, out, bits, /*float_operands=*/false)) return s;
   if (lce_hip_status s = require_device()) return s;
-  bool vec = (C * esz) % 16 == 0 && i0 % 16 == 0 && o0 % 16 == 0;
+  bool vec = (C * esz) % 16 == 0 && in.lo % 16 == 0 && out.lo % 16 == 0;
   if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
   lce::PoolArgs a;
   memset(&a, 0, sizeof a);
@@ -895,32 +969,21 @@ lce_hip_status lce_hip_pool2d(const lce_hip_pool2d_desc* d, const void* in_dev, 
   a.bits = (uint32_t*)out_bits_dev;
   a.H = d->in_height; a.W = d->in_width; a.OH = oh; a.OW = ow;
   a.fh = d->filter_height; a.fw = d->filter_width; a.sh = d->stride_height; a.sw = d->stride_width;
-  // ComputePaddingHeightWidth: total / 2 in front
-  a.ph = (int32_t)(std::max<int64_t>(0, (int64_t)(oh - 1) * d->stride_height + d->filter_height - d->in_height) / 2);
-  a.pw = (int32_t)(std::max<int64_t>(0, (int64_t)(ow - 1) * d->stride_width + d->filter_width - d->in_width) / 2);
+  a.ph = same_pad_before(oh, d->stride_height, d->filter_height, d->in_height);
+  a.pw = same_pad_before(ow, d->stride_width, d->filter_width, d->in_width);
   a.channels = (uint32_t)C;
   a.wpr = (uint32_t)wpr;
   a.per_pixel = (uint32_t)(vec ? C * esz / 16 : (C + 63) / 64);
   a.stream_loads = d->stride_height >= d->filter_height && d->stride_width >= d->filter_width ? 1u : 0u;
   a.total = pixels * a.per_pixel;
-  switch (d->activation) {    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
-    case LCE_HIP_ACT_RELU: a.lo = 0.0f; a.hi = FLT_MAX; break;
-    case LCE_HIP_ACT_RELU_N1_TO_1: a.lo = -1.0f; a.hi = 1.0f; break;
-    case LCE_HIP_ACT_RELU6: a.lo = 0.0f; a.hi = 6.0f; break;
-    default: a.lo = -FLT_MAX; a.hi = FLT_MAX;
-  }
+  float_activation_range(d->activation, &a.lo, &a.hi);
   if (d->type == LCE_HIP_I8) {
     quantized_activation_range(d->activation, d->scale, d->zero_point, &a.qlo, &a.qhi);
     a.zero_point = d->zero_point;
   }
   a.div_ow = lce::make_fastdiv((uint32_t)ow);
   a.div_oh = lce::make_fastdiv((uint32_t)oh);
-  if (vec) {
-    const uint64_t stride = (uint64_t)lce::pool_vec_grid(a.total) * 4ull * 64ull;   // chunks per grid step
-    a.step_pixels = (uint32_t)(stride / a.per_pixel);
-    a.step_chunks = (uint32_t)(stride % a.per_pixel);
-    a.div_per_pixel = lce::make_fastdiv(a.per_pixel);
-  }
+  if (vec) pool_vec_steps(a);
   const int e = lce::launch_pool(a, d->type == LCE_HIP_I8 ? lce::kPoolI8 : lce::kPoolF32,
                                  d->op == LCE_HIP_POOL_AVERAGE ? lce::kPoolAverage : lce::kPoolMax, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_pool2d: launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -936,48 +999,28 @@ lce_hip_status lce_hip_conv1x1_f32_check(const lce_hip_conv1x1_desc* d, int32_t*
   if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels_in <= 0 || d->channels_out <= 0)
     return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d] -> %d channels", who, (int)d->batch,
                 (int)d->in_height, (int)d->in_width, (int)d->channels_in, (int)d->channels_out);
-  if (d->stride_height <= 0 || d->stride_width <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)d->stride_height, (int)d->stride_width);
-  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
-    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
-  // (the kernel's pixel arithmetic, oy * stride, is 64-bit from 32-bit factors: with these bounds nothing wraps)
-  if (std::max(d->in_height, d->in_width) > (1 << 30) || std::max(d->stride_height, d->stride_width) > (1 << 30))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  const Window w{d->batch, d->in_height, d->in_width, 1, 1, d->stride_height, d->stride_width, LCE_HIP_PADDING_VALID, d->activation};
+  if (lce_hip_status s = check_window_options(who, w)) return s;
+  if (lce_hip_status s = check_extent_limit(who, w)) return s;
   // (one grid row per 128 output channels)
   if ((int64_t)d->channels_out > 65535ll * lce::kConv1x1BN)
     return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: more than %lld output channels are not supported", who, 65535ll * lce::kConv1x1BN);
   // a 1x1 filter has no padding taps: SAME and VALID both give ceil(in / stride)
   const int32_t oh = (int32_t)(((int64_t)d->in_height + d->stride_height - 1) / d->stride_height);
   const int32_t ow = (int32_t)(((int64_t)d->in_width + d->stride_width - 1) / d->stride_width);
-  if ((uint64_t)d->batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
-  if (out_height) *out_height = oh;
-  if (out_width) *out_width = ow;
-  return LCE_HIP_OK;
+  return report_output(who, w, oh, ow, out_height, out_width);
 }
 
 lce_hip_status lce_hip_conv1x1_f32(const lce_hip_conv1x1_desc* d, const float* in_dev, const float* filter_dev, const float* bias_dev,
                                    float* out_dev, int32_t* out_bits_dev, void* stream) {
   const char* who = "lce_hip_conv1x1_f32";
-  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
-  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
-  if (!filter_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
-  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  if (lce_hip_status s = check_pointers(who, d, in_dev, /*has_filter=*/true, filter_dev, out_dev, out_bits_dev)) return s;
   int32_t oh = 0, ow = 0;
   if (lce_hip_status s = lce_hip_conv1x1_f32_check(d, &oh, &ow)) return s;
   const uint64_t K = (uint64_t)d->channels_in, N = (uint64_t)d->channels_out, pixels = (uint64_t)d->batch * oh * ow, wpr = (N + 31) / 32;
-  // the outputs must not meet anything the launch reads (another wave still reads what one would overwrite) or each other
-  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uint64_t)d->batch * d->in_height * d->in_width * K * 4;
-  const uintptr_t f0 = (uintptr_t)filter_dev, f1 = f0 + N * K * 4;
-  const uintptr_t c0 = (uintptr_t)bias_dev, c1 = c0 + (bias_dev ? N * 4 : 0);
-  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? pixels * N * 4 : 0);
-  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? pixels * wpr * 4 : 0);
-  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t e0, uintptr_t e1) { return a0 < e1 && e0 < a1; };
-  if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the input", who);
-  if (meet(o0, o1, f0, f1) || meet(b0, b1, f0, f1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the filter", who);
-  if (meet(o0, o1, c0, c1) || meet(b0, b1, c0, c1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the bias", who);
-  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "%s: the two outputs overlap", who);
-  if ((i0 | f0 | c0 | o0 | b0) % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  const Span in(in_dev, (uint64_t)d->batch * d->in_height * d->in_width * K * 4), filter(filter_dev, N * K * 4), bias(bias_dev, N * 4);
+  const Span out(out_dev, pixels * N * 4), bits(out_bits_dev, pixels * wpr * 4);
+  if (lce_hip_status s = check_operand_ranges(who, in, filter, bias, out, bits, /*float_operands=*/true)) return s;
   if (lce_hip_status s = require_device()) return s;
   lce::Conv1x1Args a;
   memset(&a, 0, sizeof a);
@@ -989,13 +1032,8 @@ lce_hip_status lce_hip_conv1x1_f32(const lce_hip_conv1x1_desc* d, const float* i
   a.IHW = (uint64_t)d->in_height * (uint64_t)d->in_width;
   a.sh = (uint32_t)d->stride_height; a.sw = (uint32_t)d->stride_width;
   a.strided = d->stride_height != 1 || d->stride_width != 1 ? 1u : 0u;
-  switch (d->activation) {    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
-    case LCE_HIP_ACT_RELU: a.lo = 0.0f; a.hi = FLT_MAX; break;
-    case LCE_HIP_ACT_RELU_N1_TO_1: a.lo = -1.0f; a.hi = 1.0f; break;
-    case LCE_HIP_ACT_RELU6: a.lo = 0.0f; a.hi = 6.0f; break;
-    default: a.lo = -FLT_MAX; a.hi = FLT_MAX;
-  }
-  const bool vec = K % 4 == 0 && i0 % 16 == 0 && f0 % 16 == 0;
+  float_activation_range(d->activation, &a.lo, &a.hi);
+  const bool vec = K % 4 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
   const int e = lce::launch_conv1x1(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
@@ -1011,17 +1049,10 @@ lce_hip_status lce_hip_depthwise_conv2d_f32_check(const lce_hip_depthwise_desc* 
     return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d]", who, (int)d->batch, (int)d->in_height,
                 (int)d->in_width, (int)d->channels_in);
   if (d->depth_multiplier <= 0) return fail(LCE_HIP_ERR_INVALID, "%s: the depth multiplier must be positive, got %d", who, (int)d->depth_multiplier);
-  if (d->filter_height <= 0 || d->filter_width <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the filter must be positive, got %d x %d", who, (int)d->filter_height, (int)d->filter_width);
-  if (d->stride_height <= 0 || d->stride_width <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)d->stride_height, (int)d->stride_width);
-  if (d->padding != LCE_HIP_PADDING_SAME && d->padding != LCE_HIP_PADDING_VALID)
-    return fail(LCE_HIP_ERR_INVALID, "%s: padding must be SAME or VALID, got %d", who, (int)d->padding);
-  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
-    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
-  // (the kernels' window arithmetic, oy * stride - pad + filter, is 32-bit: with these bounds it stays below 2^31)
-  if (std::max(d->in_height, d->in_width) > (1 << 30) || std::max(d->stride_height, d->stride_width) > (1 << 30))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  const Window w{d->batch, d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height, d->stride_width, d->padding,
+                 d->activation};
+  if (lce_hip_status s = check_window_options(who, w)) return s;
+  if (lce_hip_status s = check_extent_limit(who, w)) return s;
   // (the filter's element count -- and with it Cout and each filter extent -- stays below 2^31; compared by division, so
   // that the product of four 31-bit factors is never formed)
   const uint64_t taps = (uint64_t)d->filter_height * (uint64_t)d->filter_width;
@@ -1029,44 +1060,23 @@ lce_hip_status lce_hip_depthwise_conv2d_f32_check(const lce_hip_depthwise_desc* 
   if (cout > ((1ull << 31) - 1) / taps)
     return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: a filter of 2^31 or more elements (%d x %d x %llu) is not supported", who,
                 (int)d->filter_height, (int)d->filter_width, (unsigned long long)cout);
-  int32_t oh = 0, ow = 0;
-  if (lce_hip_status s = lce_hip_bmaxpool_output_shape(d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height,
-                                                      d->stride_width, d->padding, &oh, &ow)) return s;
-  if (oh <= 0 || ow <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: empty output (a VALID filter of %d x %d on an image of %d x %d)", who, (int)d->filter_height,
-                (int)d->filter_width, (int)d->in_height, (int)d->in_width);
-  if ((uint64_t)d->batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
-  if (out_height) *out_height = oh;
-  if (out_width) *out_width = ow;
-  return LCE_HIP_OK;
+  return window_output(who, w, out_height, out_width);
 }
 
 lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* d, const float* in_dev, const float* filter_dev,
                                             const float* bias_dev, float* out_dev, int32_t* out_bits_dev, void* stream) {
   const char* who = "lce_hip_depthwise_conv2d_f32";
-  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
-  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
-  if (!filter_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
-  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  if (lce_hip_status s = check_pointers(who, d, in_dev, /*has_filter=*/true, filter_dev, out_dev, out_bits_dev)) return s;
   int32_t oh = 0, ow = 0;
   if (lce_hip_status s = lce_hip_depthwise_conv2d_f32_check(d, &oh, &ow)) return s;
   const uint64_t Cin = (uint64_t)d->channels_in, C = Cin * (uint64_t)d->depth_multiplier;
   const uint64_t pixels = (uint64_t)d->batch * oh * ow, wpr = (C + 31) / 32;
-  // the outputs must not meet anything the launch reads (another lane still reads what one would overwrite) or each other
-  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uint64_t)d->batch * d->in_height * d->in_width * Cin * 4;
-  const uintptr_t f0 = (uintptr_t)filter_dev, f1 = f0 + (uint64_t)d->filter_height * d->filter_width * C * 4;
-  const uintptr_t c0 = (uintptr_t)bias_dev, c1 = c0 + (bias_dev ? C * 4 : 0);
-  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? pixels * C * 4 : 0);
-  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? pixels * wpr * 4 : 0);
-  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t e0, uintptr_t e1) { return a0 < e1 && e0 < a1; };
-  if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the input", who);
-  if (meet(o0, o1, f0, f1) || meet(b0, b1, f0, f1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the filter", who);
-  if (meet(o0, o1, c0, c1) || meet(b0, b1, c0, c1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the bias", who);
-  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "%s: the two outputs overlap", who);
-  if ((i0 | f0 | c0 | o0 | b0) % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  const Span in(in_dev, (uint64_t)d->batch * d->in_height * d->in_width * Cin * 4);
+  const Span filter(filter_dev, (uint64_t)d->filter_height * d->filter_width * C * 4), bias(bias_dev, C * 4);
+  const Span out(out_dev, pixels * C * 4), bits(out_bits_dev, pixels * wpr * 4);
+  if (lce_hip_status s = check_operand_ranges(who, in, filter, bias, out, bits, /*float_operands=*/true)) return s;
   if (lce_hip_status s = require_device()) return s;
-  bool vec = d->depth_multiplier == 1 && C % 4 == 0 && (i0 | f0 | c0 | o0) % 16 == 0;
+  bool vec = d->depth_multiplier == 1 && C % 4 == 0 && (in.lo | filter.lo | bias.lo | out.lo) % 16 == 0;
   if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
   lce::DepthwiseArgs a;
   memset(&a, 0, sizeof a);
@@ -1077,29 +1087,18 @@ lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* d, con
   a.div_multiplier = lce::make_fastdiv((uint32_t)d->depth_multiplier);
   p.H = d->in_height; p.W = d->in_width; p.OH = oh; p.OW = ow;
   p.fh = d->filter_height; p.fw = d->filter_width; p.sh = d->stride_height; p.sw = d->stride_width;
-  // ComputePaddingHeightWidth: total / 2 in front
-  p.ph = (int32_t)(std::max<int64_t>(0, (int64_t)(oh - 1) * d->stride_height + d->filter_height - d->in_height) / 2);
-  p.pw = (int32_t)(std::max<int64_t>(0, (int64_t)(ow - 1) * d->stride_width + d->filter_width - d->in_width) / 2);
+  p.ph = same_pad_before(oh, d->stride_height, d->filter_height, d->in_height);
+  p.pw = same_pad_before(ow, d->stride_width, d->filter_width, d->in_width);
   p.channels = (uint32_t)C;
   p.wpr = (uint32_t)wpr;
   p.per_pixel = (uint32_t)(vec ? C / 4 : (C + 63) / 64);
   // the pools' rule (lce_kernels_pool.h): non-temporal window loads only where windows do not overlap
   p.stream_loads = d->stride_height >= d->filter_height && d->stride_width >= d->filter_width ? 1u : 0u;
   p.total = pixels * p.per_pixel;
-  switch (d->activation) {    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
-    case LCE_HIP_ACT_RELU: p.lo = 0.0f; p.hi = FLT_MAX; break;
-    case LCE_HIP_ACT_RELU_N1_TO_1: p.lo = -1.0f; p.hi = 1.0f; break;
-    case LCE_HIP_ACT_RELU6: p.lo = 0.0f; p.hi = 6.0f; break;
-    default: p.lo = -FLT_MAX; p.hi = FLT_MAX;
-  }
+  float_activation_range(d->activation, &p.lo, &p.hi);
   p.div_ow = lce::make_fastdiv((uint32_t)ow);
   p.div_oh = lce::make_fastdiv((uint32_t)oh);
-  if (vec) {
-    const uint64_t stride = (uint64_t)lce::pool_vec_grid(p.total) * 4ull * 64ull;   // chunks per grid step
-    p.step_pixels = (uint32_t)(stride / p.per_pixel);
-    p.step_chunks = (uint32_t)(stride % p.per_pixel);
-    p.div_per_pixel = lce::make_fastdiv(p.per_pixel);
-  }
+  if (vec) pool_vec_steps(p);
   const int e = lce::launch_depthwise(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
@@ -1114,17 +1113,10 @@ lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* d, int32_t* o
   if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels_in <= 0 || d->channels_out <= 0)
     return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d] -> %d channels", who, (int)d->batch,
                 (int)d->in_height, (int)d->in_width, (int)d->channels_in, (int)d->channels_out);
-  if (d->filter_height <= 0 || d->filter_width <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the filter must be positive, got %d x %d", who, (int)d->filter_height, (int)d->filter_width);
-  if (d->stride_height <= 0 || d->stride_width <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the stride must be positive, got %d x %d", who, (int)d->stride_height, (int)d->stride_width);
-  if (d->padding != LCE_HIP_PADDING_SAME && d->padding != LCE_HIP_PADDING_VALID)
-    return fail(LCE_HIP_ERR_INVALID, "%s: padding must be SAME or VALID, got %d", who, (int)d->padding);
-  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
-    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
-  // (the kernels' window arithmetic, oy * stride - pad + filter, is 32-bit: with these bounds it stays below 2^31)
-  if (std::max(d->in_height, d->in_width) > (1 << 30) || std::max(d->stride_height, d->stride_width) > (1 << 30))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: image extents and strides above 2^30 are not supported", who);
+  const Window w{d->batch, d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height, d->stride_width, d->padding,
+                 d->activation};
+  if (lce_hip_status s = check_window_options(who, w)) return s;
+  if (lce_hip_status s = check_extent_limit(who, w)) return s;
   // (K = fh x fw x Cin -- and with it each filter extent -- stays below 2^31; compared by division, so that the product of
   // three 31-bit factors is never formed)
   const uint64_t taps = (uint64_t)d->filter_height * (uint64_t)d->filter_width;
@@ -1134,56 +1126,29 @@ lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* d, int32_t* o
   // (one grid row per 128 output channels)
   if ((int64_t)d->channels_out > 65535ll * lce::kConv2dBN)
     return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: more than %lld output channels are not supported", who, 65535ll * lce::kConv2dBN);
-  int32_t oh = 0, ow = 0;
-  if (lce_hip_status s = lce_hip_bmaxpool_output_shape(d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height,
-                                                      d->stride_width, d->padding, &oh, &ow)) return s;
-  if (oh <= 0 || ow <= 0)
-    return fail(LCE_HIP_ERR_INVALID, "%s: empty output (a VALID filter of %d x %d on an image of %d x %d)", who, (int)d->filter_height,
-                (int)d->filter_width, (int)d->in_height, (int)d->in_width);
-  if ((uint64_t)d->batch * (uint64_t)oh * (uint64_t)ow >= (1ull << 31))
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output must have fewer than 2^31 pixels", who);
-  if (out_height) *out_height = oh;
-  if (out_width) *out_width = ow;
-  return LCE_HIP_OK;
+  return window_output(who, w, out_height, out_width);
 }
 
 lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* d, const float* in_dev, const float* filter_dev, const float* bias_dev,
                                   float* out_dev, int32_t* out_bits_dev, void* stream) {
   const char* who = "lce_hip_conv2d_f32";
-  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
-  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
-  if (!filter_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
-  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  if (lce_hip_status s = check_pointers(who, d, in_dev, /*has_filter=*/true, filter_dev, out_dev, out_bits_dev)) return s;
   int32_t oh = 0, ow = 0;
   if (lce_hip_status s = lce_hip_conv2d_f32_check(d, &oh, &ow)) return s;
   const uint64_t Cin = (uint64_t)d->channels_in, N = (uint64_t)d->channels_out;
   const uint64_t K = (uint64_t)d->filter_height * d->filter_width * Cin;             // < 2^31
   const uint64_t pixels = (uint64_t)d->batch * oh * ow, wpr = (N + 31) / 32;
-  // the outputs must not meet anything the launches read (another wave still reads what one would overwrite) or each other
-  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (uint64_t)d->batch * d->in_height * d->in_width * Cin * 4;
-  const uintptr_t f0 = (uintptr_t)filter_dev, f1 = f0 + N * K * 4;
-  const uintptr_t c0 = (uintptr_t)bias_dev, c1 = c0 + (bias_dev ? N * 4 : 0);
-  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? pixels * N * 4 : 0);
-  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? pixels * wpr * 4 : 0);
-  auto meet = [](uintptr_t a0, uintptr_t a1, uintptr_t e0, uintptr_t e1) { return a0 < e1 && e0 < a1; };
-  if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the input", who);
-  if (meet(o0, o1, f0, f1) || meet(b0, b1, f0, f1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the filter", who);
-  if (meet(o0, o1, c0, c1) || meet(b0, b1, c0, c1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the bias", who);
-  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "%s: the two outputs overlap", who);
-  if ((i0 | f0 | c0 | o0 | b0) % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  const Span in(in_dev, (uint64_t)d->batch * d->in_height * d->in_width * Cin * 4), filter(filter_dev, N * K * 4), bias(bias_dev, N * 4);
+  const Span out(out_dev, pixels * N * 4), bits(out_bits_dev, pixels * wpr * 4);
+  if (lce_hip_status s = check_operand_ranges(who, in, filter, bias, out, bits, /*float_operands=*/true)) return s;
   if (lce_hip_status s = require_device()) return s;
   lce::Conv2dArgs a;
   memset(&a, 0, sizeof a);
   a.in = in_dev; a.filter = filter_dev; a.bias = bias_dev; a.out = out_dev; a.bits = (uint32_t*)out_bits_dev;
   lce::conv2d_geometry(a, d->batch, d->in_height, d->in_width, d->channels_in, d->channels_out, d->filter_height, d->filter_width,
                        d->stride_height, d->stride_width, oh, ow);
-  switch (d->activation) {    // CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float
-    case LCE_HIP_ACT_RELU: a.lo = 0.0f; a.hi = FLT_MAX; break;
-    case LCE_HIP_ACT_RELU_N1_TO_1: a.lo = -1.0f; a.hi = 1.0f; break;
-    case LCE_HIP_ACT_RELU6: a.lo = 0.0f; a.hi = 6.0f; break;
-    default: a.lo = -FLT_MAX; a.hi = FLT_MAX;
-  }
-  const bool vec = Cin % 4 == 0 && i0 % 16 == 0 && f0 % 16 == 0;
+  float_activation_range(d->activation, &a.lo, &a.hi);
+  const bool vec = Cin % 4 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
   const int e = lce::launch_conv2d(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;

@@ -19,6 +19,9 @@
 struct lce_tflite_section {
   std::vector<int32_t> ops, inputs, outputs;
 };
+// The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
+enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
+       kAbsorbedCount };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
@@ -38,7 +41,7 @@ struct lce_tflite_model {
     int32_t conv_quantize = 0;                                          // LceQuantize launches folded into a convolution (run_dual)
     int32_t ew_ops = 0;                                                 // ADD / MUL operators inside the lce_hip_elementwise launches
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
-    Pass ew, add_i8, concat, pool, conv1x1, depthwise, conv2d;          // lce_hip_elementwise, lce_hip_add_int8, lce_hip_concat, lce_hip_pool2d, lce_hip_conv1x1_f32, lce_hip_depthwise_conv2d_f32, lce_hip_conv2d_f32
+    Pass pass[kAbsorbedCount];                                          // by kAbsorbed* kind ([0] unused)
   };
   RunStats last;                                                        // of the last run
   // ---- HIP graphs (lce_tflite_model_use_hip_graphs): a section's launches recorded once per (section, batch, semantics,
@@ -174,6 +177,56 @@ bool ConcatCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return sum == out.shape[3];
 }
 
+// ---- what the candidate predicates of the windowed passes (pool, the float convolutions) share ----
+// `in` and `out` are 4-D with positive extents, and `in` is no constant.
+bool StreamedImages(const lce_tfl::Tensor& in, const lce_tfl::Tensor& out) {
+  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
+  for (int k = 0; k < 4; ++k)
+    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
+  return true;
+}
+
+// Strides positive, padding SAME or VALID, an activation the entries know.
+bool WindowOptions(const lce_tfl::Operator& o) {
+  if (o.pool_stride_h <= 0 || o.pool_stride_w <= 0) return false;
+  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
+  return o.activation >= LCE_HIP_ACT_NONE && o.activation <= LCE_HIP_ACT_RELU6;
+}
+
+// The option block of a float convolution: WindowOptions and dilations of 1.
+bool ConvOptions(const lce_tfl::Operator& o) { return WindowOptions(o) && o.dilation_h == 1 && o.dilation_w == 1; }
+
+// The operands of a float convolution: 2 or 3 inputs (a third input of -1: no bias) and one output; input, filter and output
+// float32; StreamedImages of input and output.
+bool FloatConvOperands(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 || flt.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32) return false;
+  return StreamedImages(in, out);
+}
+
+// A constant 4-D filter with data in the file, positive extents, and as many bytes as its extents say: 4 x their product,
+// compared by division (each extent is below 2^31; the product of the four is never formed).
+bool ConstFloatFilter(const lce_tfl::Tensor& flt) {
+  if (!flt.data || flt.shape.size() != 4 || (uint64_t)flt.bytes % 4u != 0) return false;
+  uint64_t elems = (uint64_t)flt.bytes / 4u;
+  for (int32_t extent : flt.shape) {
+    if (extent <= 0 || elems % (uint64_t)extent != 0) return false;
+    elems /= (uint64_t)extent;
+  }
+  return elems == 1;
+}
+
+// The bias of a float convolution: absent (two inputs, or a third of -1) or a constant float32 [cout] with data in the file.
+bool OptionalBias(const lce_tfl::Model& M, const lce_tfl::Operator& o, int64_t cout) {
+  if (o.inputs.size() != 3 || o.inputs[2] < 0) return true;
+  const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
+  return bias.type == lce_tfl::kTensorFloat32 && bias.data && bias.shape.size() == 1 && bias.shape[0] == cout &&
+         (uint64_t)bias.bytes == (uint64_t)cout * 4u;
+}
+
 // lce_hip_pool2d_desc of a builtin pool at `batch` images, from its options and the FILE's input tensor.
 lce_hip_pool2d_desc PoolDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
   const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
@@ -203,10 +256,7 @@ bool PoolCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   if (o.inputs.size() != 1 || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
   const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
   const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
-  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
-  for (int k = 0; k < 4; ++k)
-    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
-  if (in.type != out.type || in.shape[3] != out.shape[3]) return false;
+  if (!StreamedImages(in, out) || in.type != out.type || in.shape[3] != out.shape[3]) return false;
   if (out.type == lce_tfl::kTensorInt8) {
     for (const lce_tfl::Tensor* t : {&in, &out})
       if (!t->quantized || t->zero_point < -128 || t->zero_point > 127) return false;
@@ -214,9 +264,7 @@ bool PoolCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   } else if (out.type != lce_tfl::kTensorFloat32) {
     return false;
   }
-  if (o.pool_filter_h <= 0 || o.pool_filter_w <= 0 || o.pool_stride_h <= 0 || o.pool_stride_w <= 0) return false;
-  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
-  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  if (o.pool_filter_h <= 0 || o.pool_filter_w <= 0 || !WindowOptions(o)) return false;
   const lce_hip_pool2d_desc d = PoolDesc(M, o, in.shape[0]);
   int32_t oh = 0, ow = 0;
   return lce_hip_pool2d_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
@@ -242,28 +290,12 @@ lce_hip_conv1x1_desc Conv1x1Desc(const lce_tfl::Model& M, const lce_tfl::Operato
 // activation lce_hip_conv1x1_f32 knows; the declared output height and width equal to ceil(in / stride); and a descriptor
 // lce_hip_conv1x1_f32's own check accepts.  The other half -- it becomes ready in an LCE epoch -- is decided by Partition().
 bool Conv1x1Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
-  if (o.builtin_code != lce_tfl::kBuiltinConv2d) return false;
-  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  if (o.builtin_code != lce_tfl::kBuiltinConv2d || !o.has_conv_options || !FloatConvOperands(M, o)) return false;
   const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
   const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
   const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
-  if (in.type != lce_tfl::kTensorFloat32 || flt.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32) return false;
-  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
-  for (int k = 0; k < 4; ++k)
-    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
-  if (!flt.data || flt.shape.size() != 4 || flt.shape[0] <= 0 || flt.shape[1] != 1 || flt.shape[2] != 1 || flt.shape[3] != in.shape[3]) return false;
-  const int64_t cout = flt.shape[0];
-  if ((uint64_t)flt.bytes != (uint64_t)cout * (uint64_t)in.shape[3] * 4u) return false;      // (< 2^64: both factors are below 2^31)
-  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
-    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
-    if (bias.type != lce_tfl::kTensorFloat32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != cout ||
-        (uint64_t)bias.bytes != (uint64_t)cout * 4u) return false;
-  }
-  if (out.shape[3] != cout) return false;
-  if (!o.has_conv_options) return false;
-  if (o.pool_stride_h <= 0 || o.pool_stride_w <= 0 || o.dilation_h != 1 || o.dilation_w != 1) return false;
-  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
-  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  if (!ConstFloatFilter(flt) || flt.shape[1] != 1 || flt.shape[2] != 1 || flt.shape[3] != in.shape[3]) return false;
+  if (out.shape[3] != flt.shape[0] || !OptionalBias(M, o, flt.shape[0]) || !ConvOptions(o)) return false;
   const lce_hip_conv1x1_desc d = Conv1x1Desc(M, o, in.shape[0]);
   int32_t oh = 0, ow = 0;
   return lce_hip_conv1x1_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
@@ -292,30 +324,14 @@ lce_hip_depthwise_desc DepthwiseDesc(const lce_tfl::Model& M, const lce_tfl::Ope
 // activation lce_hip_depthwise_conv2d_f32 knows; the declared output height and width what the padding rule gives; and a
 // descriptor the entry's own check accepts.  The other half -- it becomes ready in an LCE epoch -- is decided by Partition().
 bool DepthwiseCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
-  if (o.builtin_code != lce_tfl::kBuiltinDepthwiseConv2d) return false;
-  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  if (o.builtin_code != lce_tfl::kBuiltinDepthwiseConv2d || !o.has_depthwise_options || !FloatConvOperands(M, o)) return false;
   const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
   const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
   const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
-  if (in.type != lce_tfl::kTensorFloat32 || flt.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32) return false;
-  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
-  for (int k = 0; k < 4; ++k)
-    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
-  if (!flt.data || flt.shape.size() != 4 || flt.shape[0] != 1 || flt.shape[1] <= 0 || flt.shape[2] <= 0 || flt.shape[3] <= 0) return false;
+  if (!ConstFloatFilter(flt) || flt.shape[0] != 1) return false;
   const int64_t cout = flt.shape[3];
-  // (fh x fw < 2^62 and cout < 2^31: compared by division, the product of the three is never formed)
-  const uint64_t taps = (uint64_t)flt.shape[1] * (uint64_t)flt.shape[2];
-  if ((uint64_t)flt.bytes % 4u != 0 || (uint64_t)flt.bytes / 4u % taps != 0 || (uint64_t)flt.bytes / 4u / taps != (uint64_t)cout) return false;
-  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
-    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
-    if (bias.type != lce_tfl::kTensorFloat32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != cout ||
-        (uint64_t)bias.bytes != (uint64_t)cout * 4u) return false;
-  }
-  if (!o.has_depthwise_options) return false;
   if (o.depth_multiplier < 1 || (int64_t)in.shape[3] * o.depth_multiplier != cout || out.shape[3] != cout) return false;
-  if (o.pool_stride_h <= 0 || o.pool_stride_w <= 0 || o.dilation_h != 1 || o.dilation_w != 1) return false;
-  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
-  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  if (!OptionalBias(M, o, cout) || !ConvOptions(o)) return false;
   const lce_hip_depthwise_desc d = DepthwiseDesc(M, o, in.shape[0]);
   int32_t oh = 0, ow = 0;
   return lce_hip_depthwise_conv2d_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
@@ -343,37 +359,28 @@ lce_hip_conv2d_desc Conv2dDesc(const lce_tfl::Model& M, const lce_tfl::Operator&
 // what the padding rule gives; and lce_hip_conv2d_f32's own check accepts the descriptor.  The other half -- when it becomes
 // ready -- is decided by Partition().
 bool Conv2dCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
-  if (o.builtin_code != lce_tfl::kBuiltinConv2d) return false;
-  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  if (o.builtin_code != lce_tfl::kBuiltinConv2d || !o.has_conv_options || !FloatConvOperands(M, o)) return false;
   const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
   const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
   const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
-  if (in.type != lce_tfl::kTensorFloat32 || flt.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32) return false;
-  if (out.shape.size() != 4 || in.shape.size() != 4 || in.data) return false;
-  for (int k = 0; k < 4; ++k)
-    if (out.shape[k] <= 0 || in.shape[k] <= 0) return false;
-  if (!flt.data || flt.shape.size() != 4 || flt.shape[0] <= 0 || flt.shape[1] <= 0 || flt.shape[2] <= 0 || flt.shape[3] != in.shape[3]) return false;
-  const int64_t cout = flt.shape[0];
-  // (fh x fw < 2^62, cout and cin < 2^31: compared by division, the product of the four is never formed)
-  const uint64_t taps = (uint64_t)flt.shape[1] * (uint64_t)flt.shape[2], cin = (uint64_t)flt.shape[3];
-  const uint64_t elems = (uint64_t)flt.bytes / 4u;
-  if ((uint64_t)flt.bytes % 4u != 0 || elems % taps != 0 || elems / taps % cin != 0 || elems / taps / cin != (uint64_t)cout) return false;
-  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
-    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
-    if (bias.type != lce_tfl::kTensorFloat32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != cout ||
-        (uint64_t)bias.bytes != (uint64_t)cout * 4u) return false;
-  }
-  if (out.shape[3] != cout) return false;
-  if (!o.has_conv_options) return false;
-  if (o.pool_stride_h <= 0 || o.pool_stride_w <= 0 || o.dilation_h != 1 || o.dilation_w != 1) return false;
-  if (o.pool_padding != LCE_HIP_PADDING_SAME && o.pool_padding != LCE_HIP_PADDING_VALID) return false;
-  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  if (!ConstFloatFilter(flt) || flt.shape[3] != in.shape[3]) return false;
+  if (out.shape[3] != flt.shape[0] || !OptionalBias(M, o, flt.shape[0]) || !ConvOptions(o)) return false;
   const lce_hip_conv2d_desc d = Conv2dDesc(M, o, in.shape[0]);
   int32_t oh = 0, ow = 0;
   return lce_hip_conv2d_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
 }
-enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add = 2, kAbsorbedConcat = 3, kAbsorbedPool = 4, kAbsorbedConv1x1 = 5, kAbsorbedDepthwise = 6,
-       kAbsorbedConv2d = 7 };
+
+// One fused pass: the bit of `flags` (or, with `ext`, of `flags_ext`) that enables it, the static half of "a section may run
+// this operator", and the walker that runs it.  The table, in priority order, is below Walk.
+struct Walk;
+struct FusedPass {
+  int kind;
+  bool ext;
+  uint32_t bit;
+  bool (*candidate)(const lce_tfl::Model&, const lce_tfl::Operator&);
+  lce_hip_status (Walk::*walker)(int32_t);
+};
+extern const FusedPass kPasses[kAbsorbedCount - 1];
 }  // namespace
 
 // The partition a delegate would get (tensorflow/lite/graph_info.cc, PartitionGraphIntoIndependentNodeSubsets, restated from
@@ -392,23 +399,11 @@ void lce_tflite_model::Partition() {
   std::vector<int32_t> unready(n_ops, 0);
   for (int i = 0; i < n_ops; ++i) {
     is_lce[i] = IsLceOp(m.operators[i]) ? 1 : 0;
-    // LCE_TFLITE_SECTIONS_ELEMENTWISE: a float ADD / MUL joins the epoch in which it becomes ready, so it lands in a section
-    // exactly when the last of its inputs was produced by an LCE epoch (one that is ready from the start -- a stem op -- is
-    // a builtin one without LCE_TFLITE_SECTIONS_EXT_STEM, below)
-    if (flags & LCE_TFLITE_SECTIONS_ELEMENTWISE) candidate[i] = ElementwiseCandidate(m, m.operators[i]) ? kAbsorbedElementwise : 0;
-    // LCE_TFLITE_SECTIONS_INT8_ADD: the same rule for the int8 ADD of a shortcut
-    if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_INT8_ADD)) candidate[i] = Int8AddCandidate(m, m.operators[i]) ? kAbsorbedInt8Add : 0;
-    // LCE_TFLITE_SECTIONS_CONCAT: the same rule for the channel join of a dense block
-    if (!candidate[i] && (flags & LCE_TFLITE_SECTIONS_CONCAT)) candidate[i] = ConcatCandidate(m, m.operators[i]) ? kAbsorbedConcat : 0;
-    // LCE_TFLITE_SECTIONS_EXT_POOL: the same rule for a 2-D pool
-    if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_POOL)) candidate[i] = PoolCandidate(m, m.operators[i]) ? kAbsorbedPool : 0;
-    // LCE_TFLITE_SECTIONS_EXT_CONV1X1: the same rule for the float 1x1 CONV_2D of a transition block or a shortcut
-    if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_CONV1X1)) candidate[i] = Conv1x1Candidate(m, m.operators[i]) ? kAbsorbedConv1x1 : 0;
-    // LCE_TFLITE_SECTIONS_EXT_DEPTHWISE: the same rule for the float DEPTHWISE_CONV_2D of QuickNet's transition
-    if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_DEPTHWISE)) candidate[i] = DepthwiseCandidate(m, m.operators[i]) ? kAbsorbedDepthwise : 0;
-    // LCE_TFLITE_SECTIONS_EXT_CONV2D: the same rule for a float CONV_2D of any filter extent (Conv1x1Candidate was tried first: with
-    // both bits a 1x1 filter runs as before)
-    if (!candidate[i] && (flags_ext & LCE_TFLITE_SECTIONS_EXT_CONV2D)) candidate[i] = Conv2dCandidate(m, m.operators[i]) ? kAbsorbedConv2d : 0;
+    // the first pass, in the table's order, that is enabled and whose predicate holds.  An absorbed operator joins the epoch in
+    // which it becomes ready, so it lands in a section exactly when the last of its inputs was produced by an LCE epoch (one
+    // that is ready from the start -- a stem op -- is a builtin one without LCE_TFLITE_SECTIONS_EXT_STEM, below)
+    for (const FusedPass& p : kPasses)
+      if (!candidate[i] && ((p.ext ? flags_ext : flags) & p.bit) && p.candidate(m, m.operators[i])) candidate[i] = (char)p.kind;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -840,8 +835,8 @@ lce_hip_status ConstOnDevice(lce_tflite_model* model, int32_t t, void* stream, b
 
 // One walk of a section at `batch` images: shapes of every tensor it touches (shape inference exactly as the ops' Prepare
 // does it) and, with `run`, the launches.  `ptr` maps tensor -> device pointer (section inputs and outputs on entry;
-// intermediates are added from the model's scratch buffers).  A fused pass between binary layers plugs in as a candidate
-// predicate (above), a walker here that ends in FoldQuantize / FoldBuffers, and its counters in RunStats.
+// intermediates are added from the model's scratch buffers).  A fused pass between binary layers plugs in as a row of kPasses
+// (below): a candidate predicate (above) and a walker here that ends in FoldQuantize / FoldBuffers / Launched.
 struct Walk {
   lce_tflite_model* model;
   const lce_tflite_section& sec;
@@ -932,6 +927,13 @@ struct Walk {
       if (lce_hip_status s = BufferFor(f.bits_t, shapes[f.bits_t].bytes(), bits)) return s;
     return LCE_HIP_OK;
   }
+  // The tail of every fused pass: count one launch of `kind` and, when an LceQuantize folded into it, that.
+  lce_hip_status Launched(int kind, const Fold& f) {
+    lce_tflite_model::RunStats::Pass& p = model->last.pass[kind];
+    ++p.launches;
+    if (f.bits_t >= 0) ++p.quantize;
+    return LCE_HIP_OK;
+  }
 
   // A maximal chain of absorbed ADD / MUL operators that starts at operator `first`, as ONE lce_hip_elementwise launch.  The
   // chain streams a float tensor x (an input of `first`: an LceBconv2d output or a section input) and extends through an
@@ -1016,10 +1018,8 @@ struct Walk {
     if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
     if (lce_hip_status s = lce_hip_elementwise((const float*)in, rows, channels, steps.data(), (int32_t)steps.size(), (float*)out,
                                                (int32_t*)bits, stream)) return s;
-    ++model->last.ew.launches;
     model->last.ew_ops += (int32_t)chain.size();
-    if (fold.bits_t >= 0) ++model->last.ew.quantize;
-    return LCE_HIP_OK;
+    return Launched(kAbsorbedElementwise, fold);
   }
 
   // An absorbed int8 ADD (LCE_TFLITE_SECTIONS_INT8_ADD) as ONE lce_hip_add_int8 launch.  The first LceQuantize of the section
@@ -1053,9 +1053,7 @@ struct Walk {
     if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
     if (lce_hip_status s = lce_hip_add_int8(&d, (const int8_t*)in[0], (const int8_t*)in[1], (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2],
                                             (size_t)xs.dims[3], (int8_t*)out, (int32_t*)bits, stream)) return s;
-    ++model->last.add_i8.launches;
-    if (fold.bits_t >= 0) ++model->last.add_i8.quantize;
-    return LCE_HIP_OK;
+    return Launched(kAbsorbedInt8Add, fold);
   }
 
   // An absorbed CONCATENATION (LCE_TFLITE_SECTIONS_CONCAT) as ONE lce_hip_concat launch.  The first LceQuantize of the section
@@ -1097,152 +1095,90 @@ struct Walk {
     const lce_hip_dtype type = OT.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : OT.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BITPACKED;
     if (lce_hip_status s = lce_hip_concat(type, in, channels, (int32_t)n, (size_t)batch * fs[1] * fs[2],
                                           type == LCE_HIP_I8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
-    ++model->last.concat.launches;
-    if (fold.bits_t >= 0) ++model->last.concat.quantize;
-    return LCE_HIP_OK;
+    return Launched(kAbsorbedConcat, fold);
   }
 
-  // An absorbed AVERAGE_POOL_2D / MAX_POOL_2D (LCE_TFLITE_SECTIONS_EXT_POOL) as ONE lce_hip_pool2d launch.  The first
-  // LceQuantize of the section that reads the pooled tensor becomes the launch's bit output and its own launch disappears; the
-  // pooled tensor itself is written when anything else reads it or the section delivers it.
+  // An absorbed operator `i` that streams ONE input and makes ONE output of the input's type with `out_channels` channels, as
+  // ONE launch of pass `kind`; `noun` names it in the messages ("a pool").  `check(&h, &w)` is the entry's own *_check of the
+  // descriptor at this walk's batch, which gives the output's height and width; `launch(in, filter, bias, out, bits)` is the
+  // entry (filter and bias: inputs 1 and 2 of the operator when it has them, uploaded once per model).  The first LceQuantize of
+  // the section that reads the result becomes the launch's bit output and its own launch disappears; the tensor itself is
+  // written when anything else reads it or the section delivers it.
+  template <class Check, class Launch>
+  lce_hip_status StreamingPass(int32_t i, int kind, const std::string& noun, int type, int32_t out_channels, Check check, Launch launch) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
+    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    auto it = shapes.find(op.inputs[0]);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " reads a tensor nothing produced");
+    if (!Agrees(it->second, type, is[1], is[2], is[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " input's shape or type does not match the one its producer infers");
+    Shape os;
+    os.dims[0] = batch; os.dims[3] = out_channels;
+    os.type = type;
+    if (lce_hip_status s = check(&os.dims[1], &os.dims[2])) return s;
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(op.inputs[0], (noun + " input").c_str(), &in)) return s;
+    const float *filter = nullptr, *bias = nullptr;
+    if (op.inputs.size() >= 2)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &filter)) return s;
+    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = launch(in, filter, bias, out, (int32_t*)bits)) return s;
+    return Launched(kind, fold);
+  }
+
+  // An absorbed AVERAGE_POOL_2D / MAX_POOL_2D (LCE_TFLITE_SECTIONS_EXT_POOL) as ONE lce_hip_pool2d launch.
   lce_hip_status Pool2d(int32_t i) {
-    const lce_tfl::Model& M = model->m;
-    const lce_tfl::Operator& op = M.operators[i];
-    const int32_t out_t = op.outputs[0];
-    const lce_tfl::Tensor& OT = M.tensors[out_t];
-    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
-    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
-    // declares must not be read past its buffer)
-    auto it = shapes.find(op.inputs[0]);
-    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a pool reads a tensor nothing produced");
-    if (!Agrees(it->second, OT.type, is[1], is[2], is[3]))
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: a pool input's shape or type does not match the one its producer infers");
-    const lce_hip_pool2d_desc d = PoolDesc(M, op, batch);
-    Shape os;
-    os.dims[0] = batch; os.dims[3] = is[3];
-    os.type = OT.type;
-    if (lce_hip_status s = lce_hip_pool2d_check(&d, &os.dims[1], &os.dims[2])) return s;
-    shapes[out_t] = os;
-    done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os);
-    if (!run) return LCE_HIP_OK;
-    const void* in = nullptr;
-    if (lce_hip_status s = DevicePtr(op.inputs[0], "a pool input", &in)) return s;
-    void *out, *bits;
-    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    if (lce_hip_status s = lce_hip_pool2d(&d, in, out, (int32_t*)bits, stream)) return s;
-    ++model->last.pool.launches;
-    if (fold.bits_t >= 0) ++model->last.pool.quantize;
-    return LCE_HIP_OK;
+    const lce_tfl::Operator& op = model->m.operators[i];
+    const lce_tfl::Tensor& in = model->m.tensors[op.inputs[0]];
+    const lce_hip_pool2d_desc d = PoolDesc(model->m, op, batch);
+    return StreamingPass(
+        i, kAbsorbedPool, "a pool", in.type, in.shape[3], [&](int32_t* h, int32_t* w) { return lce_hip_pool2d_check(&d, h, w); },
+        [&](const void* x, const float*, const float*, void* out, int32_t* bits) { return lce_hip_pool2d(&d, x, out, bits, stream); });
   }
 
-  // An absorbed float 1x1 CONV_2D (LCE_TFLITE_SECTIONS_EXT_CONV1X1) as ONE lce_hip_conv1x1_f32 launch.  The first LceQuantize of
-  // the section that reads the result becomes the launch's bit output and its own launch disappears; the float tensor itself is
-  // written when anything else reads it or the section delivers it.  The filter and the bias are uploaded once per model.
+  // An absorbed float 1x1 CONV_2D (LCE_TFLITE_SECTIONS_EXT_CONV1X1) as ONE lce_hip_conv1x1_f32 launch.
   lce_hip_status Conv1x1(int32_t i) {
-    const lce_tfl::Model& M = model->m;
-    const lce_tfl::Operator& op = M.operators[i];
-    const int32_t out_t = op.outputs[0];
-    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
-    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
-    // declares must not be read past its buffer)
-    auto it = shapes.find(op.inputs[0]);
-    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONV_2D reads a tensor nothing produced");
-    if (!Agrees(it->second, lce_tfl::kTensorFloat32, is[1], is[2], is[3]))
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONV_2D input's shape or type does not match the one its producer infers");
-    const lce_hip_conv1x1_desc d = Conv1x1Desc(M, op, batch);
-    Shape os;
-    os.dims[0] = batch; os.dims[3] = d.channels_out;
-    os.type = lce_tfl::kTensorFloat32;
-    if (lce_hip_status s = lce_hip_conv1x1_f32_check(&d, &os.dims[1], &os.dims[2])) return s;
-    shapes[out_t] = os;
-    done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os);
-    if (!run) return LCE_HIP_OK;
-    const void* in = nullptr;
-    if (lce_hip_status s = DevicePtr(op.inputs[0], "a CONV_2D input", &in)) return s;
-    const float *filter = nullptr, *bias = nullptr;
-    if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &filter)) return s;
-    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
-      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
-    void *out, *bits;
-    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    if (lce_hip_status s = lce_hip_conv1x1_f32(&d, (const float*)in, filter, bias, (float*)out, (int32_t*)bits, stream)) return s;
-    ++model->last.conv1x1.launches;
-    if (fold.bits_t >= 0) ++model->last.conv1x1.quantize;
-    return LCE_HIP_OK;
+    const lce_hip_conv1x1_desc d = Conv1x1Desc(model->m, model->m.operators[i], batch);
+    return StreamingPass(
+        i, kAbsorbedConv1x1, "a CONV_2D", lce_tfl::kTensorFloat32, d.channels_out,
+        [&](int32_t* h, int32_t* w) { return lce_hip_conv1x1_f32_check(&d, h, w); },
+        [&](const void* x, const float* filter, const float* bias, void* out, int32_t* bits) {
+          return lce_hip_conv1x1_f32(&d, (const float*)x, filter, bias, (float*)out, bits, stream);
+        });
   }
 
-  // An absorbed float DEPTHWISE_CONV_2D (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE) as ONE lce_hip_depthwise_conv2d_f32 launch, folded and
-  // fed as Conv1x1 above.
+  // An absorbed float DEPTHWISE_CONV_2D (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE) as ONE lce_hip_depthwise_conv2d_f32 launch.
   lce_hip_status Depthwise(int32_t i) {
-    const lce_tfl::Model& M = model->m;
-    const lce_tfl::Operator& op = M.operators[i];
-    const int32_t out_t = op.outputs[0];
-    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
-    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
-    // declares must not be read past its buffer)
-    auto it = shapes.find(op.inputs[0]);
-    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a DEPTHWISE_CONV_2D reads a tensor nothing produced");
-    if (!Agrees(it->second, lce_tfl::kTensorFloat32, is[1], is[2], is[3]))
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: a DEPTHWISE_CONV_2D input's shape or type does not match the one its producer infers");
-    const lce_hip_depthwise_desc d = DepthwiseDesc(M, op, batch);
-    Shape os;
-    os.dims[0] = batch; os.dims[3] = M.tensors[op.inputs[1]].shape[3];
-    os.type = lce_tfl::kTensorFloat32;
-    if (lce_hip_status s = lce_hip_depthwise_conv2d_f32_check(&d, &os.dims[1], &os.dims[2])) return s;
-    shapes[out_t] = os;
-    done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os);
-    if (!run) return LCE_HIP_OK;
-    const void* in = nullptr;
-    if (lce_hip_status s = DevicePtr(op.inputs[0], "a DEPTHWISE_CONV_2D input", &in)) return s;
-    const float *filter = nullptr, *bias = nullptr;
-    if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &filter)) return s;
-    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
-      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
-    void *out, *bits;
-    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    if (lce_hip_status s = lce_hip_depthwise_conv2d_f32(&d, (const float*)in, filter, bias, (float*)out, (int32_t*)bits, stream)) return s;
-    ++model->last.depthwise.launches;
-    if (fold.bits_t >= 0) ++model->last.depthwise.quantize;
-    return LCE_HIP_OK;
+    const lce_tfl::Operator& op = model->m.operators[i];
+    const lce_hip_depthwise_desc d = DepthwiseDesc(model->m, op, batch);
+    return StreamingPass(
+        i, kAbsorbedDepthwise, "a DEPTHWISE_CONV_2D", lce_tfl::kTensorFloat32, model->m.tensors[op.inputs[1]].shape[3],
+        [&](int32_t* h, int32_t* w) { return lce_hip_depthwise_conv2d_f32_check(&d, h, w); },
+        [&](const void* x, const float* filter, const float* bias, void* out, int32_t* bits) {
+          return lce_hip_depthwise_conv2d_f32(&d, (const float*)x, filter, bias, (float*)out, bits, stream);
+        });
   }
 
-  // An absorbed float CONV_2D of any filter extent (LCE_TFLITE_SECTIONS_EXT_CONV2D) as ONE lce_hip_conv2d_f32 call, checked, folded
-  // and fed as Conv1x1 above.
+  // An absorbed float CONV_2D of any filter extent (LCE_TFLITE_SECTIONS_EXT_CONV2D) as ONE lce_hip_conv2d_f32 call.
   lce_hip_status Conv2d(int32_t i) {
-    const lce_tfl::Model& M = model->m;
-    const lce_tfl::Operator& op = M.operators[i];
-    const int32_t out_t = op.outputs[0];
-    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
-    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
-    // declares must not be read past its buffer)
-    auto it = shapes.find(op.inputs[0]);
-    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONV_2D reads a tensor nothing produced");
-    if (!Agrees(it->second, lce_tfl::kTensorFloat32, is[1], is[2], is[3]))
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONV_2D input's shape or type does not match the one its producer infers");
-    const lce_hip_conv2d_desc d = Conv2dDesc(M, op, batch);
-    Shape os;
-    os.dims[0] = batch; os.dims[3] = d.channels_out;
-    os.type = lce_tfl::kTensorFloat32;
-    if (lce_hip_status s = lce_hip_conv2d_f32_check(&d, &os.dims[1], &os.dims[2])) return s;
-    shapes[out_t] = os;
-    done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os);
-    if (!run) return LCE_HIP_OK;
-    const void* in = nullptr;
-    if (lce_hip_status s = DevicePtr(op.inputs[0], "a CONV_2D input", &in)) return s;
-    const float *filter = nullptr, *bias = nullptr;
-    if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &filter)) return s;
-    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
-      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
-    void *out, *bits;
-    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    if (lce_hip_status s = lce_hip_conv2d_f32(&d, (const float*)in, filter, bias, (float*)out, (int32_t*)bits, stream)) return s;
-    ++model->last.conv2d.launches;
-    if (fold.bits_t >= 0) ++model->last.conv2d.quantize;
-    return LCE_HIP_OK;
+    const lce_hip_conv2d_desc d = Conv2dDesc(model->m, model->m.operators[i], batch);
+    return StreamingPass(
+        i, kAbsorbedConv2d, "a CONV_2D", lce_tfl::kTensorFloat32, d.channels_out,
+        [&](int32_t* h, int32_t* w) { return lce_hip_conv2d_f32_check(&d, h, w); },
+        [&](const void* x, const float* filter, const float* bias, void* out, int32_t* bits) {
+          return lce_hip_conv2d_f32(&d, (const float*)x, filter, bias, (float*)out, bits, stream);
+        });
   }
 
   // The four LCE operators.  `in` is the inferred shape of operator `i`'s first input, `in_dev` its device pointer (with `run`).
@@ -1368,21 +1304,25 @@ struct Walk {
     done = std::vector<char>(M.operators.size(), 0);
     for (int32_t i : sec.ops) {
       if (done[i]) continue;
-      lce_hip_status s;
-      switch (model->absorbed[i]) {
-        case kAbsorbedElementwise: s = ElementwiseChain(i); break;
-        case kAbsorbedInt8Add: s = Int8Add(i); break;
-        case kAbsorbedConcat: s = Concat(i); break;
-        case kAbsorbedPool: s = Pool2d(i); break;
-        case kAbsorbedConv1x1: s = Conv1x1(i); break;
-        case kAbsorbedDepthwise: s = Depthwise(i); break;
-        case kAbsorbedConv2d: s = Conv2d(i); break;
-        default: s = LceOp(i);
-      }
-      if (s) return s;
+      const int kind = model->absorbed[i];
+      if (lce_hip_status s = kind ? (this->*kPasses[kind - 1].walker)(i) : LceOp(i)) return s;
     }
     return LCE_HIP_OK;
   }
+};
+
+// THE table of fused passes, in priority order (the first enabled row whose predicate holds takes the operator) and in the
+// order of the kinds (row k is kind k + 1).  A new pass is a row here, a predicate built from the helpers above, a walker that
+// ends in FoldQuantize / FoldBuffers / Launched, and an exported *_stats one-liner.
+const FusedPass kPasses[kAbsorbedCount - 1] = {
+    {kAbsorbedElementwise, false, LCE_TFLITE_SECTIONS_ELEMENTWISE, ElementwiseCandidate, &Walk::ElementwiseChain},
+    {kAbsorbedInt8Add, false, LCE_TFLITE_SECTIONS_INT8_ADD, Int8AddCandidate, &Walk::Int8Add},
+    {kAbsorbedConcat, false, LCE_TFLITE_SECTIONS_CONCAT, ConcatCandidate, &Walk::Concat},
+    {kAbsorbedPool, true, LCE_TFLITE_SECTIONS_EXT_POOL, PoolCandidate, &Walk::Pool2d},
+    {kAbsorbedConv1x1, true, LCE_TFLITE_SECTIONS_EXT_CONV1X1, Conv1x1Candidate, &Walk::Conv1x1},
+    {kAbsorbedDepthwise, true, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, DepthwiseCandidate, &Walk::Depthwise},
+    // (Conv1x1Candidate is tried first: with both bits a 1x1 filter runs as before)
+    {kAbsorbedConv2d, true, LCE_TFLITE_SECTIONS_EXT_CONV2D, Conv2dCandidate, &Walk::Conv2d},
 };
 }  // namespace
 
@@ -1477,54 +1417,34 @@ void lce_tflite_model_graph_stats(lce_tflite_model* model, int32_t* recorded, in
   if (replays) *replays = model->graph_replays;
 }
 
-void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+// The counters of the fused pass `kind` in the last run; `ops_folded` is the elementwise pass's alone.
+static void PassStats(lce_tflite_model* model, int kind, int32_t* launches, int32_t* quantize_folded, int32_t* ops_folded = nullptr) {
   if (!model) return;
   std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.ew.launches;
+  if (launches) *launches = model->last.pass[kind].launches;
   if (ops_folded) *ops_folded = model->last.ew_ops;
-  if (quantize_folded) *quantize_folded = model->last.ew.quantize;
+  if (quantize_folded) *quantize_folded = model->last.pass[kind].quantize;
 }
-
+void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+  PassStats(model, kAbsorbedElementwise, launches, quantize_folded, ops_folded);
+}
 void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.add_i8.launches;
-  if (quantize_folded) *quantize_folded = model->last.add_i8.quantize;
+  PassStats(model, kAbsorbedInt8Add, launches, quantize_folded);
 }
-
 void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.concat.launches;
-  if (quantize_folded) *quantize_folded = model->last.concat.quantize;
+  PassStats(model, kAbsorbedConcat, launches, quantize_folded);
 }
-
 void lce_tflite_model_pool_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.pool.launches;
-  if (quantize_folded) *quantize_folded = model->last.pool.quantize;
+  PassStats(model, kAbsorbedPool, launches, quantize_folded);
 }
-
 void lce_tflite_model_conv1x1_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.conv1x1.launches;
-  if (quantize_folded) *quantize_folded = model->last.conv1x1.quantize;
+  PassStats(model, kAbsorbedConv1x1, launches, quantize_folded);
 }
-
 void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.depthwise.launches;
-  if (quantize_folded) *quantize_folded = model->last.depthwise.quantize;
+  PassStats(model, kAbsorbedDepthwise, launches, quantize_folded);
 }
-
 void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.conv2d.launches;
-  if (quantize_folded) *quantize_folded = model->last.conv2d.quantize;
+  PassStats(model, kAbsorbedConv2d, launches, quantize_folded);
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

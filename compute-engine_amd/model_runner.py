@@ -102,6 +102,24 @@ class _OpenOptions56(C.Structure):
                 ("reserved2", C.c_uint32 * 4), ("reserved3", C.c_uint32 * 4)]
 
 
+# The keywords of ``LceModel`` that let builtin operators join the sections: (keyword, word of the options -- 0 ``sections``,
+# 1 ``sections_ext`` --, bit, the smallest form of ``lce_tflite_open_options`` that carries the bit; 0:
+# ``lce_tflite_model_open_ex`` does).
+_SECTION_KEYWORDS = (
+    ("elementwise_sections", 0, SECTIONS_ELEMENTWISE, 0),
+    ("int8_add_sections", 0, SECTIONS_INT8_ADD, 0),
+    ("concat_sections", 0, SECTIONS_CONCAT, 8),
+    ("pool_sections", 1, SECTIONS_EXT_POOL, 24),
+    ("conv1x1_sections", 1, SECTIONS_EXT_CONV1X1, 40),
+    ("depthwise_sections", 1, SECTIONS_EXT_DEPTHWISE, 56),
+    ("conv2d_sections", 1, SECTIONS_EXT_CONV2D, 56),
+    ("stem_sections", 1, SECTIONS_EXT_STEM, 56),
+)
+_OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
+# ``lce_tflite_model_<pass>_stats``: the counters each reports
+_PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2}
+
+
 class Section:
     """A maximal group of LCE ops with no builtin operator between them: operator indices in execution order, the
     non-constant tensors it reads from outside, the tensors it must deliver (read outside it, or graph outputs)."""
@@ -130,24 +148,13 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_open_opts.restype = C.c_void_p
         l.lce_tflite_model_open_opts.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t]   # either form of the options
         l.lce_tflite_model_operator_pool2d.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        l.lce_tflite_model_pool_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
-        l.lce_tflite_model_pool_stats.restype = None
         l.lce_tflite_model_operator_conv2d.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        l.lce_tflite_model_conv1x1_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
-        l.lce_tflite_model_conv1x1_stats.restype = None
         l.lce_tflite_model_operator_depthwise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        l.lce_tflite_model_depthwise_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
-        l.lce_tflite_model_depthwise_stats.restype = None
-        l.lce_tflite_model_conv2d_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
-        l.lce_tflite_model_conv2d_stats.restype = None
         l.lce_tflite_model_operator_axis.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        l.lce_tflite_model_concat_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
-        l.lce_tflite_model_concat_stats.restype = None
         l.lce_tflite_model_operator_activation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        l.lce_tflite_model_elementwise_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
-        l.lce_tflite_model_elementwise_stats.restype = None
-        l.lce_tflite_model_int8_add_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2
-        l.lce_tflite_model_int8_add_stats.restype = None
+        for name, counters in _PASS_STATS.items():
+            f = getattr(l, "lce_tflite_model_%s_stats" % name)
+            f.argtypes, f.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * counters, None
         l.lce_tflite_model_close.argtypes = [C.c_void_p]
         for f in ("lce_tflite_model_num_tensors", "lce_tflite_model_num_operators"):
             getattr(l, f).argtypes = [C.c_void_p]
@@ -230,34 +237,21 @@ class LceModel:
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
         self._data = bytes(flatbuffer)            # must outlive the handle (zero-copy reader)
-        self.elementwise_sections = bool(elementwise_sections)
-        self.int8_add_sections = bool(int8_add_sections)
-        self.concat_sections = bool(concat_sections)
-        self.pool_sections = bool(pool_sections)
-        self.conv1x1_sections = bool(conv1x1_sections)
-        self.depthwise_sections = bool(depthwise_sections)
-        self.conv2d_sections = bool(conv2d_sections)
-        self.stem_sections = bool(stem_sections)
+        given = dict(elementwise_sections=elementwise_sections, int8_add_sections=int8_add_sections, concat_sections=concat_sections,
+                     pool_sections=pool_sections, conv1x1_sections=conv1x1_sections, depthwise_sections=depthwise_sections,
+                     conv2d_sections=conv2d_sections, stem_sections=stem_sections)
+        words, size = [0, 0], 0               # the two flag words, and the smallest form that carries every bit asked for
+        for keyword, word, bit, form in _SECTION_KEYWORDS:
+            setattr(self, keyword, bool(given[keyword]))
+            if given[keyword]:
+                words[word] |= bit
+                size = max(size, form)
         err = C.create_string_buffer(256)
-        flags = (SECTIONS_ELEMENTWISE if elementwise_sections else 0) | (SECTIONS_INT8_ADD if int8_add_sections else 0)
-        if depthwise_sections or conv2d_sections or stem_sections:
-            opts = _OpenOptions56(C.sizeof(_OpenOptions56), flags | (SECTIONS_CONCAT if concat_sections else 0),
-                                  (SECTIONS_EXT_DEPTHWISE if depthwise_sections else 0) | (SECTIONS_EXT_CONV2D if conv2d_sections else 0) |
-                                  (SECTIONS_EXT_STEM if stem_sections else 0) | (SECTIONS_EXT_CONV1X1 if conv1x1_sections else 0) |
-                                  (SECTIONS_EXT_POOL if pool_sections else 0))
-            self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
-        elif conv1x1_sections:
-            opts = _OpenOptions40(C.sizeof(_OpenOptions40), flags | (SECTIONS_CONCAT if concat_sections else 0),
-                                  SECTIONS_EXT_CONV1X1 | (SECTIONS_EXT_POOL if pool_sections else 0))
-            self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
-        elif pool_sections:
-            opts = _OpenOptionsExt(C.sizeof(_OpenOptionsExt), flags | (SECTIONS_CONCAT if concat_sections else 0), SECTIONS_EXT_POOL)
-            self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
-        elif concat_sections:
-            opts = _OpenOptions(C.sizeof(_OpenOptions), flags | SECTIONS_CONCAT)
+        if size:
+            opts = _OPEN_OPTIONS[size](size, *words[:1 if size == 8 else 2])
             self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
         else:
-            self._h = tflite_lib().lce_tflite_model_open_ex(self._data, len(self._data), flags, err, 256)
+            self._h = tflite_lib().lce_tflite_model_open_ex(self._data, len(self._data), words[0], err, 256)
         if not self._h:
             raise ValueError("not a readable TFLite model: " + err.value.decode(errors="replace"))
         l = tflite_lib()
@@ -323,47 +317,39 @@ class LceModel:
         tflite_lib().lce_tflite_model_run_stats(self._h, C.byref(a), C.byref(b), C.byref(c))
         return int(a.value), int(b.value), int(c.value)
 
+    def _pass_stats(self, name):
+        """The counters of ``lce_tflite_model_<name>_stats``."""
+        v = [C.c_int32() for _ in range(_PASS_STATS[name])]
+        getattr(tflite_lib(), "lce_tflite_model_%s_stats" % name)(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
     def elementwise_stats(self):
         """(lce_hip_elementwise launches, ADD / MUL operators they ran, LceQuantize launches they absorbed) of the last run."""
-        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
-        tflite_lib().lce_tflite_model_elementwise_stats(self._h, C.byref(a), C.byref(b), C.byref(c))
-        return int(a.value), int(b.value), int(c.value)
+        return self._pass_stats("elementwise")
 
     def int8_add_stats(self):
         """(lce_hip_add_int8 launches, LceQuantize launches they absorbed) of the last run."""
-        a, b = C.c_int32(), C.c_int32()
-        tflite_lib().lce_tflite_model_int8_add_stats(self._h, C.byref(a), C.byref(b))
-        return int(a.value), int(b.value)
+        return self._pass_stats("int8_add")
 
     def concat_stats(self):
         """(lce_hip_concat launches, LceQuantize launches they absorbed) of the last run."""
-        a, b = C.c_int32(), C.c_int32()
-        tflite_lib().lce_tflite_model_concat_stats(self._h, C.byref(a), C.byref(b))
-        return int(a.value), int(b.value)
+        return self._pass_stats("concat")
 
     def pool_stats(self):
         """(lce_hip_pool2d launches, LceQuantize launches they absorbed) of the last run."""
-        a, b = C.c_int32(), C.c_int32()
-        tflite_lib().lce_tflite_model_pool_stats(self._h, C.byref(a), C.byref(b))
-        return int(a.value), int(b.value)
+        return self._pass_stats("pool")
 
     def conv1x1_stats(self):
         """(lce_hip_conv1x1_f32 launches, LceQuantize launches they absorbed) of the last run."""
-        a, b = C.c_int32(), C.c_int32()
-        tflite_lib().lce_tflite_model_conv1x1_stats(self._h, C.byref(a), C.byref(b))
-        return int(a.value), int(b.value)
+        return self._pass_stats("conv1x1")
 
     def depthwise_stats(self):
         """(lce_hip_depthwise_conv2d_f32 launches, LceQuantize launches they absorbed) of the last run."""
-        a, b = C.c_int32(), C.c_int32()
-        tflite_lib().lce_tflite_model_depthwise_stats(self._h, C.byref(a), C.byref(b))
-        return int(a.value), int(b.value)
+        return self._pass_stats("depthwise")
 
     def conv2d_stats(self):
         """(lce_hip_conv2d_f32 calls, LceQuantize launches they absorbed) of the last run."""
-        a, b = C.c_int32(), C.c_int32()
-        tflite_lib().lce_tflite_model_conv2d_stats(self._h, C.byref(a), C.byref(b))
-        return int(a.value), int(b.value)
+        return self._pass_stats("conv2d")
 
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
@@ -408,7 +394,7 @@ class Interpreter:
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.elementwise_sections or self.model.int8_add_sections or self.model.concat_sections or self.model.pool_sections or self.model.conv1x1_sections or self.model.depthwise_sections or self.model.conv2d_sections or self.model.stem_sections:
+        if any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

@@ -13,93 +13,13 @@ import pytest
 
 import hipcc_lib as H
 import oracle_lib as O
+from section_models import (ADD, CONCATENATION, DENSE_STAGES, MUL, NONE, RELU, _conv, _sections_of, bconv_options, concat_op,
+                            cut_at, dense_block_model, ew_op, joins_of, mixed_model)
 import synth
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, ew_op
-from test_model_reader_host import bconv_options, mixed_model
 from tflite_writer import ModelBuilder, _Scalar, _Table, _Vector
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
-
-CONCATENATION = 2                      # schema.fbs BuiltinOperator
-CONCATENATION_OPTIONS = 10             # schema.fbs BuiltinOptions
-
-
-def concat_op(b: ModelBuilder, inputs, outputs, axis=3, activation=NONE) -> int:
-    """A builtin CONCATENATION with its ConcatenationOptions table (0 axis, 1 fused_activation_function) -- or without one
-    when axis is None."""
-    fields = {0: _Scalar("I", b._code(None, CONCATENATION)), 1: _Vector("i", list(inputs)), 2: _Vector("i", list(outputs))}
-    if axis is not None:
-        fields[3] = _Scalar("B", CONCATENATION_OPTIONS)
-        fields[4] = _Table({0: _Scalar("i", axis), 1: _Scalar("b", activation)})
-    b.ops.append(_Table(fields))
-    return len(b.ops) - 1
-
-
-def _conv(b, src_bits, H, C, cout, seed, stride=1, out_type=np.float32, quant=None, k=3):
-    """LceBconv2d (k x k SAME, one-padding) on the bitpacked tensor `src_bits`; returns (output tensor, its constants)."""
-    spec = O.ConvSpec(1, H, H, C, k, k, cout, stride_h=stride, stride_w=stride, padding=O.PADDING_SAME, pad_values=1)
-    _, w, m, bias = synth.conv_inputs(spec, seed)
-    if quant is not None:
-        m = (m * np.float32(0.05)).astype(np.float32)
-    oh = spec.out_h
-    kw = {} if quant is None else dict(scale=quant[0], zero_point=quant[1])
-    y = b.tensor([1, oh, oh, cout], out_type, "y%d" % seed, **kw)
-    f32 = lambda shape, name, data: b.tensor(shape, np.float32, name, data)
-    b.custom_op("LceBconv2d", [src_bits, b.tensor(w.shape, np.int32, "w%d" % seed, w), f32([cout], "m%d" % seed, m),
-                               f32([cout], "b%d" % seed, bias), -1], [y], bconv_options(spec))
-    return y, dict(spec=spec, w=w, m=m, b=bias, y=y)
-
-
-# growth per dense layer of the two stages (a tuple: several convolutions of one layer, joined at once); 10 is ragged
-DENSE_STAGES = ((64, 10, (32, 32)), (64, 32, 64))
-
-
-def dense_block_model(H=16, C0=64, stages=DENSE_STAGES, transition=128, seed=0):
-    """x (float [1,H,H,C0]) -> LceQuantize -> LceBconv2d -> y0, then per dense layer
-         x -> MUL (bn) -> ADD (bn) -> LceQuantize -> LceBconv2d (3x3, C -> G, float) [x n] -> CONCATENATION([x, y...]) -> x'
-    at two resolutions with a stride-2 binary layer (LceQuantize -> LceBconv2d) between them; the last x' is the graph output.
-    Returns (file, input tensor, output tensor, steps): steps is the program in order -- dicts with kind "conv" (the leading
-    and the stride-2 layer), or "dense" (bn_m, bn_a, mul / add / join: operator indices, convs, out: joined tensor)."""
-    b = ModelBuilder()
-    f32 = lambda shape, name, data=None: b.tensor(shape, np.float32, name, data)
-    x0 = f32([1, H, H, C0], "x")
-    steps = []
-    n = [seed * 100]
-
-    def binary_layer(src, h, c, cout, stride):
-        n[0] += 1
-        q = b.tensor([1, h, h, (c + 31) // 32], np.int32, "q%d" % n[0])
-        b.custom_op("LceQuantize", [src], [q], b"")
-        y, info = _conv(b, q, h, c, cout, n[0], stride)
-        steps.append(dict(kind="conv", **info))
-        return y
-
-    x, h, c = binary_layer(x0, H, C0, C0, 1), H, C0
-    for s, growths in enumerate(stages):
-        if s:
-            x, h, c = binary_layer(x, h, c, transition, 2), h // 2, transition
-        for growth in growths:
-            n[0] += 1
-            g = synth.rng(n[0] + 1000)
-            bn_m = g.uniform(0.5, 1.5, c).astype(np.float32)
-            bn_a = g.standard_normal(c).astype(np.float32)
-            mm, a = f32([1, h, h, c], "bnm%d" % n[0]), f32([1, h, h, c], "bna%d" % n[0])
-            mul = ew_op(b, MUL, [x, f32([c], "bn_mul%d" % n[0], bn_m)], [mm], NONE)
-            add = ew_op(b, ADD, [mm, f32([1, 1, 1, c], "bn_add%d" % n[0], bn_a.reshape(1, 1, 1, c))], [a], NONE)
-            q = b.tensor([1, h, h, (c + 31) // 32], np.int32, "q%d" % n[0])
-            b.custom_op("LceQuantize", [a], [q], b"")
-            convs = []
-            for j, cout in enumerate(growth if isinstance(growth, tuple) else (growth,)):
-                n[0] += 1
-                convs.append(_conv(b, q, h, c, cout, n[0], k=3 if j == 0 else 1)[1])
-            c2 = c + sum(cv["spec"].channels_out for cv in convs)
-            out = f32([1, h, h, c2], "x%d" % n[0])
-            join = concat_op(b, [x] + [cv["y"] for cv in convs], [out], axis=3 if len(steps) % 2 else -1)
-            steps.append(dict(kind="dense", bn_m=bn_m, bn_a=bn_a, convs=convs, join=join, out=out, x=x, mul=mul, add=add))
-            x, c = out, c2
-    b.inputs, b.outputs = [x0], [x]
-    return b.finish(), x0, x, steps
 
 
 INT8_GROWTHS = (64, 16, 17, 31)
@@ -135,22 +55,6 @@ def int8_dense_model(H=16, C0=64, growths=INT8_GROWTHS, seed=0):
     steps.append(dict(kind="conv", zp=INT8_Q[1], **info))
     b.inputs, b.outputs = [x0], [y]
     return b.finish(), x0, y, steps
-
-
-def joins_of(steps):
-    return [s["join"] for s in steps if s["kind"] == "dense"]
-
-
-def cut_at(n_ops, cuts):
-    """Operator runs between the operators `cuts`: the partition of a chain-like graph whose only foreign operators they are."""
-    want, cur = [], []
-    for i in range(n_ops):
-        if i in cuts:
-            want.append(cur)
-            cur = []
-        else:
-            cur.append(i)
-    return [s for s in want + [cur] if s]
 
 
 def bn(v, m, a):
@@ -520,18 +424,6 @@ def test_python_checks_fail_before_any_device_call(monkeypatch, tensors, kw, msg
     monkeypatch.setattr(amd, "lib", no_device)
     with pytest.raises(ValueError, match=msg):
         amd.concat(tensors, **kw)
-
-
-# ---- the entry points ---------------------------------------------------------------------------------------------------------
-def _sections_of(handle):
-    lib = mr.tflite_lib()
-    out = []
-    for i in range(lib.lce_tflite_model_num_sections(handle)):
-        info = mr._SectionInfo()
-        assert lib.lce_tflite_model_section(handle, i, C.byref(info)) == amd.OK
-        s = mr.Section(info)
-        out.append((s.ops, s.inputs, s.outputs))
-    return out
 
 
 def test_open_opts():

@@ -15,37 +15,18 @@ import pytest
 import conv1x1_ref as R
 import hipcc_lib as H
 import oracle_lib as O
+from section_models import (ADD, CONV_2D, DEPTHWISE_CONV_2D, F32_SPECIAL, MARK, MAX_POOL_2D, MUL, NONE, RELU, RELU6, RELU_N1_TO_1,
+                            TANH, _conv, _open, _options_table, _sections_of, alexnet_body_model, bconv_options,
+                            bireal_block_model, conv2d_op, cut_at, dense_block_model, ew_op, float_fixture, mixed_model, pool_op)
 import synth
-from test_concat_sections_host import _conv, _sections_of, cut_at, dense_block_model
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, ew_op
-from test_model_reader_host import bconv_options, mixed_model
-from test_pool_sections_host import AVERAGE_POOL_2D, MARK, MAX_POOL_2D, _open, _options_table, alexnet_body_model, pool_op
 from tflite_writer import ModelBuilder, _Scalar, _Table, _Vector
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
 
-CONV_2D, DEPTHWISE_CONV_2D = 3, 4      # schema.fbs BuiltinOperator
-CONV_2D_OPTIONS = 1                    # schema.fbs BuiltinOptions
 SAME, VALID = 0, 1
 ACTS = (NONE, RELU, RELU_N1_TO_1, RELU6)
 ALL_FLAGS = dict(elementwise_sections=True, pool_sections=True, conv1x1_sections=True)
-
-
-def conv2d_op(b: ModelBuilder, inputs, outputs, stride=(1, 1), padding=SAME, activation=NONE, dilation=(1, 1), options=True,
-              code=CONV_2D) -> int:
-    """A builtin CONV_2D with its Conv2DOptions table (0 padding, 1 stride_w, 2 stride_h, 3 fused_activation_function,
-    4 dilation_w_factor, 5 dilation_h_factor) -- without the dilations when dilation is None (the schema's default 1 holds), or
-    without a table when options is False.  stride and dilation are (height, width)."""
-    fields = {0: _Scalar("I", b._code(None, code)), 1: _Vector("i", list(inputs)), 2: _Vector("i", list(outputs))}
-    if options:
-        t = {0: _Scalar("b", padding), 1: _Scalar("i", stride[1]), 2: _Scalar("i", stride[0]), 3: _Scalar("b", activation)}
-        if dilation is not None:
-            t[4], t[5] = _Scalar("i", dilation[1]), _Scalar("i", dilation[0])
-        fields[3] = _Scalar("B", CONV_2D_OPTIONS)
-        fields[4] = _Table(t)
-    b.ops.append(_Table(fields))
-    return len(b.ops) - 1
 
 
 # ---- the reference against its definition ----------------------------------------------------------------------------------------
@@ -171,30 +152,11 @@ def test_strides_select_pixels_and_the_clamp_passes_nan():
         assert set(got[0, 0, 1].tolist()) <= {float(lo), float(hi)}          # an infinity is clamped, NONE included
 
 
-# ---- the fixtures of the GPU side -----------------------------------------------------------------------------------------------
-F32_SPECIAL = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00001, 0x00000001, 0x80000001,
-                        0x007FFFFF, 0x807FFFFF], np.uint32).view(np.float32)   # +-0, +-inf, NaNs, smallest / largest subnormals
 GRID_IMAGES = [(1, 1), (5, 7), (8, 8)]
 GRID_BATCHES = (1, 3)
 GRID_CIN = (1, 2, 3, 31, 32, 33, 64, 65, 160)
 GRID_COUT = (1, 31, 32, 33, 64, 96, 160)
 GRID_STRIDES = ((1, 1), (2, 2), (2, 1))
-
-
-def float_fixture(shape, seed, special=False):
-    """Mixed-magnitude normals (products and sums round at every step).  `special`: every third pixel scaled into the
-    subnormals (subnormal inputs and results), +-0 and subnormals planted everywhere, +-inf and NaN in every third pixel."""
-    g = np.random.default_rng(seed)
-    x = (g.standard_normal(shape) * g.choice([1e-3, 1.0, 3.0, 1e4], shape)).astype(np.float32)
-    if special:
-        rows = x.reshape(-1, shape[-1])
-        rows[1::3] *= np.float32(1e-41)
-        k = max(1, rows.size // 9)
-        r, c = g.integers(0, rows.shape[0], k), g.integers(0, shape[-1], k)
-        v = F32_SPECIAL[g.integers(0, F32_SPECIAL.size, k)]
-        keep = (r % 3 == 0) | np.isfinite(v)
-        rows[r[keep], c[keep]] = v[keep]
-    return x
 
 
 def grid_operands(cin, cout, special=False):
@@ -227,43 +189,6 @@ def test_the_grid_fixtures_are_what_the_checks_need():
     assert np.isnan(got).any() and np.isinf(xs).any() and np.any((got != 0) & (np.abs(got) < 1e-38))
     one = R.conv1x1(float_fixture((3, 5, 7, 1), 9, special=True), grid_operands(1, 33, special=True)[0])
     assert np.any(np.signbit(one) & (one == 0)) and np.any(~np.signbit(one) & (one == 0))
-
-
-def bireal_block_model(H=8, C=64, seed=0):
-    """A Bi-RealNet-style downsampling block.  x (float) -> LceQuantize -> LceBconv2d (float) -> r;
-    main: r -> LceQuantize -> LceBconv2d 3x3 / 2 (C -> 2C) -> MUL (c) -> ADD (c) -> aa;
-    shortcut: r -> AVERAGE_POOL_2D 2x2 / 2 -> CONV_2D 1x1 (C -> 2C) + bias -> s;
-    ADD (aa, s) -> LceQuantize -> LceBconv2d (float, the graph output).  Returns (file, input tensor, output tensor, info)."""
-    b = ModelBuilder()
-    f32 = lambda shape, name, data=None: b.tensor(shape, np.float32, name, data)
-    g = synth.rng(seed + 301)
-    h2, c2 = H // 2, 2 * C
-    x = f32([1, H, H, C], "x")
-    q0 = b.tensor([1, H, H, C // 32], np.int32, "q0")
-    b.custom_op("LceQuantize", [x], [q0], b"")
-    r, c0 = _conv(b, q0, H, C, C, seed * 10 + 1)
-    q1 = b.tensor([1, H, H, C // 32], np.int32, "q1")
-    b.custom_op("LceQuantize", [r], [q1], b"")
-    y1, c1 = _conv(b, q1, H, C, c2, seed * 10 + 2, stride=2)
-    bn_m, bn_a = g.uniform(-1.5, 1.5, c2).astype(np.float32), g.standard_normal(c2).astype(np.float32)
-    mm, aa = f32([1, h2, h2, c2], "mm"), f32([1, h2, h2, c2], "aa")
-    mul = ew_op(b, MUL, [y1, f32([c2], "bn_m", bn_m)], [mm], NONE)
-    add = ew_op(b, ADD, [mm, f32([c2], "bn_a", bn_a)], [aa], NONE)
-    p = f32([1, h2, h2, C], "p")
-    pool = pool_op(b, AVERAGE_POOL_2D, [r], [p], (2, 2), (2, 2), VALID)
-    w = (g.standard_normal((c2, 1, 1, C)) * 0.2).astype(np.float32)
-    wb = (g.standard_normal(c2) * 8).astype(np.float32)
-    s = f32([1, h2, h2, c2], "s")
-    conv = conv2d_op(b, [p, f32([c2, 1, 1, C], "w", w), f32([c2], "wb", wb)], [s], (1, 1), SAME)
-    rr = f32([1, h2, h2, c2], "rr")
-    join = ew_op(b, ADD, [aa, s], [rr], NONE)
-    q2 = b.tensor([1, h2, h2, c2 // 32], np.int32, "q2")
-    b.custom_op("LceQuantize", [rr], [q2], b"")
-    y2, c3 = _conv(b, q2, h2, c2, c2, seed * 10 + 3)
-    b.inputs, b.outputs = [x], [y2]
-    info = dict(convs=[c0, c1, c3], bn_m=bn_m, bn_a=bn_a, mul=mul, add=add, pools=[pool], conv1x1=conv, join=join, w=w, wb=wb,
-                tensors=dict(r=r, p=p, s=s, aa=aa, rr=rr), size=H, channels=C)
-    return b.finish(), x, y2, info
 
 
 def dense_transition_model(H=8, C=64, seed=0):

@@ -6,6 +6,7 @@ tiles than one pass of a capped grid on both pixel enumerations.  What a simulat
 a chain -- is the GPU suite's (tests/test_gpu_conv2d.py)."""
 import ctypes as C
 import os
+from section_models import float_fixture
 import subprocess
 
 import numpy as np
@@ -13,7 +14,7 @@ import pytest
 
 import conv2d_ref as R
 import oracle_lib as O
-from test_conv2d_sections_host import ACTS, KNOWN, float_fixture, grid_operands, known_case
+from test_conv2d_sections_host import ACTS, KNOWN, grid_operands, known_case
 
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_conv2d")
 OUT_MARK, BITS_MARK = np.float32(777), 0x55555555

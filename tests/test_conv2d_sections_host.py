@@ -19,20 +19,17 @@ import depthwise_ref as DR
 import hipcc_lib as H
 import oracle_lib as O
 import pool_ref as PR
+from section_models import (ADD, CONV_2D, DEPTHWISE_CONV_2D, F32_SPECIAL, MAX_POOL_2D, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH,
+                            _conv, _open, _sections_of, alexnet_body_model, bconv_options, bireal_block_model, conv2d_op,
+                            dense_block_model, depthwise_op, ew_op, float_fixture, float_op, mixed_model, pool_op,
+                            quicknet_transition_model)
 import synth
-from test_concat_sections_host import _conv, _sections_of
-from test_conv1x1_sections_host import F32_SPECIAL, conv2d_op, float_fixture  # noqa: F401  (the GPU side's)
-from test_depthwise_sections_host import depthwise_op, float_op
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, ew_op
-from test_model_reader_host import bconv_options
-from test_pool_sections_host import MAX_POOL_2D, _open, pool_op
 from tflite_writer import ModelBuilder
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
 Conv2dDesc, conv2d_check = amd.Conv2dDesc, amd._conv2d_check      # (the binding under test: nothing here runs without it)
 
-CONV_2D, DEPTHWISE_CONV_2D = 3, 4      # schema.fbs BuiltinOperator
 SAME, VALID = 0, 1
 SIGN_BIT = 5
 ACTS = (NONE, RELU, RELU_N1_TO_1, RELU6)
@@ -426,11 +423,6 @@ def test_a_stem_operator_that_is_no_candidate_still_opens_a_builtin_epoch():
 
 
 def test_files_without_a_qualifying_operator_keep_their_partitions():
-    from test_concat_sections_host import dense_block_model
-    from test_conv1x1_sections_host import bireal_block_model
-    from test_depthwise_sections_host import quicknet_transition_model
-    from test_model_reader_host import mixed_model
-    from test_pool_sections_host import alexnet_body_model
     for data in (dense_block_model()[0], mixed_model()[0], alexnet_body_model()[0], bireal_block_model()[0], quicknet_transition_model()[0]):
         for kw in ({}, dict(elementwise_sections=True), dict(concat_sections=True, **PARENT_FLAGS)):
             want = _parts(mr.LceModel(data, **kw))

@@ -17,46 +17,20 @@ import depthwise_ref as R
 import hipcc_lib as H
 import oracle_lib as O
 import pool_ref as PR
+from section_models import (ADD, CONV_2D, CONV_2D_OPTIONS, DEPTHWISE_CONV_2D, F32_SPECIAL, MARK, MAX_POOL_2D, MUL, NONE, RELU,
+                            RELU6, RELU_N1_TO_1, TANH, _conv, _open, _sections_of, alexnet_body_model, bconv_options,
+                            bireal_block_model, conv2d_op, cut_at, dense_block_model, depthwise_op, ew_op, float_fixture,
+                            float_op, mixed_model, pool_op, quicknet_transition_model)
 import synth
-from test_concat_sections_host import _conv, _sections_of, cut_at
-from test_conv1x1_sections_host import F32_SPECIAL, bireal_block_model, conv2d_op, float_fixture  # noqa: F401  (the GPU side's)
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, ew_op
-from test_model_reader_host import bconv_options, mixed_model
-from test_pool_sections_host import MARK, MAX_POOL_2D, _open, pool_op
 from tflite_writer import ModelBuilder, _Scalar, _Table, _Vector
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
 
-CONV_2D, DEPTHWISE_CONV_2D = 3, 4      # schema.fbs BuiltinOperator
-CONV_2D_OPTIONS, DEPTHWISE_CONV_2D_OPTIONS = 1, 2      # schema.fbs BuiltinOptions
 SAME, VALID = 0, 1
 ACTS = (NONE, RELU, RELU_N1_TO_1, RELU6)
 OLD_FLAGS = dict(elementwise_sections=True, pool_sections=True, conv1x1_sections=True)
 ALL_FLAGS = dict(depthwise_sections=True, **OLD_FLAGS)
-
-
-def depthwise_op(b: ModelBuilder, inputs, outputs, stride=(1, 1), padding=SAME, multiplier=1, activation=NONE, dilation=(1, 1),
-                 options=True, code=DEPTHWISE_CONV_2D) -> int:
-    """A builtin DEPTHWISE_CONV_2D with its DepthwiseConv2DOptions table (0 padding, 1 stride_w, 2 stride_h, 3 depth_multiplier,
-    4 fused_activation_function, 5 dilation_w_factor, 6 dilation_h_factor) -- without the dilations when dilation is None (the
-    schema's default 1 holds), or without a table when options is False.  stride and dilation are (height, width)."""
-    fields = {0: _Scalar("I", b._code(None, code)), 1: _Vector("i", list(inputs)), 2: _Vector("i", list(outputs))}
-    if options:
-        t = {0: _Scalar("b", padding), 1: _Scalar("i", stride[1]), 2: _Scalar("i", stride[0]), 3: _Scalar("i", multiplier),
-             4: _Scalar("b", activation)}
-        if dilation is not None:
-            t[5], t[6] = _Scalar("i", dilation[1]), _Scalar("i", dilation[0])
-        fields[3] = _Scalar("B", DEPTHWISE_CONV_2D_OPTIONS)
-        fields[4] = _Table(t)
-    b.ops.append(_Table(fields))
-    return len(b.ops) - 1
-
-
-def float_op(v, op, operand, act):
-    """TFLite's float MUL / ADD: one rounding, then the clamp (std::max / std::min: a NaN passes)."""
-    with np.errstate(invalid="ignore", over="ignore"):
-        return R.clamp((v * operand if op == MUL else v + operand).astype(np.float32), act)
 
 
 # ---- the reference against its definition ----------------------------------------------------------------------------------------
@@ -202,53 +176,6 @@ def test_the_clamp_passes_nan_and_every_activation_clamps():
         assert set(got[0, 3:, 5:, 1].reshape(-1).tolist()) <= {float(lo), float(hi)}     # an infinity is clamped, NONE included
 
 
-# ---- the fixtures of the GPU side -----------------------------------------------------------------------------------------------
-def quicknet_transition_model(H=8, C=32, seed=0):
-    """A QuickNet residual layer and the transition behind it.  x (float) -> LceQuantize -> LceBconv2d (3x3, float) -> MUL (c)
-    -> ADD (c) -> ADD (x, RELU) -> MAX_POOL_2D 2x2 / 1 SAME -> DEPTHWISE_CONV_2D 3x3 / 2 SAME (the blur [1 2 1] x [1 2 1] / 16,
-    no bias) -> CONV_2D 1x1 (C -> 2C, with bias: the folded batch norm) -> LceQuantize -> LceBconv2d (3x3, float) -> MUL (c) ->
-    ADD (c), the graph output.  This layer order is QuickNet's as remembered (its transition: ReLU, max pool, blur pool, pointwise
-    convolution, batch norm); larq_zoo was not available to check it against.  Returns (file, input tensor, output tensor, info);
-    info["host"]: operator index -> what the host computes for it from its non-constant inputs."""
-    b = ModelBuilder()
-    f32 = lambda shape, name, data=None: b.tensor(shape, np.float32, name, data)
-    g = synth.rng(seed + 501)
-    h2, c2 = H // 2, 2 * C
-    x = f32([1, H, H, C], "x")
-    q0 = b.tensor([1, H, H, (C + 31) // 32], np.int32, "q0")
-    b.custom_op("LceQuantize", [x], [q0], b"")
-    y0, c0 = _conv(b, q0, H, C, C, seed * 10 + 1)
-    bn_m, bn_a = g.uniform(0.5, 1.5, C).astype(np.float32), g.standard_normal(C).astype(np.float32)
-    mm, aa, r = f32([1, H, H, C], "mm"), f32([1, H, H, C], "aa"), f32([1, H, H, C], "r")
-    mul = ew_op(b, MUL, [y0, f32([C], "bn_m", bn_m)], [mm], NONE)
-    add = ew_op(b, ADD, [mm, f32([C], "bn_a", bn_a)], [aa], NONE)
-    res = ew_op(b, ADD, [aa, x], [r], RELU)
-    p = f32([1, H, H, C], "p")
-    pool = pool_op(b, MAX_POOL_2D, [r], [p], (2, 2), (1, 1), SAME)
-    blur = np.ascontiguousarray(np.broadcast_to(R.BLUR[None, :, :, None], (1, 3, 3, C)))
-    d = f32([1, h2, h2, C], "d")
-    dw = depthwise_op(b, [p, f32([1, 3, 3, C], "blur", blur)], [d], (2, 2), SAME)
-    w = (g.standard_normal((c2, 1, 1, C)) * 0.2).astype(np.float32)
-    wb = (g.standard_normal(c2) * 2).astype(np.float32)
-    t = f32([1, h2, h2, c2], "t")
-    conv = conv2d_op(b, [d, f32([c2, 1, 1, C], "w", w), f32([c2], "wb", wb)], [t], (1, 1), SAME)
-    q1 = b.tensor([1, h2, h2, c2 // 32], np.int32, "q1")
-    b.custom_op("LceQuantize", [t], [q1], b"")
-    y1, c1 = _conv(b, q1, h2, c2, c2, seed * 10 + 2)
-    bn_m2, bn_a2 = g.uniform(0.5, 1.5, c2).astype(np.float32), g.standard_normal(c2).astype(np.float32)
-    mm2, out = f32([1, h2, h2, c2], "mm2"), f32([1, h2, h2, c2], "out")
-    mul2 = ew_op(b, MUL, [y1, f32([c2], "bn_m2", bn_m2)], [mm2], NONE)
-    add2 = ew_op(b, ADD, [mm2, f32([c2], "bn_a2", bn_a2)], [out], NONE)
-    b.inputs, b.outputs = [x], [out]
-    host = {mul: lambda v: float_op(v, MUL, bn_m, NONE), add: lambda v: float_op(v, ADD, bn_a, NONE),
-            res: lambda a, s: float_op(a, ADD, s, RELU), pool: lambda v: PR.pool2d(v, PR.MAX, (2, 2), (1, 1), PR.SAME),
-            dw: lambda v: R.depthwise(v, blur, None, (2, 2), SAME), conv: lambda v: CR.conv1x1(v, w, wb),
-            mul2: lambda v: float_op(v, MUL, bn_m2, NONE), add2: lambda v: float_op(v, ADD, bn_a2, NONE)}
-    info = dict(depthwise=dw, conv1x1=conv, host=host, tensors=dict(r=r, p=p, d=d, t=t), size=H, channels=C, convs=[c0, c1],
-                follows=[conv], w=w, wb=wb)
-    return b.finish(), x, out, info
-
-
 def blur_then_binarize_model(H=8, C=64, seed=0):
     """The fold case.  x (float) -> LceQuantize -> LceBconv2d (float) -> MUL (c) -> ADD (c, RELU_N1_TO_1) -> DEPTHWISE_CONV_2D
     3x3 / 2 SAME (signed weights and a bias, so that both signs come out) -> LceQuantize -> LceBconv2d (float, the graph
@@ -322,8 +249,6 @@ def test_a_stem_depthwise_stays_with_the_host_under_every_flag():
 
 
 def test_files_without_a_qualifying_depthwise_keep_their_partitions():
-    from test_concat_sections_host import dense_block_model
-    from test_pool_sections_host import alexnet_body_model
     for data in (dense_block_model()[0], mixed_model()[0], alexnet_body_model()[0], bireal_block_model()[0]):
         for kw in ({}, dict(elementwise_sections=True), dict(concat_sections=True, **OLD_FLAGS)):
             assert _parts(mr.LceModel(data, **kw)) == _parts(mr.LceModel(data, depthwise_sections=True, **kw))

@@ -11,71 +11,13 @@ import pytest
 
 import hipcc_lib as H
 import oracle_lib as O
+from section_models import (ADD, BODY, CONV_2D, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, SUB, TANH, bconv_options, body_model, ew_op,
+                            layer, mixed_model)
 import synth
-from test_model_reader_host import bconv_options, mixed_model
 from tflite_writer import ModelBuilder, _Scalar, _Table, _Vector
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
-
-ADD, MUL, SUB, CONV_2D = 0, 18, 41, 3           # schema.fbs BuiltinOperator
-ADD_OPTIONS, MUL_OPTIONS = 11, 21               # schema.fbs BuiltinOptions
-NONE, RELU, RELU_N1_TO_1, RELU6, TANH = 0, 1, 2, 3, 4
-
-
-def ew_op(b: ModelBuilder, code: int, inputs, outputs, activation=None) -> int:
-    """A builtin operator with an AddOptions / MulOptions table (fields 3/4 of Operator) -- or none when activation is None."""
-    fields = {0: _Scalar("I", b._code(None, code)), 1: _Vector("i", list(inputs)), 2: _Vector("i", list(outputs))}
-    if activation is not None:
-        fields[3] = _Scalar("B", MUL_OPTIONS if code == MUL else ADD_OPTIONS)
-        fields[4] = _Table({0: _Scalar("b", activation)})
-    b.ops.append(_Table(fields))
-    return len(b.ops) - 1
-
-
-def layer(b, r_prev, H, C, cout, seed, stride=1, residual=True, act=RELU):
-    """One QuickNet-style binary layer: LceQuantize -> LceBconv2d (3x3 SAME, float) -> MUL (BN) -> ADD (BN) [-> ADD residual].
-    Returns (output tensor, the layer's constants)."""
-    spec = O.ConvSpec(1, H, H, C, 3, 3, cout, stride_h=stride, stride_w=stride, padding=O.PADDING_SAME, pad_values=1)
-    _, w, m, bias = synth.conv_inputs(spec, seed)
-    g = synth.rng(seed + 1000)
-    bn_m = g.uniform(0.5, 1.5, cout).astype(np.float32)
-    bn_a = g.standard_normal(cout).astype(np.float32)
-    oh = spec.out_h
-    f32 = lambda shape, name, data=None: b.tensor(shape, np.float32, name, data)
-    q = b.tensor([1, H, H, (C + 31) // 32], np.int32, "q%d" % seed)
-    tw = b.tensor(w.shape, np.int32, "w%d" % seed, w)
-    y, mm, a = f32([1, oh, oh, cout], "y%d" % seed), f32([1, oh, oh, cout], "bnm%d" % seed), f32([1, oh, oh, cout], "bna%d" % seed)
-    b.custom_op("LceQuantize", [r_prev], [q], b"")
-    b.custom_op("LceBconv2d", [q, tw, f32([cout], "m%d" % seed, m), f32([cout], "b%d" % seed, bias), -1], [y], bconv_options(spec))
-    ew_op(b, MUL, [y, f32([cout], "bn_mul%d" % seed, bn_m)], [mm], NONE)
-    if not residual:
-        ew_op(b, ADD, [mm, f32([1, 1, 1, cout], "bn_add%d" % seed, bn_a.reshape(1, 1, 1, cout))], [a], act)
-        return a, dict(spec=spec, w=w, m=m, b=bias, bn_m=bn_m, bn_a=bn_a, residual=False, act=act)
-    ew_op(b, ADD, [mm, f32([1, 1, 1, cout], "bn_add%d" % seed, bn_a.reshape(1, 1, 1, cout))], [a], NONE)
-    r = f32([1, oh, oh, cout], "r%d" % seed)
-    ew_op(b, ADD, [a, r_prev], [r], act)
-    return r, dict(spec=spec, w=w, m=m, b=bias, bn_m=bn_m, bn_a=bn_a, residual=True, act=act)
-
-
-# the QuickNet body the GPU tests and tools/elementwise_sections.py use: (H, C, Cout, stride, residual) per layer
-BODY = ((56, 64, 64, 1, True), (56, 64, 64, 1, True), (56, 64, 128, 2, False), (28, 128, 128, 1, True),
-        (28, 128, 256, 2, False), (14, 256, 256, 1, True))
-
-
-def body_model(layers=BODY, seed=0):
-    """x (float [1,H,W,C]) -> the layers -> the last layer's float output (graph output).  Returns (file, x, output, layer list,
-    the tensor each layer's chain writes)."""
-    b = ModelBuilder()
-    H, C = layers[0][0], layers[0][1]
-    x = b.tensor([1, H, H, C], np.float32, "x")
-    r, info, outs = x, [], []
-    for k, (h, c, cout, stride, residual) in enumerate(layers):
-        r, li = layer(b, r, h, c, cout, seed + 10 * k + 1, stride, residual, RELU if k % 2 else NONE)
-        info.append(li)
-        outs.append(r)
-    b.inputs, b.outputs = [x], [r]
-    return b.finish(), x, r, info, outs
 
 
 def test_partition_of_the_mixed_graph_with_and_without_the_flag():

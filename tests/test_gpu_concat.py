@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_concat_sections_host import (DENSE_STAGES, INT8_GROWTHS, INT8_Q, dense_block_model, dense_reference, int8_dense_model,
-                                       int8_dense_reference, joins_of)
+from section_models import DENSE_STAGES, dense_block_model, joins_of
+from test_concat_sections_host import INT8_GROWTHS, INT8_Q, dense_reference, int8_dense_model, int8_dense_reference
 
 torch = pytest.importorskip("torch")
 from test_gpu_elementwise import ref_op  # noqa: E402  (TFLite's float MUL / ADD, one rounding each)

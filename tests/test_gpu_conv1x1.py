@@ -12,8 +12,9 @@ import pytest
 import conv1x1_ref as R
 import oracle_lib as O
 import pool_ref as PR
-from test_conv1x1_sections_host import (ACTS, ALL_FLAGS, CONV_2D, FIXTURES, GRID_BATCHES, GRID_CIN, GRID_COUT, GRID_IMAGES, GRID_STRIDES, KNOWN,
-                                        float_fixture, grid_operands, known_case)
+from section_models import CONV_2D, float_fixture
+from test_conv1x1_sections_host import (ACTS, ALL_FLAGS, FIXTURES, GRID_BATCHES, GRID_CIN, GRID_COUT, GRID_IMAGES, GRID_STRIDES,
+                                        KNOWN, grid_operands, known_case)
 
 torch = pytest.importorskip("torch")
 from test_gpu_elementwise import ref_op  # noqa: E402  (TFLite's float MUL / ADD, one rounding each)

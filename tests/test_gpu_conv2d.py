@@ -13,9 +13,9 @@ import pytest
 
 import conv2d_ref as R
 import oracle_lib as O
-from test_conv2d_sections_host import (ACTS, ALL_FLAGS, FIXTURES, KNOWN, PARENT_FLAGS, float_fixture, float_op, grid_operands, known_case,
+from section_models import ADD, MUL, NONE, float_fixture, float_op
+from test_conv2d_sections_host import (ACTS, ALL_FLAGS, FIXTURES, KNOWN, PARENT_FLAGS, grid_operands, known_case,
                                        quicknet_stem_model, _graph)
-from test_elementwise_sections_host import ADD, MUL, NONE
 
 torch = pytest.importorskip("torch")
 

@@ -12,7 +12,8 @@ import pytest
 
 import depthwise_ref as R
 import oracle_lib as O
-from test_depthwise_sections_host import ACTS, ALL_FLAGS, DEPTHWISE_CONV_2D, FIXTURES, KNOWN, OLD_FLAGS, float_fixture, grid_operands, known_case
+from section_models import DEPTHWISE_CONV_2D, float_fixture
+from test_depthwise_sections_host import ACTS, ALL_FLAGS, FIXTURES, KNOWN, OLD_FLAGS, grid_operands, known_case
 
 torch = pytest.importorskip("torch")
 

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_elementwise_sections_host import BODY, body_model
+from section_models import BODY, body_model
 
 torch = pytest.importorskip("torch")
 amd = importlib.import_module("compute-engine_amd")

@@ -15,8 +15,8 @@ from hypothesis import strategies as st
 
 import flexbuf
 import oracle_lib as O
+from section_models import bconv_options
 import synth
-from test_model_reader_host import bconv_options
 from tflite_writer import ModelBuilder
 
 amd = importlib.import_module("compute-engine_amd")

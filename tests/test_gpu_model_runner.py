@@ -7,9 +7,9 @@ import importlib
 import numpy as np
 import pytest
 
+from section_models import mixed_model, oracle_forward, small_model
 import synth
 import oracle_lib as O
-from test_model_reader_host import mixed_model, oracle_forward, small_model
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")

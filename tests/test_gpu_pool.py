@@ -11,8 +11,9 @@ import pytest
 
 import oracle_lib as O
 import pool_ref as R
-from test_pool_sections_host import (ACTS, BATCHES, F32_CHANNELS, GRID_IMAGES, GRID_WINDOWS, I8_CHANNELS, INT8_KNOWN, INT8_Q, POOL_Q,
-                                     WINDOW_OF, alexnet_body_model, fixture_seed, float_fixture, int8_body_model, int8_fixture,
+from section_models import alexnet_body_model
+from test_pool_sections_host import (ACTS, BATCHES, F32_CHANNELS, GRID_IMAGES, GRID_WINDOWS, I8_CHANNELS, INT8_KNOWN, INT8_Q,
+                                     POOL_Q, WINDOW_OF, fixture_seed, float_fixture, int8_body_model, int8_fixture,
                                      int8_known_case, window_of)
 
 torch = pytest.importorskip("torch")

@@ -12,9 +12,8 @@ import pytest
 import hipcc_lib as H
 import int8_add_ref as R
 import oracle_lib as O
+from section_models import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, bconv_options, ew_op, mixed_model
 import synth
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, ew_op
-from test_model_reader_host import bconv_options, mixed_model
 from tflite_writer import ModelBuilder
 
 amd = importlib.import_module("compute-engine_amd")

@@ -12,72 +12,13 @@ import pytest
 
 import flexbuf
 import oracle_lib as O
+from section_models import bconv_options, mixed_model, oracle_forward, small_model
 import synth
 from tflite_writer import ModelBuilder
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
 KATS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_kats.json")))
-
-
-def bconv_options(spec: O.ConvSpec) -> bytes:
-    return flexbuf.bconv2d_options(channels_in=spec.channels_in, dilation_height_factor=spec.dilation_h,
-                                   dilation_width_factor=spec.dilation_w, fused_activation_function=spec.activation,
-                                   pad_values=spec.pad_values, padding=spec.padding, stride_height=spec.stride_h,
-                                   stride_width=spec.stride_w)
-
-
-def small_model(seed=0):
-    """float in -> LceQuantize -> LceBconv2d(float) -> LceQuantize -> LceBconv2d(bitpacked, RELU)
-    -> LceBMaxPool2d -> LceBconv2d(int8) ; second output: LceDequantize of the pooled bits."""
-    H, C0 = 12, 64
-    s1 = O.ConvSpec(1, H, H, C0, 3, 3, 96, padding=O.PADDING_SAME, pad_values=1)
-    s2 = O.ConvSpec(1, H, H, 96, 3, 3, 40, 1, 2, 2, 1, 1, O.PADDING_VALID, 0, O.ACT_RELU)
-    oh = s2.out_h
-    s3 = O.ConvSpec(1, oh // 2, oh // 2, 40, 1, 1, 33)
-    _, w1, m1, b1 = synth.conv_inputs(s1, seed + 1)
-    _, w2, m2, b2 = synth.conv_inputs(s2, seed + 2)
-    _, w3, m3, b3 = synth.conv_inputs(s3, seed + 3)
-    thr2 = O.thresholds_converter(s2, m2, b2)
-    sc3, zp3 = synth.int8_quant_params(seed + 3)
-    b = ModelBuilder()
-    t_in = b.tensor([1, H, H, C0], np.float32, "input")
-    t_q1 = b.tensor([1, H, H, 2], np.int32, "q1")
-    t_w1 = b.tensor(w1.shape, np.int32, "w1", w1)
-    t_m1 = b.tensor([96], np.float32, "m1", m1)
-    t_b1 = b.tensor([96], np.float32, "b1", b1)
-    t_y1 = b.tensor([1, H, H, 96], np.float32, "y1")
-    t_q2 = b.tensor([1, H, H, 3], np.int32, "q2")
-    t_w2 = b.tensor(w2.shape, np.int32, "w2", w2)
-    t_t2 = b.tensor([40], np.int32, "thr2", thr2)
-    t_y2 = b.tensor([1, oh, oh, 2], np.int32, "y2")
-    t_p = b.tensor([1, oh // 2, oh // 2, 2], np.int32, "pooled")
-    t_w3 = b.tensor(w3.shape, np.int32, "w3", w3)
-    t_m3 = b.tensor([33], np.float32, "m3", m3)
-    t_b3 = b.tensor([33], np.float32, "b3", b3)
-    t_y3 = b.tensor([1, oh // 2, oh // 2, 33], np.int8, "y3", scale=float(sc3), zero_point=zp3)
-    t_d = b.tensor([1, oh // 2, oh // 2, 40], np.float32, "dequantized")
-    b.inputs, b.outputs = [t_in], [t_y3, t_d]
-    b.custom_op("LceQuantize", [t_in], [t_q1], b"")
-    b.custom_op("LceBconv2d", [t_q1, t_w1, t_m1, t_b1, -1], [t_y1], bconv_options(s1))
-    b.custom_op("LceQuantize", [t_y1], [t_q2], b"")
-    b.custom_op("LceBconv2d", [t_q2, t_w2, -1, -1, t_t2], [t_y2], bconv_options(s2))
-    b.custom_op("LceBMaxPool2d", [t_y2], [t_p], flexbuf.bmaxpool_options(2, 2, 2, 2, O.PADDING_VALID))
-    b.custom_op("LceBconv2d", [t_p, t_w3, t_m3, t_b3, -1], [t_y3], bconv_options(s3))
-    b.custom_op("LceDequantize", [t_p], [t_d], b"")
-    params = dict(s1=s1, s2=s2, s3=s3, w=(w1, w2, w3), m=(m1, m2, m3), b=(b1, b2, b3), thr2=thr2, q3=(sc3, zp3))
-    return b.finish(), params
-
-
-def oracle_forward(x, p):
-    n = x.shape[0]
-    s1, s2, s3 = (s.with_batch(n) for s in (p["s1"], p["s2"], p["s3"]))
-    y1 = O.bconv2d(s1, O.DST_F32, O.bitpack(x), p["w"][0], p["m"][0], p["b"][0])
-    y2 = O.bconv2d(s2, O.DST_BITPACKED, O.bitpack(y1), p["w"][1], thresholds=p["thr2"])
-    pooled = O.bmaxpool(y2, 2, 2, 2, 2, O.PADDING_VALID)
-    y3 = O.bconv2d(s3, O.DST_I8, pooled, p["w"][2], p["m"][2], p["b"][2], out_scale=float(p["q3"][0]),
-                   out_zero_point=p["q3"][1])
-    return y3, O.unpack(pooled, 40, np.float32)
 
 
 def test_reader_round_trips_every_field():
@@ -194,62 +135,6 @@ def test_interpreter_refuses_to_predict_graphs_with_builtin_ops():
     assert not it.lce_only and it.sections == []
     with pytest.raises(NotImplementedError, match="only LCE custom ops"):
         it.predict(np.zeros((1, 4, 4, 32), np.float32))
-
-
-CONV_2D, ADD, MAX_POOL_2D = 3, 0, 17      # schema.fbs BuiltinOperator values
-
-
-def mixed_model(seed=0):
-    """A QuickNet-shaped mixed graph (float stem, residual ADDs between binary convolutions, float pooling head):
-
-        x --CONV_2D(builtin stem)--> s --LceQuantize--> q0 --LceBconv2d(float)--> y0 --ADD(s)--> r0
-          r0 --LceQuantize--> q1 --LceBconv2d(float)--> y1 --ADD(r0)--> r1
-          r1 --LceQuantize--> q2 --LceBconv2d(bitpacked)--> b2 --LceBMaxPool2d--> p2 --LceBconv2d(float)--> y3 --MAX_POOL_2D--> out
-          b2 --LceDequantize--> d2 (second graph output)
-
-    Binary sections: {Quantize, Bconv} (s -> y0), {Quantize, Bconv} (r0 -> y1), {Quantize, Bconv, BMaxPool, Bconv, Dequantize}
-    (r1 -> y3, d2)."""
-    H, C = 10, 64
-    s_a = O.ConvSpec(1, H, H, C, 3, 3, C, padding=O.PADDING_SAME, pad_values=1)
-    s_c = O.ConvSpec(1, H, H, C, 3, 3, 96, padding=O.PADDING_SAME, pad_values=1, activation=O.ACT_RELU)
-    s_d = O.ConvSpec(1, H // 2, H // 2, 96, 3, 3, 32, padding=O.PADDING_SAME, pad_values=1)
-    _, w0, m0, b0 = synth.conv_inputs(s_a, seed + 1)
-    _, w1, m1, b1 = synth.conv_inputs(s_a, seed + 2)
-    _, w2, m2, b2 = synth.conv_inputs(s_c, seed + 3)
-    _, w3, m3, b3 = synth.conv_inputs(s_d, seed + 4)
-    thr2 = O.thresholds_converter(s_c, m2, b2)
-    b = ModelBuilder()
-    f32 = lambda shape, name, data=None: b.tensor(shape, np.float32, name, data)
-    i32 = lambda shape, name, data=None: b.tensor(shape, np.int32, name, data)
-    x = f32([1, H, H, 3], "image")
-    k = f32([C, 3, 3, 3], "stem_filter", synth.rng(seed).standard_normal((C, 3, 3, 3)).astype(np.float32))
-    kb = f32([C], "stem_bias", np.zeros(C, np.float32))
-    s = f32([1, H, H, C], "stem")
-    q0, y0, r0 = i32([1, H, H, 2], "q0"), f32([1, H, H, C], "y0"), f32([1, H, H, C], "r0")
-    q1, y1, r1 = i32([1, H, H, 2], "q1"), f32([1, H, H, C], "y1"), f32([1, H, H, C], "r1")
-    q2, bb2, p2 = i32([1, H, H, 2], "q2"), i32([1, H, H, 3], "b2"), i32([1, H // 2, H // 2, 3], "p2")
-    y3, out, d2 = f32([1, H // 2, H // 2, 32], "y3"), f32([1, 2, 2, 32], "pooled"), f32([1, H, H, 96], "d2")
-    tw = [i32(w.shape, "w%d" % i, w) for i, w in enumerate((w0, w1, w2, w3))]
-    tm = [f32([len(m)], "m%d" % i, m) for i, m in enumerate((m0, m1, m2, m3))]
-    tb = [f32([len(v)], "b%d" % i, v) for i, v in enumerate((b0, b1, b2, b3))]
-    tthr = i32([96], "thr2", thr2)
-    b.inputs, b.outputs = [x], [out, d2]
-    b.builtin_op(CONV_2D, [x, k, kb], [s])                                             # 0
-    b.custom_op("LceQuantize", [s], [q0], b"")                                         # 1
-    b.custom_op("LceBconv2d", [q0, tw[0], tm[0], tb[0], -1], [y0], bconv_options(s_a))  # 2
-    b.builtin_op(ADD, [y0, s], [r0])                                                   # 3
-    b.custom_op("LceQuantize", [r0], [q1], b"")                                        # 4
-    b.custom_op("LceBconv2d", [q1, tw[1], tm[1], tb[1], -1], [y1], bconv_options(s_a))  # 5
-    b.builtin_op(ADD, [y1, r0], [r1])                                                  # 6
-    b.custom_op("LceQuantize", [r1], [q2], b"")                                        # 7
-    b.custom_op("LceBconv2d", [q2, tw[2], -1, -1, tthr], [bb2], bconv_options(s_c))     # 8
-    b.custom_op("LceBMaxPool2d", [bb2], [p2], flexbuf.bmaxpool_options(2, 2, 2, 2, O.PADDING_VALID))   # 9
-    b.custom_op("LceBconv2d", [p2, tw[3], tm[3], tb[3], -1], [y3], bconv_options(s_d))  # 10
-    b.builtin_op(MAX_POOL_2D, [y3], [out])                                             # 11
-    b.custom_op("LceDequantize", [bb2], [d2], b"")                                     # 12
-    ids = dict(s=s, y0=y0, r0=r0, y1=y1, r1=r1, y3=y3, d2=d2, b2=bb2)
-    params = dict(specs=(s_a, s_a, s_c, s_d), w=(w0, w1, w2, w3), m=(m0, m1, m2, m3), b=(b0, b1, b2, b3), thr2=thr2)
-    return b.finish(), ids, params
 
 
 def test_binary_sections_of_a_mixed_graph():

@@ -16,32 +16,18 @@ import pytest
 import hipcc_lib as H
 import oracle_lib as O
 import pool_ref as R
+from section_models import (ADD, AVERAGE_POOL_2D, MARK, MAX_POOL_2D, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, _conv, _open,
+                            _options_table, _sections_of, alexnet_body_model, bconv_options, cut_at, dense_block_model, ew_op,
+                            mixed_model, pool_op)
 import synth
-from test_concat_sections_host import _conv, _sections_of, cut_at, dense_block_model
-from test_elementwise_sections_host import ADD, MUL, NONE, RELU, RELU6, RELU_N1_TO_1, TANH, ew_op
-from test_model_reader_host import bconv_options, mixed_model
 from tflite_writer import ModelBuilder, _Scalar, _Table, _Vector
 
 amd = importlib.import_module("compute-engine_amd")
 mr = importlib.import_module("compute-engine_amd.model_runner")
 
-AVERAGE_POOL_2D, MAX_POOL_2D = 1, 17   # schema.fbs BuiltinOperator
-POOL_2D_OPTIONS = 5                    # schema.fbs BuiltinOptions
 SAME, VALID = R.SAME, R.VALID
 ACTS = (NONE, RELU, RELU_N1_TO_1, RELU6)
 FLT_MAX = R.FLT_MAX
-
-
-def pool_op(b: ModelBuilder, code, inputs, outputs, filt=(2, 2), stride=(2, 2), padding=VALID, activation=NONE, options=True) -> int:
-    """A builtin pool with its Pool2DOptions table (0 padding, 1 stride_w, 2 stride_h, 3 filter_width, 4 filter_height,
-    5 fused_activation_function) -- or without one when options is False."""
-    fields = {0: _Scalar("I", b._code(None, code)), 1: _Vector("i", list(inputs)), 2: _Vector("i", list(outputs))}
-    if options:
-        fields[3] = _Scalar("B", POOL_2D_OPTIONS)
-        fields[4] = _Table({0: _Scalar("b", padding), 1: _Scalar("i", stride[1]), 2: _Scalar("i", stride[0]),
-                            3: _Scalar("i", filt[1]), 4: _Scalar("i", filt[0]), 5: _Scalar("b", activation)})
-    b.ops.append(_Table(fields))
-    return len(b.ops) - 1
 
 
 # ---- known answers, worked by hand ----------------------------------------------------------------------------------------
@@ -271,41 +257,6 @@ def test_the_fixtures_are_what_the_checks_need(w):
         assert differ or len(taps) < 3, image
 
 
-# ---- the partition ------------------------------------------------------------------------------------------------------------
-def alexnet_body_model(H=15, C=64, seed=0):
-    """x (float) -> LceQuantize -> LceBconv2d (float) -> MAX_POOL 3x3 / 2 VALID -> MUL (c) -> ADD (c) -> LceQuantize ->
-    LceBconv2d (float) -> AVERAGE_POOL 2x2 / 2 SAME -> LceQuantize -> LceBconv2d (float, the graph output).  Returns (file,
-    input tensor, output tensor, info): info holds the convolutions' constants, the batch norm and the operator indices."""
-    b = ModelBuilder()
-    f32 = lambda shape, name, data=None: b.tensor(shape, np.float32, name, data)
-    quant = lambda src, h, name: b.tensor([1, h, h, C // 32], np.int32, name)
-    x = f32([1, H, H, C], "x")
-    q0 = quant(x, H, "q0")
-    b.custom_op("LceQuantize", [x], [q0], b"")
-    y0, c0 = _conv(b, q0, H, C, C, seed * 10 + 1)
-    h1 = (H - 3) // 2 + 1
-    p0 = f32([1, h1, h1, C], "p0")
-    pool0 = pool_op(b, MAX_POOL_2D, [y0], [p0], (3, 3), (2, 2), VALID)
-    g = synth.rng(seed + 77)
-    bn_m, bn_a = g.uniform(-1.5, 1.5, C).astype(np.float32), g.standard_normal(C).astype(np.float32)
-    mm, aa = f32([1, h1, h1, C], "mm"), f32([1, h1, h1, C], "aa")
-    mul = ew_op(b, MUL, [p0, f32([C], "bn_m", bn_m)], [mm], NONE)
-    add = ew_op(b, ADD, [mm, f32([C], "bn_a", bn_a)], [aa], NONE)
-    q1 = quant(aa, h1, "q1")
-    b.custom_op("LceQuantize", [aa], [q1], b"")
-    y1, c1 = _conv(b, q1, h1, C, C, seed * 10 + 2)
-    h2 = (h1 + 1) // 2
-    p1 = f32([1, h2, h2, C], "p1")
-    pool1 = pool_op(b, AVERAGE_POOL_2D, [y1], [p1], (2, 2), (2, 2), SAME, RELU6)
-    q2 = quant(p1, h2, "q2")
-    b.custom_op("LceQuantize", [p1], [q2], b"")
-    y2, c2 = _conv(b, q2, h2, C, C, seed * 10 + 3)
-    b.inputs, b.outputs = [x], [y2]
-    info = dict(convs=[c0, c1, c2], bn_m=bn_m, bn_a=bn_a, pools=[pool0, pool1], mul=mul, add=add, pooled=[p0, p1], sizes=[H, h1, h2],
-                channels=C)
-    return b.finish(), x, y2, info
-
-
 POOL_Q = (0.25, -3)                    # the ONE scale and zero point of the int8 body's tensors
 
 
@@ -456,7 +407,6 @@ def _graph(case):
     return b.finish(), k
 
 
-
 @pytest.mark.parametrize("case", ["wrong_type", "int8_scales", "int8_zero_points", "int8_unquantized", "channels", "extent_off_by_one",
                                   "zero_stride", "huge_stride", "zero_filter", "tanh", "padding_2", "no_options", "two_inputs", "l2_pool", "constant",
                                   "stem", "three_d"])
@@ -513,24 +463,6 @@ def test_pool2d_options_round_trip_through_the_reader():
     v = (C.c_int32 * 5)()
     assert mr.tflite_lib().lce_tflite_model_operator_pool2d(model._h, len(model.operators), v) == amd.ERR_INVALID
     assert mr.tflite_lib().lce_tflite_model_operator_pool2d(model._h, 0, None) == amd.ERR_INVALID
-
-
-MARK = 0x5A6B7C4D
-
-
-def _options_table(data):
-    """(position of the Pool2DOptions table whose filter_height is MARK, position of the uoffset that points to it, position of
-    the vtable slot of filter_height)."""
-    at = data.index(struct.pack("<i", MARK))
-    assert data.count(struct.pack("<i", MARK)) == 1
-    for table in range(at - 4, max(0, at - 64), -4):                                  # the table start: its vtable names `at`
-        vt = table - struct.unpack_from("<i", data, table)[0]
-        if 0 <= vt < table and vt + 14 <= len(data) and struct.unpack_from("<H", data, vt)[0] == 16 and \
-                table + struct.unpack_from("<H", data, vt + 4 + 2 * 4)[0] == at:
-            refs = [p for p in range(0, table, 4) if p + struct.unpack_from("<I", data, p)[0] == table]
-            assert len(refs) == 1
-            return table, refs[0], vt + 4 + 2 * 4
-    raise AssertionError("options table not found")
 
 
 def test_a_truncated_or_out_of_bounds_options_table_is_refused_at_open():
@@ -712,29 +644,6 @@ def test_python_checks_fail_before_any_device_call(monkeypatch, x, kw, msg):
     args.update(kw)
     with pytest.raises(ValueError, match=msg):
         amd.pool2d(x, **args)
-
-
-# ---- the opt-in -----------------------------------------------------------------------------------------------------------------
-def _open(data, raw):
-    """lce_tflite_model_open_opts on the options bytes `raw`, placed so that they END at a page that cannot be read: a read
-    beyond them faults.  Returns (handle or None, message)."""
-    page = mmap.PAGESIZE
-    m = mmap.mmap(-1, 2 * page)
-    view = (C.c_char * (2 * page)).from_buffer(m)
-    base = C.addressof(view)
-    libc = C.CDLL(None, use_errno=True)
-    libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
-    at = base + page - len(raw)
-    C.memmove(at, raw, len(raw))
-    assert libc.mprotect(base + page, page, 0) == 0, C.get_errno()
-    try:
-        err = C.create_string_buffer(128)
-        h = mr.tflite_lib().lce_tflite_model_open_opts(data, len(data), C.c_void_p(at), err, 128)
-    finally:
-        assert libc.mprotect(base + page, page, mmap.PROT_READ | mmap.PROT_WRITE) == 0
-        del view
-        m.close()
-    return h, err.value
 
 
 def test_open_opts_is_versioned_by_its_size():
