@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
     "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
+    "lce_hip_fully_connected_f32", "lce_hip_fully_connected_f32_check", "lce_hip_softmax_f32", "lce_hip_softmax_f32_check",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -116,6 +117,11 @@ class Conv2dDesc(C.Structure):
                                          "filter_width", "stride_height", "stride_width", "padding", "activation")]
 
 
+class FcDesc(C.Structure):
+    """``lce_hip_fc_desc``."""
+    _fields_ = [(n, C.c_int32) for n in ("batch", "inputs", "outputs", "activation")]
+
+
 _lib = None
 
 
@@ -172,6 +178,10 @@ def lib() -> C.CDLL:
         l.lce_hip_depthwise_conv2d_f32_check.argtypes = [C.POINTER(DepthwiseDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_conv2d_f32.argtypes = [C.POINTER(Conv2dDesc)] + [C.c_void_p] * 6
         l.lce_hip_conv2d_f32_check.argtypes = [C.POINTER(Conv2dDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_fully_connected_f32.argtypes = [C.POINTER(FcDesc)] + [C.c_void_p] * 5
+        l.lce_hip_fully_connected_f32_check.argtypes = [C.POINTER(FcDesc)]
+        l.lce_hip_softmax_f32.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_softmax_f32_check.argtypes = [C.c_size_t, C.c_size_t, C.c_float]
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -866,6 +876,74 @@ def conv2d(x, w, bias=None, stride=1, padding=PADDING_SAME, activation=ACT_NONE,
     [B, OH, OW, ceil(Cout/32)] bits (value < 0), a tensor to fill, False for none.  Returns ``(out or None, bits or None)``."""
     desc, shape = _conv2d_check(x, w, bias, stride, padding, activation, out, out_bits)
     return _run_windowed("conv2d", "lce_hip_conv2d_f32", desc, shape, x, (w, bias), out, out_bits, stream)
+
+
+def _fully_connected_check(x, w, bias, activation, out):
+    """Argument checks of ``fully_connected`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (FcDesc, output shape)."""
+    xs, ws = tuple(int(v) for v in x.shape), tuple(int(v) for v in w.shape)
+    if _dtype_name(x) != "float32" or len(xs) != 2 or min(xs) < 1:
+        raise ValueError("fully_connected: x must be a non-empty float32 [batch, inputs] tensor, got %s %r" % (x.dtype, xs))
+    if _dtype_name(w) != "float32" or len(ws) != 2 or ws[0] < 1 or ws[1] != xs[1]:
+        raise ValueError("fully_connected: w must be float32 [outputs, %d], got %s %r" % (xs[1], w.dtype, ws))
+    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (ws[0],)):
+        raise ValueError("fully_connected: bias must be float32 [%d], got %s %r" % (ws[0], bias.dtype, tuple(bias.shape)))
+    _padding_activation_check("fully_connected", None, activation)
+    shape = (xs[0], ws[0])
+    _check_outputs("fully_connected", out, None, "float32", shape)
+    return FcDesc(xs[0], xs[1], ws[0], int(activation)), shape
+
+
+def fully_connected(x, w, bias=None, activation=ACT_NONE, out=None, stream: int | None = None):
+    """TFLite's builtin float FULLY_CONNECTED -- the Dense layer of a classifier head -- in one launch
+    (``lce_hip_fully_connected_f32``).  ``x``: float32 [batch, inputs] on the device (or NumPy: copied to cuda:0 and back).
+    ``w``: float32 [outputs, inputs].  ``bias``: float32 [outputs] or None.  ``activation``: ``ACT_*``.  Per output element
+    t = fmaf(x[k], w[o][k], t) over k in order from +0.0, then + bias, then the clamp: the bytes of ``conv1x1`` on a
+    [batch, 1, 1, inputs] image (include/lce_hip.h).  ``out``: None for a new tensor, or a tensor [batch, outputs] to fill (it
+    must not overlap an operand).  Returns the output."""
+    desc, shape = _fully_connected_check(x, w, bias, activation, out)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "fully_connected", "x's")
+    xd, wd, bd = on_dev(x), on_dev(w), None if bias is None else on_dev(bias)
+    out_d = torch.empty(shape, dtype=torch.float32, device=dev) if out is None else on_dev(out)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_fully_connected_f32(C.byref(desc), _dev_ptr(xd), _dev_ptr(wd), _dev_ptr(bd), _dev_ptr(out_d),
+                                                C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, None, out)[0]
+
+
+def _softmax_check(x, beta, out):
+    """Argument checks of ``softmax`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (rows, cols)."""
+    shape = tuple(int(v) for v in x.shape)
+    if _dtype_name(x) != "float32" or len(shape) < 1 or min(shape) < 1:
+        raise ValueError("softmax: x must be a non-empty float32 tensor, got %s %r" % (x.dtype, shape))
+    if not (np.isfinite(float(beta)) and float(beta) > 0):
+        raise ValueError("softmax: beta must be finite and positive, got %r" % (beta,))
+    if out is not None and out is not x:
+        _check_outputs("softmax", out, None, "float32", shape)
+    return int(np.prod(shape[:-1], dtype=np.int64)), shape[-1]
+
+
+def softmax(x, beta: float = 1.0, out=None, stream: int | None = None):
+    """TFLite's builtin float SOFTMAX over the last axis in one launch (``lce_hip_softmax_f32``), to the bytes include/lce_hip.h
+    states: the row maximum, a = (x - max) * beta, the library's own exp (a Cody-Waite reduction and a polynomial, within 1 ulp),
+    a sum in a fixed order, the correctly rounded division.  ``x``: float32 [..., cols] on the device (or NumPy: copied to cuda:0
+    and back).  ``beta``: finite and positive.  ``out``: None for a new tensor, a tensor of x's shape to fill, or ``x`` itself
+    (in place); any other overlap is refused.  Returns the output."""
+    rows, cols = _softmax_check(x, beta, out)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "softmax", "x's")
+    xd = on_dev(x)
+    out_d = torch.empty_like(xd) if out is None else xd if out is x else on_dev(out)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_softmax_f32(rows, cols, float(beta), _dev_ptr(xd), _dev_ptr(out_d),
+                                        C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, None, out)[0]
 
 
 def bmaxpool(x, filter_height, filter_width, stride_height, stride_width, padding, stream: int | None = None, out=None):

@@ -24,6 +24,7 @@
 #include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
 #include "lce_kernels_depthwise.h"   // (lce_tu_depthwise.hip)
 #include "lce_kernels_conv2d.h"      // (lce_tu_conv2d.hip)
+#include "lce_kernels_head.h"        // (lce_tu_head.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -47,6 +48,7 @@
 #include "lce_tu_conv1x1.hip"
 #include "lce_tu_depthwise.hip"
 #include "lce_tu_conv2d.hip"
+#include "lce_tu_head.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -1035,6 +1037,75 @@ lce_hip_status lce_hip_conv1x1_f32(const lce_hip_conv1x1_desc* d, const float* i
   float_activation_range(d->activation, &a.lo, &a.hi);
   const bool vec = K % 4 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
   const int e = lce::launch_conv1x1(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// the float classifier head: FULLY_CONNECTED and SOFTMAX (lce_kernels_head.h)
+// ------------------------------------------------------------------------------------
+lce_hip_status lce_hip_fully_connected_f32_check(const lce_hip_fc_desc* d) {
+  const char* who = "lce_hip_fully_connected_f32";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->batch <= 0 || d->inputs <= 0 || d->outputs <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d] -> %d outputs", who, (int)d->batch, (int)d->inputs,
+                (int)d->outputs);
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  // (the kernel numbers its 16 x 16 tiles in 32 bits)
+  const uint64_t tiles = (((uint64_t)d->batch + lce::kFcTile - 1) / lce::kFcTile) * (((uint64_t)d->outputs + lce::kFcTile - 1) / lce::kFcTile);
+  if (tiles >= (1ull << 31)) return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: an output of more than 2^31 tiles of 16 x 16 is not supported", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_fully_connected_f32(const lce_hip_fc_desc* d, const float* in_dev, const float* weights_dev, const float* bias_dev,
+                                           float* out_dev, void* stream) {
+  const char* who = "lce_hip_fully_connected_f32";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!weights_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null weights", who);
+  if (!out_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null output", who);
+  if (lce_hip_status s = lce_hip_fully_connected_f32_check(d)) return s;
+  const uint64_t M = (uint64_t)d->batch, K = (uint64_t)d->inputs, N = (uint64_t)d->outputs;
+  const Span in(in_dev, M * K * 4), weights(weights_dev, N * K * 4), bias(bias_dev, N * 4), out(out_dev, M * N * 4), none(nullptr, 0);
+  if (lce_hip_status s = check_operand_ranges(who, in, weights, bias, out, none, /*float_operands=*/true)) return s;
+  if (lce_hip_status s = require_device()) return s;
+  lce::FcArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.filter = weights_dev; a.bias = bias_dev; a.out = out_dev;
+  a.M = (uint32_t)M; a.K = (uint32_t)K; a.N = (uint32_t)N;
+  a.ntiles = (uint32_t)((N + lce::kFcTile - 1) / lce::kFcTile);
+  a.tiles = (uint32_t)((M + lce::kFcTile - 1) / lce::kFcTile) * a.ntiles;
+  float_activation_range(d->activation, &a.lo, &a.hi);
+  const bool vec = K % 4 == 0 && in.lo % 16 == 0 && weights.lo % 16 == 0;
+  const int e = lce::launch_fully_connected(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_softmax_f32_check(size_t rows, size_t cols, float beta) {
+  const char* who = "lce_hip_softmax_f32";
+  if (rows == 0 || cols == 0) return fail(LCE_HIP_ERR_INVALID, "%s: rows and cols must be positive, got %zu x %zu", who, rows, cols);
+  if (!std::isfinite(beta) || !(beta > 0.0f)) return fail(LCE_HIP_ERR_INVALID, "%s: beta must be finite and positive, got %g", who, (double)beta);
+  if ((uint64_t)cols >= (1ull << 31) || (uint64_t)rows > (1ull << 60) / (uint64_t)cols)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: rows of 2^31 elements or more, or more than 2^60 elements, are not supported", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_softmax_f32(size_t rows, size_t cols, float beta, const float* in_dev, float* out_dev, void* stream) {
+  const char* who = "lce_hip_softmax_f32";
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!out_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null output", who);
+  if (lce_hip_status s = lce_hip_softmax_f32_check(rows, cols, beta)) return s;
+  const Span in(in_dev, (uint64_t)rows * cols * 4), out(out_dev, (uint64_t)rows * cols * 4);
+  if ((in.lo | out.lo) % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  // in place is the one overlap that is safe: a lane writes only the elements it alone reads
+  if (in.lo != out.lo && meet(in.lo, in.hi, out.lo, out.hi)) return fail(LCE_HIP_ERR_INVALID, "%s: the output partly overlaps the input", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::SoftmaxArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.out = out_dev; a.rows = rows; a.cols = (uint32_t)cols; a.beta = beta;
+  const int e = lce::launch_softmax(a, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <string>
@@ -21,11 +22,14 @@ struct lce_tflite_section {
 };
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
-       kAbsorbedCount };
+       kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedCount };
+// lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
+enum { kInternalHead = 1u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
+  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head")
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
@@ -370,12 +374,126 @@ bool Conv2dCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return lce_hip_conv2d_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
 }
 
-// One fused pass: the bit of `flags` (or, with `ext`, of `flags_ext`) that enables it, the static half of "a section may run
+
+// ---- the classifier head (lce_tflite_model_open_passes, "head") ----
+// A head tensor as the section walker carries it: a rank-4 tensor as it is, a rank-2 tensor [b, C] as [b, 1, 1, C]; the extents
+// behind the batch must be positive.  False for every other rank.
+bool Carried(const lce_tfl::Tensor& t, int32_t dims[4]) {
+  if (t.shape.size() == 4) {
+    for (int k = 0; k < 4; ++k) dims[k] = t.shape[k];
+  } else if (t.shape.size() == 2) {
+    dims[0] = t.shape[0]; dims[1] = 1; dims[2] = 1; dims[3] = t.shape[1];
+  } else {
+    return false;
+  }
+  return dims[1] > 0 && dims[2] > 0 && dims[3] > 0;
+}
+
+// lce_hip_pool2d_desc of a builtin MEAN over height and width at `batch` images: the AVERAGE pool whose filter is the FILE's image.
+lce_hip_pool2d_desc MeanDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  lce_hip_pool2d_desc d;
+  memset(&d, 0, sizeof d);
+  d.op = LCE_HIP_POOL_AVERAGE;
+  d.type = LCE_HIP_F32;
+  d.batch = batch; d.in_height = in.shape[1]; d.in_width = in.shape[2]; d.channels = in.shape[3];
+  d.filter_height = in.shape[1]; d.filter_width = in.shape[2];
+  d.stride_height = 1; d.stride_width = 1;
+  d.padding = LCE_HIP_PADDING_VALID;
+  d.activation = LCE_HIP_ACT_NONE;
+  d.scale = 1.0f;
+  return d;
+}
+
+// "A builtin MEAN that a section may run": GlobalAveragePooling.  Two inputs and one output; the data input a non-constant
+// float32 4-D tensor with positive extents; the axis a constant int32 tensor (a scalar or a vector) with data in the file whose
+// entries, negative ones + 4, are exactly {1, 2}; the output float32 [b, C] (keep_dims false) or [b, 1, 1, C] (keep_dims true)
+// with the input's b and C; and lce_hip_pool2d_check accepts the AVERAGE / VALID / stride 1 pool whose filter is the image.
+bool MeanCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinMean || o.inputs.size() != 2 || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& axis = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 || in.data || in.shape.size() != 4 || out.type != lce_tfl::kTensorFloat32) return false;
+  for (int32_t extent : in.shape)
+    if (extent <= 0) return false;
+  if (axis.type != lce_tfl::kTensorInt32 || !axis.data || axis.shape.size() > 1) return false;
+  const int64_t count = axis.shape.empty() ? 1 : axis.shape[0];
+  if (count < 1 || count > 4 || (uint64_t)axis.bytes != (uint64_t)count * 4u) return false;
+  unsigned seen = 0;
+  for (int64_t k = 0; k < count; ++k) {
+    int32_t a;
+    memcpy(&a, axis.data + 4 * k, 4);
+    if (a < 0) a += 4;
+    if (a < 0 || a > 3) return false;
+    seen |= 1u << a;
+  }
+  if (seen != ((1u << 1) | (1u << 2))) return false;
+  const std::vector<int32_t>& os = out.shape;
+  if (o.keep_dims ? !(os.size() == 4 && os[1] == 1 && os[2] == 1) : os.size() != 2) return false;
+  if (os.front() != in.shape[0] || os.back() != in.shape[3]) return false;
+  const lce_hip_pool2d_desc d = MeanDesc(M, o, in.shape[0]);
+  int32_t oh = 0, ow = 0;
+  return lce_hip_pool2d_check(&d, &oh, &ow) == LCE_HIP_OK && oh == 1 && ow == 1;
+}
+
+// lce_hip_fc_desc of a builtin FULLY_CONNECTED at `batch` rows, from its options and the FILE's weight tensor.
+lce_hip_fc_desc FullyConnectedDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
+  lce_hip_fc_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = batch; d.inputs = w.shape[1]; d.outputs = w.shape[0];
+  d.activation = o.activation;
+  return d;
+}
+
+// "A builtin FULLY_CONNECTED that a section may run": the Dense layer of the head.  2 or 3 inputs (a third input of -1: no bias)
+// and one output; input, weights and output float32, the bias float32 when present; the input non-constant, of rank 2 or 4, its
+// extents behind the batch multiplying to K; the weights a constant [N, K] with data in the file; the bias absent or a constant
+// [N]; the FullyConnectedOptions table present with weights_format 0 (DEFAULT), keep_num_dims false unless the input is rank 2,
+// and an activation lce_hip_fully_connected_f32 knows; the output [b, N] with the input's b; and the entry's own check accepts
+// the descriptor.  int8 and hybrid weights, a non-constant weight, shuffled weights and TANH stay with the host.
+bool FullyConnectedCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinFullyConnected || !o.has_fc_options) return false;
+  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 || w.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32) return false;
+  if (o.fc_weights_format != 0 || (o.fc_keep_num_dims && in.shape.size() != 2)) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  int32_t id[4];
+  if (in.data || !Carried(in, id) || id[0] <= 0) return false;
+  if (!w.data || w.shape.size() != 2 || w.shape[0] <= 0 || w.shape[1] <= 0) return false;
+  const uint64_t N = (uint64_t)w.shape[0], K = (uint64_t)w.shape[1];
+  if ((uint64_t)w.bytes % 4u != 0 || ((uint64_t)w.bytes / 4u) % N != 0 || (uint64_t)w.bytes / 4u / N != K) return false;
+  if ((uint64_t)id[1] * (uint64_t)id[2] > K || (uint64_t)id[1] * (uint64_t)id[2] * (uint64_t)id[3] != K) return false;
+  if (!OptionalBias(M, o, w.shape[0])) return false;
+  if (out.shape.size() != 2 || out.shape[0] != id[0] || out.shape[1] != w.shape[0]) return false;
+  const lce_hip_fc_desc d = FullyConnectedDesc(M, o, id[0]);
+  return lce_hip_fully_connected_f32_check(&d) == LCE_HIP_OK;
+}
+
+// "A builtin SOFTMAX that a section may run": one float32 non-constant input [b, n] or [b, 1, 1, n]; a float32 output of the
+// same shape; the SoftmaxOptions table present with a beta that is finite and > 0; and the entry's own check accepts the extents.
+bool SoftmaxCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinSoftmax || !o.has_softmax_options) return false;
+  if (o.inputs.size() != 1 || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32 || in.data || in.shape != out.shape) return false;
+  int32_t id[4];
+  if (!Carried(in, id) || id[0] <= 0 || id[1] != 1 || id[2] != 1) return false;
+  if (!std::isfinite(o.softmax_beta) || !(o.softmax_beta > 0.0f)) return false;
+  return lce_hip_softmax_f32_check((size_t)id[0], (size_t)id[3], o.softmax_beta) == LCE_HIP_OK;
+}
+
+// One fused pass: the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it that enables it, the static half of "a section may run
 // this operator", and the walker that runs it.  The table, in priority order, is below Walk.
 struct Walk;
 struct FusedPass {
   int kind;
-  bool ext;
+  int word;
   uint32_t bit;
   bool (*candidate)(const lce_tfl::Model&, const lce_tfl::Operator&);
   lce_hip_status (Walk::*walker)(int32_t);
@@ -394,6 +512,7 @@ void lce_tflite_model::Partition() {
   const int n_ops = (int)m.operators.size(), n_t = (int)m.tensors.size();
   auto valid = [&](int32_t t) { return t >= 0 && t < n_t; };
   std::vector<char> produced(n_t, 0), is_output(n_t, 0), is_lce(n_ops, 0), candidate(n_ops, 0);
+  const uint32_t words[3] = {flags, flags_ext, flags_int};
   readers.assign(n_t, {});
   absorbed.assign(n_ops, 0);
   std::vector<int32_t> unready(n_ops, 0);
@@ -403,7 +522,10 @@ void lce_tflite_model::Partition() {
     // which it becomes ready, so it lands in a section exactly when the last of its inputs was produced by an LCE epoch (one
     // that is ready from the start -- a stem op -- is a builtin one without LCE_TFLITE_SECTIONS_EXT_STEM, below)
     for (const FusedPass& p : kPasses)
-      if (!candidate[i] && ((p.ext ? flags_ext : flags) & p.bit) && p.candidate(m, m.operators[i])) candidate[i] = (char)p.kind;
+      if (!candidate[i] && (words[p.word] & p.bit) && p.candidate(m, m.operators[i])) candidate[i] = (char)p.kind;
+    // a head operator (MEAN, FULLY_CONNECTED, SOFTMAX) is queued as the LCE operators are, whatever made it ready: behind a host
+    // operator the head is a section of its own, behind the body it joins the body's epoch
+    if (candidate[i] >= kAbsorbedMean) is_lce[i] = 1;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -445,7 +567,7 @@ void lce_tflite_model::Partition() {
         if (!valid(t) || made[t]) continue;
         made[t] = 1;
         for (int32_t r : readers[t])
-          if (--unready[r] == 0) queue[candidate[r] ? kind : (int)is_lce[r]].push_back(r);
+          if (--unready[r] == 0) queue[candidate[r] && !is_lce[r] ? kind : (int)is_lce[r]].push_back(r);
       }
     }
     q.clear();
@@ -496,7 +618,7 @@ lce_tflite_model* lce_tflite_model_open(const void* data, size_t size, char* err
 
 // Both entries funnel into ONE pair of flag words; `allowed` is the entry's own mask of the first.
 static lce_tflite_model* OpenWithFlags(const void* data, size_t size, uint32_t flags, uint32_t allowed, uint32_t flags_ext,
-                                       uint32_t allowed_ext, const char* refusal, char* err, size_t err_len) {
+                                       uint32_t allowed_ext, const char* refusal, char* err, size_t err_len, uint32_t flags_int = 0u) {
   auto* model = new (std::nothrow) lce_tflite_model{};
   std::string e = "out of memory";
   if (refusal) {
@@ -506,6 +628,7 @@ static lce_tflite_model* OpenWithFlags(const void* data, size_t size, uint32_t f
   } else if (model && data && model->m.Parse(data, size, &e)) {
     model->flags = flags;
     model->flags_ext = flags_ext;
+    model->flags_int = flags_int;
     model->Partition();
     return model;
   }
@@ -551,6 +674,32 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
   }
   return OpenWithFlags(data, size, sections, LCE_TFLITE_SECTIONS_ELEMENTWISE | LCE_TFLITE_SECTIONS_INT8_ADD | LCE_TFLITE_SECTIONS_CONCAT,
                        ext, allowed_ext, refusal, err, err_len);
+}
+
+lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len) {
+  struct Name { const char* name; int word; uint32_t bit; };
+  static const Name kNames[] = {
+      {"elementwise", 0, LCE_TFLITE_SECTIONS_ELEMENTWISE}, {"int8_add", 0, LCE_TFLITE_SECTIONS_INT8_ADD},
+      {"concat", 0, LCE_TFLITE_SECTIONS_CONCAT},           {"pool", 1, LCE_TFLITE_SECTIONS_EXT_POOL},
+      {"conv1x1", 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1},     {"depthwise", 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE},
+      {"conv2d", 1, LCE_TFLITE_SECTIONS_EXT_CONV2D},       {"stem", 1, LCE_TFLITE_SECTIONS_EXT_STEM},
+      {"head", 2, kInternalHead}};
+  uint32_t words[3] = {0u, 0u, 0u};
+  std::string refusal;
+  if (!passes) refusal = "null passes";
+  for (const char* at = passes; at && *at && refusal.empty();) {
+    const char* end = strchr(at, ',');
+    const std::string name = end ? std::string(at, end) : std::string(at);
+    const Name* found = nullptr;
+    for (const Name& n : kNames)
+      if (name == n.name) found = &n;
+    if (!found) refusal = "passes: unknown name '" + name + "'";
+    else if (words[found->word] & found->bit) refusal = "passes: '" + name + "' is named twice";
+    else words[found->word] |= found->bit;
+    if (end && !end[1] && refusal.empty()) refusal = "passes: unknown name ''";      // a trailing comma
+    at = end ? end + 1 : nullptr;
+  }
+  return OpenWithFlags(data, size, words[0], ~0u, words[1], ~0u, refusal.empty() ? nullptr : refusal.c_str(), err, err_len, words[2]);
 }
 
 void lce_tflite_model_close(lce_tflite_model* model) { delete model; }
@@ -643,6 +792,33 @@ lce_hip_status lce_tflite_model_operator_depthwise(const lce_tflite_model* model
   options[0] = dw ? o.pool_padding : 0; options[1] = dw ? o.pool_stride_w : 0; options[2] = dw ? o.pool_stride_h : 0;
   options[3] = dw ? o.depth_multiplier : 0;
   options[4] = dw ? o.dilation_w : 1; options[5] = dw ? o.dilation_h : 1;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_tflite_model_operator_reducer(const lce_tflite_model* model, int32_t index, int32_t* keep_dims) {
+  if (!model || !keep_dims || index < 0 || index >= (int32_t)model->m.operators.size())
+    return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_reducer: bad argument");
+  *keep_dims = model->m.operators[index].keep_dims ? 1 : 0;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_tflite_model_operator_fully_connected(const lce_tflite_model* model, int32_t index, int32_t options[3], int32_t* present) {
+  if (!model || !options || !present || index < 0 || index >= (int32_t)model->m.operators.size())
+    return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_fully_connected: bad argument");
+  const lce_tfl::Operator& o = model->m.operators[index];
+  *present = o.has_fc_options ? 1 : 0;
+  options[0] = o.has_fc_options ? o.activation : 0;
+  options[1] = o.fc_weights_format;
+  options[2] = o.fc_keep_num_dims ? 1 : 0;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_tflite_model_operator_softmax(const lce_tflite_model* model, int32_t index, float* beta, int32_t* present) {
+  if (!model || !beta || !present || index < 0 || index >= (int32_t)model->m.operators.size())
+    return Fail(LCE_HIP_ERR_INVALID, "lce_tflite_model_operator_softmax: bad argument");
+  const lce_tfl::Operator& o = model->m.operators[index];
+  *present = o.has_softmax_options ? 1 : 0;
+  *beta = o.softmax_beta;
   return LCE_HIP_OK;
 }
 
@@ -1181,6 +1357,76 @@ struct Walk {
         });
   }
 
+  // ---- the classifier head ("head" of lce_tflite_model_open_passes).  Rank-2 tensors are carried as [batch, 1, 1, C]. ----
+  // An absorbed head operator `i` that streams ONE input and makes ONE float32 output of shape `os`, as ONE launch of pass
+  // `kind`.  `launch(in, weights, bias, out)` is the entry (`constants`: inputs 1 and 2 of the operator are its weights and its
+  // optional bias, uploaded once per model).  No LceQuantize folds into it, so the output is always written.
+  template <class Launch>
+  lce_hip_status HeadPass(int32_t i, int kind, const std::string& noun, const Shape& os, bool constants, Launch launch) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    int32_t want[4];
+    auto it = shapes.find(op.inputs[0]);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " reads a tensor nothing produced");
+    if (!Carried(M.tensors[op.inputs[0]], want) || !Agrees(it->second, lce_tfl::kTensorFloat32, want[1], want[2], want[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " input's shape or type does not match the one its producer infers");
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os, /*allowed=*/false);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(op.inputs[0], (noun + " input").c_str(), &in)) return s;
+    const float *weights = nullptr, *bias = nullptr;
+    if (constants)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &weights)) return s;
+    if (constants && op.inputs.size() == 3 && op.inputs[2] >= 0)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = launch((const float*)in, weights, bias, (float*)out)) return s;
+    return Launched(kind, fold);
+  }
+  Shape HeadShape(int32_t h, int32_t w, int32_t c) const {
+    Shape os;
+    os.dims[0] = batch; os.dims[1] = h; os.dims[2] = w; os.dims[3] = c;
+    os.type = lce_tfl::kTensorFloat32;
+    return os;
+  }
+
+  // An absorbed MEAN over height and width as ONE lce_hip_pool2d launch: the AVERAGE pool whose filter is the image.
+  lce_hip_status Mean(int32_t i) {
+    const lce_hip_pool2d_desc d = MeanDesc(model->m, model->m.operators[i], batch);
+    int32_t oh = 0, ow = 0;
+    if (lce_hip_status s = lce_hip_pool2d_check(&d, &oh, &ow)) return s;
+    return HeadPass(i, kAbsorbedMean, "a MEAN", HeadShape(oh, ow, d.channels), /*constants=*/false,
+                    [&](const float* x, const float*, const float*, float* out) { return lce_hip_pool2d(&d, x, out, nullptr, stream); });
+  }
+
+  // An absorbed float FULLY_CONNECTED as ONE lce_hip_fully_connected_f32 launch.
+  lce_hip_status FullyConnected(int32_t i) {
+    const lce_hip_fc_desc d = FullyConnectedDesc(model->m, model->m.operators[i], batch);
+    if (lce_hip_status s = lce_hip_fully_connected_f32_check(&d)) return s;
+    return HeadPass(i, kAbsorbedFullyConnected, "a FULLY_CONNECTED", HeadShape(1, 1, d.outputs), /*constants=*/true,
+                    [&](const float* x, const float* weights, const float* bias, float* out) {
+                      return lce_hip_fully_connected_f32(&d, x, weights, bias, out, stream);
+                    });
+  }
+
+  // An absorbed float SOFTMAX as ONE lce_hip_softmax_f32 launch.
+  lce_hip_status Softmax(int32_t i) {
+    const lce_tfl::Operator& op = model->m.operators[i];
+    int32_t id[4];
+    if (!Carried(model->m.tensors[op.inputs[0]], id)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a SOFTMAX of a rank that is neither 2 nor 4");
+    if (lce_hip_status s = lce_hip_softmax_f32_check((size_t)batch, (size_t)id[3], op.softmax_beta)) return s;
+    return HeadPass(i, kAbsorbedSoftmax, "a SOFTMAX", HeadShape(1, 1, id[3]), /*constants=*/false,
+                    [&](const float* x, const float*, const float*, float* out) {
+                      return lce_hip_softmax_f32((size_t)batch, (size_t)id[3], op.softmax_beta, x, out, stream);
+                    });
+  }
+
   // The four LCE operators.  `in` is the inferred shape of operator `i`'s first input, `in_dev` its device pointer (with `run`).
   lce_hip_status Quantize(int32_t i, const Shape& in, const void* in_dev) {                      // quantization.cc:19-41,76-114
     const lce_tfl::Operator& op = model->m.operators[i];
@@ -1294,9 +1540,14 @@ struct Walk {
     const lce_tfl::Model& M = model->m;
     for (int32_t t : sec.inputs) {
       const lce_tfl::Tensor& T = M.tensors[t];
-      if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
       Shape sh;
-      for (int k = 0; k < 4; ++k) sh.dims[k] = T.shape[k];
+      // (a rank-2 input -- of a head that starts behind a host operator -- is carried as [batch, 1, 1, C])
+      if (T.shape.size() == 2 && (model->flags_int & kInternalHead)) {
+        if (!Carried(T, sh.dims)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a section input with an extent that is not positive");
+      } else {
+        if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
+        for (int k = 0; k < 4; ++k) sh.dims[k] = T.shape[k];
+      }
       sh.dims[0] = batch;
       sh.type = T.type;
       shapes[t] = sh;
@@ -1315,14 +1566,18 @@ struct Walk {
 // order of the kinds (row k is kind k + 1).  A new pass is a row here, a predicate built from the helpers above, a walker that
 // ends in FoldQuantize / FoldBuffers / Launched, and an exported *_stats one-liner.
 const FusedPass kPasses[kAbsorbedCount - 1] = {
-    {kAbsorbedElementwise, false, LCE_TFLITE_SECTIONS_ELEMENTWISE, ElementwiseCandidate, &Walk::ElementwiseChain},
-    {kAbsorbedInt8Add, false, LCE_TFLITE_SECTIONS_INT8_ADD, Int8AddCandidate, &Walk::Int8Add},
-    {kAbsorbedConcat, false, LCE_TFLITE_SECTIONS_CONCAT, ConcatCandidate, &Walk::Concat},
-    {kAbsorbedPool, true, LCE_TFLITE_SECTIONS_EXT_POOL, PoolCandidate, &Walk::Pool2d},
-    {kAbsorbedConv1x1, true, LCE_TFLITE_SECTIONS_EXT_CONV1X1, Conv1x1Candidate, &Walk::Conv1x1},
-    {kAbsorbedDepthwise, true, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, DepthwiseCandidate, &Walk::Depthwise},
+    {kAbsorbedElementwise, 0, LCE_TFLITE_SECTIONS_ELEMENTWISE, ElementwiseCandidate, &Walk::ElementwiseChain},
+    {kAbsorbedInt8Add, 0, LCE_TFLITE_SECTIONS_INT8_ADD, Int8AddCandidate, &Walk::Int8Add},
+    {kAbsorbedConcat, 0, LCE_TFLITE_SECTIONS_CONCAT, ConcatCandidate, &Walk::Concat},
+    {kAbsorbedPool, 1, LCE_TFLITE_SECTIONS_EXT_POOL, PoolCandidate, &Walk::Pool2d},
+    {kAbsorbedConv1x1, 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1, Conv1x1Candidate, &Walk::Conv1x1},
+    {kAbsorbedDepthwise, 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, DepthwiseCandidate, &Walk::Depthwise},
     // (Conv1x1Candidate is tried first: with both bits a 1x1 filter runs as before)
-    {kAbsorbedConv2d, true, LCE_TFLITE_SECTIONS_EXT_CONV2D, Conv2dCandidate, &Walk::Conv2d},
+    {kAbsorbedConv2d, 1, LCE_TFLITE_SECTIONS_EXT_CONV2D, Conv2dCandidate, &Walk::Conv2d},
+    // the classifier head: one internal flag enables the three rows (lce_tflite_model_open_passes, "head")
+    {kAbsorbedMean, 2, kInternalHead, MeanCandidate, &Walk::Mean},
+    {kAbsorbedFullyConnected, 2, kInternalHead, FullyConnectedCandidate, &Walk::FullyConnected},
+    {kAbsorbedSoftmax, 2, kInternalHead, SoftmaxCandidate, &Walk::Softmax},
 };
 }  // namespace
 
@@ -1445,6 +1700,12 @@ void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches
 }
 void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
   PassStats(model, kAbsorbedConv2d, launches, quantize_folded);
+}
+
+void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {
+  PassStats(model, kAbsorbedMean, mean, nullptr);
+  PassStats(model, kAbsorbedFullyConnected, fully_connected, nullptr);
+  PassStats(model, kAbsorbedSoftmax, softmax, nullptr);
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

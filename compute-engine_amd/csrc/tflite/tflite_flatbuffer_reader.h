@@ -29,6 +29,10 @@
 //   BuiltinOptions union type 2 DepthwiseConv2DOptions: 0 padding(int8)  1 stride_w(int32)  2 stride_h(int32)
 //   3 depth_multiplier(int32)  4 fused_activation_function(int8)  5 dilation_w_factor(int32, default 1)
 //   6 dilation_h_factor(int32, default 1); BuiltinOperator 4 DEPTHWISE_CONV_2D.
+//   BuiltinOptions union type 27 ReducerOptions: 0 keep_dims(bool); BuiltinOperator 40 MEAN.
+//   BuiltinOptions union type 8 FullyConnectedOptions: 0 fused_activation_function(int8)  1 weights_format(int8, 0 DEFAULT)
+//   2 keep_num_dims(bool)  3 asymmetric_quantize_inputs(bool); BuiltinOperator 9 FULLY_CONNECTED.
+//   BuiltinOptions union type 9 SoftmaxOptions: 0 beta(float); BuiltinOperator 25 SOFTMAX.
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -46,7 +50,9 @@ namespace lce_tfl {
 
 constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
 constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinConv2d = 3, kBuiltinDepthwiseConv2d = 4, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
+constexpr int32_t kBuiltinFullyConnected = 9, kBuiltinSoftmax = 25, kBuiltinMean = 40;
 constexpr int kOptionsConv2d = 1, kOptionsDepthwiseConv2d = 2, kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
+constexpr int kOptionsFullyConnected = 8, kOptionsSoftmax = 9, kOptionsReducer = 27;
 // TensorType values used by LCE graphs
 constexpr int kTensorFloat32 = 0, kTensorInt32 = 2, kTensorBool = 6, kTensorInt8 = 9;
 
@@ -78,6 +84,12 @@ struct Operator {
   // DepthwiseConv2DOptions: padding, strides and dilations in the fields above; the multiplier (0 when absent)
   int32_t depth_multiplier = 0;
   bool has_depthwise_options = false;   // a DepthwiseConv2DOptions table is present
+  // ReducerOptions (false when absent); FullyConnectedOptions (its activation in `activation`); SoftmaxOptions
+  bool keep_dims = false;
+  bool has_fc_options = false, fc_keep_num_dims = false;
+  int32_t fc_weights_format = 0;
+  bool has_softmax_options = false;
+  float softmax_beta = 0.0f;
 };
 
 class Model {
@@ -291,6 +303,26 @@ class Model {
         O.pool_padding = pad;
         O.activation = act;
         O.has_depthwise_options = true;
+      }
+      if (opt_type == kOptionsReducer && opt_pos != 0) {
+        uint8_t keep;
+        if (!Indirect(opt_pos, &opt) || !Scalar<uint8_t>(opt, 0, 0, &keep)) return Fail("bad ReducerOptions");
+        O.keep_dims = keep != 0;
+      }
+      if (opt_type == kOptionsFullyConnected && opt_pos != 0) {
+        int8_t act, format;
+        uint8_t keep;
+        if (!Indirect(opt_pos, &opt) || !Scalar<int8_t>(opt, 0, 0, &act) || !Scalar<int8_t>(opt, 1, 0, &format) ||
+            !Scalar<uint8_t>(opt, 2, 0, &keep))
+          return Fail("bad FullyConnectedOptions");
+        O.activation = act;
+        O.fc_weights_format = format;
+        O.fc_keep_num_dims = keep != 0;
+        O.has_fc_options = true;
+      }
+      if (opt_type == kOptionsSoftmax && opt_pos != 0) {
+        if (!Indirect(opt_pos, &opt) || !Scalar<float>(opt, 0, 0.0f, &O.softmax_beta)) return Fail("bad SoftmaxOptions");
+        O.has_softmax_options = true;
       }
       for (int32_t x : O.inputs) if (x < -1 || x >= (int32_t)nt) return Fail("Operator input index out of range");
       for (int32_t x : O.outputs) if (x < 0 || x >= (int32_t)nt) return Fail("Operator output index out of range");

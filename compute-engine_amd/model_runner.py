@@ -35,6 +35,11 @@ With ``conv2d_sections=True`` (LCE_TFLITE_SECTIONS_EXT_CONV2D, the 56-byte optio
 them (``lce_hip_conv2d_f32``), and with ``stem_sections=True`` (LCE_TFLITE_SECTIONS_EXT_STEM) an operator that qualifies under an
 enabled flag and is ready from the start joins the first section instead of staying with the host: with every flag the stem and
 the body of a converted network are ONE section fed by the image, which ``predict`` runs; only the head stays with the host.
+With ``head_sections=True`` (the name ``head`` of ``lce_tflite_model_open_passes``: no bit and no size of the options struct) the
+float classifier head -- MEAN over height and width, FULLY_CONNECTED, SOFTMAX -- joins them too (``lce_hip_pool2d``,
+``lce_hip_fully_connected_f32``, ``lce_hip_softmax_f32``): with every flag a converted network is ONE section from the image to the
+class probabilities, ``lce_only`` is true and ``predict(images)`` returns ``[N, classes]`` with nothing but the image and the
+scores on the bus.  The walker carries the head's rank-2 tensors as ``[batch, 1, 1, C]``; the runner restores the file's rank.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -115,6 +120,10 @@ _SECTION_KEYWORDS = (
     ("conv2d_sections", 1, SECTIONS_EXT_CONV2D, 56),
     ("stem_sections", 1, SECTIONS_EXT_STEM, 56),
 )
+# the names of ``lce_tflite_model_open_passes`` (the only entry that knows ``head``), by keyword
+_PASS_NAMES = {"elementwise_sections": "elementwise", "int8_add_sections": "int8_add", "concat_sections": "concat",
+               "pool_sections": "pool", "conv1x1_sections": "conv1x1", "depthwise_sections": "depthwise",
+               "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head"}
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
 # ``lce_tflite_model_<pass>_stats``: the counters each reports
 _PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2}
@@ -147,6 +156,12 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_open_ex.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_char_p, C.c_size_t]
         l.lce_tflite_model_open_opts.restype = C.c_void_p
         l.lce_tflite_model_open_opts.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t]   # either form of the options
+        l.lce_tflite_model_open_passes.restype = C.c_void_p
+        l.lce_tflite_model_open_passes.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t]
+        l.lce_tflite_model_head_stats.argtypes, l.lce_tflite_model_head_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
+        l.lce_tflite_model_operator_reducer.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        l.lce_tflite_model_operator_fully_connected.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_tflite_model_operator_softmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_pool2d.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_conv2d.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_depthwise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
@@ -220,7 +235,7 @@ class LceModel:
     def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
                  int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
                  conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
-                 stem_sections: bool = False):
+                 stem_sections: bool = False, head_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -232,7 +247,9 @@ class LceModel:
         options).  ``conv2d_sections``: a float CONV_2D of any filter extent -- a network's stem -- joins them
         (LCE_TFLITE_SECTIONS_EXT_CONV2D).  ``stem_sections``: an operator that qualifies under an enabled flag and is ready from
         the start joins the first section instead of staying with the host (LCE_TFLITE_SECTIONS_EXT_STEM).  Both are bits of the
-        56-byte options, which no combination of the other flags without ``depthwise_sections`` uses."""
+        56-byte options, which no combination of the other flags without ``depthwise_sections`` uses.  ``head_sections``: the float
+        classifier head (MEAN over height and width, FULLY_CONNECTED, SOFTMAX) joins them; only then does the constructor go
+        through ``lce_tflite_model_open_passes``, which names the passes -- every other combination keeps its route."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -246,8 +263,12 @@ class LceModel:
             if given[keyword]:
                 words[word] |= bit
                 size = max(size, form)
+        self.head_sections = bool(head_sections)
         err = C.create_string_buffer(256)
-        if size:
+        if self.head_sections:
+            names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]] + ["head"]
+            self._h = tflite_lib().lce_tflite_model_open_passes(self._data, len(self._data), ",".join(names).encode(), err, 256)
+        elif size:
             opts = _OPEN_OPTIONS[size](size, *words[:1 if size == 8 else 2])
             self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
         else:
@@ -351,6 +372,12 @@ class LceModel:
         """(lce_hip_conv2d_f32 calls, LceQuantize launches they absorbed) of the last run."""
         return self._pass_stats("conv2d")
 
+    def head_stats(self):
+        """(MEAN launches, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches) of the last run."""
+        v = [C.c_int32() for _ in range(3)]
+        tflite_lib().lce_tflite_model_head_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -381,20 +408,21 @@ class Interpreter:
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
                  use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
                  concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
-                 depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False):
+                 depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False,
+                 head_sections: bool = False):
         """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
-        ``conv2d_sections``, ``stem_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+        ``conv2d_sections``, ``stem_sections``, ``head_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
                                     int8_add_sections=int8_add_sections, concat_sections=concat_sections,
                                     pool_sections=pool_sections, conv1x1_sections=conv1x1_sections,
                                     depthwise_sections=depthwise_sections, conv2d_sections=conv2d_sections,
-                                    stem_sections=stem_sections))
+                                    stem_sections=stem_sections, head_sections=head_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
+        if self.model.head_sections or any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()
@@ -476,6 +504,9 @@ class Interpreter:
             self.model.run_section(index, batch, [x.data_ptr() for x in ins], [y.data_ptr() for y in outs], stream, self._sem)
             for x in ins:                                    # (the launches read them after this call returns)
                 x.record_stream(torch.cuda.current_stream())
+        # (the walker is 4-D throughout: a rank-2 tensor of the classifier head comes back in the file's rank)
+        outs = [y.reshape((batch,) + tuple(self.model.tensors[t].shape[1:])) if len(self.model.tensors[t].shape) != 4 else y
+                for t, y in zip(sec.outputs, outs)]
         by_index = dict(zip(sec.outputs, outs))
         return [by_index[t] for t in (sec.outputs if wanted is None else wanted)]
 

@@ -395,6 +395,60 @@ lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* desc, const float* 
 lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* desc, int32_t* out_height, int32_t* out_width);
 
 /* ------------------------------------------------------------------------------------
+ * The float classifier head (TFLite builtin MEAN, FULLY_CONNECTED, SOFTMAX)
+ * ---------------------------------------------------------------------------------- */
+
+/* Every converted network ends in GlobalAveragePooling -> Dense -> softmax.  The MEAN over height and width is an AVERAGE pool
+ * whose filter is the image (lce_hip_pool2d: the sequential float sum in raster order, then the IEEE division by the count,
+ * which is reference_ops::Mean's arithmetic).  The other two:
+ *
+ * lce_hip_fully_connected_f32: out[batch][outputs] from in[batch][inputs], the weights in the file's layout
+ * [outputs][inputs] and an optional bias [outputs], in ONE launch.  The arithmetic is exactly lce_hip_conv1x1_f32's chain
+ * -- t = +0.0f; t = fmaf(x[k], w[o][k], t) over k = 0 .. inputs - 1 in order, never split over k; one float32 add of the bias
+ * (skipped when bias_dev is NULL); the std::max / std::min clamp (a NaN passes) -- so the bytes are those of
+ * lce_hip_conv1x1_f32 on a [batch, 1, 1, inputs] image.  The kernel is tiled for few rows and many columns (one wave per
+ * 16 x 16 tile: lce_kernels_head.h).
+ * Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc, input, weights or output, an extent <= 0, an unknown
+ * activation, an output that overlaps the input, the weights or the bias, a pointer that is not 4-byte aligned;
+ * LCE_HIP_ERR_UNSUPPORTED: 2^31 or more tiles of 16 x 16 outputs.  Pointers need 4-byte alignment only (16-byte aligned input
+ * and weights with inputs % 4 == 0 take a faster load path); offsets are 64-bit.  Asynchronous on `stream`, capturable in a HIP
+ * graph, allocates nothing and copies nothing between host and device. */
+typedef struct lce_hip_fc_desc {
+  int32_t batch, inputs, outputs;
+  int32_t activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+} lce_hip_fc_desc;
+lce_hip_status lce_hip_fully_connected_f32(const lce_hip_fc_desc* desc, const float* in_dev, const float* weights_dev /* [outputs][inputs] */,
+                                           const float* bias_dev /* nullable */, float* out_dev, void* stream);
+/* The descriptor checks of lce_hip_fully_connected_f32 alone.  Host only: needs no device. */
+lce_hip_status lce_hip_fully_connected_f32_check(const lce_hip_fc_desc* desc);
+
+/* lce_hip_softmax_f32: the softmax over the last axis of in[rows][cols], one launch.  No two libraries agree on the bytes of a
+ * float softmax (their exp differ), so the library states its own, every step a float32 add, multiply, fmaf, round-to-integer or
+ * exponent insertion that NumPy can restate (tests/head_ref.py does):
+ *   m     = max over the row (inputs finite; +0 and -0 compare equal and either gives the same bytes)
+ *   a_i   = (x_i - m) * beta                   two IEEE operations, no contraction
+ *   e_i   = E(a_i), where E(a) is
+ *             +0.0f unless a >= -104 (a < -104, -inf, NaN; exp(-104) is below half the smallest subnormal);  a > 0 counts as 0;
+ *             n = rint(a * 1.44269502f), to nearest even;
+ *             r = fmaf(n, -0.693145751953125f, a);  r = fmaf(n, -1.42860676e-06f, r);
+ *             p = 1.98412701e-04f;  p = fmaf(p, r, c) for c = 1.38888892e-03f, 8.33333377e-03f, 4.16666679e-02f, 1.66666672e-01f,
+ *             0.5f, 1.0f, 1.0f in this order (the Taylor polynomial of exp to r^7);
+ *             n >= -125: p with n added to its exponent field (a normal number);
+ *             n <  -125: p with n + 64 added to its exponent field, times 2^-64 in ONE float32 multiply (it rounds into the
+ *             subnormals: nothing is flushed).
+ *           E is within 1 ulp of exp on [-104, 0] (measured: DESIGN.md).
+ *   s     = the sum of the row in a FIXED order: 64 partial sums, partial sum l adding e_l, e_{l+64}, e_{l+128}, ... in this
+ *           order from +0.0f; then s_l = s_l + s_{l ^ d} for d = 32, 16, 8, 4, 2, 1 (every s_l ends as the same number)
+ *   out_i = e_i / s                            the correctly rounded float32 division
+ * A row that holds a NaN or an infinity does not fault; its bytes are unspecified.  in_dev == out_dev (in place) is allowed.
+ * Refused before any device call, LCE_HIP_ERR_INVALID: a NULL pointer, rows or cols of 0, a beta that is not finite and > 0, a
+ * pointer that is not 4-byte aligned, an output that overlaps the input without being it; LCE_HIP_ERR_UNSUPPORTED: cols >= 2^31
+ * or more than 2^60 elements.  Asynchronous on `stream`, capturable in a HIP graph, allocates nothing. */
+lce_hip_status lce_hip_softmax_f32(size_t rows, size_t cols, float beta, const float* in_dev, float* out_dev, void* stream);
+/* The argument checks of lce_hip_softmax_f32 that need no pointer.  Host only: needs no device. */
+lce_hip_status lce_hip_softmax_f32_check(size_t rows, size_t cols, float beta);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

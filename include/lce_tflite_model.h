@@ -139,7 +139,8 @@ lce_tflite_model* lce_tflite_model_open_ex(const void* data, size_t size, uint32
  *   partition changes.  A stem of such operators therefore joins the first LCE epoch: stem and body are one section whose
  *   input is the model's input tensor, and a section need not contain an LCE operator.  A stem operator that does not qualify
  *   (QUANTIZE, PAD, a uint8 input) still opens a builtin epoch, and what it feeds joins later by the rules above.  After both
- *   bits only the classifier head (MEAN, FULLY_CONNECTED, SOFTMAX) of a converted network is the host's.
+ *   bits only the classifier head (MEAN, FULLY_CONNECTED, SOFTMAX) of a converted network is the host's -- through this entry.
+ *   The head joins through lce_tflite_model_open_passes (below), which names passes instead of adding a bit or a size here.
  * The flags of both words combine. */
 enum { LCE_TFLITE_SECTIONS_CONCAT = 4u };
 enum {
@@ -160,6 +161,36 @@ typedef struct lce_tflite_open_options {
 } lce_tflite_open_options;
 lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, const lce_tflite_open_options* options, char* err,
                                              size_t err_len);
+
+/* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
+ *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head
+ * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
+ * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
+ * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
+ * lce_tflite_model_open_ex are unchanged: no bit and no size of lce_tflite_open_options enables what follows.
+ *   head: the float classifier head of a converted network (GlobalAveragePooling -> Dense -> softmax) joins the sections; no
+ *   other entry can ask for it.  A head operator is queued with the LCE operators whatever made it ready: behind the body (with
+ *   the flags that make the body one section) it joins the body's section, behind an operator of the host it opens a section
+ *   of its own.  Three builtin operators qualify.
+ *   MEAN (40): two inputs and one output; the data input is a non-constant float32 4-D tensor with positive extents; the axis
+ *   is a constant int32 scalar or vector with data in the file whose entries (negative ones + 4) are exactly {1, 2}; the output
+ *   is float32 [b, C] (ReducerOptions.keep_dims false, or no options table) or [b, 1, 1, C] (keep_dims true); and
+ *   lce_hip_pool2d_check accepts the AVERAGE, VALID, stride-1 pool whose filter is the image (H x W <= LCE_HIP_POOL_MAX_TAPS).
+ *   It runs as ONE lce_hip_pool2d launch, whose arithmetic (the sequential float sum in raster order, then the IEEE division
+ *   by the count) is reference_ops::Mean's.
+ *   FULLY_CONNECTED (9): 2 or 3 inputs (a third input of -1: no bias) and one output; input, weights and output float32, the
+ *   bias when present; the input is non-constant, of rank 2 or 4, and its extents behind the batch multiply to K; the weights
+ *   are a constant [N, K] with data in the file; the bias is absent or a constant [N]; the FullyConnectedOptions table is
+ *   present, weights_format is 0 (DEFAULT), keep_num_dims is false or the input is rank 2, the fused activation is NONE / RELU /
+ *   RELU_N1_TO_1 / RELU6; the output is [b, N]; and lce_hip_fully_connected_f32_check accepts the descriptor.  It runs as ONE
+ *   lce_hip_fully_connected_f32 launch (its arithmetic: include/lce_hip.h); weights and bias are uploaded once per model.
+ *   SOFTMAX (25): one float32 non-constant input [b, n] or [b, 1, 1, n] and an output of the same shape; the SoftmaxOptions
+ *   table is present and beta is finite and > 0.  It runs as ONE lce_hip_softmax_f32 launch (its bytes: include/lce_hip.h).
+ *   Everything else stays with the host, as before: int8 or hybrid FULLY_CONNECTED, a non-constant weight, shuffled weights, a
+ *   MEAN over other axes, TANH, a missing options table, RESHAPE / Flatten (so the three-layer head of BinaryAlexNet), LOGISTIC.
+ *   No LceQuantize folds into a head operator.  With every name a converted network is ONE section from the image to the
+ *   probabilities and no builtin operator is left for the host. */
+lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
 int32_t lce_tflite_model_num_tensors(const lce_tflite_model* model);
@@ -214,6 +245,19 @@ lce_hip_status lce_tflite_model_operator_conv2d(const lce_tflite_model* model, i
  * table is absent and for every other operator.  Its fused activation is reported by lce_tflite_model_operator_activation. */
 lce_hip_status lce_tflite_model_operator_depthwise(const lce_tflite_model* model, int32_t index, int32_t options[6]);
 
+/* ReducerOptions of a builtin MEAN (or another reducer), as the file says: *keep_dims is 0 or 1; 0 when the options table is absent
+ * and for every other operator. */
+lce_hip_status lce_tflite_model_operator_reducer(const lce_tflite_model* model, int32_t index, int32_t* keep_dims);
+
+/* FullyConnectedOptions of a builtin FULLY_CONNECTED, as the file says: options[0..2] = fused_activation_function,
+ * weights_format (0 DEFAULT, 1 SHUFFLED4x16INT8), keep_num_dims (0 or 1).  *present is 0, and options {0, 0, 0}, when the
+ * options table is absent and for every other operator. */
+lce_hip_status lce_tflite_model_operator_fully_connected(const lce_tflite_model* model, int32_t index, int32_t options[3], int32_t* present);
+
+/* SoftmaxOptions of a builtin SOFTMAX, as the file says: *beta.  *present is 0, and *beta 0, when the options table is absent
+ * and for every other operator. */
+lce_hip_status lce_tflite_model_operator_softmax(const lce_tflite_model* model, int32_t index, float* beta, int32_t* present);
+
 /* Binary SECTIONS of a mixed graph.  A converted model interleaves builtin float operators (the stem, batch norms, adds,
  * the head) with LCE custom ops; what this library runs are the maximal groups of LCE ops that can execute without a
  * builtin operator in between -- the partition a TFLite delegate would be handed (TensorFlow Lite's
@@ -254,7 +298,9 @@ lce_hip_status lce_tflite_model_section(const lce_tflite_model* model, int32_t i
 lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t section, int32_t batch, int32_t semantics,
                                             const void* const* inputs_dev, void* const* outputs_dev, void* stream);
 /* Shape ([N,H,W,C], C in words for bitpacked tensors) and size in bytes of a tensor section `section` reads or produces,
- * at `batch` images.  Host-only (no device needed). */
+ * at `batch` images.  The walk is 4-D throughout: a rank-2 tensor of the classifier head ([b, C] in the file: the output of a
+ * MEAN, a FULLY_CONNECTED or a SOFTMAX) reports {batch, 1, 1, C}; the bytes are the same, and the caller restores the file's
+ * rank.  Host-only (no device needed). */
 lce_hip_status lce_tflite_model_section_tensor_shape(lce_tflite_model* model, int32_t section, int32_t tensor, int32_t batch,
                                                      int32_t semantics, int32_t dims[4], size_t* bytes);
 
@@ -283,6 +329,9 @@ void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches
 /* The LAST run's lce_hip_conv2d_f32 calls (LCE_TFLITE_SECTIONS_EXT_CONV2D): launches (one per absorbed CONV_2D) and the
  * LceQuantize launches folded into them.  Nullable outputs. */
 void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's launches for the classifier head ("head" of lce_tflite_model_open_passes): lce_hip_pool2d launches that ran a
+ * MEAN, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches.  Nullable outputs. */
+void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
