@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
     "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
+    "lce_hip_conv2d_i8", "lce_hip_conv2d_i8_check", "lce_hip_conv2d_i8_prepare",
     "lce_hip_fully_connected_f32", "lce_hip_fully_connected_f32_check", "lce_hip_softmax_f32", "lce_hip_softmax_f32_check",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
@@ -117,6 +118,12 @@ class Conv2dDesc(C.Structure):
                                          "filter_width", "stride_height", "stride_width", "padding", "activation")]
 
 
+class Conv2dI8Desc(C.Structure):
+    """``lce_hip_conv2d_i8_desc``."""
+    _fields_ = Conv2dDesc._fields_ + [("input_scale", C.c_float), ("input_zero_point", C.c_int32), ("output_scale", C.c_float),
+                                      ("output_zero_point", C.c_int32)]
+
+
 class FcDesc(C.Structure):
     """``lce_hip_fc_desc``."""
     _fields_ = [(n, C.c_int32) for n in ("batch", "inputs", "outputs", "activation")]
@@ -178,6 +185,10 @@ def lib() -> C.CDLL:
         l.lce_hip_depthwise_conv2d_f32_check.argtypes = [C.POINTER(DepthwiseDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_conv2d_f32.argtypes = [C.POINTER(Conv2dDesc)] + [C.c_void_p] * 6
         l.lce_hip_conv2d_f32_check.argtypes = [C.POINTER(Conv2dDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_conv2d_i8.argtypes = [C.POINTER(Conv2dI8Desc)] + [C.c_void_p] * 6
+        l.lce_hip_conv2d_i8_check.argtypes = [C.POINTER(Conv2dI8Desc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_conv2d_i8_prepare.argtypes = [C.POINTER(Conv2dI8Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_fully_connected_f32.argtypes = [C.POINTER(FcDesc)] + [C.c_void_p] * 5
         l.lce_hip_fully_connected_f32_check.argtypes = [C.POINTER(FcDesc)]
         l.lce_hip_softmax_f32.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -876,6 +887,89 @@ def conv2d(x, w, bias=None, stride=1, padding=PADDING_SAME, activation=ACT_NONE,
     [B, OH, OW, ceil(Cout/32)] bits (value < 0), a tensor to fill, False for none.  Returns ``(out or None, bits or None)``."""
     desc, shape = _conv2d_check(x, w, bias, stride, padding, activation, out, out_bits)
     return _run_windowed("conv2d", "lce_hip_conv2d_f32", desc, shape, x, (w, bias), out, out_bits, stream)
+
+
+def _conv2d_i8_quantization(who, q_in, q_out):
+    """``q_in`` and ``q_out`` as (scale, zero_point) pairs of an int8 tensor: (si, zi, so, zo)."""
+    vals = []
+    for name, q in (("q_in", q_in), ("q_out", q_out)):
+        if not isinstance(q, (tuple, list)) or len(q) != 2:
+            raise ValueError("%s: %s must be (scale, zero_point), got %r" % (who, name, q))
+        scale, zp = float(np.float32(q[0])), q[1]
+        if not (np.isfinite(scale) and scale > 0):
+            raise ValueError("%s: %s scale must be finite and positive, got %r" % (who, name, q[0]))
+        if int(zp) != zp or not -128 <= int(zp) <= 127:
+            raise ValueError("%s: %s zero point must be an integer in [-128, 127], got %r" % (who, name, zp))
+        vals += [scale, int(zp)]
+    return tuple(vals)
+
+
+def _conv2d_i8_filter(who, w, cin=None):
+    """``w`` is int8 [Cout, fh, fw, Cin] (``cin``: the input's channels, None: any): its four extents."""
+    ws = tuple(int(v) for v in w.shape)
+    if _dtype_name(w) != "int8" or len(ws) != 4 or min(ws) < 1 or (cin is not None and ws[3] != cin):
+        raise ValueError("%s: w must be int8 [Cout, fh, fw, %s], got %s %r" % (who, "Cin" if cin is None else cin, w.dtype, ws))
+    return ws
+
+
+def conv2d_i8_prepare(w, bias, filter_scales, q_in, q_out, activation=ACT_NONE):
+    """The constants of one quantized CONV_2D for ``conv2d_i8`` (``lce_hip_conv2d_i8_prepare``, host only).  ``w``: int8 NumPy
+    [Cout, fh, fw, Cin] (zero point 0).  ``bias``: int32 [Cout] or None.  ``filter_scales``: one float or Cout of them.
+    ``q_in``, ``q_out``: (scale, zero_point) of the input and the output tensor.  Returns ``(table, act_min, act_max)``:
+    ``table`` is int32 [3, Cout] -- c[o] = bias[o] - zi * sum(w[o]), and QuantizeMultiplier(si * sw[o] / so)'s multiplier and
+    exponent -- which ``conv2d_i8`` takes; the activation range is CalculateActivationRangeQuantized's at ``q_out``.  Raises
+    ``LceHipError`` (ERR_UNSUPPORTED) where the reference's own int32 accumulator could overflow."""
+    who = "conv2d_i8_prepare"
+    cout, fh, fw, cin = _conv2d_i8_filter(who, w)
+    si, zi, so, zo = _conv2d_i8_quantization(who, q_in, q_out)
+    _padding_activation_check(who, None, activation)
+    if bias is not None and (_dtype_name(bias) != "int32" or tuple(bias.shape) != (cout,)):
+        raise ValueError("%s: bias must be int32 [%d], got %s %r" % (who, cout, bias.dtype, tuple(bias.shape)))
+    scales = np.ascontiguousarray(np.atleast_1d(np.asarray(filter_scales, np.float32)))
+    if scales.ndim != 1 or scales.size not in (1, cout):
+        raise ValueError("%s: filter_scales must be 1 or %d scales, got shape %r" % (who, cout, scales.shape))
+    wh = np.ascontiguousarray(w)
+    bh = None if bias is None else np.ascontiguousarray(bias)
+    # (the table depends on the filter and the quantization alone: the window of this descriptor is the filter itself)
+    desc = Conv2dI8Desc(1, fh, fw, cin, cout, fh, fw, 1, 1, PADDING_VALID, int(activation), si, zi, so, zo)
+    table = np.zeros((3, cout), np.int32)
+    lo, hi = C.c_int32(), C.c_int32()
+    check(lib().lce_hip_conv2d_i8_prepare(C.byref(desc), _host_ptr(wh), None if bh is None else _host_ptr(bh), _host_ptr(scales),
+                                          int(scales.size), _host_ptr(table), C.byref(lo), C.byref(hi)))
+    return table, lo.value, hi.value
+
+
+def _conv2d_i8_check(x, w, table, q_in, q_out, stride, padding, activation, out, out_bits):
+    """Argument checks of ``conv2d_i8`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (Conv2dI8Desc, output shape)."""
+    who = "conv2d_i8"
+    _, b, h, wd, cin = _nhwc_check(who, x, ("int8",))
+    cout, fh, fw, _ = _conv2d_i8_filter(who, w, cin)
+    if _dtype_name(table) != "int32" or tuple(table.shape) != (3, cout):
+        raise ValueError("%s: table must be int32 [3, %d] (conv2d_i8_prepare), got %s %r" % (who, cout, table.dtype, tuple(table.shape)))
+    si, zi, so, zo = _conv2d_i8_quantization(who, q_in, q_out)
+    sh, sw = _pair(who, "stride", stride)
+    _padding_activation_check(who, padding, activation)
+    oh, ow = _window_output_hw(who, (h, wd), (fh, fw), (sh, sw), padding)
+    shape = (b, oh, ow, cout)
+    _check_outputs(who, None if out is True else out, None if out_bits is False else out_bits, "int8", shape)
+    return Conv2dI8Desc(b, h, wd, cin, cout, fh, fw, sh, sw, int(padding), int(activation), si, zi, so, zo), shape
+
+
+def conv2d_i8(x, w, table, q_in, q_out, stride=1, padding=PADDING_SAME, activation=ACT_NONE, out=True, out_bits=False,
+              stream: int | None = None):
+    """TFLite's builtin quantized CONV_2D with a filter of any extent (the stem of an int8-converted network, the 1x1 of a
+    downsampling shortcut or a transition) and the LceQuantize of its result, in one launch on the int8 matrix instruction
+    (``lce_hip_conv2d_i8``).  ``x``: int8 NHWC on the device (or NumPy: copied to cuda:0 and back).  ``w``: int8
+    [Cout, fh, fw, Cin].  ``table``: int32 [3, Cout] from ``conv2d_i8_prepare`` for the same filter, quantization and
+    activation.  ``q_in``, ``q_out``: (scale, zero_point) of input and output.  ``stride``: an int or (height, width).
+    ``padding``: ``PADDING_SAME`` / ``PADDING_VALID`` (taps in the padding are skipped).  ``activation``: ``ACT_*``.  Integer
+    arithmetic, exact bytes: reference_integer_ops::ConvPerChannel in the double-rounding build (include/lce_hip.h).  ``out``:
+    True for a new int8 tensor, a tensor to fill (it must not overlap an operand), False for none.  ``out_bits``: True for new
+    int32 [B, OH, OW, ceil(Cout/32)] bits (value < output zero point), a tensor to fill, False for none.  Returns
+    ``(out or None, bits or None)``."""
+    desc, shape = _conv2d_i8_check(x, w, table, q_in, q_out, stride, padding, activation, out, out_bits)
+    return _run_windowed("conv2d_i8", "lce_hip_conv2d_i8", desc, shape, x, (w, table), out, out_bits, stream)
 
 
 def _fully_connected_check(x, w, bias, activation, out):

@@ -24,6 +24,7 @@
 #include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
 #include "lce_kernels_depthwise.h"   // (lce_tu_depthwise.hip)
 #include "lce_kernels_conv2d.h"      // (lce_tu_conv2d.hip)
+#include "lce_kernels_conv2d_i8.h"   // (lce_tu_conv2d_i8.hip)
 #include "lce_kernels_head.h"        // (lce_tu_head.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
@@ -48,6 +49,7 @@
 #include "lce_tu_conv1x1.hip"
 #include "lce_tu_depthwise.hip"
 #include "lce_tu_conv2d.hip"
+#include "lce_tu_conv2d_i8.hip"
 #include "lce_tu_head.hip"
 #endif
 #include "lce_plan.h"
@@ -1178,8 +1180,10 @@ lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* d, con
 // ------------------------------------------------------------------------------------
 // float CONV_2D of any filter extent (lce_kernels_conv2d.h)
 // ------------------------------------------------------------------------------------
-lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* d, int32_t* out_height, int32_t* out_width) {
-  const char* who = "lce_hip_conv2d_f32";
+}  // extern "C"
+namespace {
+// The descriptor checks the float and the int8 CONV_2D share: every message is `who`'s own.
+lce_hip_status conv2d_desc_check(const char* who, const lce_hip_conv2d_desc* d, int32_t* out_height, int32_t* out_width) {
   if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
   if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels_in <= 0 || d->channels_out <= 0)
     return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d] -> %d channels", who, (int)d->batch,
@@ -1198,6 +1202,11 @@ lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* d, int32_t* o
   if ((int64_t)d->channels_out > 65535ll * lce::kConv2dBN)
     return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: more than %lld output channels are not supported", who, 65535ll * lce::kConv2dBN);
   return window_output(who, w, out_height, out_width);
+}
+}  // namespace
+extern "C" {
+lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* d, int32_t* out_height, int32_t* out_width) {
+  return conv2d_desc_check("lce_hip_conv2d_f32", d, out_height, out_width);
 }
 
 lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* d, const float* in_dev, const float* filter_dev, const float* bias_dev,
@@ -1221,6 +1230,144 @@ lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* d, const float* in_
   float_activation_range(d->activation, &a.lo, &a.hi);
   const bool vec = Cin % 4 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
   const int e = lce::launch_conv2d(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// int8 CONV_2D of any filter extent (lce_kernels_conv2d_i8.h)
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+static_assert(lce::kConvI8BN == lce::kConv2dBN, "conv2d_desc_check bounds the output channels for both");
+
+// The quantization of a lce_hip_conv2d_i8_desc: scales finite and positive, zero points int8 values.
+lce_hip_status conv2d_i8_quantization_check(const char* who, const lce_hip_conv2d_i8_desc* d) {
+  const float scales[2] = {d->input_scale, d->output_scale};
+  const int32_t zps[2] = {d->input_zero_point, d->output_zero_point};
+  static const char* const names[2] = {"input", "output"};
+  for (int i = 0; i < 2; ++i) {
+    if (!std::isfinite(scales[i]) || !(scales[i] > 0.0f))
+      return fail(LCE_HIP_ERR_INVALID, "%s: %s_scale must be finite and positive, got %g", who, names[i], (double)scales[i]);
+    if (zps[i] < -128 || zps[i] > 127)
+      return fail(LCE_HIP_ERR_INVALID, "%s: %s_zero_point must be in [-128, 127], got %d", who, names[i], (int)zps[i]);
+  }
+  return LCE_HIP_OK;
+}
+
+lce_hip_conv2d_desc conv2d_i8_window(const lce_hip_conv2d_i8_desc* d) {
+  return lce_hip_conv2d_desc{d->batch, d->in_height, d->in_width, d->channels_in, d->channels_out, d->filter_height, d->filter_width,
+                             d->stride_height, d->stride_width, d->padding, d->activation};
+}
+
+// Everything lce_hip_conv2d_i8_check refuses but the K limit, which lce_hip_conv2d_i8_prepare states with the bias and a channel.
+lce_hip_status conv2d_i8_desc_check(const char* who, const lce_hip_conv2d_i8_desc* d, int32_t* out_height, int32_t* out_width) {
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  const lce_hip_conv2d_desc w = conv2d_i8_window(d);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = conv2d_desc_check(who, &w, &oh, &ow)) return s;
+  if (lce_hip_status s = conv2d_i8_quantization_check(who, d)) return s;
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+}  // namespace
+extern "C" {
+
+lce_hip_status lce_hip_conv2d_i8_check(const lce_hip_conv2d_i8_desc* d, int32_t* out_height, int32_t* out_width) {
+  const char* who = "lce_hip_conv2d_i8";
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = conv2d_i8_desc_check(who, d, &oh, &ow)) return s;
+  // (lce_hip_conv2d_i8_prepare's first bound without a bias: beyond it no table exists, and the kernel's 32-bit window
+  // arithmetic relies on it)
+  const uint64_t K = (uint64_t)d->filter_height * d->filter_width * (uint64_t)d->channels_in;       // < 2^31
+  if (K > lce::kConvI8MaxK)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: a filter of %llu elements per output channel could overflow the int32 accumulator "
+                "(255 x 128 x K must not exceed 2^31 - 1: K <= %u)", who, (unsigned long long)K, (unsigned)lce::kConvI8MaxK);
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_conv2d_i8_prepare(const lce_hip_conv2d_i8_desc* d, const int8_t* filter_host, const int32_t* bias_host,
+                                         const float* filter_scales, int32_t n_scales, int32_t* table, int32_t* act_min, int32_t* act_max) {
+  const char* who = "lce_hip_conv2d_i8_prepare";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!filter_host) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
+  if (!filter_scales) return fail(LCE_HIP_ERR_INVALID, "%s: null filter scales", who);
+  if (!table || !act_min || !act_max) return fail(LCE_HIP_ERR_INVALID, "%s: null result", who);
+  if (lce_hip_status s = conv2d_i8_desc_check(who, d, nullptr, nullptr)) return s;
+  const int64_t N = d->channels_out, K = (int64_t)d->filter_height * d->filter_width * d->channels_in;       // K < 2^31
+  if (n_scales != 1 && (int64_t)n_scales != N)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the filter has %d scales, neither 1 nor one per output channel (%d)", who, (int)n_scales, (int)N);
+  for (int32_t o = 0; o < n_scales; ++o)
+    if (!std::isfinite(filter_scales[o]) || !(filter_scales[o] > 0.0f))
+      return fail(LCE_HIP_ERR_INVALID, "%s: the filter scale of channel %d must be finite and positive, got %g", who, (int)o,
+                  (double)filter_scales[o]);
+  // The reference's accumulator: |x - zi| <= 255, |w| <= 128, K products and the bias.
+  const int64_t kMax = 2147483647ll;
+  int64_t B = 0, b_channel = 0;
+  if (bias_host)
+    for (int64_t o = 0; o < N; ++o) {
+      const int64_t v = bias_host[o] < 0 ? -(int64_t)bias_host[o] : (int64_t)bias_host[o];
+      if (v > B) { B = v; b_channel = o; }
+    }
+  const int64_t bound = 255ll * 128ll * K + B;                                     // < 2^47
+  if (bound > kMax)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: 255 x 128 x K + |bias| = 255 x 128 x %lld + %lld exceeds 2^31 - 1: the reference's "
+                "int32 accumulator could overflow", who, (long long)b_channel, (long long)K, (long long)B);
+  const int32_t zi = d->input_zero_point;
+  for (int64_t o = 0; o < N; ++o) {
+    const double real = (double)d->input_scale * (double)filter_scales[n_scales == 1 ? 0 : o] / (double)d->output_scale;
+    int32_t m = 0, e = 0;
+    quantize_multiplier(real, &m, &e);
+    if (e > 0 && (e >= 31 || (bound << e) > kMax))
+      return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: the accumulator bound %lld times 2^%d (the left shift of its multiplier %g) "
+                  "exceeds 2^31 - 1", who, (long long)o, (long long)bound, (int)e, real);
+    int64_t sum = 0;
+    const int8_t* w = filter_host + (uint64_t)o * (uint64_t)K;
+    for (int64_t k = 0; k < K; ++k) sum += w[k];
+    // |zi * sum| <= 128 x 128 x K and |bias[o]| <= B, so |c| <= 128 x 128 x K + B <= 255 x 128 x K + B = bound <= 2^31 - 1:
+    // the first bound already implies that c fits.  Checked all the same.
+    const int64_t c = (bias_host ? (int64_t)bias_host[o] : 0ll) - (int64_t)zi * sum;
+    if (c > kMax || c < -kMax - 1)
+      return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: the constant bias - zero_point x sum(w) = %lld does not fit int32", who,
+                  (long long)o, (long long)c);
+    table[o] = (int32_t)c;
+    table[N + o] = m;
+    table[2 * N + o] = e;
+  }
+  quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, act_min, act_max);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_conv2d_i8(const lce_hip_conv2d_i8_desc* d, const int8_t* in_dev, const int8_t* filter_dev, const int32_t* table_dev,
+                                 int8_t* out_dev, int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_conv2d_i8";
+  if (lce_hip_status s = check_pointers(who, d, in_dev, /*has_filter=*/true, filter_dev, out_dev, out_bits_dev)) return s;
+  if (!table_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null table", who);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = lce_hip_conv2d_i8_check(d, &oh, &ow)) return s;
+  const uint64_t Cin = (uint64_t)d->channels_in, N = (uint64_t)d->channels_out;
+  const uint64_t K = (uint64_t)d->filter_height * d->filter_width * Cin;
+  const uint64_t pixels = (uint64_t)d->batch * oh * ow, wpr = (N + 31) / 32;
+  const Span in(in_dev, (uint64_t)d->batch * d->in_height * d->in_width * Cin), filter(filter_dev, N * K), table(table_dev, 3 * N * 4);
+  const Span out(out_dev, pixels * N), bits(out_bits_dev, pixels * wpr * 4);
+  // (the table stands where the float entry has its bias)
+  if (meet(out.lo, out.hi, table.lo, table.hi) || meet(bits.lo, bits.hi, table.lo, table.hi))
+    return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the table", who);
+  if (lce_hip_status s = check_operand_ranges(who, in, filter, Span(nullptr, 0), out, bits, /*float_operands=*/false)) return s;
+  if (table.lo % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: table_dev must be 4-byte aligned", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::ConvI8Args a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.filter = filter_dev; a.table = table_dev; a.out = out_dev; a.bits = (uint32_t*)out_bits_dev;
+  lce::conv2d_i8_geometry(a, d->batch, d->in_height, d->in_width, d->channels_in, d->channels_out, d->filter_height, d->filter_width,
+                          d->stride_height, d->stride_width, oh, ow);
+  a.zi = d->input_zero_point; a.zo = d->output_zero_point;
+  quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, &a.act_min, &a.act_max);
+  const bool vec = Cin % 16 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
+  const int e = lce::launch_conv2d_i8(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }

@@ -22,14 +22,14 @@ struct lce_tflite_section {
 };
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
-       kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedCount };
+       kAbsorbedConvI8, kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
-enum { kInternalHead = 1u };
+enum { kInternalHead = 1u, kInternalConvI8 = 2u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
-  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head")
+  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8")
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
@@ -40,6 +40,8 @@ struct lce_tflite_model {
   struct DevBuf { void* ptr = nullptr; size_t bytes = 0; };
   std::map<int32_t, DevBuf> scratch;                                    // intermediate tensors of a section, grow-only
   std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
+  std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D operator: lce_hip_conv2d_i8_prepare's table, uploaded once
+  std::map<int32_t, std::vector<int32_t>> host_tables;                  // ... as Partition() prepared it; dropped once it is on the device
   // What one run launched.  A recorded graph keeps the record of its recording, so a replay reports the same numbers.
   struct RunStats {
     int32_t conv_quantize = 0;                                          // LceQuantize launches folded into a convolution (run_dual)
@@ -73,6 +75,7 @@ struct lce_tflite_model {
     for (auto& kv : plans) lce_hip_bconv2d_plan_destroy(kv.second);
     for (auto& kv : scratch) if (kv.second.ptr) lce_hip_free(kv.second.ptr);
     for (auto& kv : consts) if (kv.second.ptr) lce_hip_free(kv.second.ptr);
+    for (auto& kv : tables) if (kv.second.ptr) lce_hip_free(kv.second.ptr);
   }
 };
 
@@ -374,6 +377,85 @@ bool Conv2dCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return lce_hip_conv2d_f32_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
 }
 
+// lce_hip_conv2d_i8_desc of a builtin int8 CONV_2D at `batch` images, from its options and the FILE's input, filter and output tensors.
+lce_hip_conv2d_i8_desc ConvI8Desc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  lce_hip_conv2d_i8_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = batch; d.in_height = in.shape[1]; d.in_width = in.shape[2]; d.channels_in = in.shape[3];
+  d.channels_out = flt.shape[0];
+  d.filter_height = flt.shape[1]; d.filter_width = flt.shape[2];
+  d.stride_height = o.pool_stride_h; d.stride_width = o.pool_stride_w;
+  d.padding = o.pool_padding;
+  d.activation = o.activation;
+  d.input_scale = in.scale; d.input_zero_point = (int32_t)in.zero_point;
+  d.output_scale = out.scale; d.output_zero_point = (int32_t)out.zero_point;
+  return d;
+}
+
+// lce_hip_conv2d_i8_prepare on the FILE's constants of int8 CONV_2D `o` (the candidate has checked their types and sizes).
+lce_hip_status ConvI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_hip_conv2d_i8_desc d = ConvI8Desc(M, o, M.tensors[o.inputs[0]].shape[0]);
+  const bool has_bias = o.inputs.size() == 3 && o.inputs[2] >= 0;
+  // (flatbuffer vectors are only guaranteed 4-byte aligned, which is what int32 and float need)
+  std::vector<int32_t> bias;
+  if (has_bias) {
+    bias.resize((size_t)flt.shape[0]);
+    memcpy(bias.data(), M.tensors[o.inputs[2]].data, bias.size() * 4);
+  }
+  table->assign((size_t)flt.shape[0] * 3, 0);
+  int32_t lo = 0, hi = 0;
+  return lce_hip_conv2d_i8_prepare(&d, (const int8_t*)flt.data, has_bias ? bias.data() : nullptr, flt.scales.data(), (int32_t)flt.scales.size(),
+                                   table->data(), &lo, &hi);
+}
+
+// The static half of "a builtin CONV_2D that a section may run" ("conv2d_i8" of lce_tflite_model_open_passes): the quantized
+// convolution of an int8-converted network -- its stem, the 1x1 of a downsampling shortcut or of a transition.  The options
+// table present; 2 or 3 inputs (a third input of -1: no bias) and one output; input and output int8, quantized with exactly ONE
+// scale and a zero point in [-128, 127]; a 4-D output with positive extents; a non-constant 4-D data input; the filter a
+// constant int8 [Cout, fh, fw, Cin] with data in the file whose byte count matches (compared by division), Cin the input's
+// channels (a grouped filter is the host's), no zero point other than 0, and 1 or Cout scales -- with more than one,
+// quantized_dimension 0; the bias absent or a constant int32 [Cout]; Cout the output's channels; strides positive, dilations 1,
+// padding SAME or VALID, a known activation; and the declared output height and width what the padding rule gives.  Partition()
+// then asks lce_hip_conv2d_i8_prepare ONCE whether it accepts the file's constants (a pass over the whole filter) and keeps the
+// table for the run; it also decides the other half -- when the operator becomes ready.
+bool ConvI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinConv2d || !o.has_conv_options) return false;
+  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorInt8 || flt.type != lce_tfl::kTensorInt8 || out.type != lce_tfl::kTensorInt8) return false;
+  if (!StreamedImages(in, out)) return false;
+  for (const lce_tfl::Tensor* t : {&in, &out})
+    if (!t->quantized || t->scales.size() != 1 || t->zero_points.size() > 1 || t->zero_point < -128 || t->zero_point > 127) return false;
+  if (!flt.data || flt.shape.size() != 4) return false;
+  uint64_t elems = (uint64_t)flt.bytes;
+  for (int32_t extent : flt.shape) {
+    if (extent <= 0 || elems % (uint64_t)extent != 0) return false;
+    elems /= (uint64_t)extent;
+  }
+  if (elems != 1 || flt.shape[3] != in.shape[3] || out.shape[3] != flt.shape[0]) return false;
+  for (int64_t z : flt.zero_points)
+    if (z != 0) return false;
+  const size_t n_scales = flt.scales.size();
+  if (n_scales != 1 && n_scales != (size_t)flt.shape[0]) return false;
+  if (n_scales > 1 && flt.quantized_dimension != 0) return false;
+  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
+    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
+    if (bias.type != lce_tfl::kTensorInt32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != flt.shape[0] ||
+        (uint64_t)bias.bytes != (uint64_t)flt.shape[0] * 4u)
+      return false;
+  }
+  if (!ConvOptions(o)) return false;
+  const lce_hip_conv2d_i8_desc d = ConvI8Desc(M, o, in.shape[0]);
+  int32_t oh = 0, ow = 0;
+  return lce_hip_conv2d_i8_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
+}
+
 
 // ---- the classifier head (lce_tflite_model_open_passes, "head") ----
 // A head tensor as the section walker carries it: a rank-4 tensor as it is, a rank-2 tensor [b, C] as [b, 1, 1, C]; the extents
@@ -523,6 +605,12 @@ void lce_tflite_model::Partition() {
     // that is ready from the start -- a stem op -- is a builtin one without LCE_TFLITE_SECTIONS_EXT_STEM, below)
     for (const FusedPass& p : kPasses)
       if (!candidate[i] && (words[p.word] & p.bit) && p.candidate(m, m.operators[i])) candidate[i] = (char)p.kind;
+    // an int8 CONV_2D also needs constants lce_hip_conv2d_i8_prepare accepts: prepared here, once, and kept for the first run
+    if (candidate[i] == kAbsorbedConvI8) {
+      std::vector<int32_t> table;
+      if (ConvI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
+      else candidate[i] = 0;
+    }
     // a head operator (MEAN, FULLY_CONNECTED, SOFTMAX) is queued as the LCE operators are, whatever made it ready: behind a host
     // operator the head is a section of its own, behind the body it joins the body's epoch
     if (candidate[i] >= kAbsorbedMean) is_lce[i] = 1;
@@ -683,7 +771,7 @@ lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, co
       {"concat", 0, LCE_TFLITE_SECTIONS_CONCAT},           {"pool", 1, LCE_TFLITE_SECTIONS_EXT_POOL},
       {"conv1x1", 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1},     {"depthwise", 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE},
       {"conv2d", 1, LCE_TFLITE_SECTIONS_EXT_CONV2D},       {"stem", 1, LCE_TFLITE_SECTIONS_EXT_STEM},
-      {"head", 2, kInternalHead}};
+      {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8}};
   uint32_t words[3] = {0u, 0u, 0u};
   std::string refusal;
   if (!passes) refusal = "null passes";
@@ -734,6 +822,14 @@ lce_hip_status lce_tflite_model_tensor(const lce_tflite_model* model, int32_t in
   info->bytes = t.bytes;
   info->name = t.name.c_str();
   return LCE_HIP_OK;
+}
+
+int32_t lce_tflite_model_tensor_scales(const lce_tflite_model* model, int32_t index, float* scales, int32_t cap, int32_t* quantized_dimension) {
+  if (!model || index < 0 || index >= (int32_t)model->m.tensors.size()) return -1;
+  const lce_tfl::Tensor& t = model->m.tensors[index];
+  for (int32_t k = 0; scales && k < cap && k < (int32_t)t.scales.size(); ++k) scales[k] = t.scales[k];
+  if (quantized_dimension) *quantized_dimension = t.quantized_dimension;
+  return (int32_t)t.scales.size();
 }
 
 lce_hip_status lce_tflite_model_operator(const lce_tflite_model* model, int32_t index, lce_tflite_operator_info* info) {
@@ -1357,6 +1453,38 @@ struct Walk {
         });
   }
 
+  // An absorbed int8 CONV_2D of any filter extent ("conv2d_i8" of lce_tflite_model_open_passes) as ONE lce_hip_conv2d_i8 launch.
+  // The table Partition() had lce_hip_conv2d_i8_prepare make of the file's constants is uploaded once per model, where the filters are.
+  lce_hip_status ConvI8(int32_t i) {
+    const lce_tfl::Operator& op = model->m.operators[i];
+    const lce_hip_conv2d_i8_desc d = ConvI8Desc(model->m, op, batch);
+    return StreamingPass(
+        i, kAbsorbedConvI8, "an int8 CONV_2D", lce_tfl::kTensorInt8, d.channels_out,
+        [&](int32_t* h, int32_t* w) { return lce_hip_conv2d_i8_check(&d, h, w); },
+        [&](const void* x, const float* filter, const float*, void* out, int32_t* bits) -> lce_hip_status {
+          lce_tflite_model::DevBuf& b = model->tables[i];
+          if (!b.ptr) {
+            if (capturing) return Fail(LCE_HIP_ERR_INVALID, "run_section: a constant would have to be uploaded during graph capture");
+            auto prepared = model->host_tables.find(i);
+            if (prepared == model->host_tables.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 CONV_2D without a prepared table");
+            const std::vector<int32_t>& table = prepared->second;
+            // (the buffer becomes the model's only once the copy has completed: a failed upload leaves nothing a later run would launch on)
+            void* dev = nullptr;
+            if (lce_hip_status s = lce_hip_malloc(&dev, table.size() * 4)) return s;
+            lce_hip_status s = lce_hip_memcpy_h2d(dev, table.data(), table.size() * 4, stream);
+            if (s == LCE_HIP_OK) s = lce_hip_stream_synchronize(stream);
+            if (s != LCE_HIP_OK) {
+              lce_hip_free(dev);
+              return s;
+            }
+            b.ptr = dev;
+            b.bytes = table.size() * 4;
+            model->host_tables.erase(prepared);
+          }
+          return lce_hip_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, (const int32_t*)b.ptr, (int8_t*)out, bits, stream);
+        });
+  }
+
   // ---- the classifier head ("head" of lce_tflite_model_open_passes).  Rank-2 tensors are carried as [batch, 1, 1, C]. ----
   // An absorbed head operator `i` that streams ONE input and makes ONE float32 output of shape `os`, as ONE launch of pass
   // `kind`.  `launch(in, weights, bias, out)` is the entry (`constants`: inputs 1 and 2 of the operator are its weights and its
@@ -1574,6 +1702,8 @@ const FusedPass kPasses[kAbsorbedCount - 1] = {
     {kAbsorbedDepthwise, 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, DepthwiseCandidate, &Walk::Depthwise},
     // (Conv1x1Candidate is tried first: with both bits a 1x1 filter runs as before)
     {kAbsorbedConv2d, 1, LCE_TFLITE_SECTIONS_EXT_CONV2D, Conv2dCandidate, &Walk::Conv2d},
+    // the quantized convolution: an internal flag (lce_tflite_model_open_passes, "conv2d_i8"); no float predicate takes an int8 tensor
+    {kAbsorbedConvI8, 2, kInternalConvI8, ConvI8Candidate, &Walk::ConvI8},
     // the classifier head: one internal flag enables the three rows (lce_tflite_model_open_passes, "head")
     {kAbsorbedMean, 2, kInternalHead, MeanCandidate, &Walk::Mean},
     {kAbsorbedFullyConnected, 2, kInternalHead, FullyConnectedCandidate, &Walk::FullyConnected},
@@ -1700,6 +1830,9 @@ void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches
 }
 void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
   PassStats(model, kAbsorbedConv2d, launches, quantize_folded);
+}
+void lce_tflite_model_conv_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  PassStats(model, kAbsorbedConvI8, launches, quantize_folded);
 }
 
 void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {

@@ -12,7 +12,7 @@
 //   OperatorCode     0 deprecated_builtin_code(int8)  1 custom_code  2 version  3 builtin_code(int32)
 //   SubGraph         0 tensors  1 inputs  2 outputs  3 operators  4 name
 //   Tensor           0 shape  1 type(int8)  2 buffer(uint32)  3 name  4 quantization
-//   QuantizationParameters  0 min  1 max  2 scale[float]  3 zero_point[int64]
+//   QuantizationParameters  0 min  1 max  2 scale[float]  3 zero_point[int64]  4/5 details (union)  6 quantized_dimension(int32)
 //   Operator         0 opcode_index  1 inputs  2 outputs  3/4 builtin_options (union)
 //                    5 custom_options[ubyte]  6 custom_options_format
 //   Buffer           0 data[ubyte]
@@ -62,8 +62,11 @@ struct Tensor {
   uint32_t buffer = 0;
   std::string name;
   bool quantized = false;
-  float scale = 0.0f;
-  int64_t zero_point = 0;
+  float scale = 0.0f;                // the first element of `scales`
+  int64_t zero_point = 0;            // the first element of `zero_points`
+  std::vector<float> scales;         // the whole scale vector: one element per tensor, or one per slice of quantized_dimension
+  std::vector<int64_t> zero_points;
+  int32_t quantized_dimension = 0;
   const uint8_t* data = nullptr;   // constant data (inside the model buffer), or null
   size_t bytes = 0;
 };
@@ -240,8 +243,13 @@ class Model {
         if (!Indirect(qp, &q)) return Fail("bad Tensor.quantization");
         if (!VecField(q, 2, 4, &c, &f)) return Fail("bad QuantizationParameters.scale");
         if (c >= 1) { memcpy(&T.scale, b_ + f, 4); T.quantized = true; }
+        T.scales.resize(c);                                        // (VecField has checked that c elements lie in the buffer)
+        if (c) memcpy(T.scales.data(), b_ + f, (size_t)c * 4);
         if (!VecField(q, 3, 8, &c, &f)) return Fail("bad QuantizationParameters.zero_point");
         if (c >= 1) memcpy(&T.zero_point, b_ + f, 8);
+        T.zero_points.resize(c);
+        if (c) memcpy(T.zero_points.data(), b_ + f, (size_t)c * 8);
+        if (!Scalar<int32_t>(q, 6, 0, &T.quantized_dimension)) return Fail("bad QuantizationParameters.quantized_dimension");
       }
     }
     uint32_t no; size_t ofirst;

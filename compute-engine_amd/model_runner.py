@@ -40,6 +40,11 @@ float classifier head -- MEAN over height and width, FULLY_CONNECTED, SOFTMAX --
 ``lce_hip_fully_connected_f32``, ``lce_hip_softmax_f32``): with every flag a converted network is ONE section from the image to the
 class probabilities, ``lce_only`` is true and ``predict(images)`` returns ``[N, classes]`` with nothing but the image and the
 scores on the bus.  The walker carries the head's rank-2 tensors as ``[batch, 1, 1, C]``; the runner restores the file's rank.
+With ``conv2d_i8_sections=True`` (the name ``conv2d_i8`` of ``lce_tflite_model_open_passes``) the quantized CONV_2D of an
+int8-converted network -- its stem, the 1x1 of a downsampling shortcut or a transition -- joins them (``lce_hip_conv2d_i8``:
+TFLite's integer arithmetic byte for byte on the int8 matrix instruction); with ``int8_add_sections``, ``pool_sections`` and
+``stem_sections`` an int8 residual block with its shortcut, and an int8 stem with the binary layer behind it, are one section each.  Measured at batch 256 (profiles/conv2d_i8): the kernel takes 0.80 (3x3 / 2 stem), 0.41 (7x7 / 2
+stem) and 0.57 (1x1 shortcut) of the float entry's time at the same shape.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -123,10 +128,10 @@ _SECTION_KEYWORDS = (
 # the names of ``lce_tflite_model_open_passes`` (the only entry that knows ``head``), by keyword
 _PASS_NAMES = {"elementwise_sections": "elementwise", "int8_add_sections": "int8_add", "concat_sections": "concat",
                "pool_sections": "pool", "conv1x1_sections": "conv1x1", "depthwise_sections": "depthwise",
-               "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head"}
+               "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head", "conv2d_i8_sections": "conv2d_i8"}
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
 # ``lce_tflite_model_<pass>_stats``: the counters each reports
-_PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2}
+_PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2}
 
 
 class Section:
@@ -176,6 +181,7 @@ def tflite_lib() -> C.CDLL:
         for f in ("lce_tflite_model_inputs", "lce_tflite_model_outputs"):
             getattr(l, f).argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
         l.lce_tflite_model_tensor.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_TensorInfo)]
+        l.lce_tflite_model_tensor_scales.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator.argtypes = [C.c_void_p, C.c_int32, C.POINTER(_OperatorInfo)]
         l.lce_tflite_model_bconv2d_plan.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
         l.lce_tflite_option_int.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_int32)]
@@ -197,7 +203,9 @@ def tflite_lib() -> C.CDLL:
 
 
 class Tensor:
-    def __init__(self, info: _TensorInfo):
+    def __init__(self, info: _TensorInfo, scales=(), quantized_dimension: int = 0):
+        self.scales = tuple(scales)                       # the whole scale vector of the file (per-channel filters: one per channel)
+        self.quantized_dimension = int(quantized_dimension)
         self.type = info.type
         self.shape = tuple(info.dims[i] for i in range(info.rank))
         self.scale = float(info.scale) if info.quantized else None
@@ -235,7 +243,7 @@ class LceModel:
     def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
                  int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
                  conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
-                 stem_sections: bool = False, head_sections: bool = False):
+                 stem_sections: bool = False, head_sections: bool = False, conv2d_i8_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -249,7 +257,11 @@ class LceModel:
         the start joins the first section instead of staying with the host (LCE_TFLITE_SECTIONS_EXT_STEM).  Both are bits of the
         56-byte options, which no combination of the other flags without ``depthwise_sections`` uses.  ``head_sections``: the float
         classifier head (MEAN over height and width, FULLY_CONNECTED, SOFTMAX) joins them; only then does the constructor go
-        through ``lce_tflite_model_open_passes``, which names the passes -- every other combination keeps its route."""
+        through ``lce_tflite_model_open_passes``, which names the passes -- every other combination keeps its route.
+        ``conv2d_i8_sections``: the quantized CONV_2D of an int8-converted network (stem, shortcut, transition) joins them
+        (``lce_hip_conv2d_i8``); it routes through ``lce_tflite_model_open_passes`` too (the name ``conv2d_i8``), and every
+        combination without it keeps its route.  Its kernel takes 0.41-0.80 of the float entry's time at the same shapes (module docstring;
+        profiles/conv2d_i8)."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -264,9 +276,11 @@ class LceModel:
                 words[word] |= bit
                 size = max(size, form)
         self.head_sections = bool(head_sections)
+        self.conv2d_i8_sections = bool(conv2d_i8_sections)
         err = C.create_string_buffer(256)
-        if self.head_sections:
-            names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]] + ["head"]
+        if self.head_sections or self.conv2d_i8_sections:
+            names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]]
+            names += ["head"] * self.head_sections + ["conv2d_i8"] * self.conv2d_i8_sections
             self._h = tflite_lib().lce_tflite_model_open_passes(self._data, len(self._data), ",".join(names).encode(), err, 256)
         elif size:
             opts = _OPEN_OPTIONS[size](size, *words[:1 if size == 8 else 2])
@@ -280,7 +294,11 @@ class LceModel:
         for i in range(l.lce_tflite_model_num_tensors(self._h)):
             info = _TensorInfo()
             _amd.check(l.lce_tflite_model_tensor(self._h, i, C.byref(info)))
-            self.tensors.append(Tensor(info))
+            qdim = C.c_int32()
+            n = l.lce_tflite_model_tensor_scales(self._h, i, None, 0, C.byref(qdim))
+            scales = (C.c_float * max(n, 1))()
+            l.lce_tflite_model_tensor_scales(self._h, i, scales, n, None)
+            self.tensors.append(Tensor(info, [float(scales[k]) for k in range(n)], qdim.value))
         self.operators: List[Operator] = []
         for i in range(l.lce_tflite_model_num_operators(self._h)):
             info = _OperatorInfo()
@@ -372,6 +390,10 @@ class LceModel:
         """(lce_hip_conv2d_f32 calls, LceQuantize launches they absorbed) of the last run."""
         return self._pass_stats("conv2d")
 
+    def conv_i8_stats(self):
+        """(lce_hip_conv2d_i8 launches, LceQuantize launches they absorbed) of the last run."""
+        return self._pass_stats("conv_i8")
+
     def head_stats(self):
         """(MEAN launches, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches) of the last run."""
         v = [C.c_int32() for _ in range(3)]
@@ -409,20 +431,21 @@ class Interpreter:
                  use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
                  concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
                  depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False,
-                 head_sections: bool = False):
+                 head_sections: bool = False, conv2d_i8_sections: bool = False):
         """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
-        ``conv2d_sections``, ``stem_sections``, ``head_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+        ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
                                     int8_add_sections=int8_add_sections, concat_sections=concat_sections,
                                     pool_sections=pool_sections, conv1x1_sections=conv1x1_sections,
                                     depthwise_sections=depthwise_sections, conv2d_sections=conv2d_sections,
-                                    stem_sections=stem_sections, head_sections=head_sections))
+                                    stem_sections=stem_sections, head_sections=head_sections,
+                                    conv2d_i8_sections=conv2d_i8_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.head_sections or any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
+        if self.model.head_sections or self.model.conv2d_i8_sections or any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

@@ -395,6 +395,61 @@ lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* desc, const float* 
 lce_hip_status lce_hip_conv2d_f32_check(const lce_hip_conv2d_desc* desc, int32_t* out_height, int32_t* out_width);
 
 /* ------------------------------------------------------------------------------------
+ * The int8 CONV_2D of any filter extent (TFLite builtin CONV_2D, quantized) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* An int8-converted network (inference_input_type int8) keeps three kinds of builtin CONV_2D, all quantized: the stem
+ * (3x3 / 2 or 7x7 / 2 on three channels), the 1x1 behind the 2x2 pool of a downsampling shortcut and the 1x1 of a dense
+ * network's transition.  lce_hip_conv2d_i8 is TFLite's reference_integer_ops::ConvPerChannel in its default (double-rounding)
+ * build, byte for byte.  Input: NHWC int8 [batch, in_height, in_width, channels_in] with quantization (input_scale,
+ * input_zero_point) = (si, zi).  Filter: int8 in the file's own layout [channels_out][filter_height][filter_width][channels_in]
+ * with zero point 0 and scales sw[o], one per output channel or a single one that stands for all.  Bias: optional int32
+ * [channels_out].  Output: NHWC int8 with (output_scale, output_zero_point) = (so, zo).  groups is 1 and the dilation is 1;
+ * extents and padding are lce_hip_conv2d_f32's.  Per output element:
+ *   acc = sum over in-bounds taps (fy, fx) and c of (x[iy][ix][c] - zi) * w[o][fy][fx][c]   exact, int32; taps in the padding are skipped
+ *   acc += bias[o]                                                                          when there is a bias
+ *   (m[o], e[o]) = QuantizeMultiplier((double)si * (double)sw[o] / (double)so)
+ *   acc = RoundingDivideByPOT(SaturatingRoundingDoublingHighMul(acc * 2^max(e,0), m), max(-e,0))   as lce_hip_add_int8 states the two
+ *   v   = min(max(acc + zo, act_min), act_max)      CalculateActivationRangeQuantized at (so, zo): what lce_hip_add_int8_prepare reports
+ *   bit = v < zo                                    as lce_hip_pool2d's int8 bits: LSB first, ceil(channels_out/32) words per pixel, padding bits 0
+ * Integer arithmetic has one answer: the sum runs on the int8 matrix instruction in whatever order, a tap in the padding is
+ * read as x = zi and the constant c[o] = bias[o] - zi * sum_k w[o][k] of the table makes that the reference's skip.
+ *
+ * lce_hip_conv2d_i8_check: the descriptor checks alone and the output extents (nullable).  Host only.
+ * lce_hip_conv2d_i8_prepare: host only.  From the constants of the file -- the filter, the bias (nullable), `n_scales` (1 or
+ *   channels_out) filter scales -- the table int32 [3][channels_out] = c[o], m[o], e[o], which the caller uploads once, and the
+ *   activation range.  LCE_HIP_ERR_UNSUPPORTED, with a message that names the channel: with K = filter_height x filter_width x
+ *   channels_in and B = max |bias|, 255 x 128 x K + B > 2^31 - 1 (the reference's own accumulator could overflow); for a channel
+ *   with e > 0, that bound times 2^e > 2^31 - 1; a c[o] that does not fit int32 (the first bound implies it fits).
+ *   LCE_HIP_ERR_INVALID: a NULL pointer (the bias excepted), a scale that is not finite and positive, a zero point outside
+ *   [-128, 127], n_scales neither 1 nor channels_out, and what lce_hip_conv2d_f32 refuses of a descriptor.
+ * lce_hip_conv2d_i8: ONE launch.  `table_dev`: prepare's table on the device.  `out_dev` (nullable) gets the int8 result,
+ *   `out_bits_dev` (nullable) its LceQuantize at zo.  Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc, input,
+ *   filter or table, both outputs NULL, what the check refuses, an output that overlaps the input, the filter, the table or the
+ *   other output, an out_bits_dev or table_dev that is not 4-byte aligned; LCE_HIP_ERR_UNSUPPORTED: lce_hip_conv2d_f32's limits,
+ *   and K > 65793 (255 x 128 x K > 2^31 - 1: no table exists for it).
+ *   The int8 pointers need no alignment (16-byte aligned input and filter with channels_in % 16 == 0 take a faster load path);
+ *   the byte counts are unbounded (64-bit offsets throughout).  Asynchronous on `stream`, capturable in a HIP graph, allocates
+ *   nothing and copies nothing between host and device. */
+typedef struct lce_hip_conv2d_i8_desc {
+  int32_t batch, in_height, in_width, channels_in, channels_out;
+  int32_t filter_height, filter_width, stride_height, stride_width;
+  int32_t padding;      /* lce_hip_padding: SAME or VALID */
+  int32_t activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+  float input_scale;
+  int32_t input_zero_point;
+  float output_scale;
+  int32_t output_zero_point;
+} lce_hip_conv2d_i8_desc;
+lce_hip_status lce_hip_conv2d_i8_check(const lce_hip_conv2d_i8_desc* desc, int32_t* out_height, int32_t* out_width);
+lce_hip_status lce_hip_conv2d_i8_prepare(const lce_hip_conv2d_i8_desc* desc, const int8_t* filter_host /* [Cout][fh][fw][Cin] */,
+                                         const int32_t* bias_host /* nullable */, const float* filter_scales, int32_t n_scales /* 1 or Cout */,
+                                         int32_t* table /* [3][Cout] */, int32_t* act_min, int32_t* act_max);
+lce_hip_status lce_hip_conv2d_i8(const lce_hip_conv2d_i8_desc* desc, const int8_t* in_dev, const int8_t* filter_dev /* [Cout][fh][fw][Cin] */,
+                                 const int32_t* table_dev /* [3][Cout] */, int8_t* out_dev /* nullable */,
+                                 int32_t* out_bits_dev /* nullable */, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The float classifier head (TFLite builtin MEAN, FULLY_CONNECTED, SOFTMAX)
  * ---------------------------------------------------------------------------------- */
 

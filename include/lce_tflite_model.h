@@ -163,7 +163,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
                                              size_t err_len);
 
 /* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
- *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head
+ *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8
  * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
  * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
  * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
@@ -189,7 +189,25 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   Everything else stays with the host, as before: int8 or hybrid FULLY_CONNECTED, a non-constant weight, shuffled weights, a
  *   MEAN over other axes, TANH, a missing options table, RESHAPE / Flatten (so the three-layer head of BinaryAlexNet), LOGISTIC.
  *   No LceQuantize folds into a head operator.  With every name a converted network is ONE section from the image to the
- *   probabilities and no builtin operator is left for the host. */
+ *   probabilities and no builtin operator is left for the host.
+ *   conv2d_i8: the quantized builtin CONV_2D (3) of an int8-converted network -- its stem, the 1x1 behind the pool of a
+ *   downsampling shortcut, the 1x1 of a transition -- joins the sections; no other entry can ask for it, and no float predicate
+ *   takes an int8 tensor, so it moves nothing in a float-converted file.  It qualifies when: the Conv2DOptions table is present;
+ *   it has 2 or 3 inputs (a third input of -1: no bias) and one output; input and output are int8, each quantized with exactly
+ *   one scale and a zero point in [-128, 127]; the output is 4-D with positive extents and the data input non-constant and 4-D;
+ *   the filter is a constant int8 [Cout, fh, fw, Cin] with data in the file whose byte count matches (compared by division),
+ *   Cin the input's channels, no zero point other than 0, and 1 or Cout scales (with more than one, quantized_dimension 0); the
+ *   bias is absent or a constant int32 [Cout]; the dilations are 1, the strides positive, the padding SAME or VALID, the fused
+ *   activation NONE / RELU / RELU_N1_TO_1 / RELU6; the declared output height and width are what the padding rule gives; and
+ *   lce_hip_conv2d_i8_prepare accepts the file's constants (include/lce_hip.h: where the reference's own int32 accumulator
+ *   could overflow it does not).  A grouped or dilated convolution, hybrid weights, a filter zero point, scales along another
+ *   dimension and a float bias stay with the host.  It joins the epoch in which it becomes ready, and `stem` applies to it as to
+ *   any enabled opt-in.  lce_tflite_model_run_section runs it as ONE lce_hip_conv2d_i8 launch -- TFLite's integer arithmetic
+ *   byte for byte -- whose table is prepared and uploaded once per model beside the filter; a following LceQuantize folds into
+ *   the launch's bits.  With int8_add, pool and stem an int8 Bi-RealNet-style block with its downsampling shortcut, and an int8
+ *   stem with the binary layer behind it, are one section each.  Still the host's in an int8 network: int8 DEPTHWISE_CONV_2D,
+ *   the int8 head, QUANTIZE / DEQUANTIZE.  Kernel time at batch 256 against the float entry at the same shape: 0.80 of it on the
+ *   3x3 / 2 stem, 0.41 on the 7x7 / 2 stem, 0.57 on the 1x1 shortcut (profiles/conv2d_i8). */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -222,6 +240,10 @@ typedef struct lce_tflite_operator_info {
   const uint8_t* custom_options;   /* flexbuffer map, as written by mlir/ir/lce_ops.cc:36-51 */
   size_t custom_options_size;
 } lce_tflite_operator_info;
+/* The whole scale vector of tensor `index` (lce_tflite_tensor_info::scale is its first element): up to `cap` scales are copied
+ * to `scales` (nullable) and QuantizationParameters.quantized_dimension is reported (nullable).  Returns the number of scales
+ * in the file (0: not quantized), -1 for a bad argument. */
+int32_t lce_tflite_model_tensor_scales(const lce_tflite_model* model, int32_t index, float* scales, int32_t cap, int32_t* quantized_dimension);
 lce_hip_status lce_tflite_model_operator(const lce_tflite_model* model, int32_t index, lce_tflite_operator_info* info);
 /* fused_activation_function of a builtin ADD / MUL (AddOptions / MulOptions: lce_hip_activation values, and 4 TANH /
  * 5 SIGN_BIT as the file says); 0 (NONE) when the options table is absent and for every other operator. */
@@ -329,6 +351,9 @@ void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches
 /* The LAST run's lce_hip_conv2d_f32 calls (LCE_TFLITE_SECTIONS_EXT_CONV2D): launches (one per absorbed CONV_2D) and the
  * LceQuantize launches folded into them.  Nullable outputs. */
 void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's lce_hip_conv2d_i8 launches ("conv2d_i8" of lce_tflite_model_open_passes): launches (one per absorbed int8
+ * CONV_2D) and the LceQuantize launches folded into them.  Nullable outputs. */
+void lce_tflite_model_conv_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 /* The LAST run's launches for the classifier head ("head" of lce_tflite_model_open_passes): lce_hip_pool2d launches that ran a
  * MEAN, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches.  Nullable outputs. */
 void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
