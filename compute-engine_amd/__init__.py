@@ -42,6 +42,9 @@ ABI_SYMBOLS = (
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
     "lce_hip_conv2d_i8", "lce_hip_conv2d_i8_check", "lce_hip_conv2d_i8_prepare",
     "lce_hip_fully_connected_f32", "lce_hip_fully_connected_f32_check", "lce_hip_softmax_f32", "lce_hip_softmax_f32_check",
+    "lce_hip_fully_connected_i8", "lce_hip_fully_connected_i8_check", "lce_hip_fully_connected_i8_prepare",
+    "lce_hip_mean_i8", "lce_hip_mean_i8_check", "lce_hip_mean_i8_prepare", "lce_hip_softmax_i8", "lce_hip_softmax_i8_check",
+    "lce_hip_quantize_f32_i8", "lce_hip_dequantize_i8_f32",
     "lce_hip_bconv2d_plan_create", "lce_hip_bconv2d_plan_destroy", "lce_hip_bconv2d_plan_output_shape",
     "lce_hip_bconv2d_plan_padding", "lce_hip_bconv2d_plan_set_weights", "lce_hip_bconv2d_plan_folded",
     "lce_hip_bconv2d_plan_set_option", "lce_hip_bconv2d_plan_kernel_name", "lce_hip_bconv2d_plan_kernel_name_dual", "lce_hip_bconv2d_plan_int8_epilogue", "lce_hip_bconv2d_run",
@@ -129,6 +132,18 @@ class FcDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("batch", "inputs", "outputs", "activation")]
 
 
+class FcI8Desc(C.Structure):
+    """``lce_hip_fc_i8_desc``."""
+    _fields_ = FcDesc._fields_ + [("input_scale", C.c_float), ("input_zero_point", C.c_int32), ("output_scale", C.c_float),
+                                  ("output_zero_point", C.c_int32)]
+
+
+class MeanI8Desc(C.Structure):
+    """``lce_hip_mean_i8_desc``."""
+    _fields_ = [(n, C.c_int32) for n in ("batch", "height", "width", "channels")] + [
+        ("input_scale", C.c_float), ("input_zero_point", C.c_int32), ("output_scale", C.c_float), ("output_zero_point", C.c_int32)]
+
+
 _lib = None
 
 
@@ -193,6 +208,17 @@ def lib() -> C.CDLL:
         l.lce_hip_fully_connected_f32_check.argtypes = [C.POINTER(FcDesc)]
         l.lce_hip_softmax_f32.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_softmax_f32_check.argtypes = [C.c_size_t, C.c_size_t, C.c_float]
+        l.lce_hip_fully_connected_i8.argtypes = [C.POINTER(FcI8Desc)] + [C.c_void_p] * 5
+        l.lce_hip_fully_connected_i8_check.argtypes = [C.POINTER(FcI8Desc)]
+        l.lce_hip_fully_connected_i8_prepare.argtypes = [C.POINTER(FcI8Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_mean_i8.argtypes = [C.POINTER(MeanI8Desc)] + [C.c_void_p] * 3
+        l.lce_hip_mean_i8_check.argtypes = [C.POINTER(MeanI8Desc)]
+        l.lce_hip_mean_i8_prepare.argtypes = [C.POINTER(MeanI8Desc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_softmax_i8_check.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_int32]
+        l.lce_hip_softmax_i8.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_int32] + [C.c_void_p] * 3
+        l.lce_hip_quantize_f32_i8.argtypes = [C.c_size_t, C.c_float, C.c_int32] + [C.c_void_p] * 3
+        l.lce_hip_dequantize_i8_f32.argtypes = [C.c_size_t, C.c_float, C.c_int32] + [C.c_void_p] * 3
         l.lce_hip_bmaxpool.argtypes = [C.c_void_p] + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p]
         l.lce_hip_bmaxpool_output_shape.argtypes = [C.c_int32] * 7 + [C.POINTER(C.c_int32)] * 2
         _lib = l
@@ -1038,6 +1064,179 @@ def softmax(x, beta: float = 1.0, out=None, stream: int | None = None):
         check(lib().lce_hip_softmax_f32(rows, cols, float(beta), _dev_ptr(xd), _dev_ptr(out_d),
                                         C.c_void_p(_stream_or_current(stream, dev))))
     return _results(host, out_d, None, out)[0]
+
+
+# ---------------------------------------------------------------------------------------
+# the int8 classifier head and the float / int8 boundary (include/lce_hip.h)
+# ---------------------------------------------------------------------------------------
+SOFTMAX_I8_OUT = (1.0 / 256.0, -128)                    # the one output quantization of ``softmax_i8``
+
+
+def _q1(who, name, q):
+    """One (scale, zero_point) of an int8 tensor, checked as ``_conv2d_i8_quantization`` checks its two."""
+    if not isinstance(q, (tuple, list)) or len(q) != 2:
+        raise ValueError("%s: %s must be (scale, zero_point), got %r" % (who, name, q))
+    scale, zp = float(np.float32(q[0])), q[1]
+    if not (np.isfinite(scale) and scale > 0):
+        raise ValueError("%s: %s scale must be finite and positive, got %r" % (who, name, q[0]))
+    if int(zp) != zp or not -128 <= int(zp) <= 127:
+        raise ValueError("%s: %s zero point must be an integer in [-128, 127], got %r" % (who, name, zp))
+    return scale, int(zp)
+
+
+def _fc_i8_weights(who, w, inputs=None):
+    ws = tuple(int(v) for v in w.shape)
+    if _dtype_name(w) != "int8" or len(ws) != 2 or min(ws) < 1 or (inputs is not None and ws[1] != inputs):
+        raise ValueError("%s: w must be int8 [outputs, %s], got %s %r" % (who, "inputs" if inputs is None else inputs, w.dtype, ws))
+    return ws
+
+
+def fully_connected_i8_prepare(w, bias, weight_scales, q_in, q_out, activation=ACT_NONE):
+    """The constants of one quantized FULLY_CONNECTED for ``fully_connected_i8`` (``lce_hip_fully_connected_i8_prepare``, host
+    only).  ``w``: int8 NumPy [outputs, inputs] (zero point 0).  ``bias``: int32 [outputs] or None.  ``weight_scales``: one float
+    or one per output.  Returns ``(table, act_min, act_max)`` as ``conv2d_i8_prepare`` does; raises ``LceHipError``
+    (ERR_UNSUPPORTED) where the reference's own int32 accumulator could overflow."""
+    who = "fully_connected_i8_prepare"
+    n, k = _fc_i8_weights(who, w)
+    (si, zi), (so, zo) = _q1(who, "q_in", q_in), _q1(who, "q_out", q_out)
+    _padding_activation_check(who, None, activation)
+    if bias is not None and (_dtype_name(bias) != "int32" or tuple(bias.shape) != (n,)):
+        raise ValueError("%s: bias must be int32 [%d], got %s %r" % (who, n, bias.dtype, tuple(bias.shape)))
+    scales = np.ascontiguousarray(np.atleast_1d(np.asarray(weight_scales, np.float32)))
+    if scales.ndim != 1 or scales.size not in (1, n):
+        raise ValueError("%s: weight_scales must be 1 or %d scales, got shape %r" % (who, n, scales.shape))
+    wh = np.ascontiguousarray(w)
+    bh = None if bias is None else np.ascontiguousarray(bias)
+    desc = FcI8Desc(1, k, n, int(activation), si, zi, so, zo)
+    table = np.zeros((3, n), np.int32)
+    lo, hi = C.c_int32(), C.c_int32()
+    check(lib().lce_hip_fully_connected_i8_prepare(C.byref(desc), _host_ptr(wh), None if bh is None else _host_ptr(bh),
+                                                   _host_ptr(scales), int(scales.size), _host_ptr(table), C.byref(lo), C.byref(hi)))
+    return table, lo.value, hi.value
+
+
+def _fully_connected_i8_check(x, w, table, q_in, q_out, activation, out):
+    """Argument checks of ``fully_connected_i8`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.
+    Returns (FcI8Desc, output shape)."""
+    who = "fully_connected_i8"
+    xs = tuple(int(v) for v in x.shape)
+    if _dtype_name(x) != "int8" or len(xs) != 2 or min(xs) < 1:
+        raise ValueError("%s: x must be a non-empty int8 [batch, inputs] tensor, got %s %r" % (who, x.dtype, xs))
+    n, _ = _fc_i8_weights(who, w, xs[1])
+    if _dtype_name(table) != "int32" or tuple(table.shape) != (3, n):
+        raise ValueError("%s: table must be int32 [3, %d] (fully_connected_i8_prepare), got %s %r" % (who, n, table.dtype, tuple(table.shape)))
+    (si, zi), (so, zo) = _q1(who, "q_in", q_in), _q1(who, "q_out", q_out)
+    _padding_activation_check(who, None, activation)
+    shape = (xs[0], n)
+    _check_outputs(who, out, None, "int8", shape)
+    return FcI8Desc(xs[0], xs[1], n, int(activation), si, zi, so, zo), shape
+
+
+def fully_connected_i8(x, w, table, q_in, q_out, activation=ACT_NONE, out=None, stream: int | None = None):
+    """TFLite's builtin quantized FULLY_CONNECTED -- the Dense layer of an int8 classifier head -- in one launch on the int8
+    matrix instruction (``lce_hip_fully_connected_i8``).  ``x``: int8 [batch, inputs] on the device (or NumPy: copied to cuda:0
+    and back).  ``w``: int8 [outputs, inputs].  ``table``: int32 [3, outputs] from ``fully_connected_i8_prepare``.  The bytes
+    are ``conv2d_i8``'s on a [batch, 1, 1, inputs] image.  ``out``: None for a new tensor, or an int8 tensor [batch, outputs] to
+    fill.  Returns the output."""
+    desc, shape = _fully_connected_i8_check(x, w, table, q_in, q_out, activation, out)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "fully_connected_i8", "x's")
+    xd, wd, td = on_dev(x), on_dev(w), on_dev(table)
+    out_d = torch.empty(shape, dtype=torch.int8, device=dev) if out is None else on_dev(out)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_fully_connected_i8(C.byref(desc), _dev_ptr(xd), _dev_ptr(wd), _dev_ptr(td), _dev_ptr(out_d),
+                                               C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, None, out)[0]
+
+
+def _mean_i8_desc(who, x, q_in, q_out):
+    _, b, h, w, c = _nhwc_check(who, x, ("int8",))
+    (si, zi), (so, zo) = _q1(who, "q_in", q_in), _q1(who, "q_out", q_out)
+    return MeanI8Desc(b, h, w, c, si, zi, so, zo), (b, c)
+
+
+def mean_i8_prepare(shape, q_in, q_out):
+    """``lce_hip_mean_i8_prepare`` for an NHWC ``shape``: QuantizeMultiplier(si / so) as (multiplier, exponent).  Raises
+    ``LceHipError`` (ERR_UNSUPPORTED) where an intermediate of the entry's arithmetic could leave int32."""
+    who = "mean_i8_prepare"
+    (si, zi), (so, zo) = _q1(who, "q_in", q_in), _q1(who, "q_out", q_out)
+    b, h, w, c = (int(v) for v in shape)
+    desc = MeanI8Desc(b, h, w, c, si, zi, so, zo)
+    m, e = C.c_int32(), C.c_int32()
+    check(lib().lce_hip_mean_i8_prepare(C.byref(desc), C.byref(m), C.byref(e)))
+    return m.value, e.value
+
+
+def mean_i8(x, q_in, q_out, out=None, stream: int | None = None):
+    """TFLite's builtin int8 MEAN over height and width in one launch (``lce_hip_mean_i8``).  ``x``: int8 NHWC on the device (or
+    NumPy: copied to cuda:0 and back).  Returns int8 [batch, channels]: the exact sum of x - zi, the multiplier of si / so, then
+    the division by H * W rounding half away from zero (include/lce_hip.h)."""
+    desc, shape = _mean_i8_desc("mean_i8", x, q_in, q_out)
+    _check_outputs("mean_i8", out, None, "int8", shape)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "mean_i8", "x's")
+    xd = on_dev(x)
+    out_d = torch.empty(shape, dtype=torch.int8, device=dev) if out is None else on_dev(out)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_mean_i8(C.byref(desc), _dev_ptr(xd), _dev_ptr(out_d), C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, None, out)[0]
+
+
+def softmax_i8(x, input_scale, beta: float = 1.0, q_out=SOFTMAX_I8_OUT, out=None, stream: int | None = None):
+    """TFLite's builtin int8 SOFTMAX over the last axis in one launch (``lce_hip_softmax_i8``), to the bytes include/lce_hip.h
+    states.  ``x``: int8 [..., cols] at scale ``input_scale`` (its zero point cancels).  The output is int8 at exactly
+    (1/256, -128); any other ``q_out`` raises ``LceHipError`` (ERR_UNSUPPORTED).  ``out``: None for a new tensor, a tensor of
+    x's shape to fill, or ``x`` itself (in place).  Returns the output."""
+    shape = tuple(int(v) for v in x.shape)
+    if _dtype_name(x) != "int8" or len(shape) < 1 or min(shape) < 1:
+        raise ValueError("softmax_i8: x must be a non-empty int8 tensor, got %s %r" % (x.dtype, shape))
+    if out is not None and out is not x:
+        _check_outputs("softmax_i8", out, None, "int8", shape)
+    rows, cols = int(np.prod(shape[:-1], dtype=np.int64)), shape[-1]
+    check(lib().lce_hip_softmax_i8_check(rows, cols, float(input_scale), float(beta), float(q_out[0]), int(q_out[1])))
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "softmax_i8", "x's")
+    xd = on_dev(x)
+    out_d = torch.empty_like(xd) if out is None else xd if out is x else on_dev(out)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_softmax_i8(rows, cols, float(input_scale), float(beta), float(q_out[0]), int(q_out[1]), _dev_ptr(xd),
+                                       _dev_ptr(out_d), C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, None, out)[0]
+
+
+def _quant_run(who, entry, x, in_dtype, out_dtype, q, out, stream):
+    scale, zp = _q1(who, "q", q)
+    shape = tuple(int(v) for v in x.shape)
+    if _dtype_name(x) != in_dtype:
+        raise ValueError("%s: x must be a %s tensor, got %s" % (who, in_dtype, x.dtype))
+    _check_outputs(who, out, None, out_dtype, shape)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x's")
+    xd = on_dev(x)
+    out_d = torch.empty(shape, dtype=getattr(torch, out_dtype), device=dev) if out is None else on_dev(out)
+    with torch.cuda.device(dev):
+        check(getattr(lib(), entry)(xd.numel(), scale, zp, _dev_ptr(xd), _dev_ptr(out_d), C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, None, out)[0]
+
+
+def quantize_i8(x, q, out=None, stream: int | None = None):
+    """TFLite's builtin QUANTIZE float32 -> int8 at ``q`` = (scale, zero_point) (``lce_hip_quantize_f32_i8``): the IEEE division,
+    roundf, the clamp in float, + zero point; a NaN gives the zero point, infinities saturate."""
+    return _quant_run("quantize_i8", "lce_hip_quantize_f32_i8", x, "float32", "int8", q, out, stream)
+
+
+def dequantize_i8(x, q, out=None, stream: int | None = None):
+    """TFLite's builtin DEQUANTIZE int8 -> float32 at ``q`` = (scale, zero_point) (``lce_hip_dequantize_i8_f32``):
+    (float)(x - zero_point) * scale, one float32 multiply."""
+    return _quant_run("dequantize_i8", "lce_hip_dequantize_i8_f32", x, "int8", "float32", q, out, stream)
 
 
 def bmaxpool(x, filter_height, filter_width, stride_height, stride_width, padding, stream: int | None = None, out=None):

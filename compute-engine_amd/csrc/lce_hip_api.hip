@@ -26,6 +26,7 @@
 #include "lce_kernels_conv2d.h"      // (lce_tu_conv2d.hip)
 #include "lce_kernels_conv2d_i8.h"   // (lce_tu_conv2d_i8.hip)
 #include "lce_kernels_head.h"        // (lce_tu_head.hip)
+#include "lce_kernels_head_i8.h"     // (lce_tu_head_i8.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -51,6 +52,7 @@
 #include "lce_tu_conv2d.hip"
 #include "lce_tu_conv2d_i8.hip"
 #include "lce_tu_head.hip"
+#include "lce_tu_head_i8.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -1271,6 +1273,51 @@ lce_hip_status conv2d_i8_desc_check(const char* who, const lce_hip_conv2d_i8_des
   if (out_width) *out_width = ow;
   return LCE_HIP_OK;
 }
+
+// The table of lce_hip_conv2d_i8_prepare for N output channels of K filter elements each (the FULLY_CONNECTED of the int8 head
+// is the 1x1 case: lce_hip_fully_connected_i8_prepare).  The descriptor has been checked.
+lce_hip_status conv2d_i8_table(const char* who, int64_t N, int64_t K, float si, int32_t zi, float so, const int8_t* filter_host,
+                               const int32_t* bias_host, const float* filter_scales, int32_t n_scales, int32_t* table) {
+  if (n_scales != 1 && (int64_t)n_scales != N)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the filter has %d scales, neither 1 nor one per output channel (%d)", who, (int)n_scales, (int)N);
+  for (int32_t o = 0; o < n_scales; ++o)
+    if (!std::isfinite(filter_scales[o]) || !(filter_scales[o] > 0.0f))
+      return fail(LCE_HIP_ERR_INVALID, "%s: the filter scale of channel %d must be finite and positive, got %g", who, (int)o,
+                  (double)filter_scales[o]);
+  // The reference's accumulator: |x - zi| <= 255, |w| <= 128, K products and the bias.
+  const int64_t kMax = 2147483647ll;
+  int64_t B = 0, b_channel = 0;
+  if (bias_host)
+    for (int64_t o = 0; o < N; ++o) {
+      const int64_t v = bias_host[o] < 0 ? -(int64_t)bias_host[o] : (int64_t)bias_host[o];
+      if (v > B) { B = v; b_channel = o; }
+    }
+  const int64_t bound = 255ll * 128ll * K + B;                                     // < 2^47
+  if (bound > kMax)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: 255 x 128 x K + |bias| = 255 x 128 x %lld + %lld exceeds 2^31 - 1: the reference's "
+                "int32 accumulator could overflow", who, (long long)b_channel, (long long)K, (long long)B);
+  for (int64_t o = 0; o < N; ++o) {
+    const double real = (double)si * (double)filter_scales[n_scales == 1 ? 0 : o] / (double)so;
+    int32_t m = 0, e = 0;
+    quantize_multiplier(real, &m, &e);
+    if (e > 0 && (e >= 31 || (bound << e) > kMax))
+      return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: the accumulator bound %lld times 2^%d (the left shift of its multiplier %g) "
+                  "exceeds 2^31 - 1", who, (long long)o, (long long)bound, (int)e, real);
+    int64_t sum = 0;
+    const int8_t* w = filter_host + (uint64_t)o * (uint64_t)K;
+    for (int64_t k = 0; k < K; ++k) sum += w[k];
+    // |zi * sum| <= 128 x 128 x K and |bias[o]| <= B, so |c| <= 128 x 128 x K + B <= 255 x 128 x K + B = bound <= 2^31 - 1:
+    // the first bound already implies that c fits.  Checked all the same.
+    const int64_t c = (bias_host ? (int64_t)bias_host[o] : 0ll) - (int64_t)zi * sum;
+    if (c > kMax || c < -kMax - 1)
+      return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: the constant bias - zero_point x sum(w) = %lld does not fit int32", who,
+                  (long long)o, (long long)c);
+    table[o] = (int32_t)c;
+    table[N + o] = m;
+    table[2 * N + o] = e;
+  }
+  return LCE_HIP_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -1298,45 +1345,9 @@ lce_hip_status lce_hip_conv2d_i8_prepare(const lce_hip_conv2d_i8_desc* d, const 
   if (!table || !act_min || !act_max) return fail(LCE_HIP_ERR_INVALID, "%s: null result", who);
   if (lce_hip_status s = conv2d_i8_desc_check(who, d, nullptr, nullptr)) return s;
   const int64_t N = d->channels_out, K = (int64_t)d->filter_height * d->filter_width * d->channels_in;       // K < 2^31
-  if (n_scales != 1 && (int64_t)n_scales != N)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the filter has %d scales, neither 1 nor one per output channel (%d)", who, (int)n_scales, (int)N);
-  for (int32_t o = 0; o < n_scales; ++o)
-    if (!std::isfinite(filter_scales[o]) || !(filter_scales[o] > 0.0f))
-      return fail(LCE_HIP_ERR_INVALID, "%s: the filter scale of channel %d must be finite and positive, got %g", who, (int)o,
-                  (double)filter_scales[o]);
-  // The reference's accumulator: |x - zi| <= 255, |w| <= 128, K products and the bias.
-  const int64_t kMax = 2147483647ll;
-  int64_t B = 0, b_channel = 0;
-  if (bias_host)
-    for (int64_t o = 0; o < N; ++o) {
-      const int64_t v = bias_host[o] < 0 ? -(int64_t)bias_host[o] : (int64_t)bias_host[o];
-      if (v > B) { B = v; b_channel = o; }
-    }
-  const int64_t bound = 255ll * 128ll * K + B;                                     // < 2^47
-  if (bound > kMax)
-    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: 255 x 128 x K + |bias| = 255 x 128 x %lld + %lld exceeds 2^31 - 1: the reference's "
-                "int32 accumulator could overflow", who, (long long)b_channel, (long long)K, (long long)B);
-  const int32_t zi = d->input_zero_point;
-  for (int64_t o = 0; o < N; ++o) {
-    const double real = (double)d->input_scale * (double)filter_scales[n_scales == 1 ? 0 : o] / (double)d->output_scale;
-    int32_t m = 0, e = 0;
-    quantize_multiplier(real, &m, &e);
-    if (e > 0 && (e >= 31 || (bound << e) > kMax))
-      return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: the accumulator bound %lld times 2^%d (the left shift of its multiplier %g) "
-                  "exceeds 2^31 - 1", who, (long long)o, (long long)bound, (int)e, real);
-    int64_t sum = 0;
-    const int8_t* w = filter_host + (uint64_t)o * (uint64_t)K;
-    for (int64_t k = 0; k < K; ++k) sum += w[k];
-    // |zi * sum| <= 128 x 128 x K and |bias[o]| <= B, so |c| <= 128 x 128 x K + B <= 255 x 128 x K + B = bound <= 2^31 - 1:
-    // the first bound already implies that c fits.  Checked all the same.
-    const int64_t c = (bias_host ? (int64_t)bias_host[o] : 0ll) - (int64_t)zi * sum;
-    if (c > kMax || c < -kMax - 1)
-      return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: the constant bias - zero_point x sum(w) = %lld does not fit int32", who,
-                  (long long)o, (long long)c);
-    table[o] = (int32_t)c;
-    table[N + o] = m;
-    table[2 * N + o] = e;
-  }
+  if (lce_hip_status s = conv2d_i8_table(who, N, K, d->input_scale, d->input_zero_point, d->output_scale, filter_host, bias_host,
+                                         filter_scales, n_scales, table))
+    return s;
   quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, act_min, act_max);
   return LCE_HIP_OK;
 }
@@ -1368,6 +1379,221 @@ lce_hip_status lce_hip_conv2d_i8(const lce_hip_conv2d_i8_desc* d, const int8_t* 
   quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, &a.act_min, &a.act_max);
   const bool vec = Cin % 16 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
   const int e = lce::launch_conv2d_i8(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// the int8 classifier head and the float/int8 boundary (lce_kernels_head_i8.h)
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+static_assert(lce::kFcI8MaxK == lce::kConvI8MaxK, "lce_hip_fully_connected_i8 refuses the K that lce_hip_conv2d_i8 refuses");
+
+// One (scale, zero point) of an int8 tensor: the scale finite and positive, the zero point an int8 value.
+lce_hip_status head_i8_quantization_check(const char* who, const char* name, float scale, int32_t zero_point) {
+  if (!std::isfinite(scale) || !(scale > 0.0f))
+    return fail(LCE_HIP_ERR_INVALID, "%s: %s_scale must be finite and positive, got %g", who, name, (double)scale);
+  if (zero_point < -128 || zero_point > 127)
+    return fail(LCE_HIP_ERR_INVALID, "%s: %s_zero_point must be in [-128, 127], got %d", who, name, (int)zero_point);
+  return LCE_HIP_OK;
+}
+
+// lce_hip_mean_i8's multiplier and the bound of its header comment.
+lce_hip_status mean_i8_multiplier(const char* who, const lce_hip_mean_i8_desc* d, int32_t* m, int32_t* e) {
+  if (lce_hip_status s = lce_hip_mean_i8_check(d)) return s;
+  quantize_multiplier((double)d->input_scale / (double)d->output_scale, m, e);
+  const int64_t n = (int64_t)d->height * d->width, kMax = 2147483647ll;             // n < 2^62
+  const int32_t left = *e > 0 ? *e : 0;
+  if (n > kMax / 255 || left >= 31 || ((255ll * n) << left) + n / 2 > kMax)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: 255 x n x 2^max(e,0) + n/2 with n = %lld pixels and e = %d (the multiplier %g) exceeds "
+                "2^31 - 1: an intermediate could leave int32", who, (long long)n, (int)*e,
+                (double)d->input_scale / (double)d->output_scale);
+  return LCE_HIP_OK;
+}
+
+// The quantization and pointer checks QUANTIZE and DEQUANTIZE share; `f32` / `i8`: the float and the int8 side.
+lce_hip_status quant_check(const char* who, size_t n, float scale, int32_t zero_point, const void* in, const void* out, const void* f32,
+                           uint64_t in_size, uint64_t out_size) {
+  if (!in) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!out) return fail(LCE_HIP_ERR_INVALID, "%s: null output", who);
+  if (lce_hip_status s = head_i8_quantization_check(who, "the", scale, zero_point)) return s;
+  if ((uint64_t)n > (1ull << 60)) return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: more than 2^60 elements are not supported", who);
+  if ((uintptr_t)f32 % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: the float pointer must be 4-byte aligned", who);
+  const Span i(in, (uint64_t)n * in_size), o(out, (uint64_t)n * out_size);
+  if (meet(i.lo, i.hi, o.lo, o.hi)) return fail(LCE_HIP_ERR_INVALID, "%s: the output overlaps the input", who);
+  return LCE_HIP_OK;
+}
+}  // namespace
+extern "C" {
+
+lce_hip_status lce_hip_fully_connected_i8_check(const lce_hip_fc_i8_desc* d) {
+  const char* who = "lce_hip_fully_connected_i8";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->batch <= 0 || d->inputs <= 0 || d->outputs <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d] -> %d outputs", who, (int)d->batch, (int)d->inputs,
+                (int)d->outputs);
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  if (lce_hip_status s = head_i8_quantization_check(who, "input", d->input_scale, d->input_zero_point)) return s;
+  if (lce_hip_status s = head_i8_quantization_check(who, "output", d->output_scale, d->output_zero_point)) return s;
+  if ((uint32_t)d->inputs > lce::kFcI8MaxK)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: %d inputs per output could overflow the int32 accumulator (255 x 128 x K must not exceed "
+                "2^31 - 1: K <= %u)", who, (int)d->inputs, (unsigned)lce::kFcI8MaxK);
+  // (the kernel numbers its 16 x 16 tiles in 32 bits)
+  const uint64_t tiles = (((uint64_t)d->batch + lce::kFcI8Tile - 1) / lce::kFcI8Tile) * (((uint64_t)d->outputs + lce::kFcI8Tile - 1) / lce::kFcI8Tile);
+  if (tiles >= (1ull << 31)) return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: an output of more than 2^31 tiles of 16 x 16 is not supported", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_fully_connected_i8_prepare(const lce_hip_fc_i8_desc* d, const int8_t* weights_host, const int32_t* bias_host,
+                                                  const float* weight_scales, int32_t n_scales, int32_t* table, int32_t* act_min,
+                                                  int32_t* act_max) {
+  const char* who = "lce_hip_fully_connected_i8_prepare";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!weights_host) return fail(LCE_HIP_ERR_INVALID, "%s: null weights", who);
+  if (!weight_scales) return fail(LCE_HIP_ERR_INVALID, "%s: null weight scales", who);
+  if (!table || !act_min || !act_max) return fail(LCE_HIP_ERR_INVALID, "%s: null result", who);
+  // (the descriptor checks but the K limit, which the table states with the bias and a channel -- as the conv entry's prepare)
+  lce_hip_fc_i8_desc small = *d;
+  if (small.inputs > 1) small.inputs = 1;
+  if (lce_hip_status s = lce_hip_fully_connected_i8_check(&small)) return s;
+  if (lce_hip_status s = conv2d_i8_table(who, d->outputs, d->inputs, d->input_scale, d->input_zero_point, d->output_scale, weights_host,
+                                         bias_host, weight_scales, n_scales, table))
+    return s;
+  quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, act_min, act_max);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_fully_connected_i8(const lce_hip_fc_i8_desc* d, const int8_t* in_dev, const int8_t* weights_dev,
+                                          const int32_t* table_dev, int8_t* out_dev, void* stream) {
+  const char* who = "lce_hip_fully_connected_i8";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!weights_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null weights", who);
+  if (!table_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null table", who);
+  if (!out_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null output", who);
+  if (lce_hip_status s = lce_hip_fully_connected_i8_check(d)) return s;
+  const uint64_t M = (uint64_t)d->batch, K = (uint64_t)d->inputs, N = (uint64_t)d->outputs;
+  const Span in(in_dev, M * K), weights(weights_dev, N * K), table(table_dev, 3 * N * 4), out(out_dev, M * N), none(nullptr, 0);
+  if (meet(out.lo, out.hi, table.lo, table.hi)) return fail(LCE_HIP_ERR_INVALID, "%s: the output overlaps the table", who);
+  if (lce_hip_status s = check_operand_ranges(who, in, weights, none, out, none, /*float_operands=*/false)) return s;
+  if (table.lo % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: table_dev must be 4-byte aligned", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::FcI8Args a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.filter = weights_dev; a.table = table_dev; a.out = out_dev;
+  a.M = (uint32_t)M; a.K = (uint32_t)K; a.N = (uint32_t)N;
+  a.ntiles = (uint32_t)((N + lce::kFcI8Tile - 1) / lce::kFcI8Tile);
+  a.tiles = (uint32_t)((M + lce::kFcI8Tile - 1) / lce::kFcI8Tile) * a.ntiles;
+  a.zo = d->output_zero_point;
+  quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, &a.act_min, &a.act_max);
+  const bool vec = K % 16 == 0 && in.lo % 16 == 0 && weights.lo % 16 == 0;
+  const int e = lce::launch_fully_connected_i8(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_mean_i8_check(const lce_hip_mean_i8_desc* d) {
+  const char* who = "lce_hip_mean_i8";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->batch <= 0 || d->height <= 0 || d->width <= 0 || d->channels <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d]", who, (int)d->batch, (int)d->height, (int)d->width,
+                (int)d->channels);
+  if (lce_hip_status s = head_i8_quantization_check(who, "input", d->input_scale, d->input_zero_point)) return s;
+  if (lce_hip_status s = head_i8_quantization_check(who, "output", d->output_scale, d->output_zero_point)) return s;
+  // (four factors below 2^31: compared by division)
+  const uint64_t image = (uint64_t)d->height * (uint64_t)d->width;                  // < 2^62
+  if (image > (1ull << 60) / (uint64_t)d->channels || image * (uint64_t)d->channels > (1ull << 60) / (uint64_t)d->batch)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: more than 2^60 elements are not supported", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_mean_i8_prepare(const lce_hip_mean_i8_desc* d, int32_t* multiplier, int32_t* exponent) {
+  const char* who = "lce_hip_mean_i8_prepare";
+  if (!multiplier || !exponent) return fail(LCE_HIP_ERR_INVALID, "%s: null result", who);
+  return mean_i8_multiplier(who, d, multiplier, exponent);
+}
+
+lce_hip_status lce_hip_mean_i8(const lce_hip_mean_i8_desc* d, const int8_t* in_dev, int8_t* out_dev, void* stream) {
+  const char* who = "lce_hip_mean_i8";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!out_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null output", who);
+  int32_t m = 0, e = 0;
+  if (lce_hip_status s = mean_i8_multiplier(who, d, &m, &e)) return s;
+  const uint64_t n = (uint64_t)d->height * (uint64_t)d->width, C = (uint64_t)d->channels, B = (uint64_t)d->batch;
+  const Span in(in_dev, B * n * C), out(out_dev, B * C);
+  if (meet(in.lo, in.hi, out.lo, out.hi)) return fail(LCE_HIP_ERR_INVALID, "%s: the output overlaps the input", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::MeanI8Args a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.out = out_dev; a.batch = B; a.n = (uint32_t)n; a.C = (uint32_t)C;
+  a.segs = (uint32_t)((C + lce::kMeanI8Channels - 1) / lce::kMeanI8Channels);
+  a.zi = d->input_zero_point; a.zo = d->output_zero_point;
+  a.mul = m; a.left = e > 0 ? e : 0; a.right = e > 0 ? 0 : -e;
+  const int err = lce::launch_mean_i8(a, stream);
+  if (err != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)err));
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_softmax_i8_check(size_t rows, size_t cols, float input_scale, float beta, float output_scale,
+                                        int32_t output_zero_point) {
+  const char* who = "lce_hip_softmax_i8";
+  if (rows == 0 || cols == 0) return fail(LCE_HIP_ERR_INVALID, "%s: rows and cols must be positive, got %zu x %zu", who, rows, cols);
+  if (!std::isfinite(input_scale) || !(input_scale > 0.0f))
+    return fail(LCE_HIP_ERR_INVALID, "%s: input_scale must be finite and positive, got %g", who, (double)input_scale);
+  if (!std::isfinite(beta) || !(beta > 0.0f)) return fail(LCE_HIP_ERR_INVALID, "%s: beta must be finite and positive, got %g", who, (double)beta);
+  if (lce_hip_status s = head_i8_quantization_check(who, "output", output_scale, output_zero_point)) return s;
+  if (output_scale != 1.0f / 256.0f || output_zero_point != -128)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the output quantization must be exactly (1/256, -128), got (%.9g, %d)", who,
+                (double)output_scale, (int)output_zero_point);
+  if ((uint64_t)cols >= (1ull << 31) || (uint64_t)rows > (1ull << 60) / (uint64_t)cols)
+    return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: rows of 2^31 elements or more, or more than 2^60 elements, are not supported", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_softmax_i8(size_t rows, size_t cols, float input_scale, float beta, float output_scale, int32_t output_zero_point,
+                                  const int8_t* in_dev, int8_t* out_dev, void* stream) {
+  const char* who = "lce_hip_softmax_i8";
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!out_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null output", who);
+  if (lce_hip_status s = lce_hip_softmax_i8_check(rows, cols, input_scale, beta, output_scale, output_zero_point)) return s;
+  const Span in(in_dev, (uint64_t)rows * cols), out(out_dev, (uint64_t)rows * cols);
+  // in place is the one overlap that is safe: a lane writes only the elements it alone reads
+  if (in.lo != out.lo && meet(in.lo, in.hi, out.lo, out.hi)) return fail(LCE_HIP_ERR_INVALID, "%s: the output partly overlaps the input", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::SoftmaxI8Args a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.out = out_dev; a.rows = rows; a.cols = (uint32_t)cols;
+  a.sb = input_scale * beta;                     // one float32 multiply (this file is built with -ffp-contract=off)
+  const int e = lce::launch_softmax_i8(a, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_quantize_f32_i8(size_t n, float scale, int32_t zero_point, const float* in_dev, int8_t* out_dev, void* stream) {
+  const char* who = "lce_hip_quantize_f32_i8";
+  if (lce_hip_status s = quant_check(who, n, scale, zero_point, in_dev, out_dev, in_dev, 4, 1)) return s;
+  if (n == 0) return LCE_HIP_OK;
+  if (lce_hip_status s = require_device()) return s;
+  lce::QuantArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.out = out_dev; a.n = n; a.scale = scale; a.zp = zero_point;
+  const int e = lce::launch_quantize_f32_i8(a, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_dequantize_i8_f32(size_t n, float scale, int32_t zero_point, const int8_t* in_dev, float* out_dev, void* stream) {
+  const char* who = "lce_hip_dequantize_i8_f32";
+  if (lce_hip_status s = quant_check(who, n, scale, zero_point, in_dev, out_dev, out_dev, 1, 4)) return s;
+  if (n == 0) return LCE_HIP_OK;
+  if (lce_hip_status s = require_device()) return s;
+  lce::QuantArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = in_dev; a.out = out_dev; a.n = n; a.scale = scale; a.zp = zero_point;
+  const int e = lce::launch_dequantize_i8_f32(a, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }

@@ -211,6 +211,14 @@ LCE_DEVICE float head_exp(float a) {
   return __builtin_bit_cast(float, bits) * (low ? 5.42101086e-20f : 1.0f);               // 2^-64
 }
 
+// The second half of the stated sum: s_l = s_l + s_{l ^ d} for d = 32, 16, 8, 4, 2, 1 over the wave's 64 partial sums (every lane ends
+// with the same number).  lce_kernels_head_i8.h sums its rows through this function too.
+LCE_DEVICE float head_wave_sum(float s) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s = s + __builtin_bit_cast(float, shfl_xor(__builtin_bit_cast(uint32_t, s), d));
+  return s;
+}
+
 // WAVES: the waves of a block, one row each (a template like every kernel here: one definition however many units include it)
 template <int WAVES>
 LCE_KERNEL void __launch_bounds__(64 * WAVES)
@@ -232,8 +240,7 @@ softmax_f32(const SoftmaxArgs A) {
     }
     float s = 0.0f;
     for (uint32_t i = lane; i < A.cols; i += 64u) s = s + head_exp((x[i] - m) * A.beta);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s = s + __builtin_bit_cast(float, shfl_xor(__builtin_bit_cast(uint32_t, s), d));
+    s = head_wave_sum(s);
     for (uint32_t i = lane; i < A.cols; i += 64u) y[i] = head_exp((x[i] - m) * A.beta) / s;
   }
 }

@@ -22,14 +22,15 @@ struct lce_tflite_section {
 };
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
-       kAbsorbedConvI8, kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedCount };
+       kAbsorbedConvI8, kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
+       kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
-enum { kInternalHead = 1u, kInternalConvI8 = 2u };
+enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
-  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8")
+  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize")
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
@@ -40,7 +41,7 @@ struct lce_tflite_model {
   struct DevBuf { void* ptr = nullptr; size_t bytes = 0; };
   std::map<int32_t, DevBuf> scratch;                                    // intermediate tensors of a section, grow-only
   std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
-  std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D operator: lce_hip_conv2d_i8_prepare's table, uploaded once
+  std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D / FULLY_CONNECTED operator: its prepare's table, uploaded once
   std::map<int32_t, std::vector<int32_t>> host_tables;                  // ... as Partition() prepared it; dropped once it is on the device
   // What one run launched.  A recorded graph keeps the record of its recording, so a replay reports the same numbers.
   struct RunStats {
@@ -487,16 +488,16 @@ lce_hip_pool2d_desc MeanDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o
   return d;
 }
 
-// "A builtin MEAN that a section may run": GlobalAveragePooling.  Two inputs and one output; the data input a non-constant
-// float32 4-D tensor with positive extents; the axis a constant int32 tensor (a scalar or a vector) with data in the file whose
-// entries, negative ones + 4, are exactly {1, 2}; the output float32 [b, C] (keep_dims false) or [b, 1, 1, C] (keep_dims true)
-// with the input's b and C; and lce_hip_pool2d_check accepts the AVERAGE / VALID / stride 1 pool whose filter is the image.
-bool MeanCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+// The operand rules of "a builtin MEAN that a section may run" for tensors of `type`: two inputs and one output; the data input
+// a non-constant 4-D tensor with positive extents; the axis a constant int32 tensor (a scalar or a vector) with data in the file
+// whose entries, negative ones + 4, are exactly {1, 2}; the output [b, C] (keep_dims false) or [b, 1, 1, C] (keep_dims true)
+// with the input's b and C.
+bool MeanOperands(const lce_tfl::Model& M, const lce_tfl::Operator& o, int type) {
   if (o.builtin_code != lce_tfl::kBuiltinMean || o.inputs.size() != 2 || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
   const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
   const lce_tfl::Tensor& axis = M.tensors[o.inputs[1]];
   const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
-  if (in.type != lce_tfl::kTensorFloat32 || in.data || in.shape.size() != 4 || out.type != lce_tfl::kTensorFloat32) return false;
+  if (in.type != type || in.data || in.shape.size() != 4 || out.type != type) return false;
   for (int32_t extent : in.shape)
     if (extent <= 0) return false;
   if (axis.type != lce_tfl::kTensorInt32 || !axis.data || axis.shape.size() > 1) return false;
@@ -513,8 +514,14 @@ bool MeanCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   if (seen != ((1u << 1) | (1u << 2))) return false;
   const std::vector<int32_t>& os = out.shape;
   if (o.keep_dims ? !(os.size() == 4 && os[1] == 1 && os[2] == 1) : os.size() != 2) return false;
-  if (os.front() != in.shape[0] || os.back() != in.shape[3]) return false;
-  const lce_hip_pool2d_desc d = MeanDesc(M, o, in.shape[0]);
+  return os.front() == in.shape[0] && os.back() == in.shape[3];
+}
+
+// "A builtin MEAN that a section may run": GlobalAveragePooling.  MeanOperands on float32 tensors, and lce_hip_pool2d_check
+// accepts the AVERAGE / VALID / stride 1 pool whose filter is the image.
+bool MeanCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (!MeanOperands(M, o, lce_tfl::kTensorFloat32)) return false;
+  const lce_hip_pool2d_desc d = MeanDesc(M, o, M.tensors[o.inputs[0]].shape[0]);
   int32_t oh = 0, ow = 0;
   return lce_hip_pool2d_check(&d, &oh, &ow) == LCE_HIP_OK && oh == 1 && ow == 1;
 }
@@ -570,6 +577,135 @@ bool SoftmaxCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return lce_hip_softmax_f32_check((size_t)id[0], (size_t)id[3], o.softmax_beta) == LCE_HIP_OK;
 }
 
+// ---- the int8 classifier head and the float / int8 boundary (lce_tflite_model_open_passes, "head_i8" and "quantize") ----
+// An int8 activation tensor as the entries want it: quantized with exactly ONE scale and a zero point that is an int8 value.
+bool Int8Activation(const lce_tfl::Tensor& t) {
+  return t.type == lce_tfl::kTensorInt8 && t.quantized && t.scales.size() == 1 && t.zero_points.size() <= 1 && t.zero_point >= -128 &&
+         t.zero_point <= 127;
+}
+
+// lce_hip_mean_i8_desc of a builtin int8 MEAN over height and width at `batch` images, from the FILE's tensors.
+lce_hip_mean_i8_desc MeanI8Desc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  lce_hip_mean_i8_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = batch; d.height = in.shape[1]; d.width = in.shape[2]; d.channels = in.shape[3];
+  d.input_scale = in.scale; d.input_zero_point = (int32_t)in.zero_point;
+  d.output_scale = out.scale; d.output_zero_point = (int32_t)out.zero_point;
+  return d;
+}
+
+// "A builtin int8 MEAN that a section may run": MeanOperands on int8 tensors (the axis and keep_dims rules of the float MEAN),
+// both tensors Int8Activation, and lce_hip_mean_i8_prepare accepts the descriptor (no intermediate can leave int32).
+bool MeanI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (!MeanOperands(M, o, lce_tfl::kTensorInt8)) return false;
+  if (!Int8Activation(M.tensors[o.inputs[0]]) || !Int8Activation(M.tensors[o.outputs[0]])) return false;
+  const lce_hip_mean_i8_desc d = MeanI8Desc(M, o, M.tensors[o.inputs[0]].shape[0]);
+  int32_t m = 0, e = 0;
+  return lce_hip_mean_i8_prepare(&d, &m, &e) == LCE_HIP_OK;
+}
+
+// lce_hip_fc_i8_desc of a builtin int8 FULLY_CONNECTED at `batch` rows, from its options and the FILE's tensors.
+lce_hip_fc_i8_desc FullyConnectedI8Desc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  lce_hip_fc_i8_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = batch; d.inputs = w.shape[1]; d.outputs = w.shape[0];
+  d.activation = o.activation;
+  d.input_scale = in.scale; d.input_zero_point = (int32_t)in.zero_point;
+  d.output_scale = out.scale; d.output_zero_point = (int32_t)out.zero_point;
+  return d;
+}
+
+// lce_hip_fully_connected_i8_prepare on the FILE's constants of int8 FULLY_CONNECTED `o` (the candidate has checked their types
+// and sizes).
+lce_hip_status FullyConnectedI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
+  const lce_hip_fc_i8_desc d = FullyConnectedI8Desc(M, o, M.tensors[o.inputs[0]].shape[0]);
+  const bool has_bias = o.inputs.size() == 3 && o.inputs[2] >= 0;
+  // (flatbuffer vectors are only guaranteed 4-byte aligned, which is what int32 and float need)
+  std::vector<int32_t> bias;
+  if (has_bias) {
+    bias.resize((size_t)w.shape[0]);
+    memcpy(bias.data(), M.tensors[o.inputs[2]].data, bias.size() * 4);
+  }
+  table->assign((size_t)w.shape[0] * 3, 0);
+  int32_t lo = 0, hi = 0;
+  return lce_hip_fully_connected_i8_prepare(&d, (const int8_t*)w.data, has_bias ? bias.data() : nullptr, w.scales.data(),
+                                            (int32_t)w.scales.size(), table->data(), &lo, &hi);
+}
+
+// "A builtin int8 FULLY_CONNECTED that a section may run": the Dense layer of an int8 head.  The rules of FullyConnectedCandidate
+// with: input and output Int8Activation; the weights a constant int8 [N, K] with data in the file whose byte count matches
+// (compared by division), no zero point other than 0, and 1 or N scales -- with more than one, quantized_dimension 0; the bias
+// absent or a constant int32 [N]; and the entry's own check accepts the descriptor.  Partition() then asks
+// lce_hip_fully_connected_i8_prepare ONCE whether it accepts the file's constants and keeps the table for the run.  A float
+// input (hybrid weights), int16 / uint8 tensors, a weight zero point and shuffled weights stay with the host.
+bool FullyConnectedI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinFullyConnected || !o.has_fc_options) return false;
+  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (!Int8Activation(in) || !Int8Activation(out) || w.type != lce_tfl::kTensorInt8) return false;
+  if (o.fc_weights_format != 0 || (o.fc_keep_num_dims && in.shape.size() != 2)) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  int32_t id[4];
+  if (in.data || !Carried(in, id) || id[0] <= 0) return false;
+  if (!w.data || w.shape.size() != 2 || w.shape[0] <= 0 || w.shape[1] <= 0) return false;
+  const uint64_t N = (uint64_t)w.shape[0], K = (uint64_t)w.shape[1];
+  if ((uint64_t)w.bytes % N != 0 || (uint64_t)w.bytes / N != K) return false;
+  if ((uint64_t)id[1] * (uint64_t)id[2] > K || (uint64_t)id[1] * (uint64_t)id[2] * (uint64_t)id[3] != K) return false;
+  for (int64_t z : w.zero_points)
+    if (z != 0) return false;
+  const size_t n_scales = w.scales.size();
+  if (n_scales != 1 && n_scales != (size_t)N) return false;
+  if (n_scales > 1 && w.quantized_dimension != 0) return false;
+  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
+    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
+    if (bias.type != lce_tfl::kTensorInt32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != w.shape[0] ||
+        (uint64_t)bias.bytes != N * 4u)
+      return false;
+  }
+  if (out.shape.size() != 2 || out.shape[0] != id[0] || out.shape[1] != w.shape[0]) return false;
+  const lce_hip_fc_i8_desc d = FullyConnectedI8Desc(M, o, id[0]);
+  return lce_hip_fully_connected_i8_check(&d) == LCE_HIP_OK;
+}
+
+// "A builtin int8 SOFTMAX that a section may run": one Int8Activation non-constant input [b, n] or [b, 1, 1, n]; an Int8Activation
+// output of the same shape; the SoftmaxOptions table present; and lce_hip_softmax_i8_check accepts the scale, beta and the
+// output quantization, which must be exactly (1/256, -128).
+bool SoftmaxI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinSoftmax || !o.has_softmax_options) return false;
+  if (o.inputs.size() != 1 || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (!Int8Activation(in) || !Int8Activation(out) || in.data || in.shape != out.shape) return false;
+  int32_t id[4];
+  if (!Carried(in, id) || id[0] <= 0 || id[1] != 1 || id[2] != 1) return false;
+  return lce_hip_softmax_i8_check((size_t)id[0], (size_t)id[3], in.scale, o.softmax_beta, out.scale, (int32_t)out.zero_point) == LCE_HIP_OK;
+}
+
+// "A builtin QUANTIZE / DEQUANTIZE that a section may run" ("quantize"): one non-constant input and one output of the same shape, of
+// rank 2 or 4 with positive extents; QUANTIZE float32 -> Int8Activation (an int8 input -- a requantization -- is the host's),
+// DEQUANTIZE Int8Activation -> float32.
+bool BoundaryOperands(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t code, bool to_int8) {
+  if (o.builtin_code != code || o.inputs.size() != 1 || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  const lce_tfl::Tensor& f = to_int8 ? in : out;
+  const lce_tfl::Tensor& q = to_int8 ? out : in;
+  if (f.type != lce_tfl::kTensorFloat32 || !Int8Activation(q) || in.data || in.shape != out.shape) return false;
+  if (!std::isfinite(q.scale) || !(q.scale > 0.0f)) return false;
+  int32_t id[4];
+  return Carried(in, id) && id[0] > 0;
+}
+bool QuantizeCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) { return BoundaryOperands(M, o, lce_tfl::kBuiltinQuantize, true); }
+bool DequantizeCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) { return BoundaryOperands(M, o, lce_tfl::kBuiltinDequantize, false); }
+
 // One fused pass: the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it that enables it, the static half of "a section may run
 // this operator", and the walker that runs it.  The table, in priority order, is below Walk.
 struct Walk;
@@ -611,9 +747,15 @@ void lce_tflite_model::Partition() {
       if (ConvI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
       else candidate[i] = 0;
     }
-    // a head operator (MEAN, FULLY_CONNECTED, SOFTMAX) is queued as the LCE operators are, whatever made it ready: behind a host
-    // operator the head is a section of its own, behind the body it joins the body's epoch
-    if (candidate[i] >= kAbsorbedMean) is_lce[i] = 1;
+    // ... and an int8 FULLY_CONNECTED constants lce_hip_fully_connected_i8_prepare accepts
+    if (candidate[i] == kAbsorbedFullyConnectedI8) {
+      std::vector<int32_t> table;
+      if (FullyConnectedI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
+      else candidate[i] = 0;
+    }
+    // a head operator (MEAN, FULLY_CONNECTED, SOFTMAX, float or int8) is queued as the LCE operators are, whatever made it ready:
+    // behind a host operator the head is a section of its own, behind the body it joins the body's epoch
+    if (candidate[i] >= kAbsorbedMean && candidate[i] <= kAbsorbedSoftmaxI8) is_lce[i] = 1;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -771,7 +913,8 @@ lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, co
       {"concat", 0, LCE_TFLITE_SECTIONS_CONCAT},           {"pool", 1, LCE_TFLITE_SECTIONS_EXT_POOL},
       {"conv1x1", 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1},     {"depthwise", 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE},
       {"conv2d", 1, LCE_TFLITE_SECTIONS_EXT_CONV2D},       {"stem", 1, LCE_TFLITE_SECTIONS_EXT_STEM},
-      {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8}};
+      {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8},
+      {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize}};
   uint32_t words[3] = {0u, 0u, 0u};
   std::string refusal;
   if (!passes) refusal = "null passes";
@@ -1453,6 +1596,32 @@ struct Walk {
         });
   }
 
+  // The table Partition() had an entry's prepare make of the constants of operator `i` (`noun`), on the device: uploaded once per
+  // model, where the filters are.
+  lce_hip_status TableOnDevice(int32_t i, const char* noun, const int32_t** out) {
+    lce_tflite_model::DevBuf& b = model->tables[i];
+    if (!b.ptr) {
+      if (capturing) return Fail(LCE_HIP_ERR_INVALID, "run_section: a constant would have to be uploaded during graph capture");
+      auto prepared = model->host_tables.find(i);
+      if (prepared == model->host_tables.end()) return Fail(LCE_HIP_ERR_INVALID, std::string("run_section: ") + noun + " without a prepared table");
+      const std::vector<int32_t>& table = prepared->second;
+      // (the buffer becomes the model's only once the copy has completed: a failed upload leaves nothing a later run would launch on)
+      void* dev = nullptr;
+      if (lce_hip_status s = lce_hip_malloc(&dev, table.size() * 4)) return s;
+      lce_hip_status s = lce_hip_memcpy_h2d(dev, table.data(), table.size() * 4, stream);
+      if (s == LCE_HIP_OK) s = lce_hip_stream_synchronize(stream);
+      if (s != LCE_HIP_OK) {
+        lce_hip_free(dev);
+        return s;
+      }
+      b.ptr = dev;
+      b.bytes = table.size() * 4;
+      model->host_tables.erase(prepared);
+    }
+    *out = (const int32_t*)b.ptr;
+    return LCE_HIP_OK;
+  }
+
   // An absorbed int8 CONV_2D of any filter extent ("conv2d_i8" of lce_tflite_model_open_passes) as ONE lce_hip_conv2d_i8 launch.
   // The table Partition() had lce_hip_conv2d_i8_prepare make of the file's constants is uploaded once per model, where the filters are.
   lce_hip_status ConvI8(int32_t i) {
@@ -1462,35 +1631,20 @@ struct Walk {
         i, kAbsorbedConvI8, "an int8 CONV_2D", lce_tfl::kTensorInt8, d.channels_out,
         [&](int32_t* h, int32_t* w) { return lce_hip_conv2d_i8_check(&d, h, w); },
         [&](const void* x, const float* filter, const float*, void* out, int32_t* bits) -> lce_hip_status {
-          lce_tflite_model::DevBuf& b = model->tables[i];
-          if (!b.ptr) {
-            if (capturing) return Fail(LCE_HIP_ERR_INVALID, "run_section: a constant would have to be uploaded during graph capture");
-            auto prepared = model->host_tables.find(i);
-            if (prepared == model->host_tables.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 CONV_2D without a prepared table");
-            const std::vector<int32_t>& table = prepared->second;
-            // (the buffer becomes the model's only once the copy has completed: a failed upload leaves nothing a later run would launch on)
-            void* dev = nullptr;
-            if (lce_hip_status s = lce_hip_malloc(&dev, table.size() * 4)) return s;
-            lce_hip_status s = lce_hip_memcpy_h2d(dev, table.data(), table.size() * 4, stream);
-            if (s == LCE_HIP_OK) s = lce_hip_stream_synchronize(stream);
-            if (s != LCE_HIP_OK) {
-              lce_hip_free(dev);
-              return s;
-            }
-            b.ptr = dev;
-            b.bytes = table.size() * 4;
-            model->host_tables.erase(prepared);
-          }
-          return lce_hip_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, (const int32_t*)b.ptr, (int8_t*)out, bits, stream);
+          const int32_t* table = nullptr;
+          if (lce_hip_status s = TableOnDevice(i, "an int8 CONV_2D", &table)) return s;
+          return lce_hip_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, table, (int8_t*)out, bits, stream);
         });
   }
 
   // ---- the classifier head ("head" of lce_tflite_model_open_passes).  Rank-2 tensors are carried as [batch, 1, 1, C]. ----
-  // An absorbed head operator `i` that streams ONE input and makes ONE float32 output of shape `os`, as ONE launch of pass
-  // `kind`.  `launch(in, weights, bias, out)` is the entry (`constants`: inputs 1 and 2 of the operator are its weights and its
-  // optional bias, uploaded once per model).  No LceQuantize folds into it, so the output is always written.
+  // An absorbed head operator `i` that streams ONE input of `in_type` and makes ONE output of shape and type `os`, as ONE launch
+  // of pass `kind`.  `launch(in, weights, bias, out)` is the entry; its pointers are typed float and an int8 pass casts them
+  // (`constants`: how many of inputs 1 and 2 of the operator -- its weights and its optional bias -- are uploaded as they are,
+  // once per model).  No LceQuantize folds into it, so the output is always written.
   template <class Launch>
-  lce_hip_status HeadPass(int32_t i, int kind, const std::string& noun, const Shape& os, bool constants, Launch launch) {
+  lce_hip_status HeadPass(int32_t i, int kind, const std::string& noun, const Shape& os, int constants, Launch launch,
+                          int in_type = lce_tfl::kTensorFloat32) {
     const lce_tfl::Model& M = model->m;
     const lce_tfl::Operator& op = M.operators[i];
     const int32_t out_t = op.outputs[0];
@@ -1499,7 +1653,7 @@ struct Walk {
     int32_t want[4];
     auto it = shapes.find(op.inputs[0]);
     if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " reads a tensor nothing produced");
-    if (!Carried(M.tensors[op.inputs[0]], want) || !Agrees(it->second, lce_tfl::kTensorFloat32, want[1], want[2], want[3]))
+    if (!Carried(M.tensors[op.inputs[0]], want) || !Agrees(it->second, in_type, want[1], want[2], want[3]))
       return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " input's shape or type does not match the one its producer infers");
     shapes[out_t] = os;
     done[i] = 1;
@@ -1508,19 +1662,19 @@ struct Walk {
     const void* in = nullptr;
     if (lce_hip_status s = DevicePtr(op.inputs[0], (noun + " input").c_str(), &in)) return s;
     const float *weights = nullptr, *bias = nullptr;
-    if (constants)
+    if (constants >= 1)
       if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &weights)) return s;
-    if (constants && op.inputs.size() == 3 && op.inputs[2] >= 0)
+    if (constants >= 2 && op.inputs.size() == 3 && op.inputs[2] >= 0)
       if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
     void *out, *bits;
     if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
     if (lce_hip_status s = launch((const float*)in, weights, bias, (float*)out)) return s;
     return Launched(kind, fold);
   }
-  Shape HeadShape(int32_t h, int32_t w, int32_t c) const {
+  Shape HeadShape(int32_t h, int32_t w, int32_t c, int type = lce_tfl::kTensorFloat32) const {
     Shape os;
     os.dims[0] = batch; os.dims[1] = h; os.dims[2] = w; os.dims[3] = c;
-    os.type = lce_tfl::kTensorFloat32;
+    os.type = type;
     return os;
   }
 
@@ -1529,7 +1683,7 @@ struct Walk {
     const lce_hip_pool2d_desc d = MeanDesc(model->m, model->m.operators[i], batch);
     int32_t oh = 0, ow = 0;
     if (lce_hip_status s = lce_hip_pool2d_check(&d, &oh, &ow)) return s;
-    return HeadPass(i, kAbsorbedMean, "a MEAN", HeadShape(oh, ow, d.channels), /*constants=*/false,
+    return HeadPass(i, kAbsorbedMean, "a MEAN", HeadShape(oh, ow, d.channels), /*constants=*/0,
                     [&](const float* x, const float*, const float*, float* out) { return lce_hip_pool2d(&d, x, out, nullptr, stream); });
   }
 
@@ -1537,7 +1691,7 @@ struct Walk {
   lce_hip_status FullyConnected(int32_t i) {
     const lce_hip_fc_desc d = FullyConnectedDesc(model->m, model->m.operators[i], batch);
     if (lce_hip_status s = lce_hip_fully_connected_f32_check(&d)) return s;
-    return HeadPass(i, kAbsorbedFullyConnected, "a FULLY_CONNECTED", HeadShape(1, 1, d.outputs), /*constants=*/true,
+    return HeadPass(i, kAbsorbedFullyConnected, "a FULLY_CONNECTED", HeadShape(1, 1, d.outputs), /*constants=*/2,
                     [&](const float* x, const float* weights, const float* bias, float* out) {
                       return lce_hip_fully_connected_f32(&d, x, weights, bias, out, stream);
                     });
@@ -1549,11 +1703,71 @@ struct Walk {
     int32_t id[4];
     if (!Carried(model->m.tensors[op.inputs[0]], id)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a SOFTMAX of a rank that is neither 2 nor 4");
     if (lce_hip_status s = lce_hip_softmax_f32_check((size_t)batch, (size_t)id[3], op.softmax_beta)) return s;
-    return HeadPass(i, kAbsorbedSoftmax, "a SOFTMAX", HeadShape(1, 1, id[3]), /*constants=*/false,
+    return HeadPass(i, kAbsorbedSoftmax, "a SOFTMAX", HeadShape(1, 1, id[3]), /*constants=*/0,
                     [&](const float* x, const float*, const float*, float* out) {
                       return lce_hip_softmax_f32((size_t)batch, (size_t)id[3], op.softmax_beta, x, out, stream);
                     });
   }
+
+  // ---- the int8 head and the float / int8 boundary ("head_i8" and "quantize" of lce_tflite_model_open_passes) ----
+  // An absorbed int8 MEAN over height and width as ONE lce_hip_mean_i8 launch.
+  lce_hip_status MeanI8(int32_t i) {
+    const lce_hip_mean_i8_desc d = MeanI8Desc(model->m, model->m.operators[i], batch);
+    if (lce_hip_status s = lce_hip_mean_i8_check(&d)) return s;
+    return HeadPass(i, kAbsorbedMeanI8, "an int8 MEAN", HeadShape(1, 1, d.channels, lce_tfl::kTensorInt8), /*constants=*/0,
+                    [&](const float* x, const float*, const float*, float* out) {
+                      return lce_hip_mean_i8(&d, (const int8_t*)x, (int8_t*)out, stream);
+                    }, lce_tfl::kTensorInt8);
+  }
+
+  // An absorbed int8 FULLY_CONNECTED as ONE lce_hip_fully_connected_i8 launch; its bias lives in the prepared table.
+  lce_hip_status FullyConnectedI8(int32_t i) {
+    const lce_hip_fc_i8_desc d = FullyConnectedI8Desc(model->m, model->m.operators[i], batch);
+    if (lce_hip_status s = lce_hip_fully_connected_i8_check(&d)) return s;
+    return HeadPass(i, kAbsorbedFullyConnectedI8, "an int8 FULLY_CONNECTED", HeadShape(1, 1, d.outputs, lce_tfl::kTensorInt8), /*constants=*/1,
+                    [&](const float* x, const float* weights, const float*, float* out) -> lce_hip_status {
+                      const int32_t* table = nullptr;
+                      if (lce_hip_status s = TableOnDevice(i, "an int8 FULLY_CONNECTED", &table)) return s;
+                      return lce_hip_fully_connected_i8(&d, (const int8_t*)x, (const int8_t*)weights, table, (int8_t*)out, stream);
+                    }, lce_tfl::kTensorInt8);
+  }
+
+  // An absorbed int8 SOFTMAX as ONE lce_hip_softmax_i8 launch.
+  lce_hip_status SoftmaxI8(int32_t i) {
+    const lce_tfl::Operator& op = model->m.operators[i];
+    const lce_tfl::Tensor& in = model->m.tensors[op.inputs[0]];
+    const lce_tfl::Tensor& out = model->m.tensors[op.outputs[0]];
+    int32_t id[4];
+    if (!Carried(in, id)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a SOFTMAX of a rank that is neither 2 nor 4");
+    if (lce_hip_status s = lce_hip_softmax_i8_check((size_t)batch, (size_t)id[3], in.scale, op.softmax_beta, out.scale, (int32_t)out.zero_point)) return s;
+    return HeadPass(i, kAbsorbedSoftmaxI8, "an int8 SOFTMAX", HeadShape(1, 1, id[3], lce_tfl::kTensorInt8), /*constants=*/0,
+                    [&](const float* x, const float*, const float*, float* o) {
+                      return lce_hip_softmax_i8((size_t)batch, (size_t)id[3], in.scale, op.softmax_beta, out.scale, (int32_t)out.zero_point,
+                                                (const int8_t*)x, (int8_t*)o, stream);
+                    }, lce_tfl::kTensorInt8);
+  }
+
+  // An absorbed QUANTIZE (float32 -> int8) or DEQUANTIZE (int8 -> float32) as ONE launch over the tensor's elements.
+  lce_hip_status Boundary(int32_t i, bool to_int8) {
+    const lce_tfl::Operator& op = model->m.operators[i];
+    const lce_tfl::Tensor& q = model->m.tensors[to_int8 ? op.outputs[0] : op.inputs[0]];
+    int32_t id[4];
+    if (!Carried(model->m.tensors[op.inputs[0]], id)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a QUANTIZE / DEQUANTIZE of a rank that is neither 2 nor 4");
+    const size_t n = (size_t)batch * (size_t)id[1] * (size_t)id[2] * (size_t)id[3];
+    const float scale = q.scale;
+    const int32_t zp = (int32_t)q.zero_point;
+    if (to_int8)
+      return HeadPass(i, kAbsorbedQuantize, "a QUANTIZE", HeadShape(id[1], id[2], id[3], lce_tfl::kTensorInt8), /*constants=*/0,
+                      [&](const float* x, const float*, const float*, float* out) {
+                        return lce_hip_quantize_f32_i8(n, scale, zp, x, (int8_t*)out, stream);
+                      });
+    return HeadPass(i, kAbsorbedDequantize, "a DEQUANTIZE", HeadShape(id[1], id[2], id[3]), /*constants=*/0,
+                    [&](const float* x, const float*, const float*, float* out) {
+                      return lce_hip_dequantize_i8_f32(n, scale, zp, (const int8_t*)x, out, stream);
+                    }, lce_tfl::kTensorInt8);
+  }
+  lce_hip_status QuantizeF32I8(int32_t i) { return Boundary(i, true); }
+  lce_hip_status DequantizeI8F32(int32_t i) { return Boundary(i, false); }
 
   // The four LCE operators.  `in` is the inferred shape of operator `i`'s first input, `in_dev` its device pointer (with `run`).
   lce_hip_status Quantize(int32_t i, const Shape& in, const void* in_dev) {                      // quantization.cc:19-41,76-114
@@ -1670,7 +1884,7 @@ struct Walk {
       const lce_tfl::Tensor& T = M.tensors[t];
       Shape sh;
       // (a rank-2 input -- of a head that starts behind a host operator -- is carried as [batch, 1, 1, C])
-      if (T.shape.size() == 2 && (model->flags_int & kInternalHead)) {
+      if (T.shape.size() == 2 && (model->flags_int & (kInternalHead | kInternalHeadI8 | kInternalQuantize))) {
         if (!Carried(T, sh.dims)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a section input with an extent that is not positive");
       } else {
         if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
@@ -1708,6 +1922,13 @@ const FusedPass kPasses[kAbsorbedCount - 1] = {
     {kAbsorbedMean, 2, kInternalHead, MeanCandidate, &Walk::Mean},
     {kAbsorbedFullyConnected, 2, kInternalHead, FullyConnectedCandidate, &Walk::FullyConnected},
     {kAbsorbedSoftmax, 2, kInternalHead, SoftmaxCandidate, &Walk::Softmax},
+    // the int8 head ("head_i8") and the float / int8 boundary ("quantize"): no float predicate above takes an int8 MEAN /
+    // FULLY_CONNECTED / SOFTMAX and none of these takes a float one, so the two heads never compete
+    {kAbsorbedMeanI8, 2, kInternalHeadI8, MeanI8Candidate, &Walk::MeanI8},
+    {kAbsorbedFullyConnectedI8, 2, kInternalHeadI8, FullyConnectedI8Candidate, &Walk::FullyConnectedI8},
+    {kAbsorbedSoftmaxI8, 2, kInternalHeadI8, SoftmaxI8Candidate, &Walk::SoftmaxI8},
+    {kAbsorbedQuantize, 2, kInternalQuantize, QuantizeCandidate, &Walk::QuantizeF32I8},
+    {kAbsorbedDequantize, 2, kInternalQuantize, DequantizeCandidate, &Walk::DequantizeI8F32},
 };
 }  // namespace
 
@@ -1839,6 +2060,17 @@ void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t
   PassStats(model, kAbsorbedMean, mean, nullptr);
   PassStats(model, kAbsorbedFullyConnected, fully_connected, nullptr);
   PassStats(model, kAbsorbedSoftmax, softmax, nullptr);
+}
+
+void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {
+  PassStats(model, kAbsorbedMeanI8, mean, nullptr);
+  PassStats(model, kAbsorbedFullyConnectedI8, fully_connected, nullptr);
+  PassStats(model, kAbsorbedSoftmaxI8, softmax, nullptr);
+}
+
+void lce_tflite_model_quantize_stats(lce_tflite_model* model, int32_t* quantize, int32_t* dequantize) {
+  PassStats(model, kAbsorbedQuantize, quantize, nullptr);
+  PassStats(model, kAbsorbedDequantize, dequantize, nullptr);
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

@@ -33,6 +33,7 @@
 //   BuiltinOptions union type 8 FullyConnectedOptions: 0 fused_activation_function(int8)  1 weights_format(int8, 0 DEFAULT)
 //   2 keep_num_dims(bool)  3 asymmetric_quantize_inputs(bool); BuiltinOperator 9 FULLY_CONNECTED.
 //   BuiltinOptions union type 9 SoftmaxOptions: 0 beta(float); BuiltinOperator 25 SOFTMAX.
+//   BuiltinOperator 6 DEQUANTIZE, 114 QUANTIZE: no option this reader needs.
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -51,6 +52,7 @@ namespace lce_tfl {
 constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
 constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinConv2d = 3, kBuiltinDepthwiseConv2d = 4, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
 constexpr int32_t kBuiltinFullyConnected = 9, kBuiltinSoftmax = 25, kBuiltinMean = 40;
+constexpr int32_t kBuiltinDequantize = 6, kBuiltinQuantize = 114;   // (their options tables, QuantizeOptions and DequantizeOptions, are empty)
 constexpr int kOptionsConv2d = 1, kOptionsDepthwiseConv2d = 2, kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 constexpr int kOptionsFullyConnected = 8, kOptionsSoftmax = 9, kOptionsReducer = 27;
 // TensorType values used by LCE graphs

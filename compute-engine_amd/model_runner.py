@@ -45,6 +45,11 @@ int8-converted network -- its stem, the 1x1 of a downsampling shortcut or a tran
 TFLite's integer arithmetic byte for byte on the int8 matrix instruction); with ``int8_add_sections``, ``pool_sections`` and
 ``stem_sections`` an int8 residual block with its shortcut, and an int8 stem with the binary layer behind it, are one section each.  Measured at batch 256 (profiles/conv2d_i8): the kernel takes 0.80 (3x3 / 2 stem), 0.41 (7x7 / 2
 stem) and 0.57 (1x1 shortcut) of the float entry's time at the same shape.
+With ``head_i8_sections=True`` and ``quantize_sections=True`` (the names ``head_i8`` and ``quantize``) the int8 classifier head --
+MEAN, FULLY_CONNECTED, SOFTMAX on int8 tensors -- and the builtin QUANTIZE / DEQUANTIZE of the float interface join them
+(``lce_hip_mean_i8``, ``lce_hip_fully_connected_i8``, ``lce_hip_softmax_i8``, ``lce_hip_quantize_f32_i8``,
+``lce_hip_dequantize_i8_f32``): with every keyword an int8-converted network is ONE section too, and ``predict`` takes float
+images and returns float ``[N, classes]`` on a file with a float interface, int8 on a file with an int8 interface.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -128,7 +133,10 @@ _SECTION_KEYWORDS = (
 # the names of ``lce_tflite_model_open_passes`` (the only entry that knows ``head``), by keyword
 _PASS_NAMES = {"elementwise_sections": "elementwise", "int8_add_sections": "int8_add", "concat_sections": "concat",
                "pool_sections": "pool", "conv1x1_sections": "conv1x1", "depthwise_sections": "depthwise",
-               "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head", "conv2d_i8_sections": "conv2d_i8"}
+               "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head", "conv2d_i8_sections": "conv2d_i8",
+               "head_i8_sections": "head_i8", "quantize_sections": "quantize"}
+# the keywords whose names only ``lce_tflite_model_open_passes`` knows, in the order their names are passed
+_NAMED_ONLY = ("head_sections", "conv2d_i8_sections", "head_i8_sections", "quantize_sections")
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
 # ``lce_tflite_model_<pass>_stats``: the counters each reports
 _PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2}
@@ -164,6 +172,8 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_open_passes.restype = C.c_void_p
         l.lce_tflite_model_open_passes.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t]
         l.lce_tflite_model_head_stats.argtypes, l.lce_tflite_model_head_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
+        l.lce_tflite_model_head_i8_stats.argtypes, l.lce_tflite_model_head_i8_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
+        l.lce_tflite_model_quantize_stats.argtypes, l.lce_tflite_model_quantize_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
         l.lce_tflite_model_operator_reducer.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_fully_connected.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_softmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -243,7 +253,8 @@ class LceModel:
     def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
                  int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
                  conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
-                 stem_sections: bool = False, head_sections: bool = False, conv2d_i8_sections: bool = False):
+                 stem_sections: bool = False, head_sections: bool = False, conv2d_i8_sections: bool = False,
+                 head_i8_sections: bool = False, quantize_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -261,7 +272,10 @@ class LceModel:
         ``conv2d_i8_sections``: the quantized CONV_2D of an int8-converted network (stem, shortcut, transition) joins them
         (``lce_hip_conv2d_i8``); it routes through ``lce_tflite_model_open_passes`` too (the name ``conv2d_i8``), and every
         combination without it keeps its route.  Its kernel takes 0.41-0.80 of the float entry's time at the same shapes (module docstring;
-        profiles/conv2d_i8)."""
+        profiles/conv2d_i8).  ``head_i8_sections``: the int8 classifier head (MEAN, FULLY_CONNECTED, SOFTMAX on int8 tensors)
+        joins them (``lce_hip_mean_i8``, ``lce_hip_fully_connected_i8``, ``lce_hip_softmax_i8``; the name ``head_i8``).
+        ``quantize_sections``: the builtin QUANTIZE float32 -> int8 and DEQUANTIZE int8 -> float32 join them (the name
+        ``quantize``).  With every keyword an int8-converted network is ONE section from the image to the probabilities."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -277,10 +291,12 @@ class LceModel:
                 size = max(size, form)
         self.head_sections = bool(head_sections)
         self.conv2d_i8_sections = bool(conv2d_i8_sections)
+        self.head_i8_sections = bool(head_i8_sections)
+        self.quantize_sections = bool(quantize_sections)
         err = C.create_string_buffer(256)
-        if self.head_sections or self.conv2d_i8_sections:
+        if any(getattr(self, keyword) for keyword in _NAMED_ONLY):
             names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]]
-            names += ["head"] * self.head_sections + ["conv2d_i8"] * self.conv2d_i8_sections
+            names += [_PASS_NAMES[keyword] for keyword in _NAMED_ONLY if getattr(self, keyword)]
             self._h = tflite_lib().lce_tflite_model_open_passes(self._data, len(self._data), ",".join(names).encode(), err, 256)
         elif size:
             opts = _OPEN_OPTIONS[size](size, *words[:1 if size == 8 else 2])
@@ -400,6 +416,18 @@ class LceModel:
         tflite_lib().lce_tflite_model_head_stats(self._h, *[C.byref(c) for c in v])
         return tuple(int(c.value) for c in v)
 
+    def head_i8_stats(self):
+        """(lce_hip_mean_i8, lce_hip_fully_connected_i8, lce_hip_softmax_i8 launches) of the last run."""
+        v = [C.c_int32() for _ in range(3)]
+        tflite_lib().lce_tflite_model_head_i8_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
+    def quantize_stats(self):
+        """(lce_hip_quantize_f32_i8 launches, lce_hip_dequantize_i8_f32 launches) of the last run."""
+        v = [C.c_int32() for _ in range(2)]
+        tflite_lib().lce_tflite_model_quantize_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -431,9 +459,10 @@ class Interpreter:
                  use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
                  concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
                  depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False,
-                 head_sections: bool = False, conv2d_i8_sections: bool = False):
+                 head_sections: bool = False, conv2d_i8_sections: bool = False, head_i8_sections: bool = False,
+                 quantize_sections: bool = False):
         """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
-        ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+        ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``, ``head_i8_sections``, ``quantize_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
@@ -441,11 +470,12 @@ class Interpreter:
                                     pool_sections=pool_sections, conv1x1_sections=conv1x1_sections,
                                     depthwise_sections=depthwise_sections, conv2d_sections=conv2d_sections,
                                     stem_sections=stem_sections, head_sections=head_sections,
-                                    conv2d_i8_sections=conv2d_i8_sections))
+                                    conv2d_i8_sections=conv2d_i8_sections, head_i8_sections=head_i8_sections,
+                                    quantize_sections=quantize_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if self.model.head_sections or self.model.conv2d_i8_sections or any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
+        if any(getattr(self.model, keyword) for keyword in _NAMED_ONLY) or any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

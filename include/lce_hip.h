@@ -504,6 +504,111 @@ lce_hip_status lce_hip_softmax_f32(size_t rows, size_t cols, float beta, const f
 lce_hip_status lce_hip_softmax_f32_check(size_t rows, size_t cols, float beta);
 
 /* ------------------------------------------------------------------------------------
+ * The int8 classifier head and the float/int8 boundary (TFLite builtin MEAN, FULLY_CONNECTED, SOFTMAX on int8; QUANTIZE, DEQUANTIZE)
+ * ---------------------------------------------------------------------------------- */
+
+/* An int8-converted network ends in the same GlobalAveragePooling -> Dense -> softmax, on int8 tensors, between a QUANTIZE behind
+ * its float input and a DEQUANTIZE in front of its float output.  The contracts below are the authority: each states its
+ * arithmetic completely and tests/head_i8_ref.py restates it in NumPy.  INTEGRATION.md says which TFLite function each one
+ * restates.  Common to the five launch entries: ONE launch, asynchronous on `stream`, capturable in a HIP graph, nothing
+ * allocated and nothing copied between host and device, 64-bit offsets throughout; refused before any device call with
+ * LCE_HIP_ERR_INVALID: a NULL pointer, an output that overlaps an input (the softmax in place excepted), a scale that is not finite
+ * and positive, a zero point outside [-128, 127].  int8 pointers need no alignment; the table and float pointers need 4 bytes.
+ * SRDHM (SaturatingRoundingDoublingHighMul), RoundingDivideByPOT and QuantizeMultiplier are as lce_hip_add_int8 states them.
+ *
+ * lce_hip_fully_connected_i8: out[batch][outputs] int8 at (so, zo) from in[batch][inputs] int8 at (si, zi), the weights int8 in the
+ * file's layout [outputs][inputs] with zero point 0 and scales sw[o] (one for all, or one per output), and an optional int32 bias.
+ * The arithmetic is exactly lce_hip_conv2d_i8's on a [batch, 1, 1, inputs] image with a 1x1 filter, per output element:
+ *   acc = sum_k (x[k] - zi) * w[o][k]                    exact, int32
+ *   acc += bias[o]                                       when there is a bias
+ *   (m[o], e[o]) = QuantizeMultiplier((double)si * (double)sw[o] / (double)so)
+ *   acc = RoundingDivideByPOT(SRDHM(acc * 2^max(e,0), m), max(-e,0))
+ *   v   = min(max(acc + zo, act_min), act_max)           CalculateActivationRangeQuantized at (so, zo)
+ * so the bytes are lce_hip_conv2d_i8's there.  The kernel is tiled for few rows and many columns: one wave per 16 x 16 tile on
+ * v_mfma_i32_16x16x64_i8 (lce_kernels_head_i8.h).
+ *   _check: the descriptor alone.  LCE_HIP_ERR_INVALID: a NULL desc, an extent <= 0, an unknown activation, a bad scale or zero
+ *     point.  LCE_HIP_ERR_UNSUPPORTED: inputs > 65793 (255 x 128 x K > 2^31 - 1: no table exists), 2^31 or more tiles of 16 x 16.
+ *   _prepare: host only; lce_hip_conv2d_i8_prepare's table int32 [3][outputs] = c[o] = bias[o] - zi * sum_k w[o][k], m[o], e[o], and
+ *     the activation range, with that entry's refusals, which name the channel (LCE_HIP_ERR_UNSUPPORTED: 255 x 128 x K + max|bias|
+ *     > 2^31 - 1; for a channel with e > 0 that bound times 2^e > 2^31 - 1) and its LCE_HIP_ERR_INVALID cases.
+ *   launch: `table_dev` is prepare's table on the device.  16-byte aligned input and weights with inputs % 16 == 0 take a faster
+ *     load path. */
+typedef struct lce_hip_fc_i8_desc {
+  int32_t batch, inputs, outputs;
+  int32_t activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+  float input_scale;
+  int32_t input_zero_point;
+  float output_scale;
+  int32_t output_zero_point;
+} lce_hip_fc_i8_desc;
+lce_hip_status lce_hip_fully_connected_i8_check(const lce_hip_fc_i8_desc* desc);
+lce_hip_status lce_hip_fully_connected_i8_prepare(const lce_hip_fc_i8_desc* desc, const int8_t* weights_host /* [outputs][inputs] */,
+                                                  const int32_t* bias_host /* nullable */, const float* weight_scales,
+                                                  int32_t n_scales /* 1 or outputs */, int32_t* table /* [3][outputs] */,
+                                                  int32_t* act_min, int32_t* act_max);
+lce_hip_status lce_hip_fully_connected_i8(const lce_hip_fc_i8_desc* desc, const int8_t* in_dev, const int8_t* weights_dev,
+                                          const int32_t* table_dev /* [3][outputs] */, int8_t* out_dev, void* stream);
+
+/* lce_hip_mean_i8: out[batch][channels] int8 at (so, zo) from NHWC int8 [batch, height, width, channels] at (si, zi): the MEAN over
+ * height and width (keep_dims or not: the bytes are the same).  With n = height * width, per output element:
+ *   acc    = sum over the n pixels of (x - zi)                                     exact, int32
+ *   (m, e) = QuantizeMultiplier((double)si / (double)so)
+ *   t      = RoundingDivideByPOT(SRDHM(acc * 2^max(e,0), m), max(-e,0))
+ *   q      = t > 0 ? (t + n/2) / n : (t - n/2) / n                                 C++ int32 division (truncating); n/2 truncating
+ *   v      = min(max(q + zo, -128), 127)
+ * -- multiply first, then divide rounding half away from zero (reference_integer_ops::Mean).  Equal input and output
+ * quantization goes through the same arithmetic: there is no special case.
+ *   _check: LCE_HIP_ERR_INVALID: a NULL desc, an extent <= 0, a bad scale or zero point.  LCE_HIP_ERR_UNSUPPORTED: more than 2^60
+ *     elements.
+ *   _prepare: the check, then (m, e).  LCE_HIP_ERR_UNSUPPORTED where an intermediate could leave int32: |acc| <= 255 n, the left
+ *     shift makes it 255 n 2^max(e,0), SRDHM and the rounding division do not enlarge it (m < 2^31), and n/2 is added to it, so
+ *     the entry requires  255 * n * 2^max(e,0) + n/2 <= 2^31 - 1  (a multiplier below 1 has e <= 0: n <= 8405024; equal scales
+ *     give the multiplier 1 = 2^30 x 2^(1 - 31), e = 1: n <= 4206628).
+ *   launch: what the prepare refuses, it refuses. */
+typedef struct lce_hip_mean_i8_desc {
+  int32_t batch, height, width, channels;
+  float input_scale;
+  int32_t input_zero_point;
+  float output_scale;
+  int32_t output_zero_point;
+} lce_hip_mean_i8_desc;
+lce_hip_status lce_hip_mean_i8_check(const lce_hip_mean_i8_desc* desc);
+lce_hip_status lce_hip_mean_i8_prepare(const lce_hip_mean_i8_desc* desc, int32_t* multiplier, int32_t* exponent);
+lce_hip_status lce_hip_mean_i8(const lce_hip_mean_i8_desc* desc, const int8_t* in_dev, int8_t* out_dev, void* stream);
+
+/* lce_hip_softmax_i8: the softmax over the last axis of in[rows][cols] int8 at scale si (the zero point cancels), int8 out at
+ * EXACTLY (1/256, -128).  It states its own bytes, built on lce_hip_softmax_f32's pieces (every operation float32, no contraction):
+ *   d_i = q_i - max_j q_j                         an integer in [-255, 0]
+ *   sb  = si * beta                               one float32 multiply
+ *   a_i = (float)d_i * sb
+ *   e_i = E(a_i)                                  E exactly as lce_hip_softmax_f32 states it
+ *   s   = that entry's fixed-order sum            64 partial sums in order from +0.0f, then s_l = s_l + s_{l ^ d}, d = 32 .. 1
+ *   p_i = e_i / s                                 the correctly rounded division
+ *   t   = p_i * 256.0f
+ *   r   = roundf(t)                               half away from zero (NOT floor(t + 0.5f), whose add can round up across 1.0)
+ *   v   = min((int)r - 128, 127)
+ * in_dev == out_dev (in place) is allowed.
+ *   _check: LCE_HIP_ERR_INVALID: rows or cols of 0, an input scale or beta that is not finite and positive, an output scale that
+ *     is not finite and positive, an output zero point outside [-128, 127].  LCE_HIP_ERR_UNSUPPORTED: an output quantization other
+ *     than (1/256, -128); cols >= 2^31 or more than 2^60 elements.
+ *   launch: the check and the pointers (an output that overlaps the input without being it is refused). */
+lce_hip_status lce_hip_softmax_i8_check(size_t rows, size_t cols, float input_scale, float beta, float output_scale,
+                                        int32_t output_zero_point);
+lce_hip_status lce_hip_softmax_i8(size_t rows, size_t cols, float input_scale, float beta, float output_scale,
+                                  int32_t output_zero_point, const int8_t* in_dev, int8_t* out_dev, void* stream);
+
+/* lce_hip_quantize_f32_i8 / lce_hip_dequantize_i8_f32: `n` elements across the float / int8 boundary at (scale, zero_point) = (s, zp).
+ *   dequantize: out = (float)(q - zp) * s         one float32 multiply; it equals the double product rounded once (AffineDequantize)
+ *   quantize:   t = x / s                         the IEEE float32 division
+ *               r = roundf(t)                     half away from zero
+ *               r = min(max(r, -128 - zp), 127 - zp)   in float, before the conversion: nothing is undefined
+ *               v = (int)r + zp                   a NaN gives zp; +inf and -inf saturate to 127 and -128 (AffineQuantize)
+ * n == 0 is a no-op.  LCE_HIP_ERR_INVALID: a NULL pointer, a bad scale or zero point, a float pointer that is not 4-byte aligned,
+ * an output that overlaps the input.  LCE_HIP_ERR_UNSUPPORTED: more than 2^60 elements. */
+lce_hip_status lce_hip_quantize_f32_i8(size_t n, float scale, int32_t zero_point, const float* in_dev, int8_t* out_dev, void* stream);
+lce_hip_status lce_hip_dequantize_i8_f32(size_t n, float scale, int32_t zero_point, const int8_t* in_dev, float* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * LceBconv2d
  * ---------------------------------------------------------------------------------- */
 

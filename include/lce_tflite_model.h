@@ -163,7 +163,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
                                              size_t err_len);
 
 /* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
- *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8
+ *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize
  * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
  * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
  * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
@@ -205,9 +205,30 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   any enabled opt-in.  lce_tflite_model_run_section runs it as ONE lce_hip_conv2d_i8 launch -- TFLite's integer arithmetic
  *   byte for byte -- whose table is prepared and uploaded once per model beside the filter; a following LceQuantize folds into
  *   the launch's bits.  With int8_add, pool and stem an int8 Bi-RealNet-style block with its downsampling shortcut, and an int8
- *   stem with the binary layer behind it, are one section each.  Still the host's in an int8 network: int8 DEPTHWISE_CONV_2D,
- *   the int8 head, QUANTIZE / DEQUANTIZE.  Kernel time at batch 256 against the float entry at the same shape: 0.80 of it on the
- *   3x3 / 2 stem, 0.41 on the 7x7 / 2 stem, 0.57 on the 1x1 shortcut (profiles/conv2d_i8). */
+ *   stem with the binary layer behind it, are one section each.  Not this name's: int8 DEPTHWISE_CONV_2D (the host's), the
+ *   int8 head and QUANTIZE / DEQUANTIZE (head_i8 and quantize, below).  Kernel time at batch 256 against the float entry at the same shape: 0.80 of it on the
+ *   3x3 / 2 stem, 0.41 on the 7x7 / 2 stem, 0.57 on the 1x1 shortcut (profiles/conv2d_i8).
+ *   head_i8: the int8 classifier head of an int8-converted network joins the sections, queued as `head` queues the float one; no
+ *   other entry can ask for it, no float predicate takes an int8 MEAN / FULLY_CONNECTED / SOFTMAX and none of these takes a float
+ *   one, so a float file's partition is unchanged.  Every activation tensor is int8, quantized with exactly ONE scale and a zero
+ *   point in [-128, 127].
+ *   MEAN (40): the axis / keep_dims / shape rules of `head`'s MEAN on int8 tensors, and lce_hip_mean_i8_prepare accepts the
+ *   descriptor.  ONE lce_hip_mean_i8 launch (a requantizing MEAN included: one arithmetic for every pair of quantizations).
+ *   FULLY_CONNECTED (9): the rules of `head`'s with: the weights a constant int8 [N, K] with data in the file whose byte count
+ *   matches (compared by division), no zero point other than 0, and 1 or N scales (with more than one, quantized_dimension 0);
+ *   the bias absent or a constant int32 [N]; lce_hip_fully_connected_i8_check accepts the descriptor and
+ *   lce_hip_fully_connected_i8_prepare the file's constants.  ONE lce_hip_fully_connected_i8 launch; the weights and the
+ *   prepared table are uploaded once per model.
+ *   SOFTMAX (25): `head`'s rules on int8 tensors, and lce_hip_softmax_i8_check accepts the input scale, beta and the output
+ *   quantization, which must be exactly (1/256, -128).  ONE lce_hip_softmax_i8 launch.
+ *   A hybrid FULLY_CONNECTED (float input, int8 weights), int16 and uint8 tensors, a weight zero point, another softmax output
+ *   quantization stay with the host.
+ *   quantize: the builtin QUANTIZE (114) float32 -> int8 and DEQUANTIZE (6) int8 -> float32 join the sections: one non-constant
+ *   input and one output of the same shape, rank 2 or 4 with positive extents, the int8 side quantized as above.  They join the
+ *   epoch in which they become ready, and `stem` applies to a QUANTIZE at the graph's input as to any enabled opt-in.  ONE
+ *   lce_hip_quantize_f32_i8 / lce_hip_dequantize_i8_f32 launch each.  A QUANTIZE with an int8 input (a requantization) stays with
+ *   the host.  With every name an int8-converted network with a float interface is ONE section from the float image to the
+ *   float probabilities.  Still the host's: int8 DEPTHWISE_CONV_2D, RESHAPE and the three-layer heads, LOGISTIC. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -357,6 +378,10 @@ void lce_tflite_model_conv_i8_stats(lce_tflite_model* model, int32_t* launches, 
 /* The LAST run's launches for the classifier head ("head" of lce_tflite_model_open_passes): lce_hip_pool2d launches that ran a
  * MEAN, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches.  Nullable outputs. */
 void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
+/* The LAST run's launches for the int8 head ("head_i8"): lce_hip_mean_i8, lce_hip_fully_connected_i8 and lce_hip_softmax_i8
+ * launches; and for the float / int8 boundary ("quantize"): lce_hip_quantize_f32_i8 and lce_hip_dequantize_i8_f32 launches. */
+void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
+void lce_tflite_model_quantize_stats(lce_tflite_model* model, int32_t* quantize, int32_t* dequantize);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
