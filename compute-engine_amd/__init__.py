@@ -41,6 +41,8 @@ ABI_SYMBOLS = (
     "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
     "lce_hip_conv2d_i8", "lce_hip_conv2d_i8_check", "lce_hip_conv2d_i8_prepare",
+    "lce_hip_depthwise_conv2d_i8", "lce_hip_depthwise_conv2d_i8_check", "lce_hip_depthwise_conv2d_i8_prepare",
+    "lce_hip_depthwise_conv2d_i8_path", "lce_hip_depthwise_conv2d_i8_forced",
     "lce_hip_fully_connected_f32", "lce_hip_fully_connected_f32_check", "lce_hip_softmax_f32", "lce_hip_softmax_f32_check",
     "lce_hip_fully_connected_i8", "lce_hip_fully_connected_i8_check", "lce_hip_fully_connected_i8_prepare",
     "lce_hip_mean_i8", "lce_hip_mean_i8_check", "lce_hip_mean_i8_prepare", "lce_hip_softmax_i8", "lce_hip_softmax_i8_check",
@@ -127,6 +129,12 @@ class Conv2dI8Desc(C.Structure):
                                       ("output_zero_point", C.c_int32)]
 
 
+class DepthwiseI8Desc(C.Structure):
+    """``lce_hip_depthwise_i8_desc``."""
+    _fields_ = DepthwiseDesc._fields_ + [("input_scale", C.c_float), ("input_zero_point", C.c_int32), ("output_scale", C.c_float),
+                                         ("output_zero_point", C.c_int32)]
+
+
 class FcDesc(C.Structure):
     """``lce_hip_fc_desc``."""
     _fields_ = [(n, C.c_int32) for n in ("batch", "inputs", "outputs", "activation")]
@@ -204,6 +212,12 @@ def lib() -> C.CDLL:
         l.lce_hip_conv2d_i8_check.argtypes = [C.POINTER(Conv2dI8Desc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_conv2d_i8_prepare.argtypes = [C.POINTER(Conv2dI8Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_depthwise_conv2d_i8.argtypes = [C.POINTER(DepthwiseI8Desc)] + [C.c_void_p] * 6
+        l.lce_hip_depthwise_conv2d_i8_check.argtypes = [C.POINTER(DepthwiseI8Desc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_depthwise_conv2d_i8_prepare.argtypes = [C.POINTER(DepthwiseI8Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                          C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        l.lce_hip_depthwise_conv2d_i8_path.argtypes = [C.POINTER(DepthwiseI8Desc)] + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)]
+        l.lce_hip_depthwise_conv2d_i8_forced.argtypes = [C.POINTER(DepthwiseI8Desc), C.c_int32] + [C.c_void_p] * 6
         l.lce_hip_fully_connected_f32.argtypes = [C.POINTER(FcDesc)] + [C.c_void_p] * 5
         l.lce_hip_fully_connected_f32_check.argtypes = [C.POINTER(FcDesc)]
         l.lce_hip_softmax_f32.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -996,6 +1010,108 @@ def conv2d_i8(x, w, table, q_in, q_out, stride=1, padding=PADDING_SAME, activati
     ``(out or None, bits or None)``."""
     desc, shape = _conv2d_i8_check(x, w, table, q_in, q_out, stride, padding, activation, out, out_bits)
     return _run_windowed("conv2d_i8", "lce_hip_conv2d_i8", desc, shape, x, (w, table), out, out_bits, stream)
+
+
+def _depthwise_i8_filter(who, filter, depth_multiplier, cin=None):
+    """``filter`` is int8 [1, fh, fw, Cout] or [fh, fw, Cout], Cout = Cin x ``depth_multiplier`` (``cin``: the input's channels,
+    None: any): (Cout, fh, fw)."""
+    if not isinstance(depth_multiplier, (int, np.integer)) or depth_multiplier < 1:
+        raise ValueError("%s: depth_multiplier must be a positive int, got %r" % (who, depth_multiplier))
+    fs = tuple(int(v) for v in filter.shape)
+    bad = _dtype_name(filter) != "int8" or len(fs) not in (3, 4) or min(fs) < 1 or (len(fs) == 4 and fs[0] != 1)
+    if not bad:
+        bad = fs[-1] % int(depth_multiplier) != 0 if cin is None else fs[-1] != cin * int(depth_multiplier)
+    if bad:
+        want = "Cin x %d" % depth_multiplier if cin is None else str(cin * int(depth_multiplier))
+        raise ValueError("%s: filter must be int8 [1, fh, fw, %s] or [fh, fw, %s], got %s %r" % (who, want, want, filter.dtype, fs))
+    return fs[-1], fs[-3], fs[-2]
+
+
+def depthwise_conv2d_i8_prepare(filter, bias, filter_scales, q_in, q_out, depth_multiplier=1, activation=ACT_NONE):
+    """The constants of one quantized DEPTHWISE_CONV_2D for ``depthwise_conv2d_i8`` (``lce_hip_depthwise_conv2d_i8_prepare``, host
+    only).  ``filter``: int8 NumPy [1, fh, fw, Cout] (zero point 0).  ``bias``: int32 [Cout] or None.  ``filter_scales``: one
+    float or Cout of them.  ``q_in``, ``q_out``: (scale, zero_point) of the input and the output tensor.  Returns
+    ``(table, act_min, act_max)``: ``table`` is int32 [3, Cout] -- bias[o] (0 without a bias), and
+    QuantizeMultiplier(si * sw[o] / so)'s multiplier and exponent -- which ``depthwise_conv2d_i8`` takes; the activation range
+    is CalculateActivationRangeQuantized's at ``q_out``.  Raises ``LceHipError`` (ERR_UNSUPPORTED) where the reference's own int32
+    accumulator could overflow."""
+    who = "depthwise_conv2d_i8_prepare"
+    cout, fh, fw = _depthwise_i8_filter(who, filter, depth_multiplier)
+    si, zi, so, zo = _conv2d_i8_quantization(who, q_in, q_out)
+    _padding_activation_check(who, None, activation)
+    if bias is not None and (_dtype_name(bias) != "int32" or tuple(bias.shape) != (cout,)):
+        raise ValueError("%s: bias must be int32 [%d], got %s %r" % (who, cout, bias.dtype, tuple(bias.shape)))
+    scales = np.ascontiguousarray(np.atleast_1d(np.asarray(filter_scales, np.float32)))
+    if scales.ndim != 1 or scales.size not in (1, cout):
+        raise ValueError("%s: filter_scales must be 1 or %d scales, got shape %r" % (who, cout, scales.shape))
+    fh_ = np.ascontiguousarray(filter)
+    bh = None if bias is None else np.ascontiguousarray(bias)
+    # (the table depends on the filter's extents and the quantization alone: the window of this descriptor is the filter itself)
+    desc = DepthwiseI8Desc(1, fh, fw, cout // int(depth_multiplier), int(depth_multiplier), fh, fw, 1, 1, PADDING_VALID, int(activation),
+                           si, zi, so, zo)
+    table = np.zeros((3, cout), np.int32)
+    lo, hi = C.c_int32(), C.c_int32()
+    check(lib().lce_hip_depthwise_conv2d_i8_prepare(C.byref(desc), _host_ptr(fh_), None if bh is None else _host_ptr(bh),
+                                                    _host_ptr(scales), int(scales.size), _host_ptr(table), C.byref(lo), C.byref(hi)))
+    return table, lo.value, hi.value
+
+
+def _depthwise_i8_check(x, filter, table, q_in, q_out, stride, padding, depth_multiplier, activation, out, out_bits):
+    """Argument checks of ``depthwise_conv2d_i8`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.
+    Returns (DepthwiseI8Desc, output shape)."""
+    who = "depthwise_conv2d_i8"
+    _, b, h, wd, cin = _nhwc_check(who, x, ("int8",))
+    cout, fh, fw = _depthwise_i8_filter(who, filter, depth_multiplier, cin)
+    if _dtype_name(table) != "int32" or tuple(table.shape) != (3, cout):
+        raise ValueError("%s: table must be int32 [3, %d] (depthwise_conv2d_i8_prepare), got %s %r" % (who, cout, table.dtype,
+                                                                                                      tuple(table.shape)))
+    si, zi, so, zo = _conv2d_i8_quantization(who, q_in, q_out)
+    sh, sw = _pair(who, "stride", stride)
+    _padding_activation_check(who, padding, activation)
+    oh, ow = _window_output_hw(who, (h, wd), (fh, fw), (sh, sw), padding)
+    shape = (b, oh, ow, cout)
+    _check_outputs(who, None if out is True else out, None if out_bits is False else out_bits, "int8", shape)
+    return DepthwiseI8Desc(b, h, wd, cin, int(depth_multiplier), fh, fw, sh, sw, int(padding), int(activation), si, zi, so, zo), shape
+
+
+def depthwise_conv2d_i8(x, filter, table, q_in, q_out, stride=1, padding=PADDING_SAME, depth_multiplier=1, activation=ACT_NONE, out=True,
+                        out_bits=False, stream: int | None = None, path: int | None = None, report_path: bool = False):
+    """TFLite's builtin quantized DEPTHWISE_CONV_2D (the blur of an int8 QuickNet's transition, the depthwise convolution of its
+    stem) and the LceQuantize of its result, in one launch (``lce_hip_depthwise_conv2d_i8``).  ``x``: int8 NHWC on the device (or
+    NumPy: copied to cuda:0 and back).  ``filter``: int8 [1, fh, fw, Cout] (or [fh, fw, Cout]), Cout = Cin x
+    ``depth_multiplier``; output channel o reads input channel o // depth_multiplier.  ``table``: int32 [3, Cout] from
+    ``depthwise_conv2d_i8_prepare`` for the same filter, quantization and activation.  ``q_in``, ``q_out``: (scale, zero_point)
+    of input and output.  ``stride``: an int or (height, width).  ``padding``: ``PADDING_SAME`` / ``PADDING_VALID`` (taps in the
+    padding are skipped).  ``activation``: ``ACT_*``.  Integer arithmetic, exact bytes:
+    reference_integer_ops::DepthwiseConvPerChannel in the double-rounding build (include/lce_hip.h).  ``out``: True for a new
+    int8 tensor, a tensor to fill (it must not overlap an operand), False for none.  ``out_bits``: True for new int32
+    [B, OH, OW, ceil(Cout/32)] bits (value < output zero point), a tensor to fill, False for none.  ``path``: None for the
+    entry's own choice; 0 forces the row path and 1 the 16-byte path (``lce_hip_depthwise_conv2d_i8_forced``: for tests and
+    measurements; the bytes are the same).  Returns ``(out or None, bits or None)``, and with ``report_path`` a third value: 1
+    when the launch took the 16-byte path, else 0."""
+    import torch
+    who = "depthwise_conv2d_i8"
+    desc, shape = _depthwise_i8_check(x, filter, table, q_in, q_out, stride, padding, depth_multiplier, activation, out, out_bits)
+    if path not in (None, 0, 1):
+        raise ValueError("%s: path must be None, 0 or 1, got %r" % (who, path))
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x's")
+    xd, fd, td = on_dev(x), on_dev(filter), on_dev(table)
+    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if out is True else on_dev(out)
+    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
+    ptrs = [_dev_ptr(t) for t in (xd, fd, td, out_d, bits_d)]
+    took = C.c_int32(-1)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(_stream_or_current(stream, dev))
+        if path is None:
+            check(lib().lce_hip_depthwise_conv2d_i8_path(C.byref(desc), *ptrs, C.byref(took)))
+            check(lib().lce_hip_depthwise_conv2d_i8(C.byref(desc), *ptrs, st))
+        else:
+            check(lib().lce_hip_depthwise_conv2d_i8_forced(C.byref(desc), int(path), *ptrs, st))
+            took.value = int(path)
+    res = _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+    return (*res, int(took.value)) if report_path else res
 
 
 def _fully_connected_check(x, w, bias, activation, out):

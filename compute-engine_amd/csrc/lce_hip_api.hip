@@ -27,6 +27,7 @@
 #include "lce_kernels_conv2d_i8.h"   // (lce_tu_conv2d_i8.hip)
 #include "lce_kernels_head.h"        // (lce_tu_head.hip)
 #include "lce_kernels_head_i8.h"     // (lce_tu_head_i8.hip)
+#include "lce_kernels_depthwise_i8.h"   // (lce_tu_depthwise_i8.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -53,6 +54,7 @@
 #include "lce_tu_conv2d_i8.hip"
 #include "lce_tu_head.hip"
 #include "lce_tu_head_i8.hip"
+#include "lce_tu_depthwise_i8.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -1117,8 +1119,10 @@ lce_hip_status lce_hip_softmax_f32(size_t rows, size_t cols, float beta, const f
 // ------------------------------------------------------------------------------------
 // float DEPTHWISE_CONV_2D (lce_kernels_depthwise.h)
 // ------------------------------------------------------------------------------------
-lce_hip_status lce_hip_depthwise_conv2d_f32_check(const lce_hip_depthwise_desc* d, int32_t* out_height, int32_t* out_width) {
-  const char* who = "lce_hip_depthwise_conv2d_f32";
+}  // extern "C"
+namespace {
+// The descriptor checks the float and the int8 DEPTHWISE_CONV_2D share: every message is `who`'s own.
+lce_hip_status depthwise_desc_check(const char* who, const lce_hip_depthwise_desc* d, int32_t* out_height, int32_t* out_width) {
   if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
   if (d->batch <= 0 || d->in_height <= 0 || d->in_width <= 0 || d->channels_in <= 0)
     return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d, %d, %d]", who, (int)d->batch, (int)d->in_height,
@@ -1136,6 +1140,11 @@ lce_hip_status lce_hip_depthwise_conv2d_f32_check(const lce_hip_depthwise_desc* 
     return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: a filter of 2^31 or more elements (%d x %d x %llu) is not supported", who,
                 (int)d->filter_height, (int)d->filter_width, (unsigned long long)cout);
   return window_output(who, w, out_height, out_width);
+}
+}  // namespace
+extern "C" {
+lce_hip_status lce_hip_depthwise_conv2d_f32_check(const lce_hip_depthwise_desc* d, int32_t* out_height, int32_t* out_width) {
+  return depthwise_desc_check("lce_hip_depthwise_conv2d_f32", d, out_height, out_width);
 }
 
 lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* d, const float* in_dev, const float* filter_dev,
@@ -1275,7 +1284,8 @@ lce_hip_status conv2d_i8_desc_check(const char* who, const lce_hip_conv2d_i8_des
 }
 
 // The table of lce_hip_conv2d_i8_prepare for N output channels of K filter elements each (the FULLY_CONNECTED of the int8 head
-// is the 1x1 case: lce_hip_fully_connected_i8_prepare).  The descriptor has been checked.
+// is the 1x1 case: lce_hip_fully_connected_i8_prepare).  The descriptor has been checked.  Without a filter (the depthwise
+// entry, whose kernel skips the taps in the padding and subtracts zi itself: K = fh x fw) no zero point is folded: c[o] = bias[o].
 lce_hip_status conv2d_i8_table(const char* who, int64_t N, int64_t K, float si, int32_t zi, float so, const int8_t* filter_host,
                                const int32_t* bias_host, const float* filter_scales, int32_t n_scales, int32_t* table) {
   if (n_scales != 1 && (int64_t)n_scales != N)
@@ -1304,8 +1314,10 @@ lce_hip_status conv2d_i8_table(const char* who, int64_t N, int64_t K, float si, 
       return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: channel %lld: the accumulator bound %lld times 2^%d (the left shift of its multiplier %g) "
                   "exceeds 2^31 - 1", who, (long long)o, (long long)bound, (int)e, real);
     int64_t sum = 0;
-    const int8_t* w = filter_host + (uint64_t)o * (uint64_t)K;
-    for (int64_t k = 0; k < K; ++k) sum += w[k];
+    if (filter_host) {
+      const int8_t* w = filter_host + (uint64_t)o * (uint64_t)K;
+      for (int64_t k = 0; k < K; ++k) sum += w[k];
+    }
     // |zi * sum| <= 128 x 128 x K and |bias[o]| <= B, so |c| <= 128 x 128 x K + B <= 255 x 128 x K + B = bound <= 2^31 - 1:
     // the first bound already implies that c fits.  Checked all the same.
     const int64_t c = (bias_host ? (int64_t)bias_host[o] : 0ll) - (int64_t)zi * sum;
@@ -1596,6 +1608,129 @@ lce_hip_status lce_hip_dequantize_i8_f32(size_t n, float scale, int32_t zero_poi
   const int e = lce::launch_dequantize_i8_f32(a, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// int8 DEPTHWISE_CONV_2D (lce_kernels_depthwise_i8.h)
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+lce_hip_depthwise_desc depthwise_i8_window(const lce_hip_depthwise_i8_desc* d) {
+  return lce_hip_depthwise_desc{d->batch, d->in_height, d->in_width, d->channels_in, d->depth_multiplier, d->filter_height, d->filter_width,
+                                d->stride_height, d->stride_width, d->padding, d->activation};
+}
+
+// What lce_hip_depthwise_conv2d_i8_check refuses, with `who`'s messages.
+lce_hip_status depthwise_i8_desc_check(const char* who, const lce_hip_depthwise_i8_desc* d, int32_t* out_height, int32_t* out_width) {
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  const lce_hip_depthwise_desc w = depthwise_i8_window(d);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = depthwise_desc_check(who, &w, &oh, &ow)) return s;
+  if (lce_hip_status s = head_i8_quantization_check(who, "input", d->input_scale, d->input_zero_point)) return s;
+  if (lce_hip_status s = head_i8_quantization_check(who, "output", d->output_scale, d->output_zero_point)) return s;
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+
+// The launch of lce_hip_depthwise_conv2d_i8 and of its forced form.  `path`: -1 the entry's own choice, 0 the row path, 1 the
+// 16-byte path (refused where the operands do not qualify).  `took` (nullable) gets the path; with `launch` false nothing runs.
+lce_hip_status depthwise_i8_run(const char* who, const lce_hip_depthwise_i8_desc* d, int32_t path, const int8_t* in_dev, const int8_t* filter_dev,
+                                const int32_t* table_dev, int8_t* out_dev, int32_t* out_bits_dev, void* stream, int32_t* took, bool launch) {
+  if (lce_hip_status s = check_pointers(who, d, in_dev, /*has_filter=*/true, filter_dev, out_dev, out_bits_dev)) return s;
+  if (!table_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null table", who);
+  int32_t oh = 0, ow = 0;
+  if (lce_hip_status s = depthwise_i8_desc_check(who, d, &oh, &ow)) return s;
+  const uint64_t Cin = (uint64_t)d->channels_in, C = Cin * (uint64_t)d->depth_multiplier;
+  const uint64_t pixels = (uint64_t)d->batch * oh * ow, wpr = (C + 31) / 32;
+  const Span in(in_dev, (uint64_t)d->batch * d->in_height * d->in_width * Cin);
+  const Span filter(filter_dev, (uint64_t)d->filter_height * d->filter_width * C), table(table_dev, 3 * C * 4);
+  const Span out(out_dev, pixels * C), bits(out_bits_dev, pixels * wpr * 4);
+  // (the table stands where the float entry has its bias)
+  if (meet(out.lo, out.hi, table.lo, table.hi) || meet(bits.lo, bits.hi, table.lo, table.hi))
+    return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the table", who);
+  if (lce_hip_status s = check_operand_ranges(who, in, filter, Span(nullptr, 0), out, bits, /*float_operands=*/false)) return s;
+  if (table.lo % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: table_dev must be 4-byte aligned", who);
+  bool vec = d->depth_multiplier == 1 && C % 16 == 0 && (in.lo | filter.lo | table.lo | out.lo) % 16 == 0;
+  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
+  if (path != -1 && path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
+  if (path == 1 && !vec)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the 16-byte path needs depth_multiplier 1, channels %% 16 == 0 (%% 32 with bits) and 16-byte aligned "
+                "input, filter, table and output", who);
+  if (path == 0) vec = false;
+  if (took) *took = vec ? 1 : 0;
+  if (!launch) return LCE_HIP_OK;
+  if (lce_hip_status s = require_device()) return s;
+  lce::DepthwiseI8Args a;
+  memset(&a, 0, sizeof a);
+  lce::PoolArgs& p = a.P;
+  p.in = in_dev; p.out = out_dev; p.bits = (uint32_t*)out_bits_dev;
+  a.filter = filter_dev; a.table = table_dev;
+  a.zi = d->input_zero_point;
+  a.channels_in = (uint32_t)Cin;
+  a.div_multiplier = lce::make_fastdiv((uint32_t)d->depth_multiplier);
+  p.H = d->in_height; p.W = d->in_width; p.OH = oh; p.OW = ow;
+  p.fh = d->filter_height; p.fw = d->filter_width; p.sh = d->stride_height; p.sw = d->stride_width;
+  p.ph = same_pad_before(oh, d->stride_height, d->filter_height, d->in_height);
+  p.pw = same_pad_before(ow, d->stride_width, d->filter_width, d->in_width);
+  p.channels = (uint32_t)C;
+  p.wpr = (uint32_t)wpr;
+  p.per_pixel = (uint32_t)(vec ? C / 16 : (C + 63) / 64);
+  // the pools' rule (lce_kernels_pool.h): non-temporal window loads only where windows do not overlap
+  p.stream_loads = d->stride_height >= d->filter_height && d->stride_width >= d->filter_width ? 1u : 0u;
+  p.total = pixels * p.per_pixel;
+  quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, &p.qlo, &p.qhi);
+  p.zero_point = d->output_zero_point;
+  p.div_ow = lce::make_fastdiv((uint32_t)ow);
+  p.div_oh = lce::make_fastdiv((uint32_t)oh);
+  if (vec) pool_vec_steps(p);
+  const int e = lce::launch_depthwise_i8(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+}  // namespace
+extern "C" {
+
+lce_hip_status lce_hip_depthwise_conv2d_i8_check(const lce_hip_depthwise_i8_desc* d, int32_t* out_height, int32_t* out_width) {
+  return depthwise_i8_desc_check("lce_hip_depthwise_conv2d_i8", d, out_height, out_width);
+}
+
+lce_hip_status lce_hip_depthwise_conv2d_i8_prepare(const lce_hip_depthwise_i8_desc* d, const int8_t* filter_host, const int32_t* bias_host,
+                                                   const float* filter_scales, int32_t n_scales, int32_t* table, int32_t* act_min,
+                                                   int32_t* act_max) {
+  const char* who = "lce_hip_depthwise_conv2d_i8_prepare";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!filter_host) return fail(LCE_HIP_ERR_INVALID, "%s: null filter", who);
+  if (!filter_scales) return fail(LCE_HIP_ERR_INVALID, "%s: null filter scales", who);
+  if (!table || !act_min || !act_max) return fail(LCE_HIP_ERR_INVALID, "%s: null result", who);
+  if (lce_hip_status s = depthwise_i8_desc_check(who, d, nullptr, nullptr)) return s;
+  // an output element sums K = fh x fw products; the kernel subtracts zi itself and skips the padding, so nothing is folded
+  const int64_t N = (int64_t)d->channels_in * d->depth_multiplier, K = (int64_t)d->filter_height * d->filter_width;       // both < 2^31
+  if (lce_hip_status s = conv2d_i8_table(who, N, K, d->input_scale, d->input_zero_point, d->output_scale, /*filter_host=*/nullptr, bias_host,
+                                         filter_scales, n_scales, table))
+    return s;
+  quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, act_min, act_max);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_depthwise_conv2d_i8(const lce_hip_depthwise_i8_desc* d, const int8_t* in_dev, const int8_t* filter_dev,
+                                           const int32_t* table_dev, int8_t* out_dev, int32_t* out_bits_dev, void* stream) {
+  return depthwise_i8_run("lce_hip_depthwise_conv2d_i8", d, -1, in_dev, filter_dev, table_dev, out_dev, out_bits_dev, stream, nullptr, true);
+}
+
+lce_hip_status lce_hip_depthwise_conv2d_i8_path(const lce_hip_depthwise_i8_desc* d, const int8_t* in_dev, const int8_t* filter_dev,
+                                                const int32_t* table_dev, const int8_t* out_dev, const int32_t* out_bits_dev, int32_t* path) {
+  const char* who = "lce_hip_depthwise_conv2d_i8_path";
+  if (!path) return fail(LCE_HIP_ERR_INVALID, "%s: null path", who);
+  return depthwise_i8_run(who, d, -1, in_dev, filter_dev, table_dev, (int8_t*)out_dev, (int32_t*)out_bits_dev, nullptr, path, false);
+}
+
+lce_hip_status lce_hip_depthwise_conv2d_i8_forced(const lce_hip_depthwise_i8_desc* d, int32_t path, const int8_t* in_dev,
+                                                  const int8_t* filter_dev, const int32_t* table_dev, int8_t* out_dev, int32_t* out_bits_dev,
+                                                  void* stream) {
+  const char* who = "lce_hip_depthwise_conv2d_i8_forced";
+  if (path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
+  return depthwise_i8_run(who, d, path, in_dev, filter_dev, table_dev, out_dev, out_bits_dev, stream, nullptr, true);
 }
 
 // ------------------------------------------------------------------------------------

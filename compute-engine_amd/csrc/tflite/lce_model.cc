@@ -22,15 +22,15 @@ struct lce_tflite_section {
 };
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
-       kAbsorbedConvI8, kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
+       kAbsorbedConvI8, kAbsorbedDepthwiseI8, kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
        kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
-enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u };
+enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
-  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize")
+  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize", "depthwise_i8")
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
@@ -41,7 +41,7 @@ struct lce_tflite_model {
   struct DevBuf { void* ptr = nullptr; size_t bytes = 0; };
   std::map<int32_t, DevBuf> scratch;                                    // intermediate tensors of a section, grow-only
   std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
-  std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D / FULLY_CONNECTED operator: its prepare's table, uploaded once
+  std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED operator: its prepare's table, uploaded once
   std::map<int32_t, std::vector<int32_t>> host_tables;                  // ... as Partition() prepared it; dropped once it is on the device
   // What one run launched.  A recorded graph keeps the record of its recording, so a replay reports the same numbers.
   struct RunStats {
@@ -457,6 +457,87 @@ bool ConvI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return lce_hip_conv2d_i8_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
 }
 
+// lce_hip_depthwise_i8_desc of a builtin int8 DEPTHWISE_CONV_2D at `batch` images, from its options and the FILE's input, filter and
+// output tensors.
+lce_hip_depthwise_i8_desc DepthwiseI8Desc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  lce_hip_depthwise_i8_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = batch; d.in_height = in.shape[1]; d.in_width = in.shape[2]; d.channels_in = in.shape[3];
+  d.depth_multiplier = o.depth_multiplier;
+  d.filter_height = flt.shape[1]; d.filter_width = flt.shape[2];
+  d.stride_height = o.pool_stride_h; d.stride_width = o.pool_stride_w;
+  d.padding = o.pool_padding;
+  d.activation = o.activation;
+  d.input_scale = in.scale; d.input_zero_point = (int32_t)in.zero_point;
+  d.output_scale = out.scale; d.output_zero_point = (int32_t)out.zero_point;
+  return d;
+}
+
+// lce_hip_depthwise_conv2d_i8_prepare on the FILE's constants of int8 DEPTHWISE_CONV_2D `o` (the candidate has checked their types
+// and sizes).
+lce_hip_status DepthwiseI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_hip_depthwise_i8_desc d = DepthwiseI8Desc(M, o, M.tensors[o.inputs[0]].shape[0]);
+  const bool has_bias = o.inputs.size() == 3 && o.inputs[2] >= 0;
+  // (flatbuffer vectors are only guaranteed 4-byte aligned, which is what int32 and float need)
+  std::vector<int32_t> bias;
+  if (has_bias) {
+    bias.resize((size_t)flt.shape[3]);
+    memcpy(bias.data(), M.tensors[o.inputs[2]].data, bias.size() * 4);
+  }
+  table->assign((size_t)flt.shape[3] * 3, 0);
+  int32_t lo = 0, hi = 0;
+  return lce_hip_depthwise_conv2d_i8_prepare(&d, (const int8_t*)flt.data, has_bias ? bias.data() : nullptr, flt.scales.data(),
+                                             (int32_t)flt.scales.size(), table->data(), &lo, &hi);
+}
+
+// The static half of "a builtin DEPTHWISE_CONV_2D that a section may run" ("depthwise_i8" of lce_tflite_model_open_passes): the
+// quantized blur of QuickNet's transition and the depthwise convolution of its stem.  The rules of ConvI8Candidate with these
+// replacements: the depthwise options table present; the filter a constant int8 [1, fh, fw, Cout] whose byte count matches; a depth
+// multiplier >= 1 with Cout == Cin x multiplier == the output's channels; 1 or Cout filter scales -- with more than one,
+// quantized_dimension 3; the bias absent or a constant int32 [Cout]; and the declared output height and width what the padding rule
+// gives.  A dilation, hybrid (float data, int8 filter) weights, a filter zero point other than 0, scales along another dimension or
+// a float bias leave it with the host.  Partition() then asks lce_hip_depthwise_conv2d_i8_prepare ONCE whether it accepts the
+// file's constants and keeps the table for the run; it also decides the other half -- when the operator becomes ready.
+bool DepthwiseI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinDepthwiseConv2d || !o.has_depthwise_options) return false;
+  if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorInt8 || flt.type != lce_tfl::kTensorInt8 || out.type != lce_tfl::kTensorInt8) return false;
+  if (!StreamedImages(in, out)) return false;
+  for (const lce_tfl::Tensor* t : {&in, &out})
+    if (!t->quantized || t->scales.size() != 1 || t->zero_points.size() > 1 || t->zero_point < -128 || t->zero_point > 127) return false;
+  if (!flt.data || flt.shape.size() != 4) return false;
+  uint64_t elems = (uint64_t)flt.bytes;
+  for (int32_t extent : flt.shape) {
+    if (extent <= 0 || elems % (uint64_t)extent != 0) return false;
+    elems /= (uint64_t)extent;
+  }
+  if (elems != 1 || flt.shape[0] != 1) return false;
+  const int64_t cout = flt.shape[3];
+  if (o.depth_multiplier < 1 || (int64_t)in.shape[3] * o.depth_multiplier != cout || out.shape[3] != cout) return false;
+  for (int64_t z : flt.zero_points)
+    if (z != 0) return false;
+  const size_t n_scales = flt.scales.size();
+  if (n_scales != 1 && n_scales != (size_t)cout) return false;
+  if (n_scales > 1 && flt.quantized_dimension != 3) return false;
+  if (o.inputs.size() == 3 && o.inputs[2] >= 0) {
+    const lce_tfl::Tensor& bias = M.tensors[o.inputs[2]];
+    if (bias.type != lce_tfl::kTensorInt32 || !bias.data || bias.shape.size() != 1 || bias.shape[0] != cout ||
+        (uint64_t)bias.bytes != (uint64_t)cout * 4u)
+      return false;
+  }
+  if (!ConvOptions(o)) return false;
+  const lce_hip_depthwise_i8_desc d = DepthwiseI8Desc(M, o, in.shape[0]);
+  int32_t oh = 0, ow = 0;
+  return lce_hip_depthwise_conv2d_i8_check(&d, &oh, &ow) == LCE_HIP_OK && oh == out.shape[1] && ow == out.shape[2];
+}
+
 
 // ---- the classifier head (lce_tflite_model_open_passes, "head") ----
 // A head tensor as the section walker carries it: a rank-4 tensor as it is, a rank-2 tensor [b, C] as [b, 1, 1, C]; the extents
@@ -747,6 +828,12 @@ void lce_tflite_model::Partition() {
       if (ConvI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
       else candidate[i] = 0;
     }
+    // ... an int8 DEPTHWISE_CONV_2D constants lce_hip_depthwise_conv2d_i8_prepare accepts
+    if (candidate[i] == kAbsorbedDepthwiseI8) {
+      std::vector<int32_t> table;
+      if (DepthwiseI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
+      else candidate[i] = 0;
+    }
     // ... and an int8 FULLY_CONNECTED constants lce_hip_fully_connected_i8_prepare accepts
     if (candidate[i] == kAbsorbedFullyConnectedI8) {
       std::vector<int32_t> table;
@@ -914,7 +1001,8 @@ lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, co
       {"conv1x1", 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1},     {"depthwise", 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE},
       {"conv2d", 1, LCE_TFLITE_SECTIONS_EXT_CONV2D},       {"stem", 1, LCE_TFLITE_SECTIONS_EXT_STEM},
       {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8},
-      {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize}};
+      {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize},
+      {"depthwise_i8", 2, kInternalDepthwiseI8}};
   uint32_t words[3] = {0u, 0u, 0u};
   std::string refusal;
   if (!passes) refusal = "null passes";
@@ -1637,6 +1725,21 @@ struct Walk {
         });
   }
 
+  // An absorbed int8 DEPTHWISE_CONV_2D ("depthwise_i8" of lce_tflite_model_open_passes) as ONE lce_hip_depthwise_conv2d_i8 launch; its
+  // table is uploaded once per model, as the int8 CONV_2D's.
+  lce_hip_status DepthwiseI8(int32_t i) {
+    const lce_tfl::Operator& op = model->m.operators[i];
+    const lce_hip_depthwise_i8_desc d = DepthwiseI8Desc(model->m, op, batch);
+    return StreamingPass(
+        i, kAbsorbedDepthwiseI8, "an int8 DEPTHWISE_CONV_2D", lce_tfl::kTensorInt8, model->m.tensors[op.inputs[1]].shape[3],
+        [&](int32_t* h, int32_t* w) { return lce_hip_depthwise_conv2d_i8_check(&d, h, w); },
+        [&](const void* x, const float* filter, const float*, void* out, int32_t* bits) -> lce_hip_status {
+          const int32_t* table = nullptr;
+          if (lce_hip_status s = TableOnDevice(i, "an int8 DEPTHWISE_CONV_2D", &table)) return s;
+          return lce_hip_depthwise_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, table, (int8_t*)out, bits, stream);
+        });
+  }
+
   // ---- the classifier head ("head" of lce_tflite_model_open_passes).  Rank-2 tensors are carried as [batch, 1, 1, C]. ----
   // An absorbed head operator `i` that streams ONE input of `in_type` and makes ONE output of shape and type `os`, as ONE launch
   // of pass `kind`.  `launch(in, weights, bias, out)` is the entry; its pointers are typed float and an int8 pass casts them
@@ -1918,6 +2021,8 @@ const FusedPass kPasses[kAbsorbedCount - 1] = {
     {kAbsorbedConv2d, 1, LCE_TFLITE_SECTIONS_EXT_CONV2D, Conv2dCandidate, &Walk::Conv2d},
     // the quantized convolution: an internal flag (lce_tflite_model_open_passes, "conv2d_i8"); no float predicate takes an int8 tensor
     {kAbsorbedConvI8, 2, kInternalConvI8, ConvI8Candidate, &Walk::ConvI8},
+    // the quantized depthwise convolution ("depthwise_i8"): DepthwiseCandidate above takes float tensors only
+    {kAbsorbedDepthwiseI8, 2, kInternalDepthwiseI8, DepthwiseI8Candidate, &Walk::DepthwiseI8},
     // the classifier head: one internal flag enables the three rows (lce_tflite_model_open_passes, "head")
     {kAbsorbedMean, 2, kInternalHead, MeanCandidate, &Walk::Mean},
     {kAbsorbedFullyConnected, 2, kInternalHead, FullyConnectedCandidate, &Walk::FullyConnected},
@@ -2054,6 +2159,10 @@ void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, i
 }
 void lce_tflite_model_conv_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
   PassStats(model, kAbsorbedConvI8, launches, quantize_folded);
+}
+
+void lce_tflite_model_depthwise_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  PassStats(model, kAbsorbedDepthwiseI8, launches, quantize_folded);
 }
 
 void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {

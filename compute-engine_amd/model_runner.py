@@ -50,6 +50,10 @@ MEAN, FULLY_CONNECTED, SOFTMAX on int8 tensors -- and the builtin QUANTIZE / DEQ
 (``lce_hip_mean_i8``, ``lce_hip_fully_connected_i8``, ``lce_hip_softmax_i8``, ``lce_hip_quantize_f32_i8``,
 ``lce_hip_dequantize_i8_f32``): with every keyword an int8-converted network is ONE section too, and ``predict`` takes float
 images and returns float ``[N, classes]`` on a file with a float interface, int8 on a file with an int8 interface.
+With ``depthwise_i8_sections=True`` (the name ``depthwise_i8``) the quantized DEPTHWISE_CONV_2D -- QuickNet's blur and the depthwise
+convolution of its stem -- joins them (``lce_hip_depthwise_conv2d_i8``: TFLite's integer arithmetic byte for byte), so an int8
+QuickNet is ONE section from the float image to the float probabilities (profiles/depthwise_i8: 29 / 17 / 11 us on its three
+transitions at batch 256, 53 / 29 / 16 us for the float entry).
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -134,12 +138,13 @@ _SECTION_KEYWORDS = (
 _PASS_NAMES = {"elementwise_sections": "elementwise", "int8_add_sections": "int8_add", "concat_sections": "concat",
                "pool_sections": "pool", "conv1x1_sections": "conv1x1", "depthwise_sections": "depthwise",
                "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head", "conv2d_i8_sections": "conv2d_i8",
-               "head_i8_sections": "head_i8", "quantize_sections": "quantize"}
+               "head_i8_sections": "head_i8", "quantize_sections": "quantize", "depthwise_i8_sections": "depthwise_i8"}
 # the keywords whose names only ``lce_tflite_model_open_passes`` knows, in the order their names are passed
-_NAMED_ONLY = ("head_sections", "conv2d_i8_sections", "head_i8_sections", "quantize_sections")
+_NAMED_ONLY = ("head_sections", "conv2d_i8_sections", "head_i8_sections", "quantize_sections", "depthwise_i8_sections")
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
 # ``lce_tflite_model_<pass>_stats``: the counters each reports
-_PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2}
+_PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2,
+               "depthwise_i8": 2}
 
 
 class Section:
@@ -254,7 +259,7 @@ class LceModel:
                  int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
                  conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
                  stem_sections: bool = False, head_sections: bool = False, conv2d_i8_sections: bool = False,
-                 head_i8_sections: bool = False, quantize_sections: bool = False):
+                 head_i8_sections: bool = False, quantize_sections: bool = False, depthwise_i8_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -275,7 +280,9 @@ class LceModel:
         profiles/conv2d_i8).  ``head_i8_sections``: the int8 classifier head (MEAN, FULLY_CONNECTED, SOFTMAX on int8 tensors)
         joins them (``lce_hip_mean_i8``, ``lce_hip_fully_connected_i8``, ``lce_hip_softmax_i8``; the name ``head_i8``).
         ``quantize_sections``: the builtin QUANTIZE float32 -> int8 and DEQUANTIZE int8 -> float32 join them (the name
-        ``quantize``).  With every keyword an int8-converted network is ONE section from the image to the probabilities."""
+        ``quantize``).  ``depthwise_i8_sections``: the quantized DEPTHWISE_CONV_2D of an int8-converted network -- QuickNet's blur
+        and the depthwise convolution of its stem -- joins them (``lce_hip_depthwise_conv2d_i8``; the name ``depthwise_i8``).
+        With every keyword an int8-converted network, QuickNet included, is ONE section from the image to the probabilities."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -293,6 +300,7 @@ class LceModel:
         self.conv2d_i8_sections = bool(conv2d_i8_sections)
         self.head_i8_sections = bool(head_i8_sections)
         self.quantize_sections = bool(quantize_sections)
+        self.depthwise_i8_sections = bool(depthwise_i8_sections)
         err = C.create_string_buffer(256)
         if any(getattr(self, keyword) for keyword in _NAMED_ONLY):
             names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]]
@@ -410,6 +418,10 @@ class LceModel:
         """(lce_hip_conv2d_i8 launches, LceQuantize launches they absorbed) of the last run."""
         return self._pass_stats("conv_i8")
 
+    def depthwise_i8_stats(self):
+        """(lce_hip_depthwise_conv2d_i8 launches, LceQuantize launches they absorbed) of the last run."""
+        return self._pass_stats("depthwise_i8")
+
     def head_stats(self):
         """(MEAN launches, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches) of the last run."""
         v = [C.c_int32() for _ in range(3)]
@@ -460,9 +472,10 @@ class Interpreter:
                  concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
                  depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False,
                  head_sections: bool = False, conv2d_i8_sections: bool = False, head_i8_sections: bool = False,
-                 quantize_sections: bool = False):
+                 quantize_sections: bool = False, depthwise_i8_sections: bool = False):
         """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
-        ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``, ``head_i8_sections``, ``quantize_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+        ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``, ``head_i8_sections``, ``quantize_sections``,
+        ``depthwise_i8_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
@@ -471,7 +484,7 @@ class Interpreter:
                                     depthwise_sections=depthwise_sections, conv2d_sections=conv2d_sections,
                                     stem_sections=stem_sections, head_sections=head_sections,
                                     conv2d_i8_sections=conv2d_i8_sections, head_i8_sections=head_i8_sections,
-                                    quantize_sections=quantize_sections))
+                                    quantize_sections=quantize_sections, depthwise_i8_sections=depthwise_i8_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED

@@ -450,6 +450,73 @@ lce_hip_status lce_hip_conv2d_i8(const lce_hip_conv2d_i8_desc* desc, const int8_
                                  int32_t* out_bits_dev /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The int8 DEPTHWISE_CONV_2D (TFLite builtin DEPTHWISE_CONV_2D, quantized) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* An int8-converted QuickNet keeps two quantized depthwise convolutions: the fixed 3x3 / 2 blur ([1 2 1] x [1 2 1] / 16) of every
+ * transition block and a depthwise 3x3 / 2 in the stem.  lce_hip_depthwise_conv2d_i8 is TFLite's
+ * reference_integer_ops::DepthwiseConvPerChannel in its default (double-rounding) build, byte for byte.  The geometry is exactly
+ * lce_hip_depthwise_conv2d_f32's.  Input: NHWC int8 [batch, in_height, in_width, channels_in] with quantization (input_scale,
+ * input_zero_point) = (si, zi).  Filter: int8 in the file's own layout [1, filter_height, filter_width, Cout], Cout =
+ * channels_in x depth_multiplier (= m), with zero point 0 and scales sw[o], one per output channel or a single one that stands
+ * for all.  Output channel o reads input channel o / m.  Bias: optional int32 [Cout].  Output: NHWC int8 [batch, out_height,
+ * out_width, Cout] with (output_scale, output_zero_point) = (so, zo); extents and padding are lce_hip_pool2d's (SAME or VALID,
+ * pad_before = total / 2).  The dilation is 1.  Per output element:
+ *   acc = sum over IN-BOUNDS taps (fy, fx) of (x[iy][ix][o / m] - zi) * w[fy][fx][o]       exact, int32; taps in the padding are SKIPPED
+ *                                                                                          (not read as 0), the filter index is the unclipped one
+ *   acc += bias[o]                                                                         when there is a bias
+ *   (m[o], e[o]) = QuantizeMultiplier((double)si * (double)sw[o] / (double)so)
+ *   acc = RoundingDivideByPOT(SaturatingRoundingDoublingHighMul(acc * 2^max(e,0), m), max(-e,0))   as lce_hip_add_int8 states the two
+ *   v   = min(max(acc + zo, act_min), act_max)      CalculateActivationRangeQuantized at (so, zo): what lce_hip_add_int8_prepare reports
+ *   bit = v < zo                                    as lce_hip_pool2d's int8 bits: LSB first, ceil(Cout/32) words per pixel, padding bits 0
+ * QuantizeMultiplier, the bounds below and the activation range are the routines lce_hip_conv2d_i8_prepare uses.
+ *
+ * lce_hip_depthwise_conv2d_i8_check: the descriptor checks alone and the output extents (nullable).  Host only.  It refuses
+ *   what lce_hip_depthwise_conv2d_f32_check refuses of the geometry (with this entry's name in the message), a scale that is not
+ *   finite and positive and a zero point outside [-128, 127] (LCE_HIP_ERR_INVALID).
+ * lce_hip_depthwise_conv2d_i8_prepare: host only.  From the constants of the file -- the filter (read for nothing but its
+ *   presence: the kernel subtracts zi itself), the bias (nullable), `n_scales` (1 or Cout) filter scales -- the table int32
+ *   [3][Cout] = bias[o] (0 without a bias), m[o], e[o], which the caller uploads once, and the activation range.
+ *   LCE_HIP_ERR_UNSUPPORTED, with a message that names the channel: with K = filter_height x filter_width and B = max |bias|,
+ *   255 x 128 x K + B > 2^31 - 1 (the reference's own accumulator could overflow); for a channel with e > 0, that bound times
+ *   2^e > 2^31 - 1.  LCE_HIP_ERR_INVALID: a NULL pointer (the bias excepted), a filter scale that is not finite and positive,
+ *   n_scales neither 1 nor Cout, and what the check refuses.
+ * lce_hip_depthwise_conv2d_i8: ONE launch.  `table_dev`: prepare's table on the device.  `out_dev` (nullable) gets the int8
+ *   result, `out_bits_dev` (nullable) its LceQuantize at zo.  Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc,
+ *   input, filter or table, both outputs NULL, what the check refuses, an output that overlaps the input, the filter, the table
+ *   or the other output, an out_bits_dev or table_dev that is not 4-byte aligned.  The int8 pointers need no alignment
+ *   (depth_multiplier 1 with Cout % 16 == 0 and 16-byte aligned input, filter, table and output takes a 16-byte path; with bits
+ *   it also needs Cout % 32 == 0); the byte counts are unbounded (64-bit offsets beyond the window arithmetic).  Asynchronous on
+ *   `stream`, capturable in a HIP graph, allocates nothing and copies nothing between host and device.
+ * lce_hip_depthwise_conv2d_i8_path reports the path that launch takes for these operands (1: the 16-byte path, 0: the row path;
+ *   host only, nothing runs).  lce_hip_depthwise_conv2d_i8_forced runs a given path -- for tests and measurements; the row path
+ *   serves every operand, the 16-byte path is refused where the operands do not qualify.  Both give the same bytes. */
+typedef struct lce_hip_depthwise_i8_desc {
+  int32_t batch, in_height, in_width, channels_in, depth_multiplier;
+  int32_t filter_height, filter_width, stride_height, stride_width;
+  int32_t padding;      /* lce_hip_padding: SAME or VALID */
+  int32_t activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+  float input_scale;
+  int32_t input_zero_point;
+  float output_scale;
+  int32_t output_zero_point;
+} lce_hip_depthwise_i8_desc;
+lce_hip_status lce_hip_depthwise_conv2d_i8_check(const lce_hip_depthwise_i8_desc* desc, int32_t* out_height, int32_t* out_width);
+lce_hip_status lce_hip_depthwise_conv2d_i8_prepare(const lce_hip_depthwise_i8_desc* desc, const int8_t* filter_host /* [1][fh][fw][Cout] */,
+                                                   const int32_t* bias_host /* nullable */, const float* filter_scales,
+                                                   int32_t n_scales /* 1 or Cout */, int32_t* table /* [3][Cout] */, int32_t* act_min,
+                                                   int32_t* act_max);
+lce_hip_status lce_hip_depthwise_conv2d_i8(const lce_hip_depthwise_i8_desc* desc, const int8_t* in_dev,
+                                           const int8_t* filter_dev /* [1][fh][fw][Cout] */, const int32_t* table_dev /* [3][Cout] */,
+                                           int8_t* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+lce_hip_status lce_hip_depthwise_conv2d_i8_path(const lce_hip_depthwise_i8_desc* desc, const int8_t* in_dev, const int8_t* filter_dev,
+                                                const int32_t* table_dev, const int8_t* out_dev /* nullable */,
+                                                const int32_t* out_bits_dev /* nullable */, int32_t* path);
+lce_hip_status lce_hip_depthwise_conv2d_i8_forced(const lce_hip_depthwise_i8_desc* desc, int32_t path /* 0: rows, 1: 16-byte */,
+                                                  const int8_t* in_dev, const int8_t* filter_dev, const int32_t* table_dev,
+                                                  int8_t* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The float classifier head (TFLite builtin MEAN, FULLY_CONNECTED, SOFTMAX)
  * ---------------------------------------------------------------------------------- */
 

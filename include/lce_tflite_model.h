@@ -163,7 +163,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
                                              size_t err_len);
 
 /* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
- *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize
+ *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize, depthwise_i8
  * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
  * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
  * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
@@ -205,7 +205,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   any enabled opt-in.  lce_tflite_model_run_section runs it as ONE lce_hip_conv2d_i8 launch -- TFLite's integer arithmetic
  *   byte for byte -- whose table is prepared and uploaded once per model beside the filter; a following LceQuantize folds into
  *   the launch's bits.  With int8_add, pool and stem an int8 Bi-RealNet-style block with its downsampling shortcut, and an int8
- *   stem with the binary layer behind it, are one section each.  Not this name's: int8 DEPTHWISE_CONV_2D (the host's), the
+ *   stem with the binary layer behind it, are one section each.  Not this name's: int8 DEPTHWISE_CONV_2D (depthwise_i8, below), the
  *   int8 head and QUANTIZE / DEQUANTIZE (head_i8 and quantize, below).  Kernel time at batch 256 against the float entry at the same shape: 0.80 of it on the
  *   3x3 / 2 stem, 0.41 on the 7x7 / 2 stem, 0.57 on the 1x1 shortcut (profiles/conv2d_i8).
  *   head_i8: the int8 classifier head of an int8-converted network joins the sections, queued as `head` queues the float one; no
@@ -228,7 +228,22 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   epoch in which they become ready, and `stem` applies to a QUANTIZE at the graph's input as to any enabled opt-in.  ONE
  *   lce_hip_quantize_f32_i8 / lce_hip_dequantize_i8_f32 launch each.  A QUANTIZE with an int8 input (a requantization) stays with
  *   the host.  With every name an int8-converted network with a float interface is ONE section from the float image to the
- *   float probabilities.  Still the host's: int8 DEPTHWISE_CONV_2D, RESHAPE and the three-layer heads, LOGISTIC. */
+ *   float probabilities, provided it holds no depthwise convolution (depthwise_i8, next).
+ *   depthwise_i8: the quantized builtin DEPTHWISE_CONV_2D (4) of an int8-converted network -- the fixed 3x3 / 2 blur of each of
+ *   QuickNet's transitions, the depthwise 3x3 / 2 of its stem -- joins the sections; no other entry can ask for it, no bit and no
+ *   struct size enables it, and `depthwise` takes float tensors only, so a float file's partition is unchanged.  It qualifies
+ *   under the rules of conv2d_i8 with these replacements: the DepthwiseConv2DOptions table is present; the filter is a constant
+ *   int8 [1, fh, fw, Cout] with data in the file whose byte count matches; depth_multiplier >= 1 and Cout == Cin x
+ *   depth_multiplier == the output's channels; 1 or Cout filter scales (with more than one, quantized_dimension 3); the declared
+ *   output height and width are what the padding rule gives; and lce_hip_depthwise_conv2d_i8_check accepts the descriptor and
+ *   lce_hip_depthwise_conv2d_i8_prepare the file's constants.  A dilation, hybrid weights, a filter zero point, scales along
+ *   another dimension, a float bias and a missing options table leave it with the host, as before.  It joins the epoch in which
+ *   it becomes ready, and `stem` applies to it.  lce_tflite_model_run_section runs it as ONE lce_hip_depthwise_conv2d_i8 launch
+ *   -- TFLite's integer arithmetic byte for byte -- whose filter and prepared table are uploaded once per model; a following
+ *   LceQuantize folds into the launch's bits, and the int8 tensor is written only when something else reads it or the section
+ *   delivers it.  With every name an int8 QuickNet with a float interface is ONE section from the float image to the float
+ *   probabilities.  Still the host's: dilated, hybrid, uint8 or int16 depthwise convolutions, RESHAPE and the three-layer heads,
+ *   LOGISTIC. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -375,6 +390,9 @@ void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, i
 /* The LAST run's lce_hip_conv2d_i8 launches ("conv2d_i8" of lce_tflite_model_open_passes): launches (one per absorbed int8
  * CONV_2D) and the LceQuantize launches folded into them.  Nullable outputs. */
 void lce_tflite_model_conv_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's lce_hip_depthwise_conv2d_i8 launches ("depthwise_i8" of lce_tflite_model_open_passes): launches (one per
+ * absorbed int8 DEPTHWISE_CONV_2D) and the LceQuantize launches folded into them.  Nullable outputs. */
+void lce_tflite_model_depthwise_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
 /* The LAST run's launches for the classifier head ("head" of lce_tflite_model_open_passes): lce_hip_pool2d launches that ran a
  * MEAN, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches.  Nullable outputs. */
 void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
