@@ -480,4 +480,25 @@ const char* hostsim_plan_step(void* plan, const char* options, int max_batch) {
   return line.c_str();
 }
 
+// The grid and the run constants of a launch of `batch` images on the plan as hostsim_plan_step last selected it (batch below the
+// planned launch: a slice of run_host, the last chunk of a batch): for tests/test_launch_geometry_host.py, which checks that every
+// segment / image of such a launch belongs to exactly one block.
+// out[0..7] = family (1 weight-stationary, 2 weight-streaming, 0 neither), grid x, S, SPB, GSTR, G0M, flat, images per group
+int hostsim_plan_launch(void* plan, int batch, int32_t* out) {
+  const HostPlan& h = *(HostPlan*)plan;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (!h.use_mfma || batch < 1) return 1;
+  if (h.use_wstream) {
+    const WsArgs G = make_ws_args(h, batch);
+    out[0] = 2; out[1] = G.GROUPS * G.PARTS; out[2] = G.GROUPS; out[3] = G.PARTS; out[7] = G.IPB;
+    return 0;
+  }
+  if (h.use_stream) {
+    const StreamArgs G = make_stream_args(h, batch);
+    out[0] = 1; out[1] = G.GX; out[2] = G.S; out[3] = G.SPB; out[4] = G.GSTR; out[5] = G.G0M; out[6] = G.flat;
+    return 0;
+  }
+  return 1;
+}
+
 }  // extern "C"

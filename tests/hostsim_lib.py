@@ -71,19 +71,22 @@ DEFAULT_OPTIONS = {"stream_interleave": 0}
 
 def bconv2d(spec: O.ConvSpec, dst_type: int, inp, filt, post_mul=None, post_bias=None,
             thresholds=None, out_scale=1.0, out_zero_point=0, kernel="auto", tile=(0, 0),
-            max_batch=0, engine="valu", sign_words=None, options=None):
+            max_batch=0, engine="valu", sign_words=None, options=None, out=None):
     """options: plan options by key, e.g. {"compute_units": 4, "stream_rows": 2}, on top of DEFAULT_OPTIONS and of engine / kernel /
     tile (shorthands for three of them; tile (0, 0) = auto).
     sign_words: an int32 array [B,OH,OW,ceil(Cout/32)] that receives the float output's sign bits (the
-    matrix-core kernels' second output; stays untouched when the chosen kernel variant cannot write it)."""
+    matrix-core kernels' second output; stays untouched when the chosen kernel variant cannot write it).
+    out: a C-contiguous array of the output's shape and type to write into (e.g. a view into a guarded buffer) instead of a new one."""
     inp = np.ascontiguousarray(inp, np.int32)
     filt = np.ascontiguousarray(filt, np.int32)
     mul = None if post_mul is None else np.ascontiguousarray(post_mul, np.float32)
     bias = None if post_bias is None else np.ascontiguousarray(post_bias, np.float32)
     thr = None if thresholds is None else np.ascontiguousarray(thresholds, np.int32)
     dt = {O.DST_F32: np.float32, O.DST_I8: np.int8, O.DST_BITPACKED: np.int32}[dst_type]
-    out = np.full(spec.output_shape(dst_type), 0x55, dtype=np.uint8).astype(dt) if dt == np.int8 \
-        else np.full(spec.output_shape(dst_type), -7, dtype=dt)
+    if out is None:
+        out = np.full(spec.output_shape(dst_type), 0x55, dtype=np.uint8).astype(dt) if dt == np.int8 \
+            else np.full(spec.output_shape(dst_type), -7, dtype=dt)
+    assert out.dtype == dt and out.shape == tuple(spec.output_shape(dst_type)) and out.flags.c_contiguous
     name = C.create_string_buffer(128)
     d = make_desc(spec, dst_type, out_scale, out_zero_point)
     opts = {**DEFAULT_OPTIONS, "engine": engine, "kernel": kernel, "tile": "%dx%d" % tuple(tile) if tile[0] else "auto", **(options or {})}

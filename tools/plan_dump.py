@@ -8,15 +8,13 @@ A change that must not move a plan (a refactor of csrc/lce_plan*.cpp) is checked
     python tools/plan_dump.py | sha256sum
     LCE_PLAN_DEBUG=2 python tools/plan_dump.py --auto 2>&1 >/dev/null | sha256sum      (the auto rows' [lce plan] lines)
 usage: plan_dump.py [--auto] [--count]       --auto: the auto-rule rows only; --count: print the number of lines only"""
-import ctypes as C
 import os
 import sys
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hostsim_lib as H  # noqa: E402
+import launch_geometry as L  # noqa: E402  (the ctypes plumbing of hostsim_plan_new / _step / _free, shared with the tests)
 
 F32, I8, BP = 0, 1, 2
 SAME, VALID = 0, 1
@@ -38,21 +36,7 @@ def describe(d):
         d.padding, d.pad_values, d.activation, d.semantics, DST_NAME[d.dst_type])
 
 
-def weights(d, seed):
-    """Seeded operands of the layer: filter words, multiplier, bias, thresholds.  seed < 0: the ties-everywhere int8 parameters
-    (multiplier 0.25, integer biases) that no neighbouring pair rescues."""
-    g = np.random.Generator(np.random.PCG64(abs(seed)))
-    n, taps, cwg = d.channels_out, d.filter_height * d.filter_width, (d.channels_in // d.groups + 31) // 32
-    filt = g.integers(-2 ** 31, 2 ** 31, size=(n, taps, cwg), dtype=np.int64).astype(np.int32)
-    k = taps * (d.channels_in // d.groups)
-    if seed < 0:
-        mul = np.full(n, 0.25, np.float32)
-        bias = g.integers(-4, 5, size=n).astype(np.float32)
-    else:
-        mul = g.uniform(0.5, 1.5, n).astype(np.float32) / np.float32(np.sqrt(k))
-        bias = g.standard_normal(n).astype(np.float32)
-    thr = g.integers(0, k + 1, size=n, dtype=np.int64).astype(np.int32)
-    return [np.ascontiguousarray(a) for a in (filt, mul, bias, thr)]
+weights = L.seeded_weights
 
 
 def grid(auto_only):
@@ -159,25 +143,15 @@ def grid(auto_only):
 
 
 def main():
-    lib = H.lib()
-    lib.hostsim_plan_new.restype = C.c_void_p
-    lib.hostsim_plan_step.restype = C.c_char_p
-    lib.hostsim_plan_step.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-    lib.hostsim_plan_free.argtypes = [C.c_void_p]
     lines = 0
     for tag, d, seed, steps in grid("--auto" in sys.argv):
-        w = [None] * 4 if seed is None else weights(d, seed)
-        plan = lib.hostsim_plan_new(C.byref(d), *[None if a is None else a.ctypes.data_as(C.c_void_p) for a in w])
-        if not plan:
-            print("%s | %s | seed %s | refused: %s" % (tag, describe(d), seed, lib.hostsim_last_error().decode()))
+        for i, ((opts, max_batch), out) in enumerate(zip(steps, L.plan_lines(d, seed, steps))):
             lines += 1
-            continue
-        for i, (opts, max_batch) in enumerate(steps):
-            out = lib.hostsim_plan_step(plan, opts.encode(), max_batch).decode()
-            lines += 1
+            if out is None:
+                print("%s | %s | seed %s | refused: %s" % (tag, describe(d), seed, L.planner_lib().hostsim_last_error().decode()))
+                break
             if "--count" not in sys.argv:
                 print("%s | %s | seed %s | step %d '%s' max_batch %d | %s" % (tag, describe(d), seed, i, opts, max_batch, out))
-        lib.hostsim_plan_free(plan)
     if "--count" in sys.argv:
         print(lines)
     sys.stdout.flush()
