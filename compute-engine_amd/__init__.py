@@ -32,11 +32,12 @@ SEM_REFERENCE, SEM_OPTIMIZED = 0, 1
 # every symbol include/lce_hip.h declares (tests check the library exports them all)
 ABI_SYMBOLS = (
     "lce_hip_abi_version", "lce_hip_last_error", "lce_hip_build_flavor", "lce_hip_device_count", "lce_hip_set_device",
-    "lce_hip_malloc", "lce_hip_free", "lce_hip_memcpy_h2d", "lce_hip_memcpy_d2h", "lce_hip_memset",
+    "lce_hip_malloc", "lce_hip_free", "lce_hip_memcpy_h2d", "lce_hip_memcpy_d2h", "lce_hip_memcpy_d2d", "lce_hip_memset",
     "lce_hip_host_register", "lce_hip_host_unregister",
     "lce_hip_stream_create", "lce_hip_stream_destroy", "lce_hip_stream_synchronize",
     "lce_hip_graph_begin_capture", "lce_hip_graph_end_capture", "lce_hip_graph_launch", "lce_hip_graph_destroy",
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
+    "lce_hip_elementwise_ex", "lce_hip_elementwise_grid_cap",
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
     "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
@@ -57,6 +58,8 @@ ABI_SYMBOLS = (
 POST_ADD, POST_SUB, POST_MUL, POST_DIV = 0, 1, 2, 3
 EW_ADD, EW_MUL = 0, 1                                   # lce_hip_ew_op
 EW_SCALAR, EW_PER_CHANNEL, EW_TENSOR = 0, 1, 2          # lce_hip_ew_operand
+EW_CLAMP, EW_PRELU, EW_LOGISTIC = 2, 3, 4                # lce_hip_ew_op_ex
+EW_PER_IMAGE_CHANNEL = 3                                # lce_hip_ew_operand_ex
 EW_MAX_STEPS = 8
 CONCAT_MAX_INPUTS = 8                                   # LCE_HIP_CONCAT_MAX_INPUTS
 POOL_MAX, POOL_AVERAGE = 0, 1                           # lce_hip_pool_op
@@ -84,6 +87,12 @@ class EwStep(C.Structure):
     """``lce_hip_ew_step``."""
     _fields_ = [("op", C.c_int32), ("operand", C.c_int32), ("values", C.c_void_p), ("scalar", C.c_float),
                 ("activation", C.c_int32)]
+
+
+class EwStepEx(C.Structure):
+    """``lce_hip_ew_step_ex``."""
+    _fields_ = [("op", C.c_int32), ("operand", C.c_int32), ("values", C.c_void_p), ("scalar", C.c_float),
+                ("activation", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class AddInt8Desc(C.Structure):
@@ -192,6 +201,10 @@ def lib() -> C.CDLL:
                                      C.c_int32, C.c_void_p, C.c_void_p]
         l.lce_hip_elementwise.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(EwStep), C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_elementwise_ex.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(EwStepEx), C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_elementwise_grid_cap.argtypes, l.lce_hip_elementwise_grid_cap.restype = [], C.c_int32
+        l.lce_hip_memcpy_d2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         l.lce_hip_add_int8_prepare.argtypes = [C.POINTER(AddInt8Desc), C.POINTER(AddInt8Params)]
         l.lce_hip_add_int8_variant.argtypes = [C.POINTER(AddInt8Desc), C.POINTER(C.c_int32)]
         l.lce_hip_add_int8.argtypes = [C.POINTER(AddInt8Desc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
@@ -606,6 +619,94 @@ def elementwise(x, steps, out=None, out_bits=None, stream: int | None = None):
     with torch.cuda.device(dev):
         check(lib().lce_hip_elementwise(_dev_ptr(xd), rows, channels, arr, len(steps), _dev_ptr(out_d), _dev_ptr(bits_d),
                                         C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, out, out_bits)
+
+
+_EW_EX_OPS = {EW_ADD: EW_ADD, EW_MUL: EW_MUL, EW_CLAMP: EW_CLAMP, EW_PRELU: EW_PRELU, EW_LOGISTIC: EW_LOGISTIC,
+              "add": EW_ADD, "mul": EW_MUL, "clamp": EW_CLAMP, "prelu": EW_PRELU, "logistic": EW_LOGISTIC}
+
+
+def _ew_ex_check(x, steps, out, out_bits):
+    """Argument checks of ``elementwise_ex`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    the operand kind of every step."""
+    shape = tuple(x.shape)
+    if _dtype_name(x) != "float32" or len(shape) < 2:
+        raise ValueError("elementwise_ex: x must be a float32 tensor [batch, ..., channels], got %s %r" % (x.dtype, shape))
+    channels = shape[-1]
+    per_image = (shape[0],) + (1,) * (len(shape) - 2) + (channels,)
+    if not isinstance(steps, (list, tuple)) or not 1 <= len(steps) <= EW_MAX_STEPS:
+        raise ValueError("elementwise_ex: 1..%d steps, got %r" % (EW_MAX_STEPS, steps))
+    kinds = []
+    for k, step in enumerate(steps):
+        if not isinstance(step, (list, tuple)) or len(step) != 3:
+            raise ValueError("elementwise_ex: step %d must be (op, operand, activation), got %r" % (k, step))
+        op, operand, act = step
+        if isinstance(op, (list, dict)) or op not in _EW_EX_OPS:
+            raise ValueError("elementwise_ex: step %d: unknown op %r" % (k, op))
+        op = _EW_EX_OPS[op]
+        if act not in (ACT_NONE, ACT_RELU, ACT_RELU_N1_TO_1, ACT_RELU6):
+            raise ValueError("elementwise_ex: step %d: unknown activation %r" % (k, act))
+        if op in (EW_PRELU, EW_LOGISTIC) and act != ACT_NONE:
+            raise ValueError("elementwise_ex: step %d: PRELU and LOGISTIC take no activation" % k)
+        if op in (EW_CLAMP, EW_LOGISTIC):
+            if operand is not None:
+                raise ValueError("elementwise_ex: step %d: CLAMP and LOGISTIC take no operand" % k)
+            kinds.append(EW_SCALAR)
+            continue
+        if operand is None:
+            raise ValueError("elementwise_ex: step %d: no operand" % k)
+        if isinstance(operand, (int, float, np.floating, np.integer)):
+            kinds.append(EW_SCALAR)
+            continue
+        oshape = tuple(operand.shape)
+        if _dtype_name(operand) != "float32":
+            raise ValueError("elementwise_ex: step %d: operand must be float32, got %s" % (k, operand.dtype))
+        if oshape == (channels,):
+            kinds.append(EW_PER_CHANNEL)
+        elif op == EW_PRELU:
+            raise ValueError("elementwise_ex: step %d: PRELU's alpha is a float or [channels], got shape %r" % (k, oshape))
+        elif oshape == shape:
+            kinds.append(EW_TENSOR)
+        elif oshape == per_image:
+            kinds.append(EW_PER_IMAGE_CHANNEL)
+        else:
+            raise ValueError("elementwise_ex: step %d: operand shape %r is neither x's %r, per image %r nor [channels] (%d,)"
+                             % (k, oshape, shape, per_image, channels))
+    _check_outputs("elementwise_ex", out, out_bits, "float32", shape)
+    return kinds
+
+
+def elementwise_ex(x, steps, out=None, out_bits=None, stream: int | None = None):
+    """``elementwise`` with more kinds of step (``lce_hip_elementwise_ex``; its arithmetic: include/lce_hip.h).  ``x``: float32
+    [batch, ..., C].  ``steps``: up to 8 ``(op, operand, activation)``:
+    ``("add" | "mul", operand, ACT_*)`` -- the operand a float, a [C] tensor, a tensor of x's shape, or a [batch, 1, ..., 1, C]
+    tensor (one value per image and channel: the gate of a squeeze-and-excite block);
+    ``("clamp", None, ACT_*)`` -- a standalone RELU / RELU_N1_TO_1 / RELU6;
+    ``("prelu", alpha, ACT_NONE)`` -- alpha a float or a [C] tensor;
+    ``("logistic", None, ACT_NONE)``.
+    ``out``, ``out_bits``, ``stream`` and the result: as ``elementwise``."""
+    kinds = _ew_ex_check(x, steps, out, out_bits)
+    import torch
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, "elementwise_ex", "x's")
+    xd = on_dev(x)
+    operands = [None if k == EW_SCALAR else on_dev(step[1]) for k, step in zip(kinds, steps)]
+    channels = x.shape[-1]
+    rows = xd.numel() // channels if channels else 0
+    rows_per_image = rows // x.shape[0] if x.shape[0] else 0
+    out_d = None if out is False else torch.empty_like(xd) if out is None else on_dev(out)
+    bits_d = None if out_bits is None else _new_bits(xd.shape[:-1], channels, dev) if out_bits is True else on_dev(out_bits)
+    arr = (EwStepEx * len(steps))()
+    for k, ((op, operand, act), kind, t) in enumerate(zip(steps, kinds, operands)):
+        arr[k].op = _EW_EX_OPS[op]
+        arr[k].operand = kind
+        arr[k].values = None if t is None else t.data_ptr()
+        arr[k].scalar = float(operand) if kind == EW_SCALAR and operand is not None else 0.0
+        arr[k].activation = int(act)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_elementwise_ex(_dev_ptr(xd), rows, channels, rows_per_image, arr, len(steps), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                           C.c_void_p(_stream_or_current(stream, dev))))
     return _results(host, out_d, bits_d, out, out_bits)
 
 

@@ -17,7 +17,7 @@
 #include "../../include/lce_hip.h"
 #include "lce_kernels.h"          // the LceQuantize / LceDequantize / LceBMaxPool2d kernels are launched from here
 #include "lce_kernel_types.h"    // the convolution kernels live in their own translation units (lce_tu_*.hip)
-#include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip)
+#include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip, lce_tu_eltwise_ex.hip)
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
 #include "lce_kernels_concat.h"      // (lce_tu_concat.hip)
 #include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
@@ -45,6 +45,7 @@
 #include "lce_tu_wstream_i8_floor.hip"
 #include "lce_tu_wstream_bitpacked.hip"
 #include "lce_tu_eltwise.hip"
+#include "lce_tu_eltwise_ex.hip"
 #include "lce_tu_eltwise_i8.hip"
 #include "lce_tu_concat.hip"
 #include "lce_tu_pool.hip"
@@ -429,6 +430,10 @@ lce_hip_status lce_hip_memcpy_d2h(void* dst, const void* src, size_t bytes, void
   LCE_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
   return LCE_HIP_OK;
 }
+lce_hip_status lce_hip_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
+  LCE_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return LCE_HIP_OK;
+}
 lce_hip_status lce_hip_memset(void* dst, int value, size_t bytes, void* stream) {
   LCE_HIP_TRY(hipMemsetAsync(dst, value, bytes, (hipStream_t)stream));
   return LCE_HIP_OK;
@@ -630,6 +635,69 @@ lce_hip_status lce_hip_elementwise(const float* in_dev, size_t rows, size_t chan
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_elementwise: launch failed: %s", hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
+
+// The extended chain: the steps of lce_hip_elementwise plus a per-image operand, CLAMP, PRELU and LOGISTIC (the EX = 1 instances
+// of the same two kernels).  Everything is checked before any device call.
+lce_hip_status lce_hip_elementwise_ex(const float* in_dev, size_t rows, size_t channels, size_t rows_per_image,
+                                      const lce_hip_ew_step_ex* steps, int32_t num_steps, float* out_dev, int32_t* out_bits_dev,
+                                      void* stream) {
+  const char* who = "lce_hip_elementwise_ex";
+  if (num_steps < 1 || num_steps > lce::kEwMaxSteps)
+    return fail(LCE_HIP_ERR_INVALID, "%s: num_steps must be 1..%d, got %d", who, lce::kEwMaxSteps, (int)num_steps);
+  if (!steps) return fail(LCE_HIP_ERR_INVALID, "%s: null steps", who);
+  if (channels >= (1ull << 31)) return fail(LCE_HIP_ERR_INVALID, "%s: channels must be below 2^31", who);
+  lce::EwArgsEx a;
+  memset(&a, 0, sizeof a);
+  bool aligned = ((uintptr_t)in_dev % 16 == 0) && ((uintptr_t)out_dev % 16 == 0) && ((uintptr_t)out_bits_dev % 16 == 0);
+  bool aligned4 = ((uintptr_t)in_dev % 4 == 0) && ((uintptr_t)out_dev % 4 == 0) && ((uintptr_t)out_bits_dev % 4 == 0);
+  bool per_image = false;
+  for (int32_t s = 0; s < num_steps; ++s) {
+    const lce_hip_ew_step_ex& st = steps[s];
+    lce::EwStep& k = a.steps[s];
+    if (st.op < LCE_HIP_EW_ADD || st.op > LCE_HIP_EW_LOGISTIC) return fail(LCE_HIP_ERR_INVALID, "%s: step %d: unknown op %d", who, (int)s, (int)st.op);
+    if (st.operand < LCE_HIP_EW_SCALAR || st.operand > LCE_HIP_EW_PER_IMAGE_CHANNEL)
+      return fail(LCE_HIP_ERR_INVALID, "%s: step %d: unknown operand kind %d", who, (int)s, (int)st.operand);
+    if (st.reserved[0] || st.reserved[1]) return fail(LCE_HIP_ERR_INVALID, "%s: step %d: reserved fields must be zero", who, (int)s);
+    if (!float_activation_range(st.activation, &k.lo, &k.hi))
+      return fail(LCE_HIP_ERR_INVALID, "%s: step %d: unknown activation %d", who, (int)s, (int)st.activation);
+    const bool arithmetic = st.op == LCE_HIP_EW_ADD || st.op == LCE_HIP_EW_MUL;
+    if (st.op == LCE_HIP_EW_PRELU && st.operand != LCE_HIP_EW_SCALAR && st.operand != LCE_HIP_EW_PER_CHANNEL)
+      return fail(LCE_HIP_ERR_INVALID, "%s: step %d: PRELU's alpha is SCALAR or PER_CHANNEL, got operand kind %d", who, (int)s, (int)st.operand);
+    if ((st.op == LCE_HIP_EW_PRELU || st.op == LCE_HIP_EW_LOGISTIC) && st.activation != LCE_HIP_ACT_NONE)
+      return fail(LCE_HIP_ERR_INVALID, "%s: step %d: PRELU and LOGISTIC take no activation (a CLAMP step follows them)", who, (int)s);
+    const bool reads = arithmetic || st.op == LCE_HIP_EW_PRELU;          // CLAMP and LOGISTIC have no operand: theirs is ignored
+    k.op = st.op;
+    k.operand = reads ? st.operand : (int32_t)LCE_HIP_EW_SCALAR;
+    k.values = reads && st.operand != LCE_HIP_EW_SCALAR ? st.values : nullptr;
+    k.scalar = st.scalar;
+    if (k.operand == LCE_HIP_EW_PER_IMAGE_CHANNEL) per_image = true;
+    if (k.values && (uintptr_t)k.values % 16 != 0) aligned = false;
+    if (k.values && (uintptr_t)k.values % 4 != 0) aligned4 = false;
+  }
+  if (rows_per_image == 0 && per_image) return fail(LCE_HIP_ERR_INVALID, "%s: a PER_IMAGE_CHANNEL operand needs rows_per_image", who);
+  if (rows_per_image != 0 && rows % rows_per_image != 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: rows_per_image %zu does not divide rows %zu", who, rows_per_image, rows);
+  if (rows == 0 || channels == 0) return LCE_HIP_OK;   // (an empty tensor may come with null pointers)
+  for (int32_t s = 0; s < num_steps; ++s)
+    if (a.steps[s].operand != LCE_HIP_EW_SCALAR && !a.steps[s].values) return fail(LCE_HIP_ERR_INVALID, "%s: step %d: null operand", who, (int)s);
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+  if (!aligned4) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  if (lce_hip_status s = require_device()) return s;
+  a.in = in_dev;
+  a.out = out_dev;
+  a.bits = (uint32_t*)out_bits_dev;
+  a.rows = rows;
+  a.channels = (uint32_t)channels;
+  a.wpr = (uint32_t)((channels + 31) / 32);
+  a.num_steps = num_steps;
+  a.rows_per_image = rows_per_image ? rows_per_image : rows;            // (no per-image operand: one image)
+  const int e = lce::launch_eltwise_ex(a, channels % 32 == 0 && aligned, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+int32_t lce_hip_elementwise_grid_cap(void) { return (int32_t)lce::kEwGridCap; }
 
 // ------------------------------------------------------------------------------------
 // int8 residual ADD (lce_kernels_eltwise_i8.h)

@@ -41,7 +41,7 @@
 //
 //   m   = max over the row                      (inputs finite; +0 and -0 compare equal and either gives the same bytes below)
 //   a_i = (x_i - m) * beta                      (two IEEE operations, no contraction)
-//   e_i = head_exp(a_i)                         (below)
+//   e_i = head_exp(a_i)                         (lce_kernels_exp.h; restated below)
 //   s   : lane l adds e_l, e_{l+64}, e_{l+128}, ... in this order from +0.0f; then s_l = s_l + s_{l ^ d} for d = 32, 16, 8, 4, 2, 1
 //   out_i = e_i / s                             (the correctly rounded division)
 //
@@ -91,6 +91,7 @@ int launch_softmax(const SoftmaxArgs& args, void* stream);
 
 #ifdef __HIPCC__
 #include "lce_device_intrinsics.h"
+#include "lce_kernels_exp.h"
 
 namespace lce {
 using namespace lce_dev;
@@ -189,27 +190,8 @@ fully_connected_f32(const FcArgs A) {
   }
 }
 
-// exp(a) for a <= 0 as the header comment states it.  (No contraction anywhere in this file: the library and the host
-// simulation are built with -ffp-contract=off, and `/` is the correctly rounded division -- hipcc's default for float.)
-LCE_DEVICE float head_exp(float a) {
-  if (!(a >= -104.0f)) return 0.0f;
-  a = a > 0.0f ? 0.0f : a;
-  const float n = __builtin_rintf(a * 1.44269502f);
-  float r = fma1(n, -0.693145751953125f, a);
-  r = fma1(n, -1.42860676e-06f, r);
-  float p = 1.98412701e-04f;          // 1/5040
-  p = fma1(p, r, 1.38888892e-03f);    // 1/720
-  p = fma1(p, r, 8.33333377e-03f);    // 1/120
-  p = fma1(p, r, 4.16666679e-02f);    // 1/24
-  p = fma1(p, r, 1.66666672e-01f);    // 1/6
-  p = fma1(p, r, 0.5f);
-  p = fma1(p, r, 1.0f);
-  p = fma1(p, r, 1.0f);
-  const int32_t ni = (int32_t)n;
-  const bool low = ni < -125;
-  const uint32_t bits = __builtin_bit_cast(uint32_t, p) + ((uint32_t)(ni + (low ? 64 : 0)) << 23);
-  return __builtin_bit_cast(float, bits) * (low ? 5.42101086e-20f : 1.0f);               // 2^-64
-}
+// head_exp(a): exp(a) for a <= 0 as the header comment states it, in lce_kernels_exp.h (included above) -- the LOGISTIC step of
+// lce_kernels_eltwise.h is stated on the same function.  `/` below is the correctly rounded division (hipcc's default for float).
 
 // The second half of the stated sum: s_l = s_l + s_{l ^ d} for d = 32, 16, 8, 4, 2, 1 over the wave's 64 partial sums (every lane ends
 // with the same number).  lce_kernels_head_i8.h sums its rows through this function too.

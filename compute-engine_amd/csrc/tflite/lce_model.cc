@@ -23,14 +23,15 @@ struct lce_tflite_section {
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
        kAbsorbedConvI8, kAbsorbedDepthwiseI8, kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
-       kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedCount };
+       kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedActivation, kAbsorbedReshape, kAbsorbedGate, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
-enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u };
+enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u,
+       kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
-  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize", "depthwise_i8")
+  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize", "depthwise_i8", "activation", "reshape", "gate")
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
@@ -47,6 +48,8 @@ struct lce_tflite_model {
   struct RunStats {
     int32_t conv_quantize = 0;                                          // LceQuantize launches folded into a convolution (run_dual)
     int32_t ew_ops = 0;                                                 // ADD / MUL operators inside the lce_hip_elementwise launches
+    int32_t ex_ops = 0;                                                 // operators of every kind inside the lce_hip_elementwise_ex launches
+    int32_t reshape_views = 0, reshape_copies = 0;                      // absorbed RESHAPE operators: aliased / copied device to device
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
     Pass pass[kAbsorbedCount];                                          // by kAbsorbed* kind ([0] unused)
   };
@@ -787,6 +790,103 @@ bool BoundaryOperands(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32
 bool QuantizeCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) { return BoundaryOperands(M, o, lce_tfl::kBuiltinQuantize, true); }
 bool DequantizeCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) { return BoundaryOperands(M, o, lce_tfl::kBuiltinDequantize, false); }
 
+// ---- standalone activations, RESHAPE and the per-image gate (lce_tflite_model_open_passes, "activation", "reshape", "gate") ----
+// The step a standalone activation is in the one-pass chain (lce_hip_elementwise_ex): RELU / RELU_N1_TO_1 / RELU6 are a CLAMP with
+// that activation, LOGISTIC and PRELU themselves.  False for every other operator.
+bool ActivationStep(const lce_tfl::Operator& o, int32_t* op, int32_t* activation) {
+  *activation = LCE_HIP_ACT_NONE;
+  switch (o.builtin_code) {
+    case lce_tfl::kBuiltinRelu: *op = LCE_HIP_EW_CLAMP; *activation = LCE_HIP_ACT_RELU; return true;
+    case lce_tfl::kBuiltinReluN1To1: *op = LCE_HIP_EW_CLAMP; *activation = LCE_HIP_ACT_RELU_N1_TO_1; return true;
+    case lce_tfl::kBuiltinRelu6: *op = LCE_HIP_EW_CLAMP; *activation = LCE_HIP_ACT_RELU6; return true;
+    case lce_tfl::kBuiltinLogistic: *op = LCE_HIP_EW_LOGISTIC; return true;
+    case lce_tfl::kBuiltinPrelu: *op = LCE_HIP_EW_PRELU; return true;
+    default: return false;
+  }
+}
+
+// Element count of a constant PRELU alpha that broadcasts over the last axis: BroadcastCount's shapes and [1,1,C] (what the
+// converter writes for shared_axes=[1,2]); -1 for any other shape -- a full [H,W,C] alpha is the host's.
+int64_t AlphaCount(const lce_tfl::Tensor& t) {
+  const std::vector<int32_t>& s = t.shape;
+  if (s.size() == 3 && s[0] == 1 && s[1] == 1) return s[2];
+  return BroadcastCount(t);
+}
+
+// "A standalone activation that a section may run" ("activation"): RELU, RELU_N1_TO_1, RELU6 or LOGISTIC with one input, PRELU
+// with two; one output; input and output float32 of the same shape, of rank 2 or 4 with positive extents (Carried), the input
+// non-constant; PRELU's alpha a constant float32 with data in the file, of shape [C], [1,1,C], [1,1,1,C], [1] or [] and as many
+// bytes.  int8 tensors, a full [H,W,C] alpha and TANH stay with the host.  The operator joins the epoch in which it becomes ready.
+bool ActivationCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  int32_t step, act;
+  if (!ActivationStep(o, &step, &act)) return false;
+  const bool prelu = o.builtin_code == lce_tfl::kBuiltinPrelu;
+  if (o.inputs.size() != (prelu ? 2u : 1u) || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 || out.type != lce_tfl::kTensorFloat32 || in.data || in.shape != out.shape) return false;
+  int32_t id[4];
+  if (!Carried(in, id) || id[0] <= 0) return false;
+  if (prelu) {
+    if (o.inputs[1] < 0) return false;
+    const lce_tfl::Tensor& alpha = M.tensors[o.inputs[1]];
+    if (alpha.type != lce_tfl::kTensorFloat32 || !alpha.data) return false;
+    const int64_t n = AlphaCount(alpha);
+    if ((n != 1 && n != id[3]) || (uint64_t)alpha.bytes != (uint64_t)n * 4u) return false;
+  }
+  return true;
+}
+
+// "A builtin RESHAPE that a section may run" ("reshape"): a view of the same bytes.  One or two inputs and one output; the data
+// input non-constant, float32, int8 or int32, the output of the same type (int8: the same scale and zero point); the optional
+// second input -- the new shape -- absent or a constant (the reshape is judged by the DECLARED shape of its output tensor; a shape
+// computed at run time is the host's); input and output of rank 2 or 4 with positive extents (Carried), the same leading extent
+// and the same element count behind it.  Anything that moves the batch extent stays with the host.
+bool ReshapeCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinReshape || (o.inputs.size() != 1 && o.inputs.size() != 2) || o.outputs.size() != 1) return false;
+  if (o.inputs[0] < 0) return false;
+  if (o.inputs.size() == 2 && o.inputs[1] >= 0 && !M.tensors[o.inputs[1]].data) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.data || in.type != out.type) return false;
+  if (in.type != lce_tfl::kTensorFloat32 && in.type != lce_tfl::kTensorInt8 && in.type != lce_tfl::kTensorInt32) return false;
+  if (in.type == lce_tfl::kTensorInt8 && (in.quantized != out.quantized || in.scale != out.scale || in.zero_point != out.zero_point)) return false;
+  int32_t id[4], od[4];
+  if (!Carried(in, id) || !Carried(out, od) || id[0] <= 0 || id[0] != od[0]) return false;
+  return (uint64_t)id[1] * (uint64_t)id[2] * (uint64_t)id[3] == (uint64_t)od[1] * (uint64_t)od[2] * (uint64_t)od[3];
+}
+
+// The input slot (0 or 1) of gate `o` that holds the [b,1,1,C] operand; the other slot holds the streamed [b,H,W,C] tensor.  -1
+// when the two inputs are not such a pair.  (Both [b,1,1,C]: slot 1 is the operand.)
+int GateOperandSlot(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  for (int slot = 1; slot >= 0; --slot) {
+    const lce_tfl::Tensor& g = M.tensors[o.inputs[slot]];
+    const lce_tfl::Tensor& x = M.tensors[o.inputs[1 - slot]];
+    if (g.shape.size() == 4 && g.shape[0] == out.shape[0] && g.shape[1] == 1 && g.shape[2] == 1 && g.shape[3] == out.shape[3] &&
+        x.shape == out.shape)
+      return slot;
+  }
+  return -1;
+}
+
+// "A float ADD / MUL by a per-image tensor that a section may run" ("gate"): the scale of a squeeze-and-excite block.  Two
+// inputs and one output, all float32, both inputs non-constant; a 4-D output [b,H,W,C] with positive extents; one input of the
+// output's shape, the other [b,1,1,C]; an activation lce_hip_elementwise knows.  A [b,C] operand does not qualify (TFLite's
+// broadcast aligns it to the trailing axes: it is not per image), and rank-2 ADD / MUL stay with the host.
+bool GateCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinAdd && o.builtin_code != lce_tfl::kBuiltinMul) return false;
+  if (o.inputs.size() != 2 || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (out.type != lce_tfl::kTensorFloat32 || out.shape.size() != 4) return false;
+  for (int32_t extent : out.shape)
+    if (extent <= 0) return false;
+  for (int32_t t : o.inputs)
+    if (M.tensors[t].type != lce_tfl::kTensorFloat32 || M.tensors[t].data) return false;
+  return GateOperandSlot(M, o) >= 0;
+}
+
 // One fused pass: the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it that enables it, the static half of "a section may run
 // this operator", and the walker that runs it.  The table, in priority order, is below Walk.
 struct Walk;
@@ -1002,7 +1102,8 @@ lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, co
       {"conv2d", 1, LCE_TFLITE_SECTIONS_EXT_CONV2D},       {"stem", 1, LCE_TFLITE_SECTIONS_EXT_STEM},
       {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8},
       {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize},
-      {"depthwise_i8", 2, kInternalDepthwiseI8}};
+      {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
+      {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate}};
   uint32_t words[3] = {0u, 0u, 0u};
   std::string refusal;
   if (!passes) refusal = "null passes";
@@ -1444,26 +1545,77 @@ struct Walk {
   // operator is the step's operand (a constant: scalar or per channel; otherwise a tensor of x's shape).  The chain's last
   // tensor is written in float when anything but a folded LceQuantize reads it or the section delivers it; the first
   // LceQuantize of the section that reads it becomes the launch's bit output and its own launch disappears.
+  // The chain extends, by the same rules, through the absorbed operators of the other two elementwise kinds: a standalone
+  // activation ("activation": a CLAMP, PRELU or LOGISTIC step) and an ADD / MUL by a [b,1,1,C] tensor ("gate": a
+  // PER_IMAGE_CHANNEL operand; the gate must be the operand, never the streamed tensor).  A chain that holds one of those is
+  // ONE lce_hip_elementwise_ex launch; a chain of the old step kinds alone goes through lce_hip_elementwise as before.
+  static bool ChainKind(int kind) { return kind == kAbsorbedElementwise || kind == kAbsorbedActivation || kind == kAbsorbedGate; }
   lce_hip_status ElementwiseChain(int32_t first) {
     const lce_tfl::Model& M = model->m;
     const lce_tfl::Operator& op0 = M.operators[first];
-    const int32_t x_t = M.tensors[op0.inputs[0]].data ? op0.inputs[1] : op0.inputs[0];
+    const int kind0 = model->absorbed[first];
+    int32_t x_t = M.tensors[op0.inputs[0]].data ? op0.inputs[1] : op0.inputs[0];
+    if (kind0 == kAbsorbedActivation) x_t = op0.inputs[0];
+    if (kind0 == kAbsorbedGate) x_t = op0.inputs[1 - GateOperandSlot(M, op0)];
     auto x_it = shapes.find(x_t);
     if (x_it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
     const Shape xs = x_it->second;
-    const std::vector<int32_t>& fs = M.tensors[op0.outputs[0]].shape;
-    if (!Agrees(xs, lce_tfl::kTensorFloat32, fs[1], fs[2], fs[3]))
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL input's shape does not match the one its producer infers");
+    if (kind0 == kAbsorbedElementwise) {
+      const std::vector<int32_t>& fs = M.tensors[op0.outputs[0]].shape;
+      if (!Agrees(xs, lce_tfl::kTensorFloat32, fs[1], fs[2], fs[3]))
+        return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL input's shape does not match the one its producer infers");
+    }
     const size_t rows = (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2], channels = (size_t)xs.dims[3];
 
-    std::vector<lce_hip_ew_step> steps;
+    std::vector<lce_hip_ew_step_ex> steps;
     std::vector<int32_t> chain;
+    bool extended = false, gated = false;
     int32_t cur = first, v_t = x_t;
+    // (an activation's or a gate's declared output must be the streamed tensor's shape: the file is untrusted input)
+    auto same_image = [&](const lce_tfl::Operator& o) {
+      int32_t want[4];
+      return Carried(M.tensors[o.outputs[0]], want) && Agrees(xs, lce_tfl::kTensorFloat32, want[1], want[2], want[3]);
+    };
     // the operand of operator `o` whose streamed input is `v`; false when it is not available yet (produced further down)
-    auto operand_of = [&](const lce_tfl::Operator& o, int32_t v, lce_hip_ew_step* st) -> lce_hip_status {
+    auto operand_of = [&](const lce_tfl::Operator& o, int kind, int32_t v, lce_hip_ew_step_ex* st) -> lce_hip_status {
+      memset(st, 0, sizeof *st);
+      if (kind == kAbsorbedActivation) {
+        if (!ActivationStep(o, &st->op, &st->activation) || o.inputs[0] != v || !same_image(o))
+          return Fail(LCE_HIP_ERR_INVALID, "run_section: an activation's shape does not match the one its producer infers");
+        st->operand = LCE_HIP_EW_SCALAR;
+        if (st->op != LCE_HIP_EW_PRELU) return LCE_HIP_OK;
+        const lce_tfl::Tensor& A = M.tensors[o.inputs[1]];
+        if (A.bytes == 4) {
+          memcpy(&st->scalar, A.data, 4);
+          return LCE_HIP_OK;
+        }
+        st->operand = LCE_HIP_EW_PER_CHANNEL;
+        if (A.bytes != channels * 4) return Fail(LCE_HIP_ERR_INVALID, "run_section: a PRELU alpha does not match the channels");
+        if (run)
+          if (lce_hip_status s = ConstOnDevice(model, o.inputs[1], stream, capturing, &st->values)) return s;
+        return LCE_HIP_OK;
+      }
+      if (kind == kAbsorbedGate) {
+        const int slot = GateOperandSlot(M, o);
+        if (slot < 0 || o.inputs[1 - slot] != v) return LCE_HIP_ERR_UNSUPPORTED;     // (the chain's tensor is the gate itself: it stops before `o`)
+        if (!same_image(o)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a gated ADD / MUL's shape does not match the one its producer infers");
+        auto it = shapes.find(o.inputs[slot]);
+        if (it == shapes.end()) return LCE_HIP_ERR_UNSUPPORTED;        // (not an error: the chain stops before `o`)
+        const Shape& gs = it->second;
+        if (gs.type != lce_tfl::kTensorFloat32 || gs.dims[0] != xs.dims[0] || gs.dims[1] != 1 || gs.dims[2] != 1 || gs.dims[3] != xs.dims[3])
+          return Fail(LCE_HIP_ERR_INVALID, "run_section: a gate is not [batch, 1, 1, channels] of the tensor it scales");
+        st->op = o.builtin_code == lce_tfl::kBuiltinMul ? LCE_HIP_EW_MUL : LCE_HIP_EW_ADD;
+        st->activation = o.activation;
+        st->operand = LCE_HIP_EW_PER_IMAGE_CHANNEL;
+        if (run) {
+          const void* p = nullptr;
+          if (lce_hip_status s = DevicePtr(o.inputs[slot], "a gate", &p)) return s;
+          st->values = (const float*)p;
+        }
+        return LCE_HIP_OK;
+      }
       const int32_t other = (o.inputs[0] == v) ? o.inputs[1] : o.inputs[0];
       const lce_tfl::Tensor& T = M.tensors[other];
-      memset(st, 0, sizeof *st);
       st->op = o.builtin_code == lce_tfl::kBuiltinMul ? LCE_HIP_EW_MUL : LCE_HIP_EW_ADD;
       st->activation = o.activation;
       if (T.data) {
@@ -1496,21 +1648,24 @@ struct Walk {
     };
     for (;;) {
       const lce_tfl::Operator& o = M.operators[cur];
-      lce_hip_ew_step st;
-      const lce_hip_status s = operand_of(o, v_t, &st);
+      const int kind = model->absorbed[cur];
+      lce_hip_ew_step_ex st;
+      const lce_hip_status s = operand_of(o, kind, v_t, &st);
       if (s == LCE_HIP_ERR_UNSUPPORTED && chain.empty())
         return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD / MUL reads a tensor nothing produced");
       if (s == LCE_HIP_ERR_UNSUPPORTED) break;
       if (s != LCE_HIP_OK) return s;
       steps.push_back(st);
       chain.push_back(cur);
+      extended = extended || kind != kAbsorbedElementwise;
+      gated = gated || kind == kAbsorbedGate;
       done[cur] = 1;
       v_t = o.outputs[0];
       shapes[v_t] = xs;
       const std::vector<int32_t>& rd = model->readers[v_t];
       if (steps.size() == 8 || rd.size() != 1 || IsSectionOutput(v_t)) break;
       const int32_t next = rd[0];
-      if (model->absorbed[next] != kAbsorbedElementwise || done[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
+      if (!ChainKind(model->absorbed[next]) || done[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
       cur = next;
     }
     const Fold fold = FoldQuantize(chain.back(), v_t, xs);
@@ -1519,10 +1674,54 @@ struct Walk {
     if (lce_hip_status s = DevicePtr(x_t, "an ADD / MUL input", &in)) return s;
     void *out, *bits;
     if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    if (lce_hip_status s = lce_hip_elementwise((const float*)in, rows, channels, steps.data(), (int32_t)steps.size(), (float*)out,
-                                               (int32_t*)bits, stream)) return s;
-    model->last.ew_ops += (int32_t)chain.size();
-    return Launched(kAbsorbedElementwise, fold);
+    if (!extended) {
+      std::vector<lce_hip_ew_step> old(steps.size());
+      for (size_t k = 0; k < steps.size(); ++k) {
+        memset(&old[k], 0, sizeof old[k]);
+        old[k].op = steps[k].op; old[k].operand = steps[k].operand; old[k].values = steps[k].values;
+        old[k].scalar = steps[k].scalar; old[k].activation = steps[k].activation;
+      }
+      if (lce_hip_status s = lce_hip_elementwise((const float*)in, rows, channels, old.data(), (int32_t)old.size(), (float*)out,
+                                                 (int32_t*)bits, stream)) return s;
+      model->last.ew_ops += (int32_t)chain.size();
+      return Launched(kAbsorbedElementwise, fold);
+    }
+    if (lce_hip_status s = lce_hip_elementwise_ex((const float*)in, rows, channels, (size_t)xs.dims[1] * xs.dims[2], steps.data(),
+                                                  (int32_t)steps.size(), (float*)out, (int32_t*)bits, stream)) return s;
+    model->last.ex_ops += (int32_t)chain.size();
+    if (gated) Launched(kAbsorbedGate, fold);
+    return Launched(kAbsorbedActivation, fold);
+  }
+
+  // An absorbed RESHAPE ("reshape" of lce_tflite_model_open_passes): a view of the same bytes.  Its output takes the input's
+  // device buffer -- no launch -- unless the output already has a buffer of its own (the section delivers it into the caller's):
+  // then ONE device-to-device copy on `stream`.
+  lce_hip_status Reshape(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t in_t = op.inputs[0], out_t = op.outputs[0];
+    auto it = shapes.find(in_t);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a RESHAPE reads a tensor nothing produced");
+    int32_t id[4], od[4];
+    if (!Carried(M.tensors[in_t], id) || !Carried(M.tensors[out_t], od) || !Agrees(it->second, M.tensors[in_t].type, id[1], id[2], id[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a RESHAPE input's shape or type does not match the one its producer infers");
+    Shape os;
+    os.dims[0] = batch; os.dims[1] = od[1]; os.dims[2] = od[2]; os.dims[3] = od[3];
+    os.type = it->second.type;
+    if (os.bytes() != it->second.bytes()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a RESHAPE changes the element count");
+    shapes[out_t] = os;
+    done[i] = 1;
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(in_t, "a RESHAPE input", &in)) return s;
+    auto own = ptr.find(out_t);
+    if (own == ptr.end()) {
+      ptr[out_t] = const_cast<void*>(in);
+      ++model->last.reshape_views;
+      return LCE_HIP_OK;
+    }
+    ++model->last.reshape_copies;
+    return own->second == in ? LCE_HIP_OK : lce_hip_memcpy_d2d(own->second, in, os.bytes(), stream);
   }
 
   // An absorbed int8 ADD (LCE_TFLITE_SECTIONS_INT8_ADD) as ONE lce_hip_add_int8 launch.  The first LceQuantize of the section
@@ -1987,7 +2186,7 @@ struct Walk {
       const lce_tfl::Tensor& T = M.tensors[t];
       Shape sh;
       // (a rank-2 input -- of a head that starts behind a host operator -- is carried as [batch, 1, 1, C])
-      if (T.shape.size() == 2 && (model->flags_int & (kInternalHead | kInternalHeadI8 | kInternalQuantize))) {
+      if (T.shape.size() == 2 && (model->flags_int & (kInternalHead | kInternalHeadI8 | kInternalQuantize | kInternalActivation | kInternalReshape))) {
         if (!Carried(T, sh.dims)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a section input with an extent that is not positive");
       } else {
         if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
@@ -2034,6 +2233,12 @@ const FusedPass kPasses[kAbsorbedCount - 1] = {
     {kAbsorbedSoftmaxI8, 2, kInternalHeadI8, SoftmaxI8Candidate, &Walk::SoftmaxI8},
     {kAbsorbedQuantize, 2, kInternalQuantize, QuantizeCandidate, &Walk::QuantizeF32I8},
     {kAbsorbedDequantize, 2, kInternalQuantize, DequantizeCandidate, &Walk::DequantizeI8F32},
+    // the standalone activations ("activation") and the per-image gate ("gate") are steps of the elementwise chain, so their walker
+    // is the chain's; ElementwiseCandidate above takes no ADD / MUL with a non-constant [b,1,1,C] input on a larger image, and where
+    // the image is 1 x 1 the gate is a tensor operand like any other.  RESHAPE ("reshape") launches nothing.
+    {kAbsorbedActivation, 2, kInternalActivation, ActivationCandidate, &Walk::ElementwiseChain},
+    {kAbsorbedReshape, 2, kInternalReshape, ReshapeCandidate, &Walk::Reshape},
+    {kAbsorbedGate, 2, kInternalGate, GateCandidate, &Walk::ElementwiseChain},
 };
 }  // namespace
 
@@ -2180,6 +2385,24 @@ void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int3
 void lce_tflite_model_quantize_stats(lce_tflite_model* model, int32_t* quantize, int32_t* dequantize) {
   PassStats(model, kAbsorbedQuantize, quantize, nullptr);
   PassStats(model, kAbsorbedDequantize, dequantize, nullptr);
+}
+
+void lce_tflite_model_activation_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+  PassStats(model, kAbsorbedActivation, launches, quantize_folded);
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (ops_folded) *ops_folded = model->last.ex_ops;
+}
+
+void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (views) *views = model->last.reshape_views;
+  if (copies) *copies = model->last.reshape_copies;
+}
+
+void lce_tflite_model_gate_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
+  PassStats(model, kAbsorbedGate, launches, quantize_folded);
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

@@ -34,6 +34,9 @@
 //   2 keep_num_dims(bool)  3 asymmetric_quantize_inputs(bool); BuiltinOperator 9 FULLY_CONNECTED.
 //   BuiltinOptions union type 9 SoftmaxOptions: 0 beta(float); BuiltinOperator 25 SOFTMAX.
 //   BuiltinOperator 6 DEQUANTIZE, 114 QUANTIZE: no option this reader needs.
+//   BuiltinOperator 14 LOGISTIC, 19 RELU, 20 RELU_N1_TO_1, 21 RELU6, 54 PRELU (inputs: data, alpha): no options table.
+//   BuiltinOperator 22 RESHAPE (inputs: data and, optionally, the new shape as an int32 tensor): its ReshapeOptions.new_shape
+//   repeats the declared shape of the output tensor, which is what this library goes by; the table is not read.
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -53,6 +56,7 @@ constexpr int32_t kBuiltinCustom = 32;   // BuiltinOperator_CUSTOM
 constexpr int32_t kBuiltinAdd = 0, kBuiltinAveragePool2d = 1, kBuiltinConcatenation = 2, kBuiltinConv2d = 3, kBuiltinDepthwiseConv2d = 4, kBuiltinMaxPool2d = 17, kBuiltinMul = 18;
 constexpr int32_t kBuiltinFullyConnected = 9, kBuiltinSoftmax = 25, kBuiltinMean = 40;
 constexpr int32_t kBuiltinDequantize = 6, kBuiltinQuantize = 114;   // (their options tables, QuantizeOptions and DequantizeOptions, are empty)
+constexpr int32_t kBuiltinLogistic = 14, kBuiltinRelu = 19, kBuiltinReluN1To1 = 20, kBuiltinRelu6 = 21, kBuiltinReshape = 22, kBuiltinPrelu = 54;
 constexpr int kOptionsConv2d = 1, kOptionsDepthwiseConv2d = 2, kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 constexpr int kOptionsFullyConnected = 8, kOptionsSoftmax = 9, kOptionsReducer = 27;
 // TensorType values used by LCE graphs

@@ -54,6 +54,12 @@ With ``depthwise_i8_sections=True`` (the name ``depthwise_i8``) the quantized DE
 convolution of its stem -- joins them (``lce_hip_depthwise_conv2d_i8``: TFLite's integer arithmetic byte for byte), so an int8
 QuickNet is ONE section from the float image to the float probabilities (profiles/depthwise_i8: 29 / 17 / 11 us on its three
 transitions at batch 256, 53 / 29 / 16 us for the float entry).
+With ``activation_sections=True``, ``reshape_sections=True`` and ``gate_sections=True`` (the names ``activation``, ``reshape`` and
+``gate``) a standalone RELU / RELU_N1_TO_1 / RELU6 / LOGISTIC / PRELU, a RESHAPE that keeps the batch, and an ADD / MUL by a
+``[b, 1, 1, C]`` tensor join them.  The activations and the gate are steps of the elementwise chain (``lce_hip_elementwise_ex``): the
+whole tail of a ReActNet block -- batch norm, shortcut, shift, PRELU, shift and the next layer's sign bits -- is ONE pass, a
+RealToBinaryNet block with its squeeze-and-excite gate is one section, and a head that flattens instead of pooling (RESHAPE,
+FULLY_CONNECTED, SOFTMAX) runs on the GPU; the RESHAPE itself is a view of the same bytes.
 The model file is read by the bounds-checked reader in csrc/tflite (include/lce_tflite_model.h).
 """
 from __future__ import annotations
@@ -138,9 +144,11 @@ _SECTION_KEYWORDS = (
 _PASS_NAMES = {"elementwise_sections": "elementwise", "int8_add_sections": "int8_add", "concat_sections": "concat",
                "pool_sections": "pool", "conv1x1_sections": "conv1x1", "depthwise_sections": "depthwise",
                "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head", "conv2d_i8_sections": "conv2d_i8",
-               "head_i8_sections": "head_i8", "quantize_sections": "quantize", "depthwise_i8_sections": "depthwise_i8"}
+               "head_i8_sections": "head_i8", "quantize_sections": "quantize", "depthwise_i8_sections": "depthwise_i8",
+               "activation_sections": "activation", "reshape_sections": "reshape", "gate_sections": "gate"}
 # the keywords whose names only ``lce_tflite_model_open_passes`` knows, in the order their names are passed
-_NAMED_ONLY = ("head_sections", "conv2d_i8_sections", "head_i8_sections", "quantize_sections", "depthwise_i8_sections")
+_NAMED_ONLY = ("head_sections", "conv2d_i8_sections", "head_i8_sections", "quantize_sections", "depthwise_i8_sections",
+               "activation_sections", "reshape_sections", "gate_sections")
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
 # ``lce_tflite_model_<pass>_stats``: the counters each reports
 _PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2,
@@ -179,6 +187,9 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_head_stats.argtypes, l.lce_tflite_model_head_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
         l.lce_tflite_model_head_i8_stats.argtypes, l.lce_tflite_model_head_i8_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
         l.lce_tflite_model_quantize_stats.argtypes, l.lce_tflite_model_quantize_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
+        l.lce_tflite_model_activation_stats.argtypes, l.lce_tflite_model_activation_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
+        l.lce_tflite_model_gate_stats.argtypes, l.lce_tflite_model_gate_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
+        l.lce_tflite_model_reshape_stats.argtypes, l.lce_tflite_model_reshape_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
         l.lce_tflite_model_operator_reducer.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_fully_connected.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_softmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -259,7 +270,8 @@ class LceModel:
                  int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
                  conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
                  stem_sections: bool = False, head_sections: bool = False, conv2d_i8_sections: bool = False,
-                 head_i8_sections: bool = False, quantize_sections: bool = False, depthwise_i8_sections: bool = False):
+                 head_i8_sections: bool = False, quantize_sections: bool = False, depthwise_i8_sections: bool = False,
+                 activation_sections: bool = False, reshape_sections: bool = False, gate_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -282,7 +294,12 @@ class LceModel:
         ``quantize_sections``: the builtin QUANTIZE float32 -> int8 and DEQUANTIZE int8 -> float32 join them (the name
         ``quantize``).  ``depthwise_i8_sections``: the quantized DEPTHWISE_CONV_2D of an int8-converted network -- QuickNet's blur
         and the depthwise convolution of its stem -- joins them (``lce_hip_depthwise_conv2d_i8``; the name ``depthwise_i8``).
-        With every keyword an int8-converted network, QuickNet included, is ONE section from the image to the probabilities."""
+        With every keyword an int8-converted network, QuickNet included, is ONE section from the image to the probabilities.
+        ``activation_sections``: a standalone float RELU / RELU_N1_TO_1 / RELU6 / LOGISTIC / PRELU joins them as a step of the
+        elementwise chain (``lce_hip_elementwise_ex``; the name ``activation``).  ``reshape_sections``: a RESHAPE that keeps the
+        batch joins them as a view of the same bytes (the name ``reshape``).  ``gate_sections``: a float ADD / MUL of a
+        ``[b, H, W, C]`` tensor by a non-constant ``[b, 1, 1, C]`` one -- a squeeze-and-excite gate -- joins them as a step of the
+        same chain (the name ``gate``).  All three route through ``lce_tflite_model_open_passes``."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -301,6 +318,9 @@ class LceModel:
         self.head_i8_sections = bool(head_i8_sections)
         self.quantize_sections = bool(quantize_sections)
         self.depthwise_i8_sections = bool(depthwise_i8_sections)
+        self.activation_sections = bool(activation_sections)
+        self.reshape_sections = bool(reshape_sections)
+        self.gate_sections = bool(gate_sections)
         err = C.create_string_buffer(256)
         if any(getattr(self, keyword) for keyword in _NAMED_ONLY):
             names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]]
@@ -440,6 +460,24 @@ class LceModel:
         tflite_lib().lce_tflite_model_quantize_stats(self._h, *[C.byref(c) for c in v])
         return tuple(int(c.value) for c in v)
 
+    def activation_stats(self):
+        """(lce_hip_elementwise_ex launches, operators of every kind they ran, LceQuantize launches they absorbed) of the last run."""
+        v = [C.c_int32() for _ in range(3)]
+        tflite_lib().lce_tflite_model_activation_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
+    def gate_stats(self):
+        """(lce_hip_elementwise_ex launches that hold a gate, LceQuantize launches they absorbed) of the last run."""
+        v = [C.c_int32() for _ in range(2)]
+        tflite_lib().lce_tflite_model_gate_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
+    def reshape_stats(self):
+        """(RESHAPE operators that were a view, RESHAPE operators that cost a device-to-device copy) of the last run."""
+        v = [C.c_int32() for _ in range(2)]
+        tflite_lib().lce_tflite_model_reshape_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
         pointers) and replays them as one launch; needs a stream of its own (not the null stream)."""
@@ -472,10 +510,11 @@ class Interpreter:
                  concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
                  depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False,
                  head_sections: bool = False, conv2d_i8_sections: bool = False, head_i8_sections: bool = False,
-                 quantize_sections: bool = False, depthwise_i8_sections: bool = False):
+                 quantize_sections: bool = False, depthwise_i8_sections: bool = False, activation_sections: bool = False,
+                 reshape_sections: bool = False, gate_sections: bool = False):
         """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
         ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``, ``head_i8_sections``, ``quantize_sections``,
-        ``depthwise_i8_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+        ``depthwise_i8_sections``, ``activation_sections``, ``reshape_sections``, ``gate_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
@@ -484,7 +523,9 @@ class Interpreter:
                                     depthwise_sections=depthwise_sections, conv2d_sections=conv2d_sections,
                                     stem_sections=stem_sections, head_sections=head_sections,
                                     conv2d_i8_sections=conv2d_i8_sections, head_i8_sections=head_i8_sections,
-                                    quantize_sections=quantize_sections, depthwise_i8_sections=depthwise_i8_sections))
+                                    quantize_sections=quantize_sections, depthwise_i8_sections=depthwise_i8_sections,
+                                    activation_sections=activation_sections, reshape_sections=reshape_sections,
+                                    gate_sections=gate_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED

@@ -83,6 +83,7 @@ lce_hip_status lce_hip_malloc(void** dev_ptr, size_t bytes);
 lce_hip_status lce_hip_free(void* dev_ptr);
 lce_hip_status lce_hip_memcpy_h2d(void* dst_dev, const void* src_host, size_t bytes, void* stream);
 lce_hip_status lce_hip_memcpy_d2h(void* dst_host, const void* src_dev, size_t bytes, void* stream);
+lce_hip_status lce_hip_memcpy_d2d(void* dst_dev, const void* src_dev, size_t bytes, void* stream);   /* asynchronous on `stream`, capturable */
 lce_hip_status lce_hip_memset(void* dst_dev, int value, size_t bytes, void* stream);
 /* Page-locks [host_ptr, host_ptr + bytes) (hipHostRegister) so that copies from / to it are truly
  * asynchronous and lce_hip_bconv2d_run_host can overlap them with compute.  For buffers the caller keeps
@@ -155,6 +156,43 @@ typedef struct lce_hip_ew_step {
 lce_hip_status lce_hip_elementwise(const float* in_dev, size_t rows, size_t channels,
                                    const lce_hip_ew_step* steps, int32_t num_steps,
                                    float* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+
+/* lce_hip_elementwise_ex: the same one pass with more kinds of step -- what a ReActNet tail (ADD shift, PRELU, ADD shift), the
+ * gate of a squeeze-and-excite block (MUL by a [batch, 1, 1, C] tensor) and a standalone activation need.  The contract for
+ * `out_dev`, `out_bits_dev` and in place is lce_hip_elementwise's.  A step (1..8 of them) is one of
+ *   ADD / MUL with a SCALAR, PER_CHANNEL or TENSOR operand: exactly lce_hip_elementwise's bytes.
+ *   ADD / MUL with a PER_IMAGE_CHANNEL operand: values[batch * channels], batch = rows / rows_per_image; the element of image n,
+ *     channel c reads values[n * channels + c].  One rounding per op, never an fma; the step's clamp follows.
+ *   CLAMP: no arithmetic, only the clamp of `activation` -- a standalone RELU, RELU_N1_TO_1 or RELU6:
+ *     v = v < lo ? lo : v;  v = hi < v ? hi : v.  RELU(-0.0) = -0.0; a NaN passes.  The operand is ignored.
+ *   PRELU: v = v >= 0 ? v : fl(v * alpha), alpha the SCALAR or PER_CHANNEL operand.  -0.0 stays -0.0; a NaN takes the multiply and
+ *     stays NaN; an infinity is not clamped.  `activation` must be NONE.
+ *   LOGISTIC: the library's own bytes (no two libraries agree on them), in float32 operations that NumPy restates
+ *     (tests/activation_ref.py), on the SAME E(a) that lce_hip_softmax_f32 states below:
+ *       x >= 0:  e = E(-x);  y = 1 / fl(1 + e)
+ *       x <  0:  e = E(x);   y = e / fl(1 + e)
+ *     both divisions correctly rounded.  A NaN passes unchanged; +inf -> 1; -inf and x < -104 -> +0; -0.0 -> 0.5.  Measured on
+ *     1.8e8 arguments: at most 2.40 ulp of the float32 result from 1 / (1 + exp(-x)) in float64 (tests hold
+ *     3.40).  `activation` must be NONE; the operand is ignored.
+ * `rows_per_image` (H * W of the NHWC tensor) is needed by a PER_IMAGE_CHANNEL operand and may be 0 without one; when it is not
+ * 0 it must divide `rows`.  Refused before any device call, LCE_HIP_ERR_INVALID: NULL steps, input, operand or both outputs, an
+ * unknown op, operand kind or activation, a PRELU operand that is TENSOR or PER_IMAGE_CHANNEL, an activation on PRELU or LOGISTIC,
+ * non-zero reserved fields, a rows_per_image that does not divide rows (or 0 with a per-image operand), a pointer that is not
+ * 4-byte aligned.  Zero rows or channels is a no-op.  Asynchronous on `stream`, capturable in a HIP graph, allocates nothing. */
+typedef enum lce_hip_ew_op_ex { LCE_HIP_EW_CLAMP = 2, LCE_HIP_EW_PRELU = 3, LCE_HIP_EW_LOGISTIC = 4 } lce_hip_ew_op_ex;   /* after ADD 0, MUL 1 */
+typedef enum lce_hip_ew_operand_ex { LCE_HIP_EW_PER_IMAGE_CHANNEL = 3 } lce_hip_ew_operand_ex;   /* after SCALAR 0, PER_CHANNEL 1, TENSOR 2 */
+typedef struct lce_hip_ew_step_ex {
+  int32_t op, operand;      /* lce_hip_ew_op / _ex, lce_hip_ew_operand / _ex */
+  const float* values;      /* device: [channels], [rows * channels] or [batch * channels]; NULL for SCALAR */
+  float scalar;
+  int32_t activation;       /* an lce_hip_activation: NONE, RELU, RELU_N1_TO_1 or RELU6 */
+  int32_t reserved[2];      /* 0 */
+} lce_hip_ew_step_ex;
+lce_hip_status lce_hip_elementwise_ex(const float* in_dev, size_t rows, size_t channels, size_t rows_per_image,
+                                      const lce_hip_ew_step_ex* steps, int32_t num_steps,
+                                      float* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+/* The most blocks lce_hip_elementwise and lce_hip_elementwise_ex launch (4 waves each; a wave strides over the rest).  Host only. */
+int32_t lce_hip_elementwise_grid_cap(void);
 
 /* ------------------------------------------------------------------------------------
  * int8 residual ADD between binary layers (TFLite builtin) and the LceQuantize that follows

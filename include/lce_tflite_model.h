@@ -163,7 +163,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
                                              size_t err_len);
 
 /* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
- *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize, depthwise_i8
+ *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize, depthwise_i8, activation, reshape, gate
  * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
  * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
  * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
@@ -187,7 +187,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   SOFTMAX (25): one float32 non-constant input [b, n] or [b, 1, 1, n] and an output of the same shape; the SoftmaxOptions
  *   table is present and beta is finite and > 0.  It runs as ONE lce_hip_softmax_f32 launch (its bytes: include/lce_hip.h).
  *   Everything else stays with the host, as before: int8 or hybrid FULLY_CONNECTED, a non-constant weight, shuffled weights, a
- *   MEAN over other axes, TANH, a missing options table, RESHAPE / Flatten (so the three-layer head of BinaryAlexNet), LOGISTIC.
+ *   MEAN over other axes, TANH, a missing options table.  (RESHAPE / Flatten and LOGISTIC: `reshape` and `activation`, below.)
  *   No LceQuantize folds into a head operator.  With every name a converted network is ONE section from the image to the
  *   probabilities and no builtin operator is left for the host.
  *   conv2d_i8: the quantized builtin CONV_2D (3) of an int8-converted network -- its stem, the 1x1 behind the pool of a
@@ -242,8 +242,30 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   -- TFLite's integer arithmetic byte for byte -- whose filter and prepared table are uploaded once per model; a following
  *   LceQuantize folds into the launch's bits, and the int8 tensor is written only when something else reads it or the section
  *   delivers it.  With every name an int8 QuickNet with a float interface is ONE section from the float image to the float
- *   probabilities.  Still the host's: dilated, hybrid, uint8 or int16 depthwise convolutions, RESHAPE and the three-layer heads,
- *   LOGISTIC. */
+ *   probabilities.  Still the host's: dilated, hybrid, uint8 or int16 depthwise convolutions.
+ *   activation: a standalone float RELU (19), RELU_N1_TO_1 (20), RELU6 (21), LOGISTIC (14) or PRELU (54) joins the sections -- the
+ *   RPReLU of a ReActNet (ADD, PRELU, ADD), the sigmoid of a squeeze-and-excite gate.  One input (PRELU: two) and one output;
+ *   input and output float32 of the same shape, of rank 2 or 4 with positive extents, the input non-constant; PRELU's alpha a
+ *   constant float32 with data in the file, of shape [C], [1,1,C], [1,1,1,C], [1] or [].  It joins the epoch in which it becomes
+ *   ready, and `stem` applies to it as to any opt-in.  It is a step of the elementwise chain: lce_tflite_model_run_section extends
+ *   a chain of absorbed ADD / MUL (`elementwise`) through it by the chain's own rules (one reader, not a section output, up to 8
+ *   steps), and a chain that holds one runs as ONE lce_hip_elementwise_ex launch (its arithmetic, LOGISTIC's stated bytes
+ *   included: include/lce_hip.h) whose bit output replaces a following LceQuantize: with `elementwise,activation` the whole tail
+ *   of a ReActNet block behind its binary convolution -- batch norm, shortcut, shift, PRELU, shift, sign bits -- is one pass over
+ *   the tensor.  A chain of ADD / MUL alone still runs through lce_hip_elementwise.
+ *   reshape: a builtin RESHAPE (22) of a non-constant float32, int8 or int32 tensor joins the sections when it keeps the batch:
+ *   input and output of the same type (int8: the same quantization), of rank 2 or 4 with positive extents, the same leading
+ *   extent and the same element count behind it -- Flatten in front of a Dense layer, Reshape((1,1,C)) of a gate.  It is judged
+ *   by the DECLARED shape of its output tensor; its optional second input must be a constant.  It is a view of the same bytes: no
+ *   launch, and at most one device-to-device copy where the output has a buffer of its own (the section delivers it).
+ *   gate: a float ADD (0) / MUL (18) whose two inputs are both non-constant, one of the output's [b,H,W,C] shape and the other
+ *   [b,1,1,C] -- the per-image scale of a RealToBinaryNet block -- joins the sections, with a fused activation lce_hip_elementwise
+ *   knows.  It is a step of the same chain (a PER_IMAGE_CHANNEL operand of lce_hip_elementwise_ex); the gate is always the
+ *   operand, the [b,H,W,C] tensor the one streamed.  A [b,C] operand does not qualify: TFLite's broadcast aligns it to the
+ *   trailing axes, so it is not per image.
+ *   None of the three moves anything unless it is named.  Still the host's: TANH, HARD_SWISH, LEAKY_RELU, int8 activations, a full
+ *   [H,W,C] PRELU alpha, rank-2 ADD / MUL (the dense batch norm of BinaryAlexNet), a RESHAPE that moves the batch extent or whose
+ *   shape is computed at run time, STRIDED_SLICE, PAD. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -400,6 +422,15 @@ void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t
  * launches; and for the float / int8 boundary ("quantize"): lce_hip_quantize_f32_i8 and lce_hip_dequantize_i8_f32 launches. */
 void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
 void lce_tflite_model_quantize_stats(lce_tflite_model* model, int32_t* quantize, int32_t* dequantize);
+/* The LAST run's lce_hip_elementwise_ex launches ("activation" and "gate" of lce_tflite_model_open_passes): launches (one per
+ * chain that holds a standalone activation or a gate), the operators of every kind -- ADD / MUL included -- inside them, and the
+ * LceQuantize launches they absorbed.  Chains of ADD / MUL alone are lce_tflite_model_elementwise_stats', as before. */
+void lce_tflite_model_activation_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
+/* ... those of them that hold a gate, and the LceQuantize launches these absorbed. */
+void lce_tflite_model_gate_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded);
+/* The LAST run's absorbed RESHAPE operators ("reshape"): those that were a view of their input's buffer, and those that cost one
+ * device-to-device copy. */
+void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
