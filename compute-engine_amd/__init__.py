@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "lce_hip_depthwise_conv2d_i8", "lce_hip_depthwise_conv2d_i8_check", "lce_hip_depthwise_conv2d_i8_prepare",
     "lce_hip_depthwise_conv2d_i8_path", "lce_hip_depthwise_conv2d_i8_forced",
     "lce_hip_fully_connected_f32", "lce_hip_fully_connected_f32_check", "lce_hip_softmax_f32", "lce_hip_softmax_f32_check",
+    "lce_hip_bfc_check", "lce_hip_bfc_prepare", "lce_hip_binary_fully_connected",
     "lce_hip_fully_connected_i8", "lce_hip_fully_connected_i8_check", "lce_hip_fully_connected_i8_prepare",
     "lce_hip_mean_i8", "lce_hip_mean_i8_check", "lce_hip_mean_i8_prepare", "lce_hip_softmax_i8", "lce_hip_softmax_i8_check",
     "lce_hip_quantize_f32_i8", "lce_hip_dequantize_i8_f32",
@@ -149,6 +150,11 @@ class FcDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("batch", "inputs", "outputs", "activation")]
 
 
+class BfcDesc(C.Structure):
+    """``lce_hip_bfc_desc``."""
+    _fields_ = [(n, C.c_int32) for n in ("batch", "inputs", "outputs", "activation")]
+
+
 class FcI8Desc(C.Structure):
     """``lce_hip_fc_i8_desc``."""
     _fields_ = FcDesc._fields_ + [("input_scale", C.c_float), ("input_zero_point", C.c_int32), ("output_scale", C.c_float),
@@ -235,6 +241,9 @@ def lib() -> C.CDLL:
         l.lce_hip_fully_connected_f32_check.argtypes = [C.POINTER(FcDesc)]
         l.lce_hip_softmax_f32.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_softmax_f32_check.argtypes = [C.c_size_t, C.c_size_t, C.c_float]
+        l.lce_hip_bfc_check.argtypes = [C.POINTER(BfcDesc)]
+        l.lce_hip_bfc_prepare.argtypes = [C.POINTER(BfcDesc)] + [C.c_void_p] * 3
+        l.lce_hip_binary_fully_connected.argtypes = [C.POINTER(BfcDesc)] + [C.c_void_p] * 7
         l.lce_hip_fully_connected_i8.argtypes = [C.POINTER(FcI8Desc)] + [C.c_void_p] * 5
         l.lce_hip_fully_connected_i8_check.argtypes = [C.POINTER(FcI8Desc)]
         l.lce_hip_fully_connected_i8_prepare.argtypes = [C.POINTER(FcI8Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
@@ -1281,6 +1290,74 @@ def softmax(x, beta: float = 1.0, out=None, stream: int | None = None):
         check(lib().lce_hip_softmax_f32(rows, cols, float(beta), _dev_ptr(xd), _dev_ptr(out_d),
                                         C.c_void_p(_stream_or_current(stream, dev))))
     return _results(host, out_d, None, out)[0]
+
+
+# ---------------------------------------------------------------------------------------
+# the binarized Dense layer (include/lce_hip.h)
+# ---------------------------------------------------------------------------------------
+def bfc_prepare(w):
+    """The sign bits and row scales of one binarized Dense layer for ``binary_fully_connected`` (``lce_hip_bfc_prepare``, host
+    only).  ``w``: float32 NumPy [outputs, inputs], the weights of the converted model's float FULLY_CONNECTED: every entry of
+    row o must be +s[o] or -s[o], s[o] finite with 2^-100 <= s[o] <= 2^100.  Returns ``(bits, scale)``: int32
+    [outputs, ceil(inputs/32)] (LSB first, bit 1 for a negative weight, padding bits 0) and float32 [outputs].  Raises
+    ``LceHipError`` (ERR_UNSUPPORTED) for other weights -- a zero, a NaN, an infinity, mixed magnitudes -- and for
+    inputs >= 2^23."""
+    ws = tuple(int(v) for v in w.shape)
+    if not isinstance(w, np.ndarray) or _dtype_name(w) != "float32" or len(ws) != 2 or min(ws) < 1:
+        raise ValueError("bfc_prepare: w must be a non-empty float32 NumPy array [outputs, inputs], got %s %r" % (getattr(w, "dtype", type(w)), ws))
+    n, k = ws
+    desc = BfcDesc(1, k, n, ACT_NONE)
+    check(lib().lce_hip_bfc_check(C.byref(desc)))                 # (before the buffers are sized)
+    wh = np.ascontiguousarray(w)
+    bits, scale = np.zeros((n, bitpacked_size(k)), np.int32), np.zeros(n, np.float32)
+    check(lib().lce_hip_bfc_prepare(C.byref(desc), _host_ptr(wh), _host_ptr(bits), _host_ptr(scale)))
+    return bits, scale
+
+
+def _bfc_check(x_bits, inputs, weight_bits, scale, bias, activation, out, out_bits):
+    """Argument checks of ``binary_fully_connected`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.
+    Returns (BfcDesc, output shape)."""
+    who = "binary_fully_connected"
+    if int(inputs) != inputs or int(inputs) < 1:
+        raise ValueError("%s: inputs must be a positive integer, got %r" % (who, inputs))
+    kw = bitpacked_size(int(inputs))
+    xs, ws = tuple(int(v) for v in x_bits.shape), tuple(int(v) for v in weight_bits.shape)
+    if _dtype_name(x_bits) != "int32" or len(xs) != 2 or xs[0] < 1 or xs[1] != kw:
+        raise ValueError("%s: x_bits must be int32 [batch, %d], got %s %r" % (who, kw, x_bits.dtype, xs))
+    if _dtype_name(weight_bits) != "int32" or len(ws) != 2 or ws[0] < 1 or ws[1] != kw:
+        raise ValueError("%s: weight_bits must be int32 [outputs, %d], got %s %r" % (who, kw, weight_bits.dtype, ws))
+    if _dtype_name(scale) != "float32" or tuple(scale.shape) != (ws[0],):
+        raise ValueError("%s: scale must be float32 [%d], got %s %r" % (who, ws[0], scale.dtype, tuple(scale.shape)))
+    if bias is not None and (_dtype_name(bias) != "float32" or tuple(bias.shape) != (ws[0],)):
+        raise ValueError("%s: bias must be float32 [%d], got %s %r" % (who, ws[0], bias.dtype, tuple(bias.shape)))
+    _padding_activation_check(who, None, activation)
+    shape = (xs[0], ws[0])
+    _check_outputs(who, None if out is True else out, None if out_bits is False else out_bits, "float32", shape)
+    return BfcDesc(xs[0], int(inputs), ws[0], int(activation)), shape
+
+
+def binary_fully_connected(x_bits, inputs, weight_bits, scale, bias=None, activation=ACT_NONE, out=True, out_bits=False,
+                           stream: int | None = None):
+    """A binarized Dense layer (larq's QuantDense behind a sign) and the LceQuantize of its result in one launch on the FP4 matrix
+    cores (``lce_hip_binary_fully_connected``).  ``x_bits``: int32 [batch, ceil(inputs/32)] on the device (or NumPy: copied to
+    cuda:0 and back), the bits of the activations (``bitpack``: bit 1 = negative).  ``weight_bits``, ``scale``: from
+    ``bfc_prepare``.  ``bias``: float32 [outputs] or None.  Per output element t = the exact integer sum of a_k * w_k,
+    p = t * scale[o], v = p + bias[o] (two roundings), the clamp, bit = v < 0 (include/lce_hip.h).  ``out``: True for a new
+    float32 [batch, outputs] tensor, a tensor to fill (it must not overlap an operand), False for none.  ``out_bits``: True for
+    new int32 [batch, ceil(outputs/32)] bits, a tensor to fill, False for none.  Returns ``(out or None, bits or None)``."""
+    import torch
+    who = "binary_fully_connected"
+    desc, shape = _bfc_check(x_bits, inputs, weight_bits, scale, bias, activation, out, out_bits)
+    host = isinstance(x_bits, np.ndarray)
+    dev = torch.device("cuda:0") if host else x_bits.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x_bits's")
+    xd, wd, sd, bd = on_dev(x_bits), on_dev(weight_bits), on_dev(scale), None if bias is None else on_dev(bias)
+    out_d = None if out is False else torch.empty(shape, dtype=torch.float32, device=dev) if out is True else on_dev(out)
+    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_binary_fully_connected(C.byref(desc), _dev_ptr(xd), _dev_ptr(wd), _dev_ptr(sd), _dev_ptr(bd), _dev_ptr(out_d),
+                                                   _dev_ptr(bits_d), C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
 
 
 # ---------------------------------------------------------------------------------------

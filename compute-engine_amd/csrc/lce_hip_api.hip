@@ -28,6 +28,7 @@
 #include "lce_kernels_head.h"        // (lce_tu_head.hip)
 #include "lce_kernels_head_i8.h"     // (lce_tu_head_i8.hip)
 #include "lce_kernels_depthwise_i8.h"   // (lce_tu_depthwise_i8.hip)
+#include "lce_kernels_bfc.h"         // (lce_tu_bfc.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
 #include "lce_tu_valu.hip"
@@ -56,6 +57,7 @@
 #include "lce_tu_head.hip"
 #include "lce_tu_head_i8.hip"
 #include "lce_tu_depthwise_i8.hip"
+#include "lce_tu_bfc.hip"
 #endif
 #include "lce_plan.h"
 #include "lce_prepare.h"
@@ -1180,6 +1182,80 @@ lce_hip_status lce_hip_softmax_f32(size_t rows, size_t cols, float beta, const f
   memset(&a, 0, sizeof a);
   a.in = in_dev; a.out = out_dev; a.rows = rows; a.cols = (uint32_t)cols; a.beta = beta;
   const int e = lce::launch_softmax(a, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// the binarized Dense layer (lce_kernels_bfc.h)
+// ------------------------------------------------------------------------------------
+lce_hip_status lce_hip_bfc_check(const lce_hip_bfc_desc* d) {
+  const char* who = "lce_hip_binary_fully_connected";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->batch <= 0 || d->inputs <= 0 || d->outputs <= 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: extents must be positive, got [%d, %d] -> %d outputs", who, (int)d->batch, (int)d->inputs,
+                (int)d->outputs);
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  // (every partial sum stays an exact float32 integer -- the planner's bound on a convolution's K)
+  if (d->inputs >= (1 << 23)) return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: 2^23 or more inputs are not supported", who);
+  // (the kernel numbers its 32 x 32 tiles in 32 bits)
+  const uint64_t tiles = (((uint64_t)d->batch + lce::kBfcTile - 1) / lce::kBfcTile) * (((uint64_t)d->outputs + lce::kBfcTile - 1) / lce::kBfcTile);
+  if (tiles >= (1ull << 31)) return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: an output of more than 2^31 tiles of 32 x 32 is not supported", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_bfc_prepare(const lce_hip_bfc_desc* d, const float* weights_host, int32_t* bits, float* scale) {
+  const char* who = "lce_hip_bfc_prepare";
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (!weights_host || !bits || !scale) return fail(LCE_HIP_ERR_INVALID, "%s: null weights, bits or scale", who);
+  if (lce_hip_status s = lce_hip_bfc_check(d)) return s;
+  const size_t K = (size_t)d->inputs, N = (size_t)d->outputs, Kw = (K + 31) / 32;
+  const float smin = std::ldexp(1.0f, -100), smax = std::ldexp(1.0f, 100);
+  for (size_t o = 0; o < N; ++o) {
+    const float* row = weights_host + o * K;
+    const float s = std::fabs(row[0]);
+    if (!(s >= smin && s <= smax))       // (a NaN fails both comparisons)
+      return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the weights of output %zu are not +-s with 2^-100 <= s <= 2^100 (the first is %g)", who, o,
+                  (double)row[0]);
+    uint32_t* words = (uint32_t*)bits + o * Kw;
+    for (size_t w = 0; w < Kw; ++w) words[w] = 0u;
+    for (size_t k = 0; k < K; ++k) {
+      if (!(std::fabs(row[k]) == s))
+        return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: the weights of output %zu are not all +-%g (input %zu holds %g)", who, o, (double)s, k,
+                    (double)row[k]);
+      if (std::signbit(row[k])) words[k / 32] |= 1u << (k % 32);
+    }
+    scale[o] = s;
+  }
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_binary_fully_connected(const lce_hip_bfc_desc* d, const int32_t* in_bits_dev, const int32_t* weight_bits_dev,
+                                              const float* scale_dev, const float* bias_dev, float* out_dev, int32_t* out_bits_dev,
+                                              void* stream) {
+  const char* who = "lce_hip_binary_fully_connected";
+  if (lce_hip_status s = check_pointers(who, d, in_bits_dev, /*has_filter=*/true, weight_bits_dev, out_dev, out_bits_dev)) return s;
+  if (!scale_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null scale", who);
+  if (lce_hip_status s = lce_hip_bfc_check(d)) return s;
+  const uint64_t M = (uint64_t)d->batch, K = (uint64_t)d->inputs, N = (uint64_t)d->outputs, Kw = (K + 31) / 32, wpr = (N + 31) / 32;
+  const Span in(in_bits_dev, M * Kw * 4), weights(weight_bits_dev, N * Kw * 4), scale(scale_dev, N * 4), bias(bias_dev, N * 4);
+  const Span out(out_dev, M * N * 4), bits(out_bits_dev, M * wpr * 4);
+  if (lce_hip_status s = check_operand_ranges(who, in, weights, bias, out, bits, /*float_operands=*/true)) return s;
+  if (meet(out.lo, out.hi, scale.lo, scale.hi) || meet(bits.lo, bits.hi, scale.lo, scale.hi))
+    return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the scale", who);
+  if (scale.lo % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: every pointer must be 4-byte aligned", who);
+  if (lce_hip_status s = require_device()) return s;
+  lce::BfcArgs a;
+  memset(&a, 0, sizeof a);
+  a.in = (const uint32_t*)in_bits_dev; a.weights = (const uint32_t*)weight_bits_dev; a.scale = scale_dev; a.bias = bias_dev;
+  a.out = out_dev; a.bits = (uint32_t*)out_bits_dev;
+  a.M = (uint32_t)M; a.K = (uint32_t)K; a.N = (uint32_t)N; a.Kw = (uint32_t)Kw;
+  a.ntiles = (uint32_t)wpr;
+  a.tiles = (uint32_t)((M + lce::kBfcTile - 1) / lce::kBfcTile) * a.ntiles;
+  float_activation_range(d->activation, &a.lo, &a.hi);
+  const bool vec = Kw % 4 == 0 && in.lo % 16 == 0 && weights.lo % 16 == 0;
+  const int e = lce::launch_binary_fully_connected(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }

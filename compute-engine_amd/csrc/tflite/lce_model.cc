@@ -22,19 +22,20 @@ struct lce_tflite_section {
 };
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
-       kAbsorbedConvI8, kAbsorbedDepthwiseI8, kAbsorbedMean, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
+       kAbsorbedConvI8, kAbsorbedDepthwiseI8, kAbsorbedMean, kAbsorbedBinaryDense, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
        kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedActivation, kAbsorbedReshape, kAbsorbedGate, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
 enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u,
-       kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u };
+       kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u, kInternalBinaryDense = 256u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
-  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize", "depthwise_i8", "activation", "reshape", "gate")
+  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize", "depthwise_i8", "activation", "reshape", "gate", "binary_dense")
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
+  std::vector<int32_t> producer;              // per tensor: the first operator that lists it as an output; -1: none
   void Partition();
   // ---- state of lce_tflite_model_run_section (one run at a time per model) ----
   std::mutex run_mu;
@@ -42,7 +43,7 @@ struct lce_tflite_model {
   struct DevBuf { void* ptr = nullptr; size_t bytes = 0; };
   std::map<int32_t, DevBuf> scratch;                                    // intermediate tensors of a section, grow-only
   std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
-  std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED operator: its prepare's table, uploaded once
+  std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED and binary Dense operator: its prepare's table, uploaded once
   std::map<int32_t, std::vector<int32_t>> host_tables;                  // ... as Partition() prepared it; dropped once it is on the device
   // What one run launched.  A recorded graph keeps the record of its recording, so a replay reports the same numbers.
   struct RunStats {
@@ -50,6 +51,7 @@ struct lce_tflite_model {
     int32_t ew_ops = 0;                                                 // ADD / MUL operators inside the lce_hip_elementwise launches
     int32_t ex_ops = 0;                                                 // operators of every kind inside the lce_hip_elementwise_ex launches
     int32_t reshape_views = 0, reshape_copies = 0;                      // absorbed RESHAPE operators: aliased / copied device to device
+    int32_t dequantize_skipped = 0;                                     // LceDequantize operators only binary Dense layers read: not launched
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
     Pass pass[kAbsorbedCount];                                          // by kAbsorbed* kind ([0] unused)
   };
@@ -661,6 +663,53 @@ bool SoftmaxCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return lce_hip_softmax_f32_check((size_t)id[0], (size_t)id[3], o.softmax_beta) == LCE_HIP_OK;
 }
 
+// ---- the binarized Dense layer (lce_tflite_model_open_passes, "binary_dense") ----
+// The converter leaves larq's QuantDense behind a sign as LceQuantize -> LceDequantize -> a float FULLY_CONNECTED whose row o
+// holds only +-s[o].  The static half of "a builtin FULLY_CONNECTED that runs as lce_hip_binary_fully_connected on the BITS":
+// FullyConnectedCandidate's rules, an input of rank 2 or [b, 1, 1, K], and the entry's own check accepts the descriptor.
+// Partition() decides the other half (BinaryDenseSource, BinaryDensePrepare); what it refuses falls to the rows below ("head").
+lce_hip_bfc_desc BinaryDenseDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
+  const lce_hip_fc_desc f = FullyConnectedDesc(M, o, batch);
+  lce_hip_bfc_desc d;
+  memset(&d, 0, sizeof d);
+  d.batch = f.batch; d.inputs = f.inputs; d.outputs = f.outputs; d.activation = f.activation;
+  return d;
+}
+bool BinaryDenseCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (!FullyConnectedCandidate(M, o)) return false;
+  int32_t id[4];
+  if (!Carried(M.tensors[o.inputs[0]], id) || id[1] != 1 || id[2] != 1) return false;
+  const lce_hip_bfc_desc d = BinaryDenseDesc(M, o, id[0]);
+  return lce_hip_bfc_check(&d) == LCE_HIP_OK;
+}
+// The bit tensor a binary Dense candidate `o` reads: its float input is the output of operator `producer`, an LceDequantize
+// whose own input is a non-constant bitpacked int32 tensor of rank 2 or [b, 1, 1, ceil(K/32)] with the same batch.  -1: none.
+int32_t BinaryDenseSource(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t producer) {
+  if (producer < 0) return -1;
+  const lce_tfl::Operator& dq = M.operators[producer];
+  if (dq.builtin_code != lce_tfl::kBuiltinCustom || dq.custom_code != "LceDequantize" || dq.inputs.size() != 1 || dq.outputs.size() != 1 ||
+      dq.outputs[0] != o.inputs[0] || dq.inputs[0] < 0 || dq.inputs[0] >= (int32_t)M.tensors.size())
+    return -1;
+  const lce_tfl::Tensor& bits = M.tensors[dq.inputs[0]];
+  int32_t bd[4], id[4];
+  if (bits.type != lce_tfl::kTensorInt32 || bits.data || !Carried(bits, bd) || !Carried(M.tensors[o.inputs[0]], id)) return -1;
+  if (bd[0] != id[0] || bd[1] != 1 || bd[2] != 1 || bd[3] != (id[3] + 31) / 32) return -1;
+  return dq.inputs[0];
+}
+// lce_hip_bfc_prepare on the file's weights: the table is the sign bits [N][ceil(K/32)] followed by the N scales (float32 bit
+// patterns), kept like the int8 passes' tables.
+lce_hip_status BinaryDensePrepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_hip_bfc_desc d = BinaryDenseDesc(M, o, 1);
+  const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
+  const size_t N = (size_t)d.outputs, K = (size_t)d.inputs, Kw = (K + 31) / 32;
+  std::vector<float> weights(N * K), scale(N);
+  memcpy(weights.data(), w.data, N * K * 4);                 // (the file's bytes need not be aligned)
+  table->assign(N * Kw + N, 0);
+  if (lce_hip_status s = lce_hip_bfc_prepare(&d, weights.data(), table->data(), scale.data())) return s;
+  memcpy(table->data() + N * Kw, scale.data(), N * 4);
+  return LCE_HIP_OK;
+}
+
 // ---- the int8 classifier head and the float / int8 boundary (lce_tflite_model_open_passes, "head_i8" and "quantize") ----
 // An int8 activation tensor as the entries want it: quantized with exactly ONE scale and a zero point that is an int8 value.
 bool Int8Activation(const lce_tfl::Tensor& t) {
@@ -913,15 +962,33 @@ void lce_tflite_model::Partition() {
   std::vector<char> produced(n_t, 0), is_output(n_t, 0), is_lce(n_ops, 0), candidate(n_ops, 0);
   const uint32_t words[3] = {flags, flags_ext, flags_int};
   readers.assign(n_t, {});
+  producer.assign(n_t, -1);
   absorbed.assign(n_ops, 0);
   std::vector<int32_t> unready(n_ops, 0);
+  for (int i = 0; i < n_ops; ++i)
+    for (int32_t t : m.operators[i].outputs)
+      if (valid(t) && producer[t] < 0) producer[t] = i;
   for (int i = 0; i < n_ops; ++i) {
     is_lce[i] = IsLceOp(m.operators[i]) ? 1 : 0;
     // the first pass, in the table's order, that is enabled and whose predicate holds.  An absorbed operator joins the epoch in
     // which it becomes ready, so it lands in a section exactly when the last of its inputs was produced by an LCE epoch (one
     // that is ready from the start -- a stem op -- is a builtin one without LCE_TFLITE_SECTIONS_EXT_STEM, below)
-    for (const FusedPass& p : kPasses)
-      if (!candidate[i] && (words[p.word] & p.bit) && p.candidate(m, m.operators[i])) candidate[i] = (char)p.kind;
+    auto first_pass = [&](int from_kind) {
+      for (const FusedPass& p : kPasses)
+        if (p.kind >= from_kind && (words[p.word] & p.bit) && p.candidate(m, m.operators[i])) return p.kind;
+      return 0;
+    };
+    candidate[i] = (char)first_pass(1);
+    // a binary Dense layer also needs its bits -- the input of the LceDequantize that feeds it -- and weights lce_hip_bfc_prepare
+    // accepts: prepared here, once, and kept for the first run.  What fails either is left to the rows below its own ("head")
+    if (candidate[i] == kAbsorbedBinaryDense) {
+      std::vector<int32_t> table;
+      if (BinaryDenseSource(m, m.operators[i], producer[m.operators[i].inputs[0]]) >= 0 &&
+          BinaryDensePrepare(m, m.operators[i], &table) == LCE_HIP_OK)
+        host_tables[i] = std::move(table);
+      else
+        candidate[i] = (char)first_pass(kAbsorbedBinaryDense + 1);
+    }
     // an int8 CONV_2D also needs constants lce_hip_conv2d_i8_prepare accepts: prepared here, once, and kept for the first run
     if (candidate[i] == kAbsorbedConvI8) {
       std::vector<int32_t> table;
@@ -940,7 +1007,8 @@ void lce_tflite_model::Partition() {
       if (FullyConnectedI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
       else candidate[i] = 0;
     }
-    // a head operator (MEAN, FULLY_CONNECTED, SOFTMAX, float or int8) is queued as the LCE operators are, whatever made it ready:
+    // a head operator (MEAN, FULLY_CONNECTED -- float, int8 or binary: kAbsorbedBinaryDense lies inside the range --, SOFTMAX) is
+    // queued as the LCE operators are, whatever made it ready:
     // behind a host operator the head is a section of its own, behind the body it joins the body's epoch
     if (candidate[i] >= kAbsorbedMean && candidate[i] <= kAbsorbedSoftmaxI8) is_lce[i] = 1;
     for (int32_t t : m.operators[i].outputs)
@@ -1103,7 +1171,8 @@ lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, co
       {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8},
       {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize},
       {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
-      {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate}};
+      {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate},
+      {"binary_dense", 2, kInternalBinaryDense}};
   uint32_t words[3] = {0u, 0u, 0u};
   std::string refusal;
   if (!passes) refusal = "null passes";
@@ -1999,6 +2068,45 @@ struct Walk {
                     });
   }
 
+  // An absorbed binarized Dense layer ("binary_dense" of lce_tflite_model_open_passes) as ONE lce_hip_binary_fully_connected launch
+  // on the BIT tensor its LceDequantize reads; the dequantized floats are never read.  The first LceQuantize of the section that
+  // reads the result folds into the launch (a hidden binary Dense layer then writes only bits).  The table Partition() had
+  // lce_hip_bfc_prepare make of the file's weights -- sign bits, then scales -- is uploaded once per model.
+  lce_hip_status BinaryDense(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    const lce_hip_bfc_desc d = BinaryDenseDesc(M, op, batch);
+    if (lce_hip_status s = lce_hip_bfc_check(&d)) return s;
+    const int32_t bits_t = BinaryDenseSource(M, op, model->producer[op.inputs[0]]);
+    if (bits_t < 0) return Fail(LCE_HIP_ERR_INVALID, "run_section: a binary FULLY_CONNECTED without an LceDequantize in front of it");
+    // the inferred shape and type of the bits must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    auto it = shapes.find(bits_t);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a binary FULLY_CONNECTED reads bits nothing produced");
+    if (!Agrees(it->second, lce_tfl::kTensorInt32, 1, 1, (d.inputs + 31) / 32))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a binary FULLY_CONNECTED's bits do not have the shape or type their producer infers");
+    const Shape os = HeadShape(1, 1, d.outputs);
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(bits_t, "a binary FULLY_CONNECTED's bits", &in)) return s;
+    const int32_t* table = nullptr;
+    if (lce_hip_status s = TableOnDevice(i, "a binary FULLY_CONNECTED", &table)) return s;
+    const float* bias = nullptr;
+    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    const size_t words = (size_t)d.outputs * (size_t)((d.inputs + 31) / 32);
+    if (lce_hip_status s = lce_hip_binary_fully_connected(&d, (const int32_t*)in, table, (const float*)(table + words), bias, (float*)out,
+                                                          (int32_t*)bits, stream))
+      return s;
+    return Launched(kAbsorbedBinaryDense, fold);
+  }
+
   // An absorbed float SOFTMAX as ONE lce_hip_softmax_f32 launch.
   lce_hip_status Softmax(int32_t i) {
     const lce_tfl::Operator& op = model->m.operators[i];
@@ -2091,12 +2199,23 @@ struct Walk {
   lce_hip_status Dequantize(int32_t i, const Shape& in, const void* in_dev) {                    // quantization.cc:43-74,116-147
     const lce_tfl::Operator& op = model->m.operators[i];
     const lce_tfl::Tensor& OT = model->m.tensors[op.outputs[0]];
-    if (OT.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "LceDequantize: the output's channel count comes from the file (4-D)");
+    // (any rank in the reference, quantization.cc:55-66; here rank 4, or rank 2 carried as [b, 1, 1, C] like every rank-2 tensor of the walk)
+    int32_t od[4];
+    if (!Carried(OT, od)) return Fail(LCE_HIP_ERR_UNSUPPORTED, "LceDequantize: the output's channel count comes from the file (2-D or 4-D)");
     Shape out = in;
     out.type = OT.type;
-    out.dims[3] = OT.shape[3];
+    out.dims[3] = od[3];
     if ((out.dims[3] + 31) / 32 != in.dims[3]) return Fail(LCE_HIP_ERR_INVALID, "LceDequantize: output channels do not match the packed input");
     shapes[op.outputs[0]] = out;
+    // Binary Dense layers read the BITS.  When they, in this section, are the only readers and the section does not deliver the
+    // floats, nothing reads them: no launch and no buffer (the shape stays registered)
+    bool skip = !IsSectionOutput(op.outputs[0]) && !model->readers[op.outputs[0]].empty();
+    for (int32_t r : model->readers[op.outputs[0]])
+      skip = skip && model->absorbed[r] == kAbsorbedBinaryDense && std::binary_search(sec.ops.begin(), sec.ops.end(), r);
+    if (skip) {
+      if (run) ++model->last.dequantize_skipped;
+      return LCE_HIP_OK;
+    }
     if (!run) return LCE_HIP_OK;
     void* o = nullptr;
     if (lce_hip_status s = BufferFor(op.outputs[0], out.bytes(), &o)) return s;
@@ -2186,7 +2305,7 @@ struct Walk {
       const lce_tfl::Tensor& T = M.tensors[t];
       Shape sh;
       // (a rank-2 input -- of a head that starts behind a host operator -- is carried as [batch, 1, 1, C])
-      if (T.shape.size() == 2 && (model->flags_int & (kInternalHead | kInternalHeadI8 | kInternalQuantize | kInternalActivation | kInternalReshape))) {
+      if (T.shape.size() == 2 && (model->flags_int & (kInternalHead | kInternalHeadI8 | kInternalQuantize | kInternalActivation | kInternalReshape | kInternalBinaryDense))) {
         if (!Carried(T, sh.dims)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a section input with an extent that is not positive");
       } else {
         if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
@@ -2224,6 +2343,8 @@ const FusedPass kPasses[kAbsorbedCount - 1] = {
     {kAbsorbedDepthwiseI8, 2, kInternalDepthwiseI8, DepthwiseI8Candidate, &Walk::DepthwiseI8},
     // the classifier head: one internal flag enables the three rows (lce_tflite_model_open_passes, "head")
     {kAbsorbedMean, 2, kInternalHead, MeanCandidate, &Walk::Mean},
+    // the binarized Dense layer ("binary_dense"): in front of the head's FULLY_CONNECTED row, which takes what this one refuses
+    {kAbsorbedBinaryDense, 2, kInternalBinaryDense, BinaryDenseCandidate, &Walk::BinaryDense},
     {kAbsorbedFullyConnected, 2, kInternalHead, FullyConnectedCandidate, &Walk::FullyConnected},
     {kAbsorbedSoftmax, 2, kInternalHead, SoftmaxCandidate, &Walk::Softmax},
     // the int8 head ("head_i8") and the float / int8 boundary ("quantize"): no float predicate above takes an int8 MEAN /
@@ -2374,6 +2495,13 @@ void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t
   PassStats(model, kAbsorbedMean, mean, nullptr);
   PassStats(model, kAbsorbedFullyConnected, fully_connected, nullptr);
   PassStats(model, kAbsorbedSoftmax, softmax, nullptr);
+}
+
+void lce_tflite_model_binary_dense_stats(lce_tflite_model* model, int32_t* launches, int32_t* dequantize_skipped, int32_t* quantize_absorbed) {
+  PassStats(model, kAbsorbedBinaryDense, launches, quantize_absorbed);
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  if (dequantize_skipped) *dequantize_skipped = model->last.dequantize_skipped;
 }
 
 void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {

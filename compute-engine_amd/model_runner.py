@@ -145,10 +145,11 @@ _PASS_NAMES = {"elementwise_sections": "elementwise", "int8_add_sections": "int8
                "pool_sections": "pool", "conv1x1_sections": "conv1x1", "depthwise_sections": "depthwise",
                "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head", "conv2d_i8_sections": "conv2d_i8",
                "head_i8_sections": "head_i8", "quantize_sections": "quantize", "depthwise_i8_sections": "depthwise_i8",
-               "activation_sections": "activation", "reshape_sections": "reshape", "gate_sections": "gate"}
+               "activation_sections": "activation", "reshape_sections": "reshape", "gate_sections": "gate",
+               "binary_dense_sections": "binary_dense"}
 # the keywords whose names only ``lce_tflite_model_open_passes`` knows, in the order their names are passed
 _NAMED_ONLY = ("head_sections", "conv2d_i8_sections", "head_i8_sections", "quantize_sections", "depthwise_i8_sections",
-               "activation_sections", "reshape_sections", "gate_sections")
+               "activation_sections", "reshape_sections", "gate_sections", "binary_dense_sections")
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
 # ``lce_tflite_model_<pass>_stats``: the counters each reports
 _PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2,
@@ -190,6 +191,7 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_activation_stats.argtypes, l.lce_tflite_model_activation_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
         l.lce_tflite_model_gate_stats.argtypes, l.lce_tflite_model_gate_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
         l.lce_tflite_model_reshape_stats.argtypes, l.lce_tflite_model_reshape_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
+        l.lce_tflite_model_binary_dense_stats.argtypes, l.lce_tflite_model_binary_dense_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
         l.lce_tflite_model_operator_reducer.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_fully_connected.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_softmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -271,7 +273,8 @@ class LceModel:
                  conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
                  stem_sections: bool = False, head_sections: bool = False, conv2d_i8_sections: bool = False,
                  head_i8_sections: bool = False, quantize_sections: bool = False, depthwise_i8_sections: bool = False,
-                 activation_sections: bool = False, reshape_sections: bool = False, gate_sections: bool = False):
+                 activation_sections: bool = False, reshape_sections: bool = False, gate_sections: bool = False,
+                 binary_dense_sections: bool = False):
         """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -299,7 +302,10 @@ class LceModel:
         elementwise chain (``lce_hip_elementwise_ex``; the name ``activation``).  ``reshape_sections``: a RESHAPE that keeps the
         batch joins them as a view of the same bytes (the name ``reshape``).  ``gate_sections``: a float ADD / MUL of a
         ``[b, H, W, C]`` tensor by a non-constant ``[b, 1, 1, C]`` one -- a squeeze-and-excite gate -- joins them as a step of the
-        same chain (the name ``gate``).  All three route through ``lce_tflite_model_open_passes``."""
+        same chain (the name ``gate``).  All three route through ``lce_tflite_model_open_passes``.
+        ``binary_dense_sections``: a binarized Dense layer -- LceQuantize -> LceDequantize -> a float FULLY_CONNECTED whose rows
+        hold only +-s -- joins them and runs on the bits as ONE ``lce_hip_binary_fully_connected`` launch on the FP4 matrix cores
+        (the name ``binary_dense``); with ``head_sections`` too, the float entry takes the Dense layers this one refuses."""
         if not isinstance(flatbuffer, (bytes, bytearray)):
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
@@ -321,6 +327,7 @@ class LceModel:
         self.activation_sections = bool(activation_sections)
         self.reshape_sections = bool(reshape_sections)
         self.gate_sections = bool(gate_sections)
+        self.binary_dense_sections = bool(binary_dense_sections)
         err = C.create_string_buffer(256)
         if any(getattr(self, keyword) for keyword in _NAMED_ONLY):
             names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]]
@@ -472,6 +479,13 @@ class LceModel:
         tflite_lib().lce_tflite_model_gate_stats(self._h, *[C.byref(c) for c in v])
         return tuple(int(c.value) for c in v)
 
+    def binary_dense_stats(self):
+        """(lce_hip_binary_fully_connected launches, LceDequantize operators not launched because only binary Dense layers read
+        them, LceQuantize launches the layers absorbed) of the last run."""
+        v = [C.c_int32() for _ in range(3)]
+        tflite_lib().lce_tflite_model_binary_dense_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
     def reshape_stats(self):
         """(RESHAPE operators that were a view, RESHAPE operators that cost a device-to-device copy) of the last run."""
         v = [C.c_int32() for _ in range(2)]
@@ -511,10 +525,10 @@ class Interpreter:
                  depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False,
                  head_sections: bool = False, conv2d_i8_sections: bool = False, head_i8_sections: bool = False,
                  quantize_sections: bool = False, depthwise_i8_sections: bool = False, activation_sections: bool = False,
-                 reshape_sections: bool = False, gate_sections: bool = False):
+                 reshape_sections: bool = False, gate_sections: bool = False, binary_dense_sections: bool = False):
         """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
         ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``, ``head_i8_sections``, ``quantize_sections``,
-        ``depthwise_i8_sections``, ``activation_sections``, ``reshape_sections``, ``gate_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
+        ``depthwise_i8_sections``, ``activation_sections``, ``reshape_sections``, ``gate_sections``, ``binary_dense_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
         own settings hold)."""
         self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
                       else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
@@ -525,7 +539,7 @@ class Interpreter:
                                     conv2d_i8_sections=conv2d_i8_sections, head_i8_sections=head_i8_sections,
                                     quantize_sections=quantize_sections, depthwise_i8_sections=depthwise_i8_sections,
                                     activation_sections=activation_sections, reshape_sections=reshape_sections,
-                                    gate_sections=gate_sections))
+                                    gate_sections=gate_sections, binary_dense_sections=binary_dense_sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED

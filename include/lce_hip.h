@@ -609,6 +609,46 @@ lce_hip_status lce_hip_softmax_f32(size_t rows, size_t cols, float beta, const f
 lce_hip_status lce_hip_softmax_f32_check(size_t rows, size_t cols, float beta);
 
 /* ------------------------------------------------------------------------------------
+ * The binarized Dense layer (larq's QuantDense behind a sign) on the FP4 matrix cores
+ * ---------------------------------------------------------------------------------- */
+
+/* The converter has no binary fully-connected operator: a binarized Dense layer arrives as LceQuantize -> LceDequantize -> a float
+ * FULLY_CONNECTED whose weights in row o are all +s[o] or -s[o] (the +-1 kernel times the folded batch-norm scale).
+ *
+ * lce_hip_bfc_prepare (host only, needs no device): from the descriptor and the file's float weights [outputs][inputs] it writes
+ *   bits[outputs][ceil(inputs/32)], LSB first, bit 1 for a NEGATIVE weight, the padding bits of a ragged last word 0, and
+ *   scale[outputs] = s[o].  LCE_HIP_ERR_UNSUPPORTED unless every entry of row o has the same magnitude s[o], finite, with
+ *   2^-100 <= s[o] <= 2^100: a zero (+0.0 or -0.0), a NaN, an infinity or a row of mixed magnitudes is refused, and so is
+ *   inputs >= 2^23 (every partial sum must stay an exact float32 integer).  LCE_HIP_ERR_INVALID: a NULL pointer, what the
+ *   check refuses.
+ * lce_hip_bfc_check (host only): the descriptor rules alone -- LCE_HIP_ERR_INVALID for a NULL desc, an extent <= 0, an unknown
+ *   activation; LCE_HIP_ERR_UNSUPPORTED for inputs >= 2^23 or 2^31 or more tiles of 32 x 32 outputs.
+ * lce_hip_binary_fully_connected: ONE launch on the activation BITS in_bits_dev [batch][ceil(inputs/32)] (an LceQuantize's
+ *   output: bit 1 = negative; the padding bits are never read as channels).  Per output element, the bytes stated:
+ *     t = sum over k < inputs of a_k * w_k      a_k, w_k in {+1, -1} (bit 0 is +1): an exact integer; as a float +0.0f when zero
+ *     p = t * s[o]                              one float32 multiply
+ *     v = p + bias[o]                           one float32 add, never contracted with the multiply; bias_dev NULL: no add
+ *     v = min(max(v, lo), hi)                   std::max(a, b) = a < b ? b : a: a NaN passes, -0.0 stays -0.0
+ *     bit = v < 0                               LceQuantize's rule: -0.0 and NaN give 0; padding bits of a ragged last word are 0
+ *   out_dev (nullable) gets v as float32 [batch][outputs], out_bits_dev (nullable) the bits as int32 [batch][ceil(outputs/32)].
+ *   For s[o] a power of two the bytes are those of lce_hip_unpack + lce_hip_fully_connected_f32 on the same bits and the float
+ *   weights (every step of that chain is then exact); for other s[o] this entry rounds once where the chain rounds per step.
+ *   Refused before any device call, LCE_HIP_ERR_INVALID: a NULL desc, input, weights or scale, both outputs NULL, what the check
+ *   refuses, an output that overlaps the input, the weights, the scale, the bias or the other output, a pointer that is not
+ *   4-byte aligned.  16-byte aligned input and weights with ceil(inputs/32) % 4 == 0 take a wider load path (the same bytes).
+ *   Asynchronous on `stream`, capturable in a HIP graph, allocates nothing and copies nothing between host and device. */
+typedef struct lce_hip_bfc_desc {
+  int32_t batch, inputs, outputs;
+  int32_t activation;   /* NONE | RELU | RELU_N1_TO_1 | RELU6 */
+} lce_hip_bfc_desc;
+lce_hip_status lce_hip_bfc_check(const lce_hip_bfc_desc* desc);
+lce_hip_status lce_hip_bfc_prepare(const lce_hip_bfc_desc* desc, const float* weights_host /* [outputs][inputs] */,
+                                   int32_t* bits /* [outputs][ceil(inputs/32)] */, float* scale /* [outputs] */);
+lce_hip_status lce_hip_binary_fully_connected(const lce_hip_bfc_desc* desc, const int32_t* in_bits_dev, const int32_t* weight_bits_dev,
+                                              const float* scale_dev, const float* bias_dev /* nullable */, float* out_dev /* nullable */,
+                                              int32_t* out_bits_dev /* nullable */, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The int8 classifier head and the float/int8 boundary (TFLite builtin MEAN, FULLY_CONNECTED, SOFTMAX on int8; QUANTIZE, DEQUANTIZE)
  * ---------------------------------------------------------------------------------- */
 

@@ -265,7 +265,21 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   trailing axes, so it is not per image.
  *   None of the three moves anything unless it is named.  Still the host's: TANH, HARD_SWISH, LEAKY_RELU, int8 activations, a full
  *   [H,W,C] PRELU alpha, rank-2 ADD / MUL (the dense batch norm of BinaryAlexNet), a RESHAPE that moves the batch extent or whose
- *   shape is computed at run time, STRIDED_SLICE, PAD. */
+ *   shape is computed at run time, STRIDED_SLICE, PAD.
+ *   binary_dense: a binarized Dense layer (larq's QuantDense behind a sign: BinaryAlexNet's and XNOR-Net's classifier layers, a
+ *   binarized MLP) joins the sections and runs on the FP4 matrix cores.  The converter has no binary fully-connected operator: it
+ *   leaves LceQuantize -> LceDequantize -> a float FULLY_CONNECTED (9) whose row o holds only +-s[o].  Such an operator qualifies
+ *   under the rules of `head`'s FULLY_CONNECTED with: the input of rank 2 or [b, 1, 1, K]; the input the float32 output of an
+ *   LceDequantize whose own input is a non-constant bitpacked int32 tensor of ceil(K/32) words; lce_hip_bfc_check accepts the
+ *   descriptor and lce_hip_bfc_prepare the file's weights (every entry of row o of the same magnitude s[o], finite, 2^-100 <=
+ *   s[o] <= 2^100, K < 2^23).  Its row of the pass table stands in front of `head`'s, which takes what this one refuses (with
+ *   `head` named too).  It is queued with the LCE operators, as the head's.  lce_tflite_model_run_section runs it as ONE
+ *   lce_hip_binary_fully_connected launch on the BIT tensor (the prepared sign bits and scales are uploaded once per model); the
+ *   first LceQuantize of the section that reads its result folds into the launch by the fold rule, so a hidden binary Dense layer
+ *   writes only bits.  An LceDequantize that only binary Dense operators of its own section read, and that the section does not
+ *   deliver, is not launched and gets no buffer (its shape is still registered).  LceQuantize and LceDequantize take rank-2
+ *   tensors for this, carried as [b, 1, 1, C] like every rank-2 tensor of the walk (a rank-2 SECTION INPUT needs this name or
+ *   another that carries rank-2 tensors).  No partition and no launch changes unless it is named. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -418,6 +432,10 @@ void lce_tflite_model_depthwise_i8_stats(lce_tflite_model* model, int32_t* launc
 /* The LAST run's launches for the classifier head ("head" of lce_tflite_model_open_passes): lce_hip_pool2d launches that ran a
  * MEAN, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches.  Nullable outputs. */
 void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
+/* The LAST run's binary Dense layers ("binary_dense" of lce_tflite_model_open_passes): lce_hip_binary_fully_connected launches, the
+ * LceDequantize operators that were not launched because only such layers read them, and the LceQuantize launches the layers
+ * absorbed.  Nullable outputs. */
+void lce_tflite_model_binary_dense_stats(lce_tflite_model* model, int32_t* launches, int32_t* dequantize_skipped, int32_t* quantize_absorbed);
 /* The LAST run's launches for the int8 head ("head_i8"): lce_hip_mean_i8, lce_hip_fully_connected_i8 and lce_hip_softmax_i8
  * launches; and for the float / int8 boundary ("quantize"): lce_hip_quantize_f32_i8 and lce_hip_dequantize_i8_f32 launches. */
 void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax);
