@@ -31,11 +31,12 @@ struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
   uint32_t flags_ext = 0;                     // lce_tflite_open_options.sections_ext
-  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes ("head", "conv2d_i8", "head_i8", "quantize", "depthwise_i8", "activation", "reshape", "gate", "binary_dense")
+  uint32_t flags_int = 0;                     // kInternal*: lce_tflite_model_open_passes (the names of word 2 in kPassNames)
   std::vector<lce_tflite_section> sections;   // built by Partition() right after parsing
   std::vector<char> absorbed;                 // per operator: a builtin operator that runs inside a section (kAbsorbed*)
   std::vector<std::vector<int32_t>> readers;  // per tensor: the operators that read it (once per input slot)
   std::vector<int32_t> producer;              // per tensor: the first operator that lists it as an output; -1: none
+  bool rank2_inputs = false;                  // an enabled pass reads rank-2 tensors (FusedPass::rank2): a section input may be one
   void Partition();
   // ---- state of lce_tflite_model_run_section (one run at a time per model) ----
   std::mutex run_mu;
@@ -402,7 +403,8 @@ lce_hip_conv2d_i8_desc ConvI8Desc(const lce_tfl::Model& M, const lce_tfl::Operat
 }
 
 // lce_hip_conv2d_i8_prepare on the FILE's constants of int8 CONV_2D `o` (the candidate has checked their types and sizes).
-lce_hip_status ConvI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+lce_hip_status ConvI8Prepare(const lce_tflite_model& model, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Model& M = model.m;
   const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
   const lce_hip_conv2d_i8_desc d = ConvI8Desc(M, o, M.tensors[o.inputs[0]].shape[0]);
   const bool has_bias = o.inputs.size() == 3 && o.inputs[2] >= 0;
@@ -425,9 +427,9 @@ lce_hip_status ConvI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operator& o
 // constant int8 [Cout, fh, fw, Cin] with data in the file whose byte count matches (compared by division), Cin the input's
 // channels (a grouped filter is the host's), no zero point other than 0, and 1 or Cout scales -- with more than one,
 // quantized_dimension 0; the bias absent or a constant int32 [Cout]; Cout the output's channels; strides positive, dilations 1,
-// padding SAME or VALID, a known activation; and the declared output height and width what the padding rule gives.  Partition()
-// then asks lce_hip_conv2d_i8_prepare ONCE whether it accepts the file's constants (a pass over the whole filter) and keeps the
-// table for the run; it also decides the other half -- when the operator becomes ready.
+// padding SAME or VALID, a known activation; and the declared output height and width what the padding rule gives.  The row's
+// prepare step then asks lce_hip_conv2d_i8_prepare ONCE whether it accepts the file's constants (a pass over the whole filter) and
+// Partition() keeps the table for the run; it also decides the other half -- when the operator becomes ready.
 bool ConvI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   if (o.builtin_code != lce_tfl::kBuiltinConv2d || !o.has_conv_options) return false;
   if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
@@ -483,7 +485,8 @@ lce_hip_depthwise_i8_desc DepthwiseI8Desc(const lce_tfl::Model& M, const lce_tfl
 
 // lce_hip_depthwise_conv2d_i8_prepare on the FILE's constants of int8 DEPTHWISE_CONV_2D `o` (the candidate has checked their types
 // and sizes).
-lce_hip_status DepthwiseI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+lce_hip_status DepthwiseI8Prepare(const lce_tflite_model& model, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Model& M = model.m;
   const lce_tfl::Tensor& flt = M.tensors[o.inputs[1]];
   const lce_hip_depthwise_i8_desc d = DepthwiseI8Desc(M, o, M.tensors[o.inputs[0]].shape[0]);
   const bool has_bias = o.inputs.size() == 3 && o.inputs[2] >= 0;
@@ -505,8 +508,9 @@ lce_hip_status DepthwiseI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operat
 // multiplier >= 1 with Cout == Cin x multiplier == the output's channels; 1 or Cout filter scales -- with more than one,
 // quantized_dimension 3; the bias absent or a constant int32 [Cout]; and the declared output height and width what the padding rule
 // gives.  A dilation, hybrid (float data, int8 filter) weights, a filter zero point other than 0, scales along another dimension or
-// a float bias leave it with the host.  Partition() then asks lce_hip_depthwise_conv2d_i8_prepare ONCE whether it accepts the
-// file's constants and keeps the table for the run; it also decides the other half -- when the operator becomes ready.
+// a float bias leave it with the host.  The row's prepare step then asks lce_hip_depthwise_conv2d_i8_prepare ONCE whether it
+// accepts the file's constants and Partition() keeps the table for the run; it also decides the other half -- when the operator
+// becomes ready.
 bool DepthwiseI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   if (o.builtin_code != lce_tfl::kBuiltinDepthwiseConv2d || !o.has_depthwise_options) return false;
   if ((o.inputs.size() != 2 && o.inputs.size() != 3) || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
@@ -667,7 +671,8 @@ bool SoftmaxCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
 // The converter leaves larq's QuantDense behind a sign as LceQuantize -> LceDequantize -> a float FULLY_CONNECTED whose row o
 // holds only +-s[o].  The static half of "a builtin FULLY_CONNECTED that runs as lce_hip_binary_fully_connected on the BITS":
 // FullyConnectedCandidate's rules, an input of rank 2 or [b, 1, 1, K], and the entry's own check accepts the descriptor.
-// Partition() decides the other half (BinaryDenseSource, BinaryDensePrepare); what it refuses falls to the rows below ("head").
+// The row's prepare step decides the other half (BinaryDenseSource, BinaryDensePrepare); what it refuses falls to the rows below
+// ("head").
 lce_hip_bfc_desc BinaryDenseDesc(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t batch) {
   const lce_hip_fc_desc f = FullyConnectedDesc(M, o, batch);
   lce_hip_bfc_desc d;
@@ -696,9 +701,11 @@ int32_t BinaryDenseSource(const lce_tfl::Model& M, const lce_tfl::Operator& o, i
   if (bd[0] != id[0] || bd[1] != 1 || bd[2] != 1 || bd[3] != (id[3] + 31) / 32) return -1;
   return dq.inputs[0];
 }
-// lce_hip_bfc_prepare on the file's weights: the table is the sign bits [N][ceil(K/32)] followed by the N scales (float32 bit
-// patterns), kept like the int8 passes' tables.
-lce_hip_status BinaryDensePrepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+// A binary Dense layer needs its bits -- the input of the LceDequantize that feeds it -- and weights lce_hip_bfc_prepare accepts:
+// the table is the sign bits [N][ceil(K/32)] followed by the N scales (float32 bit patterns), kept like the int8 passes' tables.
+lce_hip_status BinaryDensePrepare(const lce_tflite_model& model, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Model& M = model.m;
+  if (BinaryDenseSource(M, o, model.producer[o.inputs[0]]) < 0) return LCE_HIP_ERR_UNSUPPORTED;
   const lce_hip_bfc_desc d = BinaryDenseDesc(M, o, 1);
   const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
   const size_t N = (size_t)d.outputs, K = (size_t)d.inputs, Kw = (K + 31) / 32;
@@ -755,7 +762,8 @@ lce_hip_fc_i8_desc FullyConnectedI8Desc(const lce_tfl::Model& M, const lce_tfl::
 
 // lce_hip_fully_connected_i8_prepare on the FILE's constants of int8 FULLY_CONNECTED `o` (the candidate has checked their types
 // and sizes).
-lce_hip_status FullyConnectedI8Prepare(const lce_tfl::Model& M, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+lce_hip_status FullyConnectedI8Prepare(const lce_tflite_model& model, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Model& M = model.m;
   const lce_tfl::Tensor& w = M.tensors[o.inputs[1]];
   const lce_hip_fc_i8_desc d = FullyConnectedI8Desc(M, o, M.tensors[o.inputs[0]].shape[0]);
   const bool has_bias = o.inputs.size() == 3 && o.inputs[2] >= 0;
@@ -774,8 +782,8 @@ lce_hip_status FullyConnectedI8Prepare(const lce_tfl::Model& M, const lce_tfl::O
 // "A builtin int8 FULLY_CONNECTED that a section may run": the Dense layer of an int8 head.  The rules of FullyConnectedCandidate
 // with: input and output Int8Activation; the weights a constant int8 [N, K] with data in the file whose byte count matches
 // (compared by division), no zero point other than 0, and 1 or N scales -- with more than one, quantized_dimension 0; the bias
-// absent or a constant int32 [N]; and the entry's own check accepts the descriptor.  Partition() then asks
-// lce_hip_fully_connected_i8_prepare ONCE whether it accepts the file's constants and keeps the table for the run.  A float
+// absent or a constant int32 [N]; and the entry's own check accepts the descriptor.  The row's prepare step then asks
+// lce_hip_fully_connected_i8_prepare ONCE whether it accepts the file's constants and Partition() keeps the table for the run.  A float
 // input (hybrid weights), int16 / uint8 tensors, a weight zero point and shuffled weights stay with the host.
 bool FullyConnectedI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   if (o.builtin_code != lce_tfl::kBuiltinFullyConnected || !o.has_fc_options) return false;
@@ -936,15 +944,44 @@ bool GateCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return GateOperandSlot(M, o) >= 0;
 }
 
-// One fused pass: the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it that enables it, the static half of "a section may run
-// this operator", and the walker that runs it.  The table, in priority order, is below Walk.
+// THE names of lce_tflite_model_open_passes, each with the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it
+// that the name sets: the only place the three are written.  "stem" is a name that is no pass (Partition() reads its bit); "head",
+// "head_i8" and "quantize" enable several rows of kPasses each.
+struct PassName { const char* name; int word; uint32_t bit; };
+constexpr PassName kPassNames[] = {
+    {"elementwise", 0, LCE_TFLITE_SECTIONS_ELEMENTWISE}, {"int8_add", 0, LCE_TFLITE_SECTIONS_INT8_ADD},
+    {"concat", 0, LCE_TFLITE_SECTIONS_CONCAT},           {"pool", 1, LCE_TFLITE_SECTIONS_EXT_POOL},
+    {"conv1x1", 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1},     {"depthwise", 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE},
+    {"conv2d", 1, LCE_TFLITE_SECTIONS_EXT_CONV2D},       {"stem", 1, LCE_TFLITE_SECTIONS_EXT_STEM},
+    {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8},
+    {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize},
+    {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
+    {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate},
+    {"binary_dense", 2, kInternalBinaryDense}};
+// The entry of kPassNames called `name`; null when there is none.
+constexpr const PassName* Named(const char* name) {
+  for (const PassName& n : kPassNames) {
+    const char *a = n.name, *b = name;
+    while (*a && *a == *b) ++a, ++b;
+    if (*a == *b) return &n;
+  }
+  return nullptr;
+}
+
+// One fused pass, a row of kPasses (in priority order, below Walk): its kind; the name that enables it; the static half of "a
+// section may run this operator"; the walker that runs it; and everything else Partition() and the walk ask about a pass --
+//   prepare   (optional) the step that follows the predicate: it sees the model (the binary Dense row looks at `producer`) and
+//             fills the table Partition() keeps for the first run (host_tables); when it refuses, the search goes on with the rows below
+//   as_lce    the operator is queued as the LCE operators are, whatever made it ready (see Partition())
+//   rank2     the pass reads rank-2 tensors, carried as [b, 1, 1, C]: while its flag is set a section input may be one
 struct Walk;
 struct FusedPass {
   int kind;
-  int word;
-  uint32_t bit;
+  const PassName* name;
   bool (*candidate)(const lce_tfl::Model&, const lce_tfl::Operator&);
   lce_hip_status (Walk::*walker)(int32_t);
+  lce_hip_status (*prepare)(const lce_tflite_model&, const lce_tfl::Operator&, std::vector<int32_t>* table);
+  bool as_lce, rank2;
 };
 extern const FusedPass kPasses[kAbsorbedCount - 1];
 }  // namespace
@@ -961,6 +998,7 @@ void lce_tflite_model::Partition() {
   auto valid = [&](int32_t t) { return t >= 0 && t < n_t; };
   std::vector<char> produced(n_t, 0), is_output(n_t, 0), is_lce(n_ops, 0), candidate(n_ops, 0);
   const uint32_t words[3] = {flags, flags_ext, flags_int};
+  for (const FusedPass& p : kPasses) rank2_inputs = rank2_inputs || (p.rank2 && (words[p.name->word] & p.name->bit));
   readers.assign(n_t, {});
   producer.assign(n_t, -1);
   absorbed.assign(n_ops, 0);
@@ -970,47 +1008,23 @@ void lce_tflite_model::Partition() {
       if (valid(t) && producer[t] < 0) producer[t] = i;
   for (int i = 0; i < n_ops; ++i) {
     is_lce[i] = IsLceOp(m.operators[i]) ? 1 : 0;
-    // the first pass, in the table's order, that is enabled and whose predicate holds.  An absorbed operator joins the epoch in
+    // the first pass, in the table's order, that is enabled, whose predicate holds and whose prepare step, if it has one,
+    // accepts the file's constants (its table is kept for the first run).  An absorbed operator joins the epoch in
     // which it becomes ready, so it lands in a section exactly when the last of its inputs was produced by an LCE epoch (one
     // that is ready from the start -- a stem op -- is a builtin one without LCE_TFLITE_SECTIONS_EXT_STEM, below)
-    auto first_pass = [&](int from_kind) {
-      for (const FusedPass& p : kPasses)
-        if (p.kind >= from_kind && (words[p.word] & p.bit) && p.candidate(m, m.operators[i])) return p.kind;
-      return 0;
-    };
-    candidate[i] = (char)first_pass(1);
-    // a binary Dense layer also needs its bits -- the input of the LceDequantize that feeds it -- and weights lce_hip_bfc_prepare
-    // accepts: prepared here, once, and kept for the first run.  What fails either is left to the rows below its own ("head")
-    if (candidate[i] == kAbsorbedBinaryDense) {
-      std::vector<int32_t> table;
-      if (BinaryDenseSource(m, m.operators[i], producer[m.operators[i].inputs[0]]) >= 0 &&
-          BinaryDensePrepare(m, m.operators[i], &table) == LCE_HIP_OK)
+    for (const FusedPass& p : kPasses) {
+      if (!(words[p.name->word] & p.name->bit) || !p.candidate(m, m.operators[i])) continue;
+      if (p.prepare) {
+        std::vector<int32_t> table;
+        if (p.prepare(*this, m.operators[i], &table) != LCE_HIP_OK) continue;
         host_tables[i] = std::move(table);
-      else
-        candidate[i] = (char)first_pass(kAbsorbedBinaryDense + 1);
+      }
+      candidate[i] = (char)p.kind;
+      // a head operator (MEAN, FULLY_CONNECTED -- float, int8 or binary --, SOFTMAX) is queued as the LCE operators are, whatever
+      // made it ready: behind a host operator the head is a section of its own, behind the body it joins the body's epoch
+      if (p.as_lce) is_lce[i] = 1;
+      break;
     }
-    // an int8 CONV_2D also needs constants lce_hip_conv2d_i8_prepare accepts: prepared here, once, and kept for the first run
-    if (candidate[i] == kAbsorbedConvI8) {
-      std::vector<int32_t> table;
-      if (ConvI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
-      else candidate[i] = 0;
-    }
-    // ... an int8 DEPTHWISE_CONV_2D constants lce_hip_depthwise_conv2d_i8_prepare accepts
-    if (candidate[i] == kAbsorbedDepthwiseI8) {
-      std::vector<int32_t> table;
-      if (DepthwiseI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
-      else candidate[i] = 0;
-    }
-    // ... and an int8 FULLY_CONNECTED constants lce_hip_fully_connected_i8_prepare accepts
-    if (candidate[i] == kAbsorbedFullyConnectedI8) {
-      std::vector<int32_t> table;
-      if (FullyConnectedI8Prepare(m, m.operators[i], &table) == LCE_HIP_OK) host_tables[i] = std::move(table);
-      else candidate[i] = 0;
-    }
-    // a head operator (MEAN, FULLY_CONNECTED -- float, int8 or binary: kAbsorbedBinaryDense lies inside the range --, SOFTMAX) is
-    // queued as the LCE operators are, whatever made it ready:
-    // behind a host operator the head is a section of its own, behind the body it joins the body's epoch
-    if (candidate[i] >= kAbsorbedMean && candidate[i] <= kAbsorbedSoftmaxI8) is_lce[i] = 1;
     for (int32_t t : m.operators[i].outputs)
       if (valid(t)) produced[t] = 1;                         // produced by an operator: not ready until it has run
   }
@@ -1162,26 +1176,13 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
 }
 
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len) {
-  struct Name { const char* name; int word; uint32_t bit; };
-  static const Name kNames[] = {
-      {"elementwise", 0, LCE_TFLITE_SECTIONS_ELEMENTWISE}, {"int8_add", 0, LCE_TFLITE_SECTIONS_INT8_ADD},
-      {"concat", 0, LCE_TFLITE_SECTIONS_CONCAT},           {"pool", 1, LCE_TFLITE_SECTIONS_EXT_POOL},
-      {"conv1x1", 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1},     {"depthwise", 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE},
-      {"conv2d", 1, LCE_TFLITE_SECTIONS_EXT_CONV2D},       {"stem", 1, LCE_TFLITE_SECTIONS_EXT_STEM},
-      {"head", 2, kInternalHead},                          {"conv2d_i8", 2, kInternalConvI8},
-      {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize},
-      {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
-      {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate},
-      {"binary_dense", 2, kInternalBinaryDense}};
   uint32_t words[3] = {0u, 0u, 0u};
   std::string refusal;
   if (!passes) refusal = "null passes";
   for (const char* at = passes; at && *at && refusal.empty();) {
     const char* end = strchr(at, ',');
     const std::string name = end ? std::string(at, end) : std::string(at);
-    const Name* found = nullptr;
-    for (const Name& n : kNames)
-      if (name == n.name) found = &n;
+    const PassName* found = Named(name.c_str());
     if (!found) refusal = "passes: unknown name '" + name + "'";
     else if (words[found->word] & found->bit) refusal = "passes: '" + name + "' is named twice";
     else words[found->word] |= found->bit;
@@ -1509,7 +1510,8 @@ lce_hip_status ConstOnDevice(lce_tflite_model* model, int32_t t, void* stream, b
 // One walk of a section at `batch` images: shapes of every tensor it touches (shape inference exactly as the ops' Prepare
 // does it) and, with `run`, the launches.  `ptr` maps tensor -> device pointer (section inputs and outputs on entry;
 // intermediates are added from the model's scratch buffers).  A fused pass between binary layers plugs in as a row of kPasses
-// (below): a candidate predicate (above) and a walker here that ends in FoldQuantize / FoldBuffers / Launched.
+// (below): a candidate predicate (above) and a walker here -- a call of OnePass for a pass that streams one input into one
+// output -- that ends in FoldQuantize / FoldBuffers / Launched.
 struct Walk {
   lce_tflite_model* model;
   const lce_tflite_section& sec;
@@ -1869,87 +1871,93 @@ struct Walk {
     return Launched(kAbsorbedConcat, fold);
   }
 
-  // An absorbed operator `i` that streams ONE input and makes ONE output of the input's type with `out_channels` channels, as
-  // ONE launch of pass `kind`; `noun` names it in the messages ("a pool").  `check(&h, &w)` is the entry's own *_check of the
-  // descriptor at this walk's batch, which gives the output's height and width; `launch(in, filter, bias, out, bits)` is the
-  // entry (filter and bias: inputs 1 and 2 of the operator when it has them, uploaded once per model).  The first LceQuantize of
-  // the section that reads the result becomes the launch's bit output and its own launch disappears; the tensor itself is
-  // written when anything else reads it or the section delivers it.
-  template <class Check, class Launch>
-  lce_hip_status StreamingPass(int32_t i, int kind, const std::string& noun, int type, int32_t out_channels, Check check, Launch launch) {
+  // An absorbed operator `i` that streams ONE input of `in_type` and makes ONE output of shape and type `os`, as ONE launch of its
+  // pass; `noun` names it in the messages ("a pool").  A rank-2 input is carried as [batch, 1, 1, C].  `launch(in, c1, c2, out, bits)`
+  // is the entry, on untyped pointers: c1 and c2 are inputs 1 and 2 of the operator -- its filter or weights and its optional
+  // bias --, of which the first `constants` are uploaded as they are, once per model.  With `fold_quantize` the first LceQuantize
+  // of the section that reads the result becomes the launch's bit output and its own launch disappears, and the tensor itself is
+  // written when anything else reads it or the section delivers it; without, `bits` is null and the output is always written.
+  template <class Launch>
+  lce_hip_status OnePass(int32_t i, const std::string& noun, int in_type, const Shape& os, bool fold_quantize, int constants, Launch launch) {
     const lce_tfl::Model& M = model->m;
     const lce_tfl::Operator& op = M.operators[i];
     const int32_t out_t = op.outputs[0];
-    const std::vector<int32_t>& is = M.tensors[op.inputs[0]].shape;
     // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
     // declares must not be read past its buffer)
+    int32_t want[4];
     auto it = shapes.find(op.inputs[0]);
     if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " reads a tensor nothing produced");
-    if (!Agrees(it->second, type, is[1], is[2], is[3]))
+    if (!Carried(M.tensors[op.inputs[0]], want) || !Agrees(it->second, in_type, want[1], want[2], want[3]))
       return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " input's shape or type does not match the one its producer infers");
-    Shape os;
-    os.dims[0] = batch; os.dims[3] = out_channels;
-    os.type = type;
-    if (lce_hip_status s = check(&os.dims[1], &os.dims[2])) return s;
     shapes[out_t] = os;
     done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os);
+    const Fold fold = FoldQuantize(i, out_t, os, fold_quantize);
     if (!run) return LCE_HIP_OK;
     const void* in = nullptr;
     if (lce_hip_status s = DevicePtr(op.inputs[0], (noun + " input").c_str(), &in)) return s;
-    const float *filter = nullptr, *bias = nullptr;
-    if (op.inputs.size() >= 2)
-      if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &filter)) return s;
-    if (op.inputs.size() == 3 && op.inputs[2] >= 0)
-      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
+    const float *c1 = nullptr, *c2 = nullptr;
+    if (constants >= 1)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &c1)) return s;
+    if (constants >= 2 && op.inputs.size() == 3 && op.inputs[2] >= 0)
+      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &c2)) return s;
     void *out, *bits;
     if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    if (lce_hip_status s = launch(in, filter, bias, out, (int32_t*)bits)) return s;
-    return Launched(kind, fold);
+    if (lce_hip_status s = launch(in, (const void*)c1, (const void*)c2, out, (int32_t*)bits)) return s;
+    return Launched(model->absorbed[i], fold);
+  }
+  // The output of a pass at this walk's batch.
+  Shape OutShape(int32_t h, int32_t w, int32_t c, int type = lce_tfl::kTensorFloat32) const {
+    Shape os;
+    os.dims[0] = batch; os.dims[1] = h; os.dims[2] = w; os.dims[3] = c;
+    os.type = type;
+    return os;
   }
 
+  // ---- the windowed passes: the entry's own *_check of the descriptor at this walk's batch gives the output's height and width ----
   // An absorbed AVERAGE_POOL_2D / MAX_POOL_2D (LCE_TFLITE_SECTIONS_EXT_POOL) as ONE lce_hip_pool2d launch.
   lce_hip_status Pool2d(int32_t i) {
     const lce_tfl::Operator& op = model->m.operators[i];
     const lce_tfl::Tensor& in = model->m.tensors[op.inputs[0]];
     const lce_hip_pool2d_desc d = PoolDesc(model->m, op, batch);
-    return StreamingPass(
-        i, kAbsorbedPool, "a pool", in.type, in.shape[3], [&](int32_t* h, int32_t* w) { return lce_hip_pool2d_check(&d, h, w); },
-        [&](const void* x, const float*, const float*, void* out, int32_t* bits) { return lce_hip_pool2d(&d, x, out, bits, stream); });
+    int32_t h = 0, w = 0;
+    if (lce_hip_status s = lce_hip_pool2d_check(&d, &h, &w)) return s;
+    return OnePass(i, "a pool", in.type, OutShape(h, w, in.shape[3], in.type), /*fold_quantize=*/true, /*constants=*/0,
+                   [&](const void* x, const void*, const void*, void* out, int32_t* bits) { return lce_hip_pool2d(&d, x, out, bits, stream); });
   }
 
   // An absorbed float 1x1 CONV_2D (LCE_TFLITE_SECTIONS_EXT_CONV1X1) as ONE lce_hip_conv1x1_f32 launch.
   lce_hip_status Conv1x1(int32_t i) {
     const lce_hip_conv1x1_desc d = Conv1x1Desc(model->m, model->m.operators[i], batch);
-    return StreamingPass(
-        i, kAbsorbedConv1x1, "a CONV_2D", lce_tfl::kTensorFloat32, d.channels_out,
-        [&](int32_t* h, int32_t* w) { return lce_hip_conv1x1_f32_check(&d, h, w); },
-        [&](const void* x, const float* filter, const float* bias, void* out, int32_t* bits) {
-          return lce_hip_conv1x1_f32(&d, (const float*)x, filter, bias, (float*)out, bits, stream);
-        });
+    int32_t h = 0, w = 0;
+    if (lce_hip_status s = lce_hip_conv1x1_f32_check(&d, &h, &w)) return s;
+    return OnePass(i, "a CONV_2D", lce_tfl::kTensorFloat32, OutShape(h, w, d.channels_out), /*fold_quantize=*/true, /*constants=*/2,
+                   [&](const void* x, const void* filter, const void* bias, void* out, int32_t* bits) {
+                     return lce_hip_conv1x1_f32(&d, (const float*)x, (const float*)filter, (const float*)bias, (float*)out, bits, stream);
+                   });
   }
 
   // An absorbed float DEPTHWISE_CONV_2D (LCE_TFLITE_SECTIONS_EXT_DEPTHWISE) as ONE lce_hip_depthwise_conv2d_f32 launch.
   lce_hip_status Depthwise(int32_t i) {
     const lce_tfl::Operator& op = model->m.operators[i];
     const lce_hip_depthwise_desc d = DepthwiseDesc(model->m, op, batch);
-    return StreamingPass(
-        i, kAbsorbedDepthwise, "a DEPTHWISE_CONV_2D", lce_tfl::kTensorFloat32, model->m.tensors[op.inputs[1]].shape[3],
-        [&](int32_t* h, int32_t* w) { return lce_hip_depthwise_conv2d_f32_check(&d, h, w); },
-        [&](const void* x, const float* filter, const float* bias, void* out, int32_t* bits) {
-          return lce_hip_depthwise_conv2d_f32(&d, (const float*)x, filter, bias, (float*)out, bits, stream);
-        });
+    int32_t h = 0, w = 0;
+    if (lce_hip_status s = lce_hip_depthwise_conv2d_f32_check(&d, &h, &w)) return s;
+    return OnePass(i, "a DEPTHWISE_CONV_2D", lce_tfl::kTensorFloat32, OutShape(h, w, model->m.tensors[op.inputs[1]].shape[3]),
+                   /*fold_quantize=*/true, /*constants=*/2,
+                   [&](const void* x, const void* filter, const void* bias, void* out, int32_t* bits) {
+                     return lce_hip_depthwise_conv2d_f32(&d, (const float*)x, (const float*)filter, (const float*)bias, (float*)out, bits, stream);
+                   });
   }
 
   // An absorbed float CONV_2D of any filter extent (LCE_TFLITE_SECTIONS_EXT_CONV2D) as ONE lce_hip_conv2d_f32 call.
   lce_hip_status Conv2d(int32_t i) {
     const lce_hip_conv2d_desc d = Conv2dDesc(model->m, model->m.operators[i], batch);
-    return StreamingPass(
-        i, kAbsorbedConv2d, "a CONV_2D", lce_tfl::kTensorFloat32, d.channels_out,
-        [&](int32_t* h, int32_t* w) { return lce_hip_conv2d_f32_check(&d, h, w); },
-        [&](const void* x, const float* filter, const float* bias, void* out, int32_t* bits) {
-          return lce_hip_conv2d_f32(&d, (const float*)x, filter, bias, (float*)out, bits, stream);
-        });
+    int32_t h = 0, w = 0;
+    if (lce_hip_status s = lce_hip_conv2d_f32_check(&d, &h, &w)) return s;
+    return OnePass(i, "a CONV_2D", lce_tfl::kTensorFloat32, OutShape(h, w, d.channels_out), /*fold_quantize=*/true, /*constants=*/2,
+                   [&](const void* x, const void* filter, const void* bias, void* out, int32_t* bits) {
+                     return lce_hip_conv2d_f32(&d, (const float*)x, (const float*)filter, (const float*)bias, (float*)out, bits, stream);
+                   });
   }
 
   // The table Partition() had an entry's prepare make of the constants of operator `i` (`noun`), on the device: uploaded once per
@@ -1979,18 +1987,18 @@ struct Walk {
   }
 
   // An absorbed int8 CONV_2D of any filter extent ("conv2d_i8" of lce_tflite_model_open_passes) as ONE lce_hip_conv2d_i8 launch.
-  // The table Partition() had lce_hip_conv2d_i8_prepare make of the file's constants is uploaded once per model, where the filters are.
+  // The table the row's prepare step made of the file's constants is uploaded once per model, where the filters are (the int32
+  // bias is uploaded beside the filter, though the entry reads the table's copy).
   lce_hip_status ConvI8(int32_t i) {
-    const lce_tfl::Operator& op = model->m.operators[i];
-    const lce_hip_conv2d_i8_desc d = ConvI8Desc(model->m, op, batch);
-    return StreamingPass(
-        i, kAbsorbedConvI8, "an int8 CONV_2D", lce_tfl::kTensorInt8, d.channels_out,
-        [&](int32_t* h, int32_t* w) { return lce_hip_conv2d_i8_check(&d, h, w); },
-        [&](const void* x, const float* filter, const float*, void* out, int32_t* bits) -> lce_hip_status {
-          const int32_t* table = nullptr;
-          if (lce_hip_status s = TableOnDevice(i, "an int8 CONV_2D", &table)) return s;
-          return lce_hip_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, table, (int8_t*)out, bits, stream);
-        });
+    const lce_hip_conv2d_i8_desc d = ConvI8Desc(model->m, model->m.operators[i], batch);
+    int32_t h = 0, w = 0;
+    if (lce_hip_status s = lce_hip_conv2d_i8_check(&d, &h, &w)) return s;
+    return OnePass(i, "an int8 CONV_2D", lce_tfl::kTensorInt8, OutShape(h, w, d.channels_out, lce_tfl::kTensorInt8), /*fold_quantize=*/true,
+                   /*constants=*/2, [&](const void* x, const void* filter, const void*, void* out, int32_t* bits) -> lce_hip_status {
+                     const int32_t* table = nullptr;
+                     if (lce_hip_status s = TableOnDevice(i, "an int8 CONV_2D", &table)) return s;
+                     return lce_hip_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, table, (int8_t*)out, bits, stream);
+                   });
   }
 
   // An absorbed int8 DEPTHWISE_CONV_2D ("depthwise_i8" of lce_tflite_model_open_passes) as ONE lce_hip_depthwise_conv2d_i8 launch; its
@@ -1998,74 +2006,36 @@ struct Walk {
   lce_hip_status DepthwiseI8(int32_t i) {
     const lce_tfl::Operator& op = model->m.operators[i];
     const lce_hip_depthwise_i8_desc d = DepthwiseI8Desc(model->m, op, batch);
-    return StreamingPass(
-        i, kAbsorbedDepthwiseI8, "an int8 DEPTHWISE_CONV_2D", lce_tfl::kTensorInt8, model->m.tensors[op.inputs[1]].shape[3],
-        [&](int32_t* h, int32_t* w) { return lce_hip_depthwise_conv2d_i8_check(&d, h, w); },
-        [&](const void* x, const float* filter, const float*, void* out, int32_t* bits) -> lce_hip_status {
-          const int32_t* table = nullptr;
-          if (lce_hip_status s = TableOnDevice(i, "an int8 DEPTHWISE_CONV_2D", &table)) return s;
-          return lce_hip_depthwise_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, table, (int8_t*)out, bits, stream);
-        });
+    int32_t h = 0, w = 0;
+    if (lce_hip_status s = lce_hip_depthwise_conv2d_i8_check(&d, &h, &w)) return s;
+    return OnePass(i, "an int8 DEPTHWISE_CONV_2D", lce_tfl::kTensorInt8,
+                   OutShape(h, w, model->m.tensors[op.inputs[1]].shape[3], lce_tfl::kTensorInt8), /*fold_quantize=*/true, /*constants=*/2,
+                   [&](const void* x, const void* filter, const void*, void* out, int32_t* bits) -> lce_hip_status {
+                     const int32_t* table = nullptr;
+                     if (lce_hip_status s = TableOnDevice(i, "an int8 DEPTHWISE_CONV_2D", &table)) return s;
+                     return lce_hip_depthwise_conv2d_i8(&d, (const int8_t*)x, (const int8_t*)filter, table, (int8_t*)out, bits, stream);
+                   });
   }
 
-  // ---- the classifier head ("head" of lce_tflite_model_open_passes).  Rank-2 tensors are carried as [batch, 1, 1, C]. ----
-  // An absorbed head operator `i` that streams ONE input of `in_type` and makes ONE output of shape and type `os`, as ONE launch
-  // of pass `kind`.  `launch(in, weights, bias, out)` is the entry; its pointers are typed float and an int8 pass casts them
-  // (`constants`: how many of inputs 1 and 2 of the operator -- its weights and its optional bias -- are uploaded as they are,
-  // once per model).  No LceQuantize folds into it, so the output is always written.
-  template <class Launch>
-  lce_hip_status HeadPass(int32_t i, int kind, const std::string& noun, const Shape& os, int constants, Launch launch,
-                          int in_type = lce_tfl::kTensorFloat32) {
-    const lce_tfl::Model& M = model->m;
-    const lce_tfl::Operator& op = M.operators[i];
-    const int32_t out_t = op.outputs[0];
-    // the inferred shape and type of the input must agree with the file's (a producer whose output is smaller than the file
-    // declares must not be read past its buffer)
-    int32_t want[4];
-    auto it = shapes.find(op.inputs[0]);
-    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " reads a tensor nothing produced");
-    if (!Carried(M.tensors[op.inputs[0]], want) || !Agrees(it->second, in_type, want[1], want[2], want[3]))
-      return Fail(LCE_HIP_ERR_INVALID, "run_section: " + noun + " input's shape or type does not match the one its producer infers");
-    shapes[out_t] = os;
-    done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os, /*allowed=*/false);
-    if (!run) return LCE_HIP_OK;
-    const void* in = nullptr;
-    if (lce_hip_status s = DevicePtr(op.inputs[0], (noun + " input").c_str(), &in)) return s;
-    const float *weights = nullptr, *bias = nullptr;
-    if (constants >= 1)
-      if (lce_hip_status s = ConstOnDevice(model, op.inputs[1], stream, capturing, &weights)) return s;
-    if (constants >= 2 && op.inputs.size() == 3 && op.inputs[2] >= 0)
-      if (lce_hip_status s = ConstOnDevice(model, op.inputs[2], stream, capturing, &bias)) return s;
-    void *out, *bits;
-    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    if (lce_hip_status s = launch((const float*)in, weights, bias, (float*)out)) return s;
-    return Launched(kind, fold);
-  }
-  Shape HeadShape(int32_t h, int32_t w, int32_t c, int type = lce_tfl::kTensorFloat32) const {
-    Shape os;
-    os.dims[0] = batch; os.dims[1] = h; os.dims[2] = w; os.dims[3] = c;
-    os.type = type;
-    return os;
-  }
-
+  // ---- the classifier head ("head" of lce_tflite_model_open_passes).  Rank-2 tensors are carried as [batch, 1, 1, C]; no
+  // LceQuantize folds into a head operator. ----
   // An absorbed MEAN over height and width as ONE lce_hip_pool2d launch: the AVERAGE pool whose filter is the image.
   lce_hip_status Mean(int32_t i) {
     const lce_hip_pool2d_desc d = MeanDesc(model->m, model->m.operators[i], batch);
     int32_t oh = 0, ow = 0;
     if (lce_hip_status s = lce_hip_pool2d_check(&d, &oh, &ow)) return s;
-    return HeadPass(i, kAbsorbedMean, "a MEAN", HeadShape(oh, ow, d.channels), /*constants=*/0,
-                    [&](const float* x, const float*, const float*, float* out) { return lce_hip_pool2d(&d, x, out, nullptr, stream); });
+    return OnePass(i, "a MEAN", lce_tfl::kTensorFloat32, OutShape(oh, ow, d.channels), /*fold_quantize=*/false, /*constants=*/0,
+                   [&](const void* x, const void*, const void*, void* out, int32_t*) { return lce_hip_pool2d(&d, x, out, nullptr, stream); });
   }
 
   // An absorbed float FULLY_CONNECTED as ONE lce_hip_fully_connected_f32 launch.
   lce_hip_status FullyConnected(int32_t i) {
     const lce_hip_fc_desc d = FullyConnectedDesc(model->m, model->m.operators[i], batch);
     if (lce_hip_status s = lce_hip_fully_connected_f32_check(&d)) return s;
-    return HeadPass(i, kAbsorbedFullyConnected, "a FULLY_CONNECTED", HeadShape(1, 1, d.outputs), /*constants=*/2,
-                    [&](const float* x, const float* weights, const float* bias, float* out) {
-                      return lce_hip_fully_connected_f32(&d, x, weights, bias, out, stream);
-                    });
+    return OnePass(i, "a FULLY_CONNECTED", lce_tfl::kTensorFloat32, OutShape(1, 1, d.outputs), /*fold_quantize=*/false, /*constants=*/2,
+                   [&](const void* x, const void* weights, const void* bias, void* out, int32_t*) {
+                     return lce_hip_fully_connected_f32(&d, (const float*)x, (const float*)weights, (const float*)bias, (float*)out, stream);
+                   });
   }
 
   // An absorbed binarized Dense layer ("binary_dense" of lce_tflite_model_open_passes) as ONE lce_hip_binary_fully_connected launch
@@ -2086,7 +2056,7 @@ struct Walk {
     if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a binary FULLY_CONNECTED reads bits nothing produced");
     if (!Agrees(it->second, lce_tfl::kTensorInt32, 1, 1, (d.inputs + 31) / 32))
       return Fail(LCE_HIP_ERR_INVALID, "run_section: a binary FULLY_CONNECTED's bits do not have the shape or type their producer infers");
-    const Shape os = HeadShape(1, 1, d.outputs);
+    const Shape os = OutShape(1, 1, d.outputs);
     shapes[out_t] = os;
     done[i] = 1;
     const Fold fold = FoldQuantize(i, out_t, os);
@@ -2113,10 +2083,10 @@ struct Walk {
     int32_t id[4];
     if (!Carried(model->m.tensors[op.inputs[0]], id)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a SOFTMAX of a rank that is neither 2 nor 4");
     if (lce_hip_status s = lce_hip_softmax_f32_check((size_t)batch, (size_t)id[3], op.softmax_beta)) return s;
-    return HeadPass(i, kAbsorbedSoftmax, "a SOFTMAX", HeadShape(1, 1, id[3]), /*constants=*/0,
-                    [&](const float* x, const float*, const float*, float* out) {
-                      return lce_hip_softmax_f32((size_t)batch, (size_t)id[3], op.softmax_beta, x, out, stream);
-                    });
+    return OnePass(i, "a SOFTMAX", lce_tfl::kTensorFloat32, OutShape(1, 1, id[3]), /*fold_quantize=*/false, /*constants=*/0,
+                   [&](const void* x, const void*, const void*, void* out, int32_t*) {
+                     return lce_hip_softmax_f32((size_t)batch, (size_t)id[3], op.softmax_beta, (const float*)x, (float*)out, stream);
+                   });
   }
 
   // ---- the int8 head and the float / int8 boundary ("head_i8" and "quantize" of lce_tflite_model_open_passes) ----
@@ -2124,22 +2094,22 @@ struct Walk {
   lce_hip_status MeanI8(int32_t i) {
     const lce_hip_mean_i8_desc d = MeanI8Desc(model->m, model->m.operators[i], batch);
     if (lce_hip_status s = lce_hip_mean_i8_check(&d)) return s;
-    return HeadPass(i, kAbsorbedMeanI8, "an int8 MEAN", HeadShape(1, 1, d.channels, lce_tfl::kTensorInt8), /*constants=*/0,
-                    [&](const float* x, const float*, const float*, float* out) {
-                      return lce_hip_mean_i8(&d, (const int8_t*)x, (int8_t*)out, stream);
-                    }, lce_tfl::kTensorInt8);
+    return OnePass(i, "an int8 MEAN", lce_tfl::kTensorInt8, OutShape(1, 1, d.channels, lce_tfl::kTensorInt8), /*fold_quantize=*/false,
+                   /*constants=*/0, [&](const void* x, const void*, const void*, void* out, int32_t*) {
+                     return lce_hip_mean_i8(&d, (const int8_t*)x, (int8_t*)out, stream);
+                   });
   }
 
   // An absorbed int8 FULLY_CONNECTED as ONE lce_hip_fully_connected_i8 launch; its bias lives in the prepared table.
   lce_hip_status FullyConnectedI8(int32_t i) {
     const lce_hip_fc_i8_desc d = FullyConnectedI8Desc(model->m, model->m.operators[i], batch);
     if (lce_hip_status s = lce_hip_fully_connected_i8_check(&d)) return s;
-    return HeadPass(i, kAbsorbedFullyConnectedI8, "an int8 FULLY_CONNECTED", HeadShape(1, 1, d.outputs, lce_tfl::kTensorInt8), /*constants=*/1,
-                    [&](const float* x, const float* weights, const float*, float* out) -> lce_hip_status {
-                      const int32_t* table = nullptr;
-                      if (lce_hip_status s = TableOnDevice(i, "an int8 FULLY_CONNECTED", &table)) return s;
-                      return lce_hip_fully_connected_i8(&d, (const int8_t*)x, (const int8_t*)weights, table, (int8_t*)out, stream);
-                    }, lce_tfl::kTensorInt8);
+    return OnePass(i, "an int8 FULLY_CONNECTED", lce_tfl::kTensorInt8, OutShape(1, 1, d.outputs, lce_tfl::kTensorInt8), /*fold_quantize=*/false,
+                   /*constants=*/1, [&](const void* x, const void* weights, const void*, void* out, int32_t*) -> lce_hip_status {
+                     const int32_t* table = nullptr;
+                     if (lce_hip_status s = TableOnDevice(i, "an int8 FULLY_CONNECTED", &table)) return s;
+                     return lce_hip_fully_connected_i8(&d, (const int8_t*)x, (const int8_t*)weights, table, (int8_t*)out, stream);
+                   });
   }
 
   // An absorbed int8 SOFTMAX as ONE lce_hip_softmax_i8 launch.
@@ -2150,11 +2120,11 @@ struct Walk {
     int32_t id[4];
     if (!Carried(in, id)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a SOFTMAX of a rank that is neither 2 nor 4");
     if (lce_hip_status s = lce_hip_softmax_i8_check((size_t)batch, (size_t)id[3], in.scale, op.softmax_beta, out.scale, (int32_t)out.zero_point)) return s;
-    return HeadPass(i, kAbsorbedSoftmaxI8, "an int8 SOFTMAX", HeadShape(1, 1, id[3], lce_tfl::kTensorInt8), /*constants=*/0,
-                    [&](const float* x, const float*, const float*, float* o) {
-                      return lce_hip_softmax_i8((size_t)batch, (size_t)id[3], in.scale, op.softmax_beta, out.scale, (int32_t)out.zero_point,
-                                                (const int8_t*)x, (int8_t*)o, stream);
-                    }, lce_tfl::kTensorInt8);
+    return OnePass(i, "an int8 SOFTMAX", lce_tfl::kTensorInt8, OutShape(1, 1, id[3], lce_tfl::kTensorInt8), /*fold_quantize=*/false,
+                   /*constants=*/0, [&](const void* x, const void*, const void*, void* o, int32_t*) {
+                     return lce_hip_softmax_i8((size_t)batch, (size_t)id[3], in.scale, op.softmax_beta, out.scale, (int32_t)out.zero_point,
+                                               (const int8_t*)x, (int8_t*)o, stream);
+                   });
   }
 
   // An absorbed QUANTIZE (float32 -> int8) or DEQUANTIZE (int8 -> float32) as ONE launch over the tensor's elements.
@@ -2167,14 +2137,14 @@ struct Walk {
     const float scale = q.scale;
     const int32_t zp = (int32_t)q.zero_point;
     if (to_int8)
-      return HeadPass(i, kAbsorbedQuantize, "a QUANTIZE", HeadShape(id[1], id[2], id[3], lce_tfl::kTensorInt8), /*constants=*/0,
-                      [&](const float* x, const float*, const float*, float* out) {
-                        return lce_hip_quantize_f32_i8(n, scale, zp, x, (int8_t*)out, stream);
-                      });
-    return HeadPass(i, kAbsorbedDequantize, "a DEQUANTIZE", HeadShape(id[1], id[2], id[3]), /*constants=*/0,
-                    [&](const float* x, const float*, const float*, float* out) {
-                      return lce_hip_dequantize_i8_f32(n, scale, zp, (const int8_t*)x, out, stream);
-                    }, lce_tfl::kTensorInt8);
+      return OnePass(i, "a QUANTIZE", lce_tfl::kTensorFloat32, OutShape(id[1], id[2], id[3], lce_tfl::kTensorInt8), /*fold_quantize=*/false,
+                     /*constants=*/0, [&](const void* x, const void*, const void*, void* out, int32_t*) {
+                       return lce_hip_quantize_f32_i8(n, scale, zp, (const float*)x, (int8_t*)out, stream);
+                     });
+    return OnePass(i, "a DEQUANTIZE", lce_tfl::kTensorInt8, OutShape(id[1], id[2], id[3]), /*fold_quantize=*/false, /*constants=*/0,
+                   [&](const void* x, const void*, const void*, void* out, int32_t*) {
+                     return lce_hip_dequantize_i8_f32(n, scale, zp, (const int8_t*)x, (float*)out, stream);
+                   });
   }
   lce_hip_status QuantizeF32I8(int32_t i) { return Boundary(i, true); }
   lce_hip_status DequantizeI8F32(int32_t i) { return Boundary(i, false); }
@@ -2305,7 +2275,7 @@ struct Walk {
       const lce_tfl::Tensor& T = M.tensors[t];
       Shape sh;
       // (a rank-2 input -- of a head that starts behind a host operator -- is carried as [batch, 1, 1, C])
-      if (T.shape.size() == 2 && (model->flags_int & (kInternalHead | kInternalHeadI8 | kInternalQuantize | kInternalActivation | kInternalReshape | kInternalBinaryDense))) {
+      if (T.shape.size() == 2 && model->rank2_inputs) {
         if (!Carried(T, sh.dims)) return Fail(LCE_HIP_ERR_INVALID, "run_section: a section input with an extent that is not positive");
       } else {
         if (T.shape.size() != 4) return Fail(LCE_HIP_ERR_UNSUPPORTED, "run_section: section inputs must be 4-D tensors (NHWC)");
@@ -2325,42 +2295,72 @@ struct Walk {
   }
 };
 
-// THE table of fused passes, in priority order (the first enabled row whose predicate holds takes the operator) and in the
-// order of the kinds (row k is kind k + 1).  A new pass is a row here, a predicate built from the helpers above, a walker that
-// ends in FoldQuantize / FoldBuffers / Launched, and an exported *_stats one-liner.
-const FusedPass kPasses[kAbsorbedCount - 1] = {
-    {kAbsorbedElementwise, 0, LCE_TFLITE_SECTIONS_ELEMENTWISE, ElementwiseCandidate, &Walk::ElementwiseChain},
-    {kAbsorbedInt8Add, 0, LCE_TFLITE_SECTIONS_INT8_ADD, Int8AddCandidate, &Walk::Int8Add},
-    {kAbsorbedConcat, 0, LCE_TFLITE_SECTIONS_CONCAT, ConcatCandidate, &Walk::Concat},
-    {kAbsorbedPool, 1, LCE_TFLITE_SECTIONS_EXT_POOL, PoolCandidate, &Walk::Pool2d},
-    {kAbsorbedConv1x1, 1, LCE_TFLITE_SECTIONS_EXT_CONV1X1, Conv1x1Candidate, &Walk::Conv1x1},
-    {kAbsorbedDepthwise, 1, LCE_TFLITE_SECTIONS_EXT_DEPTHWISE, DepthwiseCandidate, &Walk::Depthwise},
+// THE table of fused passes, in priority order (the first enabled row whose predicate holds and whose prepare step accepts takes
+// the operator) and in the order of the kinds (row k is kind k + 1).  A new pass is a row here, a predicate built from the helpers
+// above, a walker that ends in FoldQuantize / FoldBuffers / Launched, and an exported *_stats.  Columns: kind, name, predicate,
+// walker, prepare step, queued as an LCE operator, reads rank-2 tensors (FusedPass).
+// A row whose prepare step refuses hands the operator to the rows below it.  For the binary Dense row that is the point: the head's
+// FULLY_CONNECTED row takes what it refuses.  For the three int8 rows it is the same as leaving the operator with the host, because
+// every predicate begins with its builtin code and no row below accepts theirs: below the int8 CONV_2D row stand DEPTHWISE_CONV_2D,
+// MEAN, FULLY_CONNECTED, SOFTMAX, QUANTIZE, DEQUANTIZE, the activations, RESHAPE and ADD / MUL (the gate); below the int8
+// DEPTHWISE_CONV_2D row the same without the first; below the int8 FULLY_CONNECTED row SOFTMAX and what follows it.
+constexpr bool kAsLce = true, kRank2 = true;
+constexpr FusedPass kPasses[kAbsorbedCount - 1] = {
+    {kAbsorbedElementwise, Named("elementwise"), ElementwiseCandidate, &Walk::ElementwiseChain, nullptr, false, false},
+    {kAbsorbedInt8Add, Named("int8_add"), Int8AddCandidate, &Walk::Int8Add, nullptr, false, false},
+    {kAbsorbedConcat, Named("concat"), ConcatCandidate, &Walk::Concat, nullptr, false, false},
+    {kAbsorbedPool, Named("pool"), PoolCandidate, &Walk::Pool2d, nullptr, false, false},
+    {kAbsorbedConv1x1, Named("conv1x1"), Conv1x1Candidate, &Walk::Conv1x1, nullptr, false, false},
+    {kAbsorbedDepthwise, Named("depthwise"), DepthwiseCandidate, &Walk::Depthwise, nullptr, false, false},
     // (Conv1x1Candidate is tried first: with both bits a 1x1 filter runs as before)
-    {kAbsorbedConv2d, 1, LCE_TFLITE_SECTIONS_EXT_CONV2D, Conv2dCandidate, &Walk::Conv2d},
-    // the quantized convolution: an internal flag (lce_tflite_model_open_passes, "conv2d_i8"); no float predicate takes an int8 tensor
-    {kAbsorbedConvI8, 2, kInternalConvI8, ConvI8Candidate, &Walk::ConvI8},
-    // the quantized depthwise convolution ("depthwise_i8"): DepthwiseCandidate above takes float tensors only
-    {kAbsorbedDepthwiseI8, 2, kInternalDepthwiseI8, DepthwiseI8Candidate, &Walk::DepthwiseI8},
-    // the classifier head: one internal flag enables the three rows (lce_tflite_model_open_passes, "head")
-    {kAbsorbedMean, 2, kInternalHead, MeanCandidate, &Walk::Mean},
-    // the binarized Dense layer ("binary_dense"): in front of the head's FULLY_CONNECTED row, which takes what this one refuses
-    {kAbsorbedBinaryDense, 2, kInternalBinaryDense, BinaryDenseCandidate, &Walk::BinaryDense},
-    {kAbsorbedFullyConnected, 2, kInternalHead, FullyConnectedCandidate, &Walk::FullyConnected},
-    {kAbsorbedSoftmax, 2, kInternalHead, SoftmaxCandidate, &Walk::Softmax},
-    // the int8 head ("head_i8") and the float / int8 boundary ("quantize"): no float predicate above takes an int8 MEAN /
-    // FULLY_CONNECTED / SOFTMAX and none of these takes a float one, so the two heads never compete
-    {kAbsorbedMeanI8, 2, kInternalHeadI8, MeanI8Candidate, &Walk::MeanI8},
-    {kAbsorbedFullyConnectedI8, 2, kInternalHeadI8, FullyConnectedI8Candidate, &Walk::FullyConnectedI8},
-    {kAbsorbedSoftmaxI8, 2, kInternalHeadI8, SoftmaxI8Candidate, &Walk::SoftmaxI8},
-    {kAbsorbedQuantize, 2, kInternalQuantize, QuantizeCandidate, &Walk::QuantizeF32I8},
-    {kAbsorbedDequantize, 2, kInternalQuantize, DequantizeCandidate, &Walk::DequantizeI8F32},
-    // the standalone activations ("activation") and the per-image gate ("gate") are steps of the elementwise chain, so their walker
-    // is the chain's; ElementwiseCandidate above takes no ADD / MUL with a non-constant [b,1,1,C] input on a larger image, and where
-    // the image is 1 x 1 the gate is a tensor operand like any other.  RESHAPE ("reshape") launches nothing.
-    {kAbsorbedActivation, 2, kInternalActivation, ActivationCandidate, &Walk::ElementwiseChain},
-    {kAbsorbedReshape, 2, kInternalReshape, ReshapeCandidate, &Walk::Reshape},
-    {kAbsorbedGate, 2, kInternalGate, GateCandidate, &Walk::ElementwiseChain},
+    {kAbsorbedConv2d, Named("conv2d"), Conv2dCandidate, &Walk::Conv2d, nullptr, false, false},
+    // the quantized convolution: no float predicate takes an int8 tensor
+    {kAbsorbedConvI8, Named("conv2d_i8"), ConvI8Candidate, &Walk::ConvI8, ConvI8Prepare, false, false},
+    // the quantized depthwise convolution: DepthwiseCandidate above takes float tensors only
+    {kAbsorbedDepthwiseI8, Named("depthwise_i8"), DepthwiseI8Candidate, &Walk::DepthwiseI8, DepthwiseI8Prepare, false, false},
+    // the classifier head: one name enables the three rows.  MEAN reads an image; the Dense layer and the softmax may read [b, C]
+    {kAbsorbedMean, Named("head"), MeanCandidate, &Walk::Mean, nullptr, kAsLce, false},
+    // the binarized Dense layer: in front of the head's FULLY_CONNECTED row, which takes what this one refuses
+    {kAbsorbedBinaryDense, Named("binary_dense"), BinaryDenseCandidate, &Walk::BinaryDense, BinaryDensePrepare, kAsLce, kRank2},
+    {kAbsorbedFullyConnected, Named("head"), FullyConnectedCandidate, &Walk::FullyConnected, nullptr, kAsLce, kRank2},
+    {kAbsorbedSoftmax, Named("head"), SoftmaxCandidate, &Walk::Softmax, nullptr, kAsLce, kRank2},
+    // the int8 head and the float / int8 boundary: no float predicate above takes an int8 MEAN / FULLY_CONNECTED / SOFTMAX and
+    // none of these takes a float one, so the two heads never compete
+    {kAbsorbedMeanI8, Named("head_i8"), MeanI8Candidate, &Walk::MeanI8, nullptr, kAsLce, false},
+    {kAbsorbedFullyConnectedI8, Named("head_i8"), FullyConnectedI8Candidate, &Walk::FullyConnectedI8, FullyConnectedI8Prepare, kAsLce, kRank2},
+    {kAbsorbedSoftmaxI8, Named("head_i8"), SoftmaxI8Candidate, &Walk::SoftmaxI8, nullptr, kAsLce, kRank2},
+    {kAbsorbedQuantize, Named("quantize"), QuantizeCandidate, &Walk::QuantizeF32I8, nullptr, false, kRank2},
+    {kAbsorbedDequantize, Named("quantize"), DequantizeCandidate, &Walk::DequantizeI8F32, nullptr, false, kRank2},
+    // the standalone activations and the per-image gate are steps of the elementwise chain, so their walker is the chain's;
+    // ElementwiseCandidate above takes no ADD / MUL with a non-constant [b,1,1,C] input on a larger image, and where the image is
+    // 1 x 1 the gate is a tensor operand like any other.  RESHAPE launches nothing.
+    {kAbsorbedActivation, Named("activation"), ActivationCandidate, &Walk::ElementwiseChain, nullptr, false, kRank2},
+    {kAbsorbedReshape, Named("reshape"), ReshapeCandidate, &Walk::Reshape, nullptr, false, kRank2},
+    {kAbsorbedGate, Named("gate"), GateCandidate, &Walk::ElementwiseChain, nullptr, false, false},
 };
+// (row k is kind k + 1, and every row names an entry of kPassNames)
+constexpr bool RowsInOrder() {
+  for (int k = 0; k < kAbsorbedCount - 1; ++k)
+    if (kPasses[k].kind != k + 1 || !kPasses[k].name) return false;
+  return true;
+}
+static_assert(RowsInOrder(), "kPasses");
+
+// The *_stats exports: `read` copies counters of the last run, under the model's lock, into the pointers that are not null.
+template <class Read>
+void Stats(lce_tflite_model* model, Read read) {
+  if (!model) return;
+  std::lock_guard<std::mutex> lock(model->run_mu);
+  read(model->last);
+}
+void Put(int32_t* out, int32_t value) {
+  if (out) *out = value;
+}
+using RunStats = lce_tflite_model::RunStats;
+// (launches of pass `kind`, LceQuantize launches folded into them): what most passes report
+void LaunchStats(lce_tflite_model* model, int kind, int32_t* launches, int32_t* quantize_folded) {
+  Stats(model, [&](const RunStats& r) { Put(launches, r.pass[kind].launches); Put(quantize_folded, r.pass[kind].quantize); });
+}
 }  // namespace
 
 extern "C" {
@@ -2454,83 +2454,63 @@ void lce_tflite_model_graph_stats(lce_tflite_model* model, int32_t* recorded, in
   if (replays) *replays = model->graph_replays;
 }
 
-// The counters of the fused pass `kind` in the last run; `ops_folded` is the elementwise pass's alone.
-static void PassStats(lce_tflite_model* model, int kind, int32_t* launches, int32_t* quantize_folded, int32_t* ops_folded = nullptr) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (launches) *launches = model->last.pass[kind].launches;
-  if (ops_folded) *ops_folded = model->last.ew_ops;
-  if (quantize_folded) *quantize_folded = model->last.pass[kind].quantize;
-}
 void lce_tflite_model_elementwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedElementwise, launches, quantize_folded, ops_folded);
+  Stats(model, [&](const RunStats& r) {
+    Put(launches, r.pass[kAbsorbedElementwise].launches); Put(ops_folded, r.ew_ops); Put(quantize_folded, r.pass[kAbsorbedElementwise].quantize);
+  });
 }
 void lce_tflite_model_int8_add_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedInt8Add, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedInt8Add, launches, quantize_folded);
 }
 void lce_tflite_model_concat_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedConcat, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedConcat, launches, quantize_folded);
 }
 void lce_tflite_model_pool_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedPool, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedPool, launches, quantize_folded);
 }
 void lce_tflite_model_conv1x1_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedConv1x1, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedConv1x1, launches, quantize_folded);
 }
 void lce_tflite_model_depthwise_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedDepthwise, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedDepthwise, launches, quantize_folded);
 }
 void lce_tflite_model_conv2d_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedConv2d, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedConv2d, launches, quantize_folded);
 }
 void lce_tflite_model_conv_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedConvI8, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedConvI8, launches, quantize_folded);
 }
-
 void lce_tflite_model_depthwise_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedDepthwiseI8, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedDepthwiseI8, launches, quantize_folded);
 }
-
-void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {
-  PassStats(model, kAbsorbedMean, mean, nullptr);
-  PassStats(model, kAbsorbedFullyConnected, fully_connected, nullptr);
-  PassStats(model, kAbsorbedSoftmax, softmax, nullptr);
-}
-
-void lce_tflite_model_binary_dense_stats(lce_tflite_model* model, int32_t* launches, int32_t* dequantize_skipped, int32_t* quantize_absorbed) {
-  PassStats(model, kAbsorbedBinaryDense, launches, quantize_absorbed);
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (dequantize_skipped) *dequantize_skipped = model->last.dequantize_skipped;
-}
-
-void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {
-  PassStats(model, kAbsorbedMeanI8, mean, nullptr);
-  PassStats(model, kAbsorbedFullyConnectedI8, fully_connected, nullptr);
-  PassStats(model, kAbsorbedSoftmaxI8, softmax, nullptr);
-}
-
-void lce_tflite_model_quantize_stats(lce_tflite_model* model, int32_t* quantize, int32_t* dequantize) {
-  PassStats(model, kAbsorbedQuantize, quantize, nullptr);
-  PassStats(model, kAbsorbedDequantize, dequantize, nullptr);
-}
-
-void lce_tflite_model_activation_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedActivation, launches, quantize_folded);
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (ops_folded) *ops_folded = model->last.ex_ops;
-}
-
-void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies) {
-  if (!model) return;
-  std::lock_guard<std::mutex> lock(model->run_mu);
-  if (views) *views = model->last.reshape_views;
-  if (copies) *copies = model->last.reshape_copies;
-}
-
 void lce_tflite_model_gate_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded) {
-  PassStats(model, kAbsorbedGate, launches, quantize_folded);
+  LaunchStats(model, kAbsorbedGate, launches, quantize_folded);
+}
+void lce_tflite_model_head_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {
+  Stats(model, [&](const RunStats& r) {
+    Put(mean, r.pass[kAbsorbedMean].launches); Put(fully_connected, r.pass[kAbsorbedFullyConnected].launches); Put(softmax, r.pass[kAbsorbedSoftmax].launches);
+  });
+}
+void lce_tflite_model_head_i8_stats(lce_tflite_model* model, int32_t* mean, int32_t* fully_connected, int32_t* softmax) {
+  Stats(model, [&](const RunStats& r) {
+    Put(mean, r.pass[kAbsorbedMeanI8].launches); Put(fully_connected, r.pass[kAbsorbedFullyConnectedI8].launches); Put(softmax, r.pass[kAbsorbedSoftmaxI8].launches);
+  });
+}
+void lce_tflite_model_binary_dense_stats(lce_tflite_model* model, int32_t* launches, int32_t* dequantize_skipped, int32_t* quantize_absorbed) {
+  Stats(model, [&](const RunStats& r) {
+    Put(launches, r.pass[kAbsorbedBinaryDense].launches); Put(dequantize_skipped, r.dequantize_skipped); Put(quantize_absorbed, r.pass[kAbsorbedBinaryDense].quantize);
+  });
+}
+void lce_tflite_model_quantize_stats(lce_tflite_model* model, int32_t* quantize, int32_t* dequantize) {
+  Stats(model, [&](const RunStats& r) { Put(quantize, r.pass[kAbsorbedQuantize].launches); Put(dequantize, r.pass[kAbsorbedDequantize].launches); });
+}
+void lce_tflite_model_activation_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+  Stats(model, [&](const RunStats& r) {
+    Put(launches, r.pass[kAbsorbedActivation].launches); Put(ops_folded, r.ex_ops); Put(quantize_folded, r.pass[kAbsorbedActivation].quantize);
+  });
+}
+void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies) {
+  Stats(model, [&](const RunStats& r) { Put(views, r.reshape_views); Put(copies, r.reshape_copies); });
 }
 
 void lce_tflite_model_run_stats(lce_tflite_model* model, int32_t* cached_plans, int32_t* fused_quantize_ops, size_t* scratch_bytes) {

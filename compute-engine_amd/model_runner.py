@@ -127,33 +127,46 @@ class _OpenOptions56(C.Structure):
                 ("reserved2", C.c_uint32 * 4), ("reserved3", C.c_uint32 * 4)]
 
 
-# The keywords of ``LceModel`` that let builtin operators join the sections: (keyword, word of the options -- 0 ``sections``,
-# 1 ``sections_ext`` --, bit, the smallest form of ``lce_tflite_open_options`` that carries the bit; 0:
-# ``lce_tflite_model_open_ex`` does).
-_SECTION_KEYWORDS = (
-    ("elementwise_sections", 0, SECTIONS_ELEMENTWISE, 0),
-    ("int8_add_sections", 0, SECTIONS_INT8_ADD, 0),
-    ("concat_sections", 0, SECTIONS_CONCAT, 8),
-    ("pool_sections", 1, SECTIONS_EXT_POOL, 24),
-    ("conv1x1_sections", 1, SECTIONS_EXT_CONV1X1, 40),
-    ("depthwise_sections", 1, SECTIONS_EXT_DEPTHWISE, 56),
-    ("conv2d_sections", 1, SECTIONS_EXT_CONV2D, 56),
-    ("stem_sections", 1, SECTIONS_EXT_STEM, 56),
+# THE table of the keywords of ``LceModel`` that let builtin operators join the sections, in the order their names are passed to
+# ``lce_tflite_model_open_passes``: (keyword, name of the pass there, word of the options -- 0 ``sections``, 1 ``sections_ext`` --,
+# bit, the smallest form of ``lce_tflite_open_options`` that carries the bit; 0: ``lce_tflite_model_open_ex`` does).  Word, bit and
+# form are None for a keyword whose name only ``lce_tflite_model_open_passes`` knows.  A new pass is a row here, a row of
+# ``_PASS_STATS``, a ``*_stats`` method and a sentence in ``LceModel``'s docstring.
+_PASSES = (
+    ("elementwise_sections", "elementwise", 0, SECTIONS_ELEMENTWISE, 0),
+    ("int8_add_sections", "int8_add", 0, SECTIONS_INT8_ADD, 0),
+    ("concat_sections", "concat", 0, SECTIONS_CONCAT, 8),
+    ("pool_sections", "pool", 1, SECTIONS_EXT_POOL, 24),
+    ("conv1x1_sections", "conv1x1", 1, SECTIONS_EXT_CONV1X1, 40),
+    ("depthwise_sections", "depthwise", 1, SECTIONS_EXT_DEPTHWISE, 56),
+    ("conv2d_sections", "conv2d", 1, SECTIONS_EXT_CONV2D, 56),
+    ("stem_sections", "stem", 1, SECTIONS_EXT_STEM, 56),
+    ("head_sections", "head", None, None, None),
+    ("conv2d_i8_sections", "conv2d_i8", None, None, None),
+    ("head_i8_sections", "head_i8", None, None, None),
+    ("quantize_sections", "quantize", None, None, None),
+    ("depthwise_i8_sections", "depthwise_i8", None, None, None),
+    ("activation_sections", "activation", None, None, None),
+    ("reshape_sections", "reshape", None, None, None),
+    ("gate_sections", "gate", None, None, None),
+    ("binary_dense_sections", "binary_dense", None, None, None),
 )
-# the names of ``lce_tflite_model_open_passes`` (the only entry that knows ``head``), by keyword
-_PASS_NAMES = {"elementwise_sections": "elementwise", "int8_add_sections": "int8_add", "concat_sections": "concat",
-               "pool_sections": "pool", "conv1x1_sections": "conv1x1", "depthwise_sections": "depthwise",
-               "conv2d_sections": "conv2d", "stem_sections": "stem", "head_sections": "head", "conv2d_i8_sections": "conv2d_i8",
-               "head_i8_sections": "head_i8", "quantize_sections": "quantize", "depthwise_i8_sections": "depthwise_i8",
-               "activation_sections": "activation", "reshape_sections": "reshape", "gate_sections": "gate",
-               "binary_dense_sections": "binary_dense"}
-# the keywords whose names only ``lce_tflite_model_open_passes`` knows, in the order their names are passed
-_NAMED_ONLY = ("head_sections", "conv2d_i8_sections", "head_i8_sections", "quantize_sections", "depthwise_i8_sections",
-               "activation_sections", "reshape_sections", "gate_sections", "binary_dense_sections")
+# three views of it: the keywords an options struct carries, every keyword's name, the keywords only the names reach
+_SECTION_KEYWORDS = tuple((keyword, word, bit, form) for keyword, _, word, bit, form in _PASSES if word is not None)
+_PASS_NAMES = {keyword: name for keyword, name, _, _, _ in _PASSES}
+_NAMED_ONLY = tuple(keyword for keyword, _, word, _, _ in _PASSES if word is None)
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
-# ``lce_tflite_model_<pass>_stats``: the counters each reports
+# ``lce_tflite_model_<pass>_stats`` and ``LceModel.<pass>_stats()``: the counters each reports
 _PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2,
-               "depthwise_i8": 2}
+               "depthwise_i8": 2, "head": 3, "head_i8": 3, "quantize": 2, "activation": 3, "gate": 2, "reshape": 2, "binary_dense": 3}
+
+
+def _section_keywords(where, sections):
+    """``sections`` -- the ``**sections`` of ``where`` -- checked against ``_PASSES``: {keyword: bool} for every keyword."""
+    for keyword in sections:
+        if keyword not in _PASS_NAMES:
+            raise TypeError("%s() got an unexpected keyword argument %r" % (where, keyword))
+    return {keyword: bool(sections.get(keyword, False)) for keyword in _PASS_NAMES}
 
 
 class Section:
@@ -185,13 +198,6 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_open_opts.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t]   # either form of the options
         l.lce_tflite_model_open_passes.restype = C.c_void_p
         l.lce_tflite_model_open_passes.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_size_t]
-        l.lce_tflite_model_head_stats.argtypes, l.lce_tflite_model_head_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
-        l.lce_tflite_model_head_i8_stats.argtypes, l.lce_tflite_model_head_i8_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
-        l.lce_tflite_model_quantize_stats.argtypes, l.lce_tflite_model_quantize_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
-        l.lce_tflite_model_activation_stats.argtypes, l.lce_tflite_model_activation_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
-        l.lce_tflite_model_gate_stats.argtypes, l.lce_tflite_model_gate_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
-        l.lce_tflite_model_reshape_stats.argtypes, l.lce_tflite_model_reshape_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 2, None
-        l.lce_tflite_model_binary_dense_stats.argtypes, l.lce_tflite_model_binary_dense_stats.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3, None
         l.lce_tflite_model_operator_reducer.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_fully_connected.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_softmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -268,14 +274,9 @@ class Operator:
 class LceModel:
     """A parsed .tflite flatbuffer (first subgraph)."""
 
-    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], elementwise_sections: bool = False,
-                 int8_add_sections: bool = False, concat_sections: bool = False, pool_sections: bool = False,
-                 conv1x1_sections: bool = False, depthwise_sections: bool = False, conv2d_sections: bool = False,
-                 stem_sections: bool = False, head_sections: bool = False, conv2d_i8_sections: bool = False,
-                 head_i8_sections: bool = False, quantize_sections: bool = False, depthwise_i8_sections: bool = False,
-                 activation_sections: bool = False, reshape_sections: bool = False, gate_sections: bool = False,
-                 binary_dense_sections: bool = False):
-        """``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
+    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], **sections):
+        """``sections``: the keywords of ``_PASSES``, each False unless given; each becomes an attribute.
+        ``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
         CONCATENATION of a dense block joins them (LCE_TFLITE_SECTIONS_CONCAT, through ``lce_tflite_model_open_opts``).  ``pool_sections``: the
@@ -310,29 +311,19 @@ class LceModel:
             with open(flatbuffer, "rb") as f:
                 flatbuffer = f.read()
         self._data = bytes(flatbuffer)            # must outlive the handle (zero-copy reader)
-        given = dict(elementwise_sections=elementwise_sections, int8_add_sections=int8_add_sections, concat_sections=concat_sections,
-                     pool_sections=pool_sections, conv1x1_sections=conv1x1_sections, depthwise_sections=depthwise_sections,
-                     conv2d_sections=conv2d_sections, stem_sections=stem_sections)
-        words, size = [0, 0], 0               # the two flag words, and the smallest form that carries every bit asked for
+        given = _section_keywords("LceModel", sections)
+        self.__dict__.update(given)
+        # a name only lce_tflite_model_open_passes knows goes there; otherwise the smallest form of the options that carries every
+        # bit asked for; otherwise lce_tflite_model_open_ex
+        words, size = [0, 0], 0
         for keyword, word, bit, form in _SECTION_KEYWORDS:
-            setattr(self, keyword, bool(given[keyword]))
             if given[keyword]:
                 words[word] |= bit
                 size = max(size, form)
-        self.head_sections = bool(head_sections)
-        self.conv2d_i8_sections = bool(conv2d_i8_sections)
-        self.head_i8_sections = bool(head_i8_sections)
-        self.quantize_sections = bool(quantize_sections)
-        self.depthwise_i8_sections = bool(depthwise_i8_sections)
-        self.activation_sections = bool(activation_sections)
-        self.reshape_sections = bool(reshape_sections)
-        self.gate_sections = bool(gate_sections)
-        self.binary_dense_sections = bool(binary_dense_sections)
         err = C.create_string_buffer(256)
-        if any(getattr(self, keyword) for keyword in _NAMED_ONLY):
-            names = [_PASS_NAMES[keyword] for keyword, _, _, _ in _SECTION_KEYWORDS if given[keyword]]
-            names += [_PASS_NAMES[keyword] for keyword in _NAMED_ONLY if getattr(self, keyword)]
-            self._h = tflite_lib().lce_tflite_model_open_passes(self._data, len(self._data), ",".join(names).encode(), err, 256)
+        if any(given[keyword] for keyword in _NAMED_ONLY):
+            names = ",".join(name for keyword, name, _, _, _ in _PASSES if given[keyword])
+            self._h = tflite_lib().lce_tflite_model_open_passes(self._data, len(self._data), names.encode(), err, 256)
         elif size:
             opts = _OPEN_OPTIONS[size](size, *words[:1 if size == 8 else 2])
             self._h = tflite_lib().lce_tflite_model_open_opts(self._data, len(self._data), C.byref(opts), err, 256)
@@ -451,46 +442,32 @@ class LceModel:
 
     def head_stats(self):
         """(MEAN launches, lce_hip_fully_connected_f32 launches, lce_hip_softmax_f32 launches) of the last run."""
-        v = [C.c_int32() for _ in range(3)]
-        tflite_lib().lce_tflite_model_head_stats(self._h, *[C.byref(c) for c in v])
-        return tuple(int(c.value) for c in v)
+        return self._pass_stats("head")
 
     def head_i8_stats(self):
         """(lce_hip_mean_i8, lce_hip_fully_connected_i8, lce_hip_softmax_i8 launches) of the last run."""
-        v = [C.c_int32() for _ in range(3)]
-        tflite_lib().lce_tflite_model_head_i8_stats(self._h, *[C.byref(c) for c in v])
-        return tuple(int(c.value) for c in v)
+        return self._pass_stats("head_i8")
 
     def quantize_stats(self):
         """(lce_hip_quantize_f32_i8 launches, lce_hip_dequantize_i8_f32 launches) of the last run."""
-        v = [C.c_int32() for _ in range(2)]
-        tflite_lib().lce_tflite_model_quantize_stats(self._h, *[C.byref(c) for c in v])
-        return tuple(int(c.value) for c in v)
+        return self._pass_stats("quantize")
 
     def activation_stats(self):
         """(lce_hip_elementwise_ex launches, operators of every kind they ran, LceQuantize launches they absorbed) of the last run."""
-        v = [C.c_int32() for _ in range(3)]
-        tflite_lib().lce_tflite_model_activation_stats(self._h, *[C.byref(c) for c in v])
-        return tuple(int(c.value) for c in v)
+        return self._pass_stats("activation")
 
     def gate_stats(self):
         """(lce_hip_elementwise_ex launches that hold a gate, LceQuantize launches they absorbed) of the last run."""
-        v = [C.c_int32() for _ in range(2)]
-        tflite_lib().lce_tflite_model_gate_stats(self._h, *[C.byref(c) for c in v])
-        return tuple(int(c.value) for c in v)
+        return self._pass_stats("gate")
 
     def binary_dense_stats(self):
         """(lce_hip_binary_fully_connected launches, LceDequantize operators not launched because only binary Dense layers read
         them, LceQuantize launches the layers absorbed) of the last run."""
-        v = [C.c_int32() for _ in range(3)]
-        tflite_lib().lce_tflite_model_binary_dense_stats(self._h, *[C.byref(c) for c in v])
-        return tuple(int(c.value) for c in v)
+        return self._pass_stats("binary_dense")
 
     def reshape_stats(self):
         """(RESHAPE operators that were a view, RESHAPE operators that cost a device-to-device copy) of the last run."""
-        v = [C.c_int32() for _ in range(2)]
-        tflite_lib().lce_tflite_model_reshape_stats(self._h, *[C.byref(c) for c in v])
-        return tuple(int(c.value) for c in v)
+        return self._pass_stats("reshape")
 
     def use_hip_graphs(self, on: bool = True):
         """``lce_tflite_model_use_hip_graphs``: run_section records a section's launches once per (batch, stream, tensor
@@ -519,31 +496,16 @@ class LceModel:
 class Interpreter:
     """``Interpreter(flatbuffer_model, batch_size=...)`` -- see the module docstring."""
 
-    def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0",
-                 use_reference_bconv: bool = False, elementwise_sections: bool = False, int8_add_sections: bool = False,
-                 concat_sections: bool = False, pool_sections: bool = False, conv1x1_sections: bool = False,
-                 depthwise_sections: bool = False, conv2d_sections: bool = False, stem_sections: bool = False,
-                 head_sections: bool = False, conv2d_i8_sections: bool = False, head_i8_sections: bool = False,
-                 quantize_sections: bool = False, depthwise_i8_sections: bool = False, activation_sections: bool = False,
-                 reshape_sections: bool = False, gate_sections: bool = False, binary_dense_sections: bool = False):
-        """``elementwise_sections``, ``int8_add_sections``, ``concat_sections``, ``pool_sections``, ``conv1x1_sections``, ``depthwise_sections``,
-        ``conv2d_sections``, ``stem_sections``, ``head_sections``, ``conv2d_i8_sections``, ``head_i8_sections``, ``quantize_sections``,
-        ``depthwise_i8_sections``, ``activation_sections``, ``reshape_sections``, ``gate_sections``, ``binary_dense_sections``: see ``LceModel`` (ignored when a ready ``LceModel`` is passed: its
-        own settings hold)."""
-        self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
-                      else LceModel(flatbuffer_model, elementwise_sections=elementwise_sections,
-                                    int8_add_sections=int8_add_sections, concat_sections=concat_sections,
-                                    pool_sections=pool_sections, conv1x1_sections=conv1x1_sections,
-                                    depthwise_sections=depthwise_sections, conv2d_sections=conv2d_sections,
-                                    stem_sections=stem_sections, head_sections=head_sections,
-                                    conv2d_i8_sections=conv2d_i8_sections, head_i8_sections=head_i8_sections,
-                                    quantize_sections=quantize_sections, depthwise_i8_sections=depthwise_i8_sections,
-                                    activation_sections=activation_sections, reshape_sections=reshape_sections,
-                                    gate_sections=gate_sections, binary_dense_sections=binary_dense_sections))
+    def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0", use_reference_bconv: bool = False,
+                 **sections):
+        """``sections``: the ``*_sections`` keywords of ``LceModel``, described there (checked, then ignored, when a ready
+        ``LceModel`` is passed: its own settings hold)."""
+        _section_keywords("Interpreter", sections)
+        self.model = flatbuffer_model if isinstance(flatbuffer_model, LceModel) else LceModel(flatbuffer_model, **sections)
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if any(getattr(self.model, keyword) for keyword in _NAMED_ONLY) or any(getattr(self.model, keyword) for keyword, _, _, _ in _SECTION_KEYWORDS):
+        if any(getattr(self.model, keyword) for keyword in _PASS_NAMES):
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

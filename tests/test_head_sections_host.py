@@ -308,3 +308,39 @@ def test_a_head_behind_an_operator_of_the_host_is_a_section_of_its_own():
     assert not mr.Interpreter(model).lce_only
     assert model.section_tensor_shape(0, info["t"], 2)[0] == (2, 5, 5, 40) and model.section_tensor_shape(0, out, 2)[0] == (2, 1, 1, 7)
     assert [s.ops for s in mr.LceModel(data, **HM.ALL_FLAGS).sections] == []
+
+
+# ---- the tables of model_runner.py against the library -------------------------------------------------------------------------------
+def test_every_row_of_the_python_tables_is_one_the_library_knows():
+    """_PASSES (keyword, name) and _PASS_STATS (export, counters) from the outside: the library accepts each name alone, the keyword
+    sets its own attribute and no other, an unknown keyword is a TypeError, and every *_stats method reports as many zeros as the
+    table says on a model that has not run."""
+    data = SM.small_model()[0]
+    lib = mr.tflite_lib()
+    keywords = [row[0] for row in mr._PASSES]
+    assert len(mr._PASSES) == 17 and len(set(keywords)) == 17 and len({row[1] for row in mr._PASSES}) == 17
+    assert keywords == [k for k, _, _, _ in mr._SECTION_KEYWORDS] + list(mr._NAMED_ONLY) == list(mr._PASS_NAMES)
+    for keyword, name, word, bit, form in mr._PASSES:
+        assert (word is None) == (bit is None) == (form is None) == (keyword in mr._NAMED_ONLY), keyword
+        assert keyword == name + "_sections" and mr._PASS_NAMES[keyword] == name
+        h, err, _ = open_passes(data, name.encode())
+        assert h, (name, err)
+        lib.lce_tflite_model_close(h)
+        model = mr.LceModel(data, **{keyword: True})
+        assert [k for k in keywords if getattr(model, k)] == [keyword]
+        assert all(getattr(model, k) is False for k in keywords if k != keyword) and getattr(model, keyword) is True
+        assert mr.Interpreter(data, **{keyword: True}).model.__dict__[keyword] is True
+    for constructor in (mr.LceModel, mr.Interpreter):
+        for unknown in ("tail_sections", "head", "elementwise_section"):
+            with pytest.raises(TypeError, match=unknown):
+                constructor(data, **{unknown: True})
+            with pytest.raises(TypeError, match=unknown):
+                constructor(data, head_sections=True, **{unknown: False})
+    with pytest.raises(TypeError, match="tail_sections"):
+        mr.Interpreter(mr.LceModel(data), tail_sections=True)            # (checked even where a ready model makes it moot)
+    assert len(mr._PASS_STATS) == 16
+    model = mr.LceModel(data)
+    for name, counters in mr._PASS_STATS.items():
+        assert hasattr(lib, "lce_tflite_model_%s_stats" % name), name
+        assert getattr(model, name + "_stats")() == (0,) * counters, name
+        assert getattr(mr.LceModel, name + "_stats").__doc__, name
