@@ -39,7 +39,7 @@ ABI_SYMBOLS = (
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
     "lce_hip_elementwise_ex", "lce_hip_elementwise_grid_cap",
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
-    "lce_hip_concat", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
+    "lce_hip_concat", "lce_hip_join_windows", "lce_hip_join_windows_check", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
     "lce_hip_conv2d_i8", "lce_hip_conv2d_i8_check", "lce_hip_conv2d_i8_prepare",
     "lce_hip_depthwise_conv2d_i8", "lce_hip_depthwise_conv2d_i8_check", "lce_hip_depthwise_conv2d_i8_prepare",
@@ -63,6 +63,7 @@ EW_CLAMP, EW_PRELU, EW_LOGISTIC = 2, 3, 4                # lce_hip_ew_op_ex
 EW_PER_IMAGE_CHANNEL = 3                                # lce_hip_ew_operand_ex
 EW_MAX_STEPS = 8
 CONCAT_MAX_INPUTS = 8                                   # LCE_HIP_CONCAT_MAX_INPUTS
+JOIN_MAX_WINDOWS = 8                                    # LCE_HIP_JOIN_MAX_WINDOWS
 POOL_MAX, POOL_AVERAGE = 0, 1                           # lce_hip_pool_op
 POOL_MAX_TAPS = 65536                                   # LCE_HIP_POOL_MAX_TAPS
 ADD_INT8_LITERAL, ADD_INT8_SPLIT, ADD_INT8_SHIFT = 0, 1, 2   # lce_hip_add_int8_variant_id
@@ -219,6 +220,8 @@ def lib() -> C.CDLL:
                                               C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_concat.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_size_t, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_join_windows.argtypes = [C.c_int, C.POINTER(Window), C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_join_windows_check.argtypes = [C.c_int, C.POINTER(Window), C.c_int32]
         l.lce_hip_pool2d.argtypes = [C.POINTER(Pool2dDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_pool2d_check.argtypes = [C.POINTER(Pool2dDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_conv1x1_f32.argtypes = [C.POINTER(Conv1x1Desc)] + [C.c_void_p] * 6
@@ -839,6 +842,90 @@ def concat(tensors, out=None, out_bits=False, zero_point: int = 0, stream: int |
         check(lib().lce_hip_concat(kind, ptrs, ch, len(ins), rows, int(zero_point), _dev_ptr(out_d), _dev_ptr(bits_d),
                                    C.c_void_p(_stream_or_current(stream, dev))))
     return _results(host, out_d, bits_d, out)
+
+
+class Window(C.Structure):
+    """``lce_hip_window``."""
+    _fields_ = [("data_dev", C.c_void_p), ("pitch", C.c_int32), ("begin", C.c_int32), ("count", C.c_int32),
+                ("addend_dev", C.c_void_p), ("reserved", C.c_int32 * 2)]
+
+
+def _join_check(windows, out, out_bits, zero_point):
+    """Argument checks of ``join_windows`` on shapes and dtypes only (NumPy or torch): nothing here touches a device.  Returns
+    (lce_hip_dtype, leading shape, [(tensor, begin, count, addend or None)])."""
+    windows = [tuple(w) for w in windows]
+    if not 1 <= len(windows) <= JOIN_MAX_WINDOWS:
+        raise ValueError("join_windows: 1..%d windows, got %d" % (JOIN_MAX_WINDOWS, len(windows)))
+    if any(len(w) not in (3, 4) for w in windows):
+        raise ValueError("join_windows: a window is (tensor, begin, count) or (tensor, begin, count, addend)")
+    windows = [w if len(w) == 4 else w + (None,) for w in windows]
+    name = _dtype_name(windows[0][0])
+    kinds = {"float32": F32, "int8": I8}
+    if name not in kinds:
+        raise ValueError("join_windows: tensors must be float32 or int8, got %s" % name)
+    lead = tuple(windows[0][0].shape[:-1])
+    for k, (t, begin, count, addend) in enumerate(windows):
+        if _dtype_name(t) != name or len(t.shape) < 1 or tuple(t.shape[:-1]) != lead:
+            raise ValueError("join_windows: tensor %d must be %s of shape %r + (C,), got %s %r" % (k, name, lead, _dtype_name(t), tuple(t.shape)))
+        if not (isinstance(begin, (int, np.integer)) and isinstance(count, (int, np.integer)) and 0 <= begin and 1 <= count and
+                begin + count <= t.shape[-1]):
+            raise ValueError("join_windows: window %d: [%r, %r + %r) is no window of %d channels" % (k, begin, begin, count, t.shape[-1]))
+        if addend is not None:
+            if name != "float32":
+                raise ValueError("join_windows: window %d: only a float32 window takes an addend" % k)
+            if _dtype_name(addend) != "float32" or tuple(addend.shape) != lead + (int(count),):
+                raise ValueError("join_windows: window %d: the addend must be float32 of shape %r, got %s %r" %
+                                 (k, lead + (int(count),), _dtype_name(addend), tuple(addend.shape)))
+    zp = int(zero_point)
+    if (name == "int8" and not -128 <= zp <= 127) or (name != "int8" and zp != 0):
+        raise ValueError("join_windows: zero point %r (int8: -128..127; float32: 0)" % (zero_point,))
+    total = sum(int(w[2]) for w in windows)
+    _check_outputs("join_windows", out, True if out_bits else None, name, lead + (total,))
+    return kinds[name], lead, windows
+
+
+def join_windows(windows, out=None, out_bits=False, zero_point: int = 0, stream: int | None = None):
+    """The join of channel windows (``lce_hip_join_windows``): ``concat`` with every source a channel range of a wider tensor.
+    ``windows``: 1..8 of ``(tensor, begin, count)`` or ``(tensor, begin, count, addend)`` -- the channels [begin, begin + count)
+    of a tensor [..., C_k]; all tensors of one dtype (float32 or int8) and one leading shape, contiguous on one device (or NumPy:
+    copied to cuda:0 and back); a tensor may appear in several windows, and these may overlap.  ``addend`` (float32 only): a
+    dense [..., count] tensor added to the window (one float32 add); a window without one is a copy, bit for bit.  MeliusNet's
+    improvement block is ``join_windows([(x, 0, C - 64), (x, C - 64, 64, w)])``.  ``out``: a tensor [..., sum count] to fill (it
+    must not overlap a source or an addend), None for a new one, False for none.  ``out_bits``: True for the int32
+    [..., ceil(sum count / 32)] bits of the joined tensor (float32: value < 0; int8: value < ``zero_point``).  Returns
+    ``(joined or None, bits or None)``."""
+    kind, lead, windows = _join_check(windows, out, out_bits, zero_point)
+    import torch
+    host = isinstance(windows[0][0], np.ndarray)
+    dev = torch.device("cuda:0") if host else windows[0][0].device
+    on_dev = lambda a: _on_dev(a, dev, "join_windows", "the first tensor's")
+    placed = {}                                           # (a NumPy source that appears twice is copied once)
+    def once(a):
+        if id(a) not in placed:
+            placed[id(a)] = on_dev(a)
+        return placed[id(a)]
+    arr = (Window * len(windows))()
+    keep = []
+    for k, (t, begin, count, addend) in enumerate(windows):
+        td, ad = once(t), None if addend is None else once(addend)
+        keep += [td, ad]
+        arr[k].data_dev, arr[k].pitch, arr[k].begin, arr[k].count = td.data_ptr(), int(t.shape[-1]), int(begin), int(count)
+        arr[k].addend_dev = None if ad is None else ad.data_ptr()
+    first = keep[0]
+    total = sum(int(w[2]) for w in windows)
+    rows = first.numel() // first.shape[-1]
+    out_d = None if out is False else torch.empty(lead + (total,), dtype=first.dtype, device=dev) if out is None else on_dev(out)
+    bits_d = _new_bits(lead, total, dev) if out_bits else None
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_join_windows(kind, arr, len(windows), rows, int(zero_point), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                         C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, out)
+
+
+def channel_slice(x, begin: int, count: int, out=None, out_bits=False, zero_point: int = 0, stream: int | None = None):
+    """The channels [begin, begin + count) of ``x`` [..., C] (TFLite's STRIDED_SLICE / SLICE on the last axis) and their
+    LceQuantize, in one pass: the one-window ``join_windows``."""
+    return join_windows([(x, begin, count)], out=out, out_bits=out_bits, zero_point=zero_point, stream=stream)
 
 
 def _pair(who, name, v):

@@ -20,6 +20,7 @@
 #include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip, lce_tu_eltwise_ex.hip)
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
 #include "lce_kernels_concat.h"      // (lce_tu_concat.hip)
+#include "lce_kernels_join.h"        // (lce_tu_join.hip)
 #include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
 #include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
 #include "lce_kernels_depthwise.h"   // (lce_tu_depthwise.hip)
@@ -49,6 +50,7 @@
 #include "lce_tu_eltwise_ex.hip"
 #include "lce_tu_eltwise_i8.hip"
 #include "lce_tu_concat.hip"
+#include "lce_tu_join.hip"
 #include "lce_tu_pool.hip"
 #include "lce_tu_conv1x1.hip"
 #include "lce_tu_depthwise.hip"
@@ -995,6 +997,69 @@ lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev,
   const int kind = type == LCE_HIP_F32 ? lce::kConcatF32 : type == LCE_HIP_I8 ? lce::kConcatI8 : lce::kConcatWords;
   const int e = lce::launch_concat(a, kind, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_concat: launch failed: %s", hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// Join of channel windows (lce_kernels_join.h)
+// ------------------------------------------------------------------------------------
+static_assert(LCE_HIP_JOIN_MAX_WINDOWS == lce::kJoinMaxWindows, "the header's bound is the kernels'");
+lce_hip_status lce_hip_join_windows_check(lce_hip_dtype type, const lce_hip_window* windows, int32_t num_windows) {
+  const char* who = "lce_hip_join_windows";
+  if (type != LCE_HIP_F32 && type != LCE_HIP_I8) return fail(LCE_HIP_ERR_INVALID, "%s: type must be float32 or int8, got %d", who, (int)type);
+  if (num_windows < 1 || num_windows > LCE_HIP_JOIN_MAX_WINDOWS)
+    return fail(LCE_HIP_ERR_INVALID, "%s: num_windows must be 1..%d, got %d", who, LCE_HIP_JOIN_MAX_WINDOWS, (int)num_windows);
+  if (!windows) return fail(LCE_HIP_ERR_INVALID, "%s: null argument", who);
+  uint64_t sum = 0;
+  for (int32_t k = 0; k < num_windows; ++k) {
+    const lce_hip_window& w = windows[k];
+    if (!w.data_dev) return fail(LCE_HIP_ERR_INVALID, "%s: window %d: data_dev is null", who, (int)k);
+    if (w.reserved[0] != 0 || w.reserved[1] != 0) return fail(LCE_HIP_ERR_INVALID, "%s: window %d: reserved fields must be 0", who, (int)k);
+    if (w.begin < 0 || w.count < 1 || w.pitch < 1 || (int64_t)w.begin + (int64_t)w.count > (int64_t)w.pitch)
+      return fail(LCE_HIP_ERR_INVALID, "%s: window %d: [%d, %d + %d) is no window of %d channels", who, (int)k, (int)w.begin, (int)w.begin,
+                  (int)w.count, (int)w.pitch);
+    if (w.addend_dev && type != LCE_HIP_F32) return fail(LCE_HIP_ERR_INVALID, "%s: window %d: only a float32 window takes an addend", who, (int)k);
+    if ((uintptr_t)w.addend_dev % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: window %d: the addend must be 4-byte aligned", who, (int)k);
+    sum += (uint64_t)w.count;
+  }
+  if (sum >= (1ull << 31)) return fail(LCE_HIP_ERR_INVALID, "%s: the joined channel count must be below 2^31", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_join_windows(lce_hip_dtype type, const lce_hip_window* windows, int32_t num_windows, size_t rows,
+                                    int32_t zero_point, void* out_dev, int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_join_windows";
+  if (rows == 0) return LCE_HIP_OK;   // (an empty tensor may come with null pointers)
+  if (lce_hip_status s = lce_hip_join_windows_check(type, windows, num_windows)) return s;
+  if (type == LCE_HIP_I8 ? (zero_point < -128 || zero_point > 127) : zero_point != 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: zero point %d (int8: -128..127; float32: 0)", who, (int)zero_point);
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  if (rows >= (1ull << 32)) return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: rows must be below 2^32", who);
+  const uint64_t esz = type == LCE_HIP_I8 ? 1 : 4;
+  uint64_t sum = 0;
+  for (int32_t k = 0; k < num_windows; ++k) sum += (uint64_t)windows[k].count;
+  const uint64_t wpr = (sum + 31) / 32;
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? rows * sum * esz : 0);
+  const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? rows * wpr * 4 : 0);
+  if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "%s: the two outputs overlap", who);
+  lce::JoinWindow jw[lce::kJoinMaxWindows];
+  for (int32_t k = 0; k < num_windows; ++k) {
+    const lce_hip_window& w = windows[k];
+    const uintptr_t i0 = (uintptr_t)w.data_dev, i1 = i0 + rows * (uint64_t)w.pitch * esz;
+    if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the source of window %d", who, (int)k);
+    if (w.addend_dev) {
+      const uintptr_t a0 = (uintptr_t)w.addend_dev, a1 = a0 + rows * (uint64_t)w.count * 4;
+      if (meet(o0, o1, a0, a1) || meet(b0, b1, a0, a1)) return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the addend of window %d", who, (int)k);
+    }
+    jw[k] = lce::JoinWindow{w.data_dev, w.addend_dev, (uint32_t)w.pitch, (uint32_t)w.begin, (uint32_t)w.count};
+  }
+  if (lce_hip_status s = require_device()) return s;
+  const int kind = type == LCE_HIP_F32 ? lce::kJoinF32 : lce::kJoinI8;
+  lce::JoinArgs a;
+  const bool vec = lce::join_fill(a, kind, jw, (int)num_windows, rows, zero_point, out_dev, (uint32_t*)out_bits_dev);
+  if (vec) lce::join_set_stride(a, lce::join_vec_grid(a.total_chunks));
+  const int e = lce::launch_join(a, kind, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
 

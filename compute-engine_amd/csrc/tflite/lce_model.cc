@@ -23,10 +23,10 @@ struct lce_tflite_section {
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
        kAbsorbedConvI8, kAbsorbedDepthwiseI8, kAbsorbedMean, kAbsorbedBinaryDense, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
-       kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedActivation, kAbsorbedReshape, kAbsorbedGate, kAbsorbedCount };
+       kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedActivation, kAbsorbedReshape, kAbsorbedGate, kAbsorbedSlice, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
 enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u,
-       kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u, kInternalBinaryDense = 256u };
+       kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u, kInternalBinaryDense = 256u, kInternalSlice = 512u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
@@ -53,6 +53,7 @@ struct lce_tflite_model {
     int32_t ex_ops = 0;                                                 // operators of every kind inside the lce_hip_elementwise_ex launches
     int32_t reshape_views = 0, reshape_copies = 0;                      // absorbed RESHAPE operators: aliased / copied device to device
     int32_t dequantize_skipped = 0;                                     // LceDequantize operators only binary Dense layers read: not launched
+    int32_t slice_joins = 0;                                            // lce_hip_join_windows launches that took over a CONCATENATION
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
     Pass pass[kAbsorbedCount];                                          // by kAbsorbed* kind ([0] unused)
   };
@@ -944,6 +945,70 @@ bool GateCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return GateOperandSlot(M, o) >= 0;
 }
 
+// The channel window [begin, begin + count) that STRIDED_SLICE / SLICE `o` cuts out of its 4-D data input, resolved as TFLite
+// resolves a stride of 1: a masked begin is 0 and a masked end the extent, a negative index gets the extent added, begin and end
+// are then clamped to [0, extent]; for SLICE a size of -1 means "to the end".  False unless the index operands are constant int32
+// [4] tensors with data in the file, every stride is 1, axes 0..2 come out as their whole extent and axis 3 as a window of at
+// least one channel.
+bool SliceWindow(const lce_tfl::Model& M, const lce_tfl::Operator& o, int32_t* begin, int32_t* count) {
+  const bool strided = o.builtin_code == lce_tfl::kBuiltinStridedSlice;
+  const size_t operands = strided ? 4 : 3;
+  if (o.inputs.size() != operands) return false;
+  int32_t v[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {1, 1, 1, 1}};        // begin, end / size, strides
+  for (size_t k = 1; k < operands; ++k) {
+    if (o.inputs[k] < 0) return false;
+    const lce_tfl::Tensor& T = M.tensors[o.inputs[k]];
+    if (T.type != lce_tfl::kTensorInt32 || !T.data || T.shape.size() != 1 || T.shape[0] != 4 || T.bytes != 16) return false;
+    memcpy(v[k - 1], T.data, 16);
+  }
+  const std::vector<int32_t>& shape = M.tensors[o.inputs[0]].shape;
+  for (int axis = 0; axis < 4; ++axis) {
+    const int64_t extent = shape[axis];
+    int64_t b = v[0][axis], e = v[1][axis];
+    if (strided) {
+      if (v[2][axis] != 1) return false;
+      if (b < 0) b += extent;
+      if (e < 0) e += extent;
+      if (o.begin_mask & (1 << axis)) b = 0;
+      if (o.end_mask & (1 << axis)) e = extent;
+      b = std::min(std::max<int64_t>(b, 0), extent);
+      e = std::min(std::max<int64_t>(e, 0), extent);
+    } else {
+      if (b < 0 || b > extent || e < -1) return false;
+      e = e == -1 ? extent : b + e;
+      if (e > extent) return false;
+    }
+    if (axis < 3 ? (b != 0 || e != extent) : e - b < 1) return false;
+    if (axis == 3) { *begin = (int32_t)b; *count = (int32_t)(e - b); }
+  }
+  return true;
+}
+
+// "A builtin STRIDED_SLICE / SLICE that a section may run" ("slice"): the channel window of MeliusNet's improvement block.  One
+// output; the data input a non-constant float32 or int8 4-D tensor with positive extents; the output of the same type and, for
+// int8, both tensors with ONE scale and zero point each, the same (a requantizing slice is the host's); for STRIDED_SLICE the
+// options table present, no ellipsis, new-axis or shrink mask and `offset` false; a window SliceWindow resolves; and the declared
+// output [b, H, W, count].  Everything else stays with the host: another axis, a stride, a run-time index tensor, another type.
+bool SliceCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinStridedSlice && o.builtin_code != lce_tfl::kBuiltinSlice) return false;
+  if (o.inputs.empty() || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (in.type != lce_tfl::kTensorFloat32 && in.type != lce_tfl::kTensorInt8) return false;
+  if (!StreamedImages(in, out) || in.type != out.type) return false;
+  if (in.type == lce_tfl::kTensorInt8) {
+    for (const lce_tfl::Tensor* t : {&in, &out})
+      if (!t->quantized || t->scales.size() != 1 || t->zero_points.size() > 1 || t->zero_point < -128 || t->zero_point > 127) return false;
+    if (in.scale != out.scale || in.zero_point != out.zero_point) return false;
+  }
+  if (o.builtin_code == lce_tfl::kBuiltinStridedSlice &&
+      (!o.has_slice_options || o.ellipsis_mask != 0 || o.new_axis_mask != 0 || o.shrink_axis_mask != 0 || o.slice_offset))
+    return false;
+  int32_t begin = 0, count = 0;
+  if (!SliceWindow(M, o, &begin, &count)) return false;
+  return out.shape[0] == in.shape[0] && out.shape[1] == in.shape[1] && out.shape[2] == in.shape[2] && out.shape[3] == count;
+}
+
 // THE names of lce_tflite_model_open_passes, each with the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it
 // that the name sets: the only place the three are written.  "stem" is a name that is no pass (Partition() reads its bit); "head",
 // "head_i8" and "quantize" enable several rows of kPasses each.
@@ -957,7 +1022,7 @@ constexpr PassName kPassNames[] = {
     {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize},
     {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
     {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate},
-    {"binary_dense", 2, kInternalBinaryDense}};
+    {"binary_dense", 2, kInternalBinaryDense},           {"slice", 2, kInternalSlice}};
 // The entry of kPassNames called `name`; null when there is none.
 constexpr const PassName* Named(const char* name) {
   for (const PassName& n : kPassNames) {
@@ -1522,6 +1587,10 @@ struct Walk {
   std::map<int32_t, void*> ptr;
   std::map<int32_t, Shape> shapes;
   std::vector<char> done;                // per operator: a launch further up has already produced its output
+  // A WINDOW TENSOR: the output of an absorbed slice (or of the ADD behind it) that is no buffer but channels [begin, begin + count)
+  // of tensor `src`, with tensor `addend` (-1: none) added, for the CONCATENATION that reads it (Slice, JoinWindows)
+  struct Window { int32_t src, begin, count, addend; };
+  std::map<int32_t, Window> windows;
 
   bool IsSectionOutput(int32_t t) const { return std::find(sec.outputs.begin(), sec.outputs.end(), t) != sec.outputs.end(); }
 
@@ -1838,6 +1907,8 @@ struct Walk {
     const int32_t out_t = op.outputs[0];
     const lce_tfl::Tensor& OT = M.tensors[out_t];
     const std::vector<int32_t>& fs = OT.shape;
+    for (int32_t t : op.inputs)
+      if (windows.count(t)) return JoinWindows(i);
     // the inferred shape and type of EVERY input must agree with the file's (a producer whose output is smaller than the file
     // declares must not be read past its buffer)
     int32_t channels[LCE_HIP_CONCAT_MAX_INPUTS];
@@ -1869,6 +1940,136 @@ struct Walk {
     if (lce_hip_status s = lce_hip_concat(type, in, channels, (int32_t)n, (size_t)batch * fs[1] * fs[2],
                                           type == LCE_HIP_I8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
     return Launched(kAbsorbedConcat, fold);
+  }
+
+  // An absorbed CONCATENATION with at least one window tensor among its inputs as ONE lce_hip_join_windows launch: a window tensor
+  // becomes its window (with its addend), a plain input the whole-tensor window.  Folds the first LceQuantize as Concat does.
+  lce_hip_status JoinWindows(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    const lce_tfl::Tensor& OT = M.tensors[out_t];
+    const std::vector<int32_t>& fs = OT.shape;
+    if (OT.type != lce_tfl::kTensorFloat32 && OT.type != lce_tfl::kTensorInt8)
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION of windows is neither float32 nor int8");
+    // the inferred shape and type of EVERY source and addend must agree with the file's before anything is read
+    Window win[LCE_HIP_JOIN_MAX_WINDOWS];
+    int32_t pitch[LCE_HIP_JOIN_MAX_WINDOWS];
+    const size_t n = op.inputs.size();
+    int64_t sum = 0;
+    for (size_t k = 0; k < n; ++k) {
+      const int32_t t = op.inputs[k];
+      auto w = windows.find(t);
+      win[k] = w != windows.end() ? w->second : Window{t, 0, M.tensors[t].shape[3], -1};
+      auto it = shapes.find(win[k].src);
+      if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION reads a tensor nothing produced");
+      const Shape& xs = it->second;
+      pitch[k] = M.tensors[win[k].src].shape[3];
+      if (!Agrees(xs, OT.type, fs[1], fs[2], pitch[k]) || win[k].begin < 0 || win[k].count < 1 || win[k].begin + (int64_t)win[k].count > pitch[k] ||
+          win[k].count != M.tensors[t].shape[3])
+        return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION input's shape or type does not match the one its producer infers");
+      if (win[k].addend >= 0) {
+        auto ad = shapes.find(win[k].addend);
+        if (ad == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an ADD behind a slice reads a tensor nothing produced");
+        if (!Agrees(ad->second, lce_tfl::kTensorFloat32, fs[1], fs[2], win[k].count) || OT.type != lce_tfl::kTensorFloat32)
+          return Fail(LCE_HIP_ERR_INVALID, "run_section: the addend of a window does not match the window's shape");
+      }
+      sum += win[k].count;
+    }
+    if (sum != fs[3]) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION's inputs do not add up to its output");
+    const Shape os = OutShape(fs[1], fs[2], fs[3], OT.type);
+    shapes[out_t] = os;
+    done[i] = 1;
+    const Fold fold = FoldQuantize(i, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    lce_hip_window w[LCE_HIP_JOIN_MAX_WINDOWS];
+    memset(w, 0, sizeof w);
+    for (size_t k = 0; k < n; ++k) {
+      if (lce_hip_status s = DevicePtr(win[k].src, "a CONCATENATION input", &w[k].data_dev)) return s;
+      w[k].pitch = pitch[k]; w[k].begin = win[k].begin; w[k].count = win[k].count;
+      if (win[k].addend >= 0) {
+        const void* a = nullptr;
+        if (lce_hip_status s = DevicePtr(win[k].addend, "the addend of a window", &a)) return s;
+        w[k].addend_dev = (const float*)a;
+      }
+    }
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    const bool i8 = OT.type == lce_tfl::kTensorInt8;
+    if (lce_hip_status s = lce_hip_join_windows(i8 ? LCE_HIP_I8 : LCE_HIP_F32, w, (int32_t)n, (size_t)batch * fs[1] * fs[2],
+                                                i8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
+    ++model->last.slice_joins;
+    return Launched(kAbsorbedSlice, fold);
+  }
+
+  // The reader of window-tensor candidate `t` (an absorbed slice's output, or the output of the ADD behind one) when `t` is not
+  // delivered and has exactly one reader, an operator of this section after `after`; -1 otherwise.
+  int32_t OnlyReader(int32_t t, int32_t after) const {
+    const std::vector<int32_t>& rd = model->readers[t];
+    if (IsSectionOutput(t) || rd.size() != 1 || rd[0] <= after || !std::binary_search(sec.ops.begin(), sec.ops.end(), rd[0])) return -1;
+    return rd[0];
+  }
+  // Operator `j` is an absorbed CONCATENATION of float32 or int8 tensors that has not run.
+  bool JoinsWindows(int32_t j) const {
+    const int type = model->m.tensors[model->m.operators[j].outputs[0]].type;
+    return model->absorbed[j] == kAbsorbedConcat && !done[j] && (type == lce_tfl::kTensorFloat32 || type == lce_tfl::kTensorInt8);
+  }
+
+  // An absorbed STRIDED_SLICE / SLICE on the channel axis ("slice" of lce_tflite_model_open_passes).  Decided from the graph
+  // alone: when its output is a WINDOW TENSOR -- not delivered, exactly one reader, later in the section, which is (a) an absorbed
+  // CONCATENATION of float32 / int8 tensors or (b) an "elementwise" float ADD with no fused activation, whose other input is a
+  // non-constant tensor of the window's shape that is neither produced by an operator of the elementwise chain's kinds in this
+  // section nor itself a window tensor, and whose output is not delivered and has exactly one reader, a CONCATENATION as in (a) --
+  // the slice launches nothing and gets no buffer (in case (b) neither does the ADD, whose output is the window with an addend):
+  // the CONCATENATION runs them as one lce_hip_join_windows launch.  Any other slice is ONE such launch with one window, into which
+  // the first LceQuantize that reads it folds.
+  lce_hip_status Slice(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t in_t = op.inputs[0], out_t = op.outputs[0];
+    const lce_tfl::Tensor& IT = M.tensors[in_t];
+    auto it = shapes.find(in_t);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a slice reads a tensor nothing produced");
+    int32_t begin = 0, count = 0;
+    if (!Agrees(it->second, IT.type, IT.shape[1], IT.shape[2], IT.shape[3]) || !SliceWindow(M, op, &begin, &count))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a slice input's shape or type does not match the one its producer infers");
+    const Shape os = OutShape(IT.shape[1], IT.shape[2], count, IT.type);
+    shapes[out_t] = os;
+    done[i] = 1;
+    const int32_t reader = OnlyReader(out_t, i);
+    if (reader >= 0 && JoinsWindows(reader)) {
+      windows[out_t] = Window{in_t, begin, count, -1};
+      return LCE_HIP_OK;
+    }
+    if (reader >= 0 && model->absorbed[reader] == kAbsorbedElementwise && !done[reader]) {
+      const lce_tfl::Operator& add = M.operators[reader];
+      const int32_t other = add.inputs[0] == out_t ? add.inputs[1] : add.inputs[0];
+      const int32_t sum_t = add.outputs[0];
+      const lce_tfl::Tensor& OT = M.tensors[other];
+      const int32_t made_by = model->producer[other];
+      const bool chained = made_by >= 0 && ChainKind(model->absorbed[made_by]) && std::binary_search(sec.ops.begin(), sec.ops.end(), made_by);
+      const int32_t join = OnlyReader(sum_t, reader);
+      if (add.builtin_code == lce_tfl::kBuiltinAdd && add.activation == LCE_HIP_ACT_NONE && IT.type == lce_tfl::kTensorFloat32 &&
+          other != out_t && !OT.data && OT.type == lce_tfl::kTensorFloat32 && OT.shape == M.tensors[out_t].shape && !chained &&
+          !windows.count(other) && join >= 0 && JoinsWindows(join)) {
+        done[reader] = 1;
+        shapes[sum_t] = os;
+        windows[sum_t] = Window{in_t, begin, count, other};
+        return LCE_HIP_OK;
+      }
+    }
+    const Fold fold = FoldQuantize(i, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    lce_hip_window w;
+    memset(&w, 0, sizeof w);
+    if (lce_hip_status s = DevicePtr(in_t, "a slice input", &w.data_dev)) return s;
+    w.pitch = IT.shape[3]; w.begin = begin; w.count = count;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    const bool i8 = IT.type == lce_tfl::kTensorInt8;
+    if (lce_hip_status s = lce_hip_join_windows(i8 ? LCE_HIP_I8 : LCE_HIP_F32, &w, 1, (size_t)batch * IT.shape[1] * IT.shape[2],
+                                                i8 ? (int32_t)IT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
+    return Launched(kAbsorbedSlice, fold);
   }
 
   // An absorbed operator `i` that streams ONE input of `in_type` and makes ONE output of shape and type `os`, as ONE launch of its
@@ -2337,6 +2538,8 @@ constexpr FusedPass kPasses[kAbsorbedCount - 1] = {
     {kAbsorbedActivation, Named("activation"), ActivationCandidate, &Walk::ElementwiseChain, nullptr, false, kRank2},
     {kAbsorbedReshape, Named("reshape"), ReshapeCandidate, &Walk::Reshape, nullptr, false, kRank2},
     {kAbsorbedGate, Named("gate"), GateCandidate, &Walk::ElementwiseChain, nullptr, false, false},
+    // the channel window of MeliusNet's improvement block: no row above takes a STRIDED_SLICE / SLICE
+    {kAbsorbedSlice, Named("slice"), SliceCandidate, &Walk::Slice, nullptr, false, false},
 };
 // (row k is kind k + 1, and every row names an entry of kPassNames)
 constexpr bool RowsInOrder() {
@@ -2507,6 +2710,11 @@ void lce_tflite_model_quantize_stats(lce_tflite_model* model, int32_t* quantize,
 void lce_tflite_model_activation_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
   Stats(model, [&](const RunStats& r) {
     Put(launches, r.pass[kAbsorbedActivation].launches); Put(ops_folded, r.ex_ops); Put(quantize_folded, r.pass[kAbsorbedActivation].quantize);
+  });
+}
+void lce_tflite_model_slice_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded, int32_t* joins) {
+  Stats(model, [&](const RunStats& r) {
+    Put(launches, r.pass[kAbsorbedSlice].launches); Put(quantize_folded, r.pass[kAbsorbedSlice].quantize); Put(joins, r.slice_joins);
   });
 }
 void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies) {

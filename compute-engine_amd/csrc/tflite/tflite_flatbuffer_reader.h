@@ -37,6 +37,9 @@
 //   BuiltinOperator 14 LOGISTIC, 19 RELU, 20 RELU_N1_TO_1, 21 RELU6, 54 PRELU (inputs: data, alpha): no options table.
 //   BuiltinOperator 22 RESHAPE (inputs: data and, optionally, the new shape as an int32 tensor): its ReshapeOptions.new_shape
 //   repeats the declared shape of the output tensor, which is what this library goes by; the table is not read.
+//   BuiltinOptions union type 32 StridedSliceOptions: 0 begin_mask  1 end_mask  2 ellipsis_mask  3 new_axis_mask
+//   4 shrink_axis_mask (all int32, default 0)  5 offset(bool, default false); BuiltinOperator 45 STRIDED_SLICE (inputs: data,
+//   begin, end, strides), 65 SLICE (inputs: data, begin, size; no option this reader needs).
 //   (Restated from the published schema.fbs: no schema file exists in the build image either.)
 // No .tflite file and no flatbuffers library exist in the build image: the only byte-level
 // known answers are the reference's flexbuffer option blobs (mlir/tests/legalize-lce.mlir:9,21),
@@ -59,6 +62,8 @@ constexpr int32_t kBuiltinDequantize = 6, kBuiltinQuantize = 114;   // (their op
 constexpr int32_t kBuiltinLogistic = 14, kBuiltinRelu = 19, kBuiltinReluN1To1 = 20, kBuiltinRelu6 = 21, kBuiltinReshape = 22, kBuiltinPrelu = 54;
 constexpr int kOptionsConv2d = 1, kOptionsDepthwiseConv2d = 2, kOptionsPool2d = 5, kOptionsConcatenation = 10, kOptionsAdd = 11, kOptionsMul = 21;   // BuiltinOptions union types
 constexpr int kOptionsFullyConnected = 8, kOptionsSoftmax = 9, kOptionsReducer = 27;
+constexpr int32_t kBuiltinStridedSlice = 45, kBuiltinSlice = 65;
+constexpr int kOptionsStridedSlice = 32;
 // TensorType values used by LCE graphs
 constexpr int kTensorFloat32 = 0, kTensorInt32 = 2, kTensorBool = 6, kTensorInt8 = 9;
 
@@ -99,6 +104,9 @@ struct Operator {
   int32_t fc_weights_format = 0;
   bool has_softmax_options = false;
   float softmax_beta = 0.0f;
+  // StridedSliceOptions (all 0 / false when absent)
+  bool has_slice_options = false, slice_offset = false;
+  int32_t begin_mask = 0, end_mask = 0, ellipsis_mask = 0, new_axis_mask = 0, shrink_axis_mask = 0;
 };
 
 class Model {
@@ -337,6 +345,15 @@ class Model {
       if (opt_type == kOptionsSoftmax && opt_pos != 0) {
         if (!Indirect(opt_pos, &opt) || !Scalar<float>(opt, 0, 0.0f, &O.softmax_beta)) return Fail("bad SoftmaxOptions");
         O.has_softmax_options = true;
+      }
+      if (opt_type == kOptionsStridedSlice && opt_pos != 0) {
+        uint8_t offset;
+        if (!Indirect(opt_pos, &opt) || !Scalar<int32_t>(opt, 0, 0, &O.begin_mask) || !Scalar<int32_t>(opt, 1, 0, &O.end_mask) ||
+            !Scalar<int32_t>(opt, 2, 0, &O.ellipsis_mask) || !Scalar<int32_t>(opt, 3, 0, &O.new_axis_mask) ||
+            !Scalar<int32_t>(opt, 4, 0, &O.shrink_axis_mask) || !Scalar<uint8_t>(opt, 5, 0, &offset))
+          return Fail("bad StridedSliceOptions");
+        O.slice_offset = offset != 0;
+        O.has_slice_options = true;
       }
       for (int32_t x : O.inputs) if (x < -1 || x >= (int32_t)nt) return Fail("Operator input index out of range");
       for (int32_t x : O.outputs) if (x < 0 || x >= (int32_t)nt) return Fail("Operator output index out of range");

@@ -268,6 +268,46 @@ lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev,
                               int32_t* out_bits_dev /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Join of channel windows (TFLite builtin STRIDED_SLICE / SLICE on the channel axis, MeliusNet's improvement block)
+ * ---------------------------------------------------------------------------------- */
+
+/* MeliusNet's improvement block adds a binary layer's 64 channels to the LAST 64 channels of its input:
+ *   f = x[..., :C-64];  b = x[..., C-64:] + w;  y = CONCATENATION(f, b)
+ * lce_hip_join_windows is lce_hip_concat with a source generalised to a channel WINDOW [begin, begin + count) of a wider
+ * NHWC tensor [rows, pitch], and an optional dense float tensor [rows, count] added to a window on the way through, so the
+ * block is ONE launch that reads x and w once and writes y once; a channel slice alone is the one-window call.  `type` is
+ * F32 or I8.  For window k, which begins at start_k = sum of the counts before it:
+ *   without an addend  out[r][start_k + c] = src_k[r][begin_k + c] -- a copy: NaN payloads, -0.0 and subnormals come
+ *                      through untouched;
+ *   with an addend     out[r][start_k + c] = fl(src_k[r][begin_k + c] + addend_k[r][c]) -- ONE float32 add, round to nearest
+ *                      even, subnormals not flushed; a NaN result is a NaN whose payload is unspecified.
+ * `out_dev` (nullable) is [rows, sum count]; `out_bits_dev` (nullable) gets the LceQuantize of that tensor exactly as
+ * lce_hip_concat writes it (bit = v < 0 for F32, v < zero_point for I8, ceil(sum count / 32) words per row, padding bits
+ * 0), from the values the pass holds.  The same source may appear in several windows and windows of one source may
+ * overlap.  `windows` is a host array read at the call.
+ * Refused (LCE_HIP_ERR_INVALID, before any device pointer is dereferenced or a device touched): a type other than F32 / I8
+ * (no converted network slices a bit tensor), num_windows outside 1..8, NULL windows or a NULL data_dev, a window outside
+ * its pitch (begin < 0, count < 1, begin + count > pitch), a sum of counts of 2^31 or more, an addend with I8, an addend
+ * that is not 4-byte aligned, a zero point outside [-128, 127] for I8 or non-zero for F32, non-zero reserved fields, both
+ * outputs NULL, an output range that overlaps a source's whole [rows, pitch] range, an addend or the other output.  Zero rows
+ * is a no-op, checked first (an empty tensor may come with null pointers).  rows must be below 2^32; byte counts are
+ * unbounded (64-bit offsets).  lce_hip_join_windows_check is the host-only part: the checks that need neither rows nor the
+ * outputs.  Asynchronous on `stream`, capturable in a HIP graph, allocates nothing and copies nothing between host and
+ * device (the window table travels in the kernel arguments). */
+typedef struct lce_hip_window {
+  const void* data_dev;     /* the source tensor [rows, pitch] */
+  int32_t pitch;            /* channels per source row */
+  int32_t begin, count;     /* the window [begin, begin + count) of every row: begin >= 0, count >= 1, begin + count <= pitch */
+  const float* addend_dev;  /* nullable, F32 only: a dense [rows, count] tensor added to the window */
+  int32_t reserved[2];      /* 0 */
+} lce_hip_window;
+#define LCE_HIP_JOIN_MAX_WINDOWS 8
+lce_hip_status lce_hip_join_windows(lce_hip_dtype type, const lce_hip_window* windows, int32_t num_windows /* 1..8 */,
+                                    size_t rows, int32_t zero_point, void* out_dev /* nullable */,
+                                    int32_t* out_bits_dev /* nullable */, void* stream);
+lce_hip_status lce_hip_join_windows_check(lce_hip_dtype type, const lce_hip_window* windows, int32_t num_windows);  /* host only */
+
+/* ------------------------------------------------------------------------------------
  * 2-D pooling between binary layers (TFLite builtin MAX_POOL_2D / AVERAGE_POOL_2D) and the LceQuantize that follows
  * ---------------------------------------------------------------------------------- */
 

@@ -163,7 +163,8 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
                                              size_t err_len);
 
 /* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
- *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize, depthwise_i8, activation, reshape, gate
+ *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize, depthwise_i8, activation, reshape, gate,
+ *   binary_dense, slice
  * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
  * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
  * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
@@ -265,7 +266,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   trailing axes, so it is not per image.
  *   None of the three moves anything unless it is named.  Still the host's: TANH, HARD_SWISH, LEAKY_RELU, int8 activations, a full
  *   [H,W,C] PRELU alpha, rank-2 ADD / MUL (the dense batch norm of BinaryAlexNet), a RESHAPE that moves the batch extent or whose
- *   shape is computed at run time, STRIDED_SLICE, PAD.
+ *   shape is computed at run time, PAD.
  *   binary_dense: a binarized Dense layer (larq's QuantDense behind a sign: BinaryAlexNet's and XNOR-Net's classifier layers, a
  *   binarized MLP) joins the sections and runs on the FP4 matrix cores.  The converter has no binary fully-connected operator: it
  *   leaves LceQuantize -> LceDequantize -> a float FULLY_CONNECTED (9) whose row o holds only +-s[o].  Such an operator qualifies
@@ -279,7 +280,32 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   writes only bits.  An LceDequantize that only binary Dense operators of its own section read, and that the section does not
  *   deliver, is not launched and gets no buffer (its shape is still registered).  LceQuantize and LceDequantize take rank-2
  *   tensors for this, carried as [b, 1, 1, C] like every rank-2 tensor of the walk (a rank-2 SECTION INPUT needs this name or
- *   another that carries rank-2 tensors).  No partition and no launch changes unless it is named. */
+ *   another that carries rank-2 tensors).  No partition and no launch changes unless it is named.
+ *   slice: a builtin STRIDED_SLICE (45) or SLICE (65) that cuts a CHANNEL window out of an image joins the sections -- MeliusNet's
+ *   improvement block is w = LceBconv2d(..x..); f = x[..., :C-64]; b = x[..., C-64:] + w; y = CONCATENATION(f, b).  No other entry
+ *   can ask for it, and no bit and no struct size enables it.  It qualifies when: it has one output; the data input (0) is a
+ *   non-constant float32 or int8 4-D tensor with positive extents; the output has the same type and, for int8, both tensors carry
+ *   ONE scale and zero point each, the same; for STRIDED_SLICE the StridedSliceOptions table is present, ellipsis_mask,
+ *   new_axis_mask and shrink_axis_mask are 0 and offset is false, begin, end and strides are constant int32 [4] tensors with data
+ *   in the file and every stride is 1; for SLICE begin and size are such tensors.  The ranges are resolved as TFLite resolves a
+ *   stride of 1: a masked begin is 0 and a masked end the extent, a negative index gets the extent added, begin and end are then
+ *   clamped to [0, extent]; a SLICE size of -1 means "to the end" (a negative SLICE begin or a range past the extent is refused).
+ *   Axes 0..2 must come out as their whole extent, axis 3 as a window of count >= 1 channels, and the declared output must be
+ *   [b, H, W, count].  Everything else stays with the host: another axis, a stride, a shrink mask, a run-time index tensor, another
+ *   type.  It joins the epoch in which it becomes ready, and `stem` applies to it as to any opt-in.
+ *   lce_tflite_model_run_section decides from the graph alone, when the walk reaches the slice, whether its output is a WINDOW
+ *   TENSOR: one the section does not deliver and that has exactly one reader, later in the section, which is (a) an absorbed
+ *   CONCATENATION (`concat`) of float32 or int8 tensors, or (b) an `elementwise`-absorbed float ADD with fused activation NONE, whose
+ *   other input is a non-constant tensor of the window's shape that is neither produced by an operator of the elementwise chain's
+ *   kinds (`elementwise`, `activation`, `gate`) in this section nor itself a window tensor, and whose output is not delivered and
+ *   has exactly one reader, a CONCATENATION as in (a).  Such a slice launches nothing and gets no buffer (its shape is still
+ *   registered); in case (b) neither does the ADD, whose output is the window with an addend.  An absorbed CONCATENATION with at
+ *   least one window tensor among its inputs runs as ONE lce_hip_join_windows launch (its plain inputs are whole-tensor windows;
+ *   the first LceQuantize that reads it folds, as for every join): with `elementwise,concat,slice` the improvement block is one
+ *   pass that reads x and w once and writes y once, and a MeliusNet body is ONE section.  Any other absorbed slice is ONE
+ *   lce_hip_join_windows launch with one window, into which a following LceQuantize folds by the fold rule.  A CONCATENATION
+ *   without a window tensor still runs on lce_hip_concat, byte for byte as before.  Nothing moves unless it is named.  Still the
+ *   host's: SPLIT / SPLIT_V, slices of other axes or with strides, slices of bit tensors. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -449,6 +475,10 @@ void lce_tflite_model_gate_stats(lce_tflite_model* model, int32_t* launches, int
 /* The LAST run's absorbed RESHAPE operators ("reshape"): those that were a view of their input's buffer, and those that cost one
  * device-to-device copy. */
 void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies);
+/* The LAST run's lce_hip_join_windows launches ("slice" of lce_tflite_model_open_passes): launches (standalone slices and
+ * CONCATENATIONs with a window tensor among their inputs), the LceQuantize launches folded into them, and those of the launches
+ * that took over a CONCATENATION (lce_tflite_model_concat_stats counts lce_hip_concat launches only).  Nullable outputs. */
+void lce_tflite_model_slice_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded, int32_t* joins);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
