@@ -19,7 +19,6 @@
 #include "lce_kernel_types.h"    // the convolution kernels live in their own translation units (lce_tu_*.hip)
 #include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip, lce_tu_eltwise_ex.hip)
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
-#include "lce_kernels_concat.h"      // (lce_tu_concat.hip)
 #include "lce_kernels_join.h"        // (lce_tu_join.hip)
 #include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
 #include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
@@ -49,7 +48,6 @@
 #include "lce_tu_eltwise.hip"
 #include "lce_tu_eltwise_ex.hip"
 #include "lce_tu_eltwise_i8.hip"
-#include "lce_tu_concat.hip"
 #include "lce_tu_join.hip"
 #include "lce_tu_pool.hip"
 #include "lce_tu_conv1x1.hip"
@@ -933,8 +931,23 @@ lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_
 }
 
 // ------------------------------------------------------------------------------------
-// Channel join (lce_kernels_concat.h)
+// Channel join: whole tensors (lce_hip_concat) and channel windows (lce_hip_join_windows), one kernel family (lce_kernels_join.h)
 // ------------------------------------------------------------------------------------
+static_assert(LCE_HIP_JOIN_MAX_WINDOWS == lce::kJoinMaxWindows, "the header's bound is the kernels'");
+static_assert(LCE_HIP_CONCAT_MAX_INPUTS <= lce::kJoinMaxWindows, "a dense join is a join of whole-tensor windows");
+
+// What both entries end with, once `who` has checked its arguments: path, grid stride, launch.
+static lce_hip_status join_run(const char* who, int kind, const lce::JoinWindow* jw, int n, uint64_t rows, int32_t zero_point,
+                               void* out_dev, int32_t* out_bits_dev, void* stream) {
+  if (lce_hip_status s = require_device()) return s;
+  lce::JoinArgs a;
+  const bool vec = lce::join_fill(a, kind, jw, n, rows, zero_point, out_dev, (uint32_t*)out_bits_dev);
+  if (vec) lce::join_set_stride(a, lce::join_vec_grid(a.total_chunks));
+  const int e = lce::launch_join(a, kind, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
 lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev, const int32_t* channels, int32_t num_inputs,
                               size_t rows, int32_t zero_point, void* out_dev, int32_t* out_bits_dev, void* stream) {
   if (type != LCE_HIP_F32 && type != LCE_HIP_I8 && type != LCE_HIP_BITPACKED)
@@ -960,50 +973,20 @@ lce_hip_status lce_hip_concat(lce_hip_dtype type, const void* const* inputs_dev,
   const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (out_dev ? rows * sum * esz : 0);
   const uintptr_t b0 = (uintptr_t)out_bits_dev, b1 = b0 + (out_bits_dev ? rows * wpr * 4 : 0);
   if (meet(o0, o1, b0, b1)) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: the two outputs overlap");
-  bool vec = (o0 % 16 == 0) && (b0 % 4 == 0);
+  lce::JoinWindow jw[lce::kJoinMaxWindows];
   for (int32_t k = 0; k < num_inputs; ++k) {
     if (!inputs_dev[k]) return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: input %d is null", (int)k);
     const uintptr_t i0 = (uintptr_t)inputs_dev[k], i1 = i0 + rows * (uint64_t)channels[k] * esz;
     if (meet(o0, o1, i0, i1) || meet(b0, b1, i0, i1))
       return fail(LCE_HIP_ERR_INVALID, "lce_hip_concat: an output overlaps input %d", (int)k);
-    vec = vec && i0 % 16 == 0 && ((uint64_t)channels[k] * esz) % 16 == 0;
+    jw[k] = lce::JoinWindow{inputs_dev[k], nullptr, (uint32_t)channels[k], 0u, (uint32_t)channels[k]};   // the whole tensor
   }
-  if (out_bits_dev && sum % 32 != 0) vec = false;   // (a word of bits then straddles rows of chunks)
-  if (lce_hip_status s = require_device()) return s;
-  lce::ConcatArgs a;
-  memset(&a, 0, sizeof a);
-  const uint64_t unit = vec ? 16 / esz : 1;          // elements per width unit
-  uint32_t at = 0;
-  for (int32_t k = 0; k < lce::kConcatMaxInputs; ++k) {
-    if (k >= num_inputs) { a.start[k] = 0xffffffffu; continue; }
-    a.in[k] = inputs_dev[k];
-    a.width[k] = (uint32_t)((uint64_t)channels[k] / unit);
-    a.start[k] = at;
-    at += a.width[k];
-  }
-  a.out = out_dev;
-  a.bits = (uint32_t*)out_bits_dev;
-  a.rows = rows;
-  a.total = at;
-  a.wpr = (uint32_t)wpr;
-  a.zero_point = zero_point;
-  if (vec) {
-    a.total_chunks = (uint64_t)rows * at;
-    const uint64_t stride = (uint64_t)lce::concat_vec_grid(a.total_chunks) * 4ull * 256ull;   // chunks per grid step
-    a.step_rows = stride / at;
-    a.step_cols = (uint32_t)(stride % at);
-    a.div_total = lce::make_fastdiv(at);
-  }
-  const int kind = type == LCE_HIP_F32 ? lce::kConcatF32 : type == LCE_HIP_I8 ? lce::kConcatI8 : lce::kConcatWords;
-  const int e = lce::launch_concat(a, kind, vec, stream);
-  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_concat: launch failed: %s", hipGetErrorString((hipError_t)e));
-  return LCE_HIP_OK;
+  // (bitpacked words are 4-byte elements that nothing interprets: there is no bit output)
+  return join_run("lce_hip_concat", type == LCE_HIP_I8 ? lce::kJoinI8 : lce::kJoinF32, jw, (int)num_inputs, rows, zero_point, out_dev,
+                  out_bits_dev, stream);
 }
 
-// ------------------------------------------------------------------------------------
-// Join of channel windows (lce_kernels_join.h)
-// ------------------------------------------------------------------------------------
-static_assert(LCE_HIP_JOIN_MAX_WINDOWS == lce::kJoinMaxWindows, "the header's bound is the kernels'");
+// ---- channel windows ----
 lce_hip_status lce_hip_join_windows_check(lce_hip_dtype type, const lce_hip_window* windows, int32_t num_windows) {
   const char* who = "lce_hip_join_windows";
   if (type != LCE_HIP_F32 && type != LCE_HIP_I8) return fail(LCE_HIP_ERR_INVALID, "%s: type must be float32 or int8, got %d", who, (int)type);
@@ -1053,14 +1036,7 @@ lce_hip_status lce_hip_join_windows(lce_hip_dtype type, const lce_hip_window* wi
     }
     jw[k] = lce::JoinWindow{w.data_dev, w.addend_dev, (uint32_t)w.pitch, (uint32_t)w.begin, (uint32_t)w.count};
   }
-  if (lce_hip_status s = require_device()) return s;
-  const int kind = type == LCE_HIP_F32 ? lce::kJoinF32 : lce::kJoinI8;
-  lce::JoinArgs a;
-  const bool vec = lce::join_fill(a, kind, jw, (int)num_windows, rows, zero_point, out_dev, (uint32_t*)out_bits_dev);
-  if (vec) lce::join_set_stride(a, lce::join_vec_grid(a.total_chunks));
-  const int e = lce::launch_join(a, kind, vec, stream);
-  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
-  return LCE_HIP_OK;
+  return join_run(who, type == LCE_HIP_F32 ? lce::kJoinF32 : lce::kJoinI8, jw, (int)num_windows, rows, zero_point, out_dev, out_bits_dev, stream);
 }
 
 // ------------------------------------------------------------------------------------

@@ -1,22 +1,31 @@
-// The join of channel WINDOWS (include/lce_hip.h, lce_hip_join_windows): lce_hip_concat generalised so that a source is a
-// channel range [begin, begin + count) of a wider tensor [rows, pitch], and a float window may have a dense [rows, count]
-// tensor added on the way through.  MeliusNet's improvement block -- y = CONCATENATION(x[..., :C-64], x[..., C-64:] + w) -- is
-// one launch of it; a standalone channel slice (TFLite's STRIDED_SLICE / SLICE on the last axis) is the one-window case.
+// The channel join (include/lce_hip.h: lce_hip_concat, lce_hip_join_windows).  A source is a channel WINDOW [begin, begin + count)
+// of a tensor [rows, pitch]; a float window may have a dense [rows, count] tensor added on the way through.  The join between the
+// binary layers of a converted DENSE network (BinaryDenseNet, MeliusNet: TFLite's builtin CONCATENATION on the channel axis) is the
+// case begin = 0, count = pitch without addends; MeliusNet's improvement block -- y = CONCATENATION(x[..., :C-64], x[..., C-64:] + w)
+// -- is one launch; a standalone channel slice (TFLite's STRIDED_SLICE / SLICE on the last axis) is the one-window case.  Either
+// way the LceQuantize of the joined tensor comes out of the same pass.
 //
 //   out[r][start_k + c] = src_k[r][begin_k + c]                      (a copy: NaN payloads, -0.0 and subnormals come through untouched)
 //   out[r][start_k + c] = fl(src_k[r][begin_k + c] + addend_k[r][c]) (one float32 add, round to nearest even, subnormals kept)
-//   bits: exactly lce_hip_concat's, from the values the pass holds (after the add)
+//   bits: bit = out < 0 (float) / out < zero_point (int8), LSB first, ceil(sum count / 32) words per row, padding bits 0
+//         (what lce_hip_bitpack writes for the joined tensor), from the values the pass holds in registers (after the add)
 //
-// Two paths, chosen as lce_hip_concat chooses, and of the shape of its two kernels (lce_kernels_concat.h):
+// Two paths, chosen as lce_hip_bitpack / lce_hip_elementwise choose:
 //   join_vec  : every begin, count and pitch x element size is a multiple of 16 bytes, every pointer 16-byte aligned (and, with
-//               bits, sum count a multiple of 32) -- the output is one flat array of 16-byte chunks, lane l of a wave moves
-//               chunks base + l + 64 j, j = 0..3.  The (row, chunk in row) of a wave's base is divided out once and advanced by
-//               the grid stride, whose quotient and remainder the host supplies.  All loads of an iteration (sources and addends)
-//               are issued before the first add.
-//   join_rows : anything else -- one wave per 64 columns of an output row, one element per lane, one ballot per two words.
+//               bits, sum count a multiple of 32) -- the OUTPUT is one flat array of 16-byte chunks; lane l of a wave moves
+//               chunks base + l + 64 j, j = 0..3: four loads in flight per lane and 1024 contiguous bytes per store instruction.
+//               The (row, chunk in row) of a wave's base is divided out ONCE per wave and then advanced by the grid stride,
+//               whose quotient and remainder the host supplies; a lane's own offset (< 256 chunks) takes one 32-bit
+//               multiply-high.  The window a chunk comes from is found by comparing against <= 7 chunk offsets that travel in
+//               the kernel arguments.  All loads of an iteration (sources and addends) are issued before the first add.
+//               Float: a chunk is 4 sign bits, 8 neighbouring lanes make a word (3 xor-shuffles).  int8: a chunk is 16 bits
+//               from four byte-parallel compares, 2 neighbouring lanes make a word (one DPP quad permute).
+//   join_rows : anything else (ragged channel counts, unaligned pointers) -- one wave per 64 columns of an output row, one
+//               element per lane, one ballot per two words.
 // A launch without any addend runs an instance that holds no addend code.  All offsets are 64-bit (rows < 2^32, sum count and
-// every pitch < 2^31).  No LDS, no scratch, nothing allocated, the window table travels in the kernel arguments: the launch is
-// capturable.  Sources may repeat and windows of one source may overlap; the outputs must not overlap a source or an addend.
+// every pitch < 2^31, their product unbounded).  No LDS, no scratch, nothing allocated, the window table travels in the kernel
+// arguments: the launch is capturable.  Sources may repeat and windows of one source may overlap; the outputs must not overlap a
+// source or an addend (the row pitches differ, so there is no in-place join).
 #pragma once
 #include <stdint.h>
 
@@ -25,13 +34,14 @@
 namespace lce {
 
 constexpr int kJoinMaxWindows = 8;
+// Element kinds.  kJoinF32: 4-byte elements; the sign test only where bits are asked for (so bitpacked int32 words, which
+// have no bit output, are joined as kJoinF32).  kJoinI8: int8.
 enum { kJoinF32 = 0, kJoinI8 = 1 };
 
 struct JoinArgs {
-  const void* src[kJoinMaxWindows];
+  const void* src[kJoinMaxWindows];       // the window's first element in row 0 (the source tensor's base + begin)
   const float* addend[kJoinMaxWindows];   // null: the window is a copy
   uint32_t pitch[kJoinMaxWindows];        // per source row: 16-byte chunks (vector path) or elements (row path)
-  uint32_t begin[kJoinMaxWindows];        // where the window begins in a source row (same unit)
   uint32_t count[kJoinMaxWindows];        // the window's width = the addend's row pitch (same unit)
   uint32_t start[kJoinMaxWindows];        // where window k begins in an output row (same unit); 0xffffffff for k >= num_windows
   void* out;                              // null: no joined tensor
@@ -70,10 +80,9 @@ inline bool join_fill(JoinArgs& a, int kind, const JoinWindow* w, int n, uint64_
   uint32_t at = 0;
   for (int k = 0; k < kJoinMaxWindows; ++k) {
     if (k >= n) { a.start[k] = 0xffffffffu; continue; }
-    a.src[k] = w[k].src;
+    a.src[k] = (const char*)w[k].src + (uint64_t)w[k].begin * esz;
     a.addend[k] = w[k].addend;
     a.pitch[k] = w[k].pitch / unit;
-    a.begin[k] = w[k].begin / unit;
     a.count[k] = w[k].count / unit;
     a.start[k] = at;
     at += a.count[k];
@@ -118,13 +127,15 @@ using namespace lce_dev;
 
 LCE_DEVICE uint32_t join_div(uint32_t n, FastDiv d) { return d.magic == 0u ? n : (mulhi_u32(n, d.magic) >> d.shift); }
 
-// Four int8 values in one dword -> 4 bits, bit k = byte k < zero_point (lce_kernels_concat.h, concat_lt4, derives it).
+// Four int8 values in one dword -> 4 bits, bit k = byte k < zero_point.  `t4` holds zero_point + 128 in every byte: with
+// u = x ^ 0x80 per byte the comparison is unsigned, u < t, and per byte u < t <=> (~u & t) | (~(u ^ t) & ~d) at bit 7, where
+// d = (u | 0x80) - (t & 0x7f) never borrows from the next byte.  The four bits 7, 15, 23, 31 are gathered by one multiply.
 LCE_DEVICE uint32_t join_lt4(uint32_t x, uint32_t t4) {
   const uint32_t H = 0x80808080u;
   const uint32_t u = x ^ H;
   const uint32_t d = (u | H) - (t4 & ~H);
   const uint32_t lt = ((~u & t4) | (~(u ^ t4) & ~d)) & H;
-  return ((lt >> 7) * 0x01020408u) >> 24;
+  return ((lt >> 7) * 0x01020408u) >> 24;                         // bits 0, 8, 16, 24 -> 24, 25, 26, 27
 }
 
 // v_mov_b32 quad_perm:[1,0,3,2]: the value of the neighbouring lane (lane ^ 1).  Every lane of the wave must be active.
@@ -137,12 +148,11 @@ join_vec(const JoinArgs A) {
   const int lane = thread_idx_x() & (kWave - 1);
   const uint64_t wave0 = (uint64_t)block_idx_x() * (uint64_t)(block_dim_x() >> 6) + (uint64_t)(thread_idx_x() >> 6);
   const uint64_t nwaves = (uint64_t)grid_dim_x() * (uint64_t)(block_dim_x() >> 6);
-  const uint64_t nblocks = (A.total_chunks + 255) / 256;
   // (row, chunk in the row) of this wave's first chunk: one division per launch, then advanced by the grid stride
   uint64_t row0 = (wave0 * 256ull) / A.total;
   uint32_t col0 = (uint32_t)(wave0 * 256ull - row0 * A.total);
   const uint32_t t4 = (uint32_t)(A.zero_point + 128) * 0x01010101u;
-  for (uint64_t blk = wave0; blk < nblocks; blk += nwaves) {       // 256 chunks = 4 KB per wave and iteration
+  for (uint64_t blk = wave0; blk * 256ull < A.total_chunks; blk += nwaves) {   // 256 chunks = 4 KB per wave and iteration
     const uint64_t g0 = blk * 256ull + (uint64_t)lane;             // this lane's chunks: g0 + 64 j
     bool ok[4], has[4];
     u32x4 v[4];
@@ -155,12 +165,12 @@ join_vec(const JoinArgs A) {
       const uint32_t c = x - q * A.total;
       const u32x4* src = (const u32x4*)A.src[0];
       const f32x4* add = (const f32x4*)A.addend[0];
-      uint32_t p = A.pitch[0], b = A.begin[0], w = A.count[0], s = 0;
+      uint32_t p = A.pitch[0], w = A.count[0], s = 0;
 #pragma unroll
       for (int k = 1; k < kJoinMaxWindows; ++k)
-        if (c >= A.start[k]) { src = (const u32x4*)A.src[k]; add = (const f32x4*)A.addend[k]; p = A.pitch[k]; b = A.begin[k]; w = A.count[k]; s = A.start[k]; }
+        if (c >= A.start[k]) { src = (const u32x4*)A.src[k]; add = (const f32x4*)A.addend[k]; p = A.pitch[k]; w = A.count[k]; s = A.start[k]; }
       const uint64_t row = row0 + q;
-      v[j] = ok[j] ? load_streaming(src + (row * (uint64_t)p + (uint64_t)b + (uint64_t)(c - s))) : u32x4{0u, 0u, 0u, 0u};
+      v[j] = ok[j] ? load_streaming(src + (row * (uint64_t)p + (uint64_t)(c - s))) : u32x4{0u, 0u, 0u, 0u};
       if constexpr (ADD) {
         has[j] = ok[j] && add != nullptr;
         ad[j] = has[j] ? load_streaming(add + (row * (uint64_t)w + (uint64_t)(c - s))) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -224,11 +234,11 @@ join_rows(const JoinArgs A, uint32_t segs, uint64_t total_tasks) {
     if (col < cols) {
       const E* src = (const E*)A.src[0];
       const float* add = A.addend[0];
-      uint32_t p = A.pitch[0], b = A.begin[0], w = A.count[0], s = 0;
+      uint32_t p = A.pitch[0], w = A.count[0], s = 0;
 #pragma unroll
       for (int k = 1; k < kJoinMaxWindows; ++k)
-        if (col >= A.start[k]) { src = (const E*)A.src[k]; add = A.addend[k]; p = A.pitch[k]; b = A.begin[k]; w = A.count[k]; s = A.start[k]; }
-      E v = src[row * (uint64_t)p + (uint64_t)b + (uint64_t)(col - s)];
+        if (col >= A.start[k]) { src = (const E*)A.src[k]; add = A.addend[k]; p = A.pitch[k]; w = A.count[k]; s = A.start[k]; }
+      E v = src[row * (uint64_t)p + (uint64_t)(col - s)];
       if constexpr (ADD) {
         if (add) v = __builtin_bit_cast(E, __builtin_bit_cast(float, v) + add[row * (uint64_t)w + (uint64_t)(col - s)]);
       }

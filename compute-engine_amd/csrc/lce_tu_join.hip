@@ -1,10 +1,10 @@
-// One translation unit of the product library (csrc/Makefile): the join of channel windows (lce_kernels_join.h).
+// One translation unit of the product library (csrc/Makefile): the channel join (lce_kernels_join.h).
 #include <hip/hip_runtime.h>
 #include "lce_kernels_join.h"
 
 namespace lce {
 namespace {
-// memory-bound streams: 4 waves per block, at most ~8 blocks per CU, grid-stride the rest (as lce_tu_concat.hip)
+// memory-bound streams: 4 waves per block, at most ~8 blocks per CU, grid-stride the rest (as lce_tu_eltwise.hip)
 unsigned join_stream_grid(uint64_t wave_tasks) {
   const uint64_t blocks = (wave_tasks + 3) / 4, cap = 256ull * 8ull;
   return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));

@@ -1588,7 +1588,7 @@ struct Walk {
   std::map<int32_t, Shape> shapes;
   std::vector<char> done;                // per operator: a launch further up has already produced its output
   // A WINDOW TENSOR: the output of an absorbed slice (or of the ADD behind it) that is no buffer but channels [begin, begin + count)
-  // of tensor `src`, with tensor `addend` (-1: none) added, for the CONCATENATION that reads it (Slice, JoinWindows)
+  // of tensor `src`, with tensor `addend` (-1: none) added, for the CONCATENATION that reads it (Slice, Concat)
   struct Window { int32_t src, begin, count, addend; };
   std::map<int32_t, Window> windows;
 
@@ -1898,61 +1898,24 @@ struct Walk {
     return Launched(kAbsorbedInt8Add, fold);
   }
 
-  // An absorbed CONCATENATION (LCE_TFLITE_SECTIONS_CONCAT) as ONE lce_hip_concat launch.  The first LceQuantize of the section
-  // that reads the joined tensor becomes the launch's bit output and its own launch disappears; the joined tensor itself is
-  // written when anything else reads it (in a dense block the next join does) or the section delivers it.
+  // An absorbed CONCATENATION (LCE_TFLITE_SECTIONS_CONCAT) as ONE launch.  Every input is a window: a window tensor gives its own
+  // (with its addend), a plain input the whole tensor.  With no window tensor among them the launch is lce_hip_concat (which also
+  // joins bitpacked words), otherwise lce_hip_join_windows.  The first LceQuantize of the section that reads the joined tensor
+  // becomes the launch's bit output and its own launch disappears; the joined tensor itself is written when anything else reads
+  // it (in a dense block the next join does) or the section delivers it.
   lce_hip_status Concat(int32_t i) {
     const lce_tfl::Model& M = model->m;
     const lce_tfl::Operator& op = M.operators[i];
     const int32_t out_t = op.outputs[0];
     const lce_tfl::Tensor& OT = M.tensors[out_t];
     const std::vector<int32_t>& fs = OT.shape;
-    for (int32_t t : op.inputs)
-      if (windows.count(t)) return JoinWindows(i);
-    // the inferred shape and type of EVERY input must agree with the file's (a producer whose output is smaller than the file
-    // declares must not be read past its buffer)
-    int32_t channels[LCE_HIP_CONCAT_MAX_INPUTS];
-    int64_t sum = 0;
-    const size_t n = op.inputs.size();
-    for (size_t k = 0; k < n; ++k) {
-      auto it = shapes.find(op.inputs[k]);
-      if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION reads a tensor nothing produced");
-      const Shape& xs = it->second;
-      if (!Agrees(xs, OT.type, fs[1], fs[2], M.tensors[op.inputs[k]].shape[3]))
-        return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION input's shape or type does not match the one its producer infers");
-      channels[k] = xs.dims[3];
-      sum += xs.dims[3];
-    }
-    if (sum != fs[3]) return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION's inputs do not add up to its output");
-    Shape os;
-    os.dims[0] = batch; os.dims[1] = fs[1]; os.dims[2] = fs[2]; os.dims[3] = fs[3];
-    os.type = OT.type;
-    shapes[out_t] = os;
-    done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os, /*allowed=*/OT.type != lce_tfl::kTensorInt32);
-    if (!run) return LCE_HIP_OK;
-    const void* in[LCE_HIP_CONCAT_MAX_INPUTS];
-    for (size_t k = 0; k < n; ++k)
-      if (lce_hip_status s = DevicePtr(op.inputs[k], "a CONCATENATION input", &in[k])) return s;
-    void *out, *bits;
-    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    const lce_hip_dtype type = OT.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : OT.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BITPACKED;
-    if (lce_hip_status s = lce_hip_concat(type, in, channels, (int32_t)n, (size_t)batch * fs[1] * fs[2],
-                                          type == LCE_HIP_I8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
-    return Launched(kAbsorbedConcat, fold);
-  }
-
-  // An absorbed CONCATENATION with at least one window tensor among its inputs as ONE lce_hip_join_windows launch: a window tensor
-  // becomes its window (with its addend), a plain input the whole-tensor window.  Folds the first LceQuantize as Concat does.
-  lce_hip_status JoinWindows(int32_t i) {
-    const lce_tfl::Model& M = model->m;
-    const lce_tfl::Operator& op = M.operators[i];
-    const int32_t out_t = op.outputs[0];
-    const lce_tfl::Tensor& OT = M.tensors[out_t];
-    const std::vector<int32_t>& fs = OT.shape;
-    if (OT.type != lce_tfl::kTensorFloat32 && OT.type != lce_tfl::kTensorInt8)
+    bool windowed = false;
+    for (int32_t t : op.inputs) windowed = windowed || windows.count(t);
+    if (windowed && OT.type != lce_tfl::kTensorFloat32 && OT.type != lce_tfl::kTensorInt8)
       return Fail(LCE_HIP_ERR_INVALID, "run_section: a CONCATENATION of windows is neither float32 nor int8");
-    // the inferred shape and type of EVERY source and addend must agree with the file's before anything is read
+    // the inferred shape and type of EVERY source and addend must agree with the file's before anything is read (a producer
+    // whose output is smaller than the file declares must not be read past its buffer)
+    static_assert(LCE_HIP_CONCAT_MAX_INPUTS <= LCE_HIP_JOIN_MAX_WINDOWS, "ConcatCandidate's bound on the inputs");
     Window win[LCE_HIP_JOIN_MAX_WINDOWS];
     int32_t pitch[LCE_HIP_JOIN_MAX_WINDOWS];
     const size_t n = op.inputs.size();
@@ -1980,7 +1943,7 @@ struct Walk {
     const Shape os = OutShape(fs[1], fs[2], fs[3], OT.type);
     shapes[out_t] = os;
     done[i] = 1;
-    const Fold fold = FoldQuantize(i, out_t, os);
+    const Fold fold = FoldQuantize(i, out_t, os, /*allowed=*/OT.type != lce_tfl::kTensorInt32);
     if (!run) return LCE_HIP_OK;
     lce_hip_window w[LCE_HIP_JOIN_MAX_WINDOWS];
     memset(w, 0, sizeof w);
@@ -1995,11 +1958,19 @@ struct Walk {
     }
     void *out, *bits;
     if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
-    const bool i8 = OT.type == lce_tfl::kTensorInt8;
-    if (lce_hip_status s = lce_hip_join_windows(i8 ? LCE_HIP_I8 : LCE_HIP_F32, w, (int32_t)n, (size_t)batch * fs[1] * fs[2],
-                                                i8 ? (int32_t)OT.zero_point : 0, out, (int32_t*)bits, stream)) return s;
-    ++model->last.slice_joins;
-    return Launched(kAbsorbedSlice, fold);
+    const lce_hip_dtype type = OT.type == lce_tfl::kTensorFloat32 ? LCE_HIP_F32 : OT.type == lce_tfl::kTensorInt8 ? LCE_HIP_I8 : LCE_HIP_BITPACKED;
+    const size_t rows = (size_t)batch * fs[1] * fs[2];
+    const int32_t zero_point = type == LCE_HIP_I8 ? (int32_t)OT.zero_point : 0;
+    if (windowed) {
+      if (lce_hip_status s = lce_hip_join_windows(type, w, (int32_t)n, rows, zero_point, out, (int32_t*)bits, stream)) return s;
+      ++model->last.slice_joins;
+      return Launched(kAbsorbedSlice, fold);
+    }
+    const void* in[LCE_HIP_CONCAT_MAX_INPUTS];
+    int32_t channels[LCE_HIP_CONCAT_MAX_INPUTS];
+    for (size_t k = 0; k < n; ++k) { in[k] = w[k].data_dev; channels[k] = w[k].count; }
+    if (lce_hip_status s = lce_hip_concat(type, in, channels, (int32_t)n, rows, zero_point, out, (int32_t*)bits, stream)) return s;
+    return Launched(kAbsorbedConcat, fold);
   }
 
   // The reader of window-tensor candidate `t` (an absorbed slice's output, or the output of the ADD behind one) when `t` is not

@@ -150,31 +150,25 @@ _PASSES = (
     ("reshape_sections", "reshape", None, None, None),
     ("gate_sections", "gate", None, None, None),
     ("binary_dense_sections", "binary_dense", None, None, None),
-)
-# Rows added since tests/test_head_sections_host.py pinned the length of the table above, of _PASS_STATS and the key order of
-# _PASS_NAMES: the same row shape, consulted beside them (one table again once that test may change).
-_PASSES_MORE = (
     ("slice_sections", "slice", None, None, None),
 )
-_PASS_STATS_MORE = {"slice": 3}
 # three views of it: the keywords an options struct carries, every keyword's name, the keywords only the names reach
 _SECTION_KEYWORDS = tuple((keyword, word, bit, form) for keyword, _, word, bit, form in _PASSES if word is not None)
 _PASS_NAMES = {keyword: name for keyword, name, _, _, _ in _PASSES}
 _NAMED_ONLY = tuple(keyword for keyword, _, word, _, _ in _PASSES if word is None)
-_NAMED_ONLY_MORE = tuple(keyword for keyword, _, word, _, _ in _PASSES_MORE if word is None)
-_ALL_PASS_NAMES = {keyword: name for keyword, name, _, _, _ in _PASSES + _PASSES_MORE}
 _OPEN_OPTIONS = {C.sizeof(t): t for t in (_OpenOptions, _OpenOptionsExt, _OpenOptions40, _OpenOptions56)}
 # ``lce_tflite_model_<pass>_stats`` and ``LceModel.<pass>_stats()``: the counters each reports
 _PASS_STATS = {"elementwise": 3, "int8_add": 2, "concat": 2, "pool": 2, "conv1x1": 2, "depthwise": 2, "conv2d": 2, "conv_i8": 2,
-               "depthwise_i8": 2, "head": 3, "head_i8": 3, "quantize": 2, "activation": 3, "gate": 2, "reshape": 2, "binary_dense": 3}
+               "depthwise_i8": 2, "head": 3, "head_i8": 3, "quantize": 2, "activation": 3, "gate": 2, "reshape": 2, "binary_dense": 3,
+               "slice": 3}
 
 
 def _section_keywords(where, sections):
     """``sections`` -- the ``**sections`` of ``where`` -- checked against ``_PASSES``: {keyword: bool} for every keyword."""
     for keyword in sections:
-        if keyword not in _ALL_PASS_NAMES:
+        if keyword not in _PASS_NAMES:
             raise TypeError("%s() got an unexpected keyword argument %r" % (where, keyword))
-    return {keyword: bool(sections.get(keyword, False)) for keyword in _ALL_PASS_NAMES}
+    return {keyword: bool(sections.get(keyword, False)) for keyword in _PASS_NAMES}
 
 
 class Section:
@@ -214,7 +208,7 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_operator_depthwise.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_axis.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.lce_tflite_model_operator_activation.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-        for name, counters in {**_PASS_STATS, **_PASS_STATS_MORE}.items():
+        for name, counters in _PASS_STATS.items():
             f = getattr(l, "lce_tflite_model_%s_stats" % name)
             f.argtypes, f.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * counters, None
         l.lce_tflite_model_close.argtypes = [C.c_void_p]
@@ -332,8 +326,8 @@ class LceModel:
                 words[word] |= bit
                 size = max(size, form)
         err = C.create_string_buffer(256)
-        if any(given[keyword] for keyword in _NAMED_ONLY + _NAMED_ONLY_MORE):
-            names = ",".join(name for keyword, name, _, _, _ in _PASSES + _PASSES_MORE if given[keyword])
+        if any(given[keyword] for keyword in _NAMED_ONLY):
+            names = ",".join(name for keyword, name, _, _, _ in _PASSES if given[keyword])
             self._h = tflite_lib().lce_tflite_model_open_passes(self._data, len(self._data), names.encode(), err, 256)
         elif size:
             opts = _OPEN_OPTIONS[size](size, *words[:1 if size == 8 else 2])
@@ -411,7 +405,7 @@ class LceModel:
 
     def _pass_stats(self, name):
         """The counters of ``lce_tflite_model_<name>_stats``."""
-        v = [C.c_int32() for _ in range({**_PASS_STATS, **_PASS_STATS_MORE}[name])]
+        v = [C.c_int32() for _ in range(_PASS_STATS[name])]
         getattr(tflite_lib(), "lce_tflite_model_%s_stats" % name)(self._h, *[C.byref(c) for c in v])
         return tuple(int(c.value) for c in v)
 
@@ -521,7 +515,7 @@ class Interpreter:
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if any(getattr(self.model, keyword) for keyword in _ALL_PASS_NAMES):
+        if any(getattr(self.model, keyword) for keyword in _PASS_NAMES):
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

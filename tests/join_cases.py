@@ -31,6 +31,25 @@ ROW_I8 = {
 }
 
 
+def dense(*channels):
+    """Whole tensors of `channels` joined: lce_hip_concat's launch, begin 0 and count = pitch."""
+    return tuple(channels), [(k, 0, c, False) for k, c in enumerate(channels)]
+
+
+def twice(c):
+    """One tensor of `c` channels joined to itself."""
+    return (c,), [(0, 0, c, False), (0, 0, c, False)]
+
+
+# the dense joins tests/test_gpu_concat.py runs on the GPU, by the path they take
+DENSE_VEC_F32 = {"dense:64x64": dense(64, 64), "dense:256x64x64": dense(256, 64, 64), "dense:8x32": dense(*(32,) * 8), "dense:64twice": twice(64)}
+DENSE_ROW_F32 = {"dense:1x31": dense(1, 31), "dense:33x64x7": dense(33, 64, 7), "dense:63x1": dense(63, 1), "dense:7twice": twice(7)}
+DENSE_VEC_I8 = {"dense:16x16": dense(16, 16), "dense:128x64": dense(128, 64), "dense:64twice": twice(64)}
+DENSE_ROW_I8 = {"dense:48x17": dense(48, 17), "dense:5x3": dense(5, 3), "dense:7twice": twice(7)}
+# bitpacked int32 words: 4-byte elements through the float kind, no bit output
+DENSE_WORDS = {"words:4x8x4": (dense(4, 8, 4), True), "words:1x3": (dense(1, 3), False)}      # (case, takes the 16-byte path)
+
+
 def build(kind, case, rows, seed):
     """The windows of `case` on random operands: [(source [rows, pitch], begin, count, addend [rows, count] or None)].  Float
     operands are random 32-bit patterns with the special values planted (tests/test_gpu_concat.py)."""

@@ -488,7 +488,7 @@ def test_stats_are_zero_before_any_run():
 
 
 # ---- the build: no scratch memory, no LDS, no scalar-memory writes -------------------------------------------------------------
-NEW_SOURCES = ("lce_kernels_concat.h", "lce_tu_concat.hip")
+NEW_SOURCES = ("lce_kernels_join.h", "lce_tu_join.hip")
 
 
 def test_the_new_sources_hold_no_scalar_memory_write():
@@ -496,9 +496,11 @@ def test_the_new_sources_hold_no_scalar_memory_write():
 
 
 def test_the_concat_kernels_use_no_scratch_and_no_lds():
-    kernels, resources, _, mnemonics = H.compile_unit("lce_tu_concat.hip")
-    assert sorted(k for k in kernels if "concat" in k) == sorted(k for k in kernels), kernels
-    assert len(kernels) == 8, kernels                        # vector: F32 / I8 with and without bits, words; rows: three
+    kernels, resources, _, mnemonics = H.compile_unit("lce_tu_join.hip")
+    assert sorted(k for k in kernels if "join" in k) == sorted(k for k in kernels), kernels
+    # vector: float with and without bits, each with and without an addend; int8 with and without bits; rows: float with and
+    # without an addend; int8
+    assert len(kernels) == 9, kernels
     for key in H.RESOURCE_KEYS:
         assert resources[key] == ["0"] * len(kernels), (key, resources[key])
     assert not [m for m in mnemonics if H.scalar_memory_write(m)]

@@ -318,7 +318,7 @@ def test_every_row_of_the_python_tables_is_one_the_library_knows():
     data = SM.small_model()[0]
     lib = mr.tflite_lib()
     keywords = [row[0] for row in mr._PASSES]
-    assert len(mr._PASSES) == 17 and len(set(keywords)) == 17 and len({row[1] for row in mr._PASSES}) == 17
+    assert len(mr._PASSES) == 18 and len(set(keywords)) == 18 and len({row[1] for row in mr._PASSES}) == 18
     assert keywords == [k for k, _, _, _ in mr._SECTION_KEYWORDS] + list(mr._NAMED_ONLY) == list(mr._PASS_NAMES)
     for keyword, name, word, bit, form in mr._PASSES:
         assert (word is None) == (bit is None) == (form is None) == (keyword in mr._NAMED_ONLY), keyword
@@ -338,7 +338,7 @@ def test_every_row_of_the_python_tables_is_one_the_library_knows():
                 constructor(data, head_sections=True, **{unknown: False})
     with pytest.raises(TypeError, match="tail_sections"):
         mr.Interpreter(mr.LceModel(data), tail_sections=True)            # (checked even where a ready model makes it moot)
-    assert len(mr._PASS_STATS) == 16
+    assert len(mr._PASS_STATS) == 17
     model = mr.LceModel(data)
     for name, counters in mr._PASS_STATS.items():
         assert hasattr(lib, "lce_tflite_model_%s_stats" % name), name

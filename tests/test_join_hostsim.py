@@ -1,5 +1,6 @@
-"""The window join's kernel bodies (csrc/lce_kernels_join.h) on the CPU against NumPy, bit for bit: both paths, every instance,
-the three output combinations, and grids capped at 1 and 3 blocks so that every wave takes several grid strides.  No GPU."""
+"""The join's kernel bodies (csrc/lce_kernels_join.h) on the CPU against NumPy, bit for bit: windows and whole tensors (the dense
+join of lce_hip_concat), both paths, every instance, the three output combinations, and grids capped at 1 and 3 blocks so that
+every wave takes several grid strides.  No GPU."""
 import numpy as np
 import pytest
 
@@ -39,6 +40,37 @@ def test_int8_windows_at_four_zero_points(name, rows, cap):
     w = J.build("i8", (J.VEC_I8 if vec else J.ROW_I8)[name], rows, rows + cap)
     for zp in (-128, 0, 5, 127):
         check(w, vec, cap, zp)
+
+
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("name", list(J.DENSE_VEC_F32) + list(J.DENSE_ROW_F32))
+def test_dense_float_joins(name, rows, cap):
+    vec = name in J.DENSE_VEC_F32
+    check(J.build("f32", (J.DENSE_VEC_F32 if vec else J.DENSE_ROW_F32)[name], rows, rows + cap), vec, cap)
+
+
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("name", list(J.DENSE_VEC_I8) + list(J.DENSE_ROW_I8))
+def test_dense_int8_joins_at_four_zero_points(name, rows, cap):
+    vec = name in J.DENSE_VEC_I8
+    w = J.build("i8", (J.DENSE_VEC_I8 if vec else J.DENSE_ROW_I8)[name], rows, rows + cap)
+    for zp in (-128, 0, 5, 127):
+        check(w, vec, cap, zp)
+
+
+@pytest.mark.parametrize("cap", [1, 3])
+@pytest.mark.parametrize("rows", ROWS)
+@pytest.mark.parametrize("name", list(J.DENSE_WORDS))
+def test_bitpacked_words_join_as_four_byte_elements(name, rows, cap):
+    """lce_hip_concat's bitpacked kind: int32 patterns through the float instances, value output only, compared as raw bits."""
+    case, vec = J.DENSE_WORDS[name]
+    w = J.build("f32", case, rows, rows + cap)
+    words = [t.view(np.int32) for t, _, _, _ in w]
+    got, none, took = H.sim(w, 0, True, False, cap)
+    assert none is None and took == vec
+    assert np.array_equal(got.view(np.int32), np.concatenate(words, axis=-1))
 
 
 @pytest.mark.parametrize("kind,name", [("f32", "192:0+128,128+64a"), ("i8", "192:0+128,128+64")])

@@ -9,8 +9,8 @@ page next to the differences.
   (a) fused     one lce_hip_join_windows launch: windows (x, 0, C-64) and (x, C-64, 64, addend w)
   (b) composed  two one-window lce_hip_join_windows launches (the slices), lce_hip_elementwise (the ADD), lce_hip_concat
   (c) concat    lce_hip_concat of a dense [rows, C-64] and a dense [rows, 64] tensor: the yardstick.  It writes the same output
-                bytes and reads as many source bytes as (a) reads of x, but no addend.  Its kernel (lce_kernels_concat.h) is
-                the parent commit's, unchanged by this pass.
+                bytes and reads as many source bytes as (a) reads of x, but no addend.  It launches the same kernels
+                (lce_kernels_join.h) on whole-tensor windows.
 
 Each figure is microseconds per block from HIP events around replays of a captured HIP graph that holds `--per-graph` blocks.
 Consecutive blocks of a graph use DIFFERENT operand sets (x, w, y and every intermediate), `--sets` of them in rotation; the sets
@@ -100,7 +100,7 @@ def main():
     print("# us per improvement block from HIP-graph replays (%d blocks per graph, %d operand sets in rotation, >= %.0f ms per figure "
           "after a spin-up); %d repeats, alternating" % (args.per_graph, args.sets, args.window_ms, args.repeats))
     print("# fused = one lce_hip_join_windows; composed = 2 x one-window lce_hip_join_windows + lce_hip_elementwise + lce_hip_concat;")
-    print("# concat = lce_hip_concat of dense [rows, C-64] and [rows, 64] (the yardstick: the same output bytes, no addend; its kernel is unchanged)")
+    print("# concat = lce_hip_concat of dense [rows, C-64] and [rows, 64] (the yardstick: the same output bytes, no addend; the same kernels on whole-tensor windows)")
     print("# %-18s %-6s %10s %10s %10s" % ("rows x C", "repeat", "fused", "composed", "concat"))
     summary = []
     for rows, c in shapes:
