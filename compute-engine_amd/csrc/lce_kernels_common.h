@@ -1,0 +1,58 @@
+// What more than one family of section kernels uses (pools, depthwise, joins, the float and the int8 CONV_2D): a host part, and
+// a device part for hipcc and for the host simulations of the kernels (tests/hostsim_*).
+#pragma once
+#include <stdint.h>
+
+#include "lce_kernel_args.h"
+
+namespace lce {
+
+// What the launch descriptors of the float and the int8 CONV_2D (Conv2dArgs, ConvI8Args) have in common, for a convolution whose
+// sizes the caller has checked and whose output extents oh x ow it knows: the channel counts, K = fh fw Cin < 2^31 and its
+// contiguous runs, the extents, the strides and the padding in front.
+template <typename Args>
+inline void conv_window_geometry(Args& a, int32_t in_height, int32_t in_width, int32_t channels_in, int32_t channels_out, int32_t filter_height,
+                                 int32_t filter_width, int32_t stride_height, int32_t stride_width, int32_t oh, int32_t ow) {
+  const uint64_t Cin = (uint64_t)channels_in, N = (uint64_t)channels_out;
+  a.Cin = (uint32_t)Cin; a.Cout = (uint32_t)N; a.wpr = (uint32_t)((N + 31) / 32);
+  a.K = (uint32_t)((uint64_t)filter_height * filter_width * Cin);
+  a.rowlen = (uint32_t)((uint64_t)filter_width * Cin);
+  a.in_row = (uint64_t)in_width * Cin;
+  a.IH = in_height; a.IW = in_width; a.OH = oh; a.OW = ow;
+  a.sh = stride_height; a.sw = stride_width;
+  // ComputePaddingHeightWidth: total / 2 in front
+  const int64_t th = (int64_t)(oh - 1) * stride_height + filter_height - in_height, tw = (int64_t)(ow - 1) * stride_width + filter_width - in_width;
+  a.ph = (int32_t)((th > 0 ? th : 0) / 2);
+  a.pw = (int32_t)((tw > 0 ? tw : 0) / 2);
+}
+
+}  // namespace lce
+
+#ifdef __HIPCC__
+#include <lce_device_intrinsics.h>  // resolved through -I: csrc/ for the product, the host replacement for the simulations
+
+namespace lce {
+using namespace lce_dev;
+
+// n / d for n < 2^31 and a launch constant d (make_fastdiv, lce_kernel_args.h): one v_mul_hi and a shift.
+LCE_DEVICE uint32_t fast_div(uint32_t n, FastDiv d) { return d.magic == 0u ? n : (mulhi_u32(n, d.magic) >> d.shift); }
+
+// The ballots of accumulator registers 4 G .. 4 G + 3 of one 32x32 instruction tile, whose rows are pixels and whose columns
+// are channels: register 4 G + i holds pixel 8 G + i of the wave's 32 in lanes 0..31 and pixel 8 G + 4 + i in lanes 32..63, so
+// the two halves of b[i] are those two pixels' bit words.  Each goes to the lane of its pixel in `words` (v_writelane: no
+// lane masks to keep; the ballots are settled once per group, lce_device_intrinsics.h).
+template <int G>
+LCE_DEVICE void tile_words(unsigned long long (&b)[4], uint32_t& words) {
+  settle_ballots(b);
+  words = write_lane_settled<8 * G + 0>((uint32_t)b[0], words);
+  words = write_lane_settled<8 * G + 1>((uint32_t)b[1], words);
+  words = write_lane_settled<8 * G + 2>((uint32_t)b[2], words);
+  words = write_lane_settled<8 * G + 3>((uint32_t)b[3], words);
+  words = write_lane_settled<8 * G + 4>((uint32_t)(b[0] >> 32), words);
+  words = write_lane_settled<8 * G + 5>((uint32_t)(b[1] >> 32), words);
+  words = write_lane_settled<8 * G + 6>((uint32_t)(b[2] >> 32), words);
+  words = write_lane_settled<8 * G + 7>((uint32_t)(b[3] >> 32), words);
+}
+
+}  // namespace lce
+#endif  // __HIPCC__

@@ -31,7 +31,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "lce_kernel_args.h"
+#include "lce_kernels_common.h"
 #include "lce_kernels_conv1x1.h"
 
 namespace lce {
@@ -70,17 +70,8 @@ struct Conv2dArgs {
 // of the kernels (tests/hostsim_conv2d) fills its launches with it too.
 inline void conv2d_geometry(Conv2dArgs& a, int32_t batch, int32_t in_height, int32_t in_width, int32_t channels_in, int32_t channels_out,
                             int32_t filter_height, int32_t filter_width, int32_t stride_height, int32_t stride_width, int32_t oh, int32_t ow) {
-  const uint64_t Cin = (uint64_t)channels_in, N = (uint64_t)channels_out;
-  a.Cin = (uint32_t)Cin; a.Cout = (uint32_t)N; a.wpr = (uint32_t)((N + 31) / 32);
-  a.K = (uint32_t)((uint64_t)filter_height * filter_width * Cin);               // < 2^31
-  a.rowlen = (uint32_t)((uint64_t)filter_width * Cin);
-  a.in_row = (uint64_t)in_width * Cin;
-  a.IH = in_height; a.IW = in_width; a.OH = oh; a.OW = ow;
-  a.fh = filter_height; a.fw = filter_width; a.sh = stride_height; a.sw = stride_width;
-  // ComputePaddingHeightWidth: total / 2 in front
-  const int64_t th = (int64_t)(oh - 1) * stride_height + filter_height - in_height, tw = (int64_t)(ow - 1) * stride_width + filter_width - in_width;
-  a.ph = (int32_t)((th > 0 ? th : 0) / 2);
-  a.pw = (int32_t)((tw > 0 ? tw : 0) / 2);
+  conv_window_geometry(a, in_height, in_width, channels_in, channels_out, filter_height, filter_width, stride_height, stride_width, oh, ow);
+  a.fh = filter_height; a.fw = filter_width;
   // the interior rectangle: output pixels o with 0 <= o * stride - pad and o * stride - pad + filter <= extent
   auto interior = [](int64_t extent, int64_t out, int64_t filter, int64_t stride, int64_t pad, uint32_t* first, uint32_t* count) {
     const int64_t lo = (pad + stride - 1) / stride;
@@ -100,7 +91,7 @@ inline void conv2d_geometry(Conv2dArgs& a, int32_t batch, int32_t in_height, int
   a.top = a.iy0 * (uint32_t)ow;
   a.side = (uint32_t)ow - a.iw;
   a.mid = a.ih * a.side;
-  a.segs = (uint32_t)((N + 63) / 64);
+  a.segs = (a.Cout + 63u) / 64u;
   a.div_rowlen = make_fastdiv(a.rowlen);
   a.div_iw = make_fastdiv(a.iw);
   a.div_ihw = make_fastdiv((uint32_t)per_image);
@@ -119,8 +110,6 @@ int launch_conv2d(const Conv2dArgs& args, bool vec, void* stream);
 #ifdef __HIPCC__
 namespace lce {
 
-LCE_DEVICE uint32_t conv2d_div(uint32_t n, FastDiv d) { return d.magic == 0u ? n : (mulhi_u32(n, d.magic) >> d.shift); }
-
 // conv1x1_rows with the tile's output pixel numbers read from LDS (`opix` points at the lane's pixel for G = 0, i = 0;
 // 0xffffffff: a row past the end).  `mlim`: 2^31 to store, 0 without a float output or for a channel past the end.
 template <int G>
@@ -136,17 +125,7 @@ LCE_DEVICE void conv2d_rows(const Conv2dArgs& A, const f32x16& acc, float bias, 
     if (m < mlim) A.out[(uint64_t)m * A.Cout + ch] = v;
     b[i] = wave_ballot(v < thr);
   }
-  if (A.bits != nullptr) {
-    settle_ballots(b);
-    words = write_lane_settled<8 * G + 0>((uint32_t)b[0], words);
-    words = write_lane_settled<8 * G + 1>((uint32_t)b[1], words);
-    words = write_lane_settled<8 * G + 2>((uint32_t)b[2], words);
-    words = write_lane_settled<8 * G + 3>((uint32_t)b[3], words);
-    words = write_lane_settled<8 * G + 4>((uint32_t)(b[0] >> 32), words);
-    words = write_lane_settled<8 * G + 5>((uint32_t)(b[1] >> 32), words);
-    words = write_lane_settled<8 * G + 6>((uint32_t)(b[2] >> 32), words);
-    words = write_lane_settled<8 * G + 7>((uint32_t)(b[3] >> 32), words);
-  }
+  if (A.bits != nullptr) tile_words<G>(b, words);
 }
 
 template <bool VEC>
@@ -183,8 +162,8 @@ conv2d_interior(const Conv2dArgs A) {
       const bool ok = m1 < A.Mi;
       xlim[i] = ok ? K : 0u;
       const uint32_t m = ok ? m1 : 0u;
-      const uint32_t b = conv2d_div(m, A.div_ihw), rem = m - b * ihw;
-      const uint32_t ry = conv2d_div(rem, A.div_iw), rx = rem - ry * A.iw;
+      const uint32_t b = fast_div(m, A.div_ihw), rem = m - b * ihw;
+      const uint32_t ry = fast_div(rem, A.div_iw), rx = rem - ry * A.iw;
       const uint32_t oy = A.iy0 + ry, ox = A.ix0 + rx;
       const uint64_t y = (uint64_t)oy * (uint32_t)A.sh - (uint32_t)A.ph, x = (uint64_t)ox * (uint32_t)A.sw - (uint32_t)A.pw;   // >= 0: interior
       xrow[i] = A.in + (((uint64_t)b * (uint32_t)A.IH + y) * (uint32_t)A.IW + x) * A.Cin;
@@ -201,7 +180,7 @@ conv2d_interior(const Conv2dArgs A) {
 #pragma unroll
       for (int e = 0; e < (VEC ? 1 : 4); ++e) {
         const uint32_t ke = k + (uint32_t)e < K ? k + (uint32_t)e : 0u;
-        const uint32_t fy = conv2d_div(ke, A.div_rowlen);
+        const uint32_t fy = fast_div(ke, A.div_rowlen);
         off[e] = (uint64_t)fy * A.in_row + (ke - fy * A.rowlen);
       }
       f32x4 xv[4], wv[4];
@@ -286,17 +265,17 @@ conv2d_border(const Conv2dArgs A) {
     const uint32_t seg = (uint32_t)(t - (uint64_t)j * A.segs);
     const uint32_t col = seg * 64u + lane;
     // the pixel: image b, the jj-th border pixel of it
-    const uint32_t b = conv2d_div(j, A.div_bpi), jj = j - b * A.bpi;
+    const uint32_t b = fast_div(j, A.div_bpi), jj = j - b * A.bpi;
     uint32_t oy, ox;
     if (jj < A.top) {
-      oy = conv2d_div(jj, A.div_ow);
+      oy = fast_div(jj, A.div_ow);
       ox = jj - oy * (uint32_t)A.OW;
     } else if (jj - A.top < A.mid) {
-      const uint32_t u = jj - A.top, ry = conv2d_div(u, A.div_side), s = u - ry * A.side;
+      const uint32_t u = jj - A.top, ry = fast_div(u, A.div_side), s = u - ry * A.side;
       oy = A.iy0 + ry;
       ox = s < A.ix0 ? s : s + A.iw;
     } else {
-      const uint32_t u = jj - A.top - A.mid, ry = conv2d_div(u, A.div_ow);
+      const uint32_t u = jj - A.top - A.mid, ry = fast_div(u, A.div_ow);
       oy = A.iy0 + A.ih + ry;
       ox = u - ry * (uint32_t)A.OW;
     }

@@ -37,7 +37,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "lce_kernel_args.h"
+#include "lce_kernels_common.h"
 #include "lce_kernels_eltwise_i8.h"
 
 namespace lce {
@@ -73,17 +73,7 @@ struct ConvI8Args {
 // fills its launches with it too.
 inline void conv2d_i8_geometry(ConvI8Args& a, int32_t batch, int32_t in_height, int32_t in_width, int32_t channels_in, int32_t channels_out,
                                int32_t filter_height, int32_t filter_width, int32_t stride_height, int32_t stride_width, int32_t oh, int32_t ow) {
-  const uint64_t Cin = (uint64_t)channels_in, N = (uint64_t)channels_out;
-  a.Cin = (uint32_t)Cin; a.Cout = (uint32_t)N; a.wpr = (uint32_t)((N + 31) / 32);
-  a.K = (uint32_t)((uint64_t)filter_height * filter_width * Cin);
-  a.rowlen = (uint32_t)((uint64_t)filter_width * Cin);
-  a.in_row = (uint64_t)in_width * Cin;
-  a.IH = in_height; a.IW = in_width; a.OH = oh; a.OW = ow;
-  a.sh = stride_height; a.sw = stride_width;
-  // ComputePaddingHeightWidth: total / 2 in front
-  const int64_t th = (int64_t)(oh - 1) * stride_height + filter_height - in_height, tw = (int64_t)(ow - 1) * stride_width + filter_width - in_width;
-  a.ph = (int32_t)((th > 0 ? th : 0) / 2);
-  a.pw = (int32_t)((tw > 0 ? tw : 0) / 2);
+  conv_window_geometry(a, in_height, in_width, channels_in, channels_out, filter_height, filter_width, stride_height, stride_width, oh, ow);
   a.M = (uint32_t)((uint64_t)batch * oh * ow);
   a.mtiles = (uint32_t)(((uint64_t)a.M + kConvI8BM - 1) / kConvI8BM);
   a.div_rowlen = make_fastdiv(a.rowlen);
@@ -111,8 +101,6 @@ namespace lce {
 typedef int32_t i32x4 __attribute__((vector_size(16)));
 typedef int32_t i32x16 __attribute__((vector_size(64)));
 
-LCE_DEVICE uint32_t conv2d_i8_div(uint32_t n, FastDiv d) { return d.magic == 0u ? n : (mulhi_u32(n, d.magic) >> d.shift); }
-
 // MultiplyByQuantizedMultiplier (tensorflow/lite/kernels/internal/common.h, the double-rounding build) for a multiplier m and
 // an exponent -31 <= e <= 30.  Compiled for both sides: the host tests run this very function.
 LCE_HOST_DEVICE int32_t conv2d_i8_requantize(int32_t acc, int32_t m, int32_t e) {
@@ -137,17 +125,7 @@ LCE_DEVICE void conv2d_i8_rows(const ConvI8Args& A, const i32x16& acc, int32_t c
     if (m < mlim) A.out[(uint64_t)m * A.Cout + ch] = (int8_t)v;
     b[i] = wave_ballot(v < thr);
   }
-  if (A.bits != nullptr) {
-    settle_ballots(b);
-    words = write_lane_settled<8 * G + 0>((uint32_t)b[0], words);
-    words = write_lane_settled<8 * G + 1>((uint32_t)b[1], words);
-    words = write_lane_settled<8 * G + 2>((uint32_t)b[2], words);
-    words = write_lane_settled<8 * G + 3>((uint32_t)b[3], words);
-    words = write_lane_settled<8 * G + 4>((uint32_t)(b[0] >> 32), words);
-    words = write_lane_settled<8 * G + 5>((uint32_t)(b[1] >> 32), words);
-    words = write_lane_settled<8 * G + 6>((uint32_t)(b[2] >> 32), words);
-    words = write_lane_settled<8 * G + 7>((uint32_t)(b[3] >> 32), words);
-  }
+  if (A.bits != nullptr) tile_words<G>(b, words);
 }
 
 template <bool VEC>
@@ -189,8 +167,8 @@ conv2d_i8(const ConvI8Args A) {
       const uint32_t m1 = m0 + r0 + kPass * (uint32_t)i;
       const bool ok = m1 < A.M;
       const uint32_t m = ok ? m1 : 0u;
-      const uint32_t b = conv2d_i8_div(m, A.div_ohw), rem = m - b * ohw;
-      const uint32_t oy = conv2d_i8_div(rem, A.div_ow), ox = rem - oy * (uint32_t)A.OW;
+      const uint32_t b = fast_div(m, A.div_ohw), rem = m - b * ohw;
+      const uint32_t oy = fast_div(rem, A.div_ow), ox = rem - oy * (uint32_t)A.OW;
       const int32_t y = (int32_t)oy * A.sh - A.ph, x = (int32_t)ox * A.sw - A.pw;
       ys[i] = ok ? y : A.IH;                                         // (every tap of such a row is out of bounds)
       xs[i] = x;
@@ -205,8 +183,8 @@ conv2d_i8(const ConvI8Args A) {
       // element k of a window is the image byte at corner + fy * in_row + r, k = fy * rowlen + r, of tap fx = r / Cin
       const uint32_t k = k0 + 16u * q;
       const uint32_t kd = k < K ? k : 0u;
-      uint32_t fy = conv2d_i8_div(kd, A.div_rowlen), r = kd - fy * A.rowlen;
-      uint32_t fx = conv2d_i8_div(r, A.div_cin), c = r - fx * A.Cin;
+      uint32_t fy = fast_div(kd, A.div_rowlen), r = kd - fy * A.rowlen;
+      uint32_t fx = fast_div(r, A.div_cin), c = r - fx * A.Cin;
       // staged where nothing is read: x' = zi (a tap in the padding, the K tail, a pixel past the end), w = 0 (the K tail, a
       // channel past the end)
       u32x4 xv[R], wv[R];

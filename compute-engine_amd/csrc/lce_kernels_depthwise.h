@@ -102,7 +102,7 @@ depthwise_vec(const DepthwiseArgs A) {
     const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
     const bool ok = g < P.total;
     const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = pool_div(x, P.div_per_pixel);
+    const uint32_t q = fast_div(x, P.div_per_pixel);
     const uint32_t c = x - q * cpp;                                // < per_pixel, also for a lane past the end
     const PoolWindow w = pool_window(P, pix0 + q, ok);
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -149,7 +149,7 @@ depthwise_rows(const DepthwiseArgs A) {
     const PoolWindow w = pool_window(P, (uint32_t)pixel, true);
     bool neg = false;
     if (col < cols) {
-      const uint32_t ic = pool_div(col, A.div_multiplier);         // < cin
+      const uint32_t ic = fast_div(col, A.div_multiplier);         // < cin
       float acc = 0.0f;
       for (int32_t y = w.y0; y < w.y1; ++y) {
         const float* row = in + ((uint64_t)w.b * (uint64_t)P.H + (uint64_t)y) * (uint64_t)P.W * cin + ic;

@@ -109,7 +109,7 @@ depthwise_i8_vec(const DepthwiseI8Args A) {
     const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
     const bool ok = g < P.total;
     const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = pool_div(x, P.div_per_pixel);
+    const uint32_t q = fast_div(x, P.div_per_pixel);
     const uint32_t c = x - q * cpp;                                // < per_pixel, also for a lane past the end
     const PoolWindow w = pool_window(P, pix0 + q, ok);
     int32_t acc[16];
@@ -158,7 +158,7 @@ depthwise_i8_rows(const DepthwiseI8Args A) {
     const PoolWindow w = pool_window(P, (uint32_t)pixel, true);
     bool neg = false;
     if (col < cols) {
-      const uint32_t ic = pool_div(col, A.div_multiplier);         // < cin
+      const uint32_t ic = fast_div(col, A.div_multiplier);         // < cin
       int32_t acc = 0;
       for (int32_t y = w.y0; y < w.y1; ++y) {
         const int8_t* row = in + ((uint64_t)w.b * (uint64_t)P.H + (uint64_t)y) * (uint64_t)P.W * cin + ic;

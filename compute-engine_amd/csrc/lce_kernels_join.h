@@ -29,7 +29,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "lce_kernel_args.h"
+#include "lce_kernels_common.h"
 
 namespace lce {
 
@@ -125,8 +125,6 @@ unsigned join_vec_grid(uint64_t total_chunks);
 namespace lce {
 using namespace lce_dev;
 
-LCE_DEVICE uint32_t join_div(uint32_t n, FastDiv d) { return d.magic == 0u ? n : (mulhi_u32(n, d.magic) >> d.shift); }
-
 // Four int8 values in one dword -> 4 bits, bit k = byte k < zero_point.  `t4` holds zero_point + 128 in every byte: with
 // u = x ^ 0x80 per byte the comparison is unsigned, u < t, and per byte u < t <=> (~u & t) | (~(u ^ t) & ~d) at bit 7, where
 // d = (u | 0x80) - (t & 0x7f) never borrows from the next byte.  The four bits 7, 15, 23, 31 are gathered by one multiply.
@@ -161,7 +159,7 @@ join_vec(const JoinArgs A) {
     for (int j = 0; j < 4; ++j) {
       ok[j] = g0 + 64u * j < A.total_chunks;
       const uint32_t x = col0 + (uint32_t)lane + 64u * j;          // < total + 256 < 2^31
-      const uint32_t q = join_div(x, A.div_total);
+      const uint32_t q = fast_div(x, A.div_total);
       const uint32_t c = x - q * A.total;
       const u32x4* src = (const u32x4*)A.src[0];
       const f32x4* add = (const f32x4*)A.addend[0];

@@ -31,7 +31,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "lce_kernel_args.h"
+#include "lce_kernels_common.h"
 
 namespace lce {
 
@@ -77,8 +77,6 @@ unsigned pool_vec_grid(uint64_t total_chunks);
 namespace lce {
 using namespace lce_dev;
 
-LCE_DEVICE uint32_t pool_div(uint32_t n, FastDiv d) { return d.magic == 0u ? n : (mulhi_u32(n, d.magic) >> d.shift); }
-
 // v_mov_b32 quad_perm:[1,0,3,2]: the value of the neighbouring lane (lane ^ 1).  Every lane of the wave must be active.
 LCE_DEVICE uint32_t pool_neighbour(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
 
@@ -97,10 +95,10 @@ struct PoolWindow {
   int32_t ys, xs;
 };
 LCE_DEVICE PoolWindow pool_window(const PoolArgs& A, uint32_t pixel, bool ok) {
-  const uint32_t row = pool_div(pixel, A.div_ow);                  // b * OH + oy
+  const uint32_t row = fast_div(pixel, A.div_ow);                  // b * OH + oy
   const int32_t ox = (int32_t)(pixel - row * (uint32_t)A.OW);
   PoolWindow w;
-  w.b = pool_div(row, A.div_oh);
+  w.b = fast_div(row, A.div_oh);
   const int32_t oy = (int32_t)(row - w.b * (uint32_t)A.OH);
   const int32_t ys = oy * A.sh - A.ph, xs = ox * A.sw - A.pw;
   w.y0 = ys < 0 ? 0 : ys;
@@ -183,7 +181,7 @@ pool_vec(const PoolArgs A) {
     const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
     const bool ok = g < A.total;
     const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = pool_div(x, A.div_per_pixel);
+    const uint32_t q = fast_div(x, A.div_per_pixel);
     const uint32_t c = x - q * cpp;
     const PoolWindow w = pool_window(A, pix0 + q, ok);
     const int32_t count = (w.y1 - w.y0) * (w.x1 - w.x0);

@@ -52,7 +52,7 @@ void launch(unsigned gx, unsigned gy, F kernel) {
 
 // d: batch, in_height, in_width, channels_in, channels_out, filter_height, filter_width, stride_height, stride_width, out_height,
 // out_width, activation.  `cap`: the most blocks per launch (the product caps its grids at 2048; a small cap makes the kernels
-// stride).  Returns 1 when the interior took the 16-byte load path.
+// stride).  Returns bit 0: the interior took the 16-byte load path; bit 1: the border launch ran.
 extern "C" int lce_hostsim_conv2d(const int32_t* d, const float* in, const float* filter, const float* bias, float* out, int32_t* bits,
                                   int32_t cap) {
   lce::Conv2dArgs a;
@@ -78,5 +78,5 @@ extern "C" int lce_hostsim_conv2d(const int32_t* d, const float* in, const float
     if (a.bits) launch(gx, 1, [&] { lce::conv2d_border<true>(a); });
     else launch(gx, 1, [&] { lce::conv2d_border<false>(a); });
   }
-  return vec ? 1 : 0;
+  return (vec ? 1 : 0) | (a.Mb > 0 ? 2 : 0);
 }

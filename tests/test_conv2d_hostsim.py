@@ -46,7 +46,7 @@ def placed(a, offset):
 
 
 def sim(x, w, bias, stride, padding, act, want_out=True, want_bits=True, cap=3, offset=0):
-    """(out, bits, took the 16-byte path); an output that was not asked for keeps its marks."""
+    """(out, bits, took the 16-byte path, ran the border launch); an output that was not asked for keeps its marks."""
     st = (stride, stride) if isinstance(stride, int) else tuple(stride)
     x, w = placed(x, offset), placed(w, offset)
     oh, ow = R.out_and_pad(x.shape[1], w.shape[1], st[0], padding)[0], R.out_and_pad(x.shape[2], w.shape[2], st[1], padding)[0]
@@ -54,9 +54,9 @@ def sim(x, w, bias, stride, padding, act, want_out=True, want_bits=True, cap=3, 
     out = np.full((x.shape[0], oh, ow, w.shape[0]), OUT_MARK, np.float32)
     bits = np.full((x.shape[0], oh, ow, (w.shape[0] + 31) // 32), BITS_MARK, np.int32)
     b = None if bias is None else np.ascontiguousarray(bias, np.float32)
-    vec = lib().lce_hostsim_conv2d(d, x.ctypes.data, w.ctypes.data, None if b is None else b.ctypes.data,
+    ran = lib().lce_hostsim_conv2d(d, x.ctypes.data, w.ctypes.data, None if b is None else b.ctypes.data,
                                    out.ctypes.data if want_out else None, bits.ctypes.data if want_bits else None, cap)
-    return out, bits, bool(vec)
+    return out, bits, bool(ran & 1), bool(ran & 2)
 
 
 def agree(got, want):
@@ -67,12 +67,15 @@ def agree(got, want):
 @pytest.mark.parametrize("name", sorted(KNOWN))
 def test_the_known_answers(name):
     x, w, bias, kw, want = known_case(name)
-    out, bits, _ = sim(x, w, bias, kw["stride"], kw["padding"], R.NONE)
+    out, bits, _, _ = sim(x, w, bias, kw["stride"], kw["padding"], R.NONE)
     assert np.array_equal(out.view(np.uint32), want.view(np.uint32)) and np.array_equal(bits, O.bitpack(want)), (out, want)
 
 
-# (filter, Cin): K = 1, 27, 24 and 36 (the 16-byte path; 36 ends a chunk inside a tap), 147 and 297 (several chunks), 15
-@pytest.mark.parametrize("filt,cin", [((1, 1), 1), ((3, 3), 3), ((2, 3), 4), ((3, 3), 4), ((7, 7), 3), ((3, 3), 33), ((1, 5), 3)])
+# (filter, Cin): K = 1, 27, 24 and 36 (the 16-byte path; 36 ends a chunk inside a tap), 147 and 297 (several chunks), 15; and
+# 1x1 filters, for which the interior launch is the whole call: K = 4 (the 16-byte path, one short chunk), 33 (the dword path,
+# ends inside a chunk), 68 (the 16-byte path, two full chunks and a tail)
+@pytest.mark.parametrize("filt,cin", [((1, 1), 1), ((3, 3), 3), ((2, 3), 4), ((3, 3), 4), ((7, 7), 3), ((3, 3), 33), ((1, 5), 3),
+                                      ((1, 1), 4), ((1, 1), 33), ((1, 1), 68)])
 @pytest.mark.parametrize("special", [False, True])
 def test_the_kernel_bodies_give_the_reference_bytes(filt, cin, special):
     w, bias = grid_operands(filt, cin, 160 if not special else 33, special)
@@ -89,8 +92,9 @@ def test_the_kernel_bodies_give_the_reference_bytes(filt, cin, special):
                     b = bias[:cout] if with_bias else None
                     want = R.finish(t[..., :cout], b, act)
                     outs = (dict(), dict(want_out=False), dict(want_bits=False))[n % 3]
-                    out, bits, vec = sim(x, w[:cout], b, stride, padding, act, offset=offset, **outs)
+                    out, bits, vec, border = sim(x, w[:cout], b, stride, padding, act, offset=offset, **outs)
                     assert vec == (cin % 4 == 0 and offset == 0)
+                    assert not (border and filt == (1, 1)), "a 1x1 filter has no clipped window: one launch"
                     vecs += vec
                     assert agree(out, want) if outs.get("want_out", True) else (out == OUT_MARK).all(), (image, stride, padding, cout, n)
                     assert np.array_equal(bits, O.bitpack(want)) if outs.get("want_bits", True) else (bits == BITS_MARK).all(), (image, stride, padding, cout, n)
@@ -108,5 +112,5 @@ def test_more_tiles_than_one_pass_of_a_capped_grid(kind):
     else:
         x, (w, bias) = float_fixture((1, 20, 20, 1), 5), grid_operands((1, 41), 1, 33)
     want = R.conv2d(x, w, bias, (1, 1), R.SAME, R.RELU)
-    out, bits, _ = sim(x, w, bias, 1, R.SAME, R.RELU, cap=2)
+    out, bits, _, _ = sim(x, w, bias, 1, R.SAME, R.RELU, cap=2)
     assert agree(out, want) and np.array_equal(bits, O.bitpack(want))

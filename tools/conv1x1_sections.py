@@ -13,7 +13,10 @@ tests/test_conv1x1_sections_host.py:
      Interpreter.run_section with the NumPy test references on the host for every operator outside the sections, with the
      host's share of that time: a check that the bytes agree and the cost of THIS project's host path, not of a TensorFlow
      Lite host.
-usage: conv1x1_sections.py [--iters N] [--rounds R] [--quick] [--kernel-only]   (--quick: for a run under rocprofv3 --kernel-trace)"""
+  --shift-input: part 1 alone, at 28x28 64 -> 128 alone, with every input one float past a 16-byte boundary, which takes the
+  entry to its dword load path (torch is not run on such memory).
+usage: conv1x1_sections.py [--iters N] [--rounds R] [--quick] [--kernel-only] [--shift-input]
+       (--quick: for a run under rocprofv3 --kernel-trace)"""
 import argparse
 import ctypes as C
 import importlib
@@ -70,15 +73,19 @@ def graph_time(fn, sets, iters):
     return a.elapsed_time(b) * 1e3 / (iters * sets)
 
 
-def kernel_rows(iters, rounds, batch=256):
+def kernel_rows(iters, rounds, batch=256, shift=False):
     lines = []
     gen = torch.Generator(device=DEV).manual_seed(7)
-    for h, cin, cout in SHAPES:
+    for h, cin, cout in SHAPES[:1] if shift else SHAPES:
         m = batch * h * h
         nbytes = (m * cin + cout * cin + m * cout) * 4
         bound_mem, bound_mat = nbytes / HBM * 1e6, 2.0 * m * cout * cin / MATRIX_F32 * 1e6
         sets = max(2, math.ceil(2 * CACHE / nbytes) + 1)
-        xs = [torch.randn((batch, h, h, cin), device=DEV, generator=gen) for _ in range(sets)]
+        if shift:                                                        # (allocations are 16-byte aligned: one float behind)
+            xs = [torch.randn((m * cin + 1,), device=DEV, generator=gen)[1:].view(batch, h, h, cin) for _ in range(sets)]
+            assert all(x.data_ptr() % 16 == 4 for x in xs)
+        else:
+            xs = [torch.randn((batch, h, h, cin), device=DEV, generator=gen) for _ in range(sets)]
         w = torch.randn((cout, cin), device=DEV, generator=gen) * 0.1
         bias = torch.randn((cout,), device=DEV, generator=gen)
         outs = [torch.empty((batch, h, h, cout), device=DEV) for _ in range(sets)]
@@ -94,6 +101,9 @@ def kernel_rows(iters, rounds, batch=256):
         how = "HIP graph"
         for _ in range(rounds):                                          # A-B-A-B; the bits variant rides along as a third leg
             ours.append(graph_time(lambda i, st: conv_into(desc, xs[i], w, bias, outs[i], None, st), sets, iters))
+            if shift:
+                with_bits.append(graph_time(lambda i, st: conv_into(desc, xs[i], w, bias, outs[i], bits[i], st), sets, iters))
+                continue
             try:
                 theirs.append(graph_time(torch_conv, sets, iters))
             except Exception as e:                                       # (a library that cannot be captured: eager, device events)
@@ -112,10 +122,13 @@ def kernel_rows(iters, rounds, batch=256):
         name = "256x%dx%d %d->%d" % (h, h, cin, cout)
         bound = max(bound_mem, bound_mat)
         for label, t in (("lce_hip_conv1x1_f32, float only  ", ours), ("lce_hip_conv1x1_f32, float + bits", with_bits),
-                         ("torch conv2d fp32, %-15s" % how, theirs)):
+                         ("torch conv2d fp32, %-15s" % how, theirs))[:2 if shift else 3]:
             med = statistics.median(t)
             lines.append("kernel  %-22s %s median %8.1f us  (min %.1f, max %.1f over %d rounds)  %5.1f TF  %5.2f TB/s  bound / time %.3f"
                          % (name, label, med, min(t), max(t), rounds, 2.0 * m * cout * cin / med / 1e6, nbytes / med / 1e6, bound / med))
+        if shift:
+            lines.append("kernel  %-22s the input one float past a 16-byte boundary (the dword load path); %d operand sets" % (name, sets))
+            continue
         conv_into(desc, xs[0], w, bias, outs[0], None, torch.cuda.current_stream(DEV).cuda_stream)
         ref = torch.nn.functional.conv2d(nchw[0], w4, bias).permute(0, 2, 3, 1)
         ratio = statistics.median(ours) / statistics.median(theirs)
@@ -214,13 +227,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--shift-input", action="store_true")
     a = ap.parse_args()
     iters = 2 if a.quick else a.iters
     rounds = 1 if a.quick else max(3, a.rounds)
     print("device:", torch.cuda.get_device_name(DEV))
-    for line in kernel_rows(iters, rounds):
+    for line in kernel_rows(iters, rounds, shift=a.shift_input):
         print(line, flush=True)
-    if not a.kernel_only:
+    if not a.kernel_only and not a.shift_input:
         for name in sorted(FIXTURES):
             for line in fixture_rows(name, max(4, iters // 2)):
                 print(line, flush=True)
