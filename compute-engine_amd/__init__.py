@@ -39,6 +39,8 @@ ABI_SYMBOLS = (
     "lce_hip_bitpacked_size", "lce_hip_bitpack", "lce_hip_unpack", "lce_hip_elementwise",
     "lce_hip_elementwise_ex", "lce_hip_elementwise_grid_cap",
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
+    "lce_hip_elementwise_i8_check", "lce_hip_elementwise_i8_table_size", "lce_hip_elementwise_i8_prepare", "lce_hip_elementwise_i8",
+    "lce_hip_elementwise_i8_path", "lce_hip_elementwise_i8_forced",
     "lce_hip_concat", "lce_hip_join_windows", "lce_hip_join_windows_check", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
     "lce_hip_conv2d_i8", "lce_hip_conv2d_i8_check", "lce_hip_conv2d_i8_prepare",
@@ -67,6 +69,8 @@ JOIN_MAX_WINDOWS = 8                                    # LCE_HIP_JOIN_MAX_WINDO
 POOL_MAX, POOL_AVERAGE = 0, 1                           # lce_hip_pool_op
 POOL_MAX_TAPS = 65536                                   # LCE_HIP_POOL_MAX_TAPS
 ADD_INT8_LITERAL, ADD_INT8_SPLIT, ADD_INT8_SHIFT = 0, 1, 2   # lce_hip_add_int8_variant_id
+EW_I8_ADD, EW_I8_PRELU, EW_I8_CLAMP, EW_I8_REQUANTIZE = 0, 1, 2, 3   # lce_hip_ew_i8_op
+EW_I8_PATH_LDS, EW_I8_PATH_GLOBAL, EW_I8_PATH_ONE_ROW = 0, 1, 2      # lce_hip_elementwise_i8_path_id
 
 
 class LceHipError(RuntimeError):
@@ -107,6 +111,27 @@ class AddInt8Params(C.Structure):
     """``lce_hip_add_int8_params``."""
     _fields_ = [(n, C.c_int32) for n in ("left_shift", "in1_multiplier", "in1_shift", "in2_multiplier", "in2_shift",
                                          "out_multiplier", "out_shift", "act_min", "act_max")]
+
+
+class EwI8Step(C.Structure):
+    """``lce_hip_ew_i8_step``."""
+    _fields_ = [("op", C.c_int32), ("operand", C.c_int32), ("values", C.c_void_p), ("operand_scale", C.c_float),
+                ("operand_zero_point", C.c_int32), ("out_scale", C.c_float), ("out_zero_point", C.c_int32), ("activation", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class EwI8Desc(C.Structure):
+    """``lce_hip_elementwise_i8_desc``."""
+    _fields_ = [("channels", C.c_int32), ("in_scale", C.c_float), ("in_zero_point", C.c_int32), ("has_head", C.c_int32),
+                ("addend_scale", C.c_float), ("addend_zero_point", C.c_int32), ("head_scale", C.c_float),
+                ("head_zero_point", C.c_int32), ("head_activation", C.c_int32), ("num_steps", C.c_int32),
+                ("steps", EwI8Step * EW_MAX_STEPS), ("reserved", C.c_int32 * 2)]
+
+
+class EwI8Launch(C.Structure):
+    """``lce_hip_elementwise_i8_launch``."""
+    _fields_ = [(n, C.c_int32) for n in ("path", "flat", "lds_max_channels", "blocks", "waves_per_block", "lds_bytes", "head_variant",
+                                         "table_rows")]
 
 
 class Pool2dDesc(C.Structure):
@@ -218,6 +243,14 @@ def lib() -> C.CDLL:
                                        C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_add_int8_forced.argtypes = [C.POINTER(AddInt8Desc), C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_elementwise_i8_check.argtypes = [C.POINTER(EwI8Desc)]
+        l.lce_hip_elementwise_i8_table_size.argtypes = [C.POINTER(EwI8Desc), C.POINTER(C.c_size_t)]
+        l.lce_hip_elementwise_i8_prepare.argtypes = [C.POINTER(EwI8Desc), C.c_void_p]
+        l.lce_hip_elementwise_i8.argtypes = [C.POINTER(EwI8Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]
+        l.lce_hip_elementwise_i8_path.argtypes = [C.POINTER(EwI8Desc), C.c_size_t] + [C.c_void_p] * 5 + [C.c_int32, C.POINTER(EwI8Launch)]
+        l.lce_hip_elementwise_i8_forced.argtypes = [C.POINTER(EwI8Desc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_concat.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_size_t, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_join_windows.argtypes = [C.c_int, C.POINTER(Window), C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -791,6 +824,143 @@ def add_int8(x1, x2, q1, q2, q_out, activation=ACT_NONE, out=None, out_bits=None
         else:
             check(lib().lce_hip_add_int8_forced(C.byref(desc), int(variant), *args))
     return _results(host, out_d, bits_d, out, out_bits)
+
+
+def _ew_i8_q(who, name, q):
+    if not isinstance(q, (list, tuple)) or len(q) != 2:
+        raise ValueError("%s: %s must be (scale, zero_point), got %r" % (who, name, q))
+    if int(q[1]) != q[1]:
+        raise ValueError("%s: %s zero point must be an integer, got %r" % (who, name, q[1]))
+    return float(q[0]), int(q[1])
+
+
+def _ew_i8_desc(who, channels, q_in, steps, head):
+    """``lce_hip_elementwise_i8_desc`` of a chain and the host arrays its ``values`` point into (keep them alive as long as the
+    descriptor).  Shapes and kinds are checked here; the numbers are the library's to refuse."""
+    channels = int(channels)
+    d = EwI8Desc()
+    d.channels = channels
+    d.in_scale, d.in_zero_point = _ew_i8_q(who, "q_in", q_in)
+    if head is not None:
+        if not isinstance(head, (list, tuple)) or len(head) not in (2, 3):
+            raise ValueError("%s: head must be (q_addend, q_out[, activation]), got %r" % (who, head))
+        d.has_head = 1
+        d.addend_scale, d.addend_zero_point = _ew_i8_q(who, "head q_addend", head[0])
+        d.head_scale, d.head_zero_point = _ew_i8_q(who, "head q_out", head[1])
+        d.head_activation = int(head[2]) if len(head) == 3 else ACT_NONE
+    steps = list(steps)
+    if len(steps) > EW_MAX_STEPS:
+        raise ValueError("%s: at most %d steps, got %d" % (who, EW_MAX_STEPS, len(steps)))
+    d.num_steps = len(steps)
+    keep = []
+    for k, st in enumerate(steps):
+        name = "step %d" % (k + 1)
+        if not isinstance(st, (list, tuple)) or not st or st[0] not in ("add", "prelu", "clamp", "requantize"):
+            raise ValueError("%s: %s must begin with 'add', 'prelu', 'clamp' or 'requantize', got %r" % (who, name, st))
+        kind = st[0]
+        want = {"add": 5, "prelu": 4, "clamp": 3, "requantize": 2}[kind]
+        if len(st) != want:
+            raise ValueError("%s: %s (%s) takes %d fields, got %d" % (who, name, kind, want, len(st)))
+        e = d.steps[k]
+        e.op = {"add": EW_I8_ADD, "prelu": EW_I8_PRELU, "clamp": EW_I8_CLAMP, "requantize": EW_I8_REQUANTIZE}[kind]
+        if kind in ("add", "prelu"):
+            v = np.asarray(st[1])
+            if v.dtype != np.int8 and not (v.dtype.kind in "iu" and v.size and -128 <= int(v.min()) and int(v.max()) <= 127):
+                raise ValueError("%s: %s operand must hold int8 values, got %s" % (who, name, v.dtype))
+            v = np.ascontiguousarray(v.astype(np.int8).reshape(-1))
+            if v.size == 1 and np.ndim(st[1]) == 0:
+                e.operand = EW_SCALAR
+            elif v.size == channels:
+                e.operand = EW_PER_CHANNEL
+            else:
+                raise ValueError("%s: %s operand must be a scalar or %d values, got shape %r" % (who, name, channels, np.shape(st[1])))
+            keep.append(v)
+            e.values = v.ctypes.data
+            e.operand_scale, e.operand_zero_point = _ew_i8_q(who, name + " operand quantization", st[2])
+            e.out_scale, e.out_zero_point = _ew_i8_q(who, name + " q_out", st[3])
+            e.activation = int(st[4]) if kind == "add" else ACT_NONE
+        else:
+            e.out_scale, e.out_zero_point = _ew_i8_q(who, name + " q_out", st[1])
+            e.activation = int(st[2]) if kind == "clamp" else ACT_NONE
+    return d, keep
+
+
+def elementwise_i8_prepare(channels, q_in, steps, head=None):
+    """The table of one int8 elementwise chain (``lce_hip_elementwise_i8_prepare``, host only): uint8 NumPy [R, 256] with
+    R = ``channels``, or R = 1 when no step has a per-channel operand; ``table[c, v + 128]`` is the chain's int8 result, as a byte,
+    for the value v in channel c.  ``q_in``: (scale, zero_point) of the input.  ``steps``: 1..8 of
+    ``("add", values, q_operand, q_out, act)``, ``("prelu", alpha, q_alpha, q_out)``, ``("clamp", q_out, act)`` and
+    ``("requantize", q_out)`` -- ``values`` / ``alpha`` a Python or NumPy scalar (SCALAR) or ``channels`` int8 values (PER_CHANNEL),
+    every q a (scale, zero_point), ``act`` an ``ACT_*``; each step's ``q_out`` is the next step's input quantization.  ``head``:
+    None, or ``(q_addend, q_out[, act])`` of a tensor + tensor ADD in front of the steps (``add_int8``'s arithmetic), whose sum the
+    steps then take.  TFLite's integer arithmetic, byte for byte (include/lce_hip.h).  Raises ``LceHipError`` naming the step the
+    library refuses."""
+    d, keep = _ew_i8_desc("elementwise_i8_prepare", channels, q_in, steps, head)
+    n = C.c_size_t()
+    check(lib().lce_hip_elementwise_i8_table_size(C.byref(d), C.byref(n)))
+    table = np.zeros((n.value // 256, 256), np.uint8)
+    check(lib().lce_hip_elementwise_i8_prepare(C.byref(d), _host_ptr(table)))
+    del keep
+    return table
+
+
+def _ew_i8_check(x, table, addend, head, out, out_bits):
+    """Argument checks of ``elementwise_i8`` on shapes and dtypes only (NumPy or torch): nothing here touches a device."""
+    who = "elementwise_i8"
+    shape = tuple(x.shape)
+    if _dtype_name(x) != "int8" or len(shape) < 1:
+        raise ValueError("%s: x must be an int8 tensor with a channel axis, got %s %r" % (who, x.dtype, shape))
+    if (addend is None) != (head is None):
+        raise ValueError("%s: addend and head come together" % who)
+    if addend is not None and (_dtype_name(addend) != "int8" or tuple(addend.shape) != shape):
+        raise ValueError("%s: addend must be int8 of x's shape %r, got %s %r" % (who, shape, addend.dtype, tuple(addend.shape)))
+    if _dtype_name(table) != "uint8" or len(table.shape) != 2 or table.shape[1] != 256 or table.shape[0] not in (1, shape[-1]):
+        raise ValueError("%s: table must be uint8 [1 or %d, 256] (elementwise_i8_prepare), got %s %r" % (who, shape[-1], table.dtype,
+                                                                                                       tuple(table.shape)))
+    _check_outputs(who, out, out_bits, "int8", shape)
+
+
+def elementwise_i8(x, table, q_in, steps, addend=None, head=None, out=None, out_bits=None, stream: int | None = None,
+                   path: int | None = None, report_launch: bool = False):
+    """One int8 elementwise chain between binary layers -- the tail of an int8 ReActNet block (residual ADD, per-channel shift,
+    PRELU, shift), a standalone RELU, an int8 requantize -- and the LceQuantize of its result at the last step's zero point, in one
+    launch (``lce_hip_elementwise_i8``).  ``x``: int8 [..., C] on the device (or NumPy: copied to cuda:0 and back).  ``table``:
+    ``elementwise_i8_prepare``'s for the same ``channels``, ``q_in``, ``steps`` and ``head`` (NumPy or on the device).
+    ``addend`` with ``head``: the second tensor of a head ADD.  ``out``: an int8 tensor to fill (may be ``x`` or ``addend``), None
+    for a new one, False for none.  ``out_bits``: an int32 [..., ceil(C/32)] tensor to fill, True for a new one, None for none.
+    ``path``: None for the entry's choice, or an ``EW_I8_PATH_*`` to force (for tests and measurements; the bytes are the same).
+    Returns ``(out, out_bits)``, and with ``report_launch`` a third value: the ``lce_hip_elementwise_i8_launch`` of the call as a
+    dict."""
+    import torch
+    who = "elementwise_i8"
+    _ew_i8_check(x, table, addend, head, out, out_bits)
+    d, keep = _ew_i8_desc(who, x.shape[-1], q_in, steps, head)
+    if path not in (None, EW_I8_PATH_LDS, EW_I8_PATH_GLOBAL, EW_I8_PATH_ONE_ROW):
+        raise ValueError("%s: unknown path %r" % (who, path))
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x's")
+    a = on_dev(x)
+    b = None if addend is None else on_dev(addend)
+    t = on_dev(table)
+    channels = x.shape[-1]
+    rows = a.numel() // channels if channels else 0
+    out_d = None if out is False else torch.empty_like(a) if out is None else on_dev(out)
+    bits_d = None if out_bits is None else _new_bits(a.shape[:-1], channels, dev) if out_bits is True else on_dev(out_bits)
+    launch = EwI8Launch()
+    with torch.cuda.device(dev):
+        st = C.c_void_p(_stream_or_current(stream, dev))
+        if report_launch and rows and channels:
+            check(lib().lce_hip_elementwise_i8_path(C.byref(d), rows, _dev_ptr(a), _dev_ptr(b), _dev_ptr(t), _dev_ptr(out_d), _dev_ptr(bits_d),
+                                                    -1 if path is None else int(path), C.byref(launch)))
+        if path is None:
+            check(lib().lce_hip_elementwise_i8(C.byref(d), _dev_ptr(a), _dev_ptr(b), _dev_ptr(t), rows, _dev_ptr(out_d), _dev_ptr(bits_d), st))
+        else:
+            check(lib().lce_hip_elementwise_i8_forced(C.byref(d), int(path), _dev_ptr(a), _dev_ptr(b), _dev_ptr(t), rows, _dev_ptr(out_d),
+                                                      _dev_ptr(bits_d), st))
+    del keep
+    res = _results(host, out_d, bits_d, out, out_bits)
+    return (*res, {n: int(getattr(launch, n)) for n, _ in EwI8Launch._fields_}) if report_launch else res
 
 
 def _concat_check(tensors, out, out_bits, zero_point):

@@ -19,6 +19,7 @@
 #include "lce_kernel_types.h"    // the convolution kernels live in their own translation units (lce_tu_*.hip)
 #include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip, lce_tu_eltwise_ex.hip)
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
+#include "lce_kernels_eltwise_i8_chain.h"   // (lce_tu_eltwise_i8_chain.hip)
 #include "lce_kernels_join.h"        // (lce_tu_join.hip)
 #include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
 #include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
@@ -48,6 +49,7 @@
 #include "lce_tu_eltwise.hip"
 #include "lce_tu_eltwise_ex.hip"
 #include "lce_tu_eltwise_i8.hip"
+#include "lce_tu_eltwise_i8_chain.hip"
 #include "lce_tu_join.hip"
 #include "lce_tu_pool.hip"
 #include "lce_tu_conv1x1.hip"
@@ -928,6 +930,304 @@ lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_
                                        int32_t* out_bits_dev, void* stream) {
   if (variant < 0) return fail(LCE_HIP_ERR_INVALID, "lce_hip_add_int8_forced: unknown variant %d", (int)variant);
   return add_int8_run(desc, variant, in1_dev, in2_dev, rows, channels, out_dev, out_bits_dev, stream, "lce_hip_add_int8_forced");
+}
+
+// ------------------------------------------------------------------------------------
+// int8 elementwise chain (lce_kernels_eltwise_i8_chain.h)
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+const char* const kEwI8OpNames[4] = {"ADD", "PRELU", "CLAMP", "REQUANTIZE"};
+// The entry's rule, from profiles/elementwise_i8/chains.txt (batch 256, a ReActNet tail): the LDS path from 128 channels up to what
+// fits (it takes 0.90 / 0.60 / 0.77 of the global path's time at 128 / 256 / 512 channels), the global path below (at 64 channels the
+// LDS path takes 1.09 of its time: few rows, so the lanes of a group crowd onto few banks) and beyond.
+constexpr int32_t kEwI8LdsFromChannels = 128;
+
+// What the host derives from one step: the function of (value, constant) it is.
+struct EwI8StepFn {
+  int32_t op = 0, zi = 0, zo = 0, za = 0, lo = -128, hi = 127;
+  int32_t m1 = 0, e1 = 0, m2 = 0, e2 = 0;                // PRELU: positive / negative side; CLAMP, REQUANTIZE: (m1, e1)
+  lce::AddI8Args add;                                    // ADD: the literal formula's parameters
+};
+
+int32_t ew_i8_mbqm(int32_t x, int32_t m, int32_t e) {    // MultiplyByQuantizedMultiplier
+  const int32_t left = e > 0 ? e : 0, right = e > 0 ? 0 : -e;
+  return lce::add_i8_rdivpot(lce::add_i8_srdhm((int32_t)((int64_t)x * ((int64_t)1 << left)), m), right);
+}
+
+int32_t ew_i8_eval(const EwI8StepFn& f, int32_t v, int32_t k) {
+  int32_t raw;
+  switch (f.op) {
+    case LCE_HIP_EW_I8_ADD: return lce::add_i8_value<lce::kAddI8Literal>(f.add, v, k) + f.zo;
+    case LCE_HIP_EW_I8_PRELU: {
+      const int32_t d = v - f.zi;
+      raw = (d >= 0 ? ew_i8_mbqm(d, f.m1, f.e1) : ew_i8_mbqm(d * (k - f.za), f.m2, f.e2)) + f.zo;
+      break;
+    }
+    default: raw = ew_i8_mbqm(v - f.zi, f.m1, f.e1) + f.zo;
+  }
+  return std::min(f.hi, std::max(f.lo, raw));
+}
+
+lce_hip_status ew_i8_quant(const char* who, const char* what, float scale, int32_t zp) {
+  if (!std::isfinite(scale) || !(scale > 0.0f))
+    return fail(LCE_HIP_ERR_INVALID, "%s: %s_scale must be finite and positive, got %g", who, what, (double)scale);
+  if (zp < -128 || zp > 127) return fail(LCE_HIP_ERR_INVALID, "%s: %s_zero_point must be in [-128, 127], got %d", who, what, (int)zp);
+  return LCE_HIP_OK;
+}
+
+// (m, e) of a PRELU / CLAMP / REQUANTIZE real multiplier, and the check that x * 2^e stays in int32 for |x| <= max_abs
+lce_hip_status ew_i8_multiplier(const char* who, double real, int64_t max_abs, int32_t* m, int32_t* e) {
+  if (!std::isfinite(real) || !(real > 0.0)) return fail(LCE_HIP_ERR_INVALID, "%s: the real multiplier is %g, not finite and positive", who, real);
+  quantize_multiplier(real, m, e);
+  if (*e > 30 || (*e > 0 && (max_abs << *e) > (int64_t)INT32_MAX))
+    return fail(LCE_HIP_ERR_INVALID, "%s: an intermediate could leave int32 (|x| up to %lld times 2^%d)", who, (long long)max_abs, (int)*e);
+  return LCE_HIP_OK;
+}
+
+void ew_i8_add_args(const lce_hip_add_int8_desc& d, const lce_hip_add_int8_params& p, lce::AddI8Args* a) {
+  memset(a, 0, sizeof *a);
+  a->z1 = d.in1_zero_point; a->m1 = p.in1_multiplier; a->n1 = -p.in1_shift;
+  a->z2 = d.in2_zero_point; a->m2 = p.in2_multiplier; a->n2 = -p.in2_shift;
+  a->zo = d.out_zero_point; a->mo = p.out_multiplier; a->no = -p.out_shift;
+  a->lo = p.act_min; a->hi = p.act_max;
+}
+
+struct EwI8Plan {
+  int32_t table_rows = 1;                                // R
+  int32_t zo_last = 0;
+  EwI8StepFn fn[LCE_HIP_EW_I8_MAX_STEPS];
+  lce_hip_add_int8_desc head;
+};
+
+// Every check of the descriptor; `who` is the entry's name.  The operand values are not read.
+lce_hip_status ew_i8_plan(const lce_hip_elementwise_i8_desc* d, const char* who, EwI8Plan* P) {
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (d->channels < 0 || d->channels >= (1 << 22)) return fail(LCE_HIP_ERR_INVALID, "%s: channels must be in [0, 2^22), got %d", who, (int)d->channels);
+  if (d->reserved[0] || d->reserved[1]) return fail(LCE_HIP_ERR_INVALID, "%s: non-zero reserved field", who);
+  if (d->has_head != 0 && d->has_head != 1) return fail(LCE_HIP_ERR_INVALID, "%s: has_head must be 0 or 1, got %d", who, (int)d->has_head);
+  if (d->num_steps < 1 || d->num_steps > LCE_HIP_EW_I8_MAX_STEPS)
+    return fail(LCE_HIP_ERR_INVALID, "%s: num_steps must be 1..%d, got %d%s", who, LCE_HIP_EW_I8_MAX_STEPS, (int)d->num_steps,
+                d->has_head && d->num_steps == 0 ? " (a head with no steps is lce_hip_add_int8's job)" : "");
+  if (lce_hip_status s = ew_i8_quant(who, "in", d->in_scale, d->in_zero_point)) return s;
+  char name[160];
+  float si = d->in_scale;
+  int32_t zi = d->in_zero_point;
+  if (d->has_head) {
+    snprintf(name, sizeof name, "%s: head", who);
+    P->head = lce_hip_add_int8_desc{d->in_scale, d->in_zero_point, d->addend_scale, d->addend_zero_point, d->head_scale,
+                                    d->head_zero_point, d->head_activation};
+    lce_hip_add_int8_params p;
+    if (lce_hip_status s = add_int8_params(&P->head, &p, name)) return s;
+    si = d->head_scale;
+    zi = d->head_zero_point;
+  }
+  P->table_rows = 1;
+  for (int k = 0; k < d->num_steps; ++k) {
+    const lce_hip_ew_i8_step& st = d->steps[k];
+    EwI8StepFn& f = P->fn[k];
+    f = EwI8StepFn();
+    if (st.op < 0 || st.op > LCE_HIP_EW_I8_REQUANTIZE) return fail(LCE_HIP_ERR_INVALID, "%s: step %d: unknown op %d", who, k + 1, (int)st.op);
+    snprintf(name, sizeof name, "%s: step %d (%s)", who, k + 1, kEwI8OpNames[st.op]);
+    const bool has_operand = st.op == LCE_HIP_EW_I8_ADD || st.op == LCE_HIP_EW_I8_PRELU;
+    if (st.reserved[0] || st.reserved[1]) return fail(LCE_HIP_ERR_INVALID, "%s: non-zero reserved field", name);
+    if (st.operand != LCE_HIP_EW_SCALAR && !(has_operand && st.operand == LCE_HIP_EW_PER_CHANNEL))
+      return fail(LCE_HIP_ERR_INVALID, "%s: operand kind %d (%s)", name, (int)st.operand,
+                  has_operand ? "SCALAR or PER_CHANNEL" : "this op takes no operand: 0");
+    if (st.activation < LCE_HIP_ACT_NONE || st.activation > LCE_HIP_ACT_RELU6) return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", name, (int)st.activation);
+    if ((st.op == LCE_HIP_EW_I8_PRELU || st.op == LCE_HIP_EW_I8_REQUANTIZE) && st.activation != LCE_HIP_ACT_NONE)
+      return fail(LCE_HIP_ERR_INVALID, "%s: the activation must be NONE, got %d", name, (int)st.activation);
+    if (lce_hip_status s = ew_i8_quant(name, "out", st.out_scale, st.out_zero_point)) return s;
+    if (has_operand) {
+      if (lce_hip_status s = ew_i8_quant(name, "operand", st.operand_scale, st.operand_zero_point)) return s;
+      if (st.operand == LCE_HIP_EW_PER_CHANNEL) P->table_rows = d->channels;
+    }
+    f.op = st.op; f.zi = zi; f.zo = st.out_zero_point; f.za = st.operand_zero_point;
+    const float so = st.out_scale;
+    if (st.op == LCE_HIP_EW_I8_ADD) {
+      const lce_hip_add_int8_desc ad{si, zi, st.operand_scale, st.operand_zero_point, so, st.out_zero_point, st.activation};
+      lce_hip_add_int8_params p;
+      if (lce_hip_status s = add_int8_params(&ad, &p, name)) return s;
+      ew_i8_add_args(ad, p, &f.add);
+    } else if (st.op == LCE_HIP_EW_I8_PRELU) {
+      const float r1 = si / so;
+      volatile float sisa = si * st.operand_scale;         // float32, left to right
+      const float r2 = sisa / so;
+      if (lce_hip_status s = ew_i8_multiplier(name, (double)r1, 255, &f.m1, &f.e1)) return s;
+      if (lce_hip_status s = ew_i8_multiplier(name, (double)r2, 255 * 255, &f.m2, &f.e2)) return s;
+    } else if (st.op == LCE_HIP_EW_I8_CLAMP) {
+      const float r = si / so;
+      if (lce_hip_status s = ew_i8_multiplier(name, (double)r, 255, &f.m1, &f.e1)) return s;
+      quantized_activation_range(st.activation, so, st.out_zero_point, &f.lo, &f.hi);
+    } else {
+      if (lce_hip_status s = ew_i8_multiplier(name, (double)si / (double)so, 255, &f.m1, &f.e1)) return s;
+    }
+    si = so;
+    zi = st.out_zero_point;
+  }
+  P->zo_last = zi;
+  return LCE_HIP_OK;
+}
+
+struct EwI8Launch {
+  lce::EwI8Args args;
+  int head, path;
+  bool flat;
+  unsigned blocks, threads, lds_bytes;
+  int32_t lds_max_channels;
+};
+
+// The launch of one call: path, layout, grid.  `forced` < 0: the entry's rule.  Nothing here touches a device.
+lce_hip_status ew_i8_launch(const lce_hip_elementwise_i8_desc* desc, int32_t forced, const int8_t* in_dev, const int8_t* addend_dev,
+                            const uint8_t* table_dev, size_t rows, const int8_t* out_dev, const int32_t* out_bits_dev, const char* who,
+                            bool need_pointers, const EwI8Plan& P, EwI8Launch* L) {
+  const uint32_t channels = (uint32_t)desc->channels;
+  lce::EwI8Args& E = L->args;
+  memset(&E, 0, sizeof E);
+  L->head = lce::kEwI8NoHead;
+  const int8_t *in1 = in_dev, *in2 = nullptr;
+  if (desc->has_head) {
+    PreparedAddI8 H;
+    if (lce_hip_status s = prepared_add_int8(&P.head, &H, who)) return s;
+    E.A = H.args;
+    E.A.c = H.c_for[H.variant];
+    L->head = H.variant;
+    in1 = H.swapped ? addend_dev : in_dev;
+    in2 = H.swapped ? in_dev : addend_dev;
+  }
+  if (need_pointers) {
+    if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+    if (!in_dev || !table_dev || (desc->has_head && !addend_dev)) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+    if (!desc->has_head && addend_dev) return fail(LCE_HIP_ERR_INVALID, "%s: an addend without a head", who);
+  }
+  if ((uintptr_t)table_dev % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: table_dev must be 4-byte aligned", who);
+  E.A.in1 = in1; E.A.in2 = in2;
+  E.A.out = const_cast<int8_t*>(out_dev);
+  E.A.bits = (uint32_t*)const_cast<int32_t*>(out_bits_dev);
+  E.A.rows = rows;
+  E.A.channels = channels;
+  E.A.wpr = (channels + 31u) / 32u;
+  E.table = table_dev;
+  E.zo_last = P.zo_last;
+  E.cpr = channels / 16u;
+  const bool aligned = ((uintptr_t)in_dev % 16 == 0) && ((uintptr_t)addend_dev % 16 == 0) && ((uintptr_t)out_dev % 16 == 0) &&
+                       ((uintptr_t)out_bits_dev % 4 == 0);
+  L->flat = channels % 32u == 0 && aligned;
+  const uint32_t lds_rows = lce::kEwI8LdsLimit / lce::kEwI8LdsPitch;
+  L->lds_max_channels = (int32_t)(L->flat ? lds_rows / 32u * 32u : lds_rows);
+  const bool one_row = P.table_rows == 1;
+  int path = one_row ? lce::kEwI8OneRow : (int32_t)channels >= kEwI8LdsFromChannels && (int32_t)channels <= L->lds_max_channels ? lce::kEwI8Lds : lce::kEwI8Global;
+  if (forced >= 0) {
+    if (forced >= lce::kEwI8Paths) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)forced);
+    if (forced == lce::kEwI8OneRow ? !one_row : (uint32_t)P.table_rows != channels)
+      return fail(LCE_HIP_ERR_INVALID, "%s: path %d cannot run a table of %d rows on %u channels (ONE_ROW takes one row, LDS and GLOBAL one per channel)",
+                  who, (int)forced, (int)P.table_rows, channels);
+    if (forced == lce::kEwI8Lds && (int32_t)channels > L->lds_max_channels)
+      return fail(LCE_HIP_ERR_INVALID, "%s: the LDS path takes at most %d channels on this layout, got %u", who, (int)L->lds_max_channels, channels);
+    path = forced;
+  }
+  L->path = path;
+  L->lds_bytes = path == lce::kEwI8Lds ? channels * lce::kEwI8LdsPitch : path == lce::kEwI8OneRow ? 256u : 0u;
+  L->threads = L->lds_bytes > lce::kEwI8WideBlockAbove ? 1024u : 256u;
+  // memory-bound streams: at most ~8 blocks of 4 waves per CU (as lce_tu_eltwise_i8.hip), fewer where the tables fill the LDS
+  const uint64_t wave_tasks = L->flat ? (rows * (uint64_t)E.A.wpr * 2ull + 255) / 256 : rows * (uint64_t)((channels + 63u) / 64u);
+  const uint64_t waves = L->threads / 64u;
+  uint64_t per_cu = 32u / waves;
+  if (L->lds_bytes) per_cu = std::max<uint64_t>(1, std::min<uint64_t>(per_cu, lce::kEwI8LdsLimit / L->lds_bytes));
+  const uint64_t blocks = (wave_tasks + waves - 1) / waves, cap = 256ull * per_cu;
+  L->blocks = (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+  return LCE_HIP_OK;
+}
+
+lce_hip_status ew_i8_run(const lce_hip_elementwise_i8_desc* desc, int32_t forced, const int8_t* in_dev, const int8_t* addend_dev,
+                         const uint8_t* table_dev, size_t rows, int8_t* out_dev, int32_t* out_bits_dev, void* stream, const char* who) {
+  EwI8Plan P;
+  if (lce_hip_status s = ew_i8_plan(desc, who, &P)) return s;
+  if (rows == 0 || desc->channels == 0) return LCE_HIP_OK;   // (an empty tensor may come with null pointers)
+  EwI8Launch L;
+  if (lce_hip_status s = ew_i8_launch(desc, forced, in_dev, addend_dev, table_dev, rows, out_dev, out_bits_dev, who, true, P, &L)) return s;
+  if (lce_hip_status s = require_device()) return s;
+  const int e = lce::launch_ew_i8(L.args, L.head, L.path, L.flat, L.blocks, L.threads, L.lds_bytes, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+}  // namespace
+extern "C" {
+
+lce_hip_status lce_hip_elementwise_i8_check(const lce_hip_elementwise_i8_desc* desc) {
+  EwI8Plan P;
+  return ew_i8_plan(desc, "lce_hip_elementwise_i8_check", &P);
+}
+
+lce_hip_status lce_hip_elementwise_i8_table_size(const lce_hip_elementwise_i8_desc* desc, size_t* bytes) {
+  if (!bytes) return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise_i8_table_size: null argument");
+  EwI8Plan P;
+  if (lce_hip_status s = ew_i8_plan(desc, "lce_hip_elementwise_i8_table_size", &P)) return s;
+  *bytes = (size_t)P.table_rows * 256u;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_elementwise_i8_prepare(const lce_hip_elementwise_i8_desc* desc, uint8_t* table_host) {
+  const char* who = "lce_hip_elementwise_i8_prepare";
+  EwI8Plan P;
+  if (lce_hip_status s = ew_i8_plan(desc, who, &P)) return s;
+  if (!table_host) return fail(LCE_HIP_ERR_INVALID, "%s: null table", who);
+  for (int k = 0; k < desc->num_steps; ++k)
+    if ((desc->steps[k].op == LCE_HIP_EW_I8_ADD || desc->steps[k].op == LCE_HIP_EW_I8_PRELU) && !desc->steps[k].values)
+      return fail(LCE_HIP_ERR_INVALID, "%s: step %d (%s): null values", who, k + 1, kEwI8OpNames[desc->steps[k].op]);
+  // a step with a SCALAR operand (or none) is the same function in every channel: evaluated once
+  uint8_t shared[LCE_HIP_EW_I8_MAX_STEPS][256];
+  auto eval_step = [&](int k, int32_t operand, uint8_t* f) {
+    for (int v = -128; v < 128; ++v) f[v + 128] = (uint8_t)(int8_t)ew_i8_eval(P.fn[k], v, operand);
+  };
+  for (int k = 0; k < desc->num_steps; ++k)
+    if (desc->steps[k].operand != LCE_HIP_EW_PER_CHANNEL) eval_step(k, desc->steps[k].values ? (int32_t)desc->steps[k].values[0] : 0, shared[k]);
+  for (int32_t r = 0; r < P.table_rows; ++r) {
+    uint8_t* row = table_host + (size_t)r * 256u;
+    for (int i = 0; i < 256; ++i) row[i] = (uint8_t)(int8_t)(i - 128);
+    for (int k = 0; k < desc->num_steps; ++k) {
+      uint8_t own[256];
+      const uint8_t* f = shared[k];
+      if (desc->steps[k].operand == LCE_HIP_EW_PER_CHANNEL) {
+        eval_step(k, (int32_t)desc->steps[k].values[r], own);
+        f = own;
+      }
+      for (int i = 0; i < 256; ++i) row[i] = f[(uint8_t)(row[i] ^ 0x80u)];
+    }
+  }
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_elementwise_i8(const lce_hip_elementwise_i8_desc* desc, const int8_t* in_dev, const int8_t* addend_dev,
+                                      const uint8_t* table_dev, size_t rows, int8_t* out_dev, int32_t* out_bits_dev, void* stream) {
+  return ew_i8_run(desc, -1, in_dev, addend_dev, table_dev, rows, out_dev, out_bits_dev, stream, "lce_hip_elementwise_i8");
+}
+
+lce_hip_status lce_hip_elementwise_i8_forced(const lce_hip_elementwise_i8_desc* desc, int32_t path, const int8_t* in_dev,
+                                             const int8_t* addend_dev, const uint8_t* table_dev, size_t rows, int8_t* out_dev,
+                                             int32_t* out_bits_dev, void* stream) {
+  if (path < 0) return fail(LCE_HIP_ERR_INVALID, "lce_hip_elementwise_i8_forced: unknown path %d", (int)path);
+  return ew_i8_run(desc, path, in_dev, addend_dev, table_dev, rows, out_dev, out_bits_dev, stream, "lce_hip_elementwise_i8_forced");
+}
+
+lce_hip_status lce_hip_elementwise_i8_path(const lce_hip_elementwise_i8_desc* desc, size_t rows, const int8_t* in_dev,
+                                           const int8_t* addend_dev, const uint8_t* table_dev, const int8_t* out_dev,
+                                           const int32_t* out_bits_dev, int32_t forced_path, lce_hip_elementwise_i8_launch* launch) {
+  const char* who = "lce_hip_elementwise_i8_path";
+  if (!launch) return fail(LCE_HIP_ERR_INVALID, "%s: null argument", who);
+  EwI8Plan P;
+  if (lce_hip_status s = ew_i8_plan(desc, who, &P)) return s;
+  EwI8Launch L;
+  if (lce_hip_status s = ew_i8_launch(desc, forced_path, in_dev, addend_dev, table_dev, rows, out_dev, out_bits_dev, who, false, P, &L)) return s;
+  launch->path = L.path;
+  launch->flat = L.flat ? 1 : 0;
+  launch->lds_max_channels = L.lds_max_channels;
+  launch->blocks = (int32_t)L.blocks;
+  launch->waves_per_block = (int32_t)(L.threads / 64u);
+  launch->lds_bytes = (int32_t)L.lds_bytes;
+  launch->head_variant = desc->has_head ? L.head : -1;
+  launch->table_rows = P.table_rows;
+  return LCE_HIP_OK;
 }
 
 // ------------------------------------------------------------------------------------

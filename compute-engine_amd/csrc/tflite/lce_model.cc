@@ -23,10 +23,12 @@ struct lce_tflite_section {
 // The kinds of builtin operator a section may absorb (lce_tflite_model::absorbed; 0: none), one fused pass each: a row of kPasses.
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
        kAbsorbedConvI8, kAbsorbedDepthwiseI8, kAbsorbedMean, kAbsorbedBinaryDense, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
-       kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedActivation, kAbsorbedReshape, kAbsorbedGate, kAbsorbedSlice, kAbsorbedCount };
+       kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedActivation, kAbsorbedReshape, kAbsorbedGate, kAbsorbedSlice,
+       kAbsorbedElementwiseI8, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
 enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u,
-       kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u, kInternalBinaryDense = 256u, kInternalSlice = 512u };
+       kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u, kInternalBinaryDense = 256u, kInternalSlice = 512u,
+       kInternalElementwiseI8 = 1024u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
@@ -45,6 +47,7 @@ struct lce_tflite_model {
   std::map<int32_t, DevBuf> scratch;                                    // intermediate tensors of a section, grow-only
   std::map<int32_t, DevBuf> consts;                                     // per-channel ADD / MUL constants on the device, uploaded once
   std::map<int32_t, DevBuf> tables;                                     // per int8 CONV_2D / DEPTHWISE_CONV_2D / FULLY_CONNECTED and binary Dense operator: its prepare's table, uploaded once
+                                                                        // (an int8 elementwise chain's table is kept under the chain's first operator)
   std::map<int32_t, std::vector<int32_t>> host_tables;                  // ... as Partition() prepared it; dropped once it is on the device
   // What one run launched.  A recorded graph keeps the record of its recording, so a replay reports the same numbers.
   struct RunStats {
@@ -54,6 +57,7 @@ struct lce_tflite_model {
     int32_t reshape_views = 0, reshape_copies = 0;                      // absorbed RESHAPE operators: aliased / copied device to device
     int32_t dequantize_skipped = 0;                                     // LceDequantize operators only binary Dense layers read: not launched
     int32_t slice_joins = 0;                                            // lce_hip_join_windows launches that took over a CONCATENATION
+    int32_t ew_i8_ops = 0;                                              // operators of every kind inside the lce_hip_elementwise_i8 launches (a head ADD included)
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
     Pass pass[kAbsorbedCount];                                          // by kAbsorbed* kind ([0] unused)
   };
@@ -1009,6 +1013,97 @@ bool SliceCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
   return out.shape[0] == in.shape[0] && out.shape[1] == in.shape[1] && out.shape[2] == in.shape[2] && out.shape[3] == count;
 }
 
+// ---- the int8 elementwise chain ("elementwise_i8" of lce_tflite_model_open_passes) ----
+// The step of lce_hip_elementwise_i8 that builtin operator `o` is, with its constant in the file (`values` points into the
+// model), and the tensor it streams.  It is a step when the output is int8 and 4-D with positive extents, the streamed input a
+// non-constant int8 tensor of the output's shape (batch ignored), every tensor quantized with ONE scale and a zero point in
+// [-128, 127] (Int8Activation), and the operator one of
+//   ADD with exactly one constant operand of shape [C], [1,1,1,C], [1] or [] whose data is in the file, as many bytes;
+//   PRELU with a constant alpha of shape [C], [1,1,C], [1,1,1,C], [1] or [], likewise;
+//   RELU, RELU_N1_TO_1, RELU6;
+//   QUANTIZE int8 -> int8 (the requantize in front of a CONCATENATION whose inputs differ in scale).
+// These stay with the host: int8 MUL and int8 LOGISTIC, a full [H,W,C] alpha, a non-constant alpha, a per-channel-quantized
+// constant, uint8 / int16 tensors, rank-2 tensors.
+bool ElementwiseI8Step(const lce_tfl::Model& M, const lce_tfl::Operator& o, lce_hip_ew_i8_step* st, int32_t* x_t) {
+  memset(st, 0, sizeof *st);
+  if (o.outputs.size() != 1 || o.inputs.empty() || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (!Int8Activation(out) || out.shape.size() != 4) return false;
+  for (int32_t extent : out.shape)
+    if (extent <= 0) return false;
+  int32_t x = o.inputs[0];
+  const lce_tfl::Tensor* k = nullptr;
+  int64_t n = 0;
+  switch (o.builtin_code) {
+    case lce_tfl::kBuiltinAdd: {
+      if (o.inputs.size() != 2 || o.inputs[1] < 0) return false;
+      const bool c0 = M.tensors[o.inputs[0]].data != nullptr, c1 = M.tensors[o.inputs[1]].data != nullptr;
+      if (c0 == c1) return false;                                  // (two tensors: the residual ADD's; two constants: nobody's)
+      x = o.inputs[c0 ? 1 : 0];
+      k = &M.tensors[o.inputs[c0 ? 0 : 1]];
+      n = BroadcastCount(*k);
+      st->op = LCE_HIP_EW_I8_ADD;
+      st->activation = o.activation;
+      break;
+    }
+    case lce_tfl::kBuiltinPrelu:
+      if (o.inputs.size() != 2 || o.inputs[1] < 0) return false;
+      k = &M.tensors[o.inputs[1]];
+      n = AlphaCount(*k);
+      st->op = LCE_HIP_EW_I8_PRELU;
+      break;
+    case lce_tfl::kBuiltinRelu: case lce_tfl::kBuiltinReluN1To1: case lce_tfl::kBuiltinRelu6:
+      if (o.inputs.size() != 1) return false;
+      st->op = LCE_HIP_EW_I8_CLAMP;
+      st->activation = o.builtin_code == lce_tfl::kBuiltinRelu ? LCE_HIP_ACT_RELU
+                       : o.builtin_code == lce_tfl::kBuiltinRelu6 ? LCE_HIP_ACT_RELU6 : LCE_HIP_ACT_RELU_N1_TO_1;
+      break;
+    case lce_tfl::kBuiltinQuantize:
+      if (o.inputs.size() != 1) return false;
+      st->op = LCE_HIP_EW_I8_REQUANTIZE;
+      break;
+    default: return false;
+  }
+  const lce_tfl::Tensor& in = M.tensors[x];
+  if (!Int8Activation(in) || !SameImage(in, out) || in.shape[3] != out.shape[3]) return false;
+  if (k) {
+    if (!k->data || !Int8Activation(*k)) return false;
+    if ((n != 1 && n != out.shape[3]) || (uint64_t)k->bytes != (uint64_t)n) return false;
+    st->operand = n == 1 ? LCE_HIP_EW_SCALAR : LCE_HIP_EW_PER_CHANNEL;
+    st->values = (const int8_t*)k->data;
+    st->operand_scale = k->scale;
+    st->operand_zero_point = (int32_t)k->zero_point;
+  }
+  st->out_scale = out.scale;
+  st->out_zero_point = (int32_t)out.zero_point;
+  *x_t = x;
+  return true;
+}
+bool ElementwiseI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  lce_hip_ew_i8_step st;
+  int32_t x = -1;
+  return ElementwiseI8Step(M, o, &st, &x);
+}
+// The row's prepare step: lce_hip_elementwise_i8_prepare on the operator as a chain of ONE step, from the file's constants.  What
+// it refuses (an ADD multiplier outside (0, 1), an intermediate that could leave int32) stays with the host.  The table it writes
+// is dropped: a run prepares ONE table for the whole chain the operator ends up in.
+lce_hip_status ElementwiseI8Prepare(const lce_tflite_model& model, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Model& M = model.m;
+  lce_hip_elementwise_i8_desc d;
+  memset(&d, 0, sizeof d);
+  int32_t x = -1;
+  if (!ElementwiseI8Step(M, o, &d.steps[0], &x)) return LCE_HIP_ERR_INVALID;
+  d.channels = M.tensors[o.outputs[0]].shape[3];
+  d.in_scale = M.tensors[x].scale;
+  d.in_zero_point = (int32_t)M.tensors[x].zero_point;
+  d.num_steps = 1;
+  size_t bytes = 0;
+  if (lce_hip_status s = lce_hip_elementwise_i8_table_size(&d, &bytes)) return s;
+  std::vector<uint8_t> scratch(bytes);
+  table->clear();
+  return lce_hip_elementwise_i8_prepare(&d, scratch.data());
+}
+
 // THE names of lce_tflite_model_open_passes, each with the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it
 // that the name sets: the only place the three are written.  "stem" is a name that is no pass (Partition() reads its bit); "head",
 // "head_i8" and "quantize" enable several rows of kPasses each.
@@ -1022,7 +1117,8 @@ constexpr PassName kPassNames[] = {
     {"head_i8", 2, kInternalHeadI8},                     {"quantize", 2, kInternalQuantize},
     {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
     {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate},
-    {"binary_dense", 2, kInternalBinaryDense},           {"slice", 2, kInternalSlice}};
+    {"binary_dense", 2, kInternalBinaryDense},           {"slice", 2, kInternalSlice},
+    {"elementwise_i8", 2, kInternalElementwiseI8}};
 // The entry of kPassNames called `name`; null when there is none.
 constexpr const PassName* Named(const char* name) {
   for (const PassName& n : kPassNames) {
@@ -1864,6 +1960,107 @@ struct Walk {
     return own->second == in ? LCE_HIP_OK : lce_hip_memcpy_d2d(own->second, in, os.bytes(), stream);
   }
 
+  // A maximal chain of absorbed int8 elementwise operators ("elementwise_i8") that starts at operator `first`, as ONE
+  // lce_hip_elementwise_i8 launch.  The chain extends by ElementwiseChain's rules: through an operator of the same kind whose
+  // streamed input has exactly one reader and is not a section output, up to 8 steps.  ONE table is prepared for the whole chain and
+  // uploaded once per model (kept under `first`); the first LceQuantize of the section that reads the chain's last tensor becomes the
+  // launch's bit output.  `head` (-1: none): an absorbed residual int8 ADD whose sum only `first` reads -- it becomes the launch's
+  // head instead of a launch of its own (Int8Add hands it over), and counts among the launch's operators.
+  lce_hip_status ElementwiseI8(int32_t first) { return ElementwiseI8Chain(first, -1); }
+  lce_hip_status ElementwiseI8Chain(int32_t first, int32_t head) {
+    const lce_tfl::Model& M = model->m;
+    lce_hip_elementwise_i8_desc d;
+    memset(&d, 0, sizeof d);
+    lce_hip_ew_i8_step st;
+    int32_t x_t = -1;
+    if (!ElementwiseI8Step(M, M.operators[first], &st, &x_t)) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 elementwise operator is no step");
+    const std::vector<int32_t>& fs = M.tensors[M.operators[first].outputs[0]].shape;
+    int32_t in_t = x_t, addend_t = -1;
+    Shape xs;
+    if (head >= 0) {
+      const lce_tfl::Operator& h = M.operators[head];
+      lce_hip_add_int8_desc hd;
+      if (!Int8AddDesc(M, h, &hd)) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD without quantization parameters");
+      for (int k = 0; k < 2; ++k) {
+        auto it = shapes.find(h.inputs[k]);
+        if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD reads a tensor nothing produced");
+        xs = it->second;
+        if (!Agrees(xs, lce_tfl::kTensorInt8, fs[1], fs[2], fs[3]))
+          return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 ADD input's shape or type does not match the one its producer infers");
+      }
+      in_t = h.inputs[0];
+      addend_t = h.inputs[1];
+      d.has_head = 1;
+      d.in_scale = hd.in1_scale; d.in_zero_point = hd.in1_zero_point;
+      d.addend_scale = hd.in2_scale; d.addend_zero_point = hd.in2_zero_point;
+      d.head_scale = hd.out_scale; d.head_zero_point = hd.out_zero_point;
+      d.head_activation = hd.activation;
+      shapes[x_t] = xs;
+      done[head] = 1;
+    } else {
+      auto it = shapes.find(x_t);
+      if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 elementwise operator reads a tensor nothing produced");
+      xs = it->second;
+      if (!Agrees(xs, lce_tfl::kTensorInt8, fs[1], fs[2], fs[3]))
+        return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 elementwise input's shape or type does not match the one its producer infers");
+      d.in_scale = M.tensors[x_t].scale;
+      d.in_zero_point = (int32_t)M.tensors[x_t].zero_point;
+    }
+    d.channels = xs.dims[3];
+    std::vector<int32_t> chain;
+    int32_t cur = first, v_t = x_t;
+    for (;;) {
+      const lce_tfl::Operator& o = M.operators[cur];
+      int32_t sx = -1;
+      const std::vector<int32_t>& os = M.tensors[o.outputs[0]].shape;
+      if (!ElementwiseI8Step(M, o, &st, &sx) || sx != v_t || !Agrees(xs, lce_tfl::kTensorInt8, os[1], os[2], os[3])) {
+        if (chain.empty()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 elementwise operator's shape does not match the one its producer infers");
+        break;
+      }
+      d.steps[d.num_steps++] = st;
+      chain.push_back(cur);
+      done[cur] = 1;
+      v_t = o.outputs[0];
+      shapes[v_t] = xs;
+      const std::vector<int32_t>& rd = model->readers[v_t];
+      if (d.num_steps == LCE_HIP_EW_I8_MAX_STEPS || rd.size() != 1 || IsSectionOutput(v_t)) break;
+      const int32_t next = rd[0];
+      if (model->absorbed[next] != kAbsorbedElementwiseI8 || done[next] || !std::binary_search(sec.ops.begin(), sec.ops.end(), next)) break;
+      cur = next;
+    }
+    const Fold fold = FoldQuantize(chain.back(), v_t, xs);
+    if (!run) return LCE_HIP_OK;
+    const void *in = nullptr, *addend = nullptr;
+    if (lce_hip_status s = DevicePtr(in_t, "an int8 elementwise input", &in)) return s;
+    if (addend_t >= 0)
+      if (lce_hip_status s = DevicePtr(addend_t, "an int8 ADD input", &addend)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    lce_tflite_model::DevBuf& b = model->tables[first];
+    if (!b.ptr) {
+      if (capturing) return Fail(LCE_HIP_ERR_INVALID, "run_section: a constant would have to be uploaded during graph capture");
+      size_t bytes = 0;
+      if (lce_hip_status s = lce_hip_elementwise_i8_table_size(&d, &bytes)) return s;
+      std::vector<uint8_t> table(bytes);
+      if (lce_hip_status s = lce_hip_elementwise_i8_prepare(&d, table.data())) return s;
+      // (the buffer becomes the model's only once the copy has completed, as TableOnDevice's)
+      void* dev = nullptr;
+      if (lce_hip_status s = lce_hip_malloc(&dev, bytes ? bytes : 1)) return s;
+      lce_hip_status s = lce_hip_memcpy_h2d(dev, table.data(), bytes, stream);
+      if (s == LCE_HIP_OK) s = lce_hip_stream_synchronize(stream);
+      if (s != LCE_HIP_OK) {
+        lce_hip_free(dev);
+        return s;
+      }
+      b.ptr = dev;
+      b.bytes = bytes;
+    }
+    if (lce_hip_status s = lce_hip_elementwise_i8(&d, (const int8_t*)in, (const int8_t*)addend, (const uint8_t*)b.ptr,
+                                                  (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2], (int8_t*)out, (int32_t*)bits, stream)) return s;
+    model->last.ew_i8_ops += (int32_t)chain.size() + (head >= 0 ? 1 : 0);
+    return Launched(kAbsorbedElementwiseI8, fold);
+  }
+
   // An absorbed int8 ADD (LCE_TFLITE_SECTIONS_INT8_ADD) as ONE lce_hip_add_int8 launch.  The first LceQuantize of the section
   // that reads the sum becomes the launch's bit output and its own launch disappears; the int8 sum is written when anything
   // else reads it (in a residual chain the next ADD does) or the section delivers it.
@@ -1872,6 +2069,11 @@ struct Walk {
     const lce_tfl::Operator& op = M.operators[i];
     const int32_t out_t = op.outputs[0];
     const std::vector<int32_t>& fs = M.tensors[out_t].shape;
+    // a sum that only an absorbed int8 elementwise chain of this section reads is that chain's head: no launch here
+    const std::vector<int32_t>& rd = model->readers[out_t];
+    if (rd.size() == 1 && !IsSectionOutput(out_t) && model->absorbed[rd[0]] == kAbsorbedElementwiseI8 && !done[rd[0]] &&
+        std::binary_search(sec.ops.begin(), sec.ops.end(), rd[0]))
+      return ElementwiseI8Chain(rd[0], i);
     // the inferred shape and type of BOTH inputs must agree with the file's (a convolution whose output is smaller than the
     // file declares must not be read past its buffer)
     Shape xs;
@@ -2511,6 +2713,9 @@ constexpr FusedPass kPasses[kAbsorbedCount - 1] = {
     {kAbsorbedGate, Named("gate"), GateCandidate, &Walk::ElementwiseChain, nullptr, false, false},
     // the channel window of MeliusNet's improvement block: no row above takes a STRIDED_SLICE / SLICE
     {kAbsorbedSlice, Named("slice"), SliceCandidate, &Walk::Slice, nullptr, false, false},
+    // the int8 tail of a ReActNet block: no row above takes an int8 ADD with a constant operand (the residual ADD's row wants two
+    // tensors), an int8 PRELU or RELU (the activation row is float) or an int8 -> int8 QUANTIZE (the quantize row wants a float input)
+    {kAbsorbedElementwiseI8, Named("elementwise_i8"), ElementwiseI8Candidate, &Walk::ElementwiseI8, ElementwiseI8Prepare, false, false},
 };
 // (row k is kind k + 1, and every row names an entry of kPassNames)
 constexpr bool RowsInOrder() {
@@ -2686,6 +2891,11 @@ void lce_tflite_model_activation_stats(lce_tflite_model* model, int32_t* launche
 void lce_tflite_model_slice_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded, int32_t* joins) {
   Stats(model, [&](const RunStats& r) {
     Put(launches, r.pass[kAbsorbedSlice].launches); Put(quantize_folded, r.pass[kAbsorbedSlice].quantize); Put(joins, r.slice_joins);
+  });
+}
+void lce_tflite_model_elementwise_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+  Stats(model, [&](const RunStats& r) {
+    Put(launches, r.pass[kAbsorbedElementwiseI8].launches); Put(ops_folded, r.ew_i8_ops); Put(quantize_folded, r.pass[kAbsorbedElementwiseI8].quantize);
   });
 }
 void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies) {

@@ -131,7 +131,9 @@ class _OpenOptions56(C.Structure):
 # ``lce_tflite_model_open_passes``: (keyword, name of the pass there, word of the options -- 0 ``sections``, 1 ``sections_ext`` --,
 # bit, the smallest form of ``lce_tflite_open_options`` that carries the bit; 0: ``lce_tflite_model_open_ex`` does).  Word, bit and
 # form are None for a keyword whose name only ``lce_tflite_model_open_passes`` knows.  A new pass is a row here, a row of
-# ``_PASS_STATS``, a ``*_stats`` method and a sentence in ``LceModel``'s docstring.
+# ``_PASS_STATS``, a ``*_stats`` method and a sentence in ``LceModel``'s docstring.  A name newer than this table has no keyword: it
+# arrives through ``LceModel(..., passes=("name",))``, which hands it to ``lce_tflite_model_open_passes`` verbatim, and its counters
+# through an ordinary method (``elementwise_i8``: ``LceModel.elementwise_i8_stats``).
 _PASSES = (
     ("elementwise_sections", "elementwise", 0, SECTIONS_ELEMENTWISE, 0),
     ("int8_add_sections", "int8_add", 0, SECTIONS_INT8_ADD, 0),
@@ -211,6 +213,8 @@ def tflite_lib() -> C.CDLL:
         for name, counters in _PASS_STATS.items():
             f = getattr(l, "lce_tflite_model_%s_stats" % name)
             f.argtypes, f.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * counters, None
+        l.lce_tflite_model_elementwise_i8_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
+        l.lce_tflite_model_elementwise_i8_stats.restype = None
         l.lce_tflite_model_close.argtypes = [C.c_void_p]
         for f in ("lce_tflite_model_num_tensors", "lce_tflite_model_num_operators"):
             getattr(l, f).argtypes = [C.c_void_p]
@@ -276,8 +280,15 @@ class Operator:
 class LceModel:
     """A parsed .tflite flatbuffer (first subgraph)."""
 
-    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], **sections):
+    def __init__(self, flatbuffer: Union[bytes, str, os.PathLike], passes=(), **sections):
         """``sections``: the keywords of ``_PASSES``, each False unless given; each becomes an attribute.
+        ``passes``: an iterable of pass names handed verbatim to ``lce_tflite_model_open_passes``, appended to the names of the
+        keywords given and kept as ``model.passes`` (a tuple).  Names newer than ``_PASSES`` arrive this way; any name in it routes
+        the constructor through ``lce_tflite_model_open_passes``, and a name the library does not know (or one given twice) raises
+        ``ValueError`` with its message.  ``passes=("elementwise_i8",)``: the int8 tail of a ReActNet-style block -- ADD of a
+        constant shift, PRELU, RELU / RELU_N1_TO_1 / RELU6 and the int8 -> int8 QUANTIZE, on int8 tensors -- joins the sections and a
+        whole chain of them runs as ONE ``lce_hip_elementwise_i8`` launch on a table the reader prepares once per model; with
+        ``int8_add_sections`` the residual ADD in front of such a chain becomes the launch's head (``elementwise_i8_stats``).
         ``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -318,6 +329,9 @@ class LceModel:
         self._data = bytes(flatbuffer)            # must outlive the handle (zero-copy reader)
         given = _section_keywords("LceModel", sections)
         self.__dict__.update(given)
+        if isinstance(passes, (str, bytes)):
+            raise TypeError("LceModel(): passes must be an iterable of names, not one string")
+        self.passes = tuple(str(name) for name in passes)
         # a name only lce_tflite_model_open_passes knows goes there; otherwise the smallest form of the options that carries every
         # bit asked for; otherwise lce_tflite_model_open_ex
         words, size = [0, 0], 0
@@ -326,8 +340,8 @@ class LceModel:
                 words[word] |= bit
                 size = max(size, form)
         err = C.create_string_buffer(256)
-        if any(given[keyword] for keyword in _NAMED_ONLY):
-            names = ",".join(name for keyword, name, _, _, _ in _PASSES if given[keyword])
+        if self.passes or any(given[keyword] for keyword in _NAMED_ONLY):
+            names = ",".join([name for keyword, name, _, _, _ in _PASSES if given[keyword]] + list(self.passes))
             self._h = tflite_lib().lce_tflite_model_open_passes(self._data, len(self._data), names.encode(), err, 256)
         elif size:
             opts = _OPEN_OPTIONS[size](size, *words[:1 if size == 8 else 2])
@@ -475,6 +489,13 @@ class LceModel:
         CONCATENATION) of the last run."""
         return self._pass_stats("slice")
 
+    def elementwise_i8_stats(self):
+        """(lce_hip_elementwise_i8 launches, operators of every kind they ran -- a residual ADD taken as a chain's head included --,
+        LceQuantize launches they absorbed) of the last run (the pass ``elementwise_i8``, asked for through ``passes``)."""
+        v = [C.c_int32() for _ in range(3)]
+        tflite_lib().lce_tflite_model_elementwise_i8_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
     def reshape_stats(self):
         """(RESHAPE operators that were a view, RESHAPE operators that cost a device-to-device copy) of the last run."""
         return self._pass_stats("reshape")
@@ -507,15 +528,16 @@ class Interpreter:
     """``Interpreter(flatbuffer_model, batch_size=...)`` -- see the module docstring."""
 
     def __init__(self, flatbuffer_model, batch_size: int = 256, device: str = "cuda:0", use_reference_bconv: bool = False,
-                 **sections):
-        """``sections``: the ``*_sections`` keywords of ``LceModel``, described there (checked, then ignored, when a ready
-        ``LceModel`` is passed: its own settings hold)."""
+                 passes=(), **sections):
+        """``sections`` and ``passes``: the ``*_sections`` keywords and the pass names of ``LceModel``, described there (checked,
+        then ignored, when a ready ``LceModel`` is passed: its own settings hold)."""
         _section_keywords("Interpreter", sections)
-        self.model = flatbuffer_model if isinstance(flatbuffer_model, LceModel) else LceModel(flatbuffer_model, **sections)
+        self.model = (flatbuffer_model if isinstance(flatbuffer_model, LceModel)
+                      else LceModel(flatbuffer_model, passes=passes, **sections))
         self.batch_size = int(batch_size)
         self.device = device
         self._sem = _amd.SEM_REFERENCE if use_reference_bconv else _amd.SEM_OPTIMIZED
-        if any(getattr(self.model, keyword) for keyword in _PASS_NAMES):
+        if self.model.passes or any(getattr(self.model, keyword) for keyword in _PASS_NAMES):
             # every operator outside the sections is the host's; one section over the whole graph runs like an LCE-only one
             # (when every operator lies in a section there is exactly one: two would need a builtin epoch in between)
             covered = set(self.model.sections[0].ops) if len(self.model.sections) == 1 else set()

@@ -244,6 +244,112 @@ lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_
                                        int32_t* out_bits_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * int8 elementwise chain between binary layers (constant ADD, PRELU, RELU, requantize) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* The tail of an int8-converted ReActNet block -- LceBconv2d (int8 out), ADD shortcut, ADD per-channel shift, PRELU, ADD
+ * per-channel shift, LceQuantize -- a standalone int8 RELU, and the int8 -> int8 QUANTIZE the converter puts in front of a
+ * CONCATENATION whose inputs differ in scale.  lce_hip_elementwise_i8 is ONE pass over an NHWC int8 tensor [rows, channels]:
+ *
+ *   v = in                                             (quantization si, zi)
+ *   optional head:  v = ADD(v, addend[rows, channels])  exactly lce_hip_add_int8's arithmetic and prepare, own (s, z) and activation
+ *   steps 1..8, each with its own output (so, zo), which is the next step's (si, zi):
+ *     ADD    constant operand k (SCALAR, or PER_CHANNEL values[channels]; int8 with its own scale and zero point):
+ *            lce_hip_add_int8's arithmetic with x2 = k or k[c]; prepare and refusals as lce_hip_add_int8_prepare
+ *     PRELU  alpha int8 SCALAR or PER_CHANNEL with (sa, za);  d = v - zi
+ *            d >= 0: MBQM(d, m1, e1) + zo      (m1, e1) = QuantizeMultiplier((double)(float)(si / so))
+ *            d <  0: MBQM(d * (alpha - za), m2, e2) + zo      (m2, e2) = QuantizeMultiplier((double)(float)(si * sa / so))
+ *            clamped to [-128, 127]; activation must be NONE
+ *            (both real multipliers are evaluated in float32, left to right, then widened: TFLite's Prepare divides two floats)
+ *     CLAMP  standalone RELU / RELU_N1_TO_1 / RELU6: MBQM(v - zi, m, e) + zo with (m, e) = QuantizeMultiplier((double)(float)(si / so)),
+ *            clamped to CalculateActivationRangeQuantized at (so, zo), which lce_hip_add_int8_prepare reports as act_min / act_max
+ *     REQUANTIZE  QUANTIZE int8 -> int8: MBQM(v - zi, m, e) + zo with (m, e) = QuantizeMultiplier((double)si / (double)so),
+ *            clamped to [-128, 127]
+ *
+ * MBQM(x, m, e) = RDivPOT(SRDHM(x * 2^max(e,0), m), max(-e,0)); SRDHM, RDivPOT and QuantizeMultiplier as lce_hip_add_int8 states
+ * them.  Real multipliers of 1 and above are allowed for PRELU, CLAMP and REQUANTIZE.  This statement is the authority (no
+ * TFLite source is consulted); tests/elementwise_i8_ref.py restates it in NumPy int64.  It restates reference_integer_ops::Add
+ * (broadcast), reference_ops::BroadcastPrelu4DSlow (int8), optimized_ops::ReluX / QuantizedReluX and reference_ops::Requantize.
+ * Against the real-valued result in float64 (clamped the same way) one step alone deviates by at most, measured over 300 seeded
+ * parameter draws per kind and all 256 inputs on the CPU: ADD 0.5000 LSB, PRELU 0.7498, CLAMP 0.7495, REQUANTIZE 0.7497 (MBQM
+ * rounds twice: a half and a quarter can stack).  tests/test_elementwise_i8_host.py holds 0.51 / 0.75 / 0.75 / 0.75.
+ *
+ * Every step is a function of one int8 value and its channel, so the chain is one 256-entry table per channel:
+ *   lce_hip_elementwise_i8_check: the descriptor checks alone (the operand values are not read).  Host only.
+ *   lce_hip_elementwise_i8_table_size: the table's bytes, 256 R with R = channels, or R = 1 when no step is PER_CHANNEL.
+ *   lce_hip_elementwise_i8_prepare: host only.  Evaluates the steps' literal arithmetic for all 256 inputs of every channel and
+ *     writes uint8 table[R][256]: table[c][v + 128] is the chain's int8 result (as a byte) for the value v in channel c.
+ *   Refused (LCE_HIP_ERR_INVALID, the message names the step): a scale that is not finite and positive or a zero point outside
+ *   [-128, 127]; an ADD real multiplier outside (0, 1) as lce_hip_add_int8_prepare refuses it; a PRELU / CLAMP / REQUANTIZE real
+ *   multiplier that is not finite and positive; an activation on PRELU or REQUANTIZE; an unknown op, operand kind or activation;
+ *   an operand on CLAMP / REQUANTIZE; non-zero reserved fields; num_steps outside 1..8 (a head with no steps is
+ *   lce_hip_add_int8's job); channels negative or 2^22 and above; an intermediate that could leave int32 (x * 2^e); in prepare a
+ *   NULL values pointer of an ADD or PRELU.
+ *   lce_hip_elementwise_i8: ONE launch.  `table_dev`: prepare's table on the device, 4-byte aligned.  `addend_dev`: the head's
+ *     second tensor (NULL without a head).  `out_dev` (nullable) gets the last step's int8 value and may be in_dev or addend_dev
+ *     (in place); `out_bits_dev` (nullable) gets its LceQuantize at the LAST step's zero point: bit = out < zo, ceil(channels/32)
+ *     words per row, padding bits 0.  The int8 pointers need no alignment.  Zero rows or channels is a no-op.  Asynchronous on
+ *     `stream`, capturable in a HIP graph, allocates and copies nothing, 64-bit offsets.  The device computes the head ADD (with
+ *     the variant lce_hip_add_int8 has proven for its parameters) and looks the rest up.
+ * The table lives in one of three places, each a path:
+ *   LDS     : every block copies the table into LDS (260 R bytes of the 160 KiB: channels <= 608 on the 16-byte layout, <= 630
+ *             on the row layout).  A kernel's first launch with more than 64 KiB of LDS raises that kernel's limit, a host call:
+ *             make it before a capture, as lce_tflite_model_run_section's eager first run does.
+ *   GLOBAL  : the table is read from global memory through the cache; any channel count.
+ *   ONE_ROW : R = 1, the 256 bytes in LDS; what a chain with R = 1 runs on.  LDS and GLOBAL need R = channels.
+ * lce_hip_elementwise_i8_path reports what the launch would be for these operands (host only, nothing runs; the pointers are
+ * looked at for their alignment alone and may be NULL where the call allows it); lce_hip_elementwise_i8_forced runs a given
+ * path -- for tests and measurements -- and refuses one that cannot hold the table. */
+typedef enum lce_hip_ew_i8_op {
+  LCE_HIP_EW_I8_ADD = 0, LCE_HIP_EW_I8_PRELU = 1, LCE_HIP_EW_I8_CLAMP = 2, LCE_HIP_EW_I8_REQUANTIZE = 3
+} lce_hip_ew_i8_op;
+typedef enum lce_hip_elementwise_i8_path_id {
+  LCE_HIP_EW_I8_PATH_LDS = 0, LCE_HIP_EW_I8_PATH_GLOBAL = 1, LCE_HIP_EW_I8_PATH_ONE_ROW = 2
+} lce_hip_elementwise_i8_path_id;
+#define LCE_HIP_EW_I8_MAX_STEPS 8
+typedef struct lce_hip_ew_i8_step {
+  int32_t op, operand;             /* lce_hip_ew_i8_op; LCE_HIP_EW_SCALAR or LCE_HIP_EW_PER_CHANNEL (0 for CLAMP / REQUANTIZE) */
+  const int8_t* values;            /* HOST, read by prepare only: [1] for SCALAR, [channels] for PER_CHANNEL; NULL for CLAMP / REQUANTIZE */
+  float operand_scale; int32_t operand_zero_point;   /* of the constant (ADD) or of alpha (PRELU); 0 otherwise */
+  float out_scale; int32_t out_zero_point;
+  int32_t activation;              /* ADD, CLAMP: an lce_hip_activation; NONE for PRELU and REQUANTIZE */
+  int32_t reserved[2];             /* 0 */
+} lce_hip_ew_i8_step;
+typedef struct lce_hip_elementwise_i8_desc {
+  int32_t channels;
+  float in_scale; int32_t in_zero_point;
+  int32_t has_head;                /* 0 or 1 */
+  float addend_scale; int32_t addend_zero_point;     /* the head's second input, its output and its activation (0 without a head) */
+  float head_scale; int32_t head_zero_point;
+  int32_t head_activation;
+  int32_t num_steps;               /* 1..8 */
+  lce_hip_ew_i8_step steps[LCE_HIP_EW_I8_MAX_STEPS];
+  int32_t reserved[2];             /* 0 */
+} lce_hip_elementwise_i8_desc;
+typedef struct lce_hip_elementwise_i8_launch {
+  int32_t path;                    /* an lce_hip_elementwise_i8_path_id */
+  int32_t flat;                    /* 1: the 16-byte layout (4096 elements per wave and iteration), 0: one wave per 64 columns of a row */
+  int32_t lds_max_channels;        /* the largest channel count the LDS path takes on this layout */
+  int32_t blocks, waves_per_block; /* the launch */
+  int32_t lds_bytes;
+  int32_t head_variant;            /* the lce_hip_add_int8_variant_id of the head, -1 without one */
+  int32_t table_rows;              /* R */
+} lce_hip_elementwise_i8_launch;
+lce_hip_status lce_hip_elementwise_i8_check(const lce_hip_elementwise_i8_desc* desc);
+lce_hip_status lce_hip_elementwise_i8_table_size(const lce_hip_elementwise_i8_desc* desc, size_t* bytes);
+lce_hip_status lce_hip_elementwise_i8_prepare(const lce_hip_elementwise_i8_desc* desc, uint8_t* table_host /* [R][256] */);
+lce_hip_status lce_hip_elementwise_i8(const lce_hip_elementwise_i8_desc* desc, const int8_t* in_dev, const int8_t* addend_dev /* nullable */,
+                                      const uint8_t* table_dev, size_t rows, int8_t* out_dev /* nullable */,
+                                      int32_t* out_bits_dev /* nullable */, void* stream);
+lce_hip_status lce_hip_elementwise_i8_path(const lce_hip_elementwise_i8_desc* desc, size_t rows, const int8_t* in_dev,
+                                           const int8_t* addend_dev, const uint8_t* table_dev, const int8_t* out_dev,
+                                           const int32_t* out_bits_dev, int32_t forced_path /* -1: the entry's rule */,
+                                           lce_hip_elementwise_i8_launch* launch);
+lce_hip_status lce_hip_elementwise_i8_forced(const lce_hip_elementwise_i8_desc* desc, int32_t path, const int8_t* in_dev,
+                                             const int8_t* addend_dev, const uint8_t* table_dev, size_t rows, int8_t* out_dev,
+                                             int32_t* out_bits_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Channel join between binary layers (TFLite builtin CONCATENATION) and the LceQuantize that follows
  * ---------------------------------------------------------------------------------- */
 

@@ -164,7 +164,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
 
 /* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
  *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize, depthwise_i8, activation, reshape, gate,
- *   binary_dense, slice
+ *   binary_dense, slice, elementwise_i8
  * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
  * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
  * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
@@ -305,7 +305,25 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   pass that reads x and w once and writes y once, and a MeliusNet body is ONE section.  Any other absorbed slice is ONE
  *   lce_hip_join_windows launch with one window, into which a following LceQuantize folds by the fold rule.  A CONCATENATION
  *   without a window tensor still runs on lce_hip_concat, byte for byte as before.  Nothing moves unless it is named.  Still the
- *   host's: SPLIT / SPLIT_V, slices of other axes or with strides, slices of bit tensors. */
+ *   host's: SPLIT / SPLIT_V, slices of other axes or with strides, slices of bit tensors.
+ *   elementwise_i8: the int8 tail of a ReActNet-style block -- LceBconv2d (int8 out), ADD shortcut, ADD per-channel shift, PRELU,
+ *   ADD per-channel shift, LceQuantize -- a standalone int8 RELU, and the int8 -> int8 QUANTIZE the converter puts in front of a
+ *   CONCATENATION whose inputs differ in scale join the sections.  An operator qualifies when its output is int8 and 4-D with
+ *   positive extents, the tensor it streams is a non-constant int8 tensor of the output's shape (batch ignored), every tensor
+ *   carries ONE scale and a zero point in [-128, 127], and it is one of: ADD with exactly one constant operand of shape [C],
+ *   [1,1,1,C], [1] or [] whose data is in the file (as many bytes); PRELU with a constant alpha of shape [C], [1,1,C], [1,1,1,C],
+ *   [1] or []; RELU, RELU_N1_TO_1, RELU6; QUANTIZE int8 -> int8 -- and lce_hip_elementwise_i8_prepare accepts it, as a chain of
+ *   one step, with the file's constants (an ADD whose real multiplier is outside (0, 1) stays with the host, as for int8_add).  It
+ *   joins the epoch in which it becomes ready.  lce_tflite_model_run_section extends a chain through consecutive absorbed
+ *   operators of this kind by the elementwise chain's rules (each step reads only the previous result, which nothing else reads and
+ *   the section does not deliver; up to 8 steps), prepares ONE table for the chain, uploads it once per model, folds the first
+ *   LceQuantize that reads the result and launches lce_hip_elementwise_i8 ONCE.  With int8_add also named, an absorbed residual
+ *   ADD whose sum only such a chain reads becomes the chain's head instead of a launch of its own: that launch is counted by
+ *   lce_tflite_model_elementwise_i8_stats (the ADD among its operators), not by lce_tflite_model_int8_add_stats.  With
+ *   `int8_add,elementwise_i8` the body of an int8 ReActNet is ONE section and each block's tail ONE launch.  Without the name
+ *   every partition, launch and counter is what it was; with it a float file's partition is unchanged.  Still the host's: int8
+ *   MUL and int8 LOGISTIC (and with them the squeeze-and-excite gate of an int8 RealToBinaryNet), a full [H,W,C] alpha, a
+ *   non-constant alpha, per-channel-quantized constants, uint8 / int16 tensors, rank-2 tensors. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -479,6 +497,10 @@ void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int
  * CONCATENATIONs with a window tensor among their inputs), the LceQuantize launches folded into them, and those of the launches
  * that took over a CONCATENATION (lce_tflite_model_concat_stats counts lce_hip_concat launches only).  Nullable outputs. */
 void lce_tflite_model_slice_stats(lce_tflite_model* model, int32_t* launches, int32_t* quantize_folded, int32_t* joins);
+/* The LAST run's lce_hip_elementwise_i8 launches ("elementwise_i8" of lce_tflite_model_open_passes): launches (one per chain),
+ * operators of every kind inside them (a residual ADD taken as a chain's head included) and LceQuantize launches folded into
+ * them.  Any pointer may be NULL. */
+void lce_tflite_model_elementwise_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
