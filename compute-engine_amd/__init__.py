@@ -41,6 +41,7 @@ ABI_SYMBOLS = (
     "lce_hip_add_int8_prepare", "lce_hip_add_int8", "lce_hip_add_int8_variant", "lce_hip_add_int8_forced",
     "lce_hip_elementwise_i8_check", "lce_hip_elementwise_i8_table_size", "lce_hip_elementwise_i8_prepare", "lce_hip_elementwise_i8",
     "lce_hip_elementwise_i8_path", "lce_hip_elementwise_i8_forced",
+    "lce_hip_mul_int8_prepare", "lce_hip_mul_int8", "lce_hip_mul_int8_path", "lce_hip_logistic_int8_prepare", "lce_hip_logistic_int8",
     "lce_hip_concat", "lce_hip_join_windows", "lce_hip_join_windows_check", "lce_hip_pool2d", "lce_hip_pool2d_check", "lce_hip_conv1x1_f32", "lce_hip_conv1x1_f32_check",
     "lce_hip_depthwise_conv2d_f32", "lce_hip_depthwise_conv2d_f32_check", "lce_hip_conv2d_f32", "lce_hip_conv2d_f32_check",
     "lce_hip_conv2d_i8", "lce_hip_conv2d_i8_check", "lce_hip_conv2d_i8_prepare",
@@ -132,6 +133,25 @@ class EwI8Launch(C.Structure):
     """``lce_hip_elementwise_i8_launch``."""
     _fields_ = [(n, C.c_int32) for n in ("path", "flat", "lds_max_channels", "blocks", "waves_per_block", "lds_bytes", "head_variant",
                                          "table_rows")]
+
+
+class MulInt8Desc(C.Structure):
+    """``lce_hip_mul_int8_desc``."""
+    _fields_ = [("in1_scale", C.c_float), ("in1_zero_point", C.c_int32), ("in2_scale", C.c_float), ("in2_zero_point", C.c_int32),
+                ("out_scale", C.c_float), ("out_zero_point", C.c_int32), ("activation", C.c_int32), ("operand", C.c_int32),
+                ("has_add", C.c_int32), ("addend_scale", C.c_float), ("addend_zero_point", C.c_int32), ("add_scale", C.c_float),
+                ("add_zero_point", C.c_int32), ("add_activation", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class MulInt8Params(C.Structure):
+    """``lce_hip_mul_int8_params``."""
+    _fields_ = [("multiplier", C.c_int32), ("shift", C.c_int32), ("act_min", C.c_int32), ("act_max", C.c_int32), ("add", AddInt8Params)]
+
+
+class MulInt8Launch(C.Structure):
+    """``lce_hip_mul_int8_launch``."""
+    _fields_ = [(n, C.c_int32) for n in ("flat", "blocks", "waves_per_block", "add_variant", "mul_variant", "product_first")] + \
+               [("add_args", C.c_int32 * 21)]
 
 
 class Pool2dDesc(C.Structure):
@@ -251,6 +271,13 @@ def lib() -> C.CDLL:
         l.lce_hip_elementwise_i8_path.argtypes = [C.POINTER(EwI8Desc), C.c_size_t] + [C.c_void_p] * 5 + [C.c_int32, C.POINTER(EwI8Launch)]
         l.lce_hip_elementwise_i8_forced.argtypes = [C.POINTER(EwI8Desc), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                     C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_mul_int8_prepare.argtypes = [C.POINTER(MulInt8Desc), C.POINTER(MulInt8Params)]
+        l.lce_hip_mul_int8.argtypes = [C.POINTER(MulInt8Desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        l.lce_hip_mul_int8_path.argtypes = [C.POINTER(MulInt8Desc), C.c_size_t, C.c_size_t, C.c_size_t] + [C.c_void_p] * 5 + \
+                                           [C.POINTER(MulInt8Launch)]
+        l.lce_hip_logistic_int8_prepare.argtypes = [C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_void_p]
+        l.lce_hip_logistic_int8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_concat.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32, C.c_size_t, C.c_int32,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
         l.lce_hip_join_windows.argtypes = [C.c_int, C.POINTER(Window), C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -961,6 +988,139 @@ def elementwise_i8(x, table, q_in, steps, addend=None, head=None, out=None, out_
     del keep
     res = _results(host, out_d, bits_d, out, out_bits)
     return (*res, {n: int(getattr(launch, n)) for n, _ in EwI8Launch._fields_}) if report_launch else res
+
+
+LOGISTIC_I8_OUT = (1.0 / 256.0, -128)                   # the output quantization TFLite fixes for an int8 LOGISTIC
+
+
+def _mul_int8_desc(who, q_x, q_operand, q_out, act, per_image, add) -> MulInt8Desc:
+    """``lce_hip_mul_int8_desc``; shapes and kinds are checked here, the numbers are the library's to refuse."""
+    d = MulInt8Desc()
+    d.in1_scale, d.in1_zero_point = _ew_i8_q(who, "q_x", q_x)
+    d.in2_scale, d.in2_zero_point = _ew_i8_q(who, "q_operand", q_operand)
+    d.out_scale, d.out_zero_point = _ew_i8_q(who, "q_out", q_out)
+    d.activation = int(act)
+    d.operand = EW_PER_IMAGE_CHANNEL if per_image else EW_TENSOR
+    if add is not None:
+        if not isinstance(add, (list, tuple)) or len(add) not in (2, 3):
+            raise ValueError("%s: add must be (q_addend, q_out[, activation]), got %r" % (who, add))
+        d.has_add = 1
+        d.addend_scale, d.addend_zero_point = _ew_i8_q(who, "add q_addend", add[0])
+        d.add_scale, d.add_zero_point = _ew_i8_q(who, "add q_out", add[1])
+        d.add_activation = int(add[2]) if len(add) == 3 else ACT_NONE
+    return d
+
+
+def mul_int8_params(q_x, q_operand, q_out, act=ACT_NONE, add=None) -> dict:
+    """Prepare of the builtin int8 MUL (``lce_hip_mul_int8_prepare``, host only): ``multiplier``, ``shift``, ``act_min``,
+    ``act_max`` and, with ``add = (q_addend, q_out[, act])`` -- a residual ADD behind the MUL -- under ``"add"`` the dict
+    ``add_int8_params`` gives for (the product, the addend).  Raises ``LceHipError`` for what the library refuses."""
+    d = _mul_int8_desc("mul_int8_params", q_x, q_operand, q_out, act, False, add)
+    p = MulInt8Params()
+    check(lib().lce_hip_mul_int8_prepare(C.byref(d), C.byref(p)))
+    out = {n: int(getattr(p, n)) for n in ("multiplier", "shift", "act_min", "act_max")}
+    if add is not None:
+        out["add"] = add_int8_params(q_out, add[0], add[1], add[2] if len(add) == 3 else ACT_NONE)
+    return out
+
+
+def _mul_int8_check(x, operand, per_image, rows_per_image, addend, add, out, out_bits):
+    """Argument checks of ``mul_int8`` on shapes and dtypes only (NumPy or torch): nothing here touches a device."""
+    who = "mul_int8"
+    shape = tuple(x.shape)
+    if _dtype_name(x) != "int8" or len(shape) < 1:
+        raise ValueError("%s: x must be an int8 tensor with a channel axis, got %s %r" % (who, x.dtype, shape))
+    if _dtype_name(operand) != "int8":
+        raise ValueError("%s: operand must be int8, got %s" % (who, operand.dtype))
+    if per_image:
+        if len(operand.shape) < 1 or operand.shape[-1] != shape[-1]:
+            raise ValueError("%s: a per-image operand must be int8 [..., %d], got %r" % (who, shape[-1], tuple(operand.shape)))
+    elif tuple(operand.shape) != shape:
+        raise ValueError("%s: operand must be int8 of x's shape %r, got %r" % (who, shape, tuple(operand.shape)))
+    if (addend is None) != (add is None):
+        raise ValueError("%s: addend and add come together" % who)
+    if addend is not None and (_dtype_name(addend) != "int8" or tuple(addend.shape) != shape):
+        raise ValueError("%s: addend must be int8 of x's shape %r, got %s %r" % (who, shape, addend.dtype, tuple(addend.shape)))
+    if int(rows_per_image) != rows_per_image or rows_per_image < 0:
+        raise ValueError("%s: rows_per_image must be a non-negative integer, got %r" % (who, rows_per_image))
+    _check_outputs(who, out, out_bits, "int8", shape)
+
+
+def mul_int8(x, operand, q_x, q_operand, q_out, act=ACT_NONE, per_image=False, rows_per_image=0, addend=None, add=None, out=None,
+             out_bits=None, stream: int | None = None, report_launch: bool = False):
+    """TFLite's builtin int8 MUL -- the gate of a squeeze-and-excite block in an int8-converted network -- byte for byte, the
+    residual ADD behind it and the LceQuantize of the result, in one launch (``lce_hip_mul_int8``).  ``x``: int8 [..., C] on the
+    device (or NumPy: copied to cuda:0 and back).  ``operand``: int8 of ``x``'s shape, or with ``per_image`` the gate
+    [rows / rows_per_image, C] (any leading shape with that many elements), ``rows_per_image`` = H * W.  ``q_x``, ``q_operand``,
+    ``q_out``: (scale, zero_point) of the inputs and the product; ``act``: the MUL's ``ACT_*``.  ``addend`` with
+    ``add = (q_addend, q_out[, act])``: the tensor ``add_int8`` then adds to the product.  ``out``: an int8 tensor to fill (may be
+    ``x`` or ``addend``), None for a new one, False for none.  ``out_bits``: an int32 [..., ceil(C/32)] tensor to fill, True for a
+    new one, None for none; the bits are taken at the last stage's zero point.  Returns ``(out, out_bits)``, and with
+    ``report_launch`` a third value: the ``lce_hip_mul_int8_launch`` of the call as a dict."""
+    import torch
+    who = "mul_int8"
+    _mul_int8_check(x, operand, per_image, rows_per_image, addend, add, out, out_bits)
+    d = _mul_int8_desc(who, q_x, q_operand, q_out, act, per_image, add)
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x's")
+    a, g = on_dev(x), on_dev(operand)
+    b = None if addend is None else on_dev(addend)
+    channels = x.shape[-1]
+    rows = a.numel() // channels if channels else 0
+    out_d = None if out is False else torch.empty_like(a) if out is None else on_dev(out)
+    bits_d = None if out_bits is None else _new_bits(a.shape[:-1], channels, dev) if out_bits is True else on_dev(out_bits)
+    if per_image and rows_per_image and rows % int(rows_per_image) == 0 and g.numel() != rows // int(rows_per_image) * channels:
+        raise ValueError("%s: a per-image operand holds %d values, got %d" % (who, rows // int(rows_per_image) * channels, g.numel()))
+    launch = MulInt8Launch()
+    with torch.cuda.device(dev):
+        if report_launch and rows and channels:
+            check(lib().lce_hip_mul_int8_path(C.byref(d), rows, channels, int(rows_per_image), _dev_ptr(a), _dev_ptr(g), _dev_ptr(b),
+                                              _dev_ptr(out_d), _dev_ptr(bits_d), C.byref(launch)))
+        check(lib().lce_hip_mul_int8(C.byref(d), _dev_ptr(a), _dev_ptr(g), _dev_ptr(b), rows, channels, int(rows_per_image),
+                                     _dev_ptr(out_d), _dev_ptr(bits_d), C.c_void_p(_stream_or_current(stream, dev))))
+    res = _results(host, out_d, bits_d, out, out_bits)
+    return (*res, {n: int(getattr(launch, n)) for n, t in MulInt8Launch._fields_ if t is C.c_int32}) if report_launch else res
+
+
+def logistic_int8_table(q_in, q_out=LOGISTIC_I8_OUT):
+    """The table of TFLite's builtin int8 LOGISTIC (``lce_hip_logistic_int8_prepare``, host only): uint8 NumPy [256];
+    ``table[v + 128]`` is the int8 result, as a byte, for the input value v at ``q_in`` = (scale, zero_point).  The output
+    quantization is fixed at (1/256, -128); any other ``q_out`` is refused."""
+    si, zi = _ew_i8_q("logistic_int8_table", "q_in", q_in)
+    so, zo = _ew_i8_q("logistic_int8_table", "q_out", q_out)
+    table = np.zeros(256, np.uint8)
+    check(lib().lce_hip_logistic_int8_prepare(si, zi, so, zo, _host_ptr(table)))
+    return table
+
+
+def logistic_int8(x, q_in, out=None, out_bits=None, stream: int | None = None, table=None):
+    """TFLite's builtin int8 LOGISTIC of ``x`` (int8 [..., C] on the device, or NumPy: copied to cuda:0 and back) at ``q_in`` =
+    (scale, zero_point), as one table look-up per element (``lce_hip_logistic_int8``); the result is at (1/256, -128).  ``table``:
+    ``logistic_int8_table(q_in)`` (NumPy or on the device) when the caller keeps it; computed and uploaded here otherwise.
+    ``out`` / ``out_bits`` as ``mul_int8``'s (bit = value < -128: every bit is 0).  Returns ``(out, out_bits)``."""
+    import torch
+    who = "logistic_int8"
+    shape = tuple(x.shape)
+    if _dtype_name(x) != "int8" or len(shape) < 1:
+        raise ValueError("%s: x must be an int8 tensor with a channel axis, got %s %r" % (who, x.dtype, shape))
+    _check_outputs(who, out, out_bits, "int8", shape)
+    if table is None:
+        table = logistic_int8_table(q_in)
+    if _dtype_name(table) != "uint8" or tuple(table.shape) != (256,):
+        raise ValueError("%s: table must be uint8 [256] (logistic_int8_table), got %s %r" % (who, table.dtype, tuple(table.shape)))
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x's")
+    a, t = on_dev(x), on_dev(table)
+    channels = x.shape[-1]
+    rows = a.numel() // channels if channels else 0
+    out_d = None if out is False else torch.empty_like(a) if out is None else on_dev(out)
+    bits_d = None if out_bits is None else _new_bits(a.shape[:-1], channels, dev) if out_bits is True else on_dev(out_bits)
+    with torch.cuda.device(dev):
+        check(lib().lce_hip_logistic_int8(_dev_ptr(t), _dev_ptr(a), rows, channels, _dev_ptr(out_d), _dev_ptr(bits_d),
+                                          C.c_void_p(_stream_or_current(stream, dev))))
+    return _results(host, out_d, bits_d, out, out_bits)
 
 
 def _concat_check(tensors, out, out_bits, zero_point):

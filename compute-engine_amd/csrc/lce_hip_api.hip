@@ -20,6 +20,7 @@
 #include "lce_kernels_eltwise.h"  // (lce_tu_eltwise.hip, lce_tu_eltwise_ex.hip)
 #include "lce_kernels_eltwise_i8.h"  // (lce_tu_eltwise_i8.hip)
 #include "lce_kernels_eltwise_i8_chain.h"   // (lce_tu_eltwise_i8_chain.hip)
+#include "lce_kernels_mul_i8.h"      // (lce_tu_mul_i8.hip)
 #include "lce_kernels_join.h"        // (lce_tu_join.hip)
 #include "lce_kernels_pool.h"        // (lce_tu_pool.hip)
 #include "lce_kernels_conv1x1.h"     // (lce_tu_conv1x1.hip)
@@ -50,6 +51,7 @@
 #include "lce_tu_eltwise_ex.hip"
 #include "lce_tu_eltwise_i8.hip"
 #include "lce_tu_eltwise_i8_chain.hip"
+#include "lce_tu_mul_i8.hip"
 #include "lce_tu_join.hip"
 #include "lce_tu_pool.hip"
 #include "lce_tu_conv1x1.hip"
@@ -1227,6 +1229,254 @@ lce_hip_status lce_hip_elementwise_i8_path(const lce_hip_elementwise_i8_desc* de
   launch->lds_bytes = (int32_t)L.lds_bytes;
   launch->head_variant = desc->has_head ? L.head : -1;
   launch->table_rows = P.table_rows;
+  return LCE_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// int8 squeeze-and-excite gate: MUL with its residual ADD (lce_kernels_mul_i8.h), LOGISTIC as a table of the chain's ONE_ROW path
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+struct MulI8Plan {
+  lce_hip_mul_int8_params params;
+  lce_hip_add_int8_desc add;
+};
+
+// Every check of the descriptor and the parameters it gives; `who` is the entry's name.
+lce_hip_status mul_i8_plan(const lce_hip_mul_int8_desc* d, const char* who, MulI8Plan* P) {
+  if (!d) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  memset(P, 0, sizeof *P);
+  if (lce_hip_status s = ew_i8_quant(who, "in1", d->in1_scale, d->in1_zero_point)) return s;
+  if (lce_hip_status s = ew_i8_quant(who, "in2", d->in2_scale, d->in2_zero_point)) return s;
+  if (lce_hip_status s = ew_i8_quant(who, "out", d->out_scale, d->out_zero_point)) return s;
+  if (d->activation < LCE_HIP_ACT_NONE || d->activation > LCE_HIP_ACT_RELU6)
+    return fail(LCE_HIP_ERR_INVALID, "%s: unknown activation %d", who, (int)d->activation);
+  if (d->operand != LCE_HIP_EW_TENSOR && d->operand != LCE_HIP_EW_PER_IMAGE_CHANNEL)
+    return fail(LCE_HIP_ERR_INVALID, "%s: operand kind %d (TENSOR or PER_IMAGE_CHANNEL)", who, (int)d->operand);
+  if (d->has_add != 0 && d->has_add != 1) return fail(LCE_HIP_ERR_INVALID, "%s: has_add must be 0 or 1, got %d", who, (int)d->has_add);
+  if (d->reserved[0] || d->reserved[1]) return fail(LCE_HIP_ERR_INVALID, "%s: non-zero reserved field", who);
+  volatile float s12 = d->in1_scale * d->in2_scale;        // float32, left to right
+  const float real = s12 / d->out_scale;
+  if (lce_hip_status s = ew_i8_multiplier(who, (double)real, 255 * 255, &P->params.multiplier, &P->params.shift)) return s;
+  quantized_activation_range(d->activation, d->out_scale, d->out_zero_point, &P->params.act_min, &P->params.act_max);
+  if (d->has_add) {
+    char name[160];
+    snprintf(name, sizeof name, "%s: add", who);
+    P->add = lce_hip_add_int8_desc{d->out_scale, d->out_zero_point, d->addend_scale, d->addend_zero_point, d->add_scale,
+                                   d->add_zero_point, d->add_activation};
+    if (lce_hip_status s = add_int8_params(&P->add, &P->params.add, name)) return s;
+  }
+  return LCE_HIP_OK;
+}
+
+// Whether the fast MUL variant gives the literal one's byte for EVERY product (x1 - z1)(x2 - z2), all 130 051 of them, under the
+// MUL parameters of `M` (the precedent: prove_add_int8).  Kept per parameter set: a model launches the same few over and over.
+bool mul_i8_fast_is_proven(const lce::MulI8Args& M) {
+  if (M.left != 0 || M.right < 1 || M.right > 30 || M.m <= 0) return false;
+  typedef std::array<int32_t, 5> Key;
+  static std::mutex mu;
+  static std::map<Key, bool> cache;
+  const Key key{M.m, M.right, M.zo, M.lo, M.hi};
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+  }
+  bool exact = true;
+  for (int32_t p = -255 * 255; p <= 255 * 255 && exact; ++p)
+    exact = lce::mul_i8_requant<lce::kMulI8Fast>(M, p) == lce::mul_i8_requant<lce::kMulI8Literal>(M, p);
+  std::lock_guard<std::mutex> lock(mu);
+  if (cache.size() >= 1024) cache.clear();
+  cache[key] = exact;
+  return exact;
+}
+
+struct MulI8Launch {
+  lce::MulI8Args args;
+  int mul, add;
+  bool per_image, flat;
+  unsigned blocks;
+};
+
+// The launch of one call: layout, ADD variant, grid.  Nothing here touches a device.
+lce_hip_status mul_i8_launch(const lce_hip_mul_int8_desc* d, const int8_t* in1_dev, const int8_t* in2_dev, const int8_t* addend_dev,
+                             size_t rows, size_t channels, size_t rows_per_image, const int8_t* out_dev, const int32_t* out_bits_dev,
+                             const char* who, bool need_pointers, MulI8Launch* L) {
+  MulI8Plan P;
+  if (lce_hip_status s = mul_i8_plan(d, who, &P)) return s;
+  if (channels >= (1ull << 31)) return fail(LCE_HIP_ERR_INVALID, "%s: channels must be below 2^31", who);
+  L->per_image = d->operand == LCE_HIP_EW_PER_IMAGE_CHANNEL;
+  if (L->per_image && rows_per_image == 0) return fail(LCE_HIP_ERR_INVALID, "%s: rows_per_image is 0 with a per-image operand", who);
+  if (rows_per_image != 0 && rows % rows_per_image != 0)
+    return fail(LCE_HIP_ERR_INVALID, "%s: rows_per_image %zu does not divide rows %zu", who, rows_per_image, rows);
+  lce::MulI8Args& M = L->args;
+  memset(&M, 0, sizeof M);
+  L->add = lce::kMulI8NoAdd;
+  M.zo_last = d->out_zero_point;
+  if (d->has_add) {
+    PreparedAddI8 H;
+    if (lce_hip_status s = prepared_add_int8(&P.add, &H, who)) return s;
+    M.A = H.args;
+    M.A.c = H.c_for[H.variant];
+    L->add = H.variant;
+    M.product_first = H.swapped ? 0u : 1u;
+    M.zo_last = d->add_zero_point;
+  }
+  if (need_pointers) {
+    if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+    if (!in1_dev || !in2_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null input", who);
+    if (d->has_add && !addend_dev) return fail(LCE_HIP_ERR_INVALID, "%s: addend_dev is null with has_add", who);
+    if (!d->has_add && addend_dev) return fail(LCE_HIP_ERR_INVALID, "%s: an addend_dev without has_add", who);
+  }
+  if ((uintptr_t)out_bits_dev % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: out_bits_dev must be 4-byte aligned", who);
+  M.x = in1_dev; M.g = in2_dev; M.addend = addend_dev;
+  M.A.out = const_cast<int8_t*>(out_dev);
+  M.A.bits = (uint32_t*)const_cast<int32_t*>(out_bits_dev);
+  M.A.rows = rows;
+  M.A.channels = (uint32_t)channels;
+  M.A.wpr = (uint32_t)((channels + 31) / 32);
+  M.z1 = d->in1_zero_point; M.z2 = d->in2_zero_point; M.zo = d->out_zero_point;
+  M.m = P.params.multiplier;
+  M.left = P.params.shift > 0 ? P.params.shift : 0;
+  M.right = P.params.shift > 0 ? 0 : -P.params.shift;
+  M.lo = P.params.act_min; M.hi = P.params.act_max;
+  M.half = M.right >= 1 ? 1 << (M.right - 1) : 0;
+  L->mul = mul_i8_fast_is_proven(M) ? lce::kMulI8Fast : lce::kMulI8Literal;
+  M.cpr = (uint32_t)(channels / 16);
+  M.rows_per_image = rows_per_image ? rows_per_image : (rows ? rows : 1);
+  const bool aligned = ((uintptr_t)in1_dev % 16 == 0) && ((uintptr_t)in2_dev % 16 == 0) && ((uintptr_t)addend_dev % 16 == 0) &&
+                       ((uintptr_t)out_dev % 16 == 0);
+  L->flat = channels % 16 == 0 && aligned;
+  // memory-bound streams: 4 waves per block, at most ~8 blocks per CU, the waves stride over the rest (as lce_tu_eltwise_i8.hip)
+  const uint64_t wave_tasks = L->flat ? (rows * (uint64_t)M.cpr + 255) / 256 : rows * (uint64_t)((channels + 63) / 64);
+  const uint64_t blocks = (wave_tasks + 3) / 4, cap = 256ull * 8ull;
+  L->blocks = (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+  return LCE_HIP_OK;
+}
+
+// E(a) and LOGISTIC of include/lce_hip.h on the host, operation for operation what lce_kernels_exp.h and lce_kernels_eltwise.h do on
+// the device (this file is built with -ffp-contract=off; fmaf is one rounding, rintf rounds to nearest even).
+float host_exp_neg(float a) {
+  if (!(a >= -104.0f)) return 0.0f;
+  a = a > 0.0f ? 0.0f : a;
+  const float n = rintf(a * 1.44269502f);
+  float r = fmaf(n, -0.693145751953125f, a);
+  r = fmaf(n, -1.42860676e-06f, r);
+  float p = 1.98412701e-04f;
+  p = fmaf(p, r, 1.38888892e-03f);
+  p = fmaf(p, r, 8.33333377e-03f);
+  p = fmaf(p, r, 4.16666679e-02f);
+  p = fmaf(p, r, 1.66666672e-01f);
+  p = fmaf(p, r, 0.5f);
+  p = fmaf(p, r, 1.0f);
+  p = fmaf(p, r, 1.0f);
+  const int32_t ni = (int32_t)n;
+  const bool low = ni < -125;
+  uint32_t bits;
+  memcpy(&bits, &p, 4);
+  bits += (uint32_t)(ni + (low ? 64 : 0)) << 23;
+  float y;
+  memcpy(&y, &bits, 4);
+  return y * (low ? 5.42101086e-20f : 1.0f);
+}
+
+float host_logistic(float x) {
+  const bool pos = x >= 0.0f;
+  const float e = host_exp_neg(pos ? -x : x);
+  volatile float den = 1.0f + e;
+  return (pos ? 1.0f : e) / den;
+}
+}  // namespace
+extern "C" {
+
+lce_hip_status lce_hip_mul_int8_prepare(const lce_hip_mul_int8_desc* desc, lce_hip_mul_int8_params* params) {
+  const char* who = "lce_hip_mul_int8_prepare";
+  if (!params) return fail(LCE_HIP_ERR_INVALID, "%s: null argument", who);
+  MulI8Plan P;
+  if (lce_hip_status s = mul_i8_plan(desc, who, &P)) return s;
+  *params = P.params;
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_mul_int8(const lce_hip_mul_int8_desc* desc, const int8_t* in1_dev, const int8_t* in2_dev,
+                                const int8_t* addend_dev, size_t rows, size_t channels, size_t rows_per_image, int8_t* out_dev,
+                                int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_mul_int8";
+  MulI8Launch L;
+  const bool empty = rows == 0 || channels == 0;              // (an empty tensor may come with null pointers)
+  if (lce_hip_status s = mul_i8_launch(desc, in1_dev, in2_dev, addend_dev, rows, channels, rows_per_image, out_dev, out_bits_dev, who,
+                                       !empty, &L)) return s;
+  if (empty) return LCE_HIP_OK;
+  if (lce_hip_status s = require_device()) return s;
+  const int e = lce::launch_mul_i8(L.args, L.mul, L.add, L.per_image, L.flat, L.blocks, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_mul_int8_path(const lce_hip_mul_int8_desc* desc, size_t rows, size_t channels, size_t rows_per_image,
+                                     const int8_t* in1_dev, const int8_t* in2_dev, const int8_t* addend_dev, const int8_t* out_dev,
+                                     const int32_t* out_bits_dev, lce_hip_mul_int8_launch* launch) {
+  const char* who = "lce_hip_mul_int8_path";
+  if (!launch) return fail(LCE_HIP_ERR_INVALID, "%s: null argument", who);
+  MulI8Launch L;
+  if (lce_hip_status s = mul_i8_launch(desc, in1_dev, in2_dev, addend_dev, rows, channels, rows_per_image, out_dev, out_bits_dev, who,
+                                       false, &L)) return s;
+  launch->flat = L.flat ? 1 : 0;
+  launch->blocks = (int32_t)L.blocks;
+  launch->waves_per_block = 4;
+  launch->add_variant = desc->has_add ? L.add : -1;
+  launch->mul_variant = L.mul;
+  // the ADD kernel's parameters are the 21 consecutive int32 of AddI8Args from z1 to hi_rel
+  static_assert(offsetof(lce::AddI8Args, hi_rel) - offsetof(lce::AddI8Args, z1) == 20 * sizeof(int32_t), "z1 .. hi_rel are 21 int32");
+  static_assert(sizeof launch->add_args == 21 * sizeof(int32_t), "add_args holds z1 .. hi_rel");
+  memset(launch->add_args, 0, sizeof launch->add_args);
+  launch->product_first = 0;
+  if (desc->has_add) {
+    launch->product_first = (int32_t)L.args.product_first;
+    memcpy(launch->add_args, &L.args.A.z1, sizeof launch->add_args);
+  }
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_logistic_int8_prepare(float in_scale, int32_t in_zero_point, float out_scale, int32_t out_zero_point,
+                                             uint8_t* table) {
+  const char* who = "lce_hip_logistic_int8_prepare";
+  if (lce_hip_status s = ew_i8_quant(who, "in", in_scale, in_zero_point)) return s;
+  if (out_scale != 1.0f / 256.0f || out_zero_point != -128)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the output quantization must be (1/256, -128), got (%g, %d)", who, (double)out_scale,
+                (int)out_zero_point);
+  if (!table) return LCE_HIP_OK;
+  for (int v = -128; v < 128; ++v) {
+    volatile float d = (float)(v - in_zero_point);
+    volatile float x = in_scale * d;
+    volatile float y256 = host_logistic(x) * 256.0f;
+    const int32_t q = (int32_t)std::round((double)y256) - 128;   // round half away from zero (exact in double)
+    table[v + 128] = (uint8_t)(int8_t)std::min(127, std::max(-128, q));
+  }
+  return LCE_HIP_OK;
+}
+
+lce_hip_status lce_hip_logistic_int8(const uint8_t* table_dev, const int8_t* in_dev, size_t rows, size_t channels, int8_t* out_dev,
+                                     int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_logistic_int8";
+  // (the chain entry's own bound, which ew_i8_plan applies and this entry does not pass through)
+  if (channels >= (1ull << 22)) return fail(LCE_HIP_ERR_INVALID, "%s: channels must be in [0, 2^22), got %zu", who, channels);
+  if (rows == 0 || channels == 0) return LCE_HIP_OK;          // (an empty tensor may come with null pointers)
+  if (!out_dev && !out_bits_dev) return fail(LCE_HIP_ERR_INVALID, "%s: both outputs are null", who);
+  if (!table_dev) return fail(LCE_HIP_ERR_INVALID, "%s: table_dev is null", who);
+  if (!in_dev) return fail(LCE_HIP_ERR_INVALID, "%s: in_dev is null", who);
+  // the chain's ONE_ROW launch without a head: one table row for every channel, the bits at the fixed zero point -128
+  lce_hip_elementwise_i8_desc d;
+  memset(&d, 0, sizeof d);
+  d.channels = (int32_t)channels;
+  EwI8Plan P;
+  P.table_rows = 1;
+  P.zo_last = -128;
+  EwI8Launch L;
+  if (lce_hip_status s = ew_i8_launch(&d, -1, in_dev, nullptr, table_dev, rows, out_dev, out_bits_dev, who, true, P, &L)) return s;
+  if (lce_hip_status s = require_device()) return s;
+  const int e = lce::launch_ew_i8(L.args, L.head, L.path, L.flat, L.blocks, L.threads, L.lds_bytes, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
 

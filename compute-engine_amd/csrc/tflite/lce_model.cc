@@ -24,11 +24,11 @@ struct lce_tflite_section {
 enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPool, kAbsorbedConv1x1, kAbsorbedDepthwise, kAbsorbedConv2d,
        kAbsorbedConvI8, kAbsorbedDepthwiseI8, kAbsorbedMean, kAbsorbedBinaryDense, kAbsorbedFullyConnected, kAbsorbedSoftmax, kAbsorbedMeanI8, kAbsorbedFullyConnectedI8,
        kAbsorbedSoftmaxI8, kAbsorbedQuantize, kAbsorbedDequantize, kAbsorbedActivation, kAbsorbedReshape, kAbsorbedGate, kAbsorbedSlice,
-       kAbsorbedElementwiseI8, kAbsorbedCount };
+       kAbsorbedElementwiseI8, kAbsorbedLogisticI8, kAbsorbedMulI8, kAbsorbedCount };
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
 enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u,
        kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u, kInternalBinaryDense = 256u, kInternalSlice = 512u,
-       kInternalElementwiseI8 = 1024u };
+       kInternalElementwiseI8 = 1024u, kInternalGateI8 = 2048u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
@@ -58,6 +58,7 @@ struct lce_tflite_model {
     int32_t dequantize_skipped = 0;                                     // LceDequantize operators only binary Dense layers read: not launched
     int32_t slice_joins = 0;                                            // lce_hip_join_windows launches that took over a CONCATENATION
     int32_t ew_i8_ops = 0;                                              // operators of every kind inside the lce_hip_elementwise_i8 launches (a head ADD included)
+    int32_t gate_i8_ops = 0;                                            // MUL and residual ADD operators inside the lce_hip_mul_int8 launches
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
     Pass pass[kAbsorbedCount];                                          // by kAbsorbed* kind ([0] unused)
   };
@@ -1022,7 +1023,7 @@ bool SliceCandidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
 //   PRELU with a constant alpha of shape [C], [1,1,C], [1,1,1,C], [1] or [], likewise;
 //   RELU, RELU_N1_TO_1, RELU6;
 //   QUANTIZE int8 -> int8 (the requantize in front of a CONCATENATION whose inputs differ in scale).
-// These stay with the host: int8 MUL and int8 LOGISTIC, a full [H,W,C] alpha, a non-constant alpha, a per-channel-quantized
+// These stay with the host (int8 MUL and int8 LOGISTIC are the "gate_i8" rows'): a full [H,W,C] alpha, a non-constant alpha, a per-channel-quantized
 // constant, uint8 / int16 tensors, rank-2 tensors.
 bool ElementwiseI8Step(const lce_tfl::Model& M, const lce_tfl::Operator& o, lce_hip_ew_i8_step* st, int32_t* x_t) {
   memset(st, 0, sizeof *st);
@@ -1104,6 +1105,65 @@ lce_hip_status ElementwiseI8Prepare(const lce_tflite_model& model, const lce_tfl
   return lce_hip_elementwise_i8_prepare(&d, scratch.data());
 }
 
+// ---- the int8 squeeze-and-excite gate ("gate_i8" of lce_tflite_model_open_passes) ----
+// "A builtin int8 LOGISTIC that a section may run": one input and one output, both Int8Activation and of the same shape, of rank 2
+// or 4 with positive extents (Carried), the input non-constant.  The prepare step (lce_hip_logistic_int8_prepare) wants the output
+// at exactly (1/256, -128) and keeps the 256-byte table for the first run.
+bool LogisticI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  if (o.builtin_code != lce_tfl::kBuiltinLogistic || o.inputs.size() != 1 || o.outputs.size() != 1 || o.inputs[0] < 0) return false;
+  const lce_tfl::Tensor& in = M.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (!Int8Activation(in) || !Int8Activation(out) || in.data || in.shape != out.shape) return false;
+  int32_t id[4];
+  return Carried(in, id) && id[0] > 0;
+}
+lce_hip_status LogisticI8Prepare(const lce_tflite_model& model, const lce_tfl::Operator& o, std::vector<int32_t>* table) {
+  const lce_tfl::Tensor& in = model.m.tensors[o.inputs[0]];
+  const lce_tfl::Tensor& out = model.m.tensors[o.outputs[0]];
+  table->assign(64, 0);
+  return lce_hip_logistic_int8_prepare(in.scale, (int32_t)in.zero_point, out.scale, (int32_t)out.zero_point, (uint8_t*)table->data());
+}
+
+// lce_hip_mul_int8_desc (without an ADD) of builtin int8 MUL `o`, the tensor it streams and its operand.  It is one when it has two
+// non-constant Int8Activation inputs and one Int8Activation 4-D output with positive extents, one input of the output's shape and
+// the other of that shape too (a TENSOR operand: input 1) or [b,1,1,C] (GateOperandSlot's rule: the per-image gate, in either slot;
+// a [b,C] operand does not qualify), and an activation in NONE..RELU6.  A constant operand stays with the host.
+bool MulI8Desc(const lce_tfl::Model& M, const lce_tfl::Operator& o, lce_hip_mul_int8_desc* d, int32_t* x_t, int32_t* g_t) {
+  memset(d, 0, sizeof *d);
+  if (o.builtin_code != lce_tfl::kBuiltinMul || o.inputs.size() != 2 || o.outputs.size() != 1 || o.inputs[0] < 0 || o.inputs[1] < 0) return false;
+  if (o.activation < LCE_HIP_ACT_NONE || o.activation > LCE_HIP_ACT_RELU6) return false;
+  const lce_tfl::Tensor& out = M.tensors[o.outputs[0]];
+  if (!Int8Activation(out) || out.shape.size() != 4) return false;
+  for (int32_t extent : out.shape)
+    if (extent <= 0) return false;
+  for (int32_t t : o.inputs)
+    if (!Int8Activation(M.tensors[t]) || M.tensors[t].data) return false;
+  const int slot = GateOperandSlot(M, o);
+  if (slot >= 0) {
+    d->operand = LCE_HIP_EW_PER_IMAGE_CHANNEL;
+    *x_t = o.inputs[1 - slot];
+    *g_t = o.inputs[slot];
+  } else {
+    if (M.tensors[o.inputs[0]].shape != out.shape || M.tensors[o.inputs[1]].shape != out.shape) return false;
+    d->operand = LCE_HIP_EW_TENSOR;
+    *x_t = o.inputs[0];
+    *g_t = o.inputs[1];
+  }
+  const lce_tfl::Tensor &x = M.tensors[*x_t], &g = M.tensors[*g_t];
+  d->in1_scale = x.scale; d->in1_zero_point = (int32_t)x.zero_point;
+  d->in2_scale = g.scale; d->in2_zero_point = (int32_t)g.zero_point;
+  d->out_scale = out.scale; d->out_zero_point = (int32_t)out.zero_point;
+  d->activation = o.activation;
+  return true;
+}
+// "A builtin int8 MUL that a section may run": MulI8Desc, and lce_hip_mul_int8_prepare accepts it.
+bool MulI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
+  lce_hip_mul_int8_desc d;
+  lce_hip_mul_int8_params p;
+  int32_t x = -1, g = -1;
+  return MulI8Desc(M, o, &d, &x, &g) && lce_hip_mul_int8_prepare(&d, &p) == LCE_HIP_OK;
+}
+
 // THE names of lce_tflite_model_open_passes, each with the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it
 // that the name sets: the only place the three are written.  "stem" is a name that is no pass (Partition() reads its bit); "head",
 // "head_i8" and "quantize" enable several rows of kPasses each.
@@ -1118,7 +1178,7 @@ constexpr PassName kPassNames[] = {
     {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
     {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate},
     {"binary_dense", 2, kInternalBinaryDense},           {"slice", 2, kInternalSlice},
-    {"elementwise_i8", 2, kInternalElementwiseI8}};
+    {"elementwise_i8", 2, kInternalElementwiseI8},       {"gate_i8", 2, kInternalGateI8}};
 // The entry of kPassNames called `name`; null when there is none.
 constexpr const PassName* Named(const char* name) {
   for (const PassName& n : kPassNames) {
@@ -2061,6 +2121,87 @@ struct Walk {
     return Launched(kAbsorbedElementwiseI8, fold);
   }
 
+  // An absorbed int8 LOGISTIC ("gate_i8") as ONE lce_hip_logistic_int8 launch on the table the row's prepare step made, uploaded once
+  // per model.  A rank-2 tensor [b, C] -- the gate of a squeeze-and-excite block -- is carried as [b, 1, 1, C].
+  lce_hip_status LogisticI8(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    int32_t od[4];
+    if (!Carried(M.tensors[M.operators[i].outputs[0]], od)) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 LOGISTIC output of no carried rank");
+    return OnePass(i, "an int8 LOGISTIC", lce_tfl::kTensorInt8, OutShape(od[1], od[2], od[3], lce_tfl::kTensorInt8), /*fold_quantize=*/true,
+                   /*constants=*/0, [&](const void* x, const void*, const void*, void* out, int32_t* bits) {
+                     const int32_t* table = nullptr;
+                     if (lce_hip_status s = TableOnDevice(i, "an int8 LOGISTIC", &table)) return s;
+                     return lce_hip_logistic_int8((const uint8_t*)table, (const int8_t*)x, (size_t)batch * od[1] * od[2], (size_t)od[3],
+                                                  (int8_t*)out, bits, stream);
+                   });
+  }
+
+  // An absorbed int8 MUL ("gate_i8") as ONE lce_hip_mul_int8 launch.  When the product's ONLY reader is an absorbed int8 residual
+  // ADD of this section ("int8_add") whose other input has the same shape and has been produced, and the section does not deliver
+  // the product, the ADD rides in the same launch (has_add: the product is never written) and is marked done; it is then counted
+  // here, not by the int8 ADD's pass.  The first LceQuantize of the section that reads the result becomes the launch's bit output.
+  lce_hip_status MulI8(int32_t i) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator& op = M.operators[i];
+    const int32_t out_t = op.outputs[0];
+    const std::vector<int32_t>& fs = M.tensors[out_t].shape;
+    lce_hip_mul_int8_desc d;
+    int32_t x_t = -1, g_t = -1;
+    if (!MulI8Desc(M, op, &d, &x_t, &g_t)) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 MUL is no gate");
+    const bool per_image = d.operand == LCE_HIP_EW_PER_IMAGE_CHANNEL;
+    // the inferred shape and type of BOTH inputs must agree with the file's (a producer whose output is smaller than the file
+    // declares must not be read past its buffer)
+    auto xi = shapes.find(x_t), gi = shapes.find(g_t);
+    if (xi == shapes.end() || gi == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 MUL reads a tensor nothing produced");
+    const Shape xs = xi->second;
+    if (!Agrees(xs, lce_tfl::kTensorInt8, fs[1], fs[2], fs[3]) ||
+        !Agrees(gi->second, lce_tfl::kTensorInt8, per_image ? 1 : fs[1], per_image ? 1 : fs[2], fs[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: an int8 MUL input's shape or type does not match the one its producer infers");
+    shapes[out_t] = xs;
+    done[i] = 1;
+    int32_t add = -1, addend_t = -1, v_t = out_t;
+    const std::vector<int32_t>& rd = model->readers[out_t];
+    if (rd.size() == 1 && !IsSectionOutput(out_t) && model->absorbed[rd[0]] == kAbsorbedInt8Add && !done[rd[0]] &&
+        std::binary_search(sec.ops.begin(), sec.ops.end(), rd[0])) {
+      const lce_tfl::Operator& a = M.operators[rd[0]];
+      const int32_t other = a.inputs[0] == out_t ? a.inputs[1] : a.inputs[0];
+      auto oi = shapes.find(other);
+      lce_hip_add_int8_desc ad;
+      // (a window tensor -- a slice's output -- has a shape and no buffer of its own: such an ADD stays the int8 ADD pass's)
+      if (oi != shapes.end() && !windows.count(other) && Agrees(oi->second, lce_tfl::kTensorInt8, fs[1], fs[2], fs[3]) &&
+          M.tensors[a.outputs[0]].shape == M.tensors[out_t].shape && Int8AddDesc(M, a, &ad)) {
+        // (TFLite's ADD scales each input by itself and sums: which slot the product stands in does not change a byte)
+        const bool first = a.inputs[0] == out_t;
+        d.has_add = 1;
+        d.addend_scale = first ? ad.in2_scale : ad.in1_scale;
+        d.addend_zero_point = first ? ad.in2_zero_point : ad.in1_zero_point;
+        d.add_scale = ad.out_scale; d.add_zero_point = ad.out_zero_point;
+        d.add_activation = ad.activation;
+        add = rd[0];
+        addend_t = other;
+        v_t = a.outputs[0];
+        shapes[v_t] = xs;
+        done[add] = 1;
+        // the product exists in registers only: the walk holds no tensor of that name (lce_tflite_model_section_tensor_shape
+        // refuses it), which is how a walk without launches shows that the two operators share one
+        shapes.erase(out_t);
+      }
+    }
+    const Fold fold = FoldQuantize(add >= 0 ? add : i, v_t, xs);
+    if (!run) return LCE_HIP_OK;
+    const void *x = nullptr, *g = nullptr, *addend = nullptr;
+    if (lce_hip_status s = DevicePtr(x_t, "an int8 MUL input", &x)) return s;
+    if (lce_hip_status s = DevicePtr(g_t, "an int8 MUL input", &g)) return s;
+    if (addend_t >= 0)
+      if (lce_hip_status s = DevicePtr(addend_t, "an int8 ADD input", &addend)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = lce_hip_mul_int8(&d, (const int8_t*)x, (const int8_t*)g, (const int8_t*)addend, (size_t)xs.dims[0] * xs.dims[1] * xs.dims[2],
+                                            (size_t)xs.dims[3], per_image ? (size_t)xs.dims[1] * xs.dims[2] : 0, (int8_t*)out, (int32_t*)bits, stream)) return s;
+    model->last.gate_i8_ops += add >= 0 ? 2 : 1;
+    return Launched(kAbsorbedMulI8, fold);
+  }
+
   // An absorbed int8 ADD (LCE_TFLITE_SECTIONS_INT8_ADD) as ONE lce_hip_add_int8 launch.  The first LceQuantize of the section
   // that reads the sum becomes the launch's bit output and its own launch disappears; the int8 sum is written when anything
   // else reads it (in a residual chain the next ADD does) or the section delivers it.
@@ -2716,6 +2857,10 @@ constexpr FusedPass kPasses[kAbsorbedCount - 1] = {
     // the int8 tail of a ReActNet block: no row above takes an int8 ADD with a constant operand (the residual ADD's row wants two
     // tensors), an int8 PRELU or RELU (the activation row is float) or an int8 -> int8 QUANTIZE (the quantize row wants a float input)
     {kAbsorbedElementwiseI8, Named("elementwise_i8"), ElementwiseI8Candidate, &Walk::ElementwiseI8, ElementwiseI8Prepare, false, false},
+    // the int8 squeeze-and-excite gate: no row above takes an int8 LOGISTIC (the activation row is float) or an int8 MUL (the
+    // elementwise and gate rows are float, the int8 chain's has no MUL step)
+    {kAbsorbedLogisticI8, Named("gate_i8"), LogisticI8Candidate, &Walk::LogisticI8, LogisticI8Prepare, false, kRank2},
+    {kAbsorbedMulI8, Named("gate_i8"), MulI8Candidate, &Walk::MulI8, nullptr, false, false},
 };
 // (row k is kind k + 1, and every row names an entry of kPassNames)
 constexpr bool RowsInOrder() {
@@ -2896,6 +3041,11 @@ void lce_tflite_model_slice_stats(lce_tflite_model* model, int32_t* launches, in
 void lce_tflite_model_elementwise_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
   Stats(model, [&](const RunStats& r) {
     Put(launches, r.pass[kAbsorbedElementwiseI8].launches); Put(ops_folded, r.ew_i8_ops); Put(quantize_folded, r.pass[kAbsorbedElementwiseI8].quantize);
+  });
+}
+void lce_tflite_model_gate_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+  Stats(model, [&](const RunStats& r) {
+    Put(launches, r.pass[kAbsorbedMulI8].launches); Put(ops_folded, r.gate_i8_ops); Put(quantize_folded, r.pass[kAbsorbedMulI8].quantize);
   });
 }
 void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies) {

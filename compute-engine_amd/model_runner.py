@@ -215,6 +215,8 @@ def tflite_lib() -> C.CDLL:
             f.argtypes, f.restype = [C.c_void_p] + [C.POINTER(C.c_int32)] * counters, None
         l.lce_tflite_model_elementwise_i8_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
         l.lce_tflite_model_elementwise_i8_stats.restype = None
+        l.lce_tflite_model_gate_i8_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
+        l.lce_tflite_model_gate_i8_stats.restype = None
         l.lce_tflite_model_close.argtypes = [C.c_void_p]
         for f in ("lce_tflite_model_num_tensors", "lce_tflite_model_num_operators"):
             getattr(l, f).argtypes = [C.c_void_p]
@@ -289,6 +291,9 @@ class LceModel:
         constant shift, PRELU, RELU / RELU_N1_TO_1 / RELU6 and the int8 -> int8 QUANTIZE, on int8 tensors -- joins the sections and a
         whole chain of them runs as ONE ``lce_hip_elementwise_i8`` launch on a table the reader prepares once per model; with
         ``int8_add_sections`` the residual ADD in front of such a chain becomes the launch's head (``elementwise_i8_stats``).
+        ``passes=("gate_i8",)``: the squeeze-and-excite gate of an int8 RealToBinaryNet block -- int8 LOGISTIC (a 256-byte table,
+        ``lce_hip_logistic_int8``) and int8 MUL by a [b,1,1,C] gate or a tensor (``lce_hip_mul_int8``) -- joins the sections; with
+        ``int8_add_sections`` the residual ADD that alone reads the product rides in the MUL's launch (``gate_i8_stats``).
         ``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -494,6 +499,13 @@ class LceModel:
         LceQuantize launches they absorbed) of the last run (the pass ``elementwise_i8``, asked for through ``passes``)."""
         v = [C.c_int32() for _ in range(3)]
         tflite_lib().lce_tflite_model_elementwise_i8_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
+    def gate_i8_stats(self):
+        """(lce_hip_mul_int8 launches, MUL and residual ADD operators inside them, LceQuantize launches they absorbed) of the last
+        run (the pass ``gate_i8``, asked for through ``passes``); the int8 LOGISTIC launches are not among them."""
+        v = [C.c_int32() for _ in range(3)]
+        tflite_lib().lce_tflite_model_gate_i8_stats(self._h, *[C.byref(c) for c in v])
         return tuple(int(c.value) for c in v)
 
     def reshape_stats(self):

@@ -272,7 +272,8 @@ lce_hip_status lce_hip_add_int8_forced(const lce_hip_add_int8_desc* desc, int32_
  * (broadcast), reference_ops::BroadcastPrelu4DSlow (int8), optimized_ops::ReluX / QuantizedReluX and reference_ops::Requantize.
  * Against the real-valued result in float64 (clamped the same way) one step alone deviates by at most, measured over 300 seeded
  * parameter draws per kind and all 256 inputs on the CPU: ADD 0.5000 LSB, PRELU 0.7498, CLAMP 0.7495, REQUANTIZE 0.7497 (MBQM
- * rounds twice: a half and a quarter can stack).  tests/test_elementwise_i8_host.py holds 0.51 / 0.75 / 0.75 / 0.75.
+ * rounds twice: a half and a quarter can stack).  tests/test_elementwise_i8_host.py holds 0.51 / 0.75 / 0.75 / 0.75.  (The same
+ * measurement for lce_hip_mul_int8 and lce_hip_logistic_int8 below: MUL 0.5039, LOGISTIC 0.5000; tests/test_gate_i8_host.py.)
  *
  * Every step is a function of one int8 value and its channel, so the chain is one 256-entry table per channel:
  *   lce_hip_elementwise_i8_check: the descriptor checks alone (the operand values are not read).  Host only.
@@ -348,6 +349,104 @@ lce_hip_status lce_hip_elementwise_i8_path(const lce_hip_elementwise_i8_desc* de
 lce_hip_status lce_hip_elementwise_i8_forced(const lce_hip_elementwise_i8_desc* desc, int32_t path, const int8_t* in_dev,
                                              const int8_t* addend_dev, const uint8_t* table_dev, size_t rows, int8_t* out_dev,
                                              int32_t* out_bits_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * int8 squeeze-and-excite gate between binary layers (TFLite builtin LOGISTIC and MUL) and the LceQuantize that follows
+ * ---------------------------------------------------------------------------------- */
+
+/* In an int8-converted RealToBinaryNet a block is  y = LceBconv2d(bits(x));  gate = MEAN(y) -> FULLY_CONNECTED -> FULLY_CONNECTED
+ * -> LOGISTIC -> RESHAPE [b,1,1,C];  out = ADD(MUL(y, gate), x).  lce_hip_mul_int8 is TFLite's builtin int8 MUL, per element
+ *
+ *   (m, e) = QuantizeMultiplier((double)(float)(s1 * s2 / so))      float32, left to right, then widened (as PRELU's above)
+ *   out    = clamp(MBQM((x1 - z1) * (x2 - z2), m, e) + zo, act_min, act_max)
+ *
+ * with MBQM, QuantizeMultiplier and the activation range exactly as lce_hip_elementwise_i8 and lce_hip_add_int8 state them.  This
+ * statement is the authority (no TFLite source is consulted); tests/gate_i8_ref.py restates it in NumPy int64 / float32.
+ * `in1_dev` is NHWC int8 [rows, channels].  `in2_dev` is, by desc->operand,
+ *   LCE_HIP_EW_TENSOR            : [rows, channels]
+ *   LCE_HIP_EW_PER_IMAGE_CHANNEL : [rows / rows_per_image, channels], the gate: element (n, c) is read at n * channels + c
+ *                                  (lce_hip_elementwise_ex's rule; rows_per_image = H * W, 0 allowed for a TENSOR operand).
+ * Optional residual ADD behind the MUL (desc->has_add): the MUL's int8 result, at the MUL's own (so, zo) and clamped, is the first
+ * input of lce_hip_add_int8's arithmetic, `addend_dev` [rows, channels] at (addend_scale, addend_zero_point) the second; the ADD has
+ * its own output quantization (add_scale, add_zero_point) and add_activation.  The bytes are exactly those of lce_hip_mul_int8
+ * without the ADD followed by lce_hip_add_int8; the ADD runs the variant lce_hip_add_int8_variant has proven for its parameters.
+ * The MUL stage has two variants of the per-element arithmetic that give the same bytes: LITERAL, the formula as written (right for
+ * every parameter set), and FAST (e <= -1: one 64-bit multiply-add and one shift for SRDHM, one add and one shift for RDivPOT).  With
+ * the literal one the launch is ALU-bound at twice the bare ADD's time (profiles/gate_i8/layers.txt), so for each parameter set the
+ * host runs FAST over ALL 130 051 products (x1 - z1)(x2 - z2) against LITERAL and uses it only if every byte agrees.
+ * Outputs as lce_hip_add_int8's: `out_dev` (nullable) may be in1_dev or addend_dev (in place); `out_bits_dev` (nullable) gets
+ * bit = value < the LAST stage's zero point (the ADD's with has_add, the MUL's without), ceil(channels/32) words per row, padding
+ * bits 0.  int8 pointers may have any alignment; out_bits_dev is 4-byte aligned.  64-bit offsets.  Zero rows or channels is a
+ * no-op.  Asynchronous on `stream`, capturable in a HIP graph, allocates and copies nothing.
+ * Against the real-valued s1 s2 (x1 - z1)(x2 - z2) / so + zo in float64, clamped the same way, the MUL deviates by at most
+ * 0.5039 LSB, measured over 300 seeded parameter draws and all 65 536 input pairs on the CPU (tests/test_gate_i8_host.py holds
+ * 0.51; the figure is that of the NumPy restatement tests/gate_i8_ref.py, to which the parameters, the kernel bodies on the CPU
+ * and the GPU's bytes are each held equal).  MBQM rounds twice here as well, but where the products of two int8 differences span the int8 range (the draws keep
+ * fewer than 10 % of the results at a clamp bound) the real multiplier is a hundredth or less, so the first rounding weighs 2^-7
+ * of the second: not the 0.75 of PRELU, CLAMP and REQUANTIZE above.  The LOGISTIC table below, as lce_hip_logistic_int8_prepare
+ * writes it: at most 0.5000 LSB from float64's 256 / (1 + exp(-x)) - 128 over 300 draws and all 256 inputs (held at 0.51).
+ * Refused, LCE_HIP_ERR_INVALID, before any pointer is touched, the message naming the field: a scale that is not finite and
+ * positive or a zero point outside [-128, 127] (in1, in2, out; with has_add also addend, add); an unknown activation or operand
+ * kind; has_add other than 0 or 1; a real multiplier that is not finite and positive, or an (x1 - z1)(x2 - z2) * 2^e that could
+ * leave int32; the ADD's refusals exactly as lce_hip_add_int8_prepare gives them; a rows_per_image of 0 with a per-image operand,
+ * or one that does not divide rows; both outputs NULL; a NULL input; has_add with a NULL addend; non-zero reserved fields.
+ *   lce_hip_mul_int8_prepare: host only; the MUL's multiplier, shift and activation range and, with has_add, the ADD's parameters
+ *     (zeros without).
+ *   lce_hip_mul_int8_path: host only, nothing runs; the launch lce_hip_mul_int8 would make for these operands (the pointers are
+ *     looked at for their alignment alone).  flat: the 16-byte layout (channels % 16 == 0 and every pointer 16-byte aligned, 4096
+ *     elements per wave and iteration); otherwise one wave per 64 columns of a row. */
+typedef struct lce_hip_mul_int8_desc {
+  float in1_scale; int32_t in1_zero_point;
+  float in2_scale; int32_t in2_zero_point;
+  float out_scale; int32_t out_zero_point;           /* of the MUL */
+  int32_t activation;                                /* of the MUL: an lce_hip_activation */
+  int32_t operand;                                   /* LCE_HIP_EW_TENSOR or LCE_HIP_EW_PER_IMAGE_CHANNEL */
+  int32_t has_add;                                   /* 0 or 1 */
+  float addend_scale; int32_t addend_zero_point;     /* the ADD's second input, its output and its activation (ignored without) */
+  float add_scale; int32_t add_zero_point;
+  int32_t add_activation;
+  int32_t reserved[2];                               /* 0 */
+} lce_hip_mul_int8_desc;
+typedef struct lce_hip_mul_int8_params {
+  int32_t multiplier, shift, act_min, act_max;
+  lce_hip_add_int8_params add;                       /* in1 = the product, in2 = the addend */
+} lce_hip_mul_int8_params;
+typedef struct lce_hip_mul_int8_launch {
+  int32_t flat;                    /* 1: the 16-byte layout, 0: one wave per 64 columns of a row */
+  int32_t blocks, waves_per_block; /* the launch */
+  int32_t add_variant;             /* the lce_hip_add_int8_variant_id of the ADD, -1 without one */
+  int32_t mul_variant;             /* 0: LITERAL, 1: FAST (proven for these parameters) */
+  /* With an ADD, what its variant's kernel is given, so that a simulation on the host runs that kernel and no other (zeros
+   * without): whether the product is the kernel's first input (the host puts a shift-form input first), and the parameters in
+   * that order -- z1, z2, zo, m1, n1, m2, n2, mo, no, lo, hi (n = -shift), then ka, kb, c, ml, mh, nb, half_b, half_o,
+   * lo - zo, hi - zo of the SPLIT and SHIFT variants. */
+  int32_t product_first;
+  int32_t add_args[21];
+} lce_hip_mul_int8_launch;
+lce_hip_status lce_hip_mul_int8_prepare(const lce_hip_mul_int8_desc* desc, lce_hip_mul_int8_params* params);
+lce_hip_status lce_hip_mul_int8(const lce_hip_mul_int8_desc* desc, const int8_t* in1_dev, const int8_t* in2_dev,
+                                const int8_t* addend_dev /* NULL without has_add */, size_t rows, size_t channels,
+                                size_t rows_per_image, int8_t* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */,
+                                void* stream);
+lce_hip_status lce_hip_mul_int8_path(const lce_hip_mul_int8_desc* desc, size_t rows, size_t channels, size_t rows_per_image,
+                                     const int8_t* in1_dev, const int8_t* in2_dev, const int8_t* addend_dev, const int8_t* out_dev,
+                                     const int32_t* out_bits_dev, lce_hip_mul_int8_launch* launch);
+
+/* TFLite's builtin int8 LOGISTIC as a 256-byte table; the launch is the ONE_ROW path of lce_hip_elementwise_i8's kernels.
+ *   lce_hip_logistic_int8_prepare: host only.  For v in -128..127, in float32:
+ *       x = fl(si * fl(v - zi));  y = LOGISTIC(x) as lce_hip_elementwise_ex states it (E(a) of lce_hip_softmax_f32), evaluated on
+ *       the host;  table[v + 128] = clamp(round_half_away(fl(y * 256)) - 128, -128, 127)
+ *     The output quantization must be exactly (1/256, -128), as TFLite fixes it; anything else is refused, as are an input scale
+ *     that is not finite and positive and an input zero point outside [-128, 127].  `table` NULL: the checks alone.
+ *   lce_hip_logistic_int8: [rows, channels] int8 of any rows (the gate's tensor is [b, C]); `table_dev`: the table on the device,
+ *     4-byte aligned; `out_dev` (nullable, may be in_dev) and `out_bits_dev` (nullable: bit = out < -128, so every bit is 0) as
+ *     above.  channels < 2^22, lce_hip_elementwise_i8's own bound.  Zero rows or channels is a no-op; both outputs NULL, a NULL
+ *     `table_dev` and a NULL `in_dev` are refused, each by name.  Asynchronous on `stream`, capturable in a HIP graph, allocates
+ *     and copies nothing. */
+lce_hip_status lce_hip_logistic_int8_prepare(float in_scale, int32_t in_zero_point, float out_scale, int32_t out_zero_point,
+                                             uint8_t* table /* [256], nullable */);
+lce_hip_status lce_hip_logistic_int8(const uint8_t* table_dev, const int8_t* in_dev, size_t rows, size_t channels,
+                                     int8_t* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Channel join between binary layers (TFLite builtin CONCATENATION) and the LceQuantize that follows

@@ -164,7 +164,7 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
 
 /* lce_tflite_model_open with the opt-ins NAMED: `passes` is a comma-separated list (no spaces) drawn from
  *   elementwise, int8_add, concat, pool, conv1x1, depthwise, conv2d, stem, head, conv2d_i8, head_i8, quantize, depthwise_i8, activation, reshape, gate,
- *   binary_dense, slice, elementwise_i8
+ *   binary_dense, slice, elementwise_i8, gate_i8
  * "" is exactly lce_tflite_model_open.  The first eight names set exactly the bits LCE_TFLITE_SECTIONS_ELEMENTWISE ..
  * LCE_TFLITE_SECTIONS_EXT_STEM set through lce_tflite_model_open_opts, so the partition is the same.  NULL, an unknown name (an
  * empty one included) and a name given twice are refused; the message names the offender.  lce_tflite_model_open_opts and
@@ -321,9 +321,27 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   ADD whose sum only such a chain reads becomes the chain's head instead of a launch of its own: that launch is counted by
  *   lce_tflite_model_elementwise_i8_stats (the ADD among its operators), not by lce_tflite_model_int8_add_stats.  With
  *   `int8_add,elementwise_i8` the body of an int8 ReActNet is ONE section and each block's tail ONE launch.  Without the name
- *   every partition, launch and counter is what it was; with it a float file's partition is unchanged.  Still the host's: int8
- *   MUL and int8 LOGISTIC (and with them the squeeze-and-excite gate of an int8 RealToBinaryNet), a full [H,W,C] alpha, a
- *   non-constant alpha, per-channel-quantized constants, uint8 / int16 tensors, rank-2 tensors. */
+ *   every partition, launch and counter is what it was; with it a float file's partition is unchanged.  Still the host's: a full
+ *   [H,W,C] alpha, a non-constant alpha, per-channel-quantized constants, uint8 / int16 tensors, rank-2 tensors (int8 MUL and int8
+ *   LOGISTIC are gate_i8's).
+ *   gate_i8: the squeeze-and-excite gate of an int8-converted RealToBinaryNet block -- y = LceBconv2d (int8 out); MEAN(y),
+ *   FULLY_CONNECTED, FULLY_CONNECTED, LOGISTIC, RESHAPE [b,1,1,C]; ADD(MUL(y, gate), x) -- joins the sections (MEAN and
+ *   FULLY_CONNECTED through head_i8, RESHAPE through reshape, the ADD through int8_add).  An int8 LOGISTIC qualifies with one
+ *   non-constant input and an output of the same shape, of rank 2 or 4 with positive extents, both with ONE scale and a zero point
+ *   in [-128, 127], when lce_hip_logistic_int8_prepare accepts the quantization (the output at exactly (1/256, -128)); its 256-byte
+ *   table is uploaded once per model and the launch is lce_hip_logistic_int8.  An int8 MUL qualifies with two non-constant inputs
+ *   and a 4-D output with positive extents, all with ONE scale and a zero point in [-128, 127], one input of the output's shape and
+ *   the other of that shape too or [b,1,1,C] (in either slot; a [b,C] operand does not qualify), an activation in NONE..RELU6, when
+ *   lce_hip_mul_int8_prepare accepts; a constant operand stays with the host.  Both join the epoch in which they become ready.
+ *   lce_tflite_model_run_section launches lce_hip_mul_int8 ONCE per MUL.  With int8_add also named, when the product's ONLY reader
+ *   is an absorbed residual int8 ADD of the same shape and the section does not deliver the product, the MUL and the ADD are ONE
+ *   launch (has_add; the product is never written, and lce_tflite_model_section_tensor_shape refuses it): the ADD is then
+ *   counted by lce_tflite_model_gate_i8_stats, not by lce_tflite_model_int8_add_stats.  An ADD whose other input has no buffer of
+ *   its own (the channel window of an absorbed slice) is not fused.  Otherwise the ADD stays int8_add's.  Either way the first LceQuantize that reads the result
+ *   folds into the launch, and the int8 tensor is written only if something else reads it.  With
+ *   `head_i8,reshape,int8_add,gate_i8` the body of an int8 RealToBinaryNet is ONE section.  Without the name every partition,
+ *   launch and counter is what it was; with it a float file's partition is unchanged.  Still the host's: int8 MUL by a constant,
+ *   a [b,C] operand, uint8 / int16 tensors. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -438,7 +456,9 @@ lce_hip_status lce_tflite_model_run_section(lce_tflite_model* model, int32_t sec
 /* Shape ([N,H,W,C], C in words for bitpacked tensors) and size in bytes of a tensor section `section` reads or produces,
  * at `batch` images.  The walk is 4-D throughout: a rank-2 tensor of the classifier head ([b, C] in the file: the output of a
  * MEAN, a FULLY_CONNECTED or a SOFTMAX) reports {batch, 1, 1, C}; the bytes are the same, and the caller restores the file's
- * rank.  Host-only (no device needed). */
+ * rank.  A product that an int8 MUL hands to its residual ADD inside one lce_hip_mul_int8 launch ("gate_i8" with "int8_add") is
+ * never written and is no tensor of the walk: asking for it is refused like a tensor the section does not touch.  Host-only
+ * (no device needed). */
 lce_hip_status lce_tflite_model_section_tensor_shape(lce_tflite_model* model, int32_t section, int32_t tensor, int32_t batch,
                                                      int32_t semantics, int32_t dims[4], size_t* bytes);
 
@@ -501,6 +521,10 @@ void lce_tflite_model_slice_stats(lce_tflite_model* model, int32_t* launches, in
  * operators of every kind inside them (a residual ADD taken as a chain's head included) and LceQuantize launches folded into
  * them.  Any pointer may be NULL. */
 void lce_tflite_model_elementwise_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
+/* The LAST run's lce_hip_mul_int8 launches ("gate_i8" of lce_tflite_model_open_passes): launches (one per absorbed int8 MUL), the
+ * MUL and residual ADD operators inside them (2 for a launch with has_add, 1 otherwise) and LceQuantize launches folded into
+ * them.  The int8 LOGISTIC launches are not among them.  Any pointer may be NULL. */
+void lce_tflite_model_gate_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a
