@@ -47,6 +47,8 @@ ABI_SYMBOLS = (
     "lce_hip_conv2d_i8", "lce_hip_conv2d_i8_check", "lce_hip_conv2d_i8_prepare",
     "lce_hip_depthwise_conv2d_i8", "lce_hip_depthwise_conv2d_i8_check", "lce_hip_depthwise_conv2d_i8_prepare",
     "lce_hip_depthwise_conv2d_i8_path", "lce_hip_depthwise_conv2d_i8_forced",
+    "lce_hip_pool_depthwise_f32", "lce_hip_pool_depthwise_f32_check", "lce_hip_pool_depthwise_f32_path", "lce_hip_pool_depthwise_f32_forced",
+    "lce_hip_pool_depthwise_i8", "lce_hip_pool_depthwise_i8_check", "lce_hip_pool_depthwise_i8_path", "lce_hip_pool_depthwise_i8_forced",
     "lce_hip_fully_connected_f32", "lce_hip_fully_connected_f32_check", "lce_hip_softmax_f32", "lce_hip_softmax_f32_check",
     "lce_hip_bfc_check", "lce_hip_bfc_prepare", "lce_hip_binary_fully_connected",
     "lce_hip_fully_connected_i8", "lce_hip_fully_connected_i8_check", "lce_hip_fully_connected_i8_prepare",
@@ -300,6 +302,12 @@ def lib() -> C.CDLL:
                                                           C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         l.lce_hip_depthwise_conv2d_i8_path.argtypes = [C.POINTER(DepthwiseI8Desc)] + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)]
         l.lce_hip_depthwise_conv2d_i8_forced.argtypes = [C.POINTER(DepthwiseI8Desc), C.c_int32] + [C.c_void_p] * 6
+        for kind, dw in (("f32", DepthwiseDesc), ("i8", DepthwiseI8Desc)):
+            descs = [C.POINTER(Pool2dDesc), C.POINTER(dw)]
+            getattr(l, "lce_hip_pool_depthwise_%s_check" % kind).argtypes = descs + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            getattr(l, "lce_hip_pool_depthwise_%s" % kind).argtypes = descs + [C.c_void_p] * 6
+            getattr(l, "lce_hip_pool_depthwise_%s_path" % kind).argtypes = descs + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)]
+            getattr(l, "lce_hip_pool_depthwise_%s_forced" % kind).argtypes = descs + [C.c_int32] + [C.c_void_p] * 6
         l.lce_hip_fully_connected_f32.argtypes = [C.POINTER(FcDesc)] + [C.c_void_p] * 5
         l.lce_hip_fully_connected_f32_check.argtypes = [C.POINTER(FcDesc)]
         l.lce_hip_softmax_f32.argtypes = [C.c_size_t, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1639,6 +1647,76 @@ def depthwise_conv2d_i8(x, filter, table, q_in, q_out, stride=1, padding=PADDING
             took.value = int(path)
     res = _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
     return (*res, int(took.value)) if report_path else res
+
+
+class _Pooled:
+    """The shape and dtype of a pooled tensor that is never made: what the depthwise checks ask of their input."""
+
+    def __init__(self, shape, dtype):
+        self.shape, self.dtype = shape, dtype
+
+
+def _pool_depthwise_run(who, kind, descs, shape, x, constants, out, out_bits, stream, path, report_path):
+    """The run ``pool_depthwise`` and ``pool_depthwise_i8`` share: the entry's own choice of path (reported by ``..._path``) or a
+    forced one."""
+    import torch
+    if path not in (None, 0, 1):
+        raise ValueError("%s: path must be None, 0 or 1, got %r" % (who, path))
+    host = isinstance(x, np.ndarray)
+    dev = torch.device("cuda:0") if host else x.device
+    on_dev = lambda a: _on_dev(a, dev, who, "x's")
+    xd = on_dev(x)
+    operands = [None if c is None else on_dev(c) for c in constants]
+    out_d = None if out is False else torch.empty(shape, dtype=xd.dtype, device=dev) if out is True else on_dev(out)
+    bits_d = None if (out_bits is False or out_bits is None) else _new_bits(shape[:-1], shape[-1], dev) if out_bits is True else on_dev(out_bits)
+    ptrs = [_dev_ptr(t) for t in (xd, *operands, out_d, bits_d)]
+    refs = [C.byref(d) for d in descs]
+    took = C.c_int32(-1)
+    with torch.cuda.device(dev):
+        st = C.c_void_p(_stream_or_current(stream, dev))
+        if path is None:
+            check(getattr(lib(), "lce_hip_pool_depthwise_%s_path" % kind)(*refs, *ptrs, C.byref(took)))
+            check(getattr(lib(), "lce_hip_pool_depthwise_%s" % kind)(*refs, *ptrs, st))
+        else:
+            check(getattr(lib(), "lce_hip_pool_depthwise_%s_forced" % kind)(*refs, int(path), *ptrs, st))
+            took.value = int(path)
+    res = _results(host, out_d, bits_d, None if out is True else out, None if out_bits is True else out_bits)
+    return (*res, int(took.value)) if report_path else res
+
+
+def pool_depthwise(x, pool_filter, filter, bias=None, pool_stride=1, pool_padding=PADDING_SAME, pool_activation=ACT_NONE, stride=1,
+                   padding=PADDING_SAME, depth_multiplier=1, activation=ACT_NONE, out=True, out_bits=False, stream: int | None = None,
+                   path: int | None = None, report_path: bool = False):
+    """A float MAX_POOL_2D and the DEPTHWISE_CONV_2D that reads it (QuickNet's transition: pool 2x2 / 1 SAME, then the 3x3 / 2
+    blur) and the LceQuantize of the result, in ONE launch that never writes the pooled tensor (``lce_hip_pool_depthwise_f32``).
+    The bytes are those of ``pool2d(x, POOL_MAX, pool_filter, pool_stride, pool_padding, pool_activation)`` followed by
+    ``depthwise_conv2d(pooled, filter, bias, stride, padding, depth_multiplier, activation)``; the arguments are theirs.  ``path``:
+    None for the entry's own choice; 0 forces the row path (any geometry) and 1 the 16-byte path (pool stride 1 and filter <= 2 x 2,
+    depthwise filter <= 3 x 3, multiplier 1, channels % 4 == 0, % 32 with bits) -- for tests and measurements, the bytes are the
+    same.  Returns ``(out or None, bits or None)``, and with ``report_path`` a third value: 1 when the launch took the 16-byte path."""
+    who = "pool_depthwise"
+    if _dtype_name(x) != "float32":
+        raise ValueError("%s: x must be a float32 NHWC tensor, got %s" % (who, x.dtype))
+    pdesc, pooled = _pool2d_check(x, POOL_MAX, pool_filter, pool_stride, pool_padding, pool_activation, True, False, None, 0)
+    ddesc, shape = _depthwise_check(_Pooled(pooled, x.dtype), filter, bias, stride, padding, depth_multiplier, activation, out, out_bits)
+    return _pool_depthwise_run(who, "f32", (pdesc, ddesc), shape, x, (filter, bias), out, out_bits, stream, path, report_path)
+
+
+def pool_depthwise_i8(x, pool_filter, filter, table, q_in, q_out, pool_stride=1, pool_padding=PADDING_SAME, pool_activation=ACT_NONE, stride=1,
+                      padding=PADDING_SAME, depth_multiplier=1, activation=ACT_NONE, out=True, out_bits=False, stream: int | None = None,
+                      path: int | None = None, report_path: bool = False):
+    """The int8 form (``lce_hip_pool_depthwise_i8``): ``q_in`` = (scale, zero_point) is the quantization of ``x`` AND of the pooled
+    tensor (TFLite's pools keep it), ``table`` comes from ``depthwise_conv2d_i8_prepare`` for the same filter, ``q_in``, ``q_out``
+    and activation.  The bytes are those of ``pool2d(x, POOL_MAX, ..., scale, zero_point)`` followed by ``depthwise_conv2d_i8``;
+    ``path`` and ``report_path`` as ``pool_depthwise``'s (the 16-byte path needs channels % 16 == 0)."""
+    who = "pool_depthwise_i8"
+    si, zi, _, _ = _conv2d_i8_quantization(who, q_in, q_out)
+    if _dtype_name(x) != "int8":
+        raise ValueError("%s: x must be an int8 NHWC tensor, got %s" % (who, x.dtype))
+    pdesc, pooled = _pool2d_check(x, POOL_MAX, pool_filter, pool_stride, pool_padding, pool_activation, True, False, si, zi)
+    ddesc, shape = _depthwise_i8_check(_Pooled(pooled, x.dtype), filter, table, q_in, q_out, stride, padding, depth_multiplier, activation, out,
+                                       out_bits)
+    return _pool_depthwise_run(who, "i8", (pdesc, ddesc), shape, x, (filter, table), out, out_bits, stream, path, report_path)
 
 
 def _fully_connected_check(x, w, bias, activation, out):

@@ -30,6 +30,7 @@
 #include "lce_kernels_head.h"        // (lce_tu_head.hip)
 #include "lce_kernels_head_i8.h"     // (lce_tu_head_i8.hip)
 #include "lce_kernels_depthwise_i8.h"   // (lce_tu_depthwise_i8.hip)
+#include "lce_kernels_transition.h"     // (lce_tu_transition.hip)
 #include "lce_kernels_bfc.h"         // (lce_tu_bfc.hip)
 #ifdef LCE_UNITY
 // single-translation-unit build (tools/build_exp.sh): the time-stamp tools read __device__ arrays that must exist once
@@ -61,6 +62,7 @@
 #include "lce_tu_head.hip"
 #include "lce_tu_head_i8.hip"
 #include "lce_tu_depthwise_i8.hip"
+#include "lce_tu_transition.hip"
 #include "lce_tu_bfc.hip"
 #endif
 #include "lce_plan.h"
@@ -2466,6 +2468,214 @@ lce_hip_status lce_hip_depthwise_conv2d_i8_forced(const lce_hip_depthwise_i8_des
   const char* who = "lce_hip_depthwise_conv2d_i8_forced";
   if (path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
   return depthwise_i8_run(who, d, path, in_dev, filter_dev, table_dev, out_dev, out_bits_dev, stream, nullptr, true);
+}
+
+// ------------------------------------------------------------------------------------
+// A transition's MAX_POOL_2D and DEPTHWISE_CONV_2D in one launch (lce_kernels_transition.h)
+// ------------------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// What the two fused checks share once each entry's own check has accepted its descriptor: `pooled_h` x `pooled_w` are the pool's
+// output extents, `dw` the depthwise window.  The pool must be of the entry's type, the depthwise convolution must read the
+// pool's output, and only then is AVERAGE told apart as unsupported.
+lce_hip_status pool_depthwise_join_check(const char* who, const lce_hip_pool2d_desc* pool, int32_t type, int32_t pooled_h, int32_t pooled_w,
+                                         const lce_hip_depthwise_desc& dw) {
+  if (pool->type != type)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the pool's type must be %s, got %d", who, type == LCE_HIP_I8 ? "int8" : "float32", (int)pool->type);
+  if (dw.batch != pool->batch || dw.in_height != pooled_h || dw.in_width != pooled_w || dw.channels_in != pool->channels)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the depthwise input [%d, %d, %d, %d] is not the pool's output [%d, %d, %d, %d]", who, (int)dw.batch,
+                (int)dw.in_height, (int)dw.in_width, (int)dw.channels_in, (int)pool->batch, (int)pooled_h, (int)pooled_w, (int)pool->channels);
+  return LCE_HIP_OK;
+}
+lce_hip_status pool_depthwise_op_check(const char* who, const lce_hip_pool2d_desc* pool) {
+  if (pool->op != LCE_HIP_POOL_MAX) return fail(LCE_HIP_ERR_UNSUPPORTED, "%s: only a MAX pool runs in the depthwise convolution's launch", who);
+  return LCE_HIP_OK;
+}
+
+lce_hip_status pool_depthwise_f32_desc_check(const char* who, const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, int32_t* pooled_h,
+                                             int32_t* pooled_w, int32_t* out_height, int32_t* out_width) {
+  if (!pool || !dw) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (lce_hip_status s = lce_hip_pool2d_check(pool, pooled_h, pooled_w)) return s;
+  if (lce_hip_status s = depthwise_desc_check(who, dw, out_height, out_width)) return s;
+  if (lce_hip_status s = pool_depthwise_join_check(who, pool, LCE_HIP_F32, *pooled_h, *pooled_w, *dw)) return s;
+  return pool_depthwise_op_check(who, pool);
+}
+lce_hip_status pool_depthwise_i8_desc_check(const char* who, const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, int32_t* pooled_h,
+                                            int32_t* pooled_w, int32_t* out_height, int32_t* out_width) {
+  if (!pool || !dw) return fail(LCE_HIP_ERR_INVALID, "%s: null desc", who);
+  if (lce_hip_status s = lce_hip_pool2d_check(pool, pooled_h, pooled_w)) return s;
+  if (lce_hip_status s = depthwise_i8_desc_check(who, dw, out_height, out_width)) return s;
+  if (lce_hip_status s = pool_depthwise_join_check(who, pool, LCE_HIP_I8, *pooled_h, *pooled_w, depthwise_i8_window(dw))) return s;
+  // (the pooled tensor is the pool's input requantized by nothing: TFLite's Prepare requires one scale and zero point of both)
+  if (dw->input_scale != pool->scale || dw->input_zero_point != pool->zero_point)
+    return fail(LCE_HIP_ERR_INVALID, "%s: the depthwise input's quantization (%g, %d) is not the pool's (%g, %d)", who, (double)dw->input_scale,
+                (int)dw->input_zero_point, (double)pool->scale, (int)pool->zero_point);
+  return pool_depthwise_op_check(who, pool);
+}
+
+// The geometry of both fused launches: the depthwise window on the pooled map into `p`, the pool in front into `q`.
+void pool_depthwise_fill(lce::PoolArgs& p, lce::TransitionPool& q, const lce_hip_pool2d_desc* pool, int32_t pooled_h, int32_t pooled_w,
+                         const lce_hip_depthwise_desc& dw, int32_t oh, int32_t ow, uint64_t C, uint64_t chunk, bool vec) {
+  p.H = pooled_h; p.W = pooled_w; p.OH = oh; p.OW = ow;
+  p.fh = dw.filter_height; p.fw = dw.filter_width; p.sh = dw.stride_height; p.sw = dw.stride_width;
+  p.ph = same_pad_before(oh, dw.stride_height, dw.filter_height, pooled_h);
+  p.pw = same_pad_before(ow, dw.stride_width, dw.filter_width, pooled_w);
+  p.channels = (uint32_t)C;
+  p.wpr = (uint32_t)((C + 31) / 32);
+  p.per_pixel = (uint32_t)(vec ? C / chunk : (C + 63) / 64);
+  p.total = (uint64_t)dw.batch * oh * ow * p.per_pixel;
+  p.div_ow = lce::make_fastdiv((uint32_t)ow);
+  p.div_oh = lce::make_fastdiv((uint32_t)oh);
+  if (vec) pool_vec_steps(p);
+  q.H = pool->in_height; q.W = pool->in_width;
+  q.fh = pool->filter_height; q.fw = pool->filter_width; q.sh = pool->stride_height; q.sw = pool->stride_width;
+  q.ph = same_pad_before(pooled_h, pool->stride_height, pool->filter_height, pool->in_height);
+  q.pw = same_pad_before(pooled_w, pool->stride_width, pool->filter_width, pool->in_width);
+  float_activation_range(pool->activation, &q.lo, &q.hi);
+  if (pool->type == LCE_HIP_I8) quantized_activation_range(pool->activation, pool->scale, pool->zero_point, &q.qlo, &q.qhi);
+}
+
+// The path both fused entries take: `vec` says whether the operands qualify for the 16-byte path; `path` is -1 (the entry's own
+// choice), 0 or 1.
+lce_hip_status pool_depthwise_path(const char* who, int32_t path, bool* vec, const char* needs) {
+  if (path != -1 && path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
+  if (path == 1 && !*vec) return fail(LCE_HIP_ERR_INVALID, "%s: the 16-byte path needs %s", who, needs);
+  if (path == 0) *vec = false;
+  return LCE_HIP_OK;
+}
+
+// The launch of lce_hip_pool_depthwise_f32 and of its forced form (`path`, `took`, `launch`: as depthwise_i8_run's).
+lce_hip_status pool_depthwise_f32_run(const char* who, const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, int32_t path,
+                                      const float* in_dev, const float* filter_dev, const float* bias_dev, float* out_dev, int32_t* out_bits_dev,
+                                      void* stream, int32_t* took, bool launch) {
+  if (lce_hip_status s = check_pointers(who, pool, in_dev, /*has_filter=*/true, filter_dev, out_dev, out_bits_dev)) return s;
+  int32_t qh = 0, qw = 0, oh = 0, ow = 0;
+  if (lce_hip_status s = pool_depthwise_f32_desc_check(who, pool, dw, &qh, &qw, &oh, &ow)) return s;
+  const uint64_t Cin = (uint64_t)dw->channels_in, C = Cin * (uint64_t)dw->depth_multiplier;
+  const uint64_t pixels = (uint64_t)dw->batch * oh * ow, wpr = (C + 31) / 32;
+  const Span in(in_dev, (uint64_t)pool->batch * pool->in_height * pool->in_width * Cin * 4);
+  const Span filter(filter_dev, (uint64_t)dw->filter_height * dw->filter_width * C * 4), bias(bias_dev, C * 4);
+  const Span out(out_dev, pixels * C * 4), bits(out_bits_dev, pixels * wpr * 4);
+  if (lce_hip_status s = check_operand_ranges(who, in, filter, bias, out, bits, /*float_operands=*/true)) return s;
+  lce::TransitionArgs a;
+  memset(&a, 0, sizeof a);
+  a.Q.fh = pool->filter_height; a.Q.fw = pool->filter_width; a.Q.sh = pool->stride_height; a.Q.sw = pool->stride_width;
+  bool vec = dw->depth_multiplier == 1 && C % 4 == 0 && (in.lo | filter.lo | bias.lo | out.lo) % 16 == 0 &&
+             lce::transition_vec_geometry(a.Q, dw->filter_height, dw->filter_width);
+  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
+  if (lce_hip_status s = pool_depthwise_path(who, path, &vec, "depth_multiplier 1, channels % 4 == 0 (% 32 with bits), 16-byte aligned input, "
+                                             "filter, bias and output, a pool of stride 1 and at most 2 x 2 and a depthwise filter of at most 3 x 3"))
+    return s;
+  if (took) *took = vec ? 1 : 0;
+  if (!launch) return LCE_HIP_OK;
+  if (lce_hip_status s = require_device()) return s;
+  lce::PoolArgs& p = a.D.P;
+  p.in = in_dev; p.out = out_dev; p.bits = (uint32_t*)out_bits_dev;
+  a.D.filter = filter_dev; a.D.bias = bias_dev;
+  a.D.channels_in = (uint32_t)Cin;
+  a.D.div_multiplier = lce::make_fastdiv((uint32_t)dw->depth_multiplier);
+  pool_depthwise_fill(p, a.Q, pool, qh, qw, *dw, oh, ow, C, 4, vec);
+  float_activation_range(dw->activation, &p.lo, &p.hi);
+  const int e = lce::launch_transition(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+
+// The launch of lce_hip_pool_depthwise_i8 and of its forced form.
+lce_hip_status pool_depthwise_i8_run(const char* who, const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, int32_t path,
+                                     const int8_t* in_dev, const int8_t* filter_dev, const int32_t* table_dev, int8_t* out_dev, int32_t* out_bits_dev,
+                                     void* stream, int32_t* took, bool launch) {
+  if (lce_hip_status s = check_pointers(who, pool, in_dev, /*has_filter=*/true, filter_dev, out_dev, out_bits_dev)) return s;
+  if (!table_dev) return fail(LCE_HIP_ERR_INVALID, "%s: null table", who);
+  int32_t qh = 0, qw = 0, oh = 0, ow = 0;
+  if (lce_hip_status s = pool_depthwise_i8_desc_check(who, pool, dw, &qh, &qw, &oh, &ow)) return s;
+  const uint64_t Cin = (uint64_t)dw->channels_in, C = Cin * (uint64_t)dw->depth_multiplier;
+  const uint64_t pixels = (uint64_t)dw->batch * oh * ow, wpr = (C + 31) / 32;
+  const Span in(in_dev, (uint64_t)pool->batch * pool->in_height * pool->in_width * Cin);
+  const Span filter(filter_dev, (uint64_t)dw->filter_height * dw->filter_width * C), table(table_dev, 3 * C * 4);
+  const Span out(out_dev, pixels * C), bits(out_bits_dev, pixels * wpr * 4);
+  if (meet(out.lo, out.hi, table.lo, table.hi) || meet(bits.lo, bits.hi, table.lo, table.hi))
+    return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the table", who);
+  if (lce_hip_status s = check_operand_ranges(who, in, filter, Span(nullptr, 0), out, bits, /*float_operands=*/false)) return s;
+  if (table.lo % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: table_dev must be 4-byte aligned", who);
+  lce::TransitionI8Args a;
+  memset(&a, 0, sizeof a);
+  a.Q.fh = pool->filter_height; a.Q.fw = pool->filter_width; a.Q.sh = pool->stride_height; a.Q.sw = pool->stride_width;
+  bool vec = dw->depth_multiplier == 1 && C % 16 == 0 && (in.lo | filter.lo | table.lo | out.lo) % 16 == 0 &&
+             lce::transition_vec_geometry(a.Q, dw->filter_height, dw->filter_width);
+  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
+  if (lce_hip_status s = pool_depthwise_path(who, path, &vec, "depth_multiplier 1, channels % 16 == 0 (% 32 with bits), 16-byte aligned input, "
+                                             "filter, table and output, a pool of stride 1 and at most 2 x 2 and a depthwise filter of at most 3 x 3"))
+    return s;
+  if (took) *took = vec ? 1 : 0;
+  if (!launch) return LCE_HIP_OK;
+  if (lce_hip_status s = require_device()) return s;
+  lce::PoolArgs& p = a.D.P;
+  p.in = in_dev; p.out = out_dev; p.bits = (uint32_t*)out_bits_dev;
+  a.D.filter = filter_dev; a.D.table = table_dev;
+  a.D.zi = dw->input_zero_point;
+  a.D.channels_in = (uint32_t)Cin;
+  a.D.div_multiplier = lce::make_fastdiv((uint32_t)dw->depth_multiplier);
+  pool_depthwise_fill(p, a.Q, pool, qh, qw, depthwise_i8_window(dw), oh, ow, C, 16, vec);
+  quantized_activation_range(dw->activation, dw->output_scale, dw->output_zero_point, &p.qlo, &p.qhi);
+  p.zero_point = dw->output_zero_point;
+  const int e = lce::launch_transition_i8(a, vec, stream);
+  if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
+  return LCE_HIP_OK;
+}
+}  // namespace
+extern "C" {
+
+lce_hip_status lce_hip_pool_depthwise_f32_check(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, int32_t* out_height,
+                                                int32_t* out_width) {
+  int32_t qh = 0, qw = 0, oh = 0, ow = 0;
+  if (lce_hip_status s = pool_depthwise_f32_desc_check("lce_hip_pool_depthwise_f32", pool, dw, &qh, &qw, &oh, &ow)) return s;
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+lce_hip_status lce_hip_pool_depthwise_f32(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, const float* in_dev,
+                                          const float* filter_dev, const float* bias_dev, float* out_dev, int32_t* out_bits_dev, void* stream) {
+  return pool_depthwise_f32_run("lce_hip_pool_depthwise_f32", pool, dw, -1, in_dev, filter_dev, bias_dev, out_dev, out_bits_dev, stream, nullptr, true);
+}
+lce_hip_status lce_hip_pool_depthwise_f32_path(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, const float* in_dev,
+                                               const float* filter_dev, const float* bias_dev, const float* out_dev, const int32_t* out_bits_dev,
+                                               int32_t* path) {
+  const char* who = "lce_hip_pool_depthwise_f32_path";
+  if (!path) return fail(LCE_HIP_ERR_INVALID, "%s: null path", who);
+  return pool_depthwise_f32_run(who, pool, dw, -1, in_dev, filter_dev, bias_dev, (float*)out_dev, (int32_t*)out_bits_dev, nullptr, path, false);
+}
+lce_hip_status lce_hip_pool_depthwise_f32_forced(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, int32_t path, const float* in_dev,
+                                                 const float* filter_dev, const float* bias_dev, float* out_dev, int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_pool_depthwise_f32_forced";
+  if (path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
+  return pool_depthwise_f32_run(who, pool, dw, path, in_dev, filter_dev, bias_dev, out_dev, out_bits_dev, stream, nullptr, true);
+}
+
+lce_hip_status lce_hip_pool_depthwise_i8_check(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, int32_t* out_height,
+                                               int32_t* out_width) {
+  int32_t qh = 0, qw = 0, oh = 0, ow = 0;
+  if (lce_hip_status s = pool_depthwise_i8_desc_check("lce_hip_pool_depthwise_i8", pool, dw, &qh, &qw, &oh, &ow)) return s;
+  if (out_height) *out_height = oh;
+  if (out_width) *out_width = ow;
+  return LCE_HIP_OK;
+}
+lce_hip_status lce_hip_pool_depthwise_i8(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, const int8_t* in_dev,
+                                         const int8_t* filter_dev, const int32_t* table_dev, int8_t* out_dev, int32_t* out_bits_dev, void* stream) {
+  return pool_depthwise_i8_run("lce_hip_pool_depthwise_i8", pool, dw, -1, in_dev, filter_dev, table_dev, out_dev, out_bits_dev, stream, nullptr, true);
+}
+lce_hip_status lce_hip_pool_depthwise_i8_path(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, const int8_t* in_dev,
+                                              const int8_t* filter_dev, const int32_t* table_dev, const int8_t* out_dev, const int32_t* out_bits_dev,
+                                              int32_t* path) {
+  const char* who = "lce_hip_pool_depthwise_i8_path";
+  if (!path) return fail(LCE_HIP_ERR_INVALID, "%s: null path", who);
+  return pool_depthwise_i8_run(who, pool, dw, -1, in_dev, filter_dev, table_dev, (int8_t*)out_dev, (int32_t*)out_bits_dev, nullptr, path, false);
+}
+lce_hip_status lce_hip_pool_depthwise_i8_forced(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, int32_t path, const int8_t* in_dev,
+                                                const int8_t* filter_dev, const int32_t* table_dev, int8_t* out_dev, int32_t* out_bits_dev, void* stream) {
+  const char* who = "lce_hip_pool_depthwise_i8_forced";
+  if (path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
+  return pool_depthwise_i8_run(who, pool, dw, path, in_dev, filter_dev, table_dev, out_dev, out_bits_dev, stream, nullptr, true);
 }
 
 // ------------------------------------------------------------------------------------

@@ -28,7 +28,7 @@ enum { kAbsorbedElementwise = 1, kAbsorbedInt8Add, kAbsorbedConcat, kAbsorbedPoo
 // lce_tflite_model::flags_int: what only lce_tflite_model_open_passes can set
 enum { kInternalHead = 1u, kInternalConvI8 = 2u, kInternalHeadI8 = 4u, kInternalQuantize = 8u, kInternalDepthwiseI8 = 16u,
        kInternalActivation = 32u, kInternalReshape = 64u, kInternalGate = 128u, kInternalBinaryDense = 256u, kInternalSlice = 512u,
-       kInternalElementwiseI8 = 1024u, kInternalGateI8 = 2048u };
+       kInternalElementwiseI8 = 1024u, kInternalGateI8 = 2048u, kInternalTransition = 4096u };
 struct lce_tflite_model {
   lce_tfl::Model m;
   uint32_t flags = 0;                         // lce_tflite_model_open_ex
@@ -59,6 +59,8 @@ struct lce_tflite_model {
     int32_t slice_joins = 0;                                            // lce_hip_join_windows launches that took over a CONCATENATION
     int32_t ew_i8_ops = 0;                                              // operators of every kind inside the lce_hip_elementwise_i8 launches (a head ADD included)
     int32_t gate_i8_ops = 0;                                            // MUL and residual ADD operators inside the lce_hip_mul_int8 launches
+    int32_t transition_launches = 0, transition_ops = 0, transition_quantize = 0;   // lce_hip_pool_depthwise_f32 launches, the MAX_POOL_2D and
+                                                                        // DEPTHWISE_CONV_2D operators inside them, the LceQuantize launches folded into them
     struct Pass { int32_t launches = 0, quantize = 0; };                // launches of a fused pass, and the LceQuantize launches folded into them
     Pass pass[kAbsorbedCount];                                          // by kAbsorbed* kind ([0] unused)
   };
@@ -1165,8 +1167,9 @@ bool MulI8Candidate(const lce_tfl::Model& M, const lce_tfl::Operator& o) {
 }
 
 // THE names of lce_tflite_model_open_passes, each with the flag word (0 `flags`, 1 `flags_ext`, 2 `flags_int`) and the bit of it
-// that the name sets: the only place the three are written.  "stem" is a name that is no pass (Partition() reads its bit); "head",
-// "head_i8" and "quantize" enable several rows of kPasses each.
+// that the name sets: the only place the three are written.  "stem" is a name that is no pass (Partition() reads its bit), and so is
+// "transition" (Walk::Pool2d reads its bit: the partition does not move); "head", "head_i8" and "quantize" enable several rows of
+// kPasses each.
 struct PassName { const char* name; int word; uint32_t bit; };
 constexpr PassName kPassNames[] = {
     {"elementwise", 0, LCE_TFLITE_SECTIONS_ELEMENTWISE}, {"int8_add", 0, LCE_TFLITE_SECTIONS_INT8_ADD},
@@ -1178,7 +1181,8 @@ constexpr PassName kPassNames[] = {
     {"depthwise_i8", 2, kInternalDepthwiseI8},           {"activation", 2, kInternalActivation},
     {"reshape", 2, kInternalReshape},                    {"gate", 2, kInternalGate},
     {"binary_dense", 2, kInternalBinaryDense},           {"slice", 2, kInternalSlice},
-    {"elementwise_i8", 2, kInternalElementwiseI8},       {"gate_i8", 2, kInternalGateI8}};
+    {"elementwise_i8", 2, kInternalElementwiseI8},       {"gate_i8", 2, kInternalGateI8},
+    {"transition", 2, kInternalTransition}};
 // The entry of kPassNames called `name`; null when there is none.
 constexpr const PassName* Named(const char* name) {
   for (const PassName& n : kPassNames) {
@@ -2429,15 +2433,76 @@ struct Walk {
   }
 
   // ---- the windowed passes: the entry's own *_check of the descriptor at this walk's batch gives the output's height and width ----
-  // An absorbed AVERAGE_POOL_2D / MAX_POOL_2D (LCE_TFLITE_SECTIONS_EXT_POOL) as ONE lce_hip_pool2d launch.
+  // An absorbed AVERAGE_POOL_2D / MAX_POOL_2D (LCE_TFLITE_SECTIONS_EXT_POOL) as ONE lce_hip_pool2d launch -- unless "transition" is
+  // named and the pool is the front of a transition (Transition, below).
   lce_hip_status Pool2d(int32_t i) {
     const lce_tfl::Operator& op = model->m.operators[i];
     const lce_tfl::Tensor& in = model->m.tensors[op.inputs[0]];
     const lce_hip_pool2d_desc d = PoolDesc(model->m, op, batch);
     int32_t h = 0, w = 0;
     if (lce_hip_status s = lce_hip_pool2d_check(&d, &h, &w)) return s;
+    const int32_t reader = TransitionReader(i, d);
+    if (reader >= 0) return Transition(i, reader, d);
     return OnePass(i, "a pool", in.type, OutShape(h, w, in.shape[3], in.type), /*fold_quantize=*/true, /*constants=*/0,
                    [&](const void* x, const void*, const void*, void* out, int32_t* bits) { return lce_hip_pool2d(&d, x, out, bits, stream); });
+  }
+
+  // ---- a transition's pool and blur as one launch ("transition" of lce_tflite_model_open_passes) ----
+  // The DEPTHWISE_CONV_2D that takes pool `i` (descriptor `d`) into its launch, or -1: the name is given and the pool is a float
+  // MAX pool; the pooled tensor is not delivered and has exactly one reader; that reader is an absorbed float depthwise convolution
+  // in this section that has not run and reads the pooled tensor as its input; and the fused entry's own check accepts the two
+  // descriptors (which compares the shapes).  Decided from the graph and the descriptors alone, so a walk without launches decides
+  // as a run does.
+  // An int8 pair is left as two launches: lce_hip_pool_depthwise_i8 measured 1.09 - 1.24 of the two launches' time at QuickNet's
+  // three transitions (profiles/transition/layers.txt; the float entry 0.82 - 0.94).  The rule is: a type is fused here only if
+  // its fused launch is faster at all three shapes by more than the larger leg's spread.
+  int32_t TransitionReader(int32_t i, const lce_hip_pool2d_desc& d) const {
+    if (!(model->flags_int & kInternalTransition) || d.op != LCE_HIP_POOL_MAX || d.type != LCE_HIP_F32) return -1;
+    const lce_tfl::Model& M = model->m;
+    const int32_t pooled_t = M.operators[i].outputs[0];
+    const int32_t r = OnlyReader(pooled_t, i);
+    if (r < 0 || done[r] || model->absorbed[r] != kAbsorbedDepthwise) return -1;
+    const lce_tfl::Operator& dw = M.operators[r];
+    if (dw.inputs.empty() || dw.inputs[0] != pooled_t) return -1;
+    const lce_hip_depthwise_desc dd = DepthwiseDesc(M, dw, batch);
+    return lce_hip_pool_depthwise_f32_check(&d, &dd, nullptr, nullptr) == LCE_HIP_OK ? r : -1;
+  }
+  // Pool `i` and the depthwise convolution `r` that alone reads it as ONE lce_hip_pool_depthwise_f32 launch.  Both operators are
+  // marked done; the pooled tensor exists in registers only, so the walk holds no tensor of that name
+  // (lce_tflite_model_section_tensor_shape refuses it).  The first LceQuantize of the section that reads the blurred map folds in as
+  // it folds into the depthwise walker's launch.  The launch is counted by lce_tflite_model_transition_stats and by neither
+  // operator's own pass.
+  lce_hip_status Transition(int32_t i, int32_t r, const lce_hip_pool2d_desc& d) {
+    const lce_tfl::Model& M = model->m;
+    const lce_tfl::Operator &op = M.operators[i], &dw = M.operators[r];
+    int32_t want[4];
+    auto it = shapes.find(op.inputs[0]);
+    if (it == shapes.end()) return Fail(LCE_HIP_ERR_INVALID, "run_section: a pool reads a tensor nothing produced");
+    if (!Carried(M.tensors[op.inputs[0]], want) || !Agrees(it->second, lce_tfl::kTensorFloat32, want[1], want[2], want[3]))
+      return Fail(LCE_HIP_ERR_INVALID, "run_section: a pool input's shape or type does not match the one its producer infers");
+    const lce_hip_depthwise_desc dd = DepthwiseDesc(M, dw, batch);
+    int32_t h = 0, w = 0;
+    if (lce_hip_status s = lce_hip_pool_depthwise_f32_check(&d, &dd, &h, &w)) return s;
+    const int32_t out_t = dw.outputs[0];
+    const Shape os = OutShape(h, w, M.tensors[dw.inputs[1]].shape[3]);
+    shapes.erase(op.outputs[0]);
+    shapes[out_t] = os;
+    done[i] = done[r] = 1;
+    const Fold fold = FoldQuantize(r, out_t, os);
+    if (!run) return LCE_HIP_OK;
+    const void* in = nullptr;
+    if (lce_hip_status s = DevicePtr(op.inputs[0], "a pool input", &in)) return s;
+    const float *filter = nullptr, *bias = nullptr;
+    if (lce_hip_status s = ConstOnDevice(model, dw.inputs[1], stream, capturing, &filter)) return s;
+    if (dw.inputs.size() == 3 && dw.inputs[2] >= 0)
+      if (lce_hip_status s = ConstOnDevice(model, dw.inputs[2], stream, capturing, &bias)) return s;
+    void *out, *bits;
+    if (lce_hip_status s = FoldBuffers(fold, &out, &bits)) return s;
+    if (lce_hip_status s = lce_hip_pool_depthwise_f32(&d, &dd, (const float*)in, filter, bias, (float*)out, (int32_t*)bits, stream)) return s;
+    ++model->last.transition_launches;
+    model->last.transition_ops += 2;
+    if (fold.bits_t >= 0) ++model->last.transition_quantize;
+    return LCE_HIP_OK;
   }
 
   // An absorbed float 1x1 CONV_2D (LCE_TFLITE_SECTIONS_EXT_CONV1X1) as ONE lce_hip_conv1x1_f32 launch.
@@ -3047,6 +3112,9 @@ void lce_tflite_model_gate_i8_stats(lce_tflite_model* model, int32_t* launches, 
   Stats(model, [&](const RunStats& r) {
     Put(launches, r.pass[kAbsorbedMulI8].launches); Put(ops_folded, r.gate_i8_ops); Put(quantize_folded, r.pass[kAbsorbedMulI8].quantize);
   });
+}
+void lce_tflite_model_transition_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded) {
+  Stats(model, [&](const RunStats& r) { Put(launches, r.transition_launches); Put(ops_folded, r.transition_ops); Put(quantize_folded, r.transition_quantize); });
 }
 void lce_tflite_model_reshape_stats(lce_tflite_model* model, int32_t* views, int32_t* copies) {
   Stats(model, [&](const RunStats& r) { Put(views, r.reshape_views); Put(copies, r.reshape_copies); });

@@ -217,6 +217,8 @@ def tflite_lib() -> C.CDLL:
         l.lce_tflite_model_elementwise_i8_stats.restype = None
         l.lce_tflite_model_gate_i8_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
         l.lce_tflite_model_gate_i8_stats.restype = None
+        l.lce_tflite_model_transition_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int32)] * 3
+        l.lce_tflite_model_transition_stats.restype = None
         l.lce_tflite_model_close.argtypes = [C.c_void_p]
         for f in ("lce_tflite_model_num_tensors", "lce_tflite_model_num_operators"):
             getattr(l, f).argtypes = [C.c_void_p]
@@ -294,6 +296,10 @@ class LceModel:
         ``passes=("gate_i8",)``: the squeeze-and-excite gate of an int8 RealToBinaryNet block -- int8 LOGISTIC (a 256-byte table,
         ``lce_hip_logistic_int8``) and int8 MUL by a [b,1,1,C] gate or a tensor (``lce_hip_mul_int8``) -- joins the sections; with
         ``int8_add_sections`` the residual ADD that alone reads the product rides in the MUL's launch (``gate_i8_stats``).
+        ``passes=("transition",)``: no operator joins or leaves a section; an absorbed MAX_POOL_2D whose pooled tensor only an
+        absorbed DEPTHWISE_CONV_2D of the same section reads (QuickNet's float transition) runs with it as ONE
+        ``lce_hip_pool_depthwise_f32`` launch and the pooled tensor is never written (``transition_stats``); an int8 pair stays two
+        launches, which measured faster than ``lce_hip_pool_depthwise_i8`` (profiles/transition/layers.txt).
         ``elementwise_sections``: float ADD / MUL between binary layers join the sections (LCE_TFLITE_SECTIONS_ELEMENTWISE,
         include/lce_tflite_model.h); the host then runs only what lies outside them.  ``int8_add_sections``: the int8
         residual ADD between binary layers joins them (LCE_TFLITE_SECTIONS_INT8_ADD).  ``concat_sections``: the channel
@@ -506,6 +512,14 @@ class LceModel:
         run (the pass ``gate_i8``, asked for through ``passes``); the int8 LOGISTIC launches are not among them."""
         v = [C.c_int32() for _ in range(3)]
         tflite_lib().lce_tflite_model_gate_i8_stats(self._h, *[C.byref(c) for c in v])
+        return tuple(int(c.value) for c in v)
+
+    def transition_stats(self):
+        """(lce_hip_pool_depthwise_f32 launches, the MAX_POOL_2D and DEPTHWISE_CONV_2D operators inside them, LceQuantize
+        launches they absorbed) of the last run (the name ``transition``, asked for through ``passes``); such a launch is in
+        neither ``pool_stats`` nor ``depthwise_stats``."""
+        v = [C.c_int32() for _ in range(3)]
+        tflite_lib().lce_tflite_model_transition_stats(self._h, *[C.byref(c) for c in v])
         return tuple(int(c.value) for c in v)
 
     def reshape_stats(self):

@@ -800,6 +800,63 @@ lce_hip_status lce_hip_depthwise_conv2d_i8_forced(const lce_hip_depthwise_i8_des
                                                   int8_t* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * A transition's MAX_POOL_2D and the DEPTHWISE_CONV_2D that reads it, in one launch (float32 and int8)
+ * ---------------------------------------------------------------------------------- */
+
+/* QuickNet's transition pools 2x2 / 1 SAME and blurs the pooled map, which is as large as the pool's input, with the fixed
+ * 3x3 / 2 depthwise filter.  lce_hip_pool_depthwise_f32 / _i8 run lce_hip_pool2d (`pool`, op MAX) and lce_hip_depthwise_conv2d_f32
+ * / _i8 (`dw`, whose input is the pool's output) as ONE launch that never writes the pooled tensor.  The contract is the
+ * composition of the two entries' contracts.  Per output element, over the depthwise filter's in-bounds taps in raster order:
+ *   - the filter index is the unclipped one;
+ *   - a tap whose POOLED pixel lies outside the pooled map is skipped, as lce_hip_depthwise_conv2d_* skips it;
+ *   - the tap's operand is the pooled value lce_hip_pool2d would have stored there:
+ *       float : m = -FLT_MAX; m = (m < x) ? x : m over the pool window's in-bounds taps in raster order (a NaN never replaces
+ *               m; of +0.0 and -0.0 the first in raster order stays), then the clamp to the pool's activation range;
+ *       int8  : the maximum, clamped to the pool's CalculateActivationRangeQuantized at its (scale, zero_point);
+ *   - everything behind the pooled value is the depthwise entry's arithmetic, unchanged: float t = fmaf(p, w, t) from +0.0, one
+ *     float32 add of the bias, the clamp, bit = v < 0; int8 the exact int32 sum of (p - zi) w, lce_hip_depthwise_conv2d_i8_prepare's
+ *     table [3][Cout] used as it is, the requantization, + zo, the clamp, bit = v < zo.
+ * So `out_dev` and `out_bits_dev` (each nullable, not both) get, byte for byte, what lce_hip_pool2d followed by
+ * lce_hip_depthwise_conv2d_f32 / _i8 writes.
+ * lce_hip_pool_depthwise_*_check: host only, and the output extents (nullable).  LCE_HIP_ERR_INVALID: a NULL desc, what
+ *   lce_hip_pool2d_check or the depthwise entry's check refuses, a pool `type` that is not the entry's, a `dw` input (batch, extents,
+ *   channels) that is not the pool's output, for int8 a `dw` input (scale, zero point) that differs from the pool's.
+ *   LCE_HIP_ERR_UNSUPPORTED: what those checks report as unsupported (the 2^31 / 2^30 bounds), and pool `op` AVERAGE.
+ * The run entries refuse, before any device call and with LCE_HIP_ERR_INVALID, also a NULL input, filter or table, both outputs
+ *   NULL, an output that overlaps the input, the filter, the bias / table or the other output, and the misalignments the
+ *   depthwise entry refuses.  ONE launch, asynchronous on `stream`, capturable in a HIP graph; allocates nothing and copies
+ *   nothing; offsets are 64-bit beyond the window arithmetic.
+ * Two paths with the same bytes (lce_hip_pool_depthwise_*_path reports the one a launch takes, host only; *_forced runs a given
+ *   one, for tests and measurements): 0, the row path, takes every geometry; 1, the 16-byte path, needs depth_multiplier 1,
+ *   channels % 4 == 0 (float) or % 16 == 0 (int8), 16-byte aligned input, filter, bias / table and output, channels % 32 == 0 with
+ *   bits, a pool of stride 1 x 1 and a filter of at most 2 x 2, and a depthwise filter of at most 3 x 3; it loads every input tap
+ *   of an output's (at most 4 x 4) footprint once. */
+lce_hip_status lce_hip_pool_depthwise_f32_check(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, int32_t* out_height,
+                                                int32_t* out_width);
+lce_hip_status lce_hip_pool_depthwise_f32(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, const float* in_dev,
+                                          const float* filter_dev /* [1][fh][fw][Cout] */, const float* bias_dev /* nullable */,
+                                          float* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+lce_hip_status lce_hip_pool_depthwise_f32_path(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw, const float* in_dev,
+                                               const float* filter_dev, const float* bias_dev /* nullable */,
+                                               const float* out_dev /* nullable */, const int32_t* out_bits_dev /* nullable */, int32_t* path);
+lce_hip_status lce_hip_pool_depthwise_f32_forced(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_desc* dw,
+                                                 int32_t path /* 0: rows, 1: 16-byte */, const float* in_dev, const float* filter_dev,
+                                                 const float* bias_dev /* nullable */, float* out_dev /* nullable */,
+                                                 int32_t* out_bits_dev /* nullable */, void* stream);
+lce_hip_status lce_hip_pool_depthwise_i8_check(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, int32_t* out_height,
+                                               int32_t* out_width);
+lce_hip_status lce_hip_pool_depthwise_i8(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, const int8_t* in_dev,
+                                         const int8_t* filter_dev /* [1][fh][fw][Cout] */, const int32_t* table_dev /* [3][Cout] */,
+                                         int8_t* out_dev /* nullable */, int32_t* out_bits_dev /* nullable */, void* stream);
+lce_hip_status lce_hip_pool_depthwise_i8_path(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw, const int8_t* in_dev,
+                                              const int8_t* filter_dev, const int32_t* table_dev, const int8_t* out_dev /* nullable */,
+                                              const int32_t* out_bits_dev /* nullable */, int32_t* path);
+lce_hip_status lce_hip_pool_depthwise_i8_forced(const lce_hip_pool2d_desc* pool, const lce_hip_depthwise_i8_desc* dw,
+                                                int32_t path /* 0: rows, 1: 16-byte */, const int8_t* in_dev, const int8_t* filter_dev,
+                                                const int32_t* table_dev, int8_t* out_dev /* nullable */,
+                                                int32_t* out_bits_dev /* nullable */, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * The float classifier head (TFLite builtin MEAN, FULLY_CONNECTED, SOFTMAX)
  * ---------------------------------------------------------------------------------- */
 

@@ -341,7 +341,18 @@ lce_tflite_model* lce_tflite_model_open_opts(const void* data, size_t size, cons
  *   folds into the launch, and the int8 tensor is written only if something else reads it.  With
  *   `head_i8,reshape,int8_add,gate_i8` the body of an int8 RealToBinaryNet is ONE section.  Without the name every partition,
  *   launch and counter is what it was; with it a float file's partition is unchanged.  Still the host's: int8 MUL by a constant,
- *   a [b,C] operand, uint8 / int16 tensors. */
+ *   a [b,C] operand, uint8 / int16 tensors.
+ *   transition: a name that enables no operator -- the partition is what it is without it -- and changes how one pair runs.  An
+ *   absorbed float MAX_POOL_2D ("pool") whose pooled tensor the section does not deliver and whose ONLY reader is an absorbed float
+ *   DEPTHWISE_CONV_2D of this section ("depthwise") that reads it as its input runs WITH that convolution as ONE
+ *   lce_hip_pool_depthwise_f32 launch, when the entry's own check accepts the two descriptors: QuickNet's transition (pool 2x2 / 1
+ *   SAME, then the 3x3 / 2 blur), whose pooled map, as large as the pool's input, is then never written -- the walk holds no tensor
+ *   of that name and lce_tflite_model_section_tensor_shape refuses it.  The first LceQuantize that reads the blurred map folds into
+ *   the launch as it folds into the depthwise launch.  The bytes are those of the two launches.  Such a launch is counted by
+ *   lce_tflite_model_transition_stats and by neither lce_tflite_model_pool_stats nor lce_tflite_model_depthwise_stats.  A pooled tensor
+ *   with a second reader or one the section delivers, and an AVERAGE pool, run as two launches as before -- and so does an int8
+ *   pair: lce_hip_pool_depthwise_i8 exists and gives the two launches' bytes, but measured slower than they are
+ *   (profiles/transition/layers.txt), so the reader does not call it. */
 lce_tflite_model* lce_tflite_model_open_passes(const void* data, size_t size, const char* passes, char* err, size_t err_len);
 void lce_tflite_model_close(lce_tflite_model* model);
 
@@ -525,6 +536,9 @@ void lce_tflite_model_elementwise_i8_stats(lce_tflite_model* model, int32_t* lau
  * MUL and residual ADD operators inside them (2 for a launch with has_add, 1 otherwise) and LceQuantize launches folded into
  * them.  The int8 LOGISTIC launches are not among them.  Any pointer may be NULL. */
 void lce_tflite_model_gate_i8_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
+/* The LAST run's lce_hip_pool_depthwise_f32 launches ("transition" of lce_tflite_model_open_passes): launches, the MAX_POOL_2D
+ * and DEPTHWISE_CONV_2D operators inside them (2 per launch) and LceQuantize launches folded into them.  Any pointer may be NULL. */
+void lce_tflite_model_transition_stats(lce_tflite_model* model, int32_t* launches, int32_t* ops_folded, int32_t* quantize_folded);
 
 /* HIP graphs for lce_tflite_model_run_section (off by default).  A binary section is a chain of short kernels -- QuickNet's
  * last layers take 10-17 us each -- and a host call per kernel leaves gaps between them.  With graphs on, the launches of a

@@ -12,7 +12,7 @@ TUS = {"lce_tu_valu": [], "lce_tu_mfma_ws": [], "lce_tu_mfma_direct": [], "lce_t
        **{"lce_tu_wstream_" + p: [] for p in ("f32", "i8", "i8_floor", "bitpacked")}}
 txt = ""
 for tu in (sys.argv[2:] or TUS):
-    cmd = ["hipcc", "-DLCE_PRODUCT_BUILD", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", *TUS[tu], "-Icompute-engine_amd/csrc",
+    cmd = ["hipcc", "-DLCE_PRODUCT_BUILD", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", *TUS.get(tu, []), "-Icompute-engine_amd/csrc",
            "-Rpass-analysis=kernel-resource-usage", "-c", "compute-engine_amd/csrc/%s.hip" % tu, "-o", "/dev/null"]
     txt += subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, rows = None, {}
