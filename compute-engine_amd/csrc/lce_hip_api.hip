@@ -108,13 +108,6 @@ lce_hip_status require_device() {
   return LCE_HIP_OK;
 }
 
-unsigned grid_for_stream(uint64_t wave_tasks, int waves_per_block) {
-  // memory-bound streams: cap at ~8 blocks per CU and grid-stride the rest
-  const uint64_t blocks = (wave_tasks + waves_per_block - 1) / waves_per_block;
-  const uint64_t cap = 256ull * 8ull;
-  return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 template <typename T>
 struct DevBuf {
   T* ptr = nullptr;
@@ -136,19 +129,9 @@ struct DevBuf {
   }
 };
 
-// CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float.  False, and the range of NONE, for an activation
-// that is none of the four.
-bool float_activation_range(int32_t activation, float* lo, float* hi) {
-  *lo = -FLT_MAX;
-  *hi = FLT_MAX;
-  switch (activation) {
-    case LCE_HIP_ACT_NONE: return true;
-    case LCE_HIP_ACT_RELU: *lo = 0.0f; return true;
-    case LCE_HIP_ACT_RELU_N1_TO_1: *lo = -1.0f; *hi = 1.0f; return true;
-    case LCE_HIP_ACT_RELU6: *lo = 0.0f; *hi = 6.0f; return true;
-    default: return false;
-  }
-}
+static_assert(LCE_HIP_ACT_NONE == 0 && LCE_HIP_ACT_RELU == 1 && LCE_HIP_ACT_RELU_N1_TO_1 == 2 && LCE_HIP_ACT_RELU6 == 3,
+              "lce::float_activation_range (lce_kernels_common.h) states the activations by value");
+using lce::float_activation_range;
 
 // ---- The host checks that the windowed passes (pool, float 1x1 / depthwise / KxK convolution) share.  `who` is the entry's
 // name: every message is the entry's own. ----
@@ -195,11 +178,6 @@ lce_hip_status window_output(const char* who, const Window& w, int32_t* out_heig
   return report_output(who, w, oh, ow, out_height, out_width);
 }
 
-// ComputePaddingHeightWidth: of the SAME padding along one axis, total / 2 goes in front.
-int32_t same_pad_before(int32_t out, int32_t stride, int32_t filter, int32_t in) {
-  return (int32_t)(std::max<int64_t>(0, (int64_t)(out - 1) * stride + filter - in) / 2);
-}
-
 // The byte range of an operand; empty for a null pointer.
 struct Span {
   uintptr_t lo, hi;
@@ -232,12 +210,19 @@ lce_hip_status check_operand_ranges(const char* who, Span in, Span filter, Span 
   return LCE_HIP_OK;
 }
 
-// The grid stepping of the 16-byte-chunk kernels of pool and depthwise: what one grid step advances, in pixels and chunks.
-void pool_vec_steps(lce::PoolArgs& p) {
-  const uint64_t stride = (uint64_t)lce::pool_vec_grid(p.total) * 4ull * 64ull;   // chunks per grid step
-  p.step_pixels = (uint32_t)(stride / p.per_pixel);
-  p.step_chunks = (uint32_t)(stride % p.per_pixel);
-  p.div_per_pixel = lce::make_fastdiv(p.per_pixel);
+// The path an entry with a forced form takes: `vec`: the operands qualify for the 16-byte path; `path`: -1 (the entry's choice), 0 or 1.
+lce_hip_status take_path(const char* who, int32_t path, bool* vec, const char* needs) {
+  if (path != -1 && path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
+  if (path == 1 && !*vec) return fail(LCE_HIP_ERR_INVALID, "%s: the 16-byte path needs %s", who, needs);
+  if (path == 0) *vec = false;
+  return LCE_HIP_OK;
+}
+
+// The window geometry of a 16-byte-chunk or row launch on PoolArgs (lce_kernels_pool.h), with the grid stride of the product's grid.
+void window_fill(lce::PoolArgs& p, int32_t batch, int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t sh, int32_t sw, int32_t oh, int32_t ow,
+                 uint64_t C, uint64_t chunk_elems, bool vec, bool stream_loads_rule) {
+  lce::pool_window_fill(p, batch, H, W, fh, fw, sh, sw, oh, ow, C, chunk_elems, vec, stream_loads_rule);
+  if (vec) lce::pool_set_stride(p, lce::pool_vec_grid(p.total));
 }
 
 }  // namespace
@@ -514,7 +499,7 @@ static lce_hip_status launch_bitpack_rows(lce_hip_dtype in_type, const void* in_
   const uint32_t wpr = (uint32_t)((cols + 31) / 32);
   const uint32_t segs = (uint32_t)((cols + 63) / 64);
   const uint64_t tasks = rows * segs;
-  const unsigned grid = grid_for_stream(tasks, 4);
+  const unsigned grid = lce::stream_grid(tasks);
   const lce::FastDiv dv = lce::make_fastdiv(segs);
   if (in_type == LCE_HIP_F32)
     lce::bitpack_rows<float><<<grid, 256, 0, st>>>((const float*)in_dev, out_dev, (uint32_t)rows, (uint32_t)cols, wpr, 0, dv, segs, tasks);
@@ -547,7 +532,7 @@ lce_hip_status lce_hip_bitpack(lce_hip_dtype in_type, const void* in_dev, size_t
     return launch_bitpack_rows(in_type, in_dev, rows, cols, zero_point, (uint32_t*)out_dev, st);
   // bitpack.h:294-298: no per-row padding -> the tensor is one flat array; 32 words per wave step
   const uint64_t blocks32 = total_words / 32;
-  const unsigned grid = grid_for_stream(blocks32, 4);
+  const unsigned grid = lce::stream_grid(blocks32);
   if (in_type == LCE_HIP_F32)
     lce::bitpack_f32_flat<><<<grid, 256, 0, st>>>((const float*)in_dev, (uint32_t*)out_dev, blocks32);
   else if (in_type == LCE_HIP_I8)
@@ -574,13 +559,13 @@ lce_hip_status lce_hip_unpack(lce_hip_dtype out_type, const int32_t* in_dev, siz
   hipStream_t st = (hipStream_t)stream;
   const uint32_t wpr = (uint32_t)((cols + 31) / 32);
   const uint64_t total = (uint64_t)rows * cols;
-  const unsigned grid = grid_for_stream((total + 63) / 64, 4);
+  const unsigned grid = lce::stream_grid((total + 63) / 64);
   // whole words only and a 16-byte aligned destination: the flat, division-free kernel
   const bool flat = cols % 32 == 0 && ((uintptr_t)out_dev & 15) == 0;
   const uint64_t chunks_f32 = total / 4, chunks_b8 = total / 16;
   auto dv = (lce_dev::u32x4*)out_dev;
   if (out_type == LCE_HIP_F32) {
-    if (flat) lce::unpack_flat<float><<<grid_for_stream((chunks_f32 + 63) / 64, 4), 256, 0, st>>>((const uint32_t*)in_dev, dv, chunks_f32, 1.0f, -1.0f);
+    if (flat) lce::unpack_flat<float><<<lce::stream_grid((chunks_f32 + 63) / 64), 256, 0, st>>>((const uint32_t*)in_dev, dv, chunks_f32, 1.0f, -1.0f);
     else lce::unpack_rows<float><<<grid, 256, 0, st>>>((const uint32_t*)in_dev, (float*)out_dev, total, (uint32_t)cols, wpr, 1.0f, -1.0f);
   } else if (out_type == LCE_HIP_I8) {
     // quantization.cc:131-138
@@ -588,10 +573,10 @@ lce_hip_status lce_hip_unpack(lce_hip_dtype out_type, const int32_t* in_dev, siz
     const int offset = (int)std::round(1.0f / scale);
     const int zero_bit = std::min(127, zero_point + offset);
     const int one_bit = std::max(-128, zero_point - offset);
-    if (flat) lce::unpack_flat<int8_t><<<grid_for_stream((chunks_b8 + 63) / 64, 4), 256, 0, st>>>((const uint32_t*)in_dev, dv, chunks_b8, (int8_t)zero_bit, (int8_t)one_bit);
+    if (flat) lce::unpack_flat<int8_t><<<lce::stream_grid((chunks_b8 + 63) / 64), 256, 0, st>>>((const uint32_t*)in_dev, dv, chunks_b8, (int8_t)zero_bit, (int8_t)one_bit);
     else lce::unpack_rows<int8_t><<<grid, 256, 0, st>>>((const uint32_t*)in_dev, (int8_t*)out_dev, total, (uint32_t)cols, wpr, (int8_t)zero_bit, (int8_t)one_bit);
   } else {
-    if (flat) lce::unpack_flat<uint8_t><<<grid_for_stream((chunks_b8 + 63) / 64, 4), 256, 0, st>>>((const uint32_t*)in_dev, dv, chunks_b8, (uint8_t)1, (uint8_t)0);
+    if (flat) lce::unpack_flat<uint8_t><<<lce::stream_grid((chunks_b8 + 63) / 64), 256, 0, st>>>((const uint32_t*)in_dev, dv, chunks_b8, (uint8_t)1, (uint8_t)0);
     else lce::unpack_rows<uint8_t><<<grid, 256, 0, st>>>((const uint32_t*)in_dev, (uint8_t*)out_dev, total, (uint32_t)cols, wpr, (uint8_t)1, (uint8_t)0);
   }
   LCE_HIP_TRY(hipGetLastError());
@@ -1631,30 +1616,17 @@ lce_hip_status lce_hip_pool2d(const lce_hip_pool2d_desc* d, const void* in_dev, 
   const Span out(out_dev, pixels * C * esz), bits(out_bits_dev, pixels * wpr * 4);
   if (lce_hip_status s = check_operand_ranges(who, in, none, none, out, bits, /*float_operands=*/false)) return s;
   if (lce_hip_status s = require_device()) return s;
-  bool vec = (C * esz) % 16 == 0 && in.lo % 16 == 0 && out.lo % 16 == 0;
-  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
+  const bool vec = lce::window_vec_rule(1, C, esz, out_bits_dev != nullptr, in_dev, out_dev, nullptr, nullptr);
   lce::PoolArgs a;
   memset(&a, 0, sizeof a);
-  a.in = in_dev;
-  a.out = out_dev;
-  a.bits = (uint32_t*)out_bits_dev;
-  a.H = d->in_height; a.W = d->in_width; a.OH = oh; a.OW = ow;
-  a.fh = d->filter_height; a.fw = d->filter_width; a.sh = d->stride_height; a.sw = d->stride_width;
-  a.ph = same_pad_before(oh, d->stride_height, d->filter_height, d->in_height);
-  a.pw = same_pad_before(ow, d->stride_width, d->filter_width, d->in_width);
-  a.channels = (uint32_t)C;
-  a.wpr = (uint32_t)wpr;
-  a.per_pixel = (uint32_t)(vec ? C * esz / 16 : (C + 63) / 64);
-  a.stream_loads = d->stride_height >= d->filter_height && d->stride_width >= d->filter_width ? 1u : 0u;
-  a.total = pixels * a.per_pixel;
+  a.in = in_dev; a.out = out_dev; a.bits = (uint32_t*)out_bits_dev;
+  window_fill(a, d->batch, d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height, d->stride_width, oh, ow, C, 16 / esz,
+              vec, /*stream_loads_rule=*/true);
   float_activation_range(d->activation, &a.lo, &a.hi);
   if (d->type == LCE_HIP_I8) {
     quantized_activation_range(d->activation, d->scale, d->zero_point, &a.qlo, &a.qhi);
     a.zero_point = d->zero_point;
   }
-  a.div_ow = lce::make_fastdiv((uint32_t)ow);
-  a.div_oh = lce::make_fastdiv((uint32_t)oh);
-  if (vec) pool_vec_steps(a);
   const int e = lce::launch_pool(a, d->type == LCE_HIP_I8 ? lce::kPoolI8 : lce::kPoolF32,
                                  d->op == LCE_HIP_POOL_AVERAGE ? lce::kPoolAverage : lce::kPoolMax, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "lce_hip_pool2d: launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -1742,12 +1714,9 @@ lce_hip_status lce_hip_fully_connected_f32(const lce_hip_fc_desc* d, const float
   lce::FcArgs a;
   memset(&a, 0, sizeof a);
   a.in = in_dev; a.filter = weights_dev; a.bias = bias_dev; a.out = out_dev;
-  a.M = (uint32_t)M; a.K = (uint32_t)K; a.N = (uint32_t)N;
-  a.ntiles = (uint32_t)((N + lce::kFcTile - 1) / lce::kFcTile);
-  a.tiles = (uint32_t)((M + lce::kFcTile - 1) / lce::kFcTile) * a.ntiles;
+  lce::fc_fill(a, d->batch, d->inputs, d->outputs);
   float_activation_range(d->activation, &a.lo, &a.hi);
-  const bool vec = K % 4 == 0 && in.lo % 16 == 0 && weights.lo % 16 == 0;
-  const int e = lce::launch_fully_connected(a, vec, stream);
+  const int e = lce::launch_fully_connected(a, lce::fc_vec_rule(a), stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
@@ -1843,12 +1812,9 @@ lce_hip_status lce_hip_binary_fully_connected(const lce_hip_bfc_desc* d, const i
   memset(&a, 0, sizeof a);
   a.in = (const uint32_t*)in_bits_dev; a.weights = (const uint32_t*)weight_bits_dev; a.scale = scale_dev; a.bias = bias_dev;
   a.out = out_dev; a.bits = (uint32_t*)out_bits_dev;
-  a.M = (uint32_t)M; a.K = (uint32_t)K; a.N = (uint32_t)N; a.Kw = (uint32_t)Kw;
-  a.ntiles = (uint32_t)wpr;
-  a.tiles = (uint32_t)((M + lce::kBfcTile - 1) / lce::kBfcTile) * a.ntiles;
+  lce::bfc_fill(a, d->batch, d->inputs, d->outputs);
   float_activation_range(d->activation, &a.lo, &a.hi);
-  const bool vec = Kw % 4 == 0 && in.lo % 16 == 0 && weights.lo % 16 == 0;
-  const int e = lce::launch_binary_fully_connected(a, vec, stream);
+  const int e = lce::launch_binary_fully_connected(a, lce::bfc_vec_rule(a), stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
@@ -1897,29 +1863,16 @@ lce_hip_status lce_hip_depthwise_conv2d_f32(const lce_hip_depthwise_desc* d, con
   const Span out(out_dev, pixels * C * 4), bits(out_bits_dev, pixels * wpr * 4);
   if (lce_hip_status s = check_operand_ranges(who, in, filter, bias, out, bits, /*float_operands=*/true)) return s;
   if (lce_hip_status s = require_device()) return s;
-  bool vec = d->depth_multiplier == 1 && C % 4 == 0 && (in.lo | filter.lo | bias.lo | out.lo) % 16 == 0;
-  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
+  const bool vec = lce::window_vec_rule(d->depth_multiplier, C, 4, out_bits_dev != nullptr, in_dev, filter_dev, bias_dev, out_dev);
   lce::DepthwiseArgs a;
   memset(&a, 0, sizeof a);
   lce::PoolArgs& p = a.P;
   p.in = in_dev; p.out = out_dev; p.bits = (uint32_t*)out_bits_dev;
   a.filter = filter_dev; a.bias = bias_dev;
-  a.channels_in = (uint32_t)Cin;
-  a.div_multiplier = lce::make_fastdiv((uint32_t)d->depth_multiplier);
-  p.H = d->in_height; p.W = d->in_width; p.OH = oh; p.OW = ow;
-  p.fh = d->filter_height; p.fw = d->filter_width; p.sh = d->stride_height; p.sw = d->stride_width;
-  p.ph = same_pad_before(oh, d->stride_height, d->filter_height, d->in_height);
-  p.pw = same_pad_before(ow, d->stride_width, d->filter_width, d->in_width);
-  p.channels = (uint32_t)C;
-  p.wpr = (uint32_t)wpr;
-  p.per_pixel = (uint32_t)(vec ? C / 4 : (C + 63) / 64);
-  // the pools' rule (lce_kernels_pool.h): non-temporal window loads only where windows do not overlap
-  p.stream_loads = d->stride_height >= d->filter_height && d->stride_width >= d->filter_width ? 1u : 0u;
-  p.total = pixels * p.per_pixel;
+  a.channels_in = (uint32_t)Cin; a.div_multiplier = lce::make_fastdiv((uint32_t)d->depth_multiplier);
+  window_fill(p, d->batch, d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height, d->stride_width, oh, ow, C, 4, vec,
+              /*stream_loads_rule=*/true);
   float_activation_range(d->activation, &p.lo, &p.hi);
-  p.div_ow = lce::make_fastdiv((uint32_t)ow);
-  p.div_oh = lce::make_fastdiv((uint32_t)oh);
-  if (vec) pool_vec_steps(p);
   const int e = lce::launch_depthwise(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
@@ -1976,8 +1929,7 @@ lce_hip_status lce_hip_conv2d_f32(const lce_hip_conv2d_desc* d, const float* in_
   lce::conv2d_geometry(a, d->batch, d->in_height, d->in_width, d->channels_in, d->channels_out, d->filter_height, d->filter_width,
                        d->stride_height, d->stride_width, oh, ow);
   float_activation_range(d->activation, &a.lo, &a.hi);
-  const bool vec = Cin % 4 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
-  const int e = lce::launch_conv2d(a, vec, stream);
+  const int e = lce::launch_conv2d(a, lce::conv2d_vec_rule(a), stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
@@ -2126,8 +2078,7 @@ lce_hip_status lce_hip_conv2d_i8(const lce_hip_conv2d_i8_desc* d, const int8_t* 
                           d->stride_height, d->stride_width, oh, ow);
   a.zi = d->input_zero_point; a.zo = d->output_zero_point;
   quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, &a.act_min, &a.act_max);
-  const bool vec = Cin % 16 == 0 && in.lo % 16 == 0 && filter.lo % 16 == 0;
-  const int e = lce::launch_conv2d_i8(a, vec, stream);
+  const int e = lce::launch_conv2d_i8(a, lce::conv2d_i8_vec_rule(a), stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
@@ -2232,13 +2183,10 @@ lce_hip_status lce_hip_fully_connected_i8(const lce_hip_fc_i8_desc* d, const int
   lce::FcI8Args a;
   memset(&a, 0, sizeof a);
   a.in = in_dev; a.filter = weights_dev; a.table = table_dev; a.out = out_dev;
-  a.M = (uint32_t)M; a.K = (uint32_t)K; a.N = (uint32_t)N;
-  a.ntiles = (uint32_t)((N + lce::kFcI8Tile - 1) / lce::kFcI8Tile);
-  a.tiles = (uint32_t)((M + lce::kFcI8Tile - 1) / lce::kFcI8Tile) * a.ntiles;
+  lce::fc_i8_fill(a, d->batch, d->inputs, d->outputs);
   a.zo = d->output_zero_point;
   quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, &a.act_min, &a.act_max);
-  const bool vec = K % 16 == 0 && in.lo % 16 == 0 && weights.lo % 16 == 0;
-  const int e = lce::launch_fully_connected_i8(a, vec, stream);
+  const int e = lce::launch_fully_connected_i8(a, lce::fc_i8_vec_rule(a), stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
 }
@@ -2388,13 +2336,10 @@ lce_hip_status depthwise_i8_run(const char* who, const lce_hip_depthwise_i8_desc
     return fail(LCE_HIP_ERR_INVALID, "%s: an output overlaps the table", who);
   if (lce_hip_status s = check_operand_ranges(who, in, filter, Span(nullptr, 0), out, bits, /*float_operands=*/false)) return s;
   if (table.lo % 4 != 0) return fail(LCE_HIP_ERR_INVALID, "%s: table_dev must be 4-byte aligned", who);
-  bool vec = d->depth_multiplier == 1 && C % 16 == 0 && (in.lo | filter.lo | table.lo | out.lo) % 16 == 0;
-  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
-  if (path != -1 && path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
-  if (path == 1 && !vec)
-    return fail(LCE_HIP_ERR_INVALID, "%s: the 16-byte path needs depth_multiplier 1, channels %% 16 == 0 (%% 32 with bits) and 16-byte aligned "
-                "input, filter, table and output", who);
-  if (path == 0) vec = false;
+  bool vec = lce::window_vec_rule(d->depth_multiplier, C, 1, out_bits_dev != nullptr, in_dev, filter_dev, table_dev, out_dev);
+  if (lce_hip_status s = take_path(who, path, &vec, "depth_multiplier 1, channels % 16 == 0 (% 32 with bits) and 16-byte aligned input, filter, "
+                                   "table and output"))
+    return s;
   if (took) *took = vec ? 1 : 0;
   if (!launch) return LCE_HIP_OK;
   if (lce_hip_status s = require_device()) return s;
@@ -2404,23 +2349,11 @@ lce_hip_status depthwise_i8_run(const char* who, const lce_hip_depthwise_i8_desc
   p.in = in_dev; p.out = out_dev; p.bits = (uint32_t*)out_bits_dev;
   a.filter = filter_dev; a.table = table_dev;
   a.zi = d->input_zero_point;
-  a.channels_in = (uint32_t)Cin;
-  a.div_multiplier = lce::make_fastdiv((uint32_t)d->depth_multiplier);
-  p.H = d->in_height; p.W = d->in_width; p.OH = oh; p.OW = ow;
-  p.fh = d->filter_height; p.fw = d->filter_width; p.sh = d->stride_height; p.sw = d->stride_width;
-  p.ph = same_pad_before(oh, d->stride_height, d->filter_height, d->in_height);
-  p.pw = same_pad_before(ow, d->stride_width, d->filter_width, d->in_width);
-  p.channels = (uint32_t)C;
-  p.wpr = (uint32_t)wpr;
-  p.per_pixel = (uint32_t)(vec ? C / 16 : (C + 63) / 64);
-  // the pools' rule (lce_kernels_pool.h): non-temporal window loads only where windows do not overlap
-  p.stream_loads = d->stride_height >= d->filter_height && d->stride_width >= d->filter_width ? 1u : 0u;
-  p.total = pixels * p.per_pixel;
+  a.channels_in = (uint32_t)Cin; a.div_multiplier = lce::make_fastdiv((uint32_t)d->depth_multiplier);
+  window_fill(p, d->batch, d->in_height, d->in_width, d->filter_height, d->filter_width, d->stride_height, d->stride_width, oh, ow, C, 16, vec,
+              /*stream_loads_rule=*/true);
   quantized_activation_range(d->activation, d->output_scale, d->output_zero_point, &p.qlo, &p.qhi);
   p.zero_point = d->output_zero_point;
-  p.div_ow = lce::make_fastdiv((uint32_t)ow);
-  p.div_oh = lce::make_fastdiv((uint32_t)oh);
-  if (vec) pool_vec_steps(p);
   const int e = lce::launch_depthwise_i8(a, vec, stream);
   if (e != hipSuccess) return fail(LCE_HIP_ERR_RUNTIME, "%s: launch failed: %s", who, hipGetErrorString((hipError_t)e));
   return LCE_HIP_OK;
@@ -2516,32 +2449,12 @@ lce_hip_status pool_depthwise_i8_desc_check(const char* who, const lce_hip_pool2
 // The geometry of both fused launches: the depthwise window on the pooled map into `p`, the pool in front into `q`.
 void pool_depthwise_fill(lce::PoolArgs& p, lce::TransitionPool& q, const lce_hip_pool2d_desc* pool, int32_t pooled_h, int32_t pooled_w,
                          const lce_hip_depthwise_desc& dw, int32_t oh, int32_t ow, uint64_t C, uint64_t chunk, bool vec) {
-  p.H = pooled_h; p.W = pooled_w; p.OH = oh; p.OW = ow;
-  p.fh = dw.filter_height; p.fw = dw.filter_width; p.sh = dw.stride_height; p.sw = dw.stride_width;
-  p.ph = same_pad_before(oh, dw.stride_height, dw.filter_height, pooled_h);
-  p.pw = same_pad_before(ow, dw.stride_width, dw.filter_width, pooled_w);
-  p.channels = (uint32_t)C;
-  p.wpr = (uint32_t)((C + 31) / 32);
-  p.per_pixel = (uint32_t)(vec ? C / chunk : (C + 63) / 64);
-  p.total = (uint64_t)dw.batch * oh * ow * p.per_pixel;
-  p.div_ow = lce::make_fastdiv((uint32_t)ow);
-  p.div_oh = lce::make_fastdiv((uint32_t)oh);
-  if (vec) pool_vec_steps(p);
-  q.H = pool->in_height; q.W = pool->in_width;
-  q.fh = pool->filter_height; q.fw = pool->filter_width; q.sh = pool->stride_height; q.sw = pool->stride_width;
-  q.ph = same_pad_before(pooled_h, pool->stride_height, pool->filter_height, pool->in_height);
-  q.pw = same_pad_before(pooled_w, pool->stride_width, pool->filter_width, pool->in_width);
+  window_fill(p, dw.batch, pooled_h, pooled_w, dw.filter_height, dw.filter_width, dw.stride_height, dw.stride_width, oh, ow, C, chunk, vec,
+              /*stream_loads_rule=*/false);
+  lce::transition_pool_fill(q, pool->in_height, pool->in_width, pool->filter_height, pool->filter_width, pool->stride_height, pool->stride_width,
+                            pooled_h, pooled_w);
   float_activation_range(pool->activation, &q.lo, &q.hi);
   if (pool->type == LCE_HIP_I8) quantized_activation_range(pool->activation, pool->scale, pool->zero_point, &q.qlo, &q.qhi);
-}
-
-// The path both fused entries take: `vec` says whether the operands qualify for the 16-byte path; `path` is -1 (the entry's own
-// choice), 0 or 1.
-lce_hip_status pool_depthwise_path(const char* who, int32_t path, bool* vec, const char* needs) {
-  if (path != -1 && path != 0 && path != 1) return fail(LCE_HIP_ERR_INVALID, "%s: unknown path %d", who, (int)path);
-  if (path == 1 && !*vec) return fail(LCE_HIP_ERR_INVALID, "%s: the 16-byte path needs %s", who, needs);
-  if (path == 0) *vec = false;
-  return LCE_HIP_OK;
 }
 
 // The launch of lce_hip_pool_depthwise_f32 and of its forced form (`path`, `took`, `launch`: as depthwise_i8_run's).
@@ -2560,10 +2473,9 @@ lce_hip_status pool_depthwise_f32_run(const char* who, const lce_hip_pool2d_desc
   lce::TransitionArgs a;
   memset(&a, 0, sizeof a);
   a.Q.fh = pool->filter_height; a.Q.fw = pool->filter_width; a.Q.sh = pool->stride_height; a.Q.sw = pool->stride_width;
-  bool vec = dw->depth_multiplier == 1 && C % 4 == 0 && (in.lo | filter.lo | bias.lo | out.lo) % 16 == 0 &&
+  bool vec = lce::window_vec_rule(dw->depth_multiplier, C, 4, out_bits_dev != nullptr, in_dev, filter_dev, bias_dev, out_dev) &&
              lce::transition_vec_geometry(a.Q, dw->filter_height, dw->filter_width);
-  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
-  if (lce_hip_status s = pool_depthwise_path(who, path, &vec, "depth_multiplier 1, channels % 4 == 0 (% 32 with bits), 16-byte aligned input, "
+  if (lce_hip_status s = take_path(who, path, &vec, "depth_multiplier 1, channels % 4 == 0 (% 32 with bits), 16-byte aligned input, "
                                              "filter, bias and output, a pool of stride 1 and at most 2 x 2 and a depthwise filter of at most 3 x 3"))
     return s;
   if (took) *took = vec ? 1 : 0;
@@ -2572,8 +2484,7 @@ lce_hip_status pool_depthwise_f32_run(const char* who, const lce_hip_pool2d_desc
   lce::PoolArgs& p = a.D.P;
   p.in = in_dev; p.out = out_dev; p.bits = (uint32_t*)out_bits_dev;
   a.D.filter = filter_dev; a.D.bias = bias_dev;
-  a.D.channels_in = (uint32_t)Cin;
-  a.D.div_multiplier = lce::make_fastdiv((uint32_t)dw->depth_multiplier);
+  a.D.channels_in = (uint32_t)Cin; a.D.div_multiplier = lce::make_fastdiv((uint32_t)dw->depth_multiplier);
   pool_depthwise_fill(p, a.Q, pool, qh, qw, *dw, oh, ow, C, 4, vec);
   float_activation_range(dw->activation, &p.lo, &p.hi);
   const int e = lce::launch_transition(a, vec, stream);
@@ -2601,10 +2512,9 @@ lce_hip_status pool_depthwise_i8_run(const char* who, const lce_hip_pool2d_desc*
   lce::TransitionI8Args a;
   memset(&a, 0, sizeof a);
   a.Q.fh = pool->filter_height; a.Q.fw = pool->filter_width; a.Q.sh = pool->stride_height; a.Q.sw = pool->stride_width;
-  bool vec = dw->depth_multiplier == 1 && C % 16 == 0 && (in.lo | filter.lo | table.lo | out.lo) % 16 == 0 &&
+  bool vec = lce::window_vec_rule(dw->depth_multiplier, C, 1, out_bits_dev != nullptr, in_dev, filter_dev, table_dev, out_dev) &&
              lce::transition_vec_geometry(a.Q, dw->filter_height, dw->filter_width);
-  if (out_bits_dev && C % 32 != 0) vec = false;     // (a word of bits then straddles pixels of chunks)
-  if (lce_hip_status s = pool_depthwise_path(who, path, &vec, "depth_multiplier 1, channels % 16 == 0 (% 32 with bits), 16-byte aligned input, "
+  if (lce_hip_status s = take_path(who, path, &vec, "depth_multiplier 1, channels % 16 == 0 (% 32 with bits), 16-byte aligned input, "
                                              "filter, table and output, a pool of stride 1 and at most 2 x 2 and a depthwise filter of at most 3 x 3"))
     return s;
   if (took) *took = vec ? 1 : 0;
@@ -2614,8 +2524,7 @@ lce_hip_status pool_depthwise_i8_run(const char* who, const lce_hip_pool2d_desc*
   p.in = in_dev; p.out = out_dev; p.bits = (uint32_t*)out_bits_dev;
   a.D.filter = filter_dev; a.D.table = table_dev;
   a.D.zi = dw->input_zero_point;
-  a.D.channels_in = (uint32_t)Cin;
-  a.D.div_multiplier = lce::make_fastdiv((uint32_t)dw->depth_multiplier);
+  a.D.channels_in = (uint32_t)Cin; a.D.div_multiplier = lce::make_fastdiv((uint32_t)dw->depth_multiplier);
   pool_depthwise_fill(p, a.Q, pool, qh, qw, depthwise_i8_window(dw), oh, ow, C, 16, vec);
   quantized_activation_range(dw->activation, dw->output_scale, dw->output_zero_point, &p.qlo, &p.qhi);
   p.zero_point = dw->output_zero_point;
@@ -2893,7 +2802,7 @@ static lce_hip_status run_images(lce_hip_bconv2d_plan* plan, const int32_t* inpu
         }
         const uint64_t chunks = (uint64_t)G.NPIX * (uint64_t)((G.CPW + 3) / 4);  // threads of expand_fp4
         if (h.phase != 2) {
-          LCE_HIP_TRY((hipError_t)lce::launch_expand_fp4(grid_for_stream((chunks + 63) / 64, 4), (void*)st, in, plan->workspace, G, chunks));
+          LCE_HIP_TRY((hipError_t)lce::launch_expand_fp4(lce::stream_grid((chunks + 63) / 64), (void*)st, in, plan->workspace, G, chunks));
         }
         if (h.phase != 1) {
           const dim3 grid((unsigned)((A.M + bm - 1) / bm), (unsigned)(h.npad / bn));
@@ -3087,7 +2996,7 @@ lce_hip_status lce_hip_bmaxpool(const int32_t* input_dev, int32_t batch, int32_t
   const bool vec = words % 4 == 0 && ((uintptr_t)input_dev & 15) == 0 && ((uintptr_t)output_dev & 15) == 0;
   const int groups = vec ? words / 4 : words;
   const uint64_t total = (uint64_t)batch * oh * ow * groups;
-  const unsigned grid = grid_for_stream((total + 63) / 64, 4);
+  const unsigned grid = lce::stream_grid((total + 63) / 64);
   auto kernel = vec ? lce::bmaxpool_words<4> : lce::bmaxpool_words<1>;
   kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const uint32_t*)input_dev, (uint32_t*)output_dev, batch, in_h, in_w,
                                                   groups, oh, ow, fh, fw, sh, sw, ph, pw, total, lce::make_fastdiv((uint32_t)groups),

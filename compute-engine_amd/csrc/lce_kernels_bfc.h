@@ -54,6 +54,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "lce_kernels_common.h"
+
 namespace lce {
 
 constexpr int kBfcTile = 32;           // rows and columns of a wave's tile
@@ -71,6 +73,14 @@ struct BfcArgs {
   uint32_t tiles;            // ceil(M / 32) * ntiles < 2^31
   float lo, hi;              // CalculateActivationRange (float)
 };
+
+// As fc_fill / fc_vec_rule / fc_grid (lce_kernels_head.h): Kw = ceil(K / 32) words per row, and the load path needs Kw % 4.
+inline void bfc_fill(BfcArgs& a, int32_t batch, int32_t inputs, int32_t outputs) {
+  dense_fill(a, batch, inputs, outputs, kBfcTile);
+  a.Kw = (a.K + 31) / 32;
+}
+inline bool bfc_vec_rule(const BfcArgs& a) { return load_vec_rule(a.Kw, 4, a.in, a.weights); }
+inline unsigned bfc_grid(const BfcArgs& a, uint64_t cap = 2048) { return stream_grid(a.tiles, 4, cap); }
 
 // Launch the kernel on `stream`; return the launch's hipError_t as an int.  Defined in lce_tu_bfc.hip.
 int launch_binary_fully_connected(const BfcArgs& args, bool vec, void* stream);

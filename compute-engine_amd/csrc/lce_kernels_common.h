@@ -7,6 +7,12 @@
 
 namespace lce {
 
+// ComputePaddingHeightWidth: of the SAME padding along one axis, total / 2 goes in front.
+inline int32_t same_pad_before(int32_t out, int32_t stride, int32_t filter, int32_t in) {
+  const int64_t total = (int64_t)(out - 1) * stride + filter - in;
+  return (int32_t)((total > 0 ? total : 0) / 2);
+}
+
 // What the launch descriptors of the float and the int8 CONV_2D (Conv2dArgs, ConvI8Args) have in common, for a convolution whose
 // sizes the caller has checked and whose output extents oh x ow it knows: the channel counts, K = fh fw Cin < 2^31 and its
 // contiguous runs, the extents, the strides and the padding in front.
@@ -20,10 +26,42 @@ inline void conv_window_geometry(Args& a, int32_t in_height, int32_t in_width, i
   a.in_row = (uint64_t)in_width * Cin;
   a.IH = in_height; a.IW = in_width; a.OH = oh; a.OW = ow;
   a.sh = stride_height; a.sw = stride_width;
-  // ComputePaddingHeightWidth: total / 2 in front
-  const int64_t th = (int64_t)(oh - 1) * stride_height + filter_height - in_height, tw = (int64_t)(ow - 1) * stride_width + filter_width - in_width;
-  a.ph = (int32_t)((th > 0 ? th : 0) / 2);
-  a.pw = (int32_t)((tw > 0 ? tw : 0) / 2);
+  a.ph = same_pad_before(oh, stride_height, filter_height, in_height);
+  a.pw = same_pad_before(ow, stride_width, filter_width, in_width);
+}
+
+// The grid of a grid-strided launch: `per_block` tasks to a block (4 wave tasks; 256 for a kernel of one element per lane), at
+// least one block (no entry launches on nothing) and at most `cap` (the product: ~8 per CU; a host simulation passes a small one).
+inline unsigned stream_grid(uint64_t tasks, unsigned per_block = 4, uint64_t cap = 2048) {
+  const uint64_t blocks = (tasks + per_block - 1) / per_block;
+  return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+
+// The 16-byte load path of the matrix kernels: K's contiguous run `k` a multiple of a load's `width` elements, both operands aligned.
+inline bool load_vec_rule(uint64_t k, unsigned width, const void* in, const void* filter) {
+  return k % width == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)filter % 16 == 0;
+}
+
+// M, K, N and the tile counts of a Dense layer's launch (FcArgs, FcI8Args, BfcArgs): one wave per tile x tile outputs.
+template <typename Args>
+inline void dense_fill(Args& a, int32_t batch, int32_t inputs, int32_t outputs, uint32_t tile) {
+  a.M = (uint32_t)batch; a.K = (uint32_t)inputs; a.N = (uint32_t)outputs;
+  a.ntiles = (a.N + tile - 1) / tile;
+  a.tiles = ((a.M + tile - 1) / tile) * a.ntiles;
+}
+
+// CalculateActivationRange (tensorflow/lite/kernels/kernel_util.h) for float and an lce_hip_activation (NONE, RELU, RELU_N1_TO_1,
+// RELU6 = 0 .. 3).  False, and the range of NONE, for an activation that is none of the four.
+inline bool float_activation_range(int32_t activation, float* lo, float* hi) {
+  *lo = -3.402823466e+38f;      // -FLT_MAX
+  *hi = 3.402823466e+38f;
+  switch (activation) {
+    case 0: return true;
+    case 1: *lo = 0.0f; return true;
+    case 2: *lo = -1.0f; *hi = 1.0f; return true;
+    case 3: *lo = 0.0f; *hi = 6.0f; return true;
+    default: return false;
+  }
 }
 
 }  // namespace lce

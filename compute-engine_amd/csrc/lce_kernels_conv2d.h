@@ -100,6 +100,14 @@ inline void conv2d_geometry(Conv2dArgs& a, int32_t batch, int32_t in_height, int
   a.div_side = make_fastdiv(a.side);
 }
 
+// conv2d_interior's 16-byte load rule (Cin % 4) and grid (as conv2d_i8_grid); conv2d_border's: a wave per (pixel, 64 channels).
+inline bool conv2d_vec_rule(const Conv2dArgs& a) { return load_vec_rule(a.Cin, 4, a.in, a.filter); }
+inline void conv2d_grid(const Conv2dArgs& a, uint32_t cap, unsigned* gx, unsigned* gy) {
+  *gx = a.mtiles < cap ? a.mtiles : cap;
+  *gy = (a.Cout + kConv2dBN - 1) / kConv2dBN;
+}
+inline unsigned conv2d_border_grid(const Conv2dArgs& a, uint64_t cap = 2048) { return stream_grid((uint64_t)a.Mb * a.segs, 4, cap); }
+
 // Launches conv2d_interior (when Mi > 0; vec: the 16-byte load path, the caller has checked Cin % 4 and both alignments) and
 // conv2d_border (when Mb > 0) on `stream`; returns the first failing launch's hipError_t as an int.  Defined in
 // lce_tu_conv2d.hip.

@@ -82,6 +82,9 @@ inline void conv2d_i8_geometry(ConvI8Args& a, int32_t batch, int32_t in_height, 
   a.div_ohw = make_fastdiv((uint32_t)((uint64_t)oh * ow));
 }
 
+// The 16-byte load path's rule: Cin % 16, both operands aligned.
+inline bool conv2d_i8_vec_rule(const ConvI8Args& a) { return load_vec_rule(a.Cin, 16, a.in, a.filter); }
+
 // The grid of the launch: 128-pixel tiles, grid-strided past `cap` blocks (the product: ~8 per CU); grid.y: the 128-channel slices.
 inline void conv2d_i8_grid(const ConvI8Args& a, uint32_t cap, unsigned* gx, unsigned* gy) {
   *gx = a.mtiles < cap ? a.mtiles : cap;

@@ -59,6 +59,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "lce_kernels_common.h"
+
 namespace lce {
 
 constexpr int kFcTile = 16;            // rows and columns of a wave's tile
@@ -82,6 +84,11 @@ struct SoftmaxArgs {
   uint32_t cols;
   float beta;
 };
+
+// fully_connected_f32's launch (entry, launcher, host simulation): tile counts, the 16-byte rule (K % 4), one wave per tile.
+inline void fc_fill(FcArgs& a, int32_t batch, int32_t inputs, int32_t outputs) { dense_fill(a, batch, inputs, outputs, kFcTile); }
+inline bool fc_vec_rule(const FcArgs& a) { return load_vec_rule(a.K, 4, a.in, a.filter); }
+inline unsigned fc_grid(const FcArgs& a, uint64_t cap = 2048) { return stream_grid(a.tiles, 4, cap); }
 
 // Launch the kernels on `stream`; return the launch's hipError_t as an int.  Defined in lce_tu_head.hip.
 int launch_fully_connected(const FcArgs& args, bool vec, void* stream);

@@ -85,6 +85,11 @@ struct QuantArgs {
   int32_t zp;
 };
 
+// The launch of fully_connected_i8, as fc_fill / fc_vec_rule / fc_grid (lce_kernels_head.h): the load path needs K % 16.
+inline void fc_i8_fill(FcI8Args& a, int32_t batch, int32_t inputs, int32_t outputs) { dense_fill(a, batch, inputs, outputs, kFcI8Tile); }
+inline bool fc_i8_vec_rule(const FcI8Args& a) { return load_vec_rule(a.K, 16, a.in, a.filter); }
+inline unsigned fc_i8_grid(const FcI8Args& a, uint64_t cap = 2048) { return stream_grid(a.tiles, 4, cap); }
+
 // Launch the kernels on `stream`; return the launch's hipError_t as an int.  Defined in lce_tu_head_i8.hip.
 int launch_fully_connected_i8(const FcI8Args& args, bool vec, void* stream);
 int launch_mean_i8(const MeanI8Args& args, void* stream);

@@ -60,12 +60,43 @@ struct PoolArgs {
   FastDiv div_per_pixel, div_ow, div_oh;
 };
 
-// Launches the vector path (vec == true; the caller has checked sizes and alignment and filled the vector-path fields for
-// the grid pool_vec_grid() gives) or the row path on `stream`; returns the launch's hipError_t as an int.  Defined in
-// lce_tu_pool.hip.
+// The 16-byte-path rule of every pass on PoolArgs: depth multiplier 1 (a pool: 1), a pixel a whole number of 16-byte chunks, the
+// operands `p0`..`p3` (0: none) 16-byte aligned and, with bits, C % 32 == 0 (a word of bits would straddle pixels of chunks).
+inline bool window_vec_rule(int32_t depth_multiplier, uint64_t channels, uint64_t elem_bytes, bool has_bits, const void* p0, const void* p1,
+                            const void* p2, const void* p3) {
+  return depth_multiplier == 1 && (channels * elem_bytes) % 16 == 0 &&
+         ((uintptr_t)p0 | (uintptr_t)p1 | (uintptr_t)p2 | (uintptr_t)p3) % 16 == 0 && !(has_bits && channels % 32 != 0);
+}
+
+// The window geometry of `p` (everything but the pointers, the clamp and the grid stride) for the output extents of the entry's
+// check; `chunk_elems` elements make a 16-byte chunk.  `stream_loads_rule`: false leaves stream_loads 0 (the transitions).
+inline void pool_window_fill(PoolArgs& p, int32_t batch, int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t sh, int32_t sw, int32_t OH,
+                             int32_t OW, uint64_t channels, uint64_t chunk_elems, bool vec, bool stream_loads_rule) {
+  p.H = H; p.W = W; p.OH = OH; p.OW = OW; p.fh = fh; p.fw = fw; p.sh = sh; p.sw = sw;
+  p.ph = same_pad_before(OH, sh, fh, H);
+  p.pw = same_pad_before(OW, sw, fw, W);
+  p.channels = (uint32_t)channels;
+  p.wpr = (uint32_t)((channels + 31) / 32);
+  p.per_pixel = (uint32_t)(vec ? channels / chunk_elems : (channels + 63) / 64);
+  p.stream_loads = stream_loads_rule && sh >= fh && sw >= fw ? 1u : 0u;
+  p.total = (uint64_t)batch * OH * OW * p.per_pixel;
+  p.div_ow = make_fastdiv((uint32_t)OW); p.div_oh = make_fastdiv((uint32_t)OH);
+}
+
+// Blocks of 4 waves for `total_chunks` chunks, 64 per wave task (a row-path launch passes its segments * 64); at most `cap`.
+inline unsigned pool_vec_grid(uint64_t total_chunks, uint64_t cap = 2048) { return stream_grid((total_chunks + 63) / 64, 4, cap); }
+
+// The grid stepping of the 16-byte-chunk kernels on `blocks` blocks: what one grid step advances, in pixels and chunks.
+inline void pool_set_stride(PoolArgs& p, unsigned blocks) {
+  const uint64_t stride = (uint64_t)blocks * 4ull * 64ull;       // chunks per grid step
+  p.step_pixels = (uint32_t)(stride / p.per_pixel);
+  p.step_chunks = (uint32_t)(stride % p.per_pixel);
+  p.div_per_pixel = make_fastdiv(p.per_pixel);
+}
+
+// Launches the vector path (vec == true; the caller has checked sizes and alignment and set the stride for the grid
+// pool_vec_grid() gives) or the row path on `stream`; returns the launch's hipError_t as an int.  Defined in lce_tu_pool.hip.
 int launch_pool(const PoolArgs& args, int kind, int op, bool vec, void* stream);
-// Blocks of 4 waves the vector path is launched with for `total_chunks` chunks (the host derives the grid stride from it).
-unsigned pool_vec_grid(uint64_t total_chunks);
 
 }  // namespace lce
 

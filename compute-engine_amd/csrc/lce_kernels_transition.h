@@ -58,6 +58,14 @@ inline bool transition_vec_geometry(const TransitionPool& q, int32_t dw_fh, int3
   return q.sh == 1 && q.sw == 1 && q.fh <= 2 && q.fw <= 2 && dw_fh <= 3 && dw_fw <= 3;
 }
 
+// The window of the pool in front (everything of `q` but the clamp): input H x W, pooled to pooled_h x pooled_w.
+inline void transition_pool_fill(TransitionPool& q, int32_t H, int32_t W, int32_t fh, int32_t fw, int32_t sh, int32_t sw, int32_t pooled_h,
+                                 int32_t pooled_w) {
+  q.H = H; q.W = W; q.fh = fh; q.fw = fw; q.sh = sh; q.sw = sw;
+  q.ph = same_pad_before(pooled_h, sh, fh, H);
+  q.pw = same_pad_before(pooled_w, sw, fw, W);
+}
+
 // Launch the vector path (vec == true; the caller has checked geometry, sizes and alignment and filled the vector-path fields for
 // the grid pool_vec_grid() gives) or the row path on `stream`; the launch's hipError_t as an int.  lce_tu_transition.hip.
 int launch_transition(const TransitionArgs& args, bool vec, void* stream);

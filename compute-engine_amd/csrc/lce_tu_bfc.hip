@@ -6,8 +6,7 @@ namespace lce {
 int launch_binary_fully_connected(const BfcArgs& args, bool vec, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   // one wave per 32 x 32 tile, four to a block, grid-strided past ~8 blocks per CU
-  const uint32_t blocks = (args.tiles + 3u) / 4u, cap = 256u * 8u;
-  const dim3 grid(blocks < cap ? blocks : cap);
+  const dim3 grid(bfc_grid(args));
   if (vec) binary_fully_connected<true><<<grid, 256, 0, st>>>(args);
   else binary_fully_connected<false><<<grid, 256, 0, st>>>(args);
   return (int)hipGetLastError();

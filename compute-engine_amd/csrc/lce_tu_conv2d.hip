@@ -7,8 +7,9 @@ int launch_conv2d(const Conv2dArgs& args, bool vec, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (args.Mi > 0) {
     // 128-pixel tiles, grid-strided past ~8 blocks per CU; grid.y: the 128-channel slices
-    const uint32_t cap = 256u * 8u;
-    const dim3 grid(args.mtiles < cap ? args.mtiles : cap, (args.Cout + kConv2dBN - 1) / kConv2dBN);
+    unsigned gx = 0, gy = 0;
+    conv2d_grid(args, 256u * 8u, &gx, &gy);
+    const dim3 grid(gx, gy);
     if (vec) conv2d_interior<true><<<grid, 256, 0, st>>>(args);
     else conv2d_interior<false><<<grid, 256, 0, st>>>(args);
     const int e = (int)hipGetLastError();
@@ -16,8 +17,7 @@ int launch_conv2d(const Conv2dArgs& args, bool vec, void* stream) {
   }
   if (args.Mb > 0) {
     // one wave per (border pixel, 64 channels), 4 per block, grid-strided past ~8 blocks per CU
-    const uint64_t tasks = (uint64_t)args.Mb * args.segs, blocks = (tasks + 3) / 4, cap = 256ull * 8ull;
-    const unsigned grid = (unsigned)(blocks < cap ? blocks : cap);
+    const unsigned grid = conv2d_border_grid(args);
     if (args.bits) conv2d_border<true><<<grid, 256, 0, st>>>(args);
     else conv2d_border<false><<<grid, 256, 0, st>>>(args);
     return (int)hipGetLastError();

@@ -7,8 +7,7 @@ namespace lce {
 int launch_fully_connected_i8(const FcI8Args& args, bool vec, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   // one wave per 16 x 16 tile, four to a block, grid-strided past ~8 blocks per CU
-  const uint32_t blocks = (args.tiles + 3u) / 4u, cap = 256u * 8u;
-  const dim3 grid(blocks < cap ? blocks : cap);
+  const dim3 grid(fc_i8_grid(args));
   if (vec) fully_connected_i8<true><<<grid, 256, 0, st>>>(args);
   else fully_connected_i8<false><<<grid, 256, 0, st>>>(args);
   return (int)hipGetLastError();
@@ -17,33 +16,25 @@ int launch_fully_connected_i8(const FcI8Args& args, bool vec, void* stream) {
 int launch_mean_i8(const MeanI8Args& args, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   // one wave per image and 16 channels, four to a block, grid-strided past ~8 blocks per CU
-  const uint64_t blocks = (args.batch * args.segs + 3u) / 4u, cap = 256u * 8u;
-  mean_i8<4><<<dim3((uint32_t)(blocks < cap ? blocks : cap)), 256, 0, st>>>(args);
+  mean_i8<4><<<dim3(stream_grid(args.batch * args.segs)), 256, 0, st>>>(args);
   return (int)hipGetLastError();
 }
 
 int launch_softmax_i8(const SoftmaxI8Args& args, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   // one wave per row, four to a block, grid-strided past ~8 blocks per CU
-  const uint64_t blocks = (args.rows + 3u) / 4u, cap = 256u * 8u;
-  softmax_i8<4><<<dim3((uint32_t)(blocks < cap ? blocks : cap)), 256, 0, st>>>(args);
+  softmax_i8<4><<<dim3(stream_grid(args.rows)), 256, 0, st>>>(args);
   return (int)hipGetLastError();
 }
 
-namespace {
-uint32_t quant_grid(uint64_t n) {
-  const uint64_t blocks = (n + 255u) / 256u, cap = 256u * 8u;
-  return (uint32_t)(blocks < cap ? blocks : cap);
-}
-}  // namespace
-
+// one element per lane and step (n > 0), grid-strided past ~8 blocks per CU
 int launch_quantize_f32_i8(const QuantArgs& args, void* stream) {
-  quant_i8<true><<<dim3(quant_grid(args.n)), 256, 0, (hipStream_t)stream>>>(args);
+  quant_i8<true><<<dim3(stream_grid(args.n, 256)), 256, 0, (hipStream_t)stream>>>(args);
   return (int)hipGetLastError();
 }
 
 int launch_dequantize_i8_f32(const QuantArgs& args, void* stream) {
-  quant_i8<false><<<dim3(quant_grid(args.n)), 256, 0, (hipStream_t)stream>>>(args);
+  quant_i8<false><<<dim3(stream_grid(args.n, 256)), 256, 0, (hipStream_t)stream>>>(args);
   return (int)hipGetLastError();
 }
 }  // namespace lce

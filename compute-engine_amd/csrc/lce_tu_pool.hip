@@ -4,16 +4,11 @@
 
 namespace lce {
 namespace {
-// memory-bound streams: 4 waves per block, at most ~8 blocks per CU, grid-stride the rest (as lce_tu_eltwise.hip)
-unsigned pool_stream_grid(uint64_t wave_tasks) {
-  const uint64_t blocks = (wave_tasks + 3) / 4, cap = 256ull * 8ull;
-  return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
+// memory-bound streams: 4 waves per block, at most ~8 blocks per CU, grid-stride the rest (stream_grid, as lce_tu_eltwise.hip)
 template <int KIND, int OP>
 void launch_kind_op(const PoolArgs& args, bool vec, hipStream_t st) {
   if (!vec) {
-    pool_rows<KIND, OP><<<pool_stream_grid(args.total), 256, 0, st>>>(args);
+    pool_rows<KIND, OP><<<stream_grid(args.total), 256, 0, st>>>(args);
     return;
   }
   const unsigned grid = pool_vec_grid(args.total);
@@ -21,8 +16,6 @@ void launch_kind_op(const PoolArgs& args, bool vec, hipStream_t st) {
   else pool_vec<KIND, OP, false><<<grid, 256, 0, st>>>(args);
 }
 }  // namespace
-
-unsigned pool_vec_grid(uint64_t total_chunks) { return pool_stream_grid((total_chunks + 63) / 64); }
 
 int launch_pool(const PoolArgs& args, int kind, int op, bool vec, void* stream) {
   hipStream_t st = (hipStream_t)stream;

@@ -2,9 +2,11 @@
 makes of it: a launch of binary_fully_connected on exact-size buffers.  No tests here."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import hostsim_lib
+from hostsim_lib import placed
 
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_binary_dense")
 OUT_MARK = np.float32(-7.5)
@@ -13,28 +15,13 @@ _lib = None
 
 
 def lib():
-    """tests/hostsim_binary_dense/liblce_hostsim_binary_dense.so, brought up to date with the kernel headers first (as
-    tests/hostsim_lib.py does: among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_binary_dense/liblce_hostsim_binary_dense.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        l = C.CDLL(os.path.join(DIR, "liblce_hostsim_binary_dense.so"))
+        l = hostsim_lib.load(DIR, "liblce_hostsim_binary_dense.so")
         l.lce_hostsim_binary_fully_connected.argtypes = [C.c_void_p] * 7 + [C.c_int32]
         _lib = l
     return _lib
-
-
-def placed(a, offset):
-    """A copy of `a` that starts `offset` bytes behind a 16-byte boundary, exact in size."""
-    a = np.ascontiguousarray(a)
-    raw = np.empty(a.nbytes + 32, np.uint8)
-    start = (-raw.ctypes.data) % 16 + offset
-    view = raw[start:start + a.nbytes].view(a.dtype).reshape(a.shape)
-    view[...] = a
-    return view
 
 
 def sim(in_bits, weight_bits, scale, bias, k, activation=0, value=True, bits=True, cap=1 << 20, offset=0):

@@ -5,20 +5,12 @@
 // integer dot product under the maps the kernel assumes -- row of A and column of B from lane l & 31, the 16 bytes of lane l
 // paired byte for byte with the 16 bytes of the B lane in the same half l >> 5; accumulator register r of lane l is row
 // (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.  The GPU suite decides that.
-#include <cstring>
-#include <vector>
-
-#include "lce_device_intrinsics.h"      // the host replacement: build/ comes first on the include path
-#define __HIPCC__ 1
-#define __host__
-#define __device__
-#define __forceinline__ inline
+#include "sim_harness.h"
 #define __shared__ static               // one block at a time, all of its lanes fibers of one thread
 typedef int32_t sim_i32x4 __attribute__((vector_size(16)));      // the kernel header's i32x4 and i32x16
 typedef int32_t sim_i32x16 __attribute__((vector_size(64)));
 inline void __syncthreads() { g_ctx.block_bar->arrive_and_wait(); }
-// (add_i8_flat's quad permute: lce_kernels_eltwise_i8.h comes along for its two gemmlowp steps; its kernels are not run here)
-inline int __builtin_amdgcn_mov_dpp(int, int, int, int, bool) { __builtin_trap(); }
+// (lce_kernels_eltwise_i8.h comes along for its two gemmlowp steps; its kernels are not run here)
 inline sim_i32x16 __builtin_amdgcn_mfma_i32_32x32x32_i8(sim_i32x4 a, sim_i32x4 b, sim_i32x16 c, int, int, int) {
   const int lane = g_ctx.tid_x & 63;
   int8_t* x = (int8_t*)g_ctx.mfma_xchg;   // per lane 32 bytes: [a: 16][b: 16]
@@ -40,22 +32,7 @@ inline sim_i32x16 __builtin_amdgcn_mfma_i32_32x32x32_i8(sim_i32x4 a, sim_i32x4 b
 
 namespace {
 template <typename F>
-void launch(unsigned gx, unsigned gy, F kernel) {
-  for (unsigned by = 0; by < gy; ++by)
-    for (unsigned bx = 0; bx < gx; ++bx) {
-      std::vector<uint32_t> xchg(4 * 64), mx(4 * 64 * 8);
-      lce_dev::FiberBarrier block_bar(256);
-      lce_dev::FiberBarrier wave_bar[4] = {lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64),
-                                           lce_dev::FiberBarrier(64)};
-      lce_dev::run_fibers(256,
-        [&](int t, lce_dev::ThreadCtx& c) {
-          const int w = t >> 6;
-          c.tid_x = t; c.bid_x = (int)bx; c.bid_y = (int)by; c.bdim_x = 256; c.gdim_x = (int)gx;
-          c.bar = &wave_bar[w]; c.xchg = xchg.data() + w * 64; c.mfma_xchg = mx.data() + w * 64 * 8; c.block_bar = &block_bar;
-        },
-        [&](int) { kernel(); });
-    }
-}
+void launch(unsigned gx, unsigned gy, F kernel) { sim::launch(gx, gy, 256, kernel, /*mfma_xchg=*/true); }
 }  // namespace
 
 // d: batch, in_height, in_width, channels_in, channels_out, filter_height, filter_width, stride_height, stride_width, out_height,
@@ -69,7 +46,7 @@ extern "C" int lce_hostsim_conv2d_i8(const int32_t* d, const int8_t* in, const i
   a.in = in; a.filter = filter; a.table = table; a.out = out; a.bits = (uint32_t*)bits;
   lce::conv2d_i8_geometry(a, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10]);
   a.zi = d[11]; a.zo = d[12]; a.act_min = d[13]; a.act_max = d[14];
-  const bool vec = a.Cin % 16 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)filter % 16 == 0;      // lce_hip_conv2d_i8's rule
+  const bool vec = lce::conv2d_i8_vec_rule(a);
   unsigned gx = 0, gy = 0;
   lce::conv2d_i8_grid(a, (uint32_t)cap, &gx, &gy);                                                  // launch_conv2d_i8's grid, capped at `cap`
   if (vec) launch(gx, gy, [&] { lce::conv2d_i8<true>(a); });

@@ -2,9 +2,11 @@
 suites make of it: one launch of the kernel, and the requantization function of its epilogue.  No tests here."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import hostsim_lib
+from hostsim_lib import placed
 
 import conv2d_i8_ref as R
 from conv2d_i8_cases import BITS_MARK, OUT_MARK
@@ -14,15 +16,10 @@ _lib = None
 
 
 def lib():
-    """tests/hostsim_conv2d_i8/liblce_hostsim_conv2d_i8.so, brought up to date with the kernel headers first (as
-    tests/hostsim_lib.py does: among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_conv2d_i8/liblce_hostsim_conv2d_i8.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        _lib = C.CDLL(os.path.join(DIR, "liblce_hostsim_conv2d_i8.so"))
+        _lib = hostsim_lib.load(DIR, "liblce_hostsim_conv2d_i8.so")
         _lib.lce_hostsim_conv2d_i8.argtypes = [C.c_void_p] * 6 + [C.c_int32]
         _lib.lce_hostsim_conv2d_i8_requantize.argtypes = [C.c_int64] + [C.c_void_p] * 4
         _lib.lce_hostsim_conv2d_i8_requantize.restype = None
@@ -35,16 +32,6 @@ def requantize(acc, m, e):
     out = np.empty(acc.shape, np.int32)
     lib().lce_hostsim_conv2d_i8_requantize(acc.size, acc.ctypes.data, m.ctypes.data, e.ctypes.data, out.ctypes.data)
     return out
-
-
-def placed(a, offset):
-    """A copy of `a` whose first byte lies `offset` bytes behind a 16-byte boundary."""
-    buf = np.zeros(a.size + 32, a.dtype)
-    start = (-buf.ctypes.data) % 16 + offset
-    v = buf[start:start + a.size].reshape(a.shape)
-    v[...] = a
-    assert v.ctypes.data % 16 == offset
-    return v
 
 
 def sim(x, w, bias, sw, q_in, q_out, stride, padding, act, want_out=True, want_bits=True, offset=0, cap=3):

@@ -2,33 +2,15 @@
 // real kernel bodies of csrc/lce_kernels_eltwise.h run on the CPU, 256 lanes of a block as fibers in lock step
 // (tests/hostsim/lce_device_intrinsics.h), so the word and image bookkeeping of the flat path, the grid stride, the partial last
 // block, the row path's ballots and every step kind are exercised without a GPU.
-#include <cfloat>
 #include <cmath>
-#include <cstring>
-#include <vector>
 
-#include "lce_device_intrinsics.h"      // the host replacement: build/ comes first on the include path
+#include "sim_harness.h"
 inline float __fmul_rn(float a, float b) { volatile float r = a * b; return r; }
-#define __HIPCC__ 1
 #include "lce_kernels_eltwise.h"
 
 namespace {
 template <typename F>
-void launch(unsigned gx, F kernel) {
-  for (unsigned bx = 0; bx < gx; ++bx) {
-    std::vector<uint32_t> xchg(4 * 64);
-    lce_dev::FiberBarrier block_bar(256);
-    lce_dev::FiberBarrier wave_bar[4] = {lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64),
-                                         lce_dev::FiberBarrier(64)};
-    lce_dev::run_fibers(256,
-      [&](int t, lce_dev::ThreadCtx& c) {
-        const int w = t >> 6;
-        c.tid_x = t; c.bid_x = (int)bx; c.bid_y = 0; c.bdim_x = 256; c.gdim_x = (int)gx;
-        c.bar = &wave_bar[w]; c.xchg = xchg.data() + w * 64; c.block_bar = &block_bar;
-      },
-      [&](int) { kernel(); });
-  }
-}
+void launch(unsigned gx, F kernel) { sim::launch(gx, 256, kernel); }
 }  // namespace
 
 // One launch of the chain.  Step s is (ops[s], operands[s], values[s], scalars[s], acts[s]).  `ex`: 1 runs the instances of
@@ -48,19 +30,11 @@ extern "C" int lce_hostsim_eltwise(int64_t rows, int32_t channels, int64_t rows_
   for (int s = 0; s < num_steps; ++s) {
     lce::EwStep& k = a.steps[s];
     k.op = ops[s]; k.operand = operands[s]; k.values = values[s]; k.scalar = scalars[s];
-    switch (acts[s]) {
-      case 1: k.lo = 0.0f; k.hi = FLT_MAX; break;
-      case 2: k.lo = -1.0f; k.hi = 1.0f; break;
-      case 3: k.lo = 0.0f; k.hi = 6.0f; break;
-      default: k.lo = -FLT_MAX; k.hi = FLT_MAX;
-    }
+    lce::float_activation_range(acts[s], &k.lo, &k.hi);
     if (k.values && (uintptr_t)k.values % 16 != 0) aligned = false;
   }
   const bool flat = channels % 32 == 0 && aligned;
-  auto grid = [&](uint64_t wave_tasks) {                    // lce_tu_eltwise.hip's, with the cap a parameter
-    const uint64_t blocks = (wave_tasks + 3) / 4;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > (uint64_t)cap ? (uint64_t)cap : blocks));
-  };
+  auto grid = [&](uint64_t wave_tasks) { return lce::stream_grid(wave_tasks, 4, (uint64_t)cap); };
   const lce::EwArgs& a0 = a;
   if (flat) {
     const uint64_t total_words = a.rows * (uint64_t)a.wpr;

@@ -4,50 +4,13 @@
 // by modular steps, the grid stride, the partial last iteration, the two-lane word and the row path's ballots are exercised without
 // a GPU.  One device-only piece is replaced: the quad permute v_mov_b32 quad_perm:[1,0,3,2] behind add_i8_neighbour is emulated as
 // the exchange with lane ^ 1 it is.
-#include <cstring>
-#include <memory>
-#include <vector>
-
-#include "lce_device_intrinsics.h"      // the host replacement: build/ comes first on the include path
-#define __HIPCC__ 1
-#define __host__
-#define __device__
-#define __forceinline__ inline
-// dpp_ctrl 0xB1 = quad_perm:[1,0,3,2], all rows and banks, bound_ctrl: the value of lane ^ 1 (every lane of the wave calls it)
-inline int __builtin_amdgcn_mov_dpp(int v, int ctrl, int row_mask, int bank_mask, bool) {
-  if (ctrl != 0xB1 || row_mask != 0xF || bank_mask != 0xF) __builtin_trap();
-  return (int)lce_dev::shfl_xor((uint32_t)v, 1);
-}
+#include "sim_harness.h"
 #include "lce_kernels_eltwise_i8_chain.h"
 
 namespace {
-constexpr unsigned kLdsGuard = 64;
-constexpr uint8_t kLdsMark = 0xA7;
-
 // `gx` blocks of `threads` threads with `lds_bytes` of LDS between guard bytes; false when a block wrote outside its LDS.
 template <typename F>
-bool launch(unsigned gx, unsigned threads, unsigned lds_bytes, F kernel) {
-  const unsigned waves = threads / 64;
-  for (unsigned bx = 0; bx < gx; ++bx) {
-    std::vector<uint32_t> xchg(waves * 64);
-    std::vector<uint8_t> lds(lds_bytes + 2 * kLdsGuard + 16, kLdsMark);
-    uint8_t* base = lds.data() + kLdsGuard;
-    base += (16 - (uintptr_t)base % 16) % 16;
-    lce_dev::FiberBarrier block_bar((int)threads);
-    std::vector<std::unique_ptr<lce_dev::FiberBarrier>> wave_bar;
-    for (unsigned w = 0; w < waves; ++w) wave_bar.emplace_back(new lce_dev::FiberBarrier(64));
-    lce_dev::run_fibers((int)threads,
-      [&](int t, lce_dev::ThreadCtx& c) {
-        const int w = t >> 6;
-        c.tid_x = t; c.bid_x = (int)bx; c.bid_y = 0; c.bdim_x = (int)threads; c.gdim_x = (int)gx;
-        c.bar = wave_bar[w].get(); c.xchg = xchg.data() + w * 64; c.block_bar = &block_bar; c.lds = base;
-      },
-      [&](int) { kernel(); });
-    for (uint8_t* p = lds.data(); p < base; ++p) if (*p != kLdsMark) return false;
-    for (uint8_t* p = base + lds_bytes; p < lds.data() + lds.size(); ++p) if (*p != kLdsMark) return false;
-  }
-  return true;
-}
+bool launch(unsigned gx, unsigned threads, unsigned lds_bytes, F kernel) { return sim::launch(gx, threads, kernel, false, (int)lds_bytes); }
 
 template <int H, int P>
 bool run_place(const lce::EwI8Args& E, bool flat, unsigned gx, unsigned threads, unsigned lds_bytes) {

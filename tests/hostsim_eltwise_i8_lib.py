@@ -4,51 +4,30 @@ tests here."""
 import ctypes as C
 import importlib
 import os
-import subprocess
 
 import numpy as np
 
+import hostsim_lib
+
 amd = importlib.import_module("compute-engine_amd")
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_eltwise_i8")
-GUARD = 64                                  # guard bytes on either side of every buffer
 _lib = None
 
 
 def lib():
-    """tests/hostsim_eltwise_i8/liblce_hostsim_eltwise_i8.so, brought up to date with the kernel headers first (as
-    tests/hostsim_lib.py does: among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_eltwise_i8/liblce_hostsim_eltwise_i8.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        l = C.CDLL(os.path.join(DIR, "liblce_hostsim_eltwise_i8.so"))
+        l = hostsim_lib.load(DIR, "liblce_hostsim_eltwise_i8.so")
         l.lce_hostsim_eltwise_i8.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                              C.c_void_p] + [C.c_int32] * 5
         _lib = l
     return _lib
 
 
-class Placed:
-    """`nbytes` bytes whose first lies `offset` bytes behind a 16-byte boundary, between GUARD bytes of `mark` on either side: a
-    write past an end is seen by intact()."""
-
-    def __init__(self, nbytes, offset, mark, data=None):
-        self.buf = np.full(nbytes + 2 * GUARD + 32, mark, np.uint8)
-        start = GUARD + (-(self.buf.ctypes.data + GUARD)) % 16 + offset
-        self.view = self.buf[start:start + nbytes]
-        assert self.view.ctypes.data % 16 == offset
-        if data is not None:
-            self.view[...] = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
-        self.start, self.n, self.mark = start, nbytes, mark
-
-    @property
-    def ptr(self):
-        return self.view.ctypes.data
-
-    def intact(self):
-        return bool(np.all(self.buf[:self.start] == self.mark) and np.all(self.buf[self.start + self.n:] == self.mark))
+def Placed(nbytes, offset, mark, data=None):
+    """`nbytes` guarded bytes `offset` bytes behind a 16-byte boundary (hostsim_lib.Placed)."""
+    return hostsim_lib.Placed((nbytes,), np.uint8, offset, mark, None if data is None else np.ascontiguousarray(data).view(np.uint8))
 
 
 def sim_chain(x, q_in, steps, addend=None, head=None, want_out=True, want_bits=True, path=None, cap=None, offset=0, bits_offset=0,

@@ -3,51 +3,28 @@ makes of it: a launch of the chain on exact-size buffers between guard words.  N
 import ctypes as C
 import importlib
 import os
-import subprocess
 
 import numpy as np
 
+import hostsim_lib
+from hostsim_lib import Placed
+
 amd = importlib.import_module("compute-engine_amd")
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_eltwise")
-GUARD = 8                                   # guard elements on either side of every buffer
 OUT_MARK = np.float32(777)
 BITS_MARK = np.uint32(0x5A5A5A5A)
 _lib = None
 
 
 def lib():
-    """tests/hostsim_eltwise/liblce_hostsim_eltwise.so, brought up to date with the kernel headers first (as tests/hostsim_lib.py
-    does: among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_eltwise/liblce_hostsim_eltwise.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        l = C.CDLL(os.path.join(DIR, "liblce_hostsim_eltwise.so"))
+        l = hostsim_lib.load(DIR, "liblce_hostsim_eltwise.so")
         l.lce_hostsim_eltwise.argtypes = [C.c_int64, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32, C.c_int32]
         l.lce_hostsim_logistic.argtypes, l.lce_hostsim_logistic.restype = [C.c_void_p, C.c_void_p, C.c_int64], None
         _lib = l
     return _lib
-
-
-class Placed:
-    """An exact-size array whose first byte lies `offset` elements behind a 16-byte boundary, between GUARD elements of `mark` on
-    either side: a read past an end meets the mark (a NaN for floats), a write past an end is seen by intact()."""
-
-    def __init__(self, shape, dtype, offset, mark, data=None):
-        n = int(np.prod(shape))
-        self.buf = np.full(n + 2 * GUARD + 8, mark, dtype)
-        start = GUARD + (-(self.buf.ctypes.data // 4 + GUARD)) % 4 + offset
-        self.view = self.buf[start:start + n].reshape(shape)
-        assert self.view.ctypes.data % 16 == 4 * offset
-        if data is not None:
-            self.view[...] = data
-        self.start, self.n, self.mark = start, n, self.buf[:1].copy()
-
-    def intact(self):
-        guard = np.concatenate([self.buf[:self.start], self.buf[self.start + self.n:]])
-        return np.array_equal(guard.view(np.uint32), np.full(guard.size, self.mark.view(np.uint32)[0], np.uint32))
 
 
 def sim_logistic(x):
@@ -66,9 +43,9 @@ def sim_chain(x, steps, want_out=True, want_bits=True, cap=2048, offset=0, ex=1,
     channels = x.shape[-1]
     rows = x.size // channels
     nan = np.float32(np.nan)
-    xin = Placed(x.shape, np.float32, offset, nan, x)
-    out = xin if in_place else Placed(x.shape, np.float32, offset, OUT_MARK) if want_out else None
-    bits = Placed(x.shape[:-1] + ((channels + 31) // 32,), np.uint32, offset, BITS_MARK) if want_bits else None
+    xin = Placed(x.shape, np.float32, 4 * offset, nan, x)
+    out = xin if in_place else Placed(x.shape, np.float32, 4 * offset, OUT_MARK) if want_out else None
+    bits = Placed(x.shape[:-1] + ((channels + 31) // 32,), np.uint32, 4 * offset, BITS_MARK) if want_bits else None
     n = len(steps)
     keep = []
     values = (C.c_void_p * n)()
@@ -79,7 +56,7 @@ def sim_chain(x, steps, want_out=True, want_bits=True, cap=2048, offset=0, ex=1,
         if kind == amd.EW_SCALAR:
             scalars[k] = 0.0 if operand is None else float(operand)
         else:
-            p = Placed(np.shape(operand), np.float32, offset, nan, operand)
+            p = Placed(np.shape(operand), np.float32, 4 * offset, nan, operand)
             keep.append(p)
             values[k] = p.view.ctypes.data
     flat = lib().lce_hostsim_eltwise(rows, channels, rows // x.shape[0], n, ops, operands, values, scalars, acts, xin.view.ctypes.data,

@@ -4,41 +4,14 @@
 // stores of an odd chunk count and the row path's ballots are exercised without a GPU.  One device-only piece is replaced: the quad
 // permute v_mov_b32 quad_perm:[1,0,3,2] behind add_i8_neighbour is emulated as the exchange with lane ^ 1 it is.
 #include <cstddef>
-#include <cstring>
-#include <memory>
-#include <vector>
 
-#include "lce_device_intrinsics.h"      // the host replacement: build/ comes first on the include path
-#define __HIPCC__ 1
-#define __host__
-#define __device__
-#define __forceinline__ inline
-// dpp_ctrl 0xB1 = quad_perm:[1,0,3,2], all rows and banks, bound_ctrl: the value of lane ^ 1 (every lane of the wave calls it)
-inline int __builtin_amdgcn_mov_dpp(int v, int ctrl, int row_mask, int bank_mask, bool) {
-  if (ctrl != 0xB1 || row_mask != 0xF || bank_mask != 0xF) __builtin_trap();
-  return (int)lce_dev::shfl_xor((uint32_t)v, 1);
-}
+#include "sim_harness.h"
 #include "lce_kernels_mul_i8.h"
 
 namespace {
 // `gx` blocks of `threads` threads, no LDS
 template <typename F>
-void launch(unsigned gx, unsigned threads, F kernel) {
-  const unsigned waves = threads / 64;
-  for (unsigned bx = 0; bx < gx; ++bx) {
-    std::vector<uint32_t> xchg(waves * 64);
-    lce_dev::FiberBarrier block_bar((int)threads);
-    std::vector<std::unique_ptr<lce_dev::FiberBarrier>> wave_bar;
-    for (unsigned w = 0; w < waves; ++w) wave_bar.emplace_back(new lce_dev::FiberBarrier(64));
-    lce_dev::run_fibers((int)threads,
-      [&](int t, lce_dev::ThreadCtx& c) {
-        const int w = t >> 6;
-        c.tid_x = t; c.bid_x = (int)bx; c.bid_y = 0; c.bdim_x = (int)threads; c.gdim_x = (int)gx;
-        c.bar = wave_bar[w].get(); c.xchg = xchg.data() + w * 64; c.block_bar = &block_bar; c.lds = nullptr;
-      },
-      [&](int) { kernel(); });
-  }
-}
+void launch(unsigned gx, unsigned threads, F kernel) { sim::launch(gx, threads, kernel); }
 
 template <int MV, int V, bool PI>
 void run_kind(const lce::MulI8Args& M, bool flat, unsigned gx, unsigned threads) {

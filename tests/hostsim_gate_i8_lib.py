@@ -4,9 +4,10 @@ here."""
 import ctypes as C
 import importlib
 import os
-import subprocess
 
 import numpy as np
+
+import hostsim_lib
 
 from hostsim_eltwise_i8_lib import Placed
 
@@ -16,15 +17,10 @@ _lib = None
 
 
 def lib():
-    """tests/hostsim_gate_i8/liblce_hostsim_gate_i8.so, brought up to date with the kernel headers first (as tests/hostsim_lib.py
-    does: among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_gate_i8/liblce_hostsim_gate_i8.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        l = C.CDLL(os.path.join(DIR, "liblce_hostsim_gate_i8.so"))
+        l = hostsim_lib.load(DIR, "liblce_hostsim_gate_i8.so")
         l.lce_hostsim_gate_i8.restype = C.c_int
         l.lce_hostsim_gate_i8.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32] + \
                                          [C.c_void_p] * 5 + [C.c_int32] * 4

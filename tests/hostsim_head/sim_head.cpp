@@ -4,13 +4,9 @@
 // tail, the epilogue, the stated exp and the order of the sum are exercised without a GPU.  What it cannot decide is the premise
 // itself: v_mfma_f32_16x16x4_f32 is emulated here as the k-ordered fmaf chain the kernel takes it for (row / column l & 15 at
 // k = l >> 4; accumulator register i of lane l is row 4 (l >> 4) + i, column l & 15).  The GPU suite decides that.
-#include <cfloat>
 #include <cmath>
-#include <cstring>
-#include <vector>
 
-#include "lce_device_intrinsics.h"      // the host replacement: build/ comes first on the include path
-#define __HIPCC__ 1
+#include "sim_harness.h"
 inline lce_dev::f32x4 __builtin_amdgcn_mfma_f32_16x16x4f32(float a, float b, lce_dev::f32x4 c, int, int, int) {
   const int lane = g_ctx.tid_x & 63;
   float* x = (float*)g_ctx.mfma_xchg;   // per lane: [a, b, ...]
@@ -27,25 +23,6 @@ inline lce_dev::f32x4 __builtin_amdgcn_mfma_f32_16x16x4f32(float a, float b, lce
 }
 #include "lce_kernels_head.h"
 
-namespace {
-template <typename F>
-void launch(unsigned gx, F kernel) {
-  for (unsigned bx = 0; bx < gx; ++bx) {
-    std::vector<uint32_t> xchg(4 * 64), mx(4 * 64 * 8);
-    lce_dev::FiberBarrier block_bar(256);
-    lce_dev::FiberBarrier wave_bar[4] = {lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64),
-                                         lce_dev::FiberBarrier(64)};
-    lce_dev::run_fibers(256,
-      [&](int t, lce_dev::ThreadCtx& c) {
-        const int w = t >> 6;
-        c.tid_x = t; c.bid_x = (int)bx; c.bid_y = 0; c.bdim_x = 256; c.gdim_x = (int)gx;
-        c.bar = &wave_bar[w]; c.xchg = xchg.data() + w * 64; c.mfma_xchg = mx.data() + w * 64 * 8; c.block_bar = &block_bar;
-      },
-      [&](int) { kernel(); });
-  }
-}
-}  // namespace
-
 // d: batch, inputs, outputs, activation.  `cap`: the most blocks of the launch (the product caps its grid at 2048; a small cap
 // makes the kernel stride).  Returns 1 when the launch took the 16-byte load path.
 extern "C" int lce_hostsim_fully_connected(const int32_t* d, const float* in, const float* weights, const float* bias, float* out,
@@ -53,19 +30,12 @@ extern "C" int lce_hostsim_fully_connected(const int32_t* d, const float* in, co
   lce::FcArgs a;
   memset(&a, 0, sizeof a);
   a.in = in; a.filter = weights; a.bias = bias; a.out = out;
-  a.M = (uint32_t)d[0]; a.K = (uint32_t)d[1]; a.N = (uint32_t)d[2];
-  a.ntiles = (a.N + lce::kFcTile - 1) / lce::kFcTile;
-  a.tiles = ((a.M + lce::kFcTile - 1) / lce::kFcTile) * a.ntiles;
-  switch (d[3]) {
-    case 1: a.lo = 0.0f; a.hi = FLT_MAX; break;
-    case 2: a.lo = -1.0f; a.hi = 1.0f; break;
-    case 3: a.lo = 0.0f; a.hi = 6.0f; break;
-    default: a.lo = -FLT_MAX; a.hi = FLT_MAX;
-  }
-  const bool vec = a.K % 4 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)weights % 16 == 0;      // lce_hip_fully_connected_f32's rule
-  const unsigned blocks = (a.tiles + 3) / 4, gx = blocks < (unsigned)cap ? blocks : (unsigned)cap;   // launch_fully_connected's grid
-  if (vec) launch(gx, [&] { lce::fully_connected_f32<true>(a); });
-  else launch(gx, [&] { lce::fully_connected_f32<false>(a); });
+  lce::fc_fill(a, d[0], d[1], d[2]);
+  lce::float_activation_range(d[3], &a.lo, &a.hi);
+  const bool vec = lce::fc_vec_rule(a);
+  const unsigned gx = lce::fc_grid(a, (uint64_t)cap);
+  if (vec) sim::launch(gx, 256, [&] { lce::fully_connected_f32<true>(a); }, /*mfma_xchg=*/true);
+  else sim::launch(gx, 256, [&] { lce::fully_connected_f32<false>(a); }, /*mfma_xchg=*/true);
   return vec ? 1 : 0;
 }
 
@@ -73,8 +43,7 @@ extern "C" void lce_hostsim_softmax(int64_t rows, int32_t cols, float beta, cons
   lce::SoftmaxArgs a;
   memset(&a, 0, sizeof a);
   a.in = in; a.out = out; a.rows = (uint64_t)rows; a.cols = (uint32_t)cols; a.beta = beta;
-  const uint64_t blocks = (a.rows + 3) / 4;
-  launch((unsigned)(blocks < (uint64_t)cap ? blocks : (uint64_t)cap), [&] { lce::softmax_f32<4>(a); });
+  sim::launch(lce::stream_grid(a.rows, 4, (uint64_t)cap), 256, [&] { lce::softmax_f32<4>(a); });
 }
 
 // The stated exp alone, element by element (the accuracy test sweeps it over 10^7 arguments).

@@ -5,17 +5,9 @@
 // itself: v_mfma_i32_16x16x64_i8 is emulated here as the exact integer dot product under the maps the kernel assumes -- row of A
 // and column of B from lane l & 15, the 16 bytes of lane l paired byte for byte with the 16 bytes of the B lane in the same
 // group l >> 4; accumulator register i of lane l is row 4 (l >> 4) + i, column l & 15.  The GPU suite decides that.
-#include <cstring>
-#include <vector>
-
-#include "lce_device_intrinsics.h"      // the host replacement: build/ comes first on the include path
-#define __HIPCC__ 1
-#define __host__
-#define __device__
-#define __forceinline__ inline
+#include "sim_harness.h"
 typedef int32_t sim_i32x4 __attribute__((vector_size(16)));      // the kernel header's i32x4
 // (lce_kernels_eltwise_i8.h and lce_kernels_head.h come along for the gemmlowp steps and the stated exp; their kernels are not run here)
-inline int __builtin_amdgcn_mov_dpp(int, int, int, int, bool) { __builtin_trap(); }
 inline lce_dev::f32x4 __builtin_amdgcn_mfma_f32_16x16x4f32(float, float, lce_dev::f32x4, int, int, int) { __builtin_trap(); }
 inline sim_i32x4 __builtin_amdgcn_mfma_i32_16x16x64_i8(sim_i32x4 a, sim_i32x4 b, sim_i32x4 c, int, int, int) {
   const int lane = g_ctx.tid_x & 63;
@@ -38,22 +30,7 @@ inline sim_i32x4 __builtin_amdgcn_mfma_i32_16x16x64_i8(sim_i32x4 a, sim_i32x4 b,
 
 namespace {
 template <typename F>
-void launch(unsigned gx, F kernel) {
-  for (unsigned bx = 0; bx < gx; ++bx) {
-    std::vector<uint32_t> xchg(4 * 64), mx(4 * 64 * 8);
-    lce_dev::FiberBarrier block_bar(256);
-    lce_dev::FiberBarrier wave_bar[4] = {lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64),
-                                         lce_dev::FiberBarrier(64)};
-    lce_dev::run_fibers(256,
-      [&](int t, lce_dev::ThreadCtx& c) {
-        const int w = t >> 6;
-        c.tid_x = t; c.bid_x = (int)bx; c.bid_y = 0; c.bdim_x = 256; c.gdim_x = (int)gx;
-        c.bar = &wave_bar[w]; c.xchg = xchg.data() + w * 64; c.mfma_xchg = mx.data() + w * 64 * 8; c.block_bar = &block_bar;
-      },
-      [&](int) { kernel(); });
-  }
-}
-unsigned capped(uint64_t blocks, int32_t cap) { return (unsigned)(blocks < (uint64_t)cap ? blocks : (uint64_t)cap); }
+void launch(unsigned gx, F kernel) { sim::launch(gx, 256, kernel, /*mfma_xchg=*/true); }
 }  // namespace
 
 // d: batch, inputs, outputs, output zero point, act_min, act_max.  `table`: [3][outputs] as lce_hip_fully_connected_i8_prepare
@@ -64,12 +41,10 @@ extern "C" int lce_hostsim_fully_connected_i8(const int32_t* d, const int8_t* in
   lce::FcI8Args a;
   memset(&a, 0, sizeof a);
   a.in = in; a.filter = weights; a.table = table; a.out = out;
-  a.M = (uint32_t)d[0]; a.K = (uint32_t)d[1]; a.N = (uint32_t)d[2];
-  a.ntiles = (a.N + lce::kFcI8Tile - 1) / lce::kFcI8Tile;
-  a.tiles = ((a.M + lce::kFcI8Tile - 1) / lce::kFcI8Tile) * a.ntiles;
+  lce::fc_i8_fill(a, d[0], d[1], d[2]);
   a.zo = d[3]; a.act_min = d[4]; a.act_max = d[5];
-  const bool vec = a.K % 16 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)weights % 16 == 0;      // lce_hip_fully_connected_i8's rule
-  const unsigned gx = capped((a.tiles + 3) / 4, cap);                                              // launch_fully_connected_i8's grid
+  const bool vec = lce::fc_i8_vec_rule(a);
+  const unsigned gx = lce::fc_i8_grid(a, (uint64_t)cap);
   if (vec) launch(gx, [&] { lce::fully_connected_i8<true>(a); });
   else launch(gx, [&] { lce::fully_connected_i8<false>(a); });
   return vec ? 1 : 0;
@@ -82,7 +57,7 @@ extern "C" void lce_hostsim_mean_i8(const int32_t* d, const int8_t* in, int8_t* 
   a.in = in; a.out = out; a.batch = (uint64_t)d[0]; a.n = (uint32_t)d[1]; a.C = (uint32_t)d[2];
   a.segs = (a.C + lce::kMeanI8Channels - 1) / lce::kMeanI8Channels;
   a.zi = d[3]; a.zo = d[4]; a.mul = d[5]; a.left = d[6] > 0 ? d[6] : 0; a.right = d[6] > 0 ? 0 : -d[6];
-  launch(capped((a.batch * a.segs + 3) / 4, cap), [&] { lce::mean_i8<4>(a); });
+  launch(lce::stream_grid(a.batch * a.segs, 4, (uint64_t)cap), [&] { lce::mean_i8<4>(a); });
 }
 
 extern "C" void lce_hostsim_softmax_i8(int64_t rows, int32_t cols, float input_scale, float beta, const int8_t* in, int8_t* out, int32_t cap) {
@@ -90,14 +65,14 @@ extern "C" void lce_hostsim_softmax_i8(int64_t rows, int32_t cols, float input_s
   memset(&a, 0, sizeof a);
   a.in = in; a.out = out; a.rows = (uint64_t)rows; a.cols = (uint32_t)cols;
   a.sb = input_scale * beta;
-  launch(capped((a.rows + 3) / 4, cap), [&] { lce::softmax_i8<4>(a); });
+  launch(lce::stream_grid(a.rows, 4, (uint64_t)cap), [&] { lce::softmax_i8<4>(a); });
 }
 
 extern "C" void lce_hostsim_quant_i8(int32_t quantize, int64_t n, float scale, int32_t zp, const void* in, void* out, int32_t cap) {
   lce::QuantArgs a;
   memset(&a, 0, sizeof a);
   a.in = in; a.out = out; a.n = (uint64_t)n; a.scale = scale; a.zp = zp;
-  const unsigned gx = capped((a.n + 255) / 256, cap);
+  const unsigned gx = lce::stream_grid(a.n, 256, (uint64_t)cap);       // one element per lane, as launch_quantize_f32_i8 launches it
   if (quantize) launch(gx, [&] { lce::quant_i8<true>(a); });
   else launch(gx, [&] { lce::quant_i8<false>(a); });
 }

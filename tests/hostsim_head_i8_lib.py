@@ -3,13 +3,14 @@ of it: one launch of each kernel on exact-size buffers, and the value functions 
 here."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import hostsim_lib
+
 import conv2d_i8_ref as CR
 import head_i8_ref as H
-from hostsim_conv2d_i8_lib import placed
+from hostsim_lib import placed
 
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_head_i8")
 OUT_MARK = np.int8(0x5A)
@@ -17,15 +18,10 @@ _lib = None
 
 
 def lib():
-    """tests/hostsim_head_i8/liblce_hostsim_head_i8.so, brought up to date with the kernel headers first (as
-    tests/hostsim_lib.py does: among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_head_i8/liblce_hostsim_head_i8.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        l = C.CDLL(os.path.join(DIR, "liblce_hostsim_head_i8.so"))
+        l = hostsim_lib.load(DIR, "liblce_hostsim_head_i8.so")
         l.lce_hostsim_fully_connected_i8.argtypes = [C.c_void_p] * 5 + [C.c_int32]
         l.lce_hostsim_mean_i8.argtypes, l.lce_hostsim_mean_i8.restype = [C.c_void_p] * 3 + [C.c_int32], None
         l.lce_hostsim_softmax_i8.argtypes = [C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]

@@ -3,32 +3,12 @@
 // so the window table, the chunk bookkeeping of the vector path, its grid stride, the partial last block, the addend, the
 // shuffles and the row path's ballots are exercised without a GPU.  The path and the kernel arguments come from the very
 // functions the entry point uses (join_fill, join_set_stride).
-#include <cstring>
-#include <vector>
-
-#include "lce_device_intrinsics.h"      // the host replacement: build/ comes first on the include path
-// v_mov_b32 quad_perm:[1,0,3,2], the only DPP control the kernels use: the neighbouring lane's value
-inline int __builtin_amdgcn_mov_dpp(int v, int, int, int, bool) { return (int)lce_dev::shfl_xor((uint32_t)v, 1); }
-#define __HIPCC__ 1
+#include "sim_harness.h"
 #include "lce_kernels_join.h"
 
 namespace {
 template <typename F>
-void launch(unsigned gx, F kernel) {
-  for (unsigned bx = 0; bx < gx; ++bx) {
-    std::vector<uint32_t> xchg(4 * 64);
-    lce_dev::FiberBarrier block_bar(256);
-    lce_dev::FiberBarrier wave_bar[4] = {lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64), lce_dev::FiberBarrier(64),
-                                         lce_dev::FiberBarrier(64)};
-    lce_dev::run_fibers(256,
-      [&](int t, lce_dev::ThreadCtx& c) {
-        const int w = t >> 6;
-        c.tid_x = t; c.bid_x = (int)bx; c.bid_y = 0; c.bdim_x = 256; c.gdim_x = (int)gx;
-        c.bar = &wave_bar[w]; c.xchg = xchg.data() + w * 64; c.block_bar = &block_bar;
-      },
-      [&](int) { kernel(); });
-  }
-}
+void launch(unsigned gx, F kernel) { sim::launch(gx, 256, kernel); }
 }  // namespace
 
 // One launch.  `kind`: 0 float32, 1 int8.  Window k is (src[k], pitch[k], begin[k], count[k], addend[k] or null), in elements.
@@ -42,10 +22,7 @@ extern "C" int lce_hostsim_join(int32_t kind, int32_t n, const void* const* src,
   lce::JoinArgs a;
   const bool vec = lce::join_fill(a, kind, w, n, (uint64_t)rows, zero_point, out, bits);
   const bool add = lce::join_has_addend(a);
-  auto grid = [&](uint64_t wave_tasks) {                    // lce_tu_join.hip's, with the cap a parameter
-    const uint64_t blocks = (wave_tasks + 3) / 4;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > (uint64_t)cap ? (uint64_t)cap : blocks));
-  };
+  auto grid = [&](uint64_t wave_tasks) { return lce::stream_grid(wave_tasks, 4, (uint64_t)cap); };
   if (vec) {
     const unsigned g = grid((a.total_chunks + 255) / 256);
     lce::join_set_stride(a, g);

@@ -2,47 +2,29 @@
 of it: a launch of the window join on exact-size buffers between guard bytes.  No tests here."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+import hostsim_lib
+
 DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_join")
-GUARD = 64                                  # guard bytes on either side of every buffer
 MARK = 0x5A
 _lib = None
 
 
 def lib():
-    """tests/hostsim_join/liblce_hostsim_join.so, brought up to date with the kernel header first (as tests/hostsim_lib.py does:
-    among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_join/liblce_hostsim_join.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        l = C.CDLL(os.path.join(DIR, "liblce_hostsim_join.so"))
+        l = hostsim_lib.load(DIR, "liblce_hostsim_join.so")
         l.lce_hostsim_join.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
         _lib = l
     return _lib
 
 
-class Placed:
-    """An exact-size array whose first byte lies `offset` bytes behind a 16-byte boundary, between GUARD bytes of MARK on either
-    side: a write past an end is seen by intact()."""
-
-    def __init__(self, shape, dtype, offset, data=None):
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        self.buf = np.full(n + 2 * GUARD + 32, MARK, np.uint8)
-        self.start = GUARD + (-(self.buf.ctypes.data + GUARD)) % 16 + offset
-        self.n = n
-        self.view = self.buf[self.start:self.start + n].view(dtype).reshape(shape)
-        assert self.view.ctypes.data % 16 == offset
-        if data is not None:
-            self.view[...] = data
-
-    def intact(self):
-        return bool(np.all(self.buf[:self.start] == MARK) and np.all(self.buf[self.start + self.n:] == MARK))
+def Placed(shape, dtype, offset, data=None):
+    """hostsim_lib.Placed with every guard byte MARK."""
+    return hostsim_lib.Placed(shape, dtype, offset, np.frombuffer(bytes([MARK]) * np.dtype(dtype).itemsize, dtype)[0], data)
 
 
 def sim(windows, zero_point=0, value=True, bits=True, cap=2048, offset=0):

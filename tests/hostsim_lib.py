@@ -32,14 +32,61 @@ def make_desc(spec: O.ConvSpec, dst_type: int, out_scale: float = 1.0, out_zero_
                 spec.semantics, float(out_scale), int(out_zero_point))
 
 
+def load(directory: str, library: str) -> C.CDLL:
+    """`library` of the host simulation in `directory`, brought up to date with the kernel headers first (among pytest-xdist
+    workers one builds and the others wait).  Every tests/hostsim_*_lib.py loads its library through this."""
+    import fcntl
+    with open(os.path.join(directory, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        subprocess.run(["make", "-C", directory], check=True, capture_output=True)
+    return C.CDLL(os.path.join(directory, library))
+
+
+def placed(a, offset=0):
+    """A copy of `a`, exact in size, whose first byte lies `offset` bytes behind a 16-byte boundary."""
+    a = np.ascontiguousarray(a)
+    buf = np.zeros(a.nbytes + 32, np.uint8)
+    start = (-buf.ctypes.data) % 16 + offset
+    v = buf[start:start + a.nbytes].view(a.dtype).reshape(a.shape)
+    v[...] = a
+    assert v.ctypes.data % 16 == offset
+    return v
+
+
+GUARD = 64                                  # guard bytes on either side of a Placed buffer
+
+
+class Placed:
+    """An exact-size array of `shape` and `dtype` whose first byte lies `offset` bytes behind a 16-byte boundary, between GUARD bytes
+    on either side.  The guards hold `mark`, an element of `dtype`, and so does the array unless `data` is given: a read past an end
+    meets the mark (a NaN for floats that ask for it), a write past an end is seen by intact()."""
+
+    def __init__(self, shape, dtype, offset, mark, data=None):
+        dt = np.dtype(dtype)
+        self.n = int(np.prod(shape)) * dt.itemsize
+        self.buf = np.zeros(self.n + 2 * GUARD + 32, np.uint8)
+        self.start = GUARD + (-(self.buf.ctypes.data + GUARD)) % 16 + offset
+        pattern = np.array([mark]).astype(dt).view(np.uint8)
+        self.buf[...] = pattern[(np.arange(self.buf.size) - self.start) % dt.itemsize]
+        self.marks = self.buf.copy()
+        self.view = self.buf[self.start:self.start + self.n].view(dt).reshape(shape)
+        assert self.view.ctypes.data % 16 == offset
+        if data is not None:
+            self.view[...] = np.ascontiguousarray(data).view(dt).reshape(shape)
+
+    @property
+    def ptr(self):
+        return self.view.ctypes.data
+
+    def intact(self):
+        end = self.start + self.n
+        return np.array_equal(self.buf[:self.start], self.marks[:self.start]) and np.array_equal(self.buf[end:], self.marks[end:])
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(_DIR, ".build.lock"), "w") as lock:       # (pytest-xdist workers: one of them builds, the others wait)
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", _DIR], check=True, capture_output=True)
-        _lib = C.CDLL(os.path.join(_DIR, "liblce_hostsim.so"))
+        _lib = load(_DIR, "liblce_hostsim.so")
         _lib.hostsim_last_error.restype = C.c_char_p
         _lib.hostsim_fastdiv.restype = C.c_uint32
     return _lib

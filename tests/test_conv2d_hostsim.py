@@ -7,12 +7,12 @@ a chain -- is the GPU suite's (tests/test_gpu_conv2d.py)."""
 import ctypes as C
 import os
 from section_models import float_fixture
-import subprocess
 
 import numpy as np
 import pytest
 
 import conv2d_ref as R
+import hostsim_lib
 import oracle_lib as O
 from test_conv2d_sections_host import ACTS, KNOWN, grid_operands, known_case
 
@@ -22,27 +22,17 @@ _lib = None
 
 
 def lib():
-    """tests/hostsim_conv2d/liblce_hostsim_conv2d.so, brought up to date with the kernel headers first (as tests/hostsim_lib.py
-    does: among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_conv2d/liblce_hostsim_conv2d.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        _lib = C.CDLL(os.path.join(DIR, "liblce_hostsim_conv2d.so"))
+        _lib = hostsim_lib.load(DIR, "liblce_hostsim_conv2d.so")
         _lib.lce_hostsim_conv2d.argtypes = [C.c_void_p] * 6 + [C.c_int32]
     return _lib
 
 
 def placed(a, offset):
     """A copy of `a` whose first byte lies `offset` floats behind a 16-byte boundary."""
-    buf = np.zeros(a.size + 8, a.dtype)
-    start = (-buf.ctypes.data // 4) % 4 + offset
-    v = buf[start:start + a.size].reshape(a.shape)
-    v[...] = a
-    assert v.ctypes.data % 16 == 4 * offset
-    return v
+    return hostsim_lib.placed(a, 4 * offset)
 
 
 def sim(x, w, bias, stride, padding, act, want_out=True, want_bits=True, cap=3, offset=0):

@@ -7,13 +7,13 @@ import ctypes as C
 import importlib
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import conv1x1_ref as CR
 import head_ref as HR
+import hostsim_lib
 from section_models import float_fixture
 
 amd = importlib.import_module("compute-engine_amd")
@@ -29,15 +29,10 @@ _lib = None
 
 
 def lib():
-    """tests/hostsim_head/liblce_hostsim_head.so, brought up to date with the kernel header first (as tests/hostsim_lib.py does:
-    among pytest-xdist workers one builds and the others wait)."""
+    """tests/hostsim_head/liblce_hostsim_head.so (hostsim_lib.load brings it up to date first)."""
     global _lib
     if _lib is None:
-        import fcntl
-        with open(os.path.join(DIR, ".build.lock"), "w") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            subprocess.run(["make", "-C", DIR], check=True, capture_output=True)
-        _lib = C.CDLL(os.path.join(DIR, "liblce_hostsim_head.so"))
+        _lib = hostsim_lib.load(DIR, "liblce_hostsim_head.so")
         _lib.lce_hostsim_fully_connected.argtypes = [C.c_void_p] * 5 + [C.c_int32]
         _lib.lce_hostsim_softmax.argtypes = [C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32]
         _lib.lce_hostsim_softmax.restype = None
@@ -48,12 +43,7 @@ def lib():
 
 def placed(a, offset):
     """A copy of `a` whose first byte lies `offset` floats behind a 16-byte boundary."""
-    buf = np.zeros(a.size + 8, a.dtype)
-    start = (-buf.ctypes.data // 4) % 4 + offset
-    v = buf[start:start + a.size].reshape(a.shape)
-    v[...] = a
-    assert v.ctypes.data % 16 == 4 * offset
-    return v
+    return hostsim_lib.placed(a, 4 * offset)
 
 
 def sim_fc(x, w, bias, act, cap=3, offset=0):
