@@ -92,5 +92,46 @@ LCE_DEVICE void tile_words(unsigned long long (&b)[4], uint32_t& words) {
   words = write_lane_settled<8 * G + 7>((uint32_t)(b[3] >> 32), words);
 }
 
+// How the section kernels write bits from the registers of the pass.  A kernel keeps its own three prologue lines (lane, wave0,
+// nwaves from thread_idx_x / block_idx_x / block_dim_x / grid_dim_x): behind a helper the compiler fetches blockDim the long way
+// (docs/kernels.md, "Shared device helpers").  The two word helpers form the word's address in front of the shuffles: written
+// inside the `if`, the compiler orders the or and the address arithmetic of every caller the other way round.
+
+// The row path: lane l of a wave holds column seg * 64 + l of row `row` and `neg`, its bit (false beyond the row's end); one
+// ballot is the row's words seg * 2 and seg * 2 + 1, which lanes 0 and 1 store if the row has them.  Every lane of the wave must
+// be active; row and seg are the wave's.
+LCE_DEVICE void store_seg_bits(uint32_t* bits, uint32_t wpr, uint64_t row, uint32_t seg, int lane, bool neg) {
+  const unsigned long long bal = wave_ballot(neg);
+  const uint32_t wd = seg * 2u + (uint32_t)lane;
+  if (lane < 2 && wd < wpr) bits[row * (uint64_t)wpr + wd] = (uint32_t)(bal >> (32 * lane));
+}
+
+// v_mov_b32 quad_perm:[1,0,3,2]: the value of the neighbouring lane (lane ^ 1).  Every lane of the wave must be active.
+LCE_DEVICE uint32_t lane_neighbour(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
+
+// A float 16-byte chunk is 4 sign bits (`nib`), and the 8 neighbouring lanes that hold chunks g & ~7 .. g | 7 make word g >> 3 with
+// three xor-shuffles; the first of them stores it.  Every lane of the wave must be active; the 8 lanes of a word must agree on ok
+// (the chunk count is a multiple of 8).
+LCE_DEVICE void store_nibble_word(uint32_t* bits, uint64_t g, int lane, bool ok, uint32_t nib) {
+  uint32_t* at = bits + (g >> 3);
+  uint32_t word = nib << (4 * (lane & 7));
+  word |= shfl_xor(word, 1);
+  word |= shfl_xor(word, 2);
+  word |= shfl_xor(word, 4);
+  if (ok && (lane & 7) == 0) *at = word;
+}
+
+// An int8 16-byte chunk is 16 bits (`m`), and lanes 2p and 2p + 1, which hold chunks g and g + 1, make word g >> 1 with one
+// lane_neighbour; the even lane stores it.  Every lane of the wave must be active; the two lanes of a word must agree on ok (the
+// chunk count is even).  ZERO_PAST_END: a lane past the end contributes 0 (the kernels on PoolArgs; the flat
+// elementwise kernels, whose lanes past the end compute on zeros, leave it out -- such a word is never stored either way).
+template <bool ZERO_PAST_END>
+LCE_DEVICE void store_half_word(uint32_t* bits, uint64_t g, int lane, bool ok, uint32_t m) {
+  uint32_t* at = bits + (g >> 1);
+  uint32_t word = ZERO_PAST_END ? (ok ? m << (16 * (lane & 1)) : 0u) : m << (16 * (lane & 1));
+  word |= lane_neighbour(word);
+  if (ok && (lane & 1) == 0) *at = word;
+}
+
 }  // namespace lce
 #endif  // __HIPCC__

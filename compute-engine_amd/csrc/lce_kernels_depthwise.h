@@ -17,7 +17,7 @@
 //                    lane owns one 16-byte chunk of one output pixel: four independent fmaf chains.  A window row is walked
 //                    with 16-byte loads, up to four taps in flight; the lane's weights w[fy][fx][c .. c + 3] are 16-byte loads
 //                    through the cache beside each input tap (the filter is a few KB and every wave reads all of it).
-//                    Bits: 8 lanes per word, three xor-shuffles.  Streaming stores.
+//                    Bits: 8 lanes per word (store_nibble_word).  Streaming stores.
 //   depthwise_rows : anything else (ragged C, m > 1, unaligned pointers, bits on C % 32 != 0) -- one wave per 64 output
 //                    channels of a pixel, one element per lane, one ballot per two words.
 // Offsets are 64-bit beyond the window arithmetic.  No LDS, no scratch, nothing allocated: the launch is capturable.  The
@@ -99,12 +99,10 @@ depthwise_vec(const DepthwiseArgs A) {
   uint32_t c0 = (uint32_t)(wave0 * 64ull - (uint64_t)pix0 * cpp);
   const bool nt = P.stream_loads != 0u;
   for (uint64_t blk = wave0; blk < nblocks; blk += nwaves) {       // 64 chunks = 1 KB of output per wave and iteration
-    const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
-    const bool ok = g < P.total;
-    const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = fast_div(x, P.div_per_pixel);
-    const uint32_t c = x - q * cpp;                                // < per_pixel, also for a lane past the end
-    const PoolWindow w = pool_window(P, pix0 + q, ok);
+    uint64_t g;                                                    // this lane's chunk
+    bool ok;
+    uint32_t c;
+    const PoolWindow w = pool_chunk_at(P, pix0, c0, blk, lane, g, ok, c);
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (nt) depthwise_walk_chunk<true, STAGED>(A, w, c, (const f32x4*)depthwise_lds, acc);
     else depthwise_walk_chunk<false, STAGED>(A, w, c, (const f32x4*)depthwise_lds, acc);
@@ -120,16 +118,8 @@ depthwise_vec(const DepthwiseArgs A) {
       nib |= (o[e] < 0.0f ? 1u : 0u) << e;
     }
     if (P.out && ok) store_streaming((f32x4*)P.out + g, o);
-    if constexpr (BITS) {                                          // per_pixel % 8 == 0: the 8 lanes of a word agree on ok
-      uint32_t word = nib << (4 * (lane & 7));
-      word |= shfl_xor(word, 1);
-      word |= shfl_xor(word, 2);
-      word |= shfl_xor(word, 4);
-      if (ok && (lane & 7) == 0) P.bits[g >> 3] = word;
-    }
-    pix0 += P.step_pixels;
-    c0 += P.step_chunks;
-    if (c0 >= cpp) { c0 -= cpp; ++pix0; }
+    if constexpr (BITS) store_nibble_word(P.bits, g, lane, ok, nib);   // per_pixel % 8 == 0: the 8 lanes of a word agree on ok
+    pool_chunk_step(P, pix0, c0);
   }
 }
 
@@ -162,11 +152,7 @@ depthwise_rows(const DepthwiseArgs A) {
       if (P.out) ((float*)P.out)[pixel * (uint64_t)cols + col] = r;
       neg = r < 0.0f;
     }
-    if constexpr (BITS) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t wd = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && wd < P.wpr) P.bits[pixel * (uint64_t)P.wpr + wd] = (uint32_t)(bal >> (32 * lane));
-    }
+    if constexpr (BITS) store_seg_bits(P.bits, P.wpr, pixel, seg, lane, neg);
   }
 }
 

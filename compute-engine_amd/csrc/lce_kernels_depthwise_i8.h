@@ -11,7 +11,7 @@
 //   v   = min(max(acc + zo, act_min), act_max);   bit = v < zo, LSB first, ceil(Cout / 32) words per pixel, padding bits 0
 //
 // Two paths, siblings of depthwise_vec / depthwise_rows and of the pools' int8 path, whose window, division, grid-stride scheme,
-// 16-byte int8 store and two-lane word (lce_kernels_pool.h) they share (DepthwiseI8Args carries a PoolArgs):
+// 16-byte int8 store (lce_kernels_pool.h) and two-lane word (store_half_word) they share (DepthwiseI8Args carries a PoolArgs):
 //   depthwise_i8_vec  : m == 1, C % 16 == 0, input, filter, table and output 16-byte aligned (and, with bits, C % 32 == 0) -- a
 //                       lane owns one 16-byte chunk (16 channels) of one output pixel: 16 int32 accumulators.  Each tap of the
 //                       CLIPPED window is one 16-byte load of the input and one of w[fy][fx][c .. c + 15], up to four taps of a
@@ -106,12 +106,10 @@ depthwise_i8_vec(const DepthwiseI8Args A) {
   const bool nt = P.stream_loads != 0u;
   const i32x4* table = (const i32x4*)A.table;                      // a row is Cout ints = 4 cpp vectors
   for (uint64_t blk = wave0; blk < nblocks; blk += nwaves) {       // 64 chunks = 1 KB of output per wave and iteration
-    const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
-    const bool ok = g < P.total;
-    const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = fast_div(x, P.div_per_pixel);
-    const uint32_t c = x - q * cpp;                                // < per_pixel, also for a lane past the end
-    const PoolWindow w = pool_window(P, pix0 + q, ok);
+    uint64_t g;                                                    // this lane's chunk
+    bool ok;
+    uint32_t c;
+    const PoolWindow w = pool_chunk_at(P, pix0, c0, blk, lane, g, ok, c);
     int32_t acc[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[e] = 0;
@@ -131,14 +129,8 @@ depthwise_i8_vec(const DepthwiseI8Args A) {
       o[d] = pack4_u8(r[0], r[1], r[2], r[3]);
     }
     if (P.out && ok) pool_store_through((u32x4*)P.out + g, o);
-    if constexpr (BITS) {                                          // per_pixel % 2 == 0: lanes 2p and 2p + 1 agree on ok
-      uint32_t word = ok ? m << (16 * (lane & 1)) : 0u;
-      word |= pool_neighbour(word);
-      if (ok && (lane & 1) == 0) P.bits[g >> 1] = word;
-    }
-    pix0 += P.step_pixels;
-    c0 += P.step_chunks;
-    if (c0 >= cpp) { c0 -= cpp; ++pix0; }
+    if constexpr (BITS) store_half_word<true>(P.bits, g, lane, ok, m);   // per_pixel % 2 == 0: lanes 2p and 2p + 1 agree on ok
+    pool_chunk_step(P, pix0, c0);
   }
 }
 
@@ -171,11 +163,7 @@ depthwise_i8_rows(const DepthwiseI8Args A) {
       if (P.out) ((int8_t*)P.out)[pixel * (uint64_t)cols + col] = (int8_t)r;
       neg = r < P.zero_point;
     }
-    if constexpr (BITS) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t wd = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && wd < P.wpr) P.bits[pixel * (uint64_t)P.wpr + wd] = (uint32_t)(bal >> (32 * lane));
-    }
+    if constexpr (BITS) store_seg_bits(P.bits, P.wpr, pixel, seg, lane, neg);
   }
 }
 

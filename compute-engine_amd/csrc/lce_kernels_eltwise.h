@@ -30,7 +30,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "lce_kernel_args.h"
+#include "lce_kernels_common.h"
 
 namespace lce {
 
@@ -260,11 +260,7 @@ eltwise_rows(const typename EwArgsOf<EX>::type A, uint32_t segs, uint64_t total_
       if (A.out) A.out[e] = v;
       neg = v < 0.0f;
     }
-    if (A.bits) {
-      const unsigned long long b = wave_ballot(neg);
-      const uint32_t w = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && w < A.wpr) A.bits[row * (uint64_t)A.wpr + w] = (uint32_t)(b >> (32 * lane));
-    }
+    if (A.bits) store_seg_bits(A.bits, A.wpr, row, seg, lane, neg);
   }
 }
 

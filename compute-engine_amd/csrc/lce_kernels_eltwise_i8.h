@@ -28,14 +28,14 @@
 // Two paths, chosen as lce_hip_bitpack / lce_hip_elementwise choose:
 //   add_i8_flat : C % 32 == 0 and every pointer 16-byte aligned -- the tensors are flat arrays; a lane turns 16 bytes of each
 //                 input per load, four loads of each tensor in flight, 64 lanes x 16 contiguous bytes per load instruction;
-//                 a lane's 16 sign bits meet its neighbour's in one DPP quad permute and the even lane stores the word.
+//                 a lane's 16 sign bits meet its neighbour's and the even lane stores the word (store_half_word).
 //   add_i8_rows : anything else -- one wave per 64 columns of a row, one element per lane, one ballot per two words.
 // `out` may alias either input: each element is read and written by the same lane, all loads of an iteration come before
 // its stores, and no pointer is declared __restrict__.  No LDS, no scratch; the parameters travel in the kernel arguments.
 #pragma once
 #include <stdint.h>
 
-#include "lce_kernel_args.h"
+#include "lce_kernels_common.h"
 
 namespace lce {
 
@@ -124,9 +124,6 @@ LCE_HOST_DEVICE int32_t add_i8_value(const AddI8Args& A, int32_t x1, int32_t x2)
   }
 }
 
-// v_mov_b32 quad_perm:[1,0,3,2]: the value of the neighbouring lane (lane ^ 1).  Every lane of the wave must be active.
-LCE_DEVICE uint32_t add_i8_neighbour(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
-
 template <int V>
 LCE_KERNEL void __launch_bounds__(256)
 add_i8_flat(const AddI8Args A, uint64_t total_chunks) {           // chunk = 16 bytes = half a word of bits; the count is even
@@ -161,11 +158,7 @@ add_i8_flat(const AddI8Args A, uint64_t total_chunks) {           // chunk = 16 
         o[w] = pack4_u8(q[0] + A.zo, q[1] + A.zo, q[2] + A.zo, q[3] + A.zo);
       }
       if (A.out && ok[j]) *((u32x4*)A.out + c0 + 64u * j) = o;
-      if (A.bits) {
-        uint32_t word = m << (16 * (lane & 1));
-        word |= add_i8_neighbour(word);
-        if (ok[j] && (lane & 1) == 0) A.bits[(c0 + 64u * j) >> 1] = word;
-      }
+      if (A.bits) store_half_word<false>(A.bits, c0 + 64u * j, lane, ok[j], m);
     }
   }
 }
@@ -188,11 +181,7 @@ add_i8_rows(const AddI8Args A, uint32_t segs, uint64_t total_tasks) {
       if (A.out) A.out[e] = (int8_t)(q + A.zo);
       neg = q < 0;
     }
-    if (A.bits) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t w = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && w < A.wpr) A.bits[row * (uint64_t)A.wpr + w] = (uint32_t)(bal >> (32 * lane));
-    }
+    if (A.bits) store_seg_bits(A.bits, A.wpr, row, seg, lane, neg);
   }
 }
 

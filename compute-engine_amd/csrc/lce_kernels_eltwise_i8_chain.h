@@ -156,9 +156,9 @@ ew_i8_flat(const EwI8Args E, uint64_t total_chunks) {              // chunk = 16
         o[w] = t[0] | (t[1] << 8) | (t[2] << 16) | (t[3] << 24);
       }
       if (A.out && ok[j]) *((u32x4*)A.out + c0 + 64u * j) = o;
-      if (A.bits) {
+      if (A.bits) {                                                // (store_half_word's text: through it two instances come out different)
         uint32_t word = m << (16 * (lane & 1));
-        word |= add_i8_neighbour(word);
+        word |= lane_neighbour(word);
         if (ok[j] && (lane & 1) == 0) A.bits[(c0 + 64u * j) >> 1] = word;
       }
     }
@@ -190,11 +190,7 @@ ew_i8_rows(const EwI8Args E, uint32_t segs, uint64_t total_tasks) {
       if (A.out) A.out[e] = (int8_t)q;
       neg = (int32_t)(int8_t)q < E.zo_last;
     }
-    if (A.bits) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t w = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && w < A.wpr) A.bits[row * (uint64_t)A.wpr + w] = (uint32_t)(bal >> (32 * lane));
-    }
+    if (A.bits) store_seg_bits(A.bits, A.wpr, row, seg, lane, neg);
   }
 }
 

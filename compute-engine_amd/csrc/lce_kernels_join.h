@@ -19,7 +19,9 @@
 //               multiply-high.  The window a chunk comes from is found by comparing against <= 7 chunk offsets that travel in
 //               the kernel arguments.  All loads of an iteration (sources and addends) are issued before the first add.
 //               Float: a chunk is 4 sign bits, 8 neighbouring lanes make a word (3 xor-shuffles).  int8: a chunk is 16 bits
-//               from four byte-parallel compares, 2 neighbouring lanes make a word (one DPP quad permute).
+//               from four byte-parallel compares, 2 neighbouring lanes make a word (lane_neighbour).  The words and the row
+//               path's ballot are written out here, not through lce_kernels_common.h's helpers: with them the compiler orders
+//               the instructions of four of the nine kernels differently (docs/kernels.md, "Shared device helpers").
 //   join_rows : anything else (ragged channel counts, unaligned pointers) -- one wave per 64 columns of an output row, one
 //               element per lane, one ballot per two words.
 // A launch without any addend runs an instance that holds no addend code.  All offsets are 64-bit (rows < 2^32, sum count and
@@ -136,9 +138,6 @@ LCE_DEVICE uint32_t join_lt4(uint32_t x, uint32_t t4) {
   return ((lt >> 7) * 0x01020408u) >> 24;                         // bits 0, 8, 16, 24 -> 24, 25, 26, 27
 }
 
-// v_mov_b32 quad_perm:[1,0,3,2]: the value of the neighbouring lane (lane ^ 1).  Every lane of the wave must be active.
-LCE_DEVICE uint32_t join_neighbour(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
-
 template <int KIND, bool BITS, bool ADD>
 LCE_KERNEL void __launch_bounds__(256)
 join_vec(const JoinArgs A) {
@@ -206,7 +205,7 @@ join_vec(const JoinArgs A) {
         const uint32_t m = join_lt4(v[j][0], t4) | (join_lt4(v[j][1], t4) << 4) | (join_lt4(v[j][2], t4) << 8) |
                            (join_lt4(v[j][3], t4) << 12);
         uint32_t word = ok[j] ? m << (16 * (lane & 1)) : 0u;
-        word |= join_neighbour(word);
+        word |= lane_neighbour(word);
         if (ok[j] && (lane & 1) == 0) A.bits[(g0 + 64u * j) >> 1] = word;
       }
     }

@@ -27,7 +27,7 @@
 //   mul_i8_flat : C % 16 == 0 and every pointer 16-byte aligned -- 16 bytes per lane and load, four loads of each tensor in
 //                 flight.  A 16-byte chunk lies in ONE row (C % 16 == 0), so in one image: every lane computes its own row and
 //                 image (64 lanes span several images when H * W * C is small) and reads its 16 gate bytes in one load; the gate
-//                 is b * C bytes and stays in cache.  Bits: for C % 32 == 0 the two halves of a word meet in add_i8_neighbour's
+//                 is b * C bytes and stays in cache.  Bits: for C % 32 == 0 the two halves of a word meet in store_half_word's
 //                 quad permute, as in the chain; for C % 32 == 16 a row has an odd number of chunks, so every lane stores its own
 //                 16 bits (a row's last chunk the whole word: the upper half is padding, 0).
 //   mul_i8_rows : anything else -- one wave per 64 columns of a row, one element per lane, one ballot per two words.  The row,
@@ -151,9 +151,7 @@ mul_i8_flat(const MulI8Args M, uint64_t total_chunks) {            // chunk = 16
       if (A.out && ok[j]) *((u32x4*)A.out + ch) = o;
       if (A.bits) {
         if (!odd) {
-          uint32_t word = m << (16 * (lane & 1));
-          word |= add_i8_neighbour(word);
-          if (ok[j] && (lane & 1) == 0) A.bits[ch >> 1] = word;
+          store_half_word<false>(A.bits, ch, lane, ok[j], m);
         } else if (ok[j]) {
           const uint32_t r = (uint32_t)(ch - row[j] * cpr);        // a row is cpr + 1 half words: half word r of row `row` is ch + row
           if (r + 1u == cpr) A.bits[row[j] * (uint64_t)A.wpr + (r >> 1)] = m;   // (r is even) the upper half is padding
@@ -185,11 +183,7 @@ mul_i8_rows(const MulI8Args M, uint32_t segs, uint64_t total_tasks) {
       if (A.out) A.out[e] = (int8_t)q;
       neg = q < M.zo_last;
     }
-    if (A.bits) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t w = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && w < A.wpr) A.bits[row * (uint64_t)A.wpr + w] = (uint32_t)(bal >> (32 * lane));
-    }
+    if (A.bits) store_seg_bits(A.bits, A.wpr, row, seg, lane, neg);
   }
 }
 

@@ -22,10 +22,10 @@
 //               of a wave's first chunk is divided out ONCE per wave and then advanced by the grid stride, whose quotient
 //               and remainder the host supplies; a lane's own offset (< 64 chunks) and the pixel's (b, oy, ox) take
 //               multiply-highs.  A lane walks its window with 16-byte loads, up to four taps of a window row in flight
-//               before they are reduced.  Float: a chunk is 4 sign bits, 8 neighbouring lanes make a word (3 xor-shuffles).
-//               int8: a chunk is 16 bits, 2 neighbouring lanes make a word (one DPP quad permute).
+//               before they are reduced.  Float: a chunk is 4 sign bits, 8 neighbouring lanes make a word
+//               (store_nibble_word).  int8: a chunk is 16 bits, 2 neighbouring lanes make a word (store_half_word).
 //   pool_rows : anything else (ragged C, unaligned pointers, bits on C % 32 != 0) -- one wave per 64 channels of an output
-//               pixel, one element per lane, one ballot per two words.
+//               pixel, one element per lane, one ballot per two words (store_seg_bits).
 // All offsets are 64-bit (output pixels < 2^31, C < 2^31, their product and the input's unbounded).  No LDS, no scratch,
 // nothing allocated: the launch is capturable.  The output must not overlap the input.
 #pragma once
@@ -108,9 +108,6 @@ int launch_pool(const PoolArgs& args, int kind, int op, bool vec, void* stream);
 namespace lce {
 using namespace lce_dev;
 
-// v_mov_b32 quad_perm:[1,0,3,2]: the value of the neighbouring lane (lane ^ 1).  Every lane of the wave must be active.
-LCE_DEVICE uint32_t pool_neighbour(uint32_t v) { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
-
 // 16-byte write-through store (sc1), the project's convention for int8 rows (lce_device_intrinsics.h, buf_store) on a flat
 // 64-bit address.  Nothing reads it back in this kernel, so nothing waits for it; the s_nop keeps the data registers
 // untouched until the store has read them.
@@ -140,6 +137,24 @@ LCE_DEVICE PoolWindow pool_window(const PoolArgs& A, uint32_t pixel, bool ok) {
   w.xs = xs;
   if (!ok) w.y1 = w.y0;                                            // (a lane past the end walks nothing)
   return w;
+}
+
+// The 16-byte-chunk kernels on PoolArgs: a wave's first chunk of an iteration is chunk c0 of pixel pix0, and lane l owns chunk
+// blk * 64 + l of the launch.  That chunk `g`, whether it exists (`ok`), its place `c` < per_pixel in its pixel (also for a lane
+// past the end) and the pixel's window.  Any lanes may be active; pix0, c0 and blk are the wave's.
+LCE_DEVICE PoolWindow pool_chunk_at(const PoolArgs& P, uint32_t pix0, uint32_t c0, uint64_t blk, int lane, uint64_t& g, bool& ok, uint32_t& c) {
+  g = blk * 64ull + (uint64_t)lane;
+  ok = g < P.total;
+  const uint32_t x = c0 + (uint32_t)lane;                          // < per_pixel + 64 < 2^31
+  const uint32_t q = fast_div(x, P.div_per_pixel);
+  c = x - q * P.per_pixel;
+  return pool_window(P, pix0 + q, ok);
+}
+// ... and the wave's first chunk one grid step on (pool_set_stride).  Wave-uniform.
+LCE_DEVICE void pool_chunk_step(const PoolArgs& P, uint32_t& pix0, uint32_t& c0) {
+  pix0 += P.step_pixels;
+  c0 += P.step_chunks;
+  if (c0 >= P.per_pixel) { c0 -= P.per_pixel; ++pix0; }
 }
 
 LCE_DEVICE float pool_clamp(float v, float lo, float hi) {
@@ -209,12 +224,10 @@ pool_vec(const PoolArgs A) {
   uint32_t c0 = (uint32_t)(wave0 * 64ull - (uint64_t)pix0 * cpp);
   const bool nt = A.stream_loads != 0u;
   for (uint64_t blk = wave0; blk < nblocks; blk += nwaves) {       // 64 chunks = 1 KB of output per wave and iteration
-    const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
-    const bool ok = g < A.total;
-    const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = fast_div(x, A.div_per_pixel);
-    const uint32_t c = x - q * cpp;
-    const PoolWindow w = pool_window(A, pix0 + q, ok);
+    uint64_t g;                                                    // this lane's chunk
+    bool ok;
+    uint32_t c;
+    const PoolWindow w = pool_chunk_at(A, pix0, c0, blk, lane, g, ok, c);
     const int32_t count = (w.y1 - w.y0) * (w.x1 - w.x0);
     float facc[kAcc];
     int32_t iacc[kAcc];
@@ -236,13 +249,7 @@ pool_vec(const PoolArgs A) {
         nib |= (o[k] < 0.0f ? 1u : 0u) << k;
       }
       if (A.out && ok) store_streaming((f32x4*)A.out + g, o);
-      if constexpr (BITS) {                                        // per_pixel % 8 == 0: the 8 lanes of a word agree on ok
-        uint32_t word = nib << (4 * (lane & 7));
-        word |= shfl_xor(word, 1);
-        word |= shfl_xor(word, 2);
-        word |= shfl_xor(word, 4);
-        if (ok && (lane & 7) == 0) A.bits[g >> 3] = word;
-      }
+      if constexpr (BITS) store_nibble_word(A.bits, g, lane, ok, nib);   // per_pixel % 8 == 0: the 8 lanes of a word agree on ok
     } else {
       u32x4 o;
       uint32_t m = 0;                                              // 16 bits
@@ -259,15 +266,9 @@ pool_vec(const PoolArgs A) {
         o[d] = pack4_u8(r[0], r[1], r[2], r[3]);
       }
       if (A.out && ok) pool_store_through((u32x4*)A.out + g, o);
-      if constexpr (BITS) {                                        // per_pixel % 2 == 0: lanes 2p and 2p + 1 agree on ok
-        uint32_t word = ok ? m << (16 * (lane & 1)) : 0u;
-        word |= pool_neighbour(word);
-        if (ok && (lane & 1) == 0) A.bits[g >> 1] = word;
-      }
+      if constexpr (BITS) store_half_word<true>(A.bits, g, lane, ok, m);   // per_pixel % 2 == 0: lanes 2p and 2p + 1 agree on ok
     }
-    pix0 += A.step_pixels;
-    c0 += A.step_chunks;
-    if (c0 >= cpp) { c0 -= cpp; ++pix0; }
+    pool_chunk_step(A, pix0, c0);
   }
 }
 
@@ -316,11 +317,7 @@ pool_rows(const PoolArgs A) {
         neg = r < A.zero_point;
       }
     }
-    if (A.bits) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t wd = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && wd < A.wpr) A.bits[pixel * (uint64_t)A.wpr + wd] = (uint32_t)(bal >> (32 * lane));
-    }
+    if (A.bits) store_seg_bits(A.bits, A.wpr, pixel, seg, lane, neg);
   }
 }
 

@@ -127,11 +127,7 @@ transition_rows(const TransitionArgs A) {
       if (P.out) ((float*)P.out)[pixel * (uint64_t)cols + col] = r;
       neg = r < 0.0f;
     }
-    if constexpr (BITS) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t wd = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && wd < P.wpr) P.bits[pixel * (uint64_t)P.wpr + wd] = (uint32_t)(bal >> (32 * lane));
-    }
+    if constexpr (BITS) store_seg_bits(P.bits, P.wpr, pixel, seg, lane, neg);
   }
 }
 
@@ -175,11 +171,7 @@ transition_i8_rows(const TransitionI8Args A) {
       if (P.out) ((int8_t*)P.out)[pixel * (uint64_t)cols + col] = (int8_t)r;
       neg = r < P.zero_point;
     }
-    if constexpr (BITS) {
-      const unsigned long long bal = wave_ballot(neg);
-      const uint32_t wd = seg * 2u + (uint32_t)lane;
-      if (lane < 2 && wd < P.wpr) P.bits[pixel * (uint64_t)P.wpr + wd] = (uint32_t)(bal >> (32 * lane));
-    }
+    if constexpr (BITS) store_seg_bits(P.bits, P.wpr, pixel, seg, lane, neg);
   }
 }
 
@@ -212,12 +204,10 @@ transition_vec(const TransitionArgs A) {
   const f32x4 lowest = {kTransitionLowest, kTransitionLowest, kTransitionLowest, kTransitionLowest};
   const bool two_rows = Q.fh == 2, two_cols = Q.fw == 2;
   for (uint64_t blk = wave0; blk < nblocks; blk += nwaves) {       // 64 chunks = 1 KB of output per wave and iteration
-    const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
-    const bool ok = g < P.total;
-    const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = fast_div(x, P.div_per_pixel);
-    const uint32_t c = x - q * cpp;                                // < per_pixel, also for a lane past the end
-    const PoolWindow w = pool_window(P, pix0 + q, ok);             // on the pooled map; a lane past the end has no pooled row
+    uint64_t g;                                                    // this lane's chunk
+    bool ok;
+    uint32_t c;
+    const PoolWindow w = pool_chunk_at(P, pix0, c0, blk, lane, g, ok, c);   // on the pooled map; a lane past the end has no pooled row
     const TransitionFootprint fp = transition_footprint(P, Q, w);
     const f32x4* flt = (const f32x4*)A.D.filter + c;
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -285,16 +275,8 @@ transition_vec(const TransitionArgs A) {
       nib |= (o[e] < 0.0f ? 1u : 0u) << e;
     }
     if (P.out && ok) store_streaming((f32x4*)P.out + g, o);
-    if constexpr (BITS) {                                          // per_pixel % 8 == 0: the 8 lanes of a word agree on ok
-      uint32_t word = nib << (4 * (lane & 7));
-      word |= shfl_xor(word, 1);
-      word |= shfl_xor(word, 2);
-      word |= shfl_xor(word, 4);
-      if (ok && (lane & 7) == 0) P.bits[g >> 3] = word;
-    }
-    pix0 += P.step_pixels;
-    c0 += P.step_chunks;
-    if (c0 >= cpp) { c0 -= cpp; ++pix0; }
+    if constexpr (BITS) store_nibble_word(P.bits, g, lane, ok, nib);   // per_pixel % 8 == 0: the 8 lanes of a word agree on ok
+    pool_chunk_step(P, pix0, c0);
   }
 }
 
@@ -317,12 +299,10 @@ transition_i8_vec(const TransitionI8Args A) {
   const bool two_rows = Q.fh == 2, two_cols = Q.fw == 2;
   const int32_t zi = A.D.zi;
   for (uint64_t blk = wave0; blk < nblocks; blk += nwaves) {       // 64 chunks = 1 KB of output per wave and iteration
-    const uint64_t g = blk * 64ull + (uint64_t)lane;               // this lane's chunk
-    const bool ok = g < P.total;
-    const uint32_t x = c0 + (uint32_t)lane;                        // < per_pixel + 64 < 2^31
-    const uint32_t q = fast_div(x, P.div_per_pixel);
-    const uint32_t c = x - q * cpp;                                // < per_pixel, also for a lane past the end
-    const PoolWindow w = pool_window(P, pix0 + q, ok);             // on the pooled map; a lane past the end has no pooled row
+    uint64_t g;                                                    // this lane's chunk
+    bool ok;
+    uint32_t c;
+    const PoolWindow w = pool_chunk_at(P, pix0, c0, blk, lane, g, ok, c);   // on the pooled map; a lane past the end has no pooled row
     const TransitionFootprint fp = transition_footprint(P, Q, w);
     const u32x4* flt = (const u32x4*)A.D.filter + c;
     int32_t acc[16];
@@ -390,14 +370,8 @@ transition_i8_vec(const TransitionI8Args A) {
       o[d] = pack4_u8(rr[0], rr[1], rr[2], rr[3]);
     }
     if (P.out && ok) pool_store_through((u32x4*)P.out + g, o);
-    if constexpr (BITS) {                                          // per_pixel % 2 == 0: lanes 2p and 2p + 1 agree on ok
-      uint32_t word = ok ? m << (16 * (lane & 1)) : 0u;
-      word |= pool_neighbour(word);
-      if (ok && (lane & 1) == 0) P.bits[g >> 1] = word;
-    }
-    pix0 += P.step_pixels;
-    c0 += P.step_chunks;
-    if (c0 >= cpp) { c0 -= cpp; ++pix0; }
+    if constexpr (BITS) store_half_word<true>(P.bits, g, lane, ok, m);   // per_pixel % 2 == 0: lanes 2p and 2p + 1 agree on ok
+    pool_chunk_step(P, pix0, c0);
   }
 }
 

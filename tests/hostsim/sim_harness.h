@@ -3,7 +3,7 @@
 // for the CPU against the host replacement of the device intrinsics (lce_device_intrinsics.h: build/ comes first on the include
 // path).  Here:
 //   - the prelude: __HIPCC__, the empty __host__ / __device__ / __forceinline__, and the quad permute v_mov_b32
-//     quad_perm:[1,0,3,2] behind pool_neighbour / add_i8_neighbour, emulated as the exchange with lane ^ 1 it is;
+//     quad_perm:[1,0,3,2] behind lane_neighbour (lce_kernels_common.h), emulated as the exchange with lane ^ 1 it is;
 //   - with SIM_HARNESS_POOL defined: lce_kernels_pool.h, its 16-byte write-through store (inline assembly) replaced by a plain
 //     store;
 //   - sim::launch, which runs a kernel body over a grid, the lanes of a block as fibers in lock step.

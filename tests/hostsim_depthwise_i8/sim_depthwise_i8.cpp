@@ -3,7 +3,7 @@
 // (tests/hostsim/lce_device_intrinsics.h), so the chunk and segment enumeration, the clipped window with its unclipped filter index,
 // the channel mapping, the epilogue, the two-lane word and the ballots are exercised without a GPU.  Two device-only pieces of
 // lce_kernels_pool.h are replaced (tests/hostsim/sim_harness.h): the 16-byte write-through store (inline assembly) is a plain store, and the quad permute
-// v_mov_b32 quad_perm:[1,0,3,2] behind pool_neighbour is emulated as the exchange with lane ^ 1 it is.
+// v_mov_b32 quad_perm:[1,0,3,2] behind lane_neighbour is emulated as the exchange with lane ^ 1 it is.
 #define SIM_HARNESS_POOL
 #include "sim_harness.h"
 #define __shared__ static               // (lce_kernels_conv2d_i8.h comes along for conv2d_i8_requantize; its kernel is not run here)

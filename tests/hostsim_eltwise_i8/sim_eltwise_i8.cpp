@@ -2,7 +2,7 @@
 // csrc/lce_kernels_eltwise_i8_chain.h run on the CPU, the lanes of a block as fibers in lock step
 // (tests/hostsim/lce_device_intrinsics.h), so the copy of the table into LDS with its row order, the chunk's place in its row kept
 // by modular steps, the grid stride, the partial last iteration, the two-lane word and the row path's ballots are exercised without
-// a GPU.  One device-only piece is replaced: the quad permute v_mov_b32 quad_perm:[1,0,3,2] behind add_i8_neighbour is emulated as
+// a GPU.  One device-only piece is replaced: the quad permute v_mov_b32 quad_perm:[1,0,3,2] behind lane_neighbour is emulated as
 // the exchange with lane ^ 1 it is.
 #include "sim_harness.h"
 #include "lce_kernels_eltwise_i8_chain.h"

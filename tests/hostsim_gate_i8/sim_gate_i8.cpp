@@ -2,7 +2,7 @@
 // csrc/lce_kernels_mul_i8.h run on the CPU, the lanes of a block as fibers in lock step (tests/hostsim/lce_device_intrinsics.h), so
 // every lane's row and image, the gate's 16-byte load, the grid stride, the partial last iteration, the two-lane word, the half-word
 // stores of an odd chunk count and the row path's ballots are exercised without a GPU.  One device-only piece is replaced: the quad
-// permute v_mov_b32 quad_perm:[1,0,3,2] behind add_i8_neighbour is emulated as the exchange with lane ^ 1 it is.
+// permute v_mov_b32 quad_perm:[1,0,3,2] behind lane_neighbour is emulated as the exchange with lane ^ 1 it is.
 #include <cstddef>
 
 #include "sim_harness.h"

@@ -3,7 +3,7 @@
 // fibers in lock step (tests/hostsim/lce_device_intrinsics.h), so the chunk and segment enumeration, the footprint streamed row by
 // row, the clipped pool windows, the skipped depthwise taps, the epilogues, the words of bits and the ballots are exercised without
 // a GPU.  Two device-only pieces of lce_kernels_pool.h are replaced (tests/hostsim/sim_harness.h): the 16-byte
-// write-through store (inline assembly) is a plain store, and the quad permute behind pool_neighbour is the exchange with lane ^ 1.
+// write-through store (inline assembly) is a plain store, and the quad permute behind lane_neighbour is the exchange with lane ^ 1.
 #define SIM_HARNESS_POOL
 #include "sim_harness.h"
 #define __shared__                      // (lce_kernels_conv2d_i8.h and depthwise_vec's staged form come along; neither is instantiated here)
