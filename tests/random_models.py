@@ -2,7 +2,7 @@
 tests/test_random_models_host.py and tests/test_gpu_random_models.py.  No tests here.
 
 `build(seed)` grows a DAG of typed tensors -- kinds f32, i8 (scale, zero point) and bits -- one operator at a time, each a
-transition the kind allows (the table in `_Gen.grow`), evaluates every operator on the seed's own input as it goes (the NumPy
+transition the kind allows (the table in `_Gen.step`), evaluates every operator on the seed's own input as it goes (the NumPy
 restatements of tests/*_ref.py and the oracle), and calibrates each operator's constants on those values so that int8 tensors
 spread over their range and bit tensors stay mixed.  The operators are then written in a random topological order.  A seed is a
 case; a failing case is named by its seed.
@@ -559,85 +559,90 @@ class _Gen:
         ts += [ts[int(g.integers(0, len(ts)))] for _ in range(n - len(ts))]
         return self.concat([ts[k] for k in g.permutation(len(ts))])
 
+    def step(self):
+        """One round of the growth: a tensor, and one transition its kind allows (the table)."""
+        g = self.g
+        fresh = [t for t in self.tensors if not t.readers and not t.output and not t.rank2]
+        live = [t for t in self.tensors if not t.rank2]
+        t = fresh[int(g.integers(0, len(fresh)))] if fresh and g.random() < 0.85 else live[int(g.integers(0, len(live)))]
+        r, out = g.random(), None
+        floats = [u for u in fresh if u.kind == "f32" and u.c != 3]
+        if "e" in self.want and floats and self.left() >= 9:
+            self.want.discard("e")
+            out = self.chain(floats[0], long=True)
+        elif "f" in self.want and floats and self.left() >= 3:
+            self.want.discard("f")
+            out = self.late_operand(floats[0])
+        elif "i" in self.want and self.left() >= 3 and any(u.kind == "i8" and u.c != 3 and u.balanced() for u in fresh):
+            self.want.discard("i")
+            out = self.residual([u for u in fresh if u.kind == "i8" and u.c != 3 and u.balanced()][0])
+        elif "w" in self.want and self.left() >= 2 and any(u.kind != "bits" and 3 < u.c <= 96 for u in fresh):
+            self.want.discard("w")
+            out = self.wide_join([u for u in fresh if u.kind != "bits" and 3 < u.c <= 96][0])
+        elif t.kind == "bits":
+            if r < 0.25 and self.left() >= 3:
+                out = self.branches(t)
+            elif r < 0.30:
+                out = self.lcedq(t)
+            elif r < 0.34 and t.c % 32 == 0:
+                out = self.join(t)
+            elif r < 0.5 and self.left() >= 2 and min(t.h, t.w) >= 4:
+                y = self.bconv(t, O.DST_BITPACKED, ones=0.73)
+                out = self.bmaxpool(y) if min(y.h, y.w) >= 2 else None
+            else:
+                out = self.bconv(t, int(g.choice([O.DST_F32, O.DST_F32, O.DST_I8, O.DST_I8, O.DST_BITPACKED])))
+                if out.kind != "bits" and out.balanced() and g.random() < 0.25 and self.left() >= 2:
+                    self.lceq(out), self.lceq(out)
+        elif t.c == 3:                                             # three channels: a stem's convolution only
+            out = (self.conv2d(t) if g.random() < 0.7 else self.depthwise(t)) if t.kind == "f32" else \
+                (self.conv_i8(t) if g.random() < 0.7 else self.depthwise_i8(t))
+        elif t.kind == "f32":
+            heavy = t.c * 6 <= 240
+            if t.c > 192 and 0.58 <= r:                            # a wide join's result: no float convolution over it, no join
+                r = 0.85 if r < 0.8 else 0.55
+            if r < 0.22 and t.balanced():
+                out = self.lceq(t)
+            elif r < 0.30:
+                out = self.quantize(t)
+            elif r < 0.52:
+                out = self.chain(t)
+            elif r < 0.58:
+                out = self.pool(t)
+            elif r < 0.70:
+                out = self.conv1x1(t)
+            elif r < 0.80 and heavy:
+                out = self.conv2d(t)
+            elif r < 0.88:
+                out = self.depthwise(t)
+            else:
+                out = self.join(t)
+        else:
+            if r < 0.2 and t.balanced():
+                out = self.lceq(t)
+            elif r < 0.28:
+                out = self.dequantize(t)
+            elif r < 0.46:
+                out = self.residual(t)
+            elif r < 0.52:
+                peers = [u for u in self.tensors if u.kind == "i8" and not u.rank2 and u is not t and (u.h, u.w, u.c) == (t.h, t.w, t.c)]
+                out = self.int8_add(t, peers[int(g.integers(0, len(peers)))]) if peers else self.pool(t)
+            elif r < 0.58:
+                out = self.pool(t)
+            elif r < 0.72:
+                out = self.conv_i8(t)
+            elif r < 0.9:
+                out = self.depthwise_i8(t)
+            elif t.c <= 192:
+                out = self.join(t)
+            else:
+                out = self.pool(t)
+        if out is not None and out.producer is not None and out.kind != "bits" and self.nodes[out.producer].name in P.FOLDING and g.random() < 0.6:
+            self.fold_variants(out)
+
     def grow(self):
         g = self.g
         while self.left() >= 1:
-            fresh = [t for t in self.tensors if not t.readers and not t.output and not t.rank2]
-            live = [t for t in self.tensors if not t.rank2]
-            t = fresh[int(g.integers(0, len(fresh)))] if fresh and g.random() < 0.85 else live[int(g.integers(0, len(live)))]
-            r, out = g.random(), None
-            floats = [u for u in fresh if u.kind == "f32" and u.c != 3]
-            if "e" in self.want and floats and self.left() >= 9:
-                self.want.discard("e")
-                out = self.chain(floats[0], long=True)
-            elif "f" in self.want and floats and self.left() >= 3:
-                self.want.discard("f")
-                out = self.late_operand(floats[0])
-            elif "i" in self.want and self.left() >= 3 and any(u.kind == "i8" and u.c != 3 and u.balanced() for u in fresh):
-                self.want.discard("i")
-                out = self.residual([u for u in fresh if u.kind == "i8" and u.c != 3 and u.balanced()][0])
-            elif "w" in self.want and self.left() >= 2 and any(u.kind != "bits" and 3 < u.c <= 96 for u in fresh):
-                self.want.discard("w")
-                out = self.wide_join([u for u in fresh if u.kind != "bits" and 3 < u.c <= 96][0])
-            elif t.kind == "bits":
-                if r < 0.25 and self.left() >= 3:
-                    out = self.branches(t)
-                elif r < 0.30:
-                    out = self.lcedq(t)
-                elif r < 0.34 and t.c % 32 == 0:
-                    out = self.join(t)
-                elif r < 0.5 and self.left() >= 2 and min(t.h, t.w) >= 4:
-                    y = self.bconv(t, O.DST_BITPACKED, ones=0.73)
-                    out = self.bmaxpool(y) if min(y.h, y.w) >= 2 else None
-                else:
-                    out = self.bconv(t, int(g.choice([O.DST_F32, O.DST_F32, O.DST_I8, O.DST_I8, O.DST_BITPACKED])))
-                    if out.kind != "bits" and out.balanced() and g.random() < 0.25 and self.left() >= 2:
-                        self.lceq(out), self.lceq(out)
-            elif t.c == 3:                                             # three channels: a stem's convolution only
-                out = (self.conv2d(t) if g.random() < 0.7 else self.depthwise(t)) if t.kind == "f32" else \
-                    (self.conv_i8(t) if g.random() < 0.7 else self.depthwise_i8(t))
-            elif t.kind == "f32":
-                heavy = t.c * 6 <= 240
-                if t.c > 192 and 0.58 <= r:                            # a wide join's result: no float convolution over it, no join
-                    r = 0.85 if r < 0.8 else 0.55
-                if r < 0.22 and t.balanced():
-                    out = self.lceq(t)
-                elif r < 0.30:
-                    out = self.quantize(t)
-                elif r < 0.52:
-                    out = self.chain(t)
-                elif r < 0.58:
-                    out = self.pool(t)
-                elif r < 0.70:
-                    out = self.conv1x1(t)
-                elif r < 0.80 and heavy:
-                    out = self.conv2d(t)
-                elif r < 0.88:
-                    out = self.depthwise(t)
-                else:
-                    out = self.join(t)
-            else:
-                if r < 0.2 and t.balanced():
-                    out = self.lceq(t)
-                elif r < 0.28:
-                    out = self.dequantize(t)
-                elif r < 0.46:
-                    out = self.residual(t)
-                elif r < 0.52:
-                    peers = [u for u in self.tensors if u.kind == "i8" and not u.rank2 and u is not t and (u.h, u.w, u.c) == (t.h, t.w, t.c)]
-                    out = self.int8_add(t, peers[int(g.integers(0, len(peers)))]) if peers else self.pool(t)
-                elif r < 0.58:
-                    out = self.pool(t)
-                elif r < 0.72:
-                    out = self.conv_i8(t)
-                elif r < 0.9:
-                    out = self.depthwise_i8(t)
-                elif t.c <= 192:
-                    out = self.join(t)
-                else:
-                    out = self.pool(t)
-            if out is not None and out.producer is not None and out.kind != "bits" and self.nodes[out.producer].name in P.FOLDING and g.random() < 0.6:
-                self.fold_variants(out)
+            self.step()
         if self.head:
             ends = [t for t in self.tensors if t.kind != "bits" and not t.rank2 and t.c != 3 and not t.readers] or \
                    [t for t in self.tensors if t.kind != "bits" and not t.rank2 and t.c != 3]
